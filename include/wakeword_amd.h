@@ -57,6 +57,11 @@ extern "C" {
 #define WW_HIDDEN 256
 #define WW_N_CLASSES 2
 #define WW_MAX_WIDTH 32 /* widest mel image (frames) the conv kernels take: T in [1, 32] */
+/* Any clip length from 0.25 s to 2 s (AudioConfig.DURATION in [0.25, 2.0], inference only): N = int(16000 * DURATION) samples,
+ * T = 1 + N / 512 frames.  The *_frames_* / *_wide_* entry points below take these; the 1 s entry points keep their limits. */
+#define WW_MIN_CLIP_SAMPLES 4000
+#define WW_MAX_CLIP_SAMPLES 32000
+#define WW_MAX_FRAMES 63 /* 1 + 32000 / 512 */
 
 typedef void* ww_stream_t;
 
@@ -155,6 +160,10 @@ WW_API int ww_resampler_prepare(int32_t sample_rate, ww_clip_desc* desc_host);
 /* raw_dev: the files' sample bytes; descs_dev: [n_clips] descriptors in device memory; pcm_out_dev [n_clips][16000]. */
 WW_API int ww_decode_resample(const uint8_t* raw_dev, const ww_clip_desc* descs_dev, int64_t n_clips, int normalize,
                               float* pcm_out_dev, ww_stream_t stream);
+/* The same with rows of n_samples (16000, or WW_MIN_CLIP_SAMPLES..WW_MAX_CLIP_SAMPLES: clips of 0.25 .. 2 s): pcm_out_dev [n_clips][n_samples];
+ * crop_start is then the first output sample of the n_samples window (pad_or_truncate against n_samples). */
+WW_API int ww_decode_resample_n(const uint8_t* raw_dev, const ww_clip_desc* descs_dev, int64_t n_clips, int normalize, int64_t n_samples,
+                                float* pcm_out_dev, ww_stream_t stream);
 
 /* ---- file-fed batches: the host half of load_audio for many files at once ------------------------------------- */
 /* Replaces, for a batch of paths, the file access of AudioProcessor.load_audio = librosa.load(path, sr=16000)
@@ -194,6 +203,8 @@ WW_API int ww_wav_probe_host(const char* path, ww_clip_desc* desc_host);
 WW_API int ww_read_wav_batch_host(ww_wav_reader* r, const char* const* paths, int64_t n, int32_t slot, ww_clip_desc** descs_host_out,
                                   int8_t* status_host, int64_t* raw_bytes_out);
 WW_API int ww_wav_batch_decode(ww_wav_reader* r, int32_t slot, int normalize, float* pcm_out_dev, ww_stream_t stream);
+/* ww_wav_batch_decode with rows of n_samples (as ww_decode_resample_n): pcm_out_dev [n][n_samples]. */
+WW_API int ww_wav_batch_decode_n(ww_wav_reader* r, int32_t slot, int normalize, int64_t n_samples, float* pcm_out_dev, ww_stream_t stream);
 
 /* ---- KA: training-time augmentation ------------------------------ */
 /* Replaces AudioProcessor.augment_audio (wakeword_training_script.py:103-123): np.roll time shift ->
@@ -243,6 +254,14 @@ WW_API int ww_kaiser_best_host(float* out_host);
 WW_API int ww_logmel_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len,
                   int normalize, float* logmel_dev, ww_stream_t stream);
 
+/* The same for any clip length (no ABI version bump: additions only):
+ *   pcm_dev      rows of clip_len valid samples as above, 0 < clip_len <= n_samples; rows are right-zero-padded to n_samples
+ *   n_samples    N in [WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES]; T = 1 + N / 512 frames
+ *   logmel_dev   [n_clips][80][T], dB in [-80, 0], per-clip max (over all T frames) exactly 0
+ * Same arithmetic modes (ww_set_logmel_math); N with T = 32 (16,000 samples among them) runs the 1 s kernel, bit for bit. */
+WW_API int ww_logmel_frames_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples,
+                                int normalize, float* logmel_dev, ww_stream_t stream);
+
 /* ---- weights ------------------------------------------------------------------------------ */
 /* The reference state_dict (train_wakeword.py:28-36 / wakeword_training_script.py:141-165) as
  * host pointers in torch layout.  conv3_* are NULL for SimpleWakewordModel.  weight_hh_l* are not
@@ -276,6 +295,17 @@ WW_API int64_t ww_cnn_scratch_bytes(int64_t n, int32_t n_conv);
 WW_API int ww_cnn_pool_f32(const float* mel_dev, int64_t n, int32_t width, const float* packed_dev,
                     int32_t n_conv, void* scratch_dev, float* pooled_dev, ww_stream_t stream);
 
+/* K2 for mel images up to WW_MAX_FRAMES wide: mel_dev [n][80][width], 1 <= width <= 63, n <= 2^24.  Widths <= 32 run ww_cnn_pool_f32 (bit
+ * for bit; scratch as there).  Wider images are covered by 32-column tiles that overlap by 2 h columns (h = 2 for n_conv 2, 3 for n_conv 3:
+ * the reach of the conv stack); each tile runs the 32-wide kernels and pools only the columns it owns, with scale 1 / (80 width), and a
+ * second kernel sums a clip's tiles in a fixed order (results do not depend on the batch).  Arithmetic: ww_set_conv_math (WW_CONV_MATH_F32
+ * or WW_CONV_MATH_F16X3, whose range exponents are then chosen per tile); WW_CONV_MATH_F16X3_DIRECT has no tiled form: widths > 32 return
+ * WW_EUNSUPPORTED under it.
+ * scratch_dev: ww_cnn_wide_scratch_bytes(n, width, n_conv) bytes, 256-byte aligned (may be NULL only where ww_cnn_pool_f32 allows it). */
+WW_API int64_t ww_cnn_wide_scratch_bytes(int64_t n, int32_t width, int32_t n_conv);
+WW_API int ww_cnn_pool_wide_f32(const float* mel_dev, int64_t n, int32_t width, const float* packed_dev, int32_t n_conv,
+                                void* scratch_dev, float* pooled_dev, ww_stream_t stream);
+
 /* ---- K3: 2-layer LSTM (one step, zero state) + Linear ---------------------------------------- */
 /* Replaces `lstm_out, _ = self.lstm(x.unsqueeze(1)); x = lstm_out[:, -1, :]; x = self.fc(x)`
  * (train_wakeword.py:42-48 / wakeword_training_script.py:175-182), dropout = identity (eval).
@@ -294,6 +324,13 @@ WW_API int ww_model_forward_f32(const float* mel_dev, int64_t n, int32_t width, 
 WW_API int ww_forward_pcm_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len,
                        int normalize, const float* packed_dev, int32_t n_conv, void* workspace_dev,
                        float* logits_dev, ww_stream_t stream);
+
+/* PCM -> logits for any clip length: ww_logmel_frames_f32 -> ww_cnn_pool_wide_f32 -> ww_lstm_fc_f32 (arguments as there);
+ * workspace_dev: ww_workspace_frames_bytes(n_clips, n_samples, n_conv) bytes, 256-byte aligned. */
+WW_API int64_t ww_workspace_frames_bytes(int64_t n, int64_t n_samples, int32_t n_conv);
+WW_API int ww_forward_pcm_frames_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples,
+                                     int normalize, const float* packed_dev, int32_t n_conv, void* workspace_dev, float* logits_dev,
+                                     ww_stream_t stream);
 
 /* ---- training step ----------------------------------------------------- */
 /* Replaces, for one batch, `output = model(data)` in train mode and `loss.backward()` of the reference's training loops

@@ -105,6 +105,8 @@ PROTOTYPES = {
     "ww_read_wav_batch_host": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int64, C.c_int32, C.POINTER(C.POINTER(ClipDesc)), C.c_void_p,
                                          C.POINTER(C.c_int64)]),
     "ww_wav_batch_decode": (C.c_int, [C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p]),
+    "ww_wav_batch_decode_n": (C.c_int, [C.c_void_p, C.c_int32, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ww_decode_resample_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "ww_augment_workspace_bytes": (C.c_int64, [C.c_int64]),
     "ww_augment_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(AugmentPlan), C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_augment_record_bytes": (C.c_int64, []),
@@ -120,6 +122,12 @@ PROTOTYPES = {
     "ww_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
     "ww_model_forward_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_forward_pcm_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_logmel_frames_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "ww_cnn_wide_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "ww_cnn_pool_wide_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_workspace_frames_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    "ww_forward_pcm_frames_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
     "ww_train_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "ww_train_forward_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(TrainParams), C.c_float, C.c_float, C.c_uint64, C.c_int32,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

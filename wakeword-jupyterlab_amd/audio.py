@@ -4,10 +4,13 @@ Same method names, arguments and return conventions:
   load_audio(path)            -> float32 ndarray at 16 kHz mono, or None (prints the error; never raises)
   normalize_audio(audio)      -> audio / max|audio|            (empty-array guard only, as the reference)
   pad_or_truncate(audio, n)   -> random crop (python `random`) or right zero-pad
-  audio_to_mel(audio)         -> ndarray [80, 32] log-mel dB     <- HIP kernel K1
-  process_audio_file(path)    -> ndarray [80, 32] or None
+  audio_to_mel(audio)         -> ndarray [80, T] log-mel dB     <- HIP kernel K1
+  process_audio_file(path)    -> ndarray [80, T] or None
 
-plus the batched form the GPU wants: `mel_batch(pcm[B, n]) -> torch.Tensor [B, 1, 80, 32]` on the device.
+plus the batched form the GPU wants: `mel_batch(pcm[B, n]) -> torch.Tensor [B, 1, 80, T]` on the device.
+T = 32 for the default 1 s config; a config with DURATION in [0.25, 2.0] gives T = 1 + int(16000 * DURATION) // 512 for audio_to_mel and
+mel_batch, and for process_audio_file / load_clips_gpu (K0 crops and pads to N samples): inference.  Augmentation stays 1 s only and
+refuses other durations.
 
   augment_audio(audio)        -> time shift / pitch shift / time stretch / noise, each with probability 0.8
                                  (random draws from python `random` in the reference's order)  <- HIP kernels KA
@@ -23,13 +26,14 @@ import numpy as np
 import torch
 
 from . import ops
-from .config import AudioConfig, AugmentationConfig, check_audio_config
+from .config import AudioConfig, AugmentationConfig, check_audio_config, is_one_second, n_samples
 
 
 class AudioProcessor:
     def __init__(self, config=AudioConfig, device=None):
         check_audio_config(config)
         self.config = config
+        self._n = n_samples(config)                      # N: 16000 at 1 s; 4000 .. 32000 over DURATION 0.25 .. 2 (inference)
         self.device = torch.device(device) if device is not None else None
 
     def _dev(self):
@@ -93,12 +97,22 @@ class AudioProcessor:
         return np.pad(audio, (0, target_length - len(audio)), mode="constant")
 
     def audio_to_mel(self, audio):
-        """[n <= 16000] samples -> ndarray [80, 32] (dB).  No normalisation here (reference :85-101)."""
+        """[n <= N] samples -> ndarray [80, T] (dB; [80, 32] at 1 s).  No normalisation here (reference :85-101)."""
         n_frames = int(self.config.SAMPLE_RATE * self.config.DURATION / self.config.HOP_LENGTH) + 1
         if len(audio) == 0:
             return np.zeros((self.config.N_MELS, n_frames))
         pcm = torch.as_tensor(np.ascontiguousarray(audio, dtype=np.float32)).unsqueeze(0).to(self._dev())
-        return ops.logmel(pcm, False)[0, 0].cpu().numpy()
+        return self._logmel(pcm, False)[0, 0].cpu().numpy()
+
+    def _logmel(self, pcm, normalize):
+        if is_one_second(self.config):
+            return ops.logmel(pcm, normalize)
+        return ops.logmel_frames(pcm, self._n, normalize)
+
+    def _one_second_only(self, what):
+        if not is_one_second(self.config):
+            raise NotImplementedError(f"{what} at DURATION {self.config.DURATION}: not supported yet (training and augmentation run "
+                                      "1 s clips only; other durations are inference only, augment=False)")
 
     def draw_augment_plan(self, config=AugmentationConfig, length=None):
         """The random draws of augment_audio (:103-123) in the reference's order -> one plan dict.
@@ -122,6 +136,7 @@ class AudioProcessor:
 
     def augment_batch(self, pcm, plans=None, config=AugmentationConfig) -> torch.Tensor:
         """pcm [B, 16000] (ndarray or tensor) -> augmented device tensor [B, 16000]; one plan per clip (drawn here if None)."""
+        self._one_second_only("augmentation")
         t = torch.as_tensor(pcm, dtype=torch.float32)
         if t.device.type != "cuda":
             t = t.to(self._dev(), non_blocking=True)
@@ -131,6 +146,7 @@ class AudioProcessor:
 
     def augment_audio(self, audio, config=AugmentationConfig):
         """[16000] samples -> augmented float32 ndarray [16000] (reference :103-123), on the GPU."""
+        self._one_second_only("augmentation")
         a = np.ascontiguousarray(audio, dtype=np.float32)
         if a.shape != (int(self.config.SAMPLE_RATE * self.config.DURATION),):
             raise ValueError(f"augment_audio takes exactly one padded clip of 16000 samples, got {a.shape}")
@@ -139,6 +155,8 @@ class AudioProcessor:
     def process_audio_file(self, file_path, augment=False):
         """load -> normalise over the whole file -> random crop / zero pad -> (augment) -> log-mel (:125-138), all on the GPU:
         native reader -> K0 -> (KA) -> K1.  The random draws are python `random`'s in the reference's order (crop, then augmentation)."""
+        if augment:
+            self._one_second_only("augmentation")
         pcm, ok = self.load_clips_gpu([file_path])
         if not bool(ok[0]):
             return None
@@ -148,18 +166,18 @@ class AudioProcessor:
 
     # ---- batched form ---------------------------------------------------------------------------
     def mel_batch(self, pcm, normalize: bool = True) -> torch.Tensor:
-        """pcm [B, n<=16000] (ndarray or tensor, any device) -> device tensor [B, 1, 80, 32].
+        """pcm [B, n<=N] (ndarray or tensor, any device) -> device tensor [B, 1, 80, T] (N = 16000, T = 32 at 1 s).
         normalize=True folds normalize_audio + zero-pad + audio_to_mel, the order process_audio_file uses."""
         t = torch.as_tensor(pcm, dtype=torch.float32)
         if t.device.type != "cuda":
             t = t.to(self._dev(), non_blocking=True)
-        return ops.logmel(t, normalize)
+        return self._logmel(t, normalize)
 
     def load_clips_gpu(self, paths, normalize: bool = True, lo: int = 0, hi=None):
         """Host: the library's reader threads open the files, walk their RIFF headers and read the sample bytes into pinned
         staging (files.WavBatchReader -> ww_read_wav_batch_host).  GPU (kernel K0): sample conversion, mono mix, polyphase
-        resample to 16 kHz, whole-file peak normalisation, random crop / zero pad to 1 s -- process_audio_file :125-133
-        up to the mel call.  `paths`: a list, or a files.EncodedPaths with a window [lo, hi).  Returns (device tensor [B, 16000],
+        resample to 16 kHz, whole-file peak normalisation, random crop / zero pad to N samples (the config's DURATION) --
+        process_audio_file :125-133 up to the mel call.  `paths`: a list, or a files.EncodedPaths with a window [lo, hi).  Returns (device tensor [B, N],
         ok mask); unreadable files give a zero row, ok False."""
         from .files import EncodedPaths
         hi = len(paths) if hi is None else hi
@@ -172,7 +190,8 @@ class AudioProcessor:
         from .files import WavBatchReader
         dev = self._dev()
         if getattr(self, "_reader", None) is None or self._reader.device != dev:
-            self._reader = WavBatchReader(max_clips=max(64, batch_size), max_raw_bytes=max(64, batch_size) * 65536, slots=3, device=dev)
+            self._reader = WavBatchReader(max_clips=max(64, batch_size), max_raw_bytes=max(64, batch_size) * 65536, slots=3, device=dev,
+                                          n_samples=self._n)
         elif self._reader.max_clips < batch_size:
             self._reader.regrow(batch_size, batch_size * 65536)
         return self._reader

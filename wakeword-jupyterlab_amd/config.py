@@ -47,9 +47,29 @@ CLIP_SAMPLES = int(AudioConfig.SAMPLE_RATE * AudioConfig.DURATION)          # 16
 N_FRAMES = 1 + CLIP_SAMPLES // AudioConfig.HOP_LENGTH                       # 32
 
 
+MIN_DURATION, MAX_DURATION = 0.25, 2.0          # inference at other clip lengths: 4,000 .. 32,000 samples, 8 .. 63 frames
+
+
 def check_audio_config(cfg) -> None:
-    """The kernels are built for exactly the reference constants; refuse anything else loudly."""
+    """The kernels are built for the reference constants, at DURATION 1.0 for everything and at any DURATION in [0.25, 2.0] for inference
+    (training, augmentation and streaming stay 1 s only); refuse anything else loudly."""
     want = {k: getattr(AudioConfig, k) for k in ("SAMPLE_RATE", "N_MELS", "N_FFT", "HOP_LENGTH", "WIN_LENGTH", "FMIN", "FMAX")}
     got = {k: getattr(cfg, k, None) for k in want}
-    if float(getattr(cfg, "DURATION", 1.0)) != 1.0 or any(float(got[k]) != float(want[k]) for k in want):
-        raise NotImplementedError(f"the HIP front-end is built for {want} at DURATION 1.0; got {got}")
+    dur = float(getattr(cfg, "DURATION", 1.0))
+    if not MIN_DURATION <= dur <= MAX_DURATION or any(float(got[k]) != float(want[k]) for k in want):
+        raise NotImplementedError(f"the HIP front-end is built for {want} at DURATION {MIN_DURATION}..{MAX_DURATION} s; got {got}, "
+                                  f"DURATION {dur}")
+
+
+def n_samples(cfg) -> int:
+    """N = int(SAMPLE_RATE * DURATION): the clip length pad_or_truncate produces (16000 at 1 s)."""
+    return int(cfg.SAMPLE_RATE * cfg.DURATION)
+
+
+def n_frames(cfg) -> int:
+    """T = 1 + N // HOP_LENGTH: the mel frames of one clip (librosa center=True; 32 at 1 s, 8 .. 63 over 0.25 .. 2 s)."""
+    return 1 + n_samples(cfg) // cfg.HOP_LENGTH
+
+
+def is_one_second(cfg) -> bool:
+    return n_samples(cfg) == CLIP_SAMPLES

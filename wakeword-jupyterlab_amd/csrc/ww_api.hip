@@ -349,6 +349,85 @@ int ww_forward_pcm_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_strid
     return launch_lstm_fc(w.pooled, n_clips, packed_dev, n_conv, logits_dev, nullptr, st);
 }
 
+// ---- any clip length in [0.25 s, 2 s] (the 1 s entry points above are unchanged) ----
+static int check_samples(int64_t clip_len, int64_t n_samples) {
+    if (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_MAX_CLIP_SAMPLES)
+        return fail(WW_EINVAL, "n_samples %lld: expected %d..%d (0.25 s .. 2 s at 16 kHz)", (long long)n_samples, WW_MIN_CLIP_SAMPLES,
+                    WW_MAX_CLIP_SAMPLES);
+    if (clip_len > n_samples) return fail(WW_EINVAL, "clip_len %lld > n_samples %lld", (long long)clip_len, (long long)n_samples);
+    return WW_OK;
+}
+static int check_wide(int64_t n, int32_t width, const float* packed, int32_t n_conv) {
+    if (width < 1 || width > WW_MAX_FRAMES) return fail(WW_EINVAL, "mel width %d: the wide conv stack takes 1..%d frames", width, WW_MAX_FRAMES);
+    if (n > (int64_t(1) << 24)) return fail(WW_EINVAL, "batch %lld out of range", (long long)n);
+    return check_model(n, width <= WW_MAX_WIDTH ? width : 1, packed, n_conv);
+}
+static int64_t wide_scratch_bytes(int64_t n, int32_t width, int32_t n_conv) {
+    return width <= WW_MAX_WIDTH ? cnn_scratch_bytes(n, n_conv) : cnn_wide_scratch_bytes(n, width, n_conv);
+}
+static int cnn_pool_any(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch, float* pooled,
+                        hipStream_t st) {
+    if (width <= WW_MAX_WIDTH) return launch_cnn_pool(mel, n, width, packed, n_conv, scratch, pooled, st);
+    return launch_cnn_pool_wide(mel, n, width, packed, n_conv, scratch, pooled, st);
+}
+
+int ww_logmel_frames_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples, int normalize,
+                         float* logmel_dev, ww_stream_t stream) {
+    if (int rc = check_samples(clip_len, n_samples)) return rc;
+    if (n_clips < 0 || n_clips > (int64_t(1) << 30)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (n_clips == 0) return WW_OK;
+    if (!pcm_dev || !logmel_dev) return fail(WW_EINVAL, "null pcm / output pointer");
+    if (clip_len <= 0) return fail(WW_EINVAL, "clip_len %lld: expected >= 1", (long long)clip_len);
+    if (clip_stride < clip_len && n_clips > 1) return fail(WW_EINVAL, "clip_stride %lld < clip_len %lld", (long long)clip_stride, (long long)clip_len);
+    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 15) || (n_clips > 1 && (clip_stride & 3)))
+        return fail(WW_EINVAL, "pcm must be 16-byte aligned with clip_stride %% 4 == 0");
+    if (int rc = require_gfx950()) return rc;
+    return launch_logmel_frames(pcm_dev, n_clips, clip_stride, clip_len, n_samples, normalize, logmel_dev, static_cast<hipStream_t>(stream));
+}
+
+int64_t ww_cnn_wide_scratch_bytes(int64_t n, int32_t width, int32_t n_conv) {
+    if (n < 0 || width < 1 || width > WW_MAX_FRAMES || (n_conv != 2 && n_conv != 3)) return fail(WW_EINVAL, "bad wide scratch query");
+    return wide_scratch_bytes(n, width, n_conv);
+}
+
+int ww_cnn_pool_wide_f32(const float* mel_dev, int64_t n, int32_t width, const float* packed_dev, int32_t n_conv, void* scratch_dev,
+                         float* pooled_dev, ww_stream_t stream) {
+    if (int rc = check_wide(n, width, packed_dev, n_conv)) return rc;
+    if (n == 0) return WW_OK;
+    if (!mel_dev || !pooled_dev) return fail(WW_EINVAL, "null tensor pointer");
+    if (width > WW_MAX_WIDTH && (!scratch_dev || (reinterpret_cast<uintptr_t>(scratch_dev) & 255)))
+        return fail(WW_EINVAL, "widths > %d need ww_cnn_wide_scratch_bytes() of 256-byte aligned scratch", WW_MAX_WIDTH);
+    if (int rc = require_gfx950()) return rc;
+    return cnn_pool_any(mel_dev, n, width, packed_dev, n_conv, scratch_dev, pooled_dev, static_cast<hipStream_t>(stream));
+}
+
+int64_t ww_workspace_frames_bytes(int64_t n, int64_t n_samples, int32_t n_conv) {
+    if (n < 0 || (n_conv != 2 && n_conv != 3) || n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_MAX_CLIP_SAMPLES)
+        return fail(WW_EINVAL, "bad workspace query");
+    const int T = int(1 + n_samples / kHop);
+    return align256(n * kMels * T * int64_t(sizeof(float))) + align256(n * 128 * int64_t(sizeof(float))) +
+           align256(wide_scratch_bytes(n, T, n_conv));
+}
+
+int ww_forward_pcm_frames_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples, int normalize,
+                              const float* packed_dev, int32_t n_conv, void* workspace_dev, float* logits_dev, ww_stream_t stream) {
+    if (int rc = check_samples(clip_len, n_samples)) return rc;
+    const int T = int(1 + n_samples / kHop);
+    if (int rc = check_wide(n_clips, T, packed_dev, n_conv)) return rc;
+    if (n_clips == 0) return WW_OK;
+    if (!logits_dev || !workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
+        return fail(WW_EINVAL, "null logits pointer, or workspace not a 256-byte aligned pointer");
+    char* p = static_cast<char*>(workspace_dev);
+    float* logmel = reinterpret_cast<float*>(p);
+    p += align256(n_clips * kMels * T * int64_t(sizeof(float)));
+    float* pooled = reinterpret_cast<float*>(p);
+    p += align256(n_clips * 128 * int64_t(sizeof(float)));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = ww_logmel_frames_f32(pcm_dev, n_clips, clip_stride, clip_len, n_samples, normalize, logmel, stream)) return rc;
+    if (int rc = cnn_pool_any(logmel, n_clips, T, packed_dev, n_conv, p, pooled, st)) return rc;
+    return launch_lstm_fc(pooled, n_clips, packed_dev, n_conv, logits_dev, nullptr, st);
+}
+
 static int check_train(const float* mel, int64_t n, int32_t width, const ww_train_params* p, const void* ws) {
     if (n < 1 || n > (int64_t(1) << 24)) return fail(WW_EINVAL, "training batch %lld out of range", (long long)n);
     if (width < 1 || width > WW_MAX_WIDTH) return fail(WW_EUNSUPPORTED, "mel width %d: the conv kernels take 1..%d frames", width, WW_MAX_WIDTH);

@@ -43,6 +43,27 @@ constexpr int kActFloats = 32 * kARows * kRS;          // 10,880
 constexpr int kMelFloats = (kH + 2) * kMelRS;          // 2,952
 constexpr int kC2LdsFloats = kActFloats + kMelFloats + 4 * 32;
 
+// Column tiling of a clip wider than kW frames (ww_cnn_pool_wide_f32).  The clip's T columns are covered by K tiles of kW columns: tile k
+// starts at k * step, the last one at T - kW (flush with the clip's right edge); step = kW - 2 h, h = the reach of the conv stack in columns
+// (2: conv1 + conv2, 3: + conv3).  A tile runs through the kernels as a "virtual clip" v = clip * K + k of width kW.  Its activations are
+// exact on every column at least h columns from a tile edge that is not the clip's own edge, and it pools only the columns it OWNS,
+// [k step + h, (k + 1) step + h) clipped to [0, T) -- a partition of the clip's columns --, with the clip's scale 1 / (80 T): the K partial
+// pools of a clip are in true units and are summed by pool_tiles_kernel.  K = 1 + ceil((T - kW) / step) puts the last tile's first owned
+// column at least h columns from its left edge.  TILED = false instances ignore the argument.
+struct ColTiling { int T, K, step, h; };
+__device__ __forceinline__ int tile_start(const ColTiling& g, int k) { return k == g.K - 1 ? g.T - kW : k * g.step; }
+// owned columns [lo, hi) of virtual clip v, in tile coordinates
+__device__ __forceinline__ void tile_owned(const ColTiling& g, int64_t v, int& lo, int& hi) {
+    const int k = int(v % g.K), s = tile_start(g, k);
+    lo = k == 0 ? 0 : k * g.step + g.h - s;
+    hi = k == g.K - 1 ? kW : (k + 1) * g.step + g.h - s;
+}
+// first element of virtual clip v's tile in the [n][80][T] input (rows T floats apart)
+__device__ __forceinline__ const float* tile_src(const float* mel, const ColTiling& g, int64_t v) {
+    const int64_t clip = v / g.K;
+    return mel + clip * int64_t(kH) * g.T + tile_start(g, int(v - clip * g.K));
+}
+
 // ReLU that propagates NaN like torch's (F.relu(nan) = nan); fmaxf(nan, 0) would return 0
 __device__ __forceinline__ float relu(float v) { return v < 0.f ? 0.f : v; }
 
@@ -114,11 +135,11 @@ __device__ __forceinline__ void mfma_rows4(const float* __restrict__ ap, const f
 // POOL : out = pooled [n][64]
 // !POOL: out = relu(conv2) as [n][80][64][32] (row, channel, column) for the conv3 kernel
 // ------------------------------------------------------------------------------------------------
-template <bool POOL>
+template <bool POOL, bool TILED = false>
 __global__ __launch_bounds__(256, 2) void cnn2_kernel(const float* __restrict__ mel, int n, int width,
                                                       const float* __restrict__ w1, const float* __restrict__ b1,
                                                       const float* __restrict__ wB, const float* __restrict__ b2,
-                                                      float* __restrict__ out) {
+                                                      float* __restrict__ out, ColTiling tl) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* act = lds;                       // [32][10][34]
     float* melt = act + kActFloats;         // [82][36]
@@ -136,14 +157,24 @@ __global__ __launch_bounds__(256, 2) void cnn2_kernel(const float* __restrict__ 
 
     zero_lds(lds, kC2LdsFloats, tid, 256);   // halos stay zero for the life of the workgroup
     const float* ap = act + (h * kARows + rg * 4) * kRS + x;
-    const float inv_area = 1.0f / float(kH * width);
+    const float inv_area = 1.0f / float(kH * (TILED ? tl.T : width));
 
     for (int clip = blockIdx.x; clip < n; clip += gridDim.x) {
         __syncthreads();   // previous clip fully consumed (and the zero fill on the first trip)
-        const float* __restrict__ src = mel + int64_t(clip) * kH * width;
-        for (int i = tid; i < kH * width; i += 256) {
-            const int y = i / width, xx = i - y * width;
-            melt[(y + 1) * kMelRS + xx + 1] = src[i];
+        int plo = 0, phi = width;   // pooled columns
+        if constexpr (TILED) {
+            const float* __restrict__ src = tile_src(mel, tl, clip);
+            for (int i = tid; i < kH * kW; i += 256) {
+                const int y = i >> 5, xx = i & 31;
+                melt[(y + 1) * kMelRS + xx + 1] = src[int64_t(y) * tl.T + xx];
+            }
+            tile_owned(tl, clip, plo, phi);
+        } else {
+            const float* __restrict__ src = mel + int64_t(clip) * kH * width;
+            for (int i = tid; i < kH * width; i += 256) {
+                const int y = i / width, xx = i - y * width;
+                melt[(y + 1) * kMelRS + xx + 1] = src[i];
+            }
         }
         float pool = 0.f;
         for (int band = 0; band < kH / kBand; ++band) {
@@ -167,7 +198,7 @@ __global__ __launch_bounds__(256, 2) void cnn2_kernel(const float* __restrict__ 
                     for (int j = 0; j < 16; ++j) {
                         const int col = (j & 3) + 8 * (j >> 2) + 4 * h;
                         const float v = relu(acc[r][j] + bias);
-                        vs[j] = (col < width) ? v : 0.f;
+                        vs[j] = (TILED ? col >= plo && col < phi : col < width) ? v : 0.f;
                     }
                     rows[r] = tree16(vs);
                 }
@@ -763,14 +794,15 @@ static_assert(kWTileRows % 4 == 0, "four producers with equal shares");
 // bits[n][40 tile rows][4 N-tiles][2 column halves][2 rows][4 j] x 64 bits (ww_train_h.hip: mask2_byte), and bits1[n][80][32] = 32 bits per position, bit c = [relu(conv1)[c] > 0]
 // (2 x uint16, one per producer half-wave): all the backward pass needs of the activations (ww_train_h.hip).
 // OUT 3 (training forward of the 3-conv model): relu(conv2) and apow2 as under OUT 0, plus bits1.
-template <int OUT>
+template <int OUT, bool TILED = false>
 __global__ __launch_bounds__(768, 3) void cnn2w_kernel(const float* __restrict__ mel, int n, int width,
                                                        const u32x4* __restrict__ w1H, const float* __restrict__ hs1,
                                                        const float* __restrict__ b1,
                                                        const u32x4* __restrict__ wH, const float* __restrict__ hs,
                                                        const float* __restrict__ b2, const float* __restrict__ rng,
                                                        float* __restrict__ out, float* __restrict__ apow2, uint16_t* __restrict__ bits,
-                                                       uint16_t* __restrict__ bits1) {
+                                                       uint16_t* __restrict__ bits1, ColTiling tl) {
+    static_assert(!TILED || OUT <= 1, "column tiling is an inference form");
 #ifdef WW_ABL_NOBITS            // timing-only ablations of the training forward: 1 = no conv2 mask image, 2 = no conv1 sign image either
     constexpr bool POOL = OUT == 1 || OUT == 2, BITS = false, BITS1 = WW_ABL_NOBITS < 2 && (OUT == 2 || OUT == 3);
 #else
@@ -815,16 +847,18 @@ __global__ __launch_bounds__(768, 3) void cnn2w_kernel(const float* __restrict__
         // model input of clip k -> two f16 planes of x * 2^-e (see cnn2h16_kernel).  All four producers meet inside (the xmax
         // counter), which also tells each of them that nobody still reads the planes being overwritten.
         auto load_mel = [&](int k, int& e_out, int& a_out) {
-            const float* __restrict__ src = mel + (int64_t(blockIdx.x) + int64_t(k) * gridDim.x) * kH * width;
+            const int64_t vclip = int64_t(blockIdx.x) + int64_t(k) * gridDim.x;
+            const float* __restrict__ src = TILED ? tile_src(mel, tl, vclip) : mel + vclip * kH * width;
+            const int rstride = TILED ? tl.T : width;                // floats between image rows
             _Float16* ph = melh0 + (k & 1) * 2 * kMelHPlane;
             const int xx = ptid & 31, y0 = ptid >> 5;
             const bool col_live = xx < width;
-            const float* __restrict__ sp = src + y0 * width + xx;
+            const float* __restrict__ sp = src + y0 * rstride + xx;
             float v[10];
             float mx = 0.f;
 #pragma unroll
             for (int t = 0; t < 10; ++t) {
-                v[t] = col_live ? sp[8 * t * width] : 0.f;
+                v[t] = col_live ? sp[8 * t * rstride] : 0.f;
                 mx = fmaxf(mx, __builtin_fabsf(v[t]));
             }
 #pragma unroll
@@ -949,6 +983,7 @@ __global__ __launch_bounds__(768, 3) void cnn2w_kernel(const float* __restrict__
         const float bias = b2[16 * nt + pi];
         const float descale = 0.5f * hs[16 * nt + pi];
         float dsc = descale, pool = 0.f;
+        int plo = 0, phi = kW;                                  // TILED: the pooled (owned) columns of the current virtual clip
 #ifdef WW_WINO_CPRIO
         __builtin_amdgcn_s_setprio(WW_WINO_CPRIO);
 #endif
@@ -963,6 +998,7 @@ __global__ __launch_bounds__(768, 3) void cnn2w_kernel(const float* __restrict__
             if (sq == 0) {
                 dsc = descale * clip_par[k & 1][0];
                 pool = 0.f;
+                if constexpr (TILED) tile_owned(tl, int64_t(blockIdx.x) + int64_t(k) * gridDim.x, plo, phi);
                 if constexpr (!POOL) {
                     if (wave == 0 && lane == 0) {     // |V3| <= 2 max relu(conv2): one more bit of headroom than a plain split needs
                         const float bound2 = fmaf(clip_par[k & 1][1], rng[2], rng[3]);
@@ -1028,7 +1064,8 @@ __global__ __launch_bounds__(768, 3) void cnn2w_kernel(const float* __restrict__
                     const float y0 = acc[0][c][j] + m12, y1 = m1m2 - acc[3][c][j];
                     const float v0 = relu2(fmaf(y0, dsc, bias)), v1 = relu2(fmaf(y1, dsc, bias));
 #endif
-                    const bool col_live = width == kW || 16 * c + 4 * kq + j < width;
+                    const bool col_live = TILED ? (POOL ? 16 * c + 4 * kq + j >= plo && 16 * c + 4 * kq + j < phi : true)
+                                                : width == kW || 16 * c + 4 * kq + j < width;
                     if constexpr (POOL) {
                         pv[4 * c + j] = col_live ? v0 + v1 : 0.f;
                     } else {
@@ -1092,7 +1129,7 @@ __global__ __launch_bounds__(768, 3) void cnn2w_kernel(const float* __restrict__
                     // once per clip: the lane index and the scale are RECOMPUTED here (mbcnt; a scalar divide) instead of being kept in
                     // VGPRs across the MFMA loop, where at the 168-register cap they were spilled to scratch
                     const int ln = int(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
-                    const float scale = 0.5f / float(kH * __builtin_amdgcn_readfirstlane(width));
+                    const float scale = 0.5f / float(kH * __builtin_amdgcn_readfirstlane(TILED ? tl.T : width));
                     out[clip * 64 + ln] = (rk[ln] + rk[64 + ln]) * scale;
                 }
             }
@@ -1497,10 +1534,12 @@ constexpr int kC3wLds = 2 * kW3Buf;
 
 // BITS (training forward): also the ReLU mask of conv3, [relu(conv3) > 0], as the accumulator ballots themselves:
 // bits3[n][40 tile rows][8 N-tiles][2 column halves][2 rows][4 j] x 64 bits (ww_train_h.hip: mask3_byte).
-template <bool BITS>
+template <bool BITS, bool TILED = false>
 __global__ __launch_bounds__(512, 2) void cnn3w_kernel(const float* __restrict__ mid, const float* __restrict__ apow2, int n, int width,
                                                        const u32x4* __restrict__ wH, const float* __restrict__ hs,
-                                                       const float* __restrict__ b3, float* __restrict__ out, uint16_t* __restrict__ bits3) {
+                                                       const float* __restrict__ b3, float* __restrict__ out, uint16_t* __restrict__ bits3,
+                                                       ColTiling tl) {
+    static_assert(!(TILED && BITS), "column tiling is an inference form");
     extern __shared__ __attribute__((aligned(16))) char ldsb[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int nt = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1519,7 +1558,7 @@ __global__ __launch_bounds__(512, 2) void cnn3w_kernel(const float* __restrict__
 
     const int my_clips = (n - int(blockIdx.x) + int(gridDim.x) - 1) / int(gridDim.x);
     const int steps = my_clips * kWTileRows;
-    const float inv_area = 1.0f / float(kH * width);
+    const float inv_area = 1.0f / float(kH * (TILED ? tl.T : width));
     const int lx = tid >> 4, lcg = tid & 15;                 // loader role: column, group of 4 channels
 
     float4 pre[4];
@@ -1560,12 +1599,14 @@ __global__ __launch_bounds__(512, 2) void cnn3w_kernel(const float* __restrict__
     if (steps > 0) { fetch(0); stash(0); }
     __syncthreads();
     float pool = 0.f, pool4 = 0.f, dsc = descale;     // pool4: partial over four tile rows (pooling order: see tree4 above)
+    int plo = 0, phi = kW;                            // TILED: the pooled (owned) columns of the current virtual clip
     for (int g = 0; g < steps; ++g) {
         const int k = g / kWTileRows, t = g - k * kWTileRows;
         if (t == 0) {
             dsc = descale * apow2[int64_t(blockIdx.x) + int64_t(k) * gridDim.x];    // the tile holds V * 2^-a2
             pool = 0.f;
             pool4 = 0.f;
+            if constexpr (TILED) tile_owned(tl, int64_t(blockIdx.x) + int64_t(k) * gridDim.x, plo, phi);
         }
         if (g + 1 < steps) fetch(g + 1);
         const char* ap = ldsb + (g & 1) * kW3Buf + pi * kW3Rec + kq * 16;
@@ -1602,7 +1643,8 @@ __global__ __launch_bounds__(512, 2) void cnn3w_kernel(const float* __restrict__
                 const float m12 = acc[1][j] + acc[2][j], m1m2 = acc[1][j] - acc[2][j];
                 const float y0 = acc[0][j] + m12, y1 = m1m2 - acc[3][j];
                 const float v0 = relu2(fmaf(y0, dsc, bias)), v1 = relu2(fmaf(y1, dsc, bias));
-                const bool col_live = width == kW || 16 * c + 4 * kq + j < width;
+                const bool col_live = TILED ? 16 * c + 4 * kq + j >= plo && 16 * c + 4 * kq + j < phi
+                                            : width == kW || 16 * c + 4 * kq + j < width;
                 pv[j] = col_live ? v0 + v1 : 0.f;
                 if constexpr (BITS) {           // bit (16 kq + pi) of the ballot <-> channel 16 nt + pi at column 16 c + 4 kq + j
                     unsigned long long cm = 0ull;   // the column mask as scalar arithmetic (see cnn2w_kernel<2>)
@@ -1668,10 +1710,11 @@ constexpr int kC3XchFloats = 4 * 4 * 16 * 64;        // [nt][r][j][lane] 16,384
 constexpr int kC3LdsFloats = kC3ActFloats + kC3XchFloats;
 
 // STORE (training forward): relu(conv3) is also kept, as [n][80][128][32] (row, channel, column; zero beyond `width`).
-template <bool STORE>
+template <bool STORE, bool TILED = false>
 __global__ __launch_bounds__(512, 2) void cnn3_kernel(const float* __restrict__ in, int n, int width,
                                                       const float* __restrict__ wB, const float* __restrict__ b3,
-                                                      float* __restrict__ out, float* __restrict__ mid3) {
+                                                      float* __restrict__ out, float* __restrict__ mid3, ColTiling tl) {
+    static_assert(!(TILED && STORE), "column tiling is an inference form");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* act = lds;                        // [64][6][34]
     float* xch = act + kC3ActFloats;         // [4][4][16][64]
@@ -1688,10 +1731,12 @@ __global__ __launch_bounds__(512, 2) void cnn3_kernel(const float* __restrict__ 
 
     zero_lds(lds, kC3ActFloats, tid, 512);
     const float* ap = act + ((32 * kh + h) * kC3Rows) * kRS + x;
-    const float inv_area = 1.0f / float(kH * width);
+    const float inv_area = 1.0f / float(kH * (TILED ? tl.T : width));
 
     for (int clip = blockIdx.x; clip < n; clip += gridDim.x) {
         float pool = 0.f;
+        int plo = 0, phi = width;   // pooled columns
+        if constexpr (TILED) tile_owned(tl, clip, plo, phi);
         for (int band = 0; band < kH / 4; ++band) {
             const int y0 = band * 4;
             __syncthreads();   // previous band's reads of act / xch retired
@@ -1729,7 +1774,7 @@ __global__ __launch_bounds__(512, 2) void cnn3_kernel(const float* __restrict__ 
                     for (int j = 0; j < 16; ++j) {
                         const int col = (j & 3) + 8 * (j >> 2) + 4 * h;
                         const float v = relu(acc[r][j] + xch[((nt * 4 + r) * 16 + j) * 64 + lane] + bias);
-                        vs[j] = (col < width) ? v : 0.f;
+                        vs[j] = (TILED ? col >= plo && col < phi : col < width) ? v : 0.f;
                     }
                     rows[r] = tree16(vs);
                     if constexpr (STORE) {
@@ -1908,6 +1953,11 @@ static int opt_in_lds() {
                                int(sizeof(float) * kC3LdsFloats)));
     WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                int(sizeof(float) * kC3LdsFloats)));
+    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn2w_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kCWLds));
+    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn2w_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kCWLds));
+    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn3w_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kC3wLds));
+    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn3_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               int(sizeof(float) * kC3LdsFloats)));
     done[dev] = true;
     return WW_OK;
 }
@@ -1923,7 +1973,7 @@ int launch_cnn2w_pool_bits(const float* mel, int64_t n, int width, const float* 
     hipLaunchKernelGGL(cnn2w_kernel<2>, dim3(int(n < cus ? n : cus)), dim3(768), kCWLds, stream, mel, int(n), width,
                        reinterpret_cast<const u32x4*>(packed + L.conv1_h), packed + L.conv1_hs, packed + L.conv1_b,
                        reinterpret_cast<const u32x4*>(packed + L.conv2_hw), packed + L.conv2_hws, packed + L.conv2_b, packed + L.range, pooled,
-                       static_cast<float*>(nullptr), reinterpret_cast<uint16_t*>(bits), reinterpret_cast<uint16_t*>(bits1));
+                       static_cast<float*>(nullptr), reinterpret_cast<uint16_t*>(bits), reinterpret_cast<uint16_t*>(bits1), ColTiling{});
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
@@ -1940,11 +1990,11 @@ int launch_cnn3w_pool_bits(const float* mel, int64_t n, int width, const float* 
     hipLaunchKernelGGL(cnn2w_kernel<3>, dim3(grid1), dim3(768), kCWLds, stream, mel, int(n), width,
                        reinterpret_cast<const u32x4*>(packed + L.conv1_h), packed + L.conv1_hs, packed + L.conv1_b,
                        reinterpret_cast<const u32x4*>(packed + L.conv2_hw), packed + L.conv2_hws, packed + L.conv2_b, packed + L.range, mid2,
-                       apow2, static_cast<uint16_t*>(nullptr), reinterpret_cast<uint16_t*>(bits1));
+                       apow2, static_cast<uint16_t*>(nullptr), reinterpret_cast<uint16_t*>(bits1), ColTiling{});
     WW_HIP(hipGetLastError());
     hipLaunchKernelGGL(cnn3w_kernel<true>, dim3(grid1), dim3(512), kC3wLds, stream, static_cast<const float*>(mid2),
                        static_cast<const float*>(apow2), int(n), width, reinterpret_cast<const u32x4*>(packed + L.conv3_hw),
-                       packed + L.conv3_hws, packed + L.conv3_b, pooled, reinterpret_cast<uint16_t*>(bits3));
+                       packed + L.conv3_hws, packed + L.conv3_b, pooled, reinterpret_cast<uint16_t*>(bits3), ColTiling{});
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
@@ -1955,7 +2005,7 @@ int launch_cnn2_f32_mid(const float* mel, int64_t n, int width, const float* w1,
     if (n == 0) return WW_OK;
     const int64_t cus = device_cu_count();
     const int grid2 = int(n < 2 * cus ? n : 2 * cus);
-    hipLaunchKernelGGL(cnn2_kernel<false>, dim3(grid2), dim3(256), sizeof(float) * kC2LdsFloats, stream, mel, int(n), width, w1, b1, wB, b2, mid);
+    hipLaunchKernelGGL(cnn2_kernel<false>, dim3(grid2), dim3(256), sizeof(float) * kC2LdsFloats, stream, mel, int(n), width, w1, b1, wB, b2, mid, ColTiling{});
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
@@ -1967,7 +2017,7 @@ int launch_cnn3_f32_store(const float* mid2, int64_t n, int width, const float* 
     if (int rc = opt_in_lds()) return rc;
     const int64_t cus = device_cu_count();
     hipLaunchKernelGGL(cnn3_kernel<true>, dim3(int(n < cus ? n : cus)), dim3(512), sizeof(float) * kC3LdsFloats, stream, mid2, int(n), width, wB, b3,
-                       pooled, mid3);
+                       pooled, mid3, ColTiling{});
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
@@ -2022,7 +2072,7 @@ int launch_cnn_pool(const float* mel, int64_t n, int width, const float* packed,
                 hipLaunchKernelGGL(cnn2w_kernel<true>, dim3(grid1), dim3(768), kCWLds, stream, mel, int(n), width, w1h,
                                    packed + L.conv1_hs, packed + L.conv1_b, w2w, packed + L.conv2_hws, packed + L.conv2_b,
                                    packed + L.range, pooled, static_cast<float*>(nullptr), static_cast<uint16_t*>(nullptr),
-                                   static_cast<uint16_t*>(nullptr));
+                                   static_cast<uint16_t*>(nullptr), ColTiling{});
                 WW_HIP(hipGetLastError());
                 return WW_OK;
             }
@@ -2035,11 +2085,11 @@ int launch_cnn_pool(const float* mel, int64_t n, int width, const float* packed,
                 const int g = int(cnt < cus ? cnt : cus);
                 hipLaunchKernelGGL(cnn2w_kernel<false>, dim3(g), dim3(768), kCWLds, stream, mel + s0 * 80 * width, int(cnt), width, w1h,
                                    packed + L.conv1_hs, packed + L.conv1_b, w2w, packed + L.conv2_hws, packed + L.conv2_b,
-                                   packed + L.range, static_cast<float*>(scratch), apw, static_cast<uint16_t*>(nullptr), static_cast<uint16_t*>(nullptr));
+                                   packed + L.range, static_cast<float*>(scratch), apw, static_cast<uint16_t*>(nullptr), static_cast<uint16_t*>(nullptr), ColTiling{});
                 WW_HIP(hipGetLastError());
                 hipLaunchKernelGGL(cnn3w_kernel<false>, dim3(g), dim3(512), kC3wLds, stream, static_cast<const float*>(scratch),
                                    static_cast<const float*>(apw), int(cnt), width, reinterpret_cast<const u32x4*>(packed + L.conv3_hw),
-                                   packed + L.conv3_hws, packed + L.conv3_b, pooled + s0 * 128, static_cast<uint16_t*>(nullptr));
+                                   packed + L.conv3_hws, packed + L.conv3_b, pooled + s0 * 128, static_cast<uint16_t*>(nullptr), ColTiling{});
                 WW_HIP(hipGetLastError());
             }
             return WW_OK;
@@ -2067,16 +2117,107 @@ int launch_cnn_pool(const float* mel, int64_t n, int width, const float* packed,
     const size_t lds2 = sizeof(float) * kC2LdsFloats;
     if (n_conv == 2) {
         hipLaunchKernelGGL(cnn2_kernel<true>, dim3(grid2), dim3(256), lds2, stream, mel, int(n), width,
-                           packed + L.conv1_w, packed + L.conv1_b, packed + L.conv2_w, packed + L.conv2_b, pooled);
+                           packed + L.conv1_w, packed + L.conv1_b, packed + L.conv2_w, packed + L.conv2_b, pooled, ColTiling{});
         WW_HIP(hipGetLastError());
         return WW_OK;
     }
     float* mid = static_cast<float*>(scratch);
     hipLaunchKernelGGL(cnn2_kernel<false>, dim3(grid2), dim3(256), lds2, stream, mel, int(n), width,
-                       packed + L.conv1_w, packed + L.conv1_b, packed + L.conv2_w, packed + L.conv2_b, mid);
+                       packed + L.conv1_w, packed + L.conv1_b, packed + L.conv2_w, packed + L.conv2_b, mid, ColTiling{});
     WW_HIP(hipGetLastError());
     hipLaunchKernelGGL(cnn3_kernel<false>, dim3(grid1), dim3(512), sizeof(float) * kC3LdsFloats, stream, mid, int(n), width,
-                       packed + L.conv3_w, packed + L.conv3_b, pooled, static_cast<float*>(nullptr));
+                       packed + L.conv3_w, packed + L.conv3_b, pooled, static_cast<float*>(nullptr), ColTiling{});
+    WW_HIP(hipGetLastError());
+    return WW_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// K2 for clips of 33..63 columns (ww_cnn_pool_wide_f32): the clip is cut into column tiles (ColTiling above), every tile runs through
+// the kernels above as a virtual clip of width kW, each pooling the columns it owns; pool_tiles_kernel sums a clip's partial pools.
+// ------------------------------------------------------------------------------------------------
+static ColTiling col_tiling(int width, int n_conv) {
+    const int h = n_conv == 3 ? 3 : 2, step = kW - 2 * h;
+    return ColTiling{width, 1 + (width - kW + step - 1) / step, step, h};
+}
+int cnn_wide_tiles(int width, int n_conv) { return col_tiling(width, n_conv).K; }
+
+static int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
+int64_t cnn_wide_scratch_bytes(int64_t n, int width, int n_conv) {
+    const int64_t nv = n * col_tiling(width, n_conv).K;
+    return align256(nv * (n_conv == 3 ? 128 : 64) * int64_t(sizeof(float))) + cnn_scratch_bytes(nv, n_conv);
+}
+
+// pooled[clip][c] = partial[clip K][c] + partial[clip K + 1][c] + ... in tile order: no atomics, the same bits for any batch or grid
+__global__ __launch_bounds__(256) void pool_tiles_kernel(const float* __restrict__ partial, int64_t n_out, int K, int C,
+                                                         float* __restrict__ pooled) {
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n_out) return;
+    const int64_t clip = i / C;
+    const float* p = partial + clip * K * C + (i - clip * C);
+    float s = p[0];
+    for (int k = 1; k < K; ++k) s += p[int64_t(k) * C];
+    pooled[i] = s;
+}
+
+int launch_cnn_pool_wide(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch, float* pooled,
+                         hipStream_t stream) {
+    if (n == 0) return WW_OK;
+    if (!scratch) return fail(WW_EINVAL, "the wide conv stack needs ww_cnn_wide_scratch_bytes() of scratch");
+    const ColTiling tl = col_tiling(width, n_conv);
+    const int64_t nv64 = n * tl.K;
+    if (nv64 > (int64_t(1) << 30)) return fail(WW_EINVAL, "batch too large for the column-tiled conv stack: %lld tiles", (long long)nv64);
+    const int nv = int(nv64);
+    const int C = n_conv == 3 ? 128 : 64;
+    const PackedLayout L = packed_layout(n_conv);
+    if (int rc = opt_in_lds()) return rc;
+    float* partial = static_cast<float*>(scratch);
+    char* rest = static_cast<char*>(scratch) + align256(nv64 * C * int64_t(sizeof(float)));
+    const int cus = device_cu_count();
+    const int grid1 = nv < cus ? nv : cus;
+    const int cmath = conv_math_mode();
+    if (cmath == WW_CONV_MATH_F16X3_DIRECT)   // one model, one arithmetic: no silent switch to the Winograd form for wide images
+        return fail(WW_EUNSUPPORTED, "WW_CONV_MATH_F16X3_DIRECT has no column-tiled form (widths > 32): use WW_CONV_MATH_F16X3 or WW_CONV_MATH_F32");
+    if (cmath != 0) {        // f16x3: the Winograd kernels
+        const u32x4* w1h = reinterpret_cast<const u32x4*>(packed + L.conv1_h);
+        const u32x4* w2w = reinterpret_cast<const u32x4*>(packed + L.conv2_hw);
+        if (n_conv == 2) {
+            hipLaunchKernelGGL((cnn2w_kernel<1, true>), dim3(grid1), dim3(768), kCWLds, stream, mel, nv, kW, w1h, packed + L.conv1_hs,
+                               packed + L.conv1_b, w2w, packed + L.conv2_hws, packed + L.conv2_b, packed + L.range, partial,
+                               static_cast<float*>(nullptr), static_cast<uint16_t*>(nullptr), static_cast<uint16_t*>(nullptr), tl);
+            WW_HIP(hipGetLastError());
+        } else {
+            float* mid = reinterpret_cast<float*>(rest);
+            float* apw = reinterpret_cast<float*>(rest + mid_bytes(nv64));
+            hipLaunchKernelGGL((cnn2w_kernel<0, true>), dim3(grid1), dim3(768), kCWLds, stream, mel, nv, kW, w1h, packed + L.conv1_hs,
+                               packed + L.conv1_b, w2w, packed + L.conv2_hws, packed + L.conv2_b, packed + L.range, mid, apw,
+                               static_cast<uint16_t*>(nullptr), static_cast<uint16_t*>(nullptr), tl);
+            WW_HIP(hipGetLastError());
+            hipLaunchKernelGGL((cnn3w_kernel<false, true>), dim3(grid1), dim3(512), kC3wLds, stream, static_cast<const float*>(mid),
+                               static_cast<const float*>(apw), nv, kW, reinterpret_cast<const u32x4*>(packed + L.conv3_hw),
+                               packed + L.conv3_hws, packed + L.conv3_b, partial, static_cast<uint16_t*>(nullptr), tl);
+            WW_HIP(hipGetLastError());
+        }
+    } else {                 // exact f32
+        const int grid2 = int(nv64 < 2 * int64_t(cus) ? nv64 : 2 * int64_t(cus));
+        const size_t lds2 = sizeof(float) * kC2LdsFloats;
+        if (n_conv == 2) {
+            hipLaunchKernelGGL((cnn2_kernel<true, true>), dim3(grid2), dim3(256), lds2, stream, mel, nv, kW, packed + L.conv1_w,
+                               packed + L.conv1_b, packed + L.conv2_w, packed + L.conv2_b, partial, tl);
+            WW_HIP(hipGetLastError());
+        } else {
+            float* mid = reinterpret_cast<float*>(rest);
+            hipLaunchKernelGGL((cnn2_kernel<false, true>), dim3(grid2), dim3(256), lds2, stream, mel, nv, kW, packed + L.conv1_w,
+                               packed + L.conv1_b, packed + L.conv2_w, packed + L.conv2_b, mid, tl);
+            WW_HIP(hipGetLastError());
+            hipLaunchKernelGGL((cnn3_kernel<false, true>), dim3(grid1), dim3(512), sizeof(float) * kC3LdsFloats, stream,
+                               static_cast<const float*>(mid), nv, kW, packed + L.conv3_w, packed + L.conv3_b, partial,
+                               static_cast<float*>(nullptr), tl);
+            WW_HIP(hipGetLastError());
+        }
+    }
+    const int64_t n_out = n * C;
+    hipLaunchKernelGGL(pool_tiles_kernel, dim3(unsigned((n_out + 255) / 256)), dim3(256), 0, stream, static_cast<const float*>(partial),
+                       n_out, tl.K, C, pooled);
     WW_HIP(hipGetLastError());
     return WW_OK;
 }

@@ -124,11 +124,12 @@ __device__ __forceinline__ bool resample_in_lds(int up, int down, int half_len) 
     return !(up == 1 && down == 1) && lh <= kRsTaps && lh / up + 8 < kRsSpan / 2;
 }
 
+// row_len: samples per output row -- 16,000 (1 s) for ww_decode_resample, N for ww_decode_resample_n (0.25 .. 2 s clips).
 // One workgroup per file.  Output blocks of up to 2048 samples: the block's input span is decoded (sample format, channel mean) into LDS
 // once -- the direct form decodes every input frame once per tap that touches it, ~20 times at 48 kHz --, the filter sits in LDS beside it,
 // and each output is the same fused multiply-add chain in the same order as decode_resample_kernel's (bit-identical results).
 __global__ __launch_bounds__(kRsThreads) void resample_lds_kernel(const uint8_t* __restrict__ raw, const ww_clip_desc* __restrict__ descs,
-                                                                  int n_clips, int normalize, float* __restrict__ out) {
+                                                                  int n_clips, int normalize, float* __restrict__ out, int row_len) {
     extern __shared__ __attribute__((aligned(16))) float rs_lds[];
     float* tapsL = rs_lds;
     float* xs = rs_lds + kRsTaps;
@@ -152,9 +153,9 @@ __global__ __launch_bounds__(kRsThreads) void resample_lds_kernel(const uint8_t*
         n_out = n_out / down + (n_out % down ? 1 : 0);
         const int n_pre_pad = down - half_len % down;
         const int n_pre_remove = (half_len + n_pre_pad) / down;
-        float* __restrict__ o = out + int64_t(clip) * kClip;
+        float* __restrict__ o = out + int64_t(clip) * row_len;
         float peak = 0.f;
-        const int64_t total = n_out > d.crop_start + kClip ? n_out : d.crop_start + kClip;   // also writes the zero pad
+        const int64_t total = n_out > d.crop_start + row_len ? n_out : d.crop_start + row_len;   // also writes the zero pad
         int64_t blk64 = int64_t(kRsSpan - lh / up - 8) * up / down;
         const int blk = int(blk64 > 2048 ? 2048 : (blk64 < 1 ? 1 : blk64));
         auto first_in = [&](int64_t c) -> int64_t { return c - lh + 1 <= 0 ? 0 : (c - lh + 1 + up - 1) / up; };
@@ -165,7 +166,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_lds_kernel(const uint8_t*
         // without normalisation nothing outside the 1 s window is needed (no whole-file peak): load_audio's windows then cost one window each,
         // not one file each (round-3 review: a long recording was resampled once per second of its length); per output the same fma chain
         const int64_t j_begin = normalize ? 0 : d.crop_start;
-        const int64_t j_end = normalize || total < d.crop_start + kClip ? total : d.crop_start + kClip;
+        const int64_t j_end = normalize || total < d.crop_start + row_len ? total : d.crop_start + row_len;
         for (int64_t j0 = j_begin; j0 < j_end; j0 += blk) {
             const int64_t j1 = (j0 + blk < n_out ? j0 + blk : n_out) - 1;       // last filtered output of the block (j1 < j0: none)
             const int64_t i_min = first_in((j0 + n_pre_remove) * int64_t(down) - n_pre_pad);
@@ -194,7 +195,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_lds_kernel(const uint8_t*
                     peak = fmaxf(peak, fabsf(y));
                 }
                 const int64_t w = j - d.crop_start;
-                if (w >= 0 && w < kClip) o[w] = y;
+                if (w >= 0 && w < row_len) o[w] = y;
             }
         }
 #pragma unroll
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_lds_kernel(const uint8_t*
 #pragma unroll
         for (int w = 1; w < kRsThreads / 64; ++w) peak = fmaxf(peak, red[w]);
         if (normalize) {
-            const int64_t valid = n_out - d.crop_start < kClip ? n_out - d.crop_start : kClip;
+            const int64_t valid = n_out - d.crop_start < row_len ? n_out - d.crop_start : row_len;
             for (int w = tid; w < valid; w += kRsThreads) o[w] = o[w] / peak;
         }
     }
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_lds_kernel(const uint8_t*
 
 __global__ __launch_bounds__(256) void decode_resample_kernel(const uint8_t* __restrict__ raw,
                                                              const ww_clip_desc* __restrict__ descs, int n_clips,
-                                                             int normalize, float* __restrict__ out) {
+                                                             int normalize, float* __restrict__ out, int row_len) {
     __shared__ float red[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int clip = blockIdx.x; clip < n_clips; clip += gridDim.x) {
@@ -231,13 +232,13 @@ __global__ __launch_bounds__(256) void decode_resample_kernel(const uint8_t* __r
         const int n_pre_pad = (up == 1 && down == 1) ? 0 : down - half_len % down;
         const int n_pre_remove = (up == 1 && down == 1) ? 0 : (half_len + n_pre_pad) / down;
         const int lh = 2 * half_len + 1;
-        float* __restrict__ o = out + int64_t(clip) * kClip;
+        float* __restrict__ o = out + int64_t(clip) * row_len;
         float peak = 0.f;
 #ifndef WW_ABL_K0_NOFAST
         // the data set's usual file -- 16 kHz, mono, PCM-16, at most one second (create_sample_data's format) -- in one pass: eight samples
         // per 16-byte load, the clip held in registers between the peak reduction and the scaled store (the general loop below stores,
         // reduces, then reads and rewrites).  Same conversion, same division: bit-identical.
-        if (up == 1 && down == 1 && d.channels == 1 && d.format == WW_FMT_S16 && n_in <= kClip && d.crop_start == 0 &&
+        if (row_len == kClip && up == 1 && down == 1 && d.channels == 1 && d.format == WW_FMT_S16 && n_in <= kClip && d.crop_start == 0 &&
             (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
             constexpr int kV = (kClip / 8 + 255) / 256;                  // 8 vectors of 8 samples per thread cover 16,384 >= 16,000
             float v[kV][8];
@@ -277,9 +278,9 @@ __global__ __launch_bounds__(256) void decode_resample_kernel(const uint8_t* __r
             continue;
         }
 #endif
-        const int64_t total = n_out > d.crop_start + kClip ? n_out : d.crop_start + kClip;   // also writes the zero pad
+        const int64_t total = n_out > d.crop_start + row_len ? n_out : d.crop_start + row_len;   // also writes the zero pad
         const int64_t j_begin = normalize ? 0 : d.crop_start;          // see resample_lds_kernel
-        const int64_t j_end = normalize || total < d.crop_start + kClip ? total : d.crop_start + kClip;
+        const int64_t j_end = normalize || total < d.crop_start + row_len ? total : d.crop_start + row_len;
         for (int64_t j = j_begin + tid; j < j_end; j += 256) {
             float y = 0.f;
             if (j < n_out) {
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(256) void decode_resample_kernel(const uint8_t* __r
                 peak = fmaxf(peak, fabsf(y));
             }
             const int64_t w = j - d.crop_start;
-            if (w >= 0 && w < kClip) o[w] = y;
+            if (w >= 0 && w < row_len) o[w] = y;
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) peak = fmaxf(peak, __shfl_xor(peak, off));
@@ -308,7 +309,7 @@ __global__ __launch_bounds__(256) void decode_resample_kernel(const uint8_t* __r
         if (normalize) {
             // x / max|x| over the WHOLE file (normalize_audio precedes pad_or_truncate); 0/0 = NaN like the reference,
             // except for the zero padding, which the reference appends after normalising
-            const int64_t valid = n_out - d.crop_start < kClip ? n_out - d.crop_start : kClip;
+            const int64_t valid = n_out - d.crop_start < row_len ? n_out - d.crop_start : row_len;
             for (int w = tid; w < valid; w += 256) o[w] = o[w] / peak;
         }
     }
@@ -344,6 +345,13 @@ int ww_resampler_prepare(int32_t sample_rate, ww_clip_desc* desc_host) {
 
 int ww_decode_resample(const uint8_t* raw_dev, const ww_clip_desc* descs_dev, int64_t n_clips, int normalize,
                        float* pcm_out_dev, ww_stream_t stream) {
+    return ww_decode_resample_n(raw_dev, descs_dev, n_clips, normalize, kClip, pcm_out_dev, stream);
+}
+
+int ww_decode_resample_n(const uint8_t* raw_dev, const ww_clip_desc* descs_dev, int64_t n_clips, int normalize, int64_t n_samples,
+                         float* pcm_out_dev, ww_stream_t stream) {
+    if (n_samples != kClip && (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_MAX_CLIP_SAMPLES))
+        return fail(WW_EINVAL, "n_samples %lld: expected %d..%d", (long long)n_samples, WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES);
     if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
     if (n_clips == 0) return WW_OK;
     if (!raw_dev || !descs_dev || !pcm_out_dev) return fail(WW_EINVAL, "null pointer");
@@ -351,11 +359,11 @@ int ww_decode_resample(const uint8_t* raw_dev, const ww_clip_desc* descs_dev, in
     const int64_t resident = int64_t(device_cu_count()) * 8;
     const int grid = int(n_clips < resident ? n_clips : resident);
     hipLaunchKernelGGL(decode_resample_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), raw_dev,
-                       descs_dev, int(n_clips), normalize, pcm_out_dev);
+                       descs_dev, int(n_clips), normalize, pcm_out_dev, int(n_samples));
 #ifndef WW_ABL_K0_DIRECT
     const int64_t resident2 = int64_t(device_cu_count()) * 2;
     hipLaunchKernelGGL(resample_lds_kernel, dim3(int(n_clips < resident2 ? n_clips : resident2)), dim3(kRsThreads), kRsLds,
-                       static_cast<hipStream_t>(stream), raw_dev, descs_dev, int(n_clips), normalize, pcm_out_dev);
+                       static_cast<hipStream_t>(stream), raw_dev, descs_dev, int(n_clips), normalize, pcm_out_dev, int(n_samples));
 #endif
     WW_HIP(hipGetLastError());
     return WW_OK;

@@ -473,6 +473,12 @@ int ww_read_wav_batch_host(ww_wav_reader* r, const char* const* paths, int64_t n
 }
 
 int ww_wav_batch_decode(ww_wav_reader* r, int32_t slot, int normalize, float* pcm_out_dev, ww_stream_t stream) {
+    return ww_wav_batch_decode_n(r, slot, normalize, WW_CLIP_SAMPLES, pcm_out_dev, stream);
+}
+
+int ww_wav_batch_decode_n(ww_wav_reader* r, int32_t slot, int normalize, int64_t n_samples, float* pcm_out_dev, ww_stream_t stream) {
+    if (n_samples != WW_CLIP_SAMPLES && (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_MAX_CLIP_SAMPLES))
+        return fail(WW_EINVAL, "n_samples %lld: expected %d..%d", (long long)n_samples, WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES);
     if (!r || !pcm_out_dev) return fail(WW_EINVAL, "ww_wav_batch_decode: null argument");
     if (slot < 0 || slot >= r->n_slots) return fail(WW_EINVAL, "slot %d of %d", slot, r->n_slots);
     if (r->host_only) return fail(WW_EUNSUPPORTED, "this reader was created WW_READER_HOST_ONLY (no device twin to decode from)");
@@ -485,7 +491,7 @@ int ww_wav_batch_decode(ww_wav_reader* r, int32_t slot, int normalize, float* pc
     WW_HIP(hipEventRecord(s.copied, r->copy_stream));
     s.copy_inflight = true;
     WW_HIP(hipStreamWaitEvent(st, s.copied, 0));
-    if (int rc = ww_decode_resample(s.raw_dev, s.descs_dev, s.n, normalize, pcm_out_dev, stream)) return rc;
+    if (int rc = ww_decode_resample_n(s.raw_dev, s.descs_dev, s.n, normalize, n_samples, pcm_out_dev, stream)) return rc;
     WW_HIP(hipEventRecord(s.decoded, st));
     s.decode_inflight = true;
     return WW_OK;

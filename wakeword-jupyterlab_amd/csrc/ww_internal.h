@@ -113,6 +113,9 @@ PackedLayout packed_layout(int n_conv);
 int launch_logmel(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int normalize,
                   const int32_t* ring_pos /*nullable: streaming ring start per launch*/, int64_t ring_len,
                   float* logmel, hipStream_t stream);
+// any clip length: rows of n_samples (<= 32000; clip_len <= n_samples valid), T = 1 + n_samples / 512 frames in [8, 63] -> [n][80][T]
+int launch_logmel_frames(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples, int normalize,
+                         float* logmel, hipStream_t stream);
 // log-mel arithmetic: 0 = f32 FFT, 1 = f64 FFT (what the reference's numpy.fft.rfft is), 2 = auto (f32, then the clips whose
 // quiet bands sit on the f32 FFT's rounding floor are redone in f64)
 int logmel_math_mode();
@@ -128,6 +131,11 @@ void build_kaiser_best(float* out /*[32769]*/);
 int sync_timeouts(unsigned int* count);   // bounded LDS-counter waits that expired (must be 0)
 int launch_cnn_pool(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch,
                     float* pooled, hipStream_t stream);
+// K2 for 33..63 columns: column tiles of 32 run through the kernels above as virtual clips, each pooling the columns it owns (ww_cnn.hip)
+int cnn_wide_tiles(int width, int n_conv);
+int64_t cnn_wide_scratch_bytes(int64_t n, int width, int n_conv);
+int launch_cnn_pool_wide(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch, float* pooled,
+                         hipStream_t stream);
 // conv math: 0 = exact f32 MFMA (v_mfma_f32_32x32x2_f32), 1 = f16x3 split (3 x v_mfma_f32_16x16x32_f16 per product block; conv2 of
 // the 2-conv model as 1-D Winograd), 2 = f16x3 split with every conv in its direct form
 int conv_math_mode();

@@ -15,7 +15,11 @@
 // applied to the 2560 mel powers instead of the 16000 samples (the peak falls out of the frame loads).
 //
 // Algorithmic HBM bytes per clip: 64,000 read + 10,240 written = 74,240.
+//
+// Other clip lengths (ww_logmel_frames_f32, 0.25 .. 2 s): the same kernels with a 64-frame mel tile (template parameter FR = 64), computing
+// ceil(T / waves) rounds of frames and keeping the first T; the epilogue maps lane = frame, and auto mode's frame mask is 64 bits wide.
 #include <mutex>
+#include <type_traits>
 
 #include "ww_internal.h"
 
@@ -23,7 +27,6 @@ namespace ww {
 
 // wave slab: 1024 complex = 2048 floats (+4 keeps 16-byte alignment and staggers the slabs over the banks)
 constexpr int kSlab = 2048 + 4;
-constexpr int kMelStride = kFrames + 1;
 // The per-wave piece sums live in the upper half of the wave's slab (the power spectrum only needs floats 0..1024).
 constexpr int kPartialInSlab = 1032;
 static_assert(kPartialInSlab + kPieces <= kSlab, "piece sums must fit behind the power spectrum");
@@ -40,26 +43,32 @@ static_assert(kPartialInSlab + kPieces <= kSlab, "piece sums must fit behind the
 #ifndef WW_K1_RESIDENT
 #define WW_K1_RESIDENT 0
 #endif
-template <int WAVES>
+// FR: the frames the mel tile holds.  FR = 32 (kFrames) is the 1 s kernel; FR = 64 takes any T = 1 + n_samples / 512 in [8, 63]
+// (ww_logmel_frames_f32), computing ceil(T / WAVES) rounds of frames and using the first T.
+template <int WAVES, int FR = kFrames>
 struct K1Layout {
     static constexpr int kWaves = WAVES;
     static constexpr int kThreads = WAVES * 64;
+    static constexpr int kMelStr = FR + 1;
     static constexpr int kOffMel = WAVES * kSlab;
-    static constexpr int kOffRed = kOffMel + kMels * kMelStride;
-    static constexpr int kOffFrm = kOffRed + 16;            // auto mode: [WAVES][32] per-frame energy partials, [80] 1 / wmax_b, [4] redo flag
-    static constexpr int kOffInvw = kOffFrm + WAVES * 32;
+    static constexpr int kOffRed = kOffMel + kMels * kMelStr;
+    static constexpr int kOffFrm = kOffRed + 16;            // auto mode: [WAVES][FR] per-frame energy partials, [80] 1 / wmax_b, [4] redo flag
+    static constexpr int kOffInvw = kOffFrm + WAVES * FR;
     static constexpr int kOffFlag = kOffInvw + kMels;
-    static constexpr int kOffDcNy = kOffFlag + 4;           // auto mode: [32] |X_0|^2 + |X_1024|^2 per frame (the two bins no mel band sees)
-    static constexpr int kOffPinfo = kOffDcNy + 32;         // [kPieces] ints
+    static constexpr int kOffDcNy = kOffFlag + 4;           // auto mode: [FR] |X_0|^2 + |X_1024|^2 per frame (the two bins no mel band sees)
+    static constexpr int kOffPinfo = kOffDcNy + FR;         // [kPieces] ints
     static constexpr int kOffFp0 = kOffPinfo + kPieces;     // [80] ints
     static constexpr int kOffFcnt = kOffFp0 + kMels;        // [80] ints
     static constexpr int kOffTw2 = kOffFcnt + kMels;        // [7][16] float2
     static constexpr int kOffTwp = kOffTw2 + 7 * 16 * 2;    // [512] float2
     static constexpr int kLdsFloats = kOffTwp + 512 * 2;
-    static constexpr int kWavesPerSimd = WAVES == 4 ? (WW_K1_RESIDENT ? 2 : 3) : 2;   // launch bound: 3 (2) x 4 waves or 1 x 8 waves per CU
-    static constexpr int kBlocksPerCu = WAVES == 4 ? (WW_K1_RESIDENT ? 2 : 3) : 1;
+    // launch bound: 3 (2) x 4 waves or 1 x 8 waves per CU; the 64-frame tile (62 KB with 4 waves) admits two 4-wave workgroups
+    static constexpr int kWavesPerSimd = WAVES == 4 ? (WW_K1_RESIDENT || FR != kFrames ? 2 : 3) : 2;
+    static constexpr int kBlocksPerCu = WAVES == 4 ? (WW_K1_RESIDENT || FR != kFrames ? 2 : 3) : 1;
     static_assert(kOffPinfo % 4 == 0 && kOffTw2 % 4 == 0 && kOffTwp % 2 == 0, "LDS table alignment");
-    static_assert(kFrames % WAVES == 0 && WAVES <= 8, "frames are dealt to the waves in whole rounds; red[] holds 16 floats");
+    static_assert(FR % WAVES == 0 && WAVES <= 8, "frames are dealt to the waves in whole rounds; red[] holds 16 floats");
+    static_assert(FR == kFrames || (FR == 64 && WW_K1_RESIDENT != 2), "the long-clip tile: 64 frames, frames dealt round-robin");
+    static_assert(kBlocksPerCu * sizeof(float) * kLdsFloats <= 160 * 1024, "LDS per CU");
 };
 
 __device__ __forceinline__ float2 operator+(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
@@ -180,19 +189,22 @@ __device__ unsigned long long g_stamps[16];
 
 // mark != 0 (auto mode): a clip with a live mel band on the float FFT's rounding floor gets kRedoMark in the first word of its
 // output and is recomputed by logmel64_kernel<RING, true>, which runs behind this kernel on the same stream.
-template <bool RING, int WAVES>
-__global__ __launch_bounds__(WAVES * 64, K1Layout<WAVES>::kWavesPerSimd) void logmel_kernel(const float* __restrict__ pcm, int64_t clip_stride,
+// FR = 64 (long clips): `n_frames` = T; the output is [n][80][T].  The FR = 32 instance ignores it.
+template <bool RING, int WAVES, int FR = kFrames>
+__global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) void logmel_kernel(const float* __restrict__ pcm, int64_t clip_stride,
                                                              int clip_len, int n_clips, int normalize,
                                                              const int32_t* __restrict__ ring_pos_p, int ring_len,
                                                              const LogmelTables* __restrict__ tb,
-                                                             float* __restrict__ out, int mark) {
-    using L = K1Layout<WAVES>;
+                                                             float* __restrict__ out, int mark, int n_frames) {
+    using L = K1Layout<WAVES, FR>;
+    constexpr int kMelStride = L::kMelStr;
+    const int nfr = FR == kFrames ? kFrames : n_frames;
     constexpr int kWavesPerBlock = WAVES, kThreads = L::kThreads;
     constexpr int kOffMel = L::kOffMel, kOffRed = L::kOffRed, kOffFrm = L::kOffFrm, kOffInvw = L::kOffInvw, kOffFlag = L::kOffFlag,
                   kOffDcNy = L::kOffDcNy, kOffPinfo = L::kOffPinfo, kOffFp0 = L::kOffFp0,
                   kOffFcnt = L::kOffFcnt, kOffTw2 = L::kOffTw2, kOffTwp = L::kOffTwp;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* mel = lds + kOffMel;                                 // [80][33]
+    float* mel = lds + kOffMel;                                 // [80][FR + 1]
     float* red = lds + kOffRed;                                 // [16]
     const float4* pw4 = reinterpret_cast<const float4*>(&tb->piece_w[0][0][0]);
     const int* pinfo = reinterpret_cast<const int*>(lds + kOffPinfo);
@@ -247,7 +259,7 @@ __global__ __launch_bounds__(WAVES * 64, K1Layout<WAVES>::kWavesPerSimd) void lo
         const float* base = pcm + int64_t(ok ? c : 0) * clip_stride;
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, ok ? clip_bytes : 0u, 0x00020000);
     };
-    constexpr int kRounds = kFrames / kWavesPerBlock;
+    const int kRounds = FR == kFrames ? kFrames / kWavesPerBlock : (nfr + kWavesPerBlock - 1) / kWavesPerBlock;
 #if WW_K1_RESIDENT == 2
     const int frame0 = wave * kRounds;                 // this wave's frames: frame0 .. frame0 + kRounds - 1
 #else
@@ -529,6 +541,83 @@ __global__ __launch_bounds__(WAVES * 64, K1Layout<WAVES>::kWavesPerSimd) void lo
 #if WW_K1_RESIDENT == 2
         load_frame<RING, 0, 6>(sn, rs_next, frame0 * kHop - kNfft / 2 + 4 * lane_id, ring_pos, ring_len);   // in flight under the epilogue
 #endif
+        if constexpr (FR != kFrames) {
+            // ---- long clip (T frames of the FR-frame tile): lane = frame, the wave's bands wave, wave + WAVES, ... ----
+            __syncthreads();   // all frames' mel bands are in LDS
+            uint32_t* flag = reinterpret_cast<uint32_t*>(lds) + kOffFlag;     // [clip parity][2]: the 64-bit frame mask (auto mode)
+            if (mark && tid == 0) { flag[2 * ((clip_it + 1) & 1)] = 0u; flag[2 * ((clip_it + 1) & 1) + 1] = 0u; }
+            const bool fr_live = lane < nfr;
+            const float* invw = lds + kOffInvw;
+            float* frm = lds + kOffFrm;
+            float mmax = 0.f, e_part = 0.f;
+            if (fr_live)
+                for (int b = wave; b < kMels; b += kWavesPerBlock) {
+                    const float p = mel[b * kMelStride + lane];
+                    mmax = fmaxf(mmax, p);
+                    if (mark) e_part = fmaf(p, invw[b], e_part);
+                }
+            if (mark) frm[wave * FR + lane] = e_part;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                mmax = fmaxf(mmax, __shfl_xor(mmax, off));
+                peak = fmaxf(peak, __shfl_xor(peak, off));
+            }
+            if (lane == 0) { red[wave] = mmax; red[kWavesPerBlock + wave] = peak; }
+            __syncthreads();
+            mmax = red[0];
+            peak = red[kWavesPerBlock];
+#pragma unroll
+            for (int w = 1; w < kWavesPerBlock; ++w) { mmax = fmaxf(mmax, red[w]); peak = fmaxf(peak, red[kWavesPerBlock + w]); }
+            const float amin = 1e-10f;
+            float g2 = 1.f;
+            if (normalize) { const float g = 1.0f / peak; g2 = g * g; }
+            float ref = mmax * g2;
+            ref = ref < amin ? amin : ref;
+            const float ref_db = db10(ref);
+            float* __restrict__ o = out + int64_t(clip) * (kMels * nfr);
+            float floor_e = 0.f;
+            if (mark) {
+#pragma unroll
+                for (int w = 0; w < kWavesPerBlock; ++w) floor_e += frm[w * FR + lane];
+                floor_e += lds[kOffDcNy + lane];
+                floor_e *= kFloorRatio;
+            }
+            const float live_thr = fmaxf(mmax * 0.99e-8f, amin / g2);
+            bool redo = false;
+            if (fr_live)
+                for (int b = wave; b < kMels; b += kWavesPerBlock) {
+                    const float p = mel[b * kMelStride + lane];
+                    float v = p * g2;
+                    v = v < amin ? amin : v;
+                    float db = db10(v) - ref_db;
+                    db = db < -80.0f ? -80.0f : db;
+                    o[b * nfr + lane] = db;
+                    if (mark) redo |= p > live_thr && p * invw[b] < floor_e;     // false for NaN
+                }
+            if (mark) {
+                const unsigned long long bal = __builtin_amdgcn_ballot_w64(redo);   // bit = frame
+                if (bal != 0ull && lane == 0) {
+                    __hip_atomic_fetch_or(flag + 2 * (clip_it & 1), uint32_t(bal), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_or(flag + 2 * (clip_it & 1) + 1, uint32_t(bal >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+            __syncthreads();   // the frame mask is complete; every read of mel / red / frm for the dB pass is done
+            if (mark) {
+                const uint32_t f_lo = flag[2 * (clip_it & 1)], f_hi = flag[2 * (clip_it & 1) + 1];   // uniform
+                if ((f_lo | f_hi) != 0u) {
+                    // a marked clip: powers instead of dB; words 0, 1, 2 (frames 0..2 of band 0) carry the mark and the 64-bit mask
+                    if (fr_live)
+                        for (int b = wave; b < kMels; b += kWavesPerBlock)
+                            if (b * nfr + lane >= 3) o[b * nfr + lane] = mel[b * kMelStride + lane] * g2;
+                    if (tid == 0) {
+                        reinterpret_cast<uint32_t*>(o)[0] = kRedoMark;
+                        reinterpret_cast<uint32_t*>(o)[1] = f_lo | 7u;
+                        reinterpret_cast<uint32_t*>(o)[2] = f_hi;
+                    }
+                    __syncthreads();   // mel is read above: no wave may start the next clip's frames (which rewrite it) before all are done
+                }
+            }
+        } else {
         __syncthreads();   // all 32 frames' mel bands are in LDS
         STAMP(6);
         // auto mode's frame mask lives in flag[clip_it & 1]; the other word (the previous clip's, whose readers are all past the barrier
@@ -610,6 +699,7 @@ __global__ __launch_bounds__(WAVES * 64, K1Layout<WAVES>::kWavesPerSimd) void lo
                 }
             }
         }
+        }
         STAMP(7);
     }
 #ifdef WW_STAMPS
@@ -681,23 +771,37 @@ __device__ __forceinline__ void dft16(cd (&v)[16]) {
 }
 
 constexpr int kSlab64 = 2 * 2048 + 8;                       // floats per wave: 1024 complex doubles (+ pad)
-constexpr int k64OffMel = 4 * kSlab64;
-constexpr int k64OffRed = k64OffMel + kMels * kMelStride;
-constexpr int k64OffPinfo = k64OffRed + 16;
-constexpr int k64OffFp0 = k64OffPinfo + kPieces;
-constexpr int k64OffFcnt = k64OffFp0 + kMels;
-constexpr int k64OffTw2 = (k64OffFcnt + kMels + 3) & ~3;     // [7][16] complex doubles
-constexpr int k64LdsFloats = k64OffTw2 + 7 * 16 * 4;
-static_assert(k64OffMel % 4 == 0 && k64OffTw2 % 4 == 0, "16-byte alignment of the double tables");
+// FR: frames of the mel tile, as in K1Layout (32: the 1 s kernel; 64: ww_logmel_frames_f32, one 90 KB workgroup per CU)
+template <int FR = kFrames>
+struct K64Layout {
+    static constexpr int kMelStr = FR + 1;
+    static constexpr int kOffMel = 4 * kSlab64;
+    static constexpr int kOffRed = kOffMel + kMels * kMelStr;
+    static constexpr int kOffPinfo = kOffRed + 16;
+    static constexpr int kOffFp0 = kOffPinfo + kPieces;
+    static constexpr int kOffFcnt = kOffFp0 + kMels;
+    static constexpr int kOffTw2 = (kOffFcnt + kMels + 3) & ~3;     // [7][16] complex doubles
+    static constexpr int kLdsFloats = kOffTw2 + 7 * 16 * 4;
+    static constexpr int kBlocksPerCu = FR == kFrames ? 2 : 1;
+    static_assert(kOffMel % 4 == 0 && kOffTw2 % 4 == 0, "16-byte alignment of the double tables");
+    static_assert(kBlocksPerCu * (sizeof(float) * kLdsFloats + 512) <= 160 * 1024, "LDS per CU");
+};
+constexpr int k64LdsFloats = K64Layout<>::kLdsFloats;
 // Round 4: TWO workgroups per CU (two waves per SIMD; round 3 ran one 93 KB workgroup = one wave per SIMD, every LDS and L2 round trip
 // exposed): the 8 KB pair-twiddle table is read through L1 like the window and the pass-1 twiddles, which brings a workgroup under 80 KB.
 static_assert(sizeof(float) * k64LdsFloats + 512 <= 80 * 1024, "two logmel64 workgroups per CU");
 
-template <bool RING, bool ONLY_FLAGGED>
+// FR = 64: `n_frames` = T, output [n][80][T]; a marked clip's frame mask is 64 bits in words 1 and 2 (logmel_kernel<.., 64>).
+template <bool RING, bool ONLY_FLAGGED, int FR = kFrames>
 __global__ __launch_bounds__(256, 2) void logmel64_kernel(const float* __restrict__ pcm, int64_t clip_stride, int clip_len, int n_clips,
                                                           int normalize, const int32_t* __restrict__ ring_pos_p, int ring_len,
-                                                          const LogmelTables* __restrict__ tb, float* __restrict__ out) {
+                                                          const LogmelTables* __restrict__ tb, float* __restrict__ out, int n_frames) {
     constexpr int kWavesPerBlock = 4, kThreads = 256;
+    using L64 = K64Layout<FR>;
+    constexpr int kMelStride = L64::kMelStr, k64OffMel = L64::kOffMel, k64OffRed = L64::kOffRed, k64OffPinfo = L64::kOffPinfo,
+                  k64OffFp0 = L64::kOffFp0, k64OffFcnt = L64::kOffFcnt, k64OffTw2 = L64::kOffTw2;
+    const int nfr = FR == kFrames ? kFrames : n_frames;
+    using mask_t = typename std::conditional<FR == kFrames, uint32_t, unsigned long long>::type;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* mel = lds + k64OffMel;
     float* red = lds + k64OffRed;
@@ -717,7 +821,7 @@ __global__ __launch_bounds__(256, 2) void logmel64_kernel(const float* __restric
         // tables are staged (the launch then costs a few microseconds)
         int any = 0;
         for (int c = int(blockIdx.x) + tid * int(gridDim.x); c < n_clips; c += kThreads * int(gridDim.x))
-            any |= __float_as_uint(__builtin_nontemporal_load(out + int64_t(c) * (kMels * kFrames))) == kRedoMark;
+            any |= __float_as_uint(__builtin_nontemporal_load(out + int64_t(c) * (kMels * nfr))) == kRedoMark;
         if (!__syncthreads_or(any)) return;
     }
     float* slabf = lds + wave * kSlab64;                        // power spectrum / piece sums (floats) reuse the slab
@@ -740,23 +844,29 @@ __global__ __launch_bounds__(256, 2) void logmel64_kernel(const float* __restric
 
 #pragma unroll 1
     for (int clip = blockIdx.x; clip < n_clips; clip += gridDim.x) {
-        float* __restrict__ o = out + int64_t(clip) * (kMels * kFrames);
-        uint32_t fmask = 0xffffffffu;                  // the frames this launch computes; all of them unless the float kernel said which
+        float* __restrict__ o = out + int64_t(clip) * (kMels * nfr);
+        // the frames this launch computes; all of them unless the float kernel said which
+        mask_t fmask = FR == kFrames ? mask_t(0xffffffffu) : (nfr >= 64 ? ~mask_t(0) : (mask_t(1) << nfr) - 1u);
         if constexpr (ONLY_FLAGGED) {
             if (__builtin_amdgcn_readfirstlane(__float_as_uint(__builtin_nontemporal_load(o))) != kRedoMark) continue;   // uniform
             fmask = __builtin_amdgcn_readfirstlane(__float_as_uint(__builtin_nontemporal_load(o + 1)));
+            if constexpr (FR != kFrames)
+                fmask |= mask_t(__builtin_amdgcn_readfirstlane(__float_as_uint(__builtin_nontemporal_load(o + 2)))) << 32;
 #ifdef WW_ABL_WHOLE_CLIP          // A/B: redo every frame of a marked clip (round 3's behaviour)
             fmask = 0xffffffffu;
 #endif
             // the other frames' mel powers as the float kernel left them (already carrying the peak gain)
-            for (int idx = tid; idx < kMels * kFrames; idx += kThreads)
-                if (!((fmask >> (idx & 31)) & 1u)) mel[(idx >> 5) * kMelStride + (idx & 31)] = __builtin_nontemporal_load(o + idx);
+            for (int idx = tid; idx < kMels * nfr; idx += kThreads) {
+                const int b = FR == kFrames ? idx >> 5 : idx / nfr, t = FR == kFrames ? idx & 31 : idx - b * nfr;
+                if (!((fmask >> t) & 1u)) mel[b * kMelStride + t] = __builtin_nontemporal_load(o + idx);
+            }
         }
-        const int n_mine = (__builtin_popcount(fmask) - wave + kWavesPerBlock - 1) / kWavesPerBlock;     // this wave takes the masked frames number wave, wave + 4, ...
+        const int n_mine = (int(FR == kFrames ? __builtin_popcount(uint32_t(fmask)) : __builtin_popcountll(fmask)) - wave + kWavesPerBlock - 1) /
+                           kWavesPerBlock;     // this wave takes the masked frames number wave, wave + 4, ...
         auto nth_frame = [&](int n) -> int {           // index of the n-th set bit of fmask (scalar); past the last one: a frame outside the clip (zero loads)
-            uint32_t m = fmask;
+            mask_t m = fmask;
             for (int i = 0; i < n && m; ++i) m &= m - 1u;
-            return m ? __builtin_ctz(m) : 64;
+            return m ? (FR == kFrames ? __builtin_ctz(uint32_t(m)) : __builtin_ctzll(m)) : 2 * FR;
         };
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pcm + int64_t(clip) * clip_stride), 0,
                                                                              clip_bytes, 0x00020000);
@@ -767,7 +877,7 @@ __global__ __launch_bounds__(256, 2) void logmel64_kernel(const float* __restric
         float peak = 0.f;
         if (normalize) {
 #pragma unroll 1
-            for (int round = 0; round < kFrames / kWavesPerBlock; ++round) {
+            for (int round = 0; round < (nfr + kWavesPerBlock - 1) / kWavesPerBlock; ++round) {
                 float4 sn[8];
                 load_frame<RING>(sn, rs, (round * kWavesPerBlock + wave) * kHop - kNfft / 2 + 4 * lane, ring_pos, ring_len);
                 peak = absmax3(sn[4].z, sn[4].w, absmax3(sn[4].x, sn[4].y, peak));
@@ -941,8 +1051,9 @@ __global__ __launch_bounds__(256, 2) void logmel64_kernel(const float* __restric
         // a NaN anywhere (silent clip, 0/0) must reach every output like in the reference: fmaxf would drop it
         float mmax = 0.f;
         bool any_nan = false;
-        for (int idx = tid; idx < kMels * kFrames; idx += kThreads) {
-            const float p = mel[(idx >> 5) * kMelStride + (idx & 31)];
+        for (int idx = tid; idx < kMels * nfr; idx += kThreads) {
+            const int b = FR == kFrames ? idx >> 5 : idx / nfr, t = FR == kFrames ? idx & 31 : idx - b * nfr;
+            const float p = mel[b * kMelStride + t];
             any_nan |= p != p;
             mmax = fmaxf(mmax, p);
         }
@@ -958,8 +1069,9 @@ __global__ __launch_bounds__(256, 2) void logmel64_kernel(const float* __restric
         float ref = mmax;
         ref = ref < amin ? amin : ref;
         const float ref_db = db10(ref);
-        for (int idx = tid; idx < kMels * kFrames; idx += kThreads) {
-            float v = mel[(idx >> 5) * kMelStride + (idx & 31)];
+        for (int idx = tid; idx < kMels * nfr; idx += kThreads) {
+            const int b = FR == kFrames ? idx >> 5 : idx / nfr, t = FR == kFrames ? idx & 31 : idx - b * nfr;
+            float v = mel[b * kMelStride + t];
             v = v < amin ? amin : v;
             float db = db10(v) - ref_db;
             db = db < -80.0f ? -80.0f : db;
@@ -969,35 +1081,43 @@ __global__ __launch_bounds__(256, 2) void logmel64_kernel(const float* __restric
     }
 }
 
-template <int WAVES>
+template <int WAVES, int FR = kFrames>
 static int launch_logmel_w(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int normalize,
-                           const int32_t* ring_pos, int64_t ring_len, float* logmel, const LogmelTables* tb, int mark, hipStream_t stream) {
-    using L = K1Layout<WAVES>;
+                           const int32_t* ring_pos, int64_t ring_len, float* logmel, const LogmelTables* tb, int mark, hipStream_t stream,
+                           int n_frames = kFrames) {
+    using L = K1Layout<WAVES, FR>;
     const int64_t resident = int64_t(device_cu_count()) * L::kBlocksPerCu;   // what LDS and VGPRs admit per CU
     const int grid = int(n_clips < resident ? n_clips : resident);
     const size_t lds_bytes = sizeof(float) * L::kLdsFloats;
-    if (ring_pos)
+    if constexpr (FR != kFrames)      // long clips: no ring form
+        hipLaunchKernelGGL((logmel_kernel<false, WAVES, FR>), dim3(grid), dim3(L::kThreads), lds_bytes, stream, pcm, clip_stride, int(clip_len),
+                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark, n_frames);
+    else if (ring_pos)
         hipLaunchKernelGGL((logmel_kernel<true, WAVES>), dim3(grid), dim3(L::kThreads), lds_bytes, stream, pcm, clip_stride, int(clip_len),
-                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark);
+                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark, kFrames);
     else
         hipLaunchKernelGGL((logmel_kernel<false, WAVES>), dim3(grid), dim3(L::kThreads), lds_bytes, stream, pcm, clip_stride, int(clip_len),
-                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark);
+                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark, kFrames);
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
 
-template <bool ONLY_FLAGGED>
+template <bool ONLY_FLAGGED, int FR = kFrames>
 static int launch_logmel64(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int normalize,
-                           const int32_t* ring_pos, int64_t ring_len, float* logmel, const LogmelTables* tb, hipStream_t stream) {
-    const int64_t resident = 2 * int64_t(device_cu_count());      // two 80 KB workgroups per CU
+                           const int32_t* ring_pos, int64_t ring_len, float* logmel, const LogmelTables* tb, hipStream_t stream,
+                           int n_frames = kFrames) {
+    const int64_t resident = K64Layout<FR>::kBlocksPerCu * int64_t(device_cu_count());      // two 80 KB workgroups per CU (FR 32)
     const int grid = int(n_clips < resident ? n_clips : resident);
-    const size_t lds_bytes = sizeof(float) * k64LdsFloats;
-    if (ring_pos)
+    const size_t lds_bytes = sizeof(float) * K64Layout<FR>::kLdsFloats;
+    if constexpr (FR != kFrames)
+        hipLaunchKernelGGL((logmel64_kernel<false, ONLY_FLAGGED, FR>), dim3(grid), dim3(256), lds_bytes, stream, pcm, clip_stride, int(clip_len),
+                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, n_frames);
+    else if (ring_pos)
         hipLaunchKernelGGL((logmel64_kernel<true, ONLY_FLAGGED>), dim3(grid), dim3(256), lds_bytes, stream, pcm, clip_stride, int(clip_len),
-                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel);
+                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, kFrames);
     else
         hipLaunchKernelGGL((logmel64_kernel<false, ONLY_FLAGGED>), dim3(grid), dim3(256), lds_bytes, stream, pcm, clip_stride, int(clip_len),
-                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel);
+                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, kFrames);
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
@@ -1021,6 +1141,12 @@ static int logmel_opt_in_lds() {
     WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, b64));
     WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, b64));
     WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, b64));
+    const int c4 = int(sizeof(float) * K1Layout<4, 64>::kLdsFloats), c8 = int(sizeof(float) * K1Layout<8, 64>::kLdsFloats);
+    const int c64 = int(sizeof(float) * K64Layout<64>::kLdsFloats);
+    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<false, 4, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c4));
+    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<false, 8, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c8));
+    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<false, true, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c64));
+    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<false, false, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c64));
     done[dev] = true;
     return WW_OK;
 }
@@ -1043,6 +1169,29 @@ int launch_logmel(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_
         rc = launch_logmel_w<4>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, mark, stream);
     if (rc != WW_OK || !mark) return rc;
     return launch_logmel64<true>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, stream);
+}
+
+// Any clip length (ww_logmel_frames_f32): rows of n_samples (clip_len valid, the rest zero), T = 1 + n_samples / 512 frames, [n][80][T].
+// T = 32 is the 1 s kernel itself (bit for bit); every other T runs the 64-frame instances, in the same three arithmetics.
+int launch_logmel_frames(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples, int normalize,
+                         float* logmel, hipStream_t stream) {
+    const int T = int(1 + n_samples / kHop);
+    if (T == kFrames) return launch_logmel(pcm, n_clips, clip_stride, clip_len, normalize, nullptr, 0, logmel, stream);
+    if (n_clips == 0) return WW_OK;
+    const LogmelTables* tb = device_tables();
+    if (!tb) return WW_EHIP;
+    if (int rc = logmel_opt_in_lds()) return rc;
+    const int mode = logmel_math_mode();
+    if (mode == WW_LOGMEL_MATH_F64)
+        return launch_logmel64<false, 64>(pcm, n_clips, clip_stride, clip_len, normalize, nullptr, 0, logmel, tb, stream, T);
+    const int mark = mode == WW_LOGMEL_MATH_AUTO;
+    int rc;
+    if (n_clips <= device_cu_count())
+        rc = launch_logmel_w<8, 64>(pcm, n_clips, clip_stride, clip_len, normalize, nullptr, 0, logmel, tb, mark, stream, T);
+    else
+        rc = launch_logmel_w<4, 64>(pcm, n_clips, clip_stride, clip_len, normalize, nullptr, 0, logmel, tb, mark, stream, T);
+    if (rc != WW_OK || !mark) return rc;
+    return launch_logmel64<true, 64>(pcm, n_clips, clip_stride, clip_len, normalize, nullptr, 0, logmel, tb, stream, T);
 }
 
 }  // namespace ww

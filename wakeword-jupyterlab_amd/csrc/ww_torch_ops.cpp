@@ -3,6 +3,7 @@
 // torch.library (no Meta kernel: FakeTensor tracing / torch.compile of the drop-in modules could not work, and every call paid Python
 // dispatch); this translation unit replaces them.  It is host code only: it validates tensors, allocates outputs with ATen and calls
 //   ww_logmel_f32 / ww_cnn_pool_f32 / ww_lstm_fc_f32 / ww_model_forward_f32 / ww_forward_pcm_f32      (include/wakeword_amd.h)
+// and, for clips of 0.25 s to 2 s, ww_logmel_frames_f32 / ww_cnn_pool_wide_f32 / ww_forward_pcm_frames_f32
 // on torch's current HIP stream.  The ww_* functions are neither linked nor looked up by name: the Python package hands their ADDRESSES in
 // (ww_torch_bind, from the ctypes handle of libwakeword_amd.so or of the build named by WW_LIB_OVERRIDE), so nothing enters the global
 // symbol scope -- several builds of the library can live in one process (scripts/ab_kernels.py) without interposing each other's kernels.
@@ -20,6 +21,7 @@
 namespace {
 
 constexpr int64_t kClip = WW_CLIP_SAMPLES, kMels = WW_N_MELS, kFrames = WW_N_FRAMES;
+constexpr int64_t kMinSamples = WW_MIN_CLIP_SAMPLES, kMaxSamples = WW_MAX_CLIP_SAMPLES, kMaxFrames = WW_MAX_FRAMES;
 
 // the C ABI entry points this library calls, bound once by ww_torch_bind (order = ops.py::_TORCH_BIND_ORDER)
 struct Abi {
@@ -32,8 +34,13 @@ struct Abi {
     decltype(&::ww_lstm_fc_f32) lstm_fc_f32 = nullptr;
     decltype(&::ww_model_forward_f32) model_forward_f32 = nullptr;
     decltype(&::ww_forward_pcm_f32) forward_pcm_f32 = nullptr;
+    decltype(&::ww_logmel_frames_f32) logmel_frames_f32 = nullptr;
+    decltype(&::ww_cnn_wide_scratch_bytes) cnn_wide_scratch_bytes = nullptr;
+    decltype(&::ww_cnn_pool_wide_f32) cnn_pool_wide_f32 = nullptr;
+    decltype(&::ww_workspace_frames_bytes) workspace_frames_bytes = nullptr;
+    decltype(&::ww_forward_pcm_frames_f32) forward_pcm_frames_f32 = nullptr;
 } abi;
-constexpr int kAbiEntries = 9;
+constexpr int kAbiEntries = 14;
 const Abi& bound() {
     TORCH_CHECK(abi.forward_pcm_f32 != nullptr, "wakeword_amd: the operators are not bound to libwakeword_amd.so (import wakeword_jupyterlab_amd does it)");
     return abi;
@@ -47,6 +54,11 @@ const Abi& bound() {
 #define ww_lstm_fc_f32 bound().lstm_fc_f32
 #define ww_model_forward_f32 bound().model_forward_f32
 #define ww_forward_pcm_f32 bound().forward_pcm_f32
+#define ww_logmel_frames_f32 bound().logmel_frames_f32
+#define ww_cnn_wide_scratch_bytes bound().cnn_wide_scratch_bytes
+#define ww_cnn_pool_wide_f32 bound().cnn_pool_wide_f32
+#define ww_workspace_frames_bytes bound().workspace_frames_bytes
+#define ww_forward_pcm_frames_f32 bound().forward_pcm_frames_f32
 
 void* stream_of(const at::Tensor& t) { return static_cast<void*>(c10::hip::getCurrentHIPStream(t.device().index()).stream()); }
 
@@ -65,11 +77,12 @@ int64_t c_last(int64_t n_conv) {
 }
 
 // [B, n <= 16000] float32 with unit sample stride, row stride a multiple of 4 floats and a 16-byte aligned base, copying only if needed
-at::Tensor checked_pcm(const at::Tensor& pcm) {
+// (max_samples: the clip length of the *_frames ops, n_samples; the 1 s ops take 16000)
+at::Tensor checked_pcm(const at::Tensor& pcm, int64_t max_samples = kClip) {
     require_cuda_f32(pcm, "pcm");
     TORCH_CHECK(pcm.dim() == 2, "pcm: expected [B, samples], got ", pcm.sizes());
     const int64_t B = pcm.size(0), n = pcm.size(1);
-    TORCH_CHECK(n >= 1 && n <= kClip, "pcm: ", n, " samples per clip; the front-end takes 1..", kClip,
+    TORCH_CHECK(n >= 1 && n <= max_samples, "pcm: ", n, " samples per clip; the front-end takes 1..", max_samples,
                 " (crop longer clips on the host, pad_or_truncate wakeword_training_script.py:78-83)");
     if (pcm.stride(1) == 1 && (B <= 1 || pcm.stride(0) % 4 == 0) && reinterpret_cast<uintptr_t>(pcm.data_ptr()) % 16 == 0) return pcm;
     at::Tensor p = pcm.contiguous();
@@ -86,6 +99,19 @@ at::Tensor checked_x(const at::Tensor& x) {
     TORCH_CHECK(x.dim() == 4 && x.size(1) == 1 && x.size(2) == kMels, "x: expected [B, 1, ", kMels, ", T], got ", x.sizes());
     TORCH_CHECK_NOT_IMPLEMENTED(x.size(3) >= 1 && x.size(3) <= 32, "x: T = ", x.size(3), " frames; the conv kernels are built for 1..32 (1 s clips give 32)");
     return x.contiguous();
+}
+
+at::Tensor checked_x_wide(const at::Tensor& x) {
+    require_cuda_f32(x, "x");
+    TORCH_CHECK(x.dim() == 4 && x.size(1) == 1 && x.size(2) == kMels, "x: expected [B, 1, ", kMels, ", T], got ", x.sizes());
+    TORCH_CHECK(x.size(3) >= 1 && x.size(3) <= kMaxFrames, "x: T = ", x.size(3), " frames; the wide conv stack takes 1..", kMaxFrames, " (2 s clips give 63)");
+    return x.contiguous();
+}
+
+int64_t frames_of(int64_t n_samples) {
+    TORCH_CHECK(n_samples >= kMinSamples && n_samples <= kMaxSamples, "n_samples = ", n_samples, ": clips of ", kMinSamples, "..", kMaxSamples,
+                " samples (0.25 s .. 2 s)");
+    return 1 + n_samples / WW_HOP;
 }
 
 void check_packed(const at::Tensor& packed, int64_t n_conv, const at::Tensor& like) {
@@ -161,6 +187,47 @@ at::Tensor forward_pcm_cuda(const at::Tensor& pcm_in, const at::Tensor& packed, 
     return logits;
 }
 
+// clips of n_samples (0.25 s .. 2 s): [B, n <= n_samples] -> [B, 1, 80, T], T = 1 + n_samples / 512
+at::Tensor logmel_frames_cuda(const at::Tensor& pcm_in, int64_t n_samples, bool normalize) {
+    const int64_t T = frames_of(n_samples);
+    const at::Tensor pcm = checked_pcm(pcm_in, n_samples);
+    const int64_t B = pcm.size(0), n = pcm.size(1);
+    at::Tensor out = at::empty({B, 1, kMels, T}, pcm.options());
+    c10::DeviceGuard guard(pcm.device());
+    check_rc(ww_logmel_frames_f32(pcm.data_ptr<float>(), B, B > 1 ? pcm.stride(0) : n, n, n_samples, normalize ? 1 : 0, out.data_ptr<float>(),
+                                  stream_of(pcm)), "logmel_frames");
+    return out;
+}
+
+at::Tensor cnn_pool_wide_cuda(const at::Tensor& x_in, const at::Tensor& packed, int64_t n_conv) {
+    const at::Tensor x = checked_x_wide(x_in);
+    check_packed(packed, n_conv, x);
+    const int64_t B = x.size(0), T = x.size(3);
+    at::Tensor pooled = at::empty({B, c_last(n_conv)}, x.options());
+    const int64_t nbytes = ww_cnn_wide_scratch_bytes(B, int32_t(T), int32_t(n_conv));
+    check_rc(nbytes, "cnn_pool_wide");
+    at::Tensor scratch = at::empty({nbytes > 0 ? nbytes : 1}, x.options().dtype(at::kByte));
+    c10::DeviceGuard guard(x.device());
+    check_rc(ww_cnn_pool_wide_f32(x.data_ptr<float>(), B, int32_t(T), packed.data_ptr<float>(), int32_t(n_conv), nbytes > 0 ? scratch.data_ptr() : nullptr,
+                                  pooled.data_ptr<float>(), stream_of(x)), "cnn_pool_wide");
+    return pooled;
+}
+
+at::Tensor forward_pcm_frames_cuda(const at::Tensor& pcm_in, const at::Tensor& packed, int64_t n_conv, int64_t n_samples, bool normalize) {
+    (void)frames_of(n_samples);
+    const at::Tensor pcm = checked_pcm(pcm_in, n_samples);
+    check_packed(packed, n_conv, pcm);
+    const int64_t B = pcm.size(0), n = pcm.size(1);
+    at::Tensor logits = at::empty({B, 2}, pcm.options());
+    const int64_t nbytes = ww_workspace_frames_bytes(B, n_samples, int32_t(n_conv));
+    check_rc(nbytes, "forward_pcm_frames");
+    at::Tensor ws = at::empty({nbytes > 0 ? nbytes : 1}, pcm.options().dtype(at::kByte));
+    c10::DeviceGuard guard(pcm.device());
+    check_rc(ww_forward_pcm_frames_f32(pcm.data_ptr<float>(), B, B > 1 ? pcm.stride(0) : n, n, n_samples, normalize ? 1 : 0, packed.data_ptr<float>(),
+                                       int32_t(n_conv), ws.data_ptr(), logits.data_ptr<float>(), stream_of(pcm)), "forward_pcm_frames");
+    return logits;
+}
+
 // ---------------------------------------------------------------- Meta kernels: shapes only (FakeTensor / torch.compile tracing)
 at::Tensor logmel_meta(const at::Tensor& pcm, bool) {
     TORCH_CHECK(pcm.dim() == 2 && pcm.size(1) >= 1 && pcm.size(1) <= kClip, "pcm: expected [B, 1..", kClip, "], got ", pcm.sizes());
@@ -185,6 +252,23 @@ at::Tensor forward_pcm_meta(const at::Tensor& pcm, const at::Tensor&, int64_t n_
     return at::empty({pcm.size(0), 2}, pcm.options().dtype(at::kFloat));
 }
 
+at::Tensor logmel_frames_meta(const at::Tensor& pcm, int64_t n_samples, bool) {
+    const int64_t T = frames_of(n_samples);
+    TORCH_CHECK(pcm.dim() == 2 && pcm.size(1) >= 1 && pcm.size(1) <= n_samples, "pcm: expected [B, 1..", n_samples, "], got ", pcm.sizes());
+    return at::empty({pcm.size(0), 1, kMels, T}, pcm.options().dtype(at::kFloat));
+}
+at::Tensor cnn_pool_wide_meta(const at::Tensor& x, const at::Tensor&, int64_t n_conv) {
+    TORCH_CHECK(x.dim() == 4 && x.size(1) == 1 && x.size(2) == kMels && x.size(3) >= 1 && x.size(3) <= kMaxFrames, "x: expected [B, 1, ", kMels,
+                ", 1..", kMaxFrames, "], got ", x.sizes());
+    return at::empty({x.size(0), c_last(n_conv)}, x.options().dtype(at::kFloat));
+}
+at::Tensor forward_pcm_frames_meta(const at::Tensor& pcm, const at::Tensor&, int64_t n_conv, int64_t n_samples, bool) {
+    (void)frames_of(n_samples);
+    TORCH_CHECK(pcm.dim() == 2 && pcm.size(1) >= 1 && pcm.size(1) <= n_samples, "pcm: expected [B, 1..", n_samples, "], got ", pcm.sizes());
+    (void)c_last(n_conv);
+    return at::empty({pcm.size(0), 2}, pcm.options().dtype(at::kFloat));
+}
+
 // ---------------------------------------------------------------- CPU: there is none
 [[noreturn]] void no_cpu(const char* name) {
     TORCH_CHECK(false, "wakeword_amd::", name, ": no CPU implementation exists (HIP/gfx950 only); move the tensors to the GPU");
@@ -194,6 +278,9 @@ at::Tensor cnn_pool_cpu(const at::Tensor&, const at::Tensor&, int64_t) { no_cpu(
 at::Tensor lstm_fc_cpu(const at::Tensor&, const at::Tensor&, int64_t) { no_cpu("lstm_fc"); }
 at::Tensor cnn_lstm_forward_cpu(const at::Tensor&, const at::Tensor&, int64_t) { no_cpu("cnn_lstm_forward"); }
 at::Tensor forward_pcm_cpu(const at::Tensor&, const at::Tensor&, int64_t, bool) { no_cpu("forward_pcm"); }
+at::Tensor logmel_frames_cpu(const at::Tensor&, int64_t, bool) { no_cpu("logmel_frames"); }
+at::Tensor cnn_pool_wide_cpu(const at::Tensor&, const at::Tensor&, int64_t) { no_cpu("cnn_pool_wide"); }
+at::Tensor forward_pcm_frames_cpu(const at::Tensor&, const at::Tensor&, int64_t, int64_t, bool) { no_cpu("forward_pcm_frames"); }
 
 }  // namespace
 
@@ -206,9 +293,15 @@ at::Tensor forward_pcm_cpu(const at::Tensor&, const at::Tensor&, int64_t, bool) 
 #undef ww_lstm_fc_f32
 #undef ww_model_forward_f32
 #undef ww_forward_pcm_f32
+#undef ww_logmel_frames_f32
+#undef ww_cnn_wide_scratch_bytes
+#undef ww_cnn_pool_wide_f32
+#undef ww_workspace_frames_bytes
+#undef ww_forward_pcm_frames_f32
 
 // fns[kAbiEntries]: addresses of ww_last_error, ww_packed_weights_floats, ww_cnn_scratch_bytes, ww_workspace_bytes, ww_logmel_f32,
-// ww_cnn_pool_f32, ww_lstm_fc_f32, ww_model_forward_f32, ww_forward_pcm_f32 of ONE build of libwakeword_amd.so.  Returns 0, or -1 on a bad table.
+// ww_cnn_pool_f32, ww_lstm_fc_f32, ww_model_forward_f32, ww_forward_pcm_f32, ww_logmel_frames_f32, ww_cnn_wide_scratch_bytes, ww_cnn_pool_wide_f32,
+// ww_workspace_frames_bytes, ww_forward_pcm_frames_f32 of ONE build of libwakeword_amd.so.  Returns 0, or -1 on a bad table.
 extern "C" __attribute__((visibility("default"))) int ww_torch_bind(const void* const* fns, int n) {
     if (!fns || n != kAbiEntries) return -1;
     for (int i = 0; i < n; ++i)
@@ -222,6 +315,11 @@ extern "C" __attribute__((visibility("default"))) int ww_torch_bind(const void* 
     abi.lstm_fc_f32 = reinterpret_cast<decltype(abi.lstm_fc_f32)>(const_cast<void*>(fns[6]));
     abi.model_forward_f32 = reinterpret_cast<decltype(abi.model_forward_f32)>(const_cast<void*>(fns[7]));
     abi.forward_pcm_f32 = reinterpret_cast<decltype(abi.forward_pcm_f32)>(const_cast<void*>(fns[8]));
+    abi.logmel_frames_f32 = reinterpret_cast<decltype(abi.logmel_frames_f32)>(const_cast<void*>(fns[9]));
+    abi.cnn_wide_scratch_bytes = reinterpret_cast<decltype(abi.cnn_wide_scratch_bytes)>(const_cast<void*>(fns[10]));
+    abi.cnn_pool_wide_f32 = reinterpret_cast<decltype(abi.cnn_pool_wide_f32)>(const_cast<void*>(fns[11]));
+    abi.workspace_frames_bytes = reinterpret_cast<decltype(abi.workspace_frames_bytes)>(const_cast<void*>(fns[12]));
+    abi.forward_pcm_frames_f32 = reinterpret_cast<decltype(abi.forward_pcm_frames_f32)>(const_cast<void*>(fns[13]));
     return 0;
 }
 
@@ -231,6 +329,9 @@ TORCH_LIBRARY(wakeword_amd, m) {
     m.def("lstm_fc(Tensor pooled, Tensor packed, int n_conv) -> Tensor");
     m.def("cnn_lstm_forward(Tensor x, Tensor packed, int n_conv) -> Tensor");
     m.def("forward_pcm(Tensor pcm, Tensor packed, int n_conv, bool normalize=True) -> Tensor");
+    m.def("logmel_frames(Tensor pcm, int n_samples, bool normalize=True) -> Tensor");
+    m.def("cnn_pool_wide(Tensor x, Tensor packed, int n_conv) -> Tensor");
+    m.def("forward_pcm_frames(Tensor pcm, Tensor packed, int n_conv, int n_samples, bool normalize=True) -> Tensor");
 }
 TORCH_LIBRARY_IMPL(wakeword_amd, CUDA, m) {
     m.impl("logmel", &logmel_cuda);
@@ -238,6 +339,9 @@ TORCH_LIBRARY_IMPL(wakeword_amd, CUDA, m) {
     m.impl("lstm_fc", &lstm_fc_cuda);
     m.impl("cnn_lstm_forward", &cnn_lstm_forward_cuda);
     m.impl("forward_pcm", &forward_pcm_cuda);
+    m.impl("logmel_frames", &logmel_frames_cuda);
+    m.impl("cnn_pool_wide", &cnn_pool_wide_cuda);
+    m.impl("forward_pcm_frames", &forward_pcm_frames_cuda);
 }
 TORCH_LIBRARY_IMPL(wakeword_amd, Meta, m) {
     m.impl("logmel", &logmel_meta);
@@ -245,6 +349,9 @@ TORCH_LIBRARY_IMPL(wakeword_amd, Meta, m) {
     m.impl("lstm_fc", &lstm_fc_meta);
     m.impl("cnn_lstm_forward", &cnn_lstm_forward_meta);
     m.impl("forward_pcm", &forward_pcm_meta);
+    m.impl("logmel_frames", &logmel_frames_meta);
+    m.impl("cnn_pool_wide", &cnn_pool_wide_meta);
+    m.impl("forward_pcm_frames", &forward_pcm_frames_meta);
 }
 TORCH_LIBRARY_IMPL(wakeword_amd, CPU, m) {
     m.impl("logmel", &logmel_cpu);
@@ -252,4 +359,7 @@ TORCH_LIBRARY_IMPL(wakeword_amd, CPU, m) {
     m.impl("lstm_fc", &lstm_fc_cpu);
     m.impl("cnn_lstm_forward", &cnn_lstm_forward_cpu);
     m.impl("forward_pcm", &forward_pcm_cpu);
+    m.impl("logmel_frames", &logmel_frames_cpu);
+    m.impl("cnn_pool_wide", &cnn_pool_wide_cpu);
+    m.impl("forward_pcm_frames", &forward_pcm_frames_cpu);
 }

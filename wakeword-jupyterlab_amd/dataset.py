@@ -9,7 +9,8 @@ order): the library's reader threads feed kernels K0 / KA / K1 once per batch, y
 
 One deliberate deviation: when a file fails to load the reference substitutes `np.zeros((80, 31))`
 (:210-211), whose width (31) differs from real items (32) and makes `default_collate` raise.  Here the
-substitute is zeros of the real width, [80, 32].
+substitute is zeros of the real width, [80, 32] -- or [80, T] for a processor configured with another DURATION
+(0.25 .. 2 s, inference: items and batches are [1, 80, T] / [B, 1, 80, T], T = 1 + int(16000 * DURATION) // 512).
 
 `augment=True` (the training split, :456) runs AudioProcessor.augment_audio's transforms on the GPU (kernels KA)
 between decode and log-mel: per item in `__getitem__`, per batch in `batches()`.
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from .config import N_FRAMES
+from .config import n_frames
 
 
 class WakewordDataset(Dataset):
@@ -49,7 +50,7 @@ class WakewordDataset(Dataset):
         mel_spec = self.processor.process_audio_file(self.files[idx], augment=self.augment)
         if mel_spec is None:
             self.unreadable += 1
-            mel_spec = np.zeros((self.processor.config.N_MELS, N_FRAMES))
+            mel_spec = np.zeros((self.processor.config.N_MELS, n_frames(self.processor.config)))
         return torch.FloatTensor(np.asarray(mel_spec, dtype=np.float32)).unsqueeze(0), torch.LongTensor([self.labels[idx]])
 
     def batches(self, batch_size=16):
@@ -106,7 +107,7 @@ class GpuBatchLoader:
                 # test datasets, :448-458: validating in the middle of an epoch, zip(train, val)): this iteration gets a reader of its own
                 from .files import WavBatchReader
                 reader = WavBatchReader(max_clips=max(64, self.batch_size), max_raw_bytes=max(64, self.batch_size) * 65536, slots=3,
-                                        device=reader.device)
+                                        device=reader.device, n_samples=reader.n_samples)
             s = 0
             while s < len(files):
                 try:

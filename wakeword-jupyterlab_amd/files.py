@@ -81,15 +81,20 @@ class EncodedPaths:
 
 
 class WavBatchReader:
-    """`read(paths, slot)` (host, blocking) -> `decode(slot)` (GPU, asynchronous) -> device tensor [B, 16000].
+    """`read(paths, slot)` (host, blocking) -> `decode(slot)` (GPU, asynchronous) -> device tensor [B, n_samples].
 
-    max_raw_bytes: sample bytes one batch may hold (16-byte aligned per file); grows on demand in `load()`."""
+    max_raw_bytes: sample bytes one batch may hold (16-byte aligned per file); grows on demand in `load()`.
+    n_samples: the clip length the crops are drawn against and the rows K0 writes: 16000 (1 s), or 4000..32000 for inference at
+    DURATION 0.25 .. 2 (ww_wav_batch_decode_n)."""
 
     def __init__(self, max_clips: int = 4096, max_raw_bytes: int | None = None, threads: int | None = None, slots: int = 2, device=None,
-                 host_only: bool = False):
+                 host_only: bool = False, n_samples: int = CLIP_SAMPLES):
         """host_only=True: staging in ordinary memory and no device twin -- `read()` works without a GPU (tests of the reader
         threads and the RIFF walk), `decode()` raises."""
         self.host_only = bool(host_only)
+        self.n_samples = int(n_samples)
+        if self.n_samples != CLIP_SAMPLES and not 4000 <= self.n_samples <= 32000:
+            raise NotImplementedError(f"WavBatchReader: clips of {self.n_samples} samples; K0 writes 16000, or 4000..32000 (0.25 .. 2 s)")
         if not host_only and not torch.cuda.is_available():
             raise RuntimeError("WavBatchReader feeds the GPU decode kernel (K0) and no GPU is visible (no CPU fallback)")
         self.device = None if host_only else (torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device()))
@@ -160,20 +165,24 @@ class WavBatchReader:
         return np.frombuffer(buf, dtype=DESC_DTYPE, count=n), status[:n]
 
     def decode(self, slot: int = 0, normalize: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
-        """Upload the slot and run K0 on torch's current stream -> [n, 16000] float32 on the device (asynchronous)."""
-        n = self._n[slot]
+        """Upload the slot and run K0 on torch's current stream -> [n, n_samples] float32 on the device (asynchronous)."""
+        n, ns = self._n[slot], self.n_samples
         if self.host_only:
             raise RuntimeError("decode: this reader is host_only (no device twin)")
         if out is None:
-            out = torch.empty((n, CLIP_SAMPLES), device=self.device, dtype=torch.float32)
-        elif out.shape != (n, CLIP_SAMPLES) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f"decode: out must be a contiguous float32 [{n}, {CLIP_SAMPLES}] tensor on {self.device}")
+            out = torch.empty((n, ns), device=self.device, dtype=torch.float32)
+        elif out.shape != (n, ns) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"decode: out must be a contiguous float32 [{n}, {ns}] tensor on {self.device}")
         if self.host_only:
             raise RuntimeError("decode: this reader is host_only (no device twin)")
         if n:
             with torch.cuda.device(self.device):
-                nat.check(nat.lib.ww_wav_batch_decode(self._h, slot, int(bool(normalize)), C.c_void_p(out.data_ptr()),
-                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                if ns == CLIP_SAMPLES:
+                    nat.check(nat.lib.ww_wav_batch_decode(self._h, slot, int(bool(normalize)), C.c_void_p(out.data_ptr()),
+                                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                else:
+                    nat.check(nat.lib.ww_wav_batch_decode_n(self._h, slot, int(bool(normalize)), ns, C.c_void_p(out.data_ptr()),
+                                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return out
 
     @staticmethod
@@ -184,7 +193,7 @@ class WavBatchReader:
             descs["crop_start"][i] = random.randint(0, int(n_out[i]) - n)
 
     def load(self, paths, normalize: bool = True, out: torch.Tensor | None = None, verbose: bool = True, lo: int = 0, hi: int | None = None):
-        """read + crop draw + decode of one batch (`paths[lo:hi]`) on the next slot -> (device tensor [B, 16000], ok mask).
+        """read + crop draw + decode of one batch (`paths[lo:hi]`) on the next slot -> (device tensor [B, n_samples], ok mask).
         Unreadable files give a zero row and ok False, with the reference's message (:70)."""
         self._not_streaming("load")
         hi = len(paths) if hi is None else hi
@@ -200,7 +209,7 @@ class WavBatchReader:
             self._regrow(max(n, self.max_clips), int(e.needed * 1.25) + 4096)
             slot = self.next_slot()
             descs, status = self.read(paths, slot, lo, hi)
-        self.draw_crops(descs, status)
+        self.draw_crops(descs, status, self.n_samples)
         ok = status == 1
         if verbose and not ok.all():
             names = paths.paths if isinstance(paths, EncodedPaths) else paths
@@ -257,7 +266,7 @@ class WavBatchReader:
                 if isinstance(item, BaseException):
                     raise item
                 slot, lo, status, descs = item
-                self.draw_crops(descs, status)            # the slot's descriptors stay writable until decode() uploads them
+                self.draw_crops(descs, status, self.n_samples)            # the slot's descriptors stay writable until decode() uploads them
                 ok = status == 1
                 if verbose and not ok.all():
                     for i in np.nonzero(~ok)[0][:8]:
@@ -281,7 +290,7 @@ class WavBatchReader:
         if not self.host_only:
             torch.cuda.synchronize(self.device)
         self.close()
-        self.__init__(max_clips, max_raw_bytes, self.threads, self.slots, self.device, self.host_only)
+        self.__init__(max_clips, max_raw_bytes, self.threads, self.slots, self.device, self.host_only, self.n_samples)
 
 
 def probe(path) -> dict | None:

@@ -50,7 +50,8 @@ def predict_wakeword(audio_file_path, model, processor, device, threshold=0.8):
 
 
 def evaluate_pcm(model, pcm: torch.Tensor, batch_size: int = 4096, normalize: bool = True):
-    """PCM [N, n<=16000] on the device -> (logits [N,2], predictions [N]) in batches of `batch_size`."""
+    """PCM [N, n<=16000] on the device (n <= the model's clip length for a model built with another DURATION) -> (logits [N,2], predictions [N])
+    in batches of `batch_size`."""
     model.eval()
     outs = []
     with torch.no_grad():

@@ -20,11 +20,11 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .config import AudioConfig, Config, ModelConfig
+from .config import CLIP_SAMPLES, AudioConfig, Config, ModelConfig, n_frames, n_samples
 
 
 class _CnnLstm(nn.Module):
-    def __init__(self, channels, hidden, num_layers, dropout, num_classes):
+    def __init__(self, channels, hidden, num_layers, dropout, num_classes, audio_config=AudioConfig):
         super().__init__()
         if hidden != 256 or num_layers != 2 or num_classes != 2:
             raise NotImplementedError("the HIP head is built for hidden 256, 2 LSTM layers, 2 classes (the reference configs)")
@@ -36,6 +36,9 @@ class _CnnLstm(nn.Module):
         self.dropout = nn.Dropout(dropout)
         self.fc = nn.Linear(hidden, num_classes)
         self._n_conv = len(channels) - 1
+        # clip length (inference at 0.25 .. 2 s): forward takes T <= max(32, T of the config), forward_pcm rows of <= N samples
+        self._n_samples = n_samples(audio_config)
+        self._max_width = max(32, n_frames(audio_config))
         self._packed = None
         self._packed_key = None
 
@@ -55,6 +58,12 @@ class _CnnLstm(nn.Module):
         return self._packed
 
     def forward(self, x):
+        wide = x.dim() == 4 and 32 < x.shape[3] <= self._max_width
+        if wide and self.training:
+            raise NotImplementedError(f"training at T = {x.shape[3]} frames is not supported yet: the training kernels take 1..32 "
+                                      "(clips of up to 1 s); clips of up to 2 s run in eval mode only")
+        if wide:
+            return ops.lstm_fc(ops.cnn_pool_wide(x, self.packed_weights(), self._n_conv), self.packed_weights(), self._n_conv)
         if self.training:
             if self.fc.weight.device.type != "cuda":
                 raise RuntimeError("model parameters are on the CPU: this path has no CPU implementation; call .to('cuda')")
@@ -65,24 +74,29 @@ class _CnnLstm(nn.Module):
         return ops.cnn_lstm_forward(x, self.packed_weights(), self._n_conv)
 
     def forward_pcm(self, pcm, normalize: bool = True):
-        """PCM [B, n<=16000] -> logits [B, 2]: the Dataset's mel path and forward() in one call (boundary B3)."""
+        """PCM [B, n<=N] -> logits [B, 2]: the Dataset's mel path and forward() in one call (boundary B3).  N = 16000, or the clip
+        length of the model's audio_config."""
         if self.training:
             raise NotImplementedError("call model.eval() first")
-        return ops.forward_pcm(pcm, self.packed_weights(), self._n_conv, normalize)
+        if self._n_samples == CLIP_SAMPLES:
+            return ops.forward_pcm(pcm, self.packed_weights(), self._n_conv, normalize)
+        return ops.forward_pcm_frames(pcm, self.packed_weights(), self._n_conv, self._n_samples, normalize)
 
 
 class SimpleWakewordModel(_CnnLstm):
-    """train_wakeword.py:28-36: Conv(1,32) Conv(32,64) pool LSTM(64,256,2,dropout .5) Linear(256,2)."""
+    """train_wakeword.py:28-36: Conv(1,32) Conv(32,64) pool LSTM(64,256,2,dropout .5) Linear(256,2).
+    `audio_config` (not in the reference's signature, keyword only): the clip length the model takes in eval mode, default 1 s."""
 
-    def __init__(self):
-        super().__init__([1, 32, 64], Config.HIDDEN_SIZE, Config.NUM_LAYERS, Config.DROPOUT, 2)
+    def __init__(self, *, audio_config=AudioConfig):
+        super().__init__([1, 32, 64], Config.HIDDEN_SIZE, Config.NUM_LAYERS, Config.DROPOUT, 2, audio_config)
+        self.audio_config = audio_config
 
 
 class WakewordModel(_CnnLstm):
     """wakeword_training_script.py:141-165: three convs (1,32,64,128), LSTM(128,256,2,dropout .6)."""
 
     def __init__(self, config=ModelConfig, audio_config=AudioConfig):
-        super().__init__([1, 32, 64, 128], config.HIDDEN_SIZE, config.NUM_LAYERS, config.DROPOUT, config.NUM_CLASSES)
+        super().__init__([1, 32, 64, 128], config.HIDDEN_SIZE, config.NUM_LAYERS, config.DROPOUT, config.NUM_CLASSES, audio_config)
         self.config = config
         self.audio_config = audio_config
         self.mel_height = audio_config.N_MELS

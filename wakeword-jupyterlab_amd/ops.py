@@ -194,7 +194,7 @@ def _forward_pcm_impl(pcm: torch.Tensor, packed: torch.Tensor, n_conv: int, norm
 # section 7 step 2).  The CUDA kernels validate, allocate with ATen and call the C ABI on torch's current stream; the Meta kernels give
 # shapes only (FakeTensor / torch.compile tracing of the drop-in modules); the CPU kernels refuse.  Rounds 1-3 registered the Python
 # functions above through torch.library; those stay as plain functions (`_logmel_impl` ...: tests and the raw launches of bench.py's legs).
-# The library does not link libwakeword_amd.so: it is handed the addresses of the nine C ABI functions it calls.
+# The library does not link libwakeword_amd.so: it is handed the addresses of the fourteen C ABI functions it calls.
 # No fallback: without the compiled library the package does not import.
 import os as _os_ops
 
@@ -205,7 +205,9 @@ if not _os_ops.path.exists(TORCH_LIB_PATH):
 torch.ops.load_library(TORCH_LIB_PATH)
 # bind the operators to THE copy of libwakeword_amd.so this process uses (the shipped one or a WW_LIB_OVERRIDE build): addresses, not names
 _TORCH_BIND_ORDER = ("ww_last_error", "ww_packed_weights_floats", "ww_cnn_scratch_bytes", "ww_workspace_bytes", "ww_logmel_f32",
-                     "ww_cnn_pool_f32", "ww_lstm_fc_f32", "ww_model_forward_f32", "ww_forward_pcm_f32")
+                     "ww_cnn_pool_f32", "ww_lstm_fc_f32", "ww_model_forward_f32", "ww_forward_pcm_f32",
+                     "ww_logmel_frames_f32", "ww_cnn_wide_scratch_bytes", "ww_cnn_pool_wide_f32", "ww_workspace_frames_bytes",
+                     "ww_forward_pcm_frames_f32")
 _torch_lib = C.CDLL(TORCH_LIB_PATH)
 _table = (C.c_void_p * len(_TORCH_BIND_ORDER))(*[C.cast(getattr(nat.lib, _n), C.c_void_p).value for _n in _TORCH_BIND_ORDER])
 if _torch_lib.ww_torch_bind(_table, len(_TORCH_BIND_ORDER)) != 0:
@@ -261,6 +263,52 @@ def forward_pcm(pcm, packed, n_conv, normalize: bool = True):
     _precheck_pcm(pcm)
     _check_packed(packed, n_conv, pcm)
     return torch.ops.wakeword_amd.forward_pcm(pcm, packed, n_conv, bool(normalize))
+
+
+# ---- clips of 0.25 s .. 2 s (inference): torch.ops.wakeword_amd.{logmel_frames,cnn_pool_wide,forward_pcm_frames} ----
+MAX_FRAMES = 63                         # 1 + 32000 // 512
+MIN_CLIP_SAMPLES, MAX_CLIP_SAMPLES = 4000, 32000
+
+
+def frames_of(n_samples: int) -> int:
+    if not MIN_CLIP_SAMPLES <= int(n_samples) <= MAX_CLIP_SAMPLES:
+        raise NotImplementedError(f"clips of {n_samples} samples: the front-end takes {MIN_CLIP_SAMPLES}..{MAX_CLIP_SAMPLES} (0.25 s .. 2 s)")
+    return 1 + int(n_samples) // 512
+
+
+def _precheck_pcm_frames(pcm, n_samples: int) -> None:
+    frames_of(n_samples)
+    _require_cuda_f32(pcm, "pcm")
+    if pcm.dim() != 2:
+        raise ValueError(f"pcm: expected [B, samples], got {tuple(pcm.shape)}")
+    if pcm.shape[1] == 0 or pcm.shape[1] > n_samples:
+        raise ValueError(f"pcm: {pcm.shape[1]} samples per clip; this clip length takes 1..{n_samples} (crop longer clips on the host)")
+
+
+def logmel_frames(pcm: torch.Tensor, n_samples: int, normalize: bool = True) -> torch.Tensor:
+    """pcm [B, n <= n_samples] -> [B, 1, 80, T], T = 1 + n_samples // 512: the log-mel of clips zero-padded to n_samples.
+    n_samples = 16000 gives exactly `logmel`'s result."""
+    _precheck_pcm_frames(pcm, n_samples)
+    return torch.ops.wakeword_amd.logmel_frames(pcm, int(n_samples), bool(normalize))
+
+
+def cnn_pool_wide(x, packed, n_conv):
+    """x [B, 1, 80, T], 1 <= T <= 63 -> pooled features [B, C_last].  T <= 32 gives exactly `cnn_pool`'s result; wider images run the
+    32-wide conv kernels over overlapping column tiles (csrc/ww_cnn.hip, ColTiling)."""
+    _require_cuda_f32(x, "x")
+    if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != N_MELS:
+        raise ValueError(f"x: expected [B, 1, {N_MELS}, T], got {tuple(x.shape)}")
+    if not 1 <= x.shape[3] <= MAX_FRAMES:
+        raise NotImplementedError(f"x: T = {x.shape[3]} frames; the conv kernels take 1..{MAX_FRAMES} (2 s clips give 63)")
+    _check_packed(packed, n_conv, x)
+    return torch.ops.wakeword_amd.cnn_pool_wide(x, packed, n_conv)
+
+
+def forward_pcm_frames(pcm, packed, n_conv, n_samples: int, normalize: bool = True):
+    """pcm [B, n <= n_samples] -> logits [B, 2]: logmel_frames -> cnn_pool_wide -> lstm_fc in one native call."""
+    _precheck_pcm_frames(pcm, n_samples)
+    _check_packed(packed, n_conv, pcm)
+    return torch.ops.wakeword_amd.forward_pcm_frames(pcm, packed, n_conv, int(n_samples), bool(normalize))
 
 
 # ------------------------------------------------------------------------------------------------

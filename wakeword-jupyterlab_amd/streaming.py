@@ -21,6 +21,8 @@ class StreamingDetector:
     def __init__(self, model, n_mics: int = 256, hop_samples: int = 160, threshold: float = 0.8, device=None):
         if model.training:
             raise NotImplementedError("call model.eval() first")
+        if getattr(model, "_n_samples", CLIP_SAMPLES) != CLIP_SAMPLES:
+            raise NotImplementedError(f"streaming runs 1 s windows only; this model is built for clips of {model._n_samples} samples")
         self.device = torch.device(device) if device is not None else model.fc.weight.device
         if self.device.type != "cuda":
             raise RuntimeError("StreamingDetector needs the model on the MI355X (no CPU path)")
