@@ -79,6 +79,11 @@ WW_API int ww_device_info(int* n_cu, int* clock_khz, char* name, int name_len);
  * A workgroup whose wait expired overwrites every output it produced with NaN before it exits, so a broken launch
  * cannot be consumed silently even without this call. */
 WW_API int ww_sync_timeouts(void);
+/* Health check (synchronises the device): how many FLAC files since the library was loaded had CRCs that verified but a bitstream the
+ * decoder could not follow (reserved codes, a negative LPC shift, a residual layout the block does not allow, a sample outside its bit
+ * width, subframes running past the frame).  Each such file was decoded to a zero row; its `ok` flag (decided on the host) stays True.
+ * 0 for files any conforming encoder writes; negative = error code. */
+WW_API int ww_flac_errors(void);
 
 /* Arithmetic of the implicit GEMMs (conv1/conv2/conv3 and the LSTM gate GEMMs: all but ~1 % of the model's flops);
  * process-wide, default F16X3.
@@ -142,6 +147,10 @@ WW_API int ww_hann_window_host(float* out_host);
 #define WW_FMT_F32 4
 #define WW_FMT_U8 5
 #define WW_FMT_F64 6 /* IEEE double samples (WAVE_FORMAT_IEEE_FLOAT, 64 bits): rounded to float32 as soundfile does for dtype float32 */
+#define WW_FMT_FLAC 7 /* a FLAC file (RFC 9639, 4..24 bits, 1..8 channels) as the reader and the probe report it; byte_offset = its first
+                         frame.  ww_wav_batch_decode decodes it on the device to float32 x * 2^-(bps-1) (what a WAV of the same integers
+                         gives) and K0 reads that as WW_FMT_F32.  K0 itself does not decode it: a descriptor that still says
+                         WW_FMT_FLAC gives a zero row and no sample byte is read. */
 typedef struct ww_clip_desc {
     int64_t byte_offset;  /* start of the interleaved sample data of this file inside raw_dev */
     int64_t n_frames;     /* sample frames in the file */
@@ -177,15 +186,21 @@ WW_API int ww_decode_resample_n(const uint8_t* raw_dev, const ww_clip_desc* desc
  *                           caller's draw: n_out = ceil(n_frames * up / down) is known now).  status_host[i] = 1, or a
  *                           WW_WAV_E* code for a file that could not be used (the reference prints and substitutes
  *                           zeros, :66-71, :210-211: such a file decodes to a zero clip here).  Blocks until the slot's
- *                           previous upload has left the staging buffer.
- *   ww_wav_batch_decode     H2D copy of the slot on the reader's copy stream, then K0 (ww_decode_resample) on `stream`
+ *                           previous upload has left the staging buffer.  A FLAC file (magic "fLaC", an ID3v2 tag may precede
+ *                           it) is staged as its frames plus a frame index built here (every CRC-8 and CRC-16 verified, no
+ *                           sample decoded); its descriptor says WW_FMT_FLAC, and its decoded float32 samples count against
+ *                           the same max_raw_bytes in a device-only region (WW_ENOSPACE reports the larger of the two needs).
+ *   ww_wav_batch_decode     H2D copy of the slot on the reader's copy stream, then (only when the slot holds FLAC files) the
+ *                           FLAC decode kernel, then K0 (ww_decode_resample) on `stream`
  *                           behind it: pcm_out_dev [n][16000].  Asynchronous; the next ww_read_wav_batch_host on ANOTHER
  *                           slot overlaps with it.  The upload of a slot waits for the K0 that last read its device twin.
  * A reader serves ONE caller at a time (its thread pool runs one batch); use one reader per consumer thread. */
 #define WW_WAV_EOPEN (-1)    /* cannot open */
-#define WW_WAV_ENOTRIFF (-2) /* not a RIFF/WAVE file */
-#define WW_WAV_ECHUNK (-3)   /* fmt or data chunk missing / truncated */
-#define WW_WAV_EFORMAT (-4)  /* encoding K0 does not take (it takes PCM u8/s16/s24/s32 and float32/float64), or an absurd rate */
+#define WW_WAV_ENOTRIFF (-2) /* neither a RIFF/WAVE nor a FLAC file */
+#define WW_WAV_ECHUNK (-3)   /* fmt or data chunk missing / truncated; FLAC: STREAMINFO missing, a frame header or CRC-16 that does not
+                                verify, a truncated frame */
+#define WW_WAV_EFORMAT (-4)  /* encoding K0 does not take (it takes PCM u8/s16/s24/s32 and float32/float64, FLAC of 4..24 bits), or an
+                                absurd rate */
 #define WW_WAV_EIO (-5)      /* read error */
 #define WW_WAV_ESPACE (-6)   /* the staging buffer was full (the call then returns WW_ENOSPACE with the size needed) */
 typedef struct ww_wav_reader ww_wav_reader;
@@ -197,7 +212,8 @@ WW_API int ww_wav_reader_destroy(ww_wav_reader* r);
 /* The slot's staging buffer as the last ww_read_wav_batch_host left it (descs[i].byte_offset points into it); for tests. */
 WW_API int ww_wav_reader_staging(ww_wav_reader* r, int32_t slot, const uint8_t** raw_host_out, int64_t* raw_bytes_out);
 /* One file's header only (no GPU needed): returns 1 and fills n_frames / channels / sample_rate / format / up / down / half_len, with
- * byte_offset = the position of the sample data INSIDE THE FILE; or a WW_WAV_E* code. */
+ * byte_offset = the position of the sample data INSIDE THE FILE; or a WW_WAV_E* code.  A FLAC file is scanned whole (its frame index
+ * gives n_frames): format = WW_FMT_FLAC, byte_offset = its first frame. */
 WW_API int ww_wav_probe_host(const char* path, ww_clip_desc* desc_host);
 /* raw_bytes_out (may be NULL): sample bytes of the batch, 16-byte aligned per file; on WW_ENOSPACE the size to create a reader with. */
 WW_API int ww_read_wav_batch_host(ww_wav_reader* r, const char* const* paths, int64_t n, int32_t slot, ww_clip_desc** descs_host_out,
@@ -205,6 +221,13 @@ WW_API int ww_read_wav_batch_host(ww_wav_reader* r, const char* const* paths, in
 WW_API int ww_wav_batch_decode(ww_wav_reader* r, int32_t slot, int normalize, float* pcm_out_dev, ww_stream_t stream);
 /* ww_wav_batch_decode with rows of n_samples (as ww_decode_resample_n): pcm_out_dev [n][n_samples]. */
 WW_API int ww_wav_batch_decode_n(ww_wav_reader* r, int32_t slot, int normalize, int64_t n_samples, float* pcm_out_dev, ww_stream_t stream);
+/* The upload half of ww_wav_batch_decode, for a caller that runs K0 itself on windows of its own (AudioProcessor.load_audio): the slot's
+ * H2D and, when it holds FLAC files, their decode on `stream`; then (synchronous) descs_out [n] receives the slot's descriptors as K0
+ * takes them -- a FLAC file as WW_FMT_F32 at its decoded samples, n_frames 0 when its bitstream was inconsistent -- and *raw_dev_out the
+ * device buffer their byte_offsets index.  Both stay valid until the next ww_read_wav_batch_host of the slot; whatever the caller
+ * launches on them must have finished before the slot's next ww_wav_batch_decode / _stage.  The descriptors ww_read_wav_batch_host
+ * returned are not changed by either call (a FLAC file keeps WW_FMT_FLAC and its staging offset there). */
+WW_API int ww_wav_batch_stage(ww_wav_reader* r, int32_t slot, ww_stream_t stream, const uint8_t** raw_dev_out, ww_clip_desc* descs_out);
 
 /* ---- KA: training-time augmentation ------------------------------ */
 /* Replaces AudioProcessor.augment_audio (wakeword_training_script.py:103-123): np.roll time shift ->

@@ -74,8 +74,9 @@ class AugmentPlan(C.Structure):
     ]
 
 
-FMT_S16, FMT_S24, FMT_S32, FMT_F32, FMT_U8, FMT_F64 = 1, 2, 3, 4, 5, 6
-WAV_STATUS = {1: "ok", -1: "cannot open", -2: "not a RIFF/WAVE file", -3: "missing fmt/data chunk", -4: "unsupported WAV encoding",
+FMT_S16, FMT_S24, FMT_S32, FMT_F32, FMT_U8, FMT_F64, FMT_FLAC = 1, 2, 3, 4, 5, 6, 7
+WAV_STATUS = {1: "ok", -1: "cannot open", -2: "not a RIFF/WAVE or FLAC file",
+              -3: "missing fmt/data chunk, or a damaged FLAC stream (STREAMINFO, frame header or CRC)", -4: "unsupported WAV / FLAC encoding",
               -5: "read error", -6: "staging buffer full"}
 
 # name -> (restype, argtypes); kept in one table so tests can check it against the header
@@ -93,6 +94,7 @@ PROTOTYPES = {
     "ww_get_logmel_math": (C.c_int, []),
     "ww_device_info": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "ww_sync_timeouts": (C.c_int, []),
+    "ww_flac_errors": (C.c_int, []),
     "ww_mel_filterbank_host": (C.c_int, [C.c_void_p]),
     "ww_hann_window_host": (C.c_int, [C.c_void_p]),
     "ww_resample_taps_host": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -106,6 +108,7 @@ PROTOTYPES = {
                                          C.POINTER(C.c_int64)]),
     "ww_wav_batch_decode": (C.c_int, [C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p]),
     "ww_wav_batch_decode_n": (C.c_int, [C.c_void_p, C.c_int32, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ww_wav_batch_stage": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
     "ww_decode_resample_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "ww_augment_workspace_bytes": (C.c_int64, [C.c_int64]),
     "ww_augment_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(AugmentPlan), C.c_void_p, C.c_void_p, C.c_void_p]),

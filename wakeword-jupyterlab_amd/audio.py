@@ -16,7 +16,7 @@ refuses other durations.
                                  (random draws from python `random` in the reference's order)  <- HIP kernels KA
 `load_audio` / `process_audio_file` read the file with the library's native reader (csrc/ww_files.cpp) and decode, mix down and
 resample it on the GPU (kernel K0: scipy.signal.resample_poly's Kaiser design -- NOT librosa's soxr resampler, an absent third-party
-library: parity unpinned) -- the same code path as the batched loaders, one file at a time.  PCM / float WAV only.
+library: parity unpinned) -- the same code path as the batched loaders, one file at a time.  PCM / float WAV and FLAC.
 """
 from __future__ import annotations
 
@@ -69,16 +69,24 @@ class AudioProcessor:
             if n_out == 0:
                 return np.zeros(0, dtype=np.float32)
             n_win = -(-n_out // CLIP_SAMPLES)
-            win = np.repeat(np.asarray(descs[:1]), n_win)                        # a copy: same bytes, same filter, one window each
-            win["crop_start"] = np.arange(n_win, dtype=np.int64) * CLIP_SAMPLES
             dev = self._dev()
             with torch.cuda.device(dev):
-                raw_dev = torch.from_numpy(rd.staging(slot)).to(dev)
+                stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+                if int(descs["format"][0]) == nat.FMT_FLAC:
+                    # FLAC: the reader uploads the frames and decodes them on the device; K0 then reads the float32 samples it points at
+                    staged = np.zeros(1, dtype=DESC_DTYPE)
+                    raw_p = C.c_void_p()
+                    nat.check(nat.lib.ww_wav_batch_stage(rd._h, slot, stream, C.byref(raw_p), staged.ctypes.data))
+                    src, raw_dev = staged, None
+                else:
+                    raw_dev = torch.from_numpy(rd.staging(slot)).to(dev)
+                    src, raw_p = descs[:1], C.c_void_p(raw_dev.data_ptr())
+                win = np.repeat(np.asarray(src), n_win)                          # a copy: same bytes, same filter, one window each
+                win["crop_start"] = np.arange(n_win, dtype=np.int64) * CLIP_SAMPLES
                 descs_dev = torch.from_numpy(win.view(np.uint8).reshape(n_win, DESC_DTYPE.itemsize)).to(dev)
                 out = torch.empty((n_win, CLIP_SAMPLES), device=dev, dtype=torch.float32)
-                nat.check(nat.lib.ww_decode_resample(C.c_void_p(raw_dev.data_ptr()), C.c_void_p(descs_dev.data_ptr()), n_win, 0,
-                                                     C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-                audio = out.reshape(-1)[:n_out].cpu().numpy()
+                nat.check(nat.lib.ww_decode_resample(raw_p, C.c_void_p(descs_dev.data_ptr()), n_win, 0, C.c_void_p(out.data_ptr()), stream))
+                audio = out.reshape(-1)[:n_out].cpu().numpy()      # (synchronises: the slot's device buffer is free again)
             return np.ascontiguousarray(audio, dtype=np.float32)
         except Exception as e:                                             # reference: print and return None (:66-71)
             print(f"Error loading {file_path}: {e}")

@@ -240,6 +240,14 @@ int ww_sync_timeouts(void) {
     return int(c > 0x7fffffffu ? 0x7fffffffu : c);
 }
 
+int ww_flac_errors(void) {
+    if (int rc = require_gfx950()) return rc;
+    WW_HIP(hipDeviceSynchronize());
+    unsigned int c = 0;
+    if (int rc = flac_errors(&c)) return rc;
+    return int(c > 0x7fffffffu ? 0x7fffffffu : c);
+}
+
 int ww_device_info(int* n_cu, int* clock_khz, char* name, int name_len) {
     if (int rc = require_gfx950()) return rc;
     int dev = 0;

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_lds_kernel(const uint8_t*
         const int up = d.up, down = d.down, half_len = d.half_len;
         if (!resample_in_lds(up, down, half_len)) continue;
         const uint8_t* __restrict__ p = raw + d.byte_offset;
-        const int64_t n_in = d.n_frames;
+        const int64_t n_in = d.format == WW_FMT_FLAC ? 0 : d.n_frames;   // compressed FLAC bytes are no samples: a zero row, nothing read
         const int lh = 2 * half_len + 1;
         if (d.taps_dev != taps_loaded) {                          // consecutive files usually share their rate
             __syncthreads();
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void decode_resample_kernel(const uint8_t* __r
 #endif
         const uint8_t* __restrict__ p = raw + d.byte_offset;
         const float* __restrict__ taps = reinterpret_cast<const float*>(d.taps_dev);
-        const int64_t n_in = d.n_frames;
+        const int64_t n_in = d.format == WW_FMT_FLAC ? 0 : d.n_frames;   // (see resample_lds_kernel)
         const int up = d.up, down = d.down, half_len = d.half_len;
         int64_t n_out = n_in * up;
         n_out = n_out / down + (n_out % down ? 1 : 0);

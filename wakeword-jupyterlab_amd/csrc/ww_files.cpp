@@ -55,6 +55,12 @@ static bool fetch(int fd, const uint8_t* win, int64_t win_len, int64_t pos, int6
     return true;
 }
 
+}  // namespace ww
+
+#include "ww_flac_index.h"   // FLAC container walk and frame index (uses fetch above)
+
+namespace ww {
+
 // RIFF/WAVE chunk walk: the last `fmt ` and the last `data` chunk win, odd chunk sizes are padded, a data chunk longer
 // than the file is cut at the end of the file (the host reader of audio.py walks the same way).  `win` holds the first
 // win_len bytes of the file; anything beyond is fetched with pread.
@@ -132,11 +138,18 @@ static int format_of(const WavInfo& w) {
 struct Slot {
     uint8_t* raw_host = nullptr;          // pinned
     ww_clip_desc* descs_host = nullptr;   // pinned
-    uint8_t* raw_dev = nullptr;
+    uint8_t* raw_dev = nullptr;           // max_raw bytes of staging twin; once the slot has held FLAC files, max_raw more for their samples
     ww_clip_desc* descs_dev = nullptr;
     hipEvent_t copied = nullptr, decoded = nullptr;
     bool copy_inflight = false, decode_inflight = false;
     int64_t n = 0, raw_bytes = 0;
+    // FLAC files of the batch (ww_flac_index.h / ww_flac.hip): filled by the reader threads, uploaded by ww_wav_batch_decode
+    std::vector<FlacClip> flac;
+    int64_t n_flac = 0, flac_frames = 0;
+    bool dec_space = false;               // raw_dev holds the decoded-sample region
+    FlacClip* flac_host = nullptr;        // pinned, max_clips (allocated with the first FLAC batch)
+    FlacClip* flac_dev = nullptr;
+    ww_clip_desc* descs_k0_host = nullptr;   // pinned, max_clips: the descriptors as uploaded when the batch holds FLAC files
 };
 
 struct Job {
@@ -146,6 +159,7 @@ struct Job {
     int8_t* status = nullptr;
     std::atomic<int64_t> next{0}, cursor{0};
     int64_t capacity = 0;
+    std::atomic<int64_t> dec_cursor{0}, n_flac{0};   // FLAC: decoded float32 bytes reserved (capacity: the same max_raw), files
 };
 
 }  // namespace ww
@@ -197,6 +211,66 @@ static void copy_to_staging(uint8_t* dst, const uint8_t* src, size_t n) {
 #endif
 }
 
+// A FLAC file: the frames (file bytes from the first frame on) go to staging, then the frame index behind them, and the decoded samples get
+// a reservation in the device-only region; the descriptor says WW_FMT_FLAC until ww_wav_batch_decode points it at the decoded samples.
+static int read_flac(Job* j, int64_t i, int fd, int64_t fsize, const uint8_t* win, int64_t win_len, ww_clip_desc* d) {
+    FlacHead h;
+    int st = flac_parse_head(fd, fsize, win, win_len, &h);
+    if (st != 1) return st;
+    const int64_t len = fsize - h.audio_start;
+    if (len < 8) return WW_WAV_ECHUNK;
+    static thread_local std::vector<FlacFrame> frames;
+    int64_t n_samples = 0;
+    const int64_t aligned = (len + 15) & ~int64_t(15);
+    const bool in_window = h.audio_start + len <= win_len;
+    if (in_window) {                                          // scan the bytes where they are warm, copy them once they are known good
+        if ((st = flac_index(win + h.audio_start, len, h, &frames, &n_samples)) != 1) return st;
+    }
+    // every reservation is made whether the earlier ones fitted or not: WW_ENOSPACE then reports what the whole batch needs
+    const int64_t off = j->cursor.fetch_add(aligned, std::memory_order_relaxed);
+    const bool fits = off + aligned <= j->capacity;
+    uint8_t* dst = fits ? j->slot->raw_host + off : nullptr;
+    int64_t have = len;
+    if (in_window) {
+        if (fits) copy_to_staging(dst, win + h.audio_start, size_t(len));
+    } else {
+        std::vector<uint8_t> spill;                           // no room in staging: read it aside, only to size the batch
+        uint8_t* buf = dst;
+        if (!fits) {
+            if (len > (int64_t(1) << 28)) return WW_WAV_ESPACE;          // (beyond 256 MB the report covers the bytes alone)
+            spill.resize(size_t(len));
+            buf = spill.data();
+        }
+        int64_t got = 0;
+        if (h.audio_start < win_len) {
+            got = win_len - h.audio_start;
+            std::memcpy(buf, win + h.audio_start, size_t(got));
+        }
+        while (got < len) {
+            const ssize_t r = pread(fd, buf + got, size_t(len - got), off_t(h.audio_start + got));
+            if (r <= 0) break;
+            got += r;
+        }
+        have = got;                                           // a file cut under us: its last frame fails the CRC-16
+        if ((st = flac_index(buf, have, h, &frames, &n_samples)) != 1) return st;
+    }
+    if (fits) std::memset(dst + have, 0, size_t(aligned - have));
+    const int64_t fbytes = int64_t(frames.size() * sizeof(FlacFrame));
+    const int64_t foff = j->cursor.fetch_add(fbytes, std::memory_order_relaxed);
+    // the decoded size comes from the index of the bytes actually read, never from STREAMINFO
+    const int64_t dbytes = (n_samples * h.channels * int64_t(sizeof(float)) + 15) & ~int64_t(15);
+    const int64_t doff = j->dec_cursor.fetch_add(dbytes, std::memory_order_relaxed);
+    if (!fits || foff + fbytes > j->capacity || doff + dbytes > j->capacity) return WW_WAV_ESPACE;
+    std::memcpy(j->slot->raw_host + foff, frames.data(), size_t(fbytes));
+    FlacClip c;
+    std::memset(&c, 0, sizeof c);
+    c.comp_off = off; c.frames_off = foff; c.dec_off = doff; c.n_blocks = int32_t(frames.size()); c.clip = int32_t(i);
+    c.channels = h.channels; c.bps = h.bps;
+    j->slot->flac[size_t(j->n_flac.fetch_add(1, std::memory_order_relaxed))] = c;
+    d->byte_offset = off; d->n_frames = n_samples; d->channels = h.channels; d->sample_rate = h.sample_rate; d->format = WW_FMT_FLAC;
+    return 1;
+}
+
 static void read_one(Job* j, int64_t i, uint8_t* win) {
     ww_clip_desc d;
     std::memset(&d, 0, sizeof d);
@@ -207,8 +281,8 @@ static void read_one(Job* j, int64_t i, uint8_t* win) {
         WavInfo w;
         int64_t fsize = 0;
         const int64_t win_len = read_head(fd, win, &fsize);
-        st = win_len < 0 ? WW_WAV_EIO : parse_wav(fd, fsize, win, win_len, &w);
-        if (st == 1) {
+        st = win_len < 0 ? WW_WAV_EIO : flac_magic(win, win_len) ? read_flac(j, i, fd, fsize, win, win_len, &d) : parse_wav(fd, fsize, win, win_len, &w);
+        if (st == 1 && d.format != WW_FMT_FLAC) {
             const int fmt = format_of(w);
             if (!fmt || w.channels < 1 || w.sample_rate < 1000 || w.sample_rate > 384000) st = WW_WAV_EFORMAT;
             else {
@@ -321,8 +395,59 @@ static void free_slots(ww_wav_reader* r) {
         if (s.descs_host) (void)hipHostFree(s.descs_host);
         if (s.raw_dev) (void)hipFree(s.raw_dev);
         if (s.descs_dev) (void)hipFree(s.descs_dev);
+        if (s.flac_host) (void)hipHostFree(s.flac_host);
+        if (s.flac_dev) (void)hipFree(s.flac_dev);
+        if (s.descs_k0_host) (void)hipHostFree(s.descs_k0_host);
     }
     r->slots.clear();
+}
+
+// H2D of a slot on the copy stream and, when it holds FLAC files, their decode on `st` behind it: afterwards descs_dev describes every
+// file as K0 takes it.  The FLAC files' descriptors are rewritten (WW_FMT_F32 at their decoded samples) in a copy of their own, so that
+// the descriptors ww_read_wav_batch_host handed out keep saying what the file is.
+static int upload_slot(ww_wav_reader* r, Slot& s, hipStream_t st) {
+    const ww_clip_desc* descs_up = s.descs_host;
+    if (s.n_flac) {
+        // first FLAC batch of this slot: the device twin gets the decoded-sample region behind the staging, the file table and the
+        // rewritten descriptors their buffers
+        if (!s.dec_space) {
+            if (s.decode_inflight) WW_HIP(hipEventSynchronize(s.decoded));
+            WW_HIP(hipFree(s.raw_dev));
+            s.raw_dev = nullptr;
+            WW_HIP(hipMalloc(reinterpret_cast<void**>(&s.raw_dev), size_t(2 * r->max_raw)));
+            s.dec_space = true;
+        }
+        if (!s.flac_host) {
+            WW_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.flac_host), sizeof(FlacClip) * size_t(r->max_clips), hipHostMallocDefault));
+            WW_HIP(hipMalloc(reinterpret_cast<void**>(&s.flac_dev), sizeof(FlacClip) * size_t(r->max_clips)));
+            WW_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.descs_k0_host), sizeof(ww_clip_desc) * size_t(r->max_clips), hipHostMallocDefault));
+        }
+        if (s.copy_inflight) {                                  // (a second decode of the same batch) the last upload still reads flac_host
+            WW_HIP(hipEventSynchronize(s.copied));
+            s.copy_inflight = false;
+        }
+        std::memcpy(s.descs_k0_host, s.descs_host, sizeof(ww_clip_desc) * size_t(s.n));
+        for (int64_t k = 0; k < s.n_flac; ++k) {
+            FlacClip c = s.flac[size_t(k)];
+            c.dec_off += r->max_raw;
+            s.flac_host[k] = c;
+            ww_clip_desc& d = s.descs_k0_host[c.clip];
+            d.format = WW_FMT_F32;
+            d.byte_offset = c.dec_off;
+        }
+        descs_up = s.descs_k0_host;
+    }
+    if (s.decode_inflight) WW_HIP(hipStreamWaitEvent(r->copy_stream, s.decoded, 0));   // K0 of the previous batch still reads raw_dev
+    if (s.raw_bytes) WW_HIP(hipMemcpyAsync(s.raw_dev, s.raw_host, size_t(s.raw_bytes), hipMemcpyHostToDevice, r->copy_stream));
+    WW_HIP(hipMemcpyAsync(s.descs_dev, descs_up, sizeof(ww_clip_desc) * size_t(s.n), hipMemcpyHostToDevice, r->copy_stream));
+    if (s.n_flac)
+        WW_HIP(hipMemcpyAsync(s.flac_dev, s.flac_host, sizeof(FlacClip) * size_t(s.n_flac), hipMemcpyHostToDevice, r->copy_stream));
+    WW_HIP(hipEventRecord(s.copied, r->copy_stream));
+    s.copy_inflight = true;
+    WW_HIP(hipStreamWaitEvent(st, s.copied, 0));
+    if (s.n_flac)                                              // FLAC files -> float32 samples, then K0 reads them like any float WAV
+        if (int rc = launch_flac_decode(s.raw_dev, s.flac_dev, int(s.n_flac), s.flac_frames, s.descs_dev, st)) return rc;
+    return WW_OK;
 }
 
 }  // namespace ww
@@ -338,6 +463,27 @@ int ww_wav_probe_host(const char* path, ww_clip_desc* desc_host) {
     alignas(16) uint8_t win[kHeadWindow];
     int64_t fsize = 0;
     const int64_t win_len = read_head(fd, win, &fsize);
+    if (win_len >= 0 && flac_magic(win, win_len)) {            // FLAC: the frame index gives n_frames; byte_offset = the first frame
+        FlacHead h;
+        int st = flac_parse_head(fd, fsize, win, win_len, &h);
+        if (st == 1) {
+            const int64_t len = fsize - h.audio_start;
+            std::vector<uint8_t> a(size_t(len > 0 ? len : 0));
+            std::vector<FlacFrame> frames;
+            int64_t n_samples = 0;
+            st = len < 8 || !fetch(fd, win, win_len, h.audio_start, len, a.data()) ? WW_WAV_ECHUNK : flac_index(a.data(), len, h, &frames, &n_samples);
+            if (st == 1) {
+                desc_host->byte_offset = h.audio_start;
+                desc_host->n_frames = n_samples;
+                desc_host->channels = h.channels;
+                desc_host->sample_rate = h.sample_rate;
+                desc_host->format = WW_FMT_FLAC;
+                (void)ww_resample_taps_host(h.sample_rate, nullptr, 0, &desc_host->up, &desc_host->down, &desc_host->half_len);
+            }
+        }
+        close(fd);
+        return st;
+    }
     int st = win_len < 0 ? WW_WAV_EIO : parse_wav(fd, fsize, win, win_len, &w);
     close(fd);
     if (st != 1) return st;
@@ -432,6 +578,7 @@ int ww_read_wav_batch_host(ww_wav_reader* r, const char* const* paths, int64_t n
     }
     Job j;
     j.paths = paths; j.n = n; j.slot = &s; j.status = status_host; j.capacity = r->max_raw;
+    if (int64_t(s.flac.size()) < n) s.flac.resize(size_t(n));
     static const bool trace = getenv("WW_READER_TRACE") != nullptr;     // diagnostics: time of the threaded part of every call, on stderr
     const auto t0 = std::chrono::steady_clock::now();
     run_job(r, &j);
@@ -439,13 +586,23 @@ int ww_read_wav_batch_host(ww_wav_reader* r, const char* const* paths, int64_t n
         std::fprintf(stderr, "[ww reader] %lld files, %d threads: %.3f ms\n", (long long)n, r->n_threads,
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     s.n = n;
-    const int64_t need = j.cursor.load();                      // every usable file reserved its aligned size, whether it fitted or not
-    s.raw_bytes = need < r->max_raw ? need : r->max_raw;
+    const int64_t staged = j.cursor.load();                    // every usable file reserved its aligned size, whether it fitted or not
+    const int64_t dec = j.dec_cursor.load();                   // FLAC files: their decoded float32 samples, held to the same capacity
+    const int64_t need = staged > dec ? staged : dec;
+    s.raw_bytes = staged < r->max_raw ? staged : r->max_raw;
+    s.n_flac = j.n_flac.load();
+    s.flac_frames = 0;
+    for (int64_t k = 0; k < s.n_flac; ++k) {                   // where each file's frames start in the batch's list of FLAC frames
+        s.flac[size_t(k)].first_frame = s.flac_frames;
+        s.flac_frames += s.flac[size_t(k)].n_blocks;
+    }
     if (raw_bytes_out) *raw_bytes_out = need;
     if (descs_host_out) *descs_host_out = s.descs_host;
-    if (need > r->max_raw)
+    if (need > r->max_raw) {
+        s.n_flac = 0;
         return fail(WW_ENOSPACE, "staging too small: this batch holds %lld bytes of samples, the reader was created with %lld", (long long)need,
                     (long long)r->max_raw);
+    }
     if (r->host_only) {                        // no device: the resampler geometry only (taps_dev stays NULL)
         for (int64_t i = 0; i < n; ++i) {
             ww_clip_desc& d = s.descs_host[i];
@@ -485,15 +642,27 @@ int ww_wav_batch_decode_n(ww_wav_reader* r, int32_t slot, int normalize, int64_t
     Slot& s = r->slots[size_t(slot)];
     if (s.n == 0) return WW_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (s.decode_inflight) WW_HIP(hipStreamWaitEvent(r->copy_stream, s.decoded, 0));   // K0 of the previous batch still reads raw_dev
-    if (s.raw_bytes) WW_HIP(hipMemcpyAsync(s.raw_dev, s.raw_host, size_t(s.raw_bytes), hipMemcpyHostToDevice, r->copy_stream));
-    WW_HIP(hipMemcpyAsync(s.descs_dev, s.descs_host, sizeof(ww_clip_desc) * size_t(s.n), hipMemcpyHostToDevice, r->copy_stream));
-    WW_HIP(hipEventRecord(s.copied, r->copy_stream));
-    s.copy_inflight = true;
-    WW_HIP(hipStreamWaitEvent(st, s.copied, 0));
+    if (int rc = upload_slot(r, s, st)) return rc;
     if (int rc = ww_decode_resample_n(s.raw_dev, s.descs_dev, s.n, normalize, n_samples, pcm_out_dev, stream)) return rc;
     WW_HIP(hipEventRecord(s.decoded, st));
     s.decode_inflight = true;
+    return WW_OK;
+}
+
+int ww_wav_batch_stage(ww_wav_reader* r, int32_t slot, ww_stream_t stream, const uint8_t** raw_dev_out, ww_clip_desc* descs_out) {
+    if (!r || !raw_dev_out || !descs_out) return fail(WW_EINVAL, "ww_wav_batch_stage: null argument");
+    if (slot < 0 || slot >= r->n_slots) return fail(WW_EINVAL, "slot %d of %d", slot, r->n_slots);
+    if (r->host_only) return fail(WW_EUNSUPPORTED, "this reader was created WW_READER_HOST_ONLY (no device twin to stage into)");
+    Slot& s = r->slots[size_t(slot)];
+    *raw_dev_out = s.raw_dev;
+    if (s.n == 0) return WW_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = upload_slot(r, s, st)) return rc;
+    WW_HIP(hipMemcpyAsync(descs_out, s.descs_dev, sizeof(ww_clip_desc) * size_t(s.n), hipMemcpyDeviceToHost, st));
+    WW_HIP(hipEventRecord(s.decoded, st));
+    s.decode_inflight = true;
+    WW_HIP(hipStreamSynchronize(st));
+    *raw_dev_out = s.raw_dev;                                  // (upload_slot may have re-allocated it)
     return WW_OK;
 }
 

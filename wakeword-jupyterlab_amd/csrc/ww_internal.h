@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "wakeword_amd.h"
 
 namespace ww {
@@ -177,6 +179,41 @@ int launch_conv3_dgrad_h(const float* act2, const uint32_t* maskbits, const floa
                          float* dzs, int grid, hipStream_t st);
 int launch_conv2_dgrad_h(const float* mel, const uint32_t* maskbits, const uint32_t* bits1, const float* gp, const float* w2, float* scratch,
                          int64_t n, int width, float* partial, int grid, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------
+// FLAC (ww_flac_index.h: container walk + frame index on the host, inside ww_files.cpp; ww_flac.hip: sample decode on the device)
+// ---------------------------------------------------------------------------------------------
+struct FlacHead {                 // STREAMINFO and where the first frame starts
+    int channels = 0, bps = 0, sample_rate = 0, min_block = 0, max_block = 0;
+    int64_t total_samples = 0, audio_start = 0;
+};
+// One verified frame of a file.  Byte positions are relative to the file's first frame.
+struct FlacFrame {
+    int64_t byte_off;             // first byte of the frame header
+    int64_t sample_off;           // first sample frame of the block inside the file
+    int32_t byte_len;             // header .. CRC-16 inclusive
+    int32_t header_len;           // header bytes, CRC-8 included (the subframes start behind it)
+    int32_t block_size;
+    int32_t chan_assign;          // 0..7 = 1..8 independent channels, 8 left/side, 9 side/right, 10 mid/side
+};
+static_assert(sizeof(FlacFrame) == 32, "FlacFrame is shared with the device");
+// One FLAC file of a batch, as the decode kernel sees it.  Offsets are bytes from the slot's device buffer.
+struct FlacClip {
+    int64_t comp_off;             // the file's frames (uploaded with the staging)
+    int64_t frames_off;           // its FlacFrame records (uploaded with the staging)
+    int64_t dec_off;              // float32 interleaved output, n_samples * channels (behind the staging's max_raw bytes)
+    int64_t first_frame;          // index of its first frame among all FLAC frames of the batch
+    int32_t n_blocks, clip, channels, bps;
+    int32_t err, _pad[3];         // err: set by the device when the file's bitstream is inconsistent
+};
+static_assert(sizeof(FlacClip) == 64, "FlacClip is shared with the device");
+
+// The decode kernel: one lane per frame; writes float32 samples at raw_dev + dec_off; a file with an inconsistent bitstream gets
+// n_frames = 0 in its descriptor (K0 then writes a zero row) and is counted in the FLAC error counter.
+// (default visibility: ww_files.cpp is also linked on its own against the library, by the reader's ThreadSanitizer test)
+__attribute__((visibility("default"))) int launch_flac_decode(uint8_t* raw_dev, FlacClip* clips_dev, int n_flac, int64_t n_frames_total, ww_clip_desc* descs_dev,
+                       hipStream_t stream);
+int flac_errors(unsigned int* count);
 
 int require_gfx950();
 int device_cu_count();   // CUs of the current device (256 on MI355X); cached

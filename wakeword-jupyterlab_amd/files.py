@@ -1,4 +1,4 @@
-"""File-fed batches: many WAV files -> normalised 1 s clips [B, 16000] on the GPU.
+"""File-fed batches: many WAV or FLAC files -> normalised 1 s clips [B, 16000] on the GPU.
 
 Host half of the reference's `AudioProcessor.load_audio` (/root/reference/wakeword_training_script.py:65-71) as its
 `DataLoader(batch_size=16, num_workers=2)` drives it (:461-463), for a whole batch of paths at once: the library's thread
@@ -294,9 +294,16 @@ class WavBatchReader:
 
 
 def probe(path) -> dict | None:
-    """Header of one WAV file (no GPU): {'n_frames', 'channels', 'sample_rate', 'format', 'data_offset', 'up', 'down'} or None."""
+    """Header of one WAV or FLAC file (no GPU): {'n_frames', 'channels', 'sample_rate', 'format', 'data_offset', 'up', 'down'} or None.
+    A FLAC file is scanned whole (n_frames comes from its frame index): format = _native.FMT_FLAC, data_offset = its first frame."""
     d = nat.ClipDesc()
     if nat.lib.ww_wav_probe_host(os.fsencode(path), C.byref(d)) != 1:
         return None
     return {"n_frames": d.n_frames, "channels": d.channels, "sample_rate": d.sample_rate, "format": d.format, "data_offset": d.byte_offset,
             "up": d.up, "down": d.down}
+
+
+def flac_errors() -> int:
+    """FLAC files since the library was loaded whose CRCs verified but whose bitstream the GPU decoder could not follow: each was decoded
+    to a zero row while its `ok` flag stayed True (ww_flac_errors; synchronises the device).  0 for files any conforming encoder writes."""
+    return nat.check(nat.lib.ww_flac_errors())
