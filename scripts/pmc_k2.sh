@@ -1,6 +1,6 @@
 #!/bin/bash
 # SQ / LDS counter passes over the conv kernel alone (counters only, no tracing domains).  usage: pmc_k2.sh <outdir-under-gpurun_out> [env...]
-#   e.g.  bash scripts/pmc_k2.sh k2_w16        bash scripts/pmc_k2.sh k2_x32 WW_K2_FORM=x32
+#   e.g.  bash scripts/pmc_k2.sh k2_w16        bash scripts/pmc_k2.sh k2_direct WW_CONV_MATH=f16x3d
 set -e
 out=$GRAFT_REPO_ROOT/gpurun_out/$1; shift; mkdir -p $out
 for kv in "$@"; do export "$kv"; done

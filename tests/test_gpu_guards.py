@@ -397,51 +397,3 @@ def test_expired_wait_poisons_the_outputs_with_nan():
         r = res[key]
         assert r["nan_rows"] > 0, (key, r)                                   # the broken run cannot be consumed silently
         assert r["nan_rows"] + r["finite_rows"] == r["rows"], (key, r)        # never a half-written clip
-
-
-_X32_CHILD = r"""
-import json, os, sys
-sys.path.insert(0, os.environ["WW_ROOT"])
-import numpy as np, torch
-import wakeword_jupyterlab_amd as pkg
-from wakeword_jupyterlab_amd import _native as nat, ops
-from oracle import model_oracle
-dev = torch.device("cuda", 0)
-sd = pkg.synth.make_state_dict("simple", seed=1234)
-packed = torch.from_numpy(ops.pack_state_dict(sd)).to(dev)
-pcm = torch.from_numpy(pkg.synth.make_clips(0, 24)).to(dev)
-mel = ops.logmel(pcm, True)
-res = {}
-for width in (32, 31, 5):
-    m = mel[..., :width].contiguous()
-    a = ops.cnn_pool(m, packed, 2); b = ops.cnn_pool(m, packed, 2)
-    torch.cuda.synchronize()
-    ref = model_oracle.pooled_features_np(m.cpu().numpy().astype(np.float64), sd)
-    scale = np.abs(ref).max(axis=1, keepdims=True)
-    res[str(width)] = {"err": float((np.abs(a.cpu().numpy() - ref) / scale).max()), "repeat": bool((a == b).all())}
-    if width == 32:
-        a_full = a
-big = mel.repeat(46, 1, 1, 1)[:1100].contiguous()     # > 4 clips per workgroup: rings and exchange slots wrap; every 24th row is the same image
-pb = ops.cnn_pool(big, packed, 2)
-torch.cuda.synchronize()
-res["tiled_equal"] = bool((pb[:24] == pb[24:48]).all()) and bool((pb[:24] == pb[1056:1080]).all()) and bool((pb[:24] == a_full).all())
-res["timeouts"] = int(nat.lib.ww_sync_timeouts())
-print("RESULT " + json.dumps(res))
-"""
-
-
-def test_conv2_on_32x32x16_tiles_is_a_parity_correct_alternative():
-    """cnn2x_kernel (WW_K2_FORM=x32, read once per process: hence the child): conv2 of the 2-conv model with the consumers on
-    v_mfma_f32_32x32x16_f16 and the four Winograd xi split over wave pairs that exchange an accumulator through LDS.  Round 4 measured it 20 %
-    slower than the shipped 16x16x32 form (profiles/r04_k2_census.txt) and it is not the default; it stays in the library as the
-    measured alternative, so it must keep meeting the same bound as the shipped kernel: pooled features within 1e-6 of the float64
-    oracle relative to the clip's largest feature, bitwise repeatable, no expired wait, for full and ragged widths."""
-    env = dict(os.environ, WW_ROOT=ROOT, WW_K2_FORM="x32")
-    p = subprocess.run([sys.executable, "-c", _X32_CHILD], env=env, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    res = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
-    assert res["timeouts"] == 0
-    assert res["tiled_equal"]
-    for width in ("32", "31", "5"):
-        assert res[width]["err"] <= 1e-6, (width, res[width])
-        assert res[width]["repeat"], width

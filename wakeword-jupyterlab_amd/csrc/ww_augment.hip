@@ -11,8 +11,6 @@
 //                     over the output steps whose two columns are there: thread = bin; librosa's arithmetic types are kept
 //                     (float32 magnitudes and phase accumulator, float64 phase advance) so that the accumulator rounds the
 //                     same way; angle / magnitude / phasor by short in-kernel forms instead of libm's atan2f / hypotf / sincosf.
-//                     (stft_kernel + pv_kernel, the two-launch form with the columns in HBM, are kept for the
-//                     WW_AUG_SPLIT_STFT_PV timing build: same bits.)
 //   istft_kernel      Hermitian spectrum -> conj(Z) -> the same forward FFT -> frame, four frames per round into a ring
 //                     of eight LDS slabs; the hop segments a round completes are summed straight from the slabs in
 //                     frame order with the window and its sum-square, centre-trimmed, cropped / zero-padded
@@ -33,11 +31,6 @@ constexpr int kAugFrames = kFrames;                 // STFT frames of a 16000-sa
 constexpr int kAugMaxOut = 46;                      // phase-vocoder output steps: ceil(32 / rate), rate >= 32/46
 constexpr int kAugYStride = 25600;                  // stretched-clip scratch row
 constexpr int kSpec = kBins;                        // 1025 complex bins per spectrum row
-#ifdef WW_AUG_SPLIT_STFT_PV                         // timing-only build: stft_kernel and pv_kernel as two launches with the columns in HBM
-constexpr int kAugDFrames = kAugFrames;
-#else
-constexpr int kAugDFrames = 0;                      // the STFT columns live in LDS (stft_pv_kernel): no spectrum buffer in the workspace
-#endif
 
 struct AugDev {            // one per clip, derived on the host from ww_augment_plan
     int32_t shift;         // np.roll shift reduced to [0, L)
@@ -68,75 +61,16 @@ __global__ __launch_bounds__(256) void roll_kernel(const float* __restrict__ in,
     *reinterpret_cast<float4*>(out + int64_t(clip) * kClip + i) = v;
 }
 
-#ifdef WW_AUG_SPLIT_STFT_PV     // timing-only build: the two-launch form (stft_kernel, pv_kernel below) with the columns in HBM
-// ------------------------------------------------------------------------------------------------
-// which = 0: pitch stage, 1: stretch stage (selects the on/off flag)
-__global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ x, const AugDev* __restrict__ plan, int which,
-                                                   const LogmelTables* __restrict__ tb, float2* __restrict__ D) {
-    __shared__ __attribute__((aligned(16))) float slabs[4 * fft::kSlabFloats];
-    const int clip = blockIdx.x;
-    if ((which == 0 ? plan[clip].p_out : plan[clip].s_out) == 0) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* slab = slabs + wave * fft::kSlabFloats;
-    const float2* slab2 = reinterpret_cast<const float2*>(slab);
-    const float* xc = x + int64_t(clip) * kClip;
-    const float4* win4 = reinterpret_cast<const float4*>(&tb->window[0]);
-    for (int frame = wave; frame < kAugFrames; frame += 4) {
-        float2 za[8], zb[8];
-        const int base = frame * kHop - kNfft / 2 + 4 * lane;
-#pragma unroll
-        for (int n1 = 0; n1 < 8; ++n1) {
-            const int idx = base + 256 * n1;                     // multiple of 4: the float4 is all inside or all outside
-            const float4 s = (idx >= 0 && idx < kClip) ? *reinterpret_cast<const float4*>(xc + idx) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 w = win4[64 * n1 + lane];
-            za[n1] = make_float2(s.x * w.x, s.y * w.y);
-            zb[n1] = make_float2(s.z * w.z, s.w * w.w);
-        }
-        fft::wave_fft1024(za, zb, slab, tb, lane);
-        // real-input split: X[k] = E + W^k O, X[1024-k] = conj(E - W^k O), E = (Z[k] + conj Z[1024-k])/2, O = (Z[k] - conj Z[1024-k])/(2i)
-        float2* Dr = D + (int64_t(clip) * kAugFrames + frame) * kSpec;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int k = lane + 64 * j;                         // 0..511
-            const float2 a = slab2[fft::zpos(k)], b = slab2[fft::zpos((1024 - k) & 1023)];
-            const float2 tw = tb->twr[k];
-            const float2 e = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
-            const float2 o = make_float2(0.5f * (a.y + b.y), 0.5f * (b.x - a.x));
-            const float2 t = fft::cmul(o, tw);
-            Dr[k] = make_float2(e.x + t.x, e.y + t.y);
-            Dr[1024 - k] = make_float2(e.x - t.x, -(e.y - t.y));
-        }
-        if (lane == 0) { const float2 z = slab2[fft::zpos(512)]; Dr[512] = make_float2(z.x, -z.y); }
-        fft::lds_order();                                        // the slab is rewritten by the next frame
-    }
-}
-
-#endif
-
-#ifdef WW_AUG_SPLIT_STFT_PV
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float2 pv_col(const float2* __restrict__ Dc, int f, int k) {
-    return f < kAugFrames ? Dc[int64_t(f) * kSpec + k] : make_float2(0.f, 0.f);     // librosa pads two zero columns
-}
-#endif
-
 // atan2 for the vocoder: a = min/max in [0, 1], atan(a) = a P(a^2) (degree 8 in a^2, |err| <= 1.2e-7 in float32 evaluation -- the size of
 // libm's own last-place error at these magnitudes), octant and quadrant folded back; signed zeros and (0, 0) as atan2f has them.
 __device__ __forceinline__ float pv_atan2(float y, float x) {
-#ifdef WW_ABL_PV_LIBM_ATAN
-    return atan2f(y, x);
-#endif
     const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
     float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-#ifndef WW_ABL_PV_PRECISE_DIV
     // min / max by v_rcp_f32 (1 ulp; the polynomial's own error is of that size).  The hardware reciprocal takes denormals for zero, so
     // tiny pairs are scaled up first (exact, the ratio is unchanged)
     const float sc = mx < 5.4210109e-20f ? 1.8446744e19f : 1.0f;                      // 2^-64, 2^64
     mx *= sc; mn *= sc;
     const float a = mx > 0.f ? mn * __builtin_amdgcn_rcpf(mx) : 0.f;
-#else
-    const float a = mx > 0.f ? mn / mx : 0.f;
-#endif
     const float q = a * a;
     float p = 2.399661113e-03f;
     p = fmaf(p, q, -1.415910292e-02f);
@@ -159,85 +93,29 @@ __device__ __forceinline__ float pv_atan2(float y, float x) {
 // on the output samples).
 // |c| by v_sqrt_f32 (1 ulp) instead of the correctly rounded expansion
 __device__ __forceinline__ float pv_abs(float2 c) {
-#ifndef WW_ABL_PV_PRECISE_DIV
     return __builtin_amdgcn_sqrtf(fmaf(c.x, c.x, c.y * c.y));
-#else
-    return sqrtf(fmaf(c.x, c.x, c.y * c.y));
-#endif
 }
 
 // round(dphase / 2 pi) with the quotient formed by the reciprocal: differs from the division only when the quotient is within an ulp of a
 // half-integer, where either neighbour wraps the phase to the same angle (the accumulator then differs by its own rounding of +-2 pi)
 __device__ __forceinline__ double pv_wrap(double dphase) {
     const double two_pi = 6.283185307179586476925286766559;
-#ifndef WW_ABL_PV_PRECISE_DIV
     return dphase - two_pi * __builtin_rint(dphase * 0.15915494309189533576888);
-#else
-    return dphase - two_pi * __builtin_rint(dphase / two_pi);
-#endif
 }
 
 __device__ __forceinline__ void pv_sincos(float acc, float& sn, float& cs) {
-#ifdef WW_ABL_PV_LIBM_SINCOS
-    sincosf(acc, &sn, &cs);
-    return;
-#endif
     const double turns = double(acc) * 0.15915494309189533576888;       // 1 / (2 pi)
     const float fr = float(turns - __builtin_rint(turns));                // [-0.5, 0.5]
     sn = __builtin_amdgcn_sinf(fr);
     cs = __builtin_amdgcn_cosf(fr);
 }
 
-#ifdef WW_AUG_SPLIT_STFT_PV
-__global__ __launch_bounds__(256) void pv_kernel(const float2* __restrict__ D, const AugDev* __restrict__ plan, int which,
-                                                 float2* __restrict__ S) {
-#pragma clang fp contract(off)
-    const int clip = blockIdx.x;
-    const int n_out = which == 0 ? plan[clip].p_out : plan[clip].s_out;
-    if (n_out == 0) return;
-    const double rate = which == 0 ? plan[clip].p_rate : plan[clip].s_rate;
-    const float2* Dc = D + int64_t(clip) * kAugFrames * kSpec;
-    float2* Sc = S + int64_t(clip) * kAugMaxOut * kSpec;
-    const double two_pi = 6.283185307179586476925286766559;
-    for (int k = threadIdx.x; k < kSpec; k += 256) {
-        const double phi = double(k) * two_pi * 0.25;            // hop * 2 pi k / n_fft
-        const float2 d0 = Dc[k];
-        float acc = pv_atan2(d0.y, d0.x);                        // np.angle(D[:, 0]): float32 accumulator
-        // |c| and angle(c) of the two columns a step reads are kept from the previous step: the column index moves on by 0, 1 or 2 per
-        // step (uniform over the workgroup), so most steps compute one new column instead of two (same values, a third less work)
-        int have = -2;                                           // columns `have`, `have + 1` are in (m0, a0), (m1, a1)
-        float m0 = 0.f, a0 = 0.f, m1 = 0.f, a1 = 0.f;
-        for (int t = 0; t < n_out; ++t) {
-            const double step = double(t) * rate;                // np.arange(0, n, rate)[t]
-            const int i0 = int(step);
-            const double alpha = step - double(i0);
-            if (i0 != have) {
-                if (i0 == have + 1) { m0 = m1; a0 = a1; }
-                else { const float2 c0 = pv_col(Dc, i0, k); m0 = pv_abs(c0); a0 = pv_atan2(c0.y, c0.x); }
-                const float2 c1 = pv_col(Dc, i0 + 1, k);
-                m1 = pv_abs(c1);                                 // |c|: STFT magnitudes of unit-peak clips stay far inside float range
-                a1 = pv_atan2(c1.y, c1.x);
-                have = i0;
-            }
-            const float mag = float(1.0 - alpha) * m0 + float(alpha) * m1;
-            float sn, cs;
-            pv_sincos(acc, sn, cs);
-            Sc[int64_t(t) * kSpec + k] = make_float2(cs * mag, sn * mag);
-            const float da = a1 - a0;
-            double dphase = double(da) - phi;
-            dphase = pv_wrap(dphase);
-            acc = float(double(acc) + (phi + dphase));
-        }
-    }
-}
-#endif
-
 // ------------------------------------------------------------------------------------------------
-// stft_kernel + pv_kernel in one pass over the clip: the STFT columns never leave the CU.  Four frames per round (one per wave) are
+// The STFT and the phase vocoder in one pass over the clip: the STFT columns never leave the CU.  Four frames per round (one per wave) are
 // transformed into a ring of eight LDS slabs and split IN PLACE into their spectrum column (a lane reads Z[k], Z[1024-k] and writes
 // D[k], D[1024-k] back to the same two slots; D[1024] takes the slab's spare slot), then every thread advances its bins' vocoder state
 // over the output steps whose two columns are there.  A step reads columns i0, i0 + 1 with i0 non-decreasing, so round r + 1 may
-// overwrite the columns of round r - 1 (two barriers per round).  Same arithmetic as the two kernels, bit-identical S.
+// overwrite the columns of round r - 1 (two barriers per round).
 constexpr int kStftPvLds = 8 * fft::kSlabFloats * int(sizeof(float));                    // 65,664 B: two workgroups per CU
 
 __global__ __launch_bounds__(256) void stft_pv_kernel(const float* __restrict__ x, const AugDev* __restrict__ plan, int which,
@@ -489,22 +367,13 @@ __global__ __launch_bounds__(1024) void resample_kernel(const float* __restrict_
             const float eta_r = float(if_r - double(off_r));
             int k_max = (kKbLen - off_r) / index_step;
             k_max = k_max < n_orig - n - 1 ? k_max : n_orig - n - 1;
-#ifdef WW_ABL_RS_SAMEROW          // timing-only ablation: every lane of a wave reads the same table rows (broadcast reads; results are garbage)
-            const float* l0 = P + __builtin_amdgcn_readfirstlane(off_l) * R;
-            const float* r0 = P + __builtin_amdgcn_readfirstlane(off_r) * R;
-#else
             const float* l0 = P + off_l * R;
             const float* r0 = P + off_r * R;
-#endif
             const float* l1 = l0 + R;
             const float* r1 = r0 + R;
             auto left4 = [&](int i) {
                 const float4 t0 = *reinterpret_cast<const float4*>(l0 + i), t1 = *reinterpret_cast<const float4*>(l1 + i);
-#ifdef WW_ABL_RS_NOY              // timing-only ablation: no sample loads
-                const f4u yy = {eta_l, t0.x, t1.y, 1.0f};
-#else
                 const f4u yy = *reinterpret_cast<const f4u*>(y + n - i - 3);              // y[n-i-3 .. n-i]
-#endif
                 accl = fmaf(fmaf(eta_l, t1.x - t0.x, t0.x), yy.w, accl);
                 accl = fmaf(fmaf(eta_l, t1.y - t0.y, t0.y), yy.z, accl);
                 accl = fmaf(fmaf(eta_l, t1.z - t0.z, t0.z), yy.y, accl);
@@ -512,11 +381,7 @@ __global__ __launch_bounds__(1024) void resample_kernel(const float* __restrict_
             };
             auto right4 = [&](int k) {
                 const float4 t0 = *reinterpret_cast<const float4*>(r0 + k), t1 = *reinterpret_cast<const float4*>(r1 + k);
-#ifdef WW_ABL_RS_NOY
-                const f4u yy = {eta_r, t0.x, t1.y, 1.0f};
-#else
                 const f4u yy = *reinterpret_cast<const f4u*>(y + n + 1 + k);              // y[n+1+k .. n+4+k]
-#endif
                 accr = fmaf(fmaf(eta_r, t1.x - t0.x, t0.x), yy.x, accr);
                 accr = fmaf(fmaf(eta_r, t1.y - t0.y, t0.y), yy.y, accr);
                 accr = fmaf(fmaf(eta_r, t1.z - t0.z, t0.z), yy.z, accr);
@@ -524,16 +389,13 @@ __global__ __launch_bounds__(1024) void resample_kernel(const float* __restrict_
             };
             const int both = (i_max < k_max ? i_max : k_max) & ~3;
             int i = 0;
-#ifndef WW_ABL_RS_SEQUENTIAL
             for (; i < both; i += 4) { left4(i); right4(i); }
-#endif
             int k = i;
             for (; i + 4 <= i_max; i += 4) left4(i);
             for (; k + 4 <= k_max; k += 4) right4(k);
             // the last one to three taps of a wing: one more block of four with the weights past the end set to zero (fma(0, y, acc) = acc:
             // the same sum) when its four samples are inside the signal, tap by tap at the signal's edges -- a tap-by-tap tail is a
             // dependent load round trip per tap
-#ifndef WW_ABL_RS_SCALAR_TAIL
             if (i < i_max && n - i - 3 >= 0) {
                 const float4 t0 = *reinterpret_cast<const float4*>(l0 + i), t1 = *reinterpret_cast<const float4*>(l1 + i);
                 const f4u yy = *reinterpret_cast<const f4u*>(y + n - i - 3);
@@ -550,7 +412,6 @@ __global__ __launch_bounds__(1024) void resample_kernel(const float* __restrict_
                 accr = fmaf(k + 2 < k_max ? fmaf(eta_r, t1.z - t0.z, t0.z) : 0.f, yy.z, accr);
                 k = k_max;
             }
-#endif
             for (; i < i_max; ++i) {
                 const float w0 = l0[i], w1 = l1[i];
                 accl = fmaf(fmaf(eta_l, w1 - w0, w0), y[n - i], accl);
@@ -607,8 +468,8 @@ __global__ __launch_bounds__(256) void noise_kernel(const float* __restrict__ in
 static int64_t up256(int64_t b) { return (b + 255) & ~int64_t(255); }
 
 int64_t augment_workspace_bytes(int64_t n) {
-    return up256(n * int64_t(sizeof(AugDev))) + 2 * up256(n * int64_t(kClip) * 4) + up256(n * int64_t(kAugDFrames) * kSpec * 8) +
-           up256(n * int64_t(kAugMaxOut) * kSpec * 8) + up256(n * int64_t(kAugYStride) * 4);
+    return up256(n * int64_t(sizeof(AugDev))) + 2 * up256(n * int64_t(kClip) * 4) + up256(n * int64_t(kAugMaxOut) * kSpec * 8) +
+           up256(n * int64_t(kAugYStride) * 4);
 }
 
 // Pinned staging for the per-clip records: two slots per device, each guarded by an event, so the call can return as soon as the
@@ -681,7 +542,6 @@ int launch_augment_records(const float* pcm, int64_t n, int64_t stride, const vo
     w += up256(n * int64_t(sizeof(AugDev)));                        // (the slot ww_augment_f32 copies its records into)
     float* bufA = reinterpret_cast<float*>(w); w += up256(n * int64_t(kClip) * 4);
     float* bufB = reinterpret_cast<float*>(w); w += up256(n * int64_t(kClip) * 4);
-    [[maybe_unused]] float2* D = reinterpret_cast<float2*>(w); w += up256(n * int64_t(kAugDFrames) * kSpec * 8);
     float2* S = reinterpret_cast<float2*>(w); w += up256(n * int64_t(kAugMaxOut) * kSpec * 8);
     float* Y = reinterpret_cast<float*>(w);
     {
@@ -702,24 +562,14 @@ int launch_augment_records(const float* pcm, int64_t n, int64_t stride, const vo
     float* cur = bufA;
     float* other = bufB;
     if (any_pitch) {
-#ifdef WW_AUG_SPLIT_STFT_PV
-        hipLaunchKernelGGL(stft_kernel, dim3(unsigned(n)), dim3(256), 0, stream, cur, plan, 0, tb, D);
-        hipLaunchKernelGGL(pv_kernel, dim3(unsigned(n)), dim3(256), 0, stream, D, plan, 0, S);
-#else
         hipLaunchKernelGGL(stft_pv_kernel, dim3(unsigned(n)), dim3(256), kStftPvLds, stream, cur, plan, 0, tb, S);
-#endif
         hipLaunchKernelGGL(istft_kernel, dim3(unsigned(n)), dim3(256), kIstftLds, stream, S, plan, 0, tb,
                            static_cast<const float*>(nullptr), Y, int64_t(kAugYStride));
         hipLaunchKernelGGL(resample_kernel, dim3(unsigned(n)), dim3(1024), kResampleLds, stream, Y, plan, tb, cur, other);
         float* t = cur; cur = other; other = t;
     }
     if (any_stretch) {
-#ifdef WW_AUG_SPLIT_STFT_PV
-        hipLaunchKernelGGL(stft_kernel, dim3(unsigned(n)), dim3(256), 0, stream, cur, plan, 1, tb, D);
-        hipLaunchKernelGGL(pv_kernel, dim3(unsigned(n)), dim3(256), 0, stream, D, plan, 1, S);
-#else
         hipLaunchKernelGGL(stft_pv_kernel, dim3(unsigned(n)), dim3(256), kStftPvLds, stream, cur, plan, 1, tb, S);
-#endif
         hipLaunchKernelGGL(istft_kernel, dim3(unsigned(n)), dim3(256), kIstftLds, stream, S, plan, 1, tb, cur, other, int64_t(kClip));
         float* t = cur; cur = other; other = t;
     }

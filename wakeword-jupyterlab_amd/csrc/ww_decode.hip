@@ -220,9 +220,7 @@ __global__ __launch_bounds__(256) void decode_resample_kernel(const uint8_t* __r
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int clip = blockIdx.x; clip < n_clips; clip += gridDim.x) {
         const ww_clip_desc d = descs[clip];
-#ifndef WW_ABL_K0_DIRECT
         if (resample_in_lds(d.up, d.down, d.half_len)) continue;      // resample_lds_kernel's
-#endif
         const uint8_t* __restrict__ p = raw + d.byte_offset;
         const float* __restrict__ taps = reinterpret_cast<const float*>(d.taps_dev);
         const int64_t n_in = d.format == WW_FMT_FLAC ? 0 : d.n_frames;   // (see resample_lds_kernel)
@@ -234,7 +232,6 @@ __global__ __launch_bounds__(256) void decode_resample_kernel(const uint8_t* __r
         const int lh = 2 * half_len + 1;
         float* __restrict__ o = out + int64_t(clip) * row_len;
         float peak = 0.f;
-#ifndef WW_ABL_K0_NOFAST
         // the data set's usual file -- 16 kHz, mono, PCM-16, at most one second (create_sample_data's format) -- in one pass: eight samples
         // per 16-byte load, the clip held in registers between the peak reduction and the scaled store (the general loop below stores,
         // reduces, then reads and rewrites).  Same conversion, same division: bit-identical.
@@ -277,7 +274,6 @@ __global__ __launch_bounds__(256) void decode_resample_kernel(const uint8_t* __r
             }
             continue;
         }
-#endif
         const int64_t total = n_out > d.crop_start + row_len ? n_out : d.crop_start + row_len;   // also writes the zero pad
         const int64_t j_begin = normalize ? 0 : d.crop_start;          // see resample_lds_kernel
         const int64_t j_end = normalize || total < d.crop_start + row_len ? total : d.crop_start + row_len;
@@ -360,11 +356,9 @@ int ww_decode_resample_n(const uint8_t* raw_dev, const ww_clip_desc* descs_dev, 
     const int grid = int(n_clips < resident ? n_clips : resident);
     hipLaunchKernelGGL(decode_resample_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), raw_dev,
                        descs_dev, int(n_clips), normalize, pcm_out_dev, int(n_samples));
-#ifndef WW_ABL_K0_DIRECT
     const int64_t resident2 = int64_t(device_cu_count()) * 2;
     hipLaunchKernelGGL(resample_lds_kernel, dim3(int(n_clips < resident2 ? n_clips : resident2)), dim3(kRsThreads), kRsLds,
                        static_cast<hipStream_t>(stream), raw_dev, descs_dev, int(n_clips), normalize, pcm_out_dev, int(n_samples));
-#endif
     WW_HIP(hipGetLastError());
     return WW_OK;
 }

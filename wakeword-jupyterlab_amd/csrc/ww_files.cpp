@@ -30,7 +30,6 @@
 
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
 #include <emmintrin.h>
-#define WW_STREAMING_COPY 1
 #endif
 
 namespace ww {
@@ -103,13 +102,10 @@ static int parse_wav(int fd, int64_t fsize, const uint8_t* win, int64_t win_len,
 // much staging a file gets: a streaming header (RIFF / data size 0xFFFFFFFF) or a truncated file would otherwise reserve gigabytes and
 // fail the whole batch with WW_ENOSPACE (round-3 review); every length is clamped to the bytes that exist.  Whatever of the sample data
 // the window does not hold is read straight into the pinned staging buffer.
-#ifndef WW_HEAD_WINDOW
-#define WW_HEAD_WINDOW 69632
-#endif
 // 68 KB: a 1 s / 16 kHz PCM-16 clip (32,044 bytes, the reference's data format) arrives whole in the head read: open + ONE pread + close
 // and a 32 KB copy into the staging buffer.  Measured against a 512-byte head (two preads, samples straight into staging, no copy) on
 // the same MI355X host, interleaved (scripts/ab_reader.py, 16 threads): 1.06 M vs 0.96 M files/s.
-constexpr int64_t kHeadWindow = WW_HEAD_WINDOW;
+constexpr int64_t kHeadWindow = 69632;
 static int64_t read_head(int fd, uint8_t* win, int64_t* fsize_out) {
     const ssize_t r = pread(fd, win, size_t(kHeadWindow), 0);
     if (r < 0) return -1;
@@ -192,7 +188,7 @@ namespace ww {
 static void copy_to_staging(uint8_t* dst, const uint8_t* src, size_t n) {
 #if !defined(__HIP_DEVICE_COMPILE__)
     size_t i = 0;
-#ifdef WW_STREAMING_COPY
+#ifdef __x86_64__
     if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0 && n >= 256) {
         for (; i + 64 <= n; i += 64) {
             const __m128i a = _mm_loadu_si128(reinterpret_cast<const __m128i*>(src + i));

@@ -16,10 +16,6 @@ namespace ww {
 
 constexpr int kHS = kHidden + 4;   // LDS row stride for [32 clips][256]: 16-byte aligned rows, 4 banks apart
 
-#ifdef WW_K3_PRECISE_MATH
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f / (expf(2.0f * x) + 1.0f); }
-#else
 // hardware exp2 / reciprocal (v_exp_f32, v_rcp_f32: ~1 ulp each).  sigmoid(x) = 1/(1 + 2^(-x log2 e));
 // tanh(x) = 1 - 2/(2^(2x log2 e) + 1): monotone, saturates cleanly to +-1, NaN in -> NaN out.
 __device__ __forceinline__ float sigmoidf_(float x) {
@@ -28,7 +24,6 @@ __device__ __forceinline__ float sigmoidf_(float x) {
 __device__ __forceinline__ float tanhf_(float x) {
     return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(2.88539008177792681f * x) + 1.0f);
 }
-#endif
 
 // LDS activation rows use the same within-16 permutation as the packed weights: element k of a row sits at
 // 16*(k>>4) + slot16(k), slot16 = (k&3)*4 + ((k&15)>>2), so that lane (clip, kq) reads its A values of four

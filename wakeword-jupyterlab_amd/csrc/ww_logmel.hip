@@ -36,13 +36,6 @@ static_assert(kPartialInSlab + kPieces <= kSlab, "piece sums must fit behind the
 // WAVES = 4: the throughput form, three workgroups per CU, persistent over clips.
 // WAVES = 8: the latency form for batches of at most one clip per CU (streaming): a clip's 32 frames take 4 rounds
 //            instead of 8, one 83 KB workgroup per CU.
-// WW_K1_RESIDENT 1: the lane's 32 window values and 28 pass-1 twiddles live in registers for the life of the workgroup
-// (60 VGPRs) instead of being re-read through L1 for every frame; two waves per SIMD instead of three.
-// WW_K1_RESIDENT 2: also, a wave takes CONSECUTIVE frames of a clip and keeps the raw samples: frame t + 1 is frame t moved on
-// by 512 samples = two of the eight 256-sample groups, so six groups are register moves and only two are loaded.
-#ifndef WW_K1_RESIDENT
-#define WW_K1_RESIDENT 0
-#endif
 // FR: the frames the mel tile holds.  FR = 32 (kFrames) is the 1 s kernel; FR = 64 takes any T = 1 + n_samples / 512 in [8, 63]
 // (ww_logmel_frames_f32), computing ceil(T / WAVES) rounds of frames and using the first T.
 template <int WAVES, int FR = kFrames>
@@ -63,11 +56,11 @@ struct K1Layout {
     static constexpr int kOffTwp = kOffTw2 + 7 * 16 * 2;    // [512] float2
     static constexpr int kLdsFloats = kOffTwp + 512 * 2;
     // launch bound: 3 (2) x 4 waves or 1 x 8 waves per CU; the 64-frame tile (62 KB with 4 waves) admits two 4-wave workgroups
-    static constexpr int kWavesPerSimd = WAVES == 4 ? (WW_K1_RESIDENT || FR != kFrames ? 2 : 3) : 2;
-    static constexpr int kBlocksPerCu = WAVES == 4 ? (WW_K1_RESIDENT || FR != kFrames ? 2 : 3) : 1;
+    static constexpr int kWavesPerSimd = WAVES == 4 ? (FR != kFrames ? 2 : 3) : 2;
+    static constexpr int kBlocksPerCu = WAVES == 4 ? (FR != kFrames ? 2 : 3) : 1;
     static_assert(kOffPinfo % 4 == 0 && kOffTw2 % 4 == 0 && kOffTwp % 2 == 0, "LDS table alignment");
     static_assert(FR % WAVES == 0 && WAVES <= 8, "frames are dealt to the waves in whole rounds; red[] holds 16 floats");
-    static_assert(FR == kFrames || (FR == 64 && WW_K1_RESIDENT != 2), "the long-clip tile: 64 frames, frames dealt round-robin");
+    static_assert(FR == kFrames || FR == 64, "the long-clip tile: 64 frames, frames dealt round-robin");
     static_assert(kBlocksPerCu * sizeof(float) * kLdsFloats <= 160 * 1024, "LDS per CU");
 };
 
@@ -145,10 +138,10 @@ __device__ __forceinline__ float absmax3(float a, float b, float m) {
 // range-checked.  Ring mode (streaming): sample i of the window lives at (pos + i) mod len.
 using u32x4_t = __attribute__((ext_vector_type(4))) unsigned int;
 
-template <bool RING, int N0 = 0, int N1 = 8>
+template <bool RING>
 __device__ __forceinline__ void load_frame(float4 (&sn)[8], __amdgpu_buffer_rsrc_t rsrc, int base, int ring_pos, int ring_len) {
 #pragma unroll
-    for (int n1 = N0; n1 < N1; ++n1) {
+    for (int n1 = 0; n1 < 8; ++n1) {
         const int idx = base + 256 * n1;              // multiple of 4; may be negative or past the end
         int off = idx * 4;
         if constexpr (RING) {
@@ -174,10 +167,7 @@ constexpr uint32_t kRedoMark = 0x7fc5a11eu;
 // below kFloorRatio * E sends its clip to the float64 kernel.  E is estimated from the mel tile itself: the triangles
 // M_bk / wmax_b are a partition of unity over the bins 1..1023, so sum_b P_b / wmax_b ~ E without the DC and Nyquist bins, which carry
 // zero mel weight; those two are added from Z[0] (round 3: a pure Nyquist tone was missed without them, 1.07e-4 dB).
-#ifndef WW_FLOOR_RATIO
-#define WW_FLOOR_RATIO 1.0e-5f
-#endif
-constexpr float kFloorRatio = WW_FLOOR_RATIO;
+constexpr float kFloorRatio = 1.0e-5f;
 
 #ifdef WW_STAMPS
 __device__ unsigned long long g_stamps[16];
@@ -260,20 +250,9 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, ok ? clip_bytes : 0u, 0x00020000);
     };
     const int kRounds = FR == kFrames ? kFrames / kWavesPerBlock : (nfr + kWavesPerBlock - 1) / kWavesPerBlock;
-#if WW_K1_RESIDENT == 2
-    const int frame0 = wave * kRounds;                 // this wave's frames: frame0 .. frame0 + kRounds - 1
-#else
     const int frame0 = wave;                           // frames wave, wave + WAVES, ...
-#endif
     float4 sn[8];
     load_frame<RING>(sn, clip_rsrc(blockIdx.x), frame0 * kHop - kNfft / 2 + 4 * lane, ring_pos, ring_len);
-#if WW_K1_RESIDENT
-    float4 wres[8], t1res[7];
-#pragma unroll
-    for (int n1 = 0; n1 < 8; ++n1) wres[n1] = win4[64 * n1 + lane_id];
-#pragma unroll
-    for (int k1 = 1; k1 < 8; ++k1) t1res[k1 - 1] = tw1_4[(k1 - 1) * 64 + lane_id];
-#endif
     int clip_it = 0;
 #pragma unroll 1
     for (int clip = blockIdx.x; clip < n_clips; clip += gridDim.x, ++clip_it) {
@@ -283,21 +262,13 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
 
 #pragma unroll 1
         for (int round = 0; round < kRounds; ++round) {
-#if WW_K1_RESIDENT == 2
-            const int frame = frame0 + round;
-#else
             const int frame = round * kWavesPerBlock + wave;
-#endif
             // Opaque copy of the lane id: every swizzled LDS address below is a function of it.  Without this the
             // compiler hoists ~100 loop-invariant address VGPRs out of the frame loop and spills the prefetched samples.
             int lane = lane_id;
             asm volatile("" : "+v"(lane));
             const int k1r = lane >> 3, jr = lane & 7;                   // pass-2 role: (k1, j)
-#if WW_K1_RESIDENT == 2
-            const int base_next = (frame + 1) * kHop - kNfft / 2 + 4 * lane;
-#else
             const int base_next = (frame + kWavesPerBlock) * kHop - kNfft / 2 + 4 * lane;
-#endif
 
             STAMP(8);
             // ---- load + window: lane holds z[128 n1 + 2 lane + q], q = 0,1, n1 = 0..7 ----
@@ -305,13 +276,7 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
 #pragma unroll
             for (int n1 = 0; n1 < 8; ++n1) {
                 const float4 s = sn[n1];
-#if WW_K1_RESIDENT
-                const float4 w = wres[n1];
-#elif defined(WW_K1_ABL_NOTAB)      // timing-only ablation: no window / pass-1 twiddle loads (results are garbage)
-                const float4 w = make_float4(0.5f, 0.25f, 0.75f, 1.0f);
-#else
                 const float4 w = win4[64 * n1 + lane];
-#endif
                 // every sample sits in 4 frames; samples [512 t, 512 t + 512) = loads n1 4 and 5 of frame t tile the clip once
                 if (n1 == 4 || n1 == 5) peak = absmax3(s.z, s.w, absmax3(s.x, s.y, peak));
                 za[n1] = make_float2(s.x * w.x, s.y * w.y);
@@ -322,24 +287,10 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
             // is issued right there and the wave pays one L1 / LDS round trip per twiddle.
             float4 t1[7];
 #pragma unroll
-#if WW_K1_RESIDENT
-            for (int k1 = 1; k1 < 8; ++k1) t1[k1 - 1] = t1res[k1 - 1];
-#elif defined(WW_K1_ABL_NOTAB)
-            for (int k1 = 1; k1 < 8; ++k1) t1[k1 - 1] = make_float4(0.7f, -0.7f, 0.6f, -0.8f);
-#else
             for (int k1 = 1; k1 < 8; ++k1) t1[k1 - 1] = tw1_4[(k1 - 1) * 64 + lane];
             __builtin_amdgcn_sched_barrier(0);
-#endif
             dft8(za);
             dft8(zb);
-#ifdef WW_K1_ABL_NOX1                  // timing-only ablation: exchange 1 without its LDS round trip (results are garbage)
-#pragma unroll
-            for (int k1 = 1; k1 < 8; ++k1) {
-                const float4 t = t1[k1 - 1];
-                za[k1] = cmul(za[k1], make_float2(t.x, t.y));
-                zb[k1] = cmul(zb[k1], make_float2(t.z, t.w));
-            }
-#else
             slab4[lane] = make_float4(za[0].x, za[0].y, zb[0].x, zb[0].y);
 #pragma unroll
             for (int k1 = 1; k1 < 8; ++k1) {
@@ -348,7 +299,6 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
                 const float2 b = cmul(zb[k1], make_float2(t.z, t.w));
                 slab4[k1 * 64 + (lane ^ (8 * ((k1 >> 1) & 1)))] = make_float4(a.x, a.y, b.x, b.y);
             }
-#endif
             lds_order();
             STAMP(0);
             // ---- pass 2: lane = (k1, j): radix 8 over n2 of y[k1][16 n2 + 2j + q]; twiddle W_128; store X2 ----
@@ -357,25 +307,19 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
                 const int s8 = 8 * ((k1r >> 1) & 1);
                 const float4* x1e = slab4 + k1r * 64 + jr + s8;
                 const float4* x1o = slab4 + k1r * 64 + jr - s8;
-#ifndef WW_K1_ABL_NOX1
 #pragma unroll
                 for (int n2 = 0; n2 < 8; ++n2) {
                     const float4 v = (n2 & 1) ? x1o[n2 * 8] : x1e[n2 * 8];
                     za[n2] = make_float2(v.x, v.y);
                     zb[n2] = make_float2(v.z, v.w);
                 }
-#else
-                asm volatile("" :: "v"(x1e), "v"(x1o));
-#endif
                 float4 t2[7];
 #pragma unroll
                 for (int k2 = 1; k2 < 8; ++k2) t2[k2 - 1] = tw2_4[(k2 - 1) * 8 + jr];
                 lds_order();
                 __builtin_amdgcn_sched_barrier(0);
-#ifndef WW_K1_ABL_NODFT8P2             // timing-only ablation: pass 2's butterflies
                 dft8(za);
                 dft8(zb);
-#endif
                 // writer (k1, j), reader lane 8 k1 + k2, slot j ^ ((reader >> 1) & 7) = j ^ (4 (k1 & 1) + (k2 >> 1)):
                 // four lane bases (one per k2 >> 1), everything else is an immediate offset
                 float4* x2w[4];
@@ -389,11 +333,7 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
                         a = cmul(a, make_float2(t.x, t.y));
                         b = cmul(b, make_float2(t.z, t.w));
                     }
-#ifdef WW_K1_ABL_NOX2                  // timing-only ablation: exchange 2 without its LDS round trip
-                    za[k2] = a; zb[k2] = b;
-#else
                     x2w[k2 >> 1][8 * k2] = make_float4(a.x, a.y, b.x, b.y);
-#endif
                 }
             }
             lds_order();
@@ -402,22 +342,14 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
             {
                 float2 u[16];
                 const int sw2 = (lane >> 1) & 7;
-#ifdef WW_K1_ABL_NOX2
-#pragma unroll
-                for (int m = 0; m < 8; ++m) { u[2 * m] = za[m]; u[2 * m + 1] = zb[m]; }
-                asm volatile("" :: "v"(sw2));
-#else
 #pragma unroll
                 for (int m = 0; m < 8; ++m) {
                     const float4 v = slab4[lane * 8 + (m ^ sw2)];
                     u[2 * m] = make_float2(v.x, v.y);
                     u[2 * m + 1] = make_float2(v.z, v.w);
                 }
-#endif
                 lds_order();
-#ifndef WW_K1_ABL_NODFT16              // timing-only ablation: what pass 3's butterflies cost the vector ALU (results are garbage)
                 dft16(u);
-#endif
                 const int lp = (lane >> 3) + 8 * (lane & 7);
                 float2* zw = slab2 + (lp ^ (((lp >> 4) & 3) << 1));     // bits 4-5 of k = lp + 64 kk are lp's: one base
 #pragma unroll
@@ -437,16 +369,8 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
             // power / mel stages (about a third of the frame time, several times the HBM latency)
             {
                 const bool last = round + 1 == kRounds;            // uniform: descriptor select, no branch
-#if WW_K1_RESIDENT == 2
-                // the next frame's groups 0..5 are this frame's 2..7; groups 6, 7 are new.  On the clip's last round these are
-                // the next clip's first frame's 6, 7 and its groups 0..5 are loaded behind the round loop.
-#pragma unroll
-                for (int n1 = 0; n1 < 6; ++n1) sn[n1] = sn[n1 + 2];
-                load_frame<RING, 6, 8>(sn, last ? rs_next : rs_cur, last ? frame0 * kHop - kNfft / 2 + 4 * lane : base_next, ring_pos, ring_len);
-#else
                 load_frame<RING>(sn, last ? rs_next : rs_cur, last ? frame0 * kHop - kNfft / 2 + 4 * lane : base_next, ring_pos,
                                  ring_len);
-#endif
             }
             // ---- real-input split + power: bins k = lane + 64 j and 1024 - k ----
             {
@@ -538,9 +462,6 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
             lds_order();   // the slab and `partial` are rewritten by the next frame
             STAMP(5);
         }
-#if WW_K1_RESIDENT == 2
-        load_frame<RING, 0, 6>(sn, rs_next, frame0 * kHop - kNfft / 2 + 4 * lane_id, ring_pos, ring_len);   // in flight under the epilogue
-#endif
         if constexpr (FR != kFrames) {
             // ---- long clip (T frames of the FR-frame tile): lane = frame, the wave's bands wave, wave + WAVES, ... ----
             __syncthreads();   // all frames' mel bands are in LDS
@@ -852,9 +773,6 @@ __global__ __launch_bounds__(256, 2) void logmel64_kernel(const float* __restric
             fmask = __builtin_amdgcn_readfirstlane(__float_as_uint(__builtin_nontemporal_load(o + 1)));
             if constexpr (FR != kFrames)
                 fmask |= mask_t(__builtin_amdgcn_readfirstlane(__float_as_uint(__builtin_nontemporal_load(o + 2)))) << 32;
-#ifdef WW_ABL_WHOLE_CLIP          // A/B: redo every frame of a marked clip (round 3's behaviour)
-            fmask = 0xffffffffu;
-#endif
             // the other frames' mel powers as the float kernel left them (already carrying the peak gain)
             for (int idx = tid; idx < kMels * nfr; idx += kThreads) {
                 const int b = FR == kFrames ? idx >> 5 : idx / nfr, t = FR == kFrames ? idx & 31 : idx - b * nfr;
@@ -967,9 +885,7 @@ __global__ __launch_bounds__(256, 2) void logmel64_kernel(const float* __restric
                     u[2 * m + 1] = src[512];
                 }
                 lds_order();
-#ifndef WW_K1_ABL_NODFT16              // timing-only ablation: what pass 3's butterflies cost the vector ALU (results are garbage)
                 dft16(u);
-#endif
                 const int lp = (lane >> 3) + 8 * (lane & 7);
                 cd* zw = slabc + (lp ^ ((lp >> 3) & 7));      // Z[k] at k ^ ((k >> 3) & 7): 16-byte elements, conflict-free stores and `a` reads
 #pragma unroll

@@ -380,9 +380,7 @@ __global__ __launch_bounds__(768, 3) void conv2_wgrad_h_kernel(const float* __re
     if (total > 0) produce(0);
     __syncthreads();
     for (int gs = 0; gs < total; ++gs) {
-#ifndef WW_HABL_NOPROD            // timing-only ablation: consumers alone (results are garbage)
         if (gs + 1 < total) produce(gs + 1);
-#endif
         __syncthreads();
     }
     } else {
@@ -471,9 +469,7 @@ __global__ __launch_bounds__(768, 3) void conv2_wgrad_h_kernel(const float* __re
 
     __syncthreads();
     for (int gs = 0; gs < total; ++gs) {
-#ifndef WW_HABL_NOCONS            // timing-only ablation: producers alone
         consume(gs);
-#endif
         __syncthreads();
     }
     {
@@ -980,10 +976,7 @@ __global__ __launch_bounds__(512, 2) void conv2_dgrad_h_kernel(const float* __re
             const int mt = it & 1, kb = (it >> 1) & 1, tp = it >> 2, dy = tp / 3, dx = tp - 3 * dy;
             return __builtin_bit_cast(half8, *reinterpret_cast<const u32x4*>(rowp[dy] + (16 * mt + 1 - dx) * L::kGRec + half * 128 + kb * 64));
         };
-#ifndef WW_DG_PF
-#define WW_DG_PF 3
-#endif
-        constexpr int PF = WW_DG_PF, RING = PF + 1;
+        constexpr int PF = 3, RING = PF + 1;
         half8 fh[RING], fl[DENSE ? RING : 1];
 #pragma unroll
         for (int i = 0; i < PF; ++i) {
