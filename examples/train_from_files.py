@@ -4,7 +4,9 @@ AudioProcessor / WakewordModel -> WakewordDataset x 3 (training split augmented)
 epochs (the loop bodies of WakewordTrainer, :241-289) -> best / final checkpoints.  Only the imports differ from the reference's script:
 every class and `DataLoader` come from `wakeword_jupyterlab_amd`; criterion, optimiser and scheduler are torch's.
 
-    PYTHONPATH=. python examples/train_from_files.py [--epochs 10] [--data DIR] [--lr 1e-4]
+    PYTHONPATH=. python examples/train_from_files.py [--epochs 10] [--data DIR] [--lr 1e-4] [--duration 1.0]
+
+--duration sets AudioConfig.DURATION (0.25 .. 1.0: the clip lengths augmentation and training take).
 """
 import argparse
 import glob
@@ -17,7 +19,7 @@ import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 import torch.optim as optim  # noqa: E402
 
-from wakeword_jupyterlab_amd import AudioProcessor, DataLoader, WakewordDataset, WakewordModel  # noqa: E402
+from wakeword_jupyterlab_amd import AudioConfig, AudioProcessor, DataLoader, WakewordDataset, WakewordModel  # noqa: E402
 from wakeword_jupyterlab_amd.synth import create_sample_data  # noqa: E402
 
 
@@ -58,6 +60,7 @@ def main():
     ap.add_argument("--data", default=".")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--batch-size", type=int, default=16)
+    ap.add_argument("--duration", type=float, default=AudioConfig.DURATION, help="clip length in seconds, 0.25 .. 1.0")
     a = ap.parse_args()
     device = torch.device("cuda")
     print(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
@@ -69,8 +72,9 @@ def main():
     print(f"Wakeword files: {len(wake)}   Negative files: {len(neg)}")
     w_tr, w_va, w_te = split(wake)
     n_tr, n_va, n_te = split(neg)
-    processor = AudioProcessor()
-    model = WakewordModel().to(device)
+    audio_config = type("AudioConfig", (AudioConfig,), {"DURATION": a.duration})
+    processor = AudioProcessor(audio_config)
+    model = WakewordModel(audio_config=audio_config).to(device)
     print(f"Parameters: {sum(p.numel() for p in model.parameters()):,}")
     train_loader = DataLoader(WakewordDataset(w_tr, n_tr, processor, augment=True), batch_size=a.batch_size, shuffle=True, num_workers=2)
     val_loader = DataLoader(WakewordDataset(w_va, n_va, processor, augment=False), batch_size=a.batch_size, shuffle=False, num_workers=2)

@@ -13,8 +13,8 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the legacy default stream).  All launch
  *     functions are asynchronous on that stream, allocate nothing, never synchronise and are
  *     therefore capturable into a hipGraph once ww_init() has run on the device (exception, stated
- *     at the function: ww_augment_f32 reads its plans from host memory and is not capturable; its two-call form
- *     ww_augment_plans_prepare + ww_augment_records_f32 is).
+ *     at the function: ww_augment_f32 / ww_augment_n_f32 read their plans from host memory and are not capturable; the two-call
+ *     forms ww_augment_plans_prepare(_n) + ww_augment_records(_n)_f32 are).
  *   - return value: WW_OK (0) or a negative WW_E* code; ww_last_error() gives the message of the
  *     calling thread's most recent failure.  Nothing falls back to a CPU path: without a usable
  *     gfx950 device every launch function fails with WW_ENODEVICE.
@@ -238,7 +238,7 @@ WW_API int ww_wav_batch_stage(ww_wav_reader* r, int32_t slot, ww_stream_t stream
  * the build's counter-based generator: parity against librosa itself is unpinned (oracle/augment_oracle.py). */
 typedef struct ww_augment_plan {
     int32_t shift;        /* np.roll shift in samples, any sign; 0 = no shift (:106-108) */
-    int32_t crop_start;   /* pad_or_truncate's random crop start after time_stretch, in [0, round(16000/rate) - 16000] */
+    int32_t crop_start;   /* pad_or_truncate's random crop start after time_stretch, in [0, round(16000/rate) - 16000] (N: see *_n below) */
     double pitch_rate;    /* 2^(-n_steps/12) of pitch_shift (:110-112); 0 = off */
     double stretch_rate;  /* time_stretch rate (:114-117); 0 = off.  Both rates: 32/46 <= rate < 32 */
     float noise_sigma;    /* NOISE_FACTOR (:119-121); 0 = off */
@@ -260,6 +260,19 @@ WW_API int64_t ww_augment_record_bytes(void);
 WW_API int ww_augment_plans_prepare(const ww_augment_plan* plans_host, int64_t n_clips, void* records_host);
 WW_API int ww_augment_records_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, const void* records_dev, float* out_dev,
                                   void* workspace_dev, ww_stream_t stream);
+/* The four calls above for clips of n_samples = N samples, WW_MIN_CLIP_SAMPLES <= N <= WW_AUG_MAX_SAMPLES (T = 1 + N / 512 <= 32
+ * frames, what the training kernels take); any other N is WW_EINVAL before anything is launched.  pcm_dev rows as above (16-byte aligned,
+ * clip_stride >= N, clip_stride % 4 == 0); out_dev [n_clips] rows of N samples at out_dev + i*out_stride (out_stride >= N, any value;
+ * 4-byte aligned), may alias pcm_dev.  The plan's shift is reduced mod N and crop_start lies in [0, round(N/rate) - N]; the rate bounds
+ * are the 1 s ones (32/46 <= rate) at every N, with rate < T.  Records (still ww_augment_record_bytes() each) are valid only for the N
+ * they were prepared for.  N = 16000 runs the 1 s kernels: results equal ww_augment_f32's bit for bit. */
+#define WW_AUG_MAX_SAMPLES 16383 /* 1 + 16383 / 512 = 32 frames */
+WW_API int64_t ww_augment_n_workspace_bytes(int64_t n_clips, int64_t n_samples);
+WW_API int ww_augment_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
+                            float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream);
+WW_API int ww_augment_plans_prepare_n(const ww_augment_plan* plans_host, int64_t n_clips, int64_t n_samples, void* records_host);
+WW_API int ww_augment_records_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* records_dev,
+                                    float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream);
 /* The resampler's half-window (32769 floats: 64 zero crossings x 512 + 1) on the host, for checking on a CPU. */
 WW_API int ww_kaiser_best_host(float* out_host);
 

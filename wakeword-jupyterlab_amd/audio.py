@@ -9,8 +9,8 @@ Same method names, arguments and return conventions:
 
 plus the batched form the GPU wants: `mel_batch(pcm[B, n]) -> torch.Tensor [B, 1, 80, T]` on the device.
 T = 32 for the default 1 s config; a config with DURATION in [0.25, 2.0] gives T = 1 + int(16000 * DURATION) // 512 for audio_to_mel and
-mel_batch, and for process_audio_file / load_clips_gpu (K0 crops and pads to N samples): inference.  Augmentation stays 1 s only and
-refuses other durations.
+mel_batch, and for process_audio_file / load_clips_gpu (K0 crops and pads to N samples).  Augmentation runs where training does,
+T <= 32 (DURATION 0.25 .. 1.0, N = 4000 .. 16000 samples), and refuses longer clips.
 
   augment_audio(audio)        -> time shift / pitch shift / time stretch / noise, each with probability 0.8
                                  (random draws from python `random` in the reference's order)  <- HIP kernels KA
@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .config import AudioConfig, AugmentationConfig, check_audio_config, is_one_second, n_samples
+from .config import AudioConfig, AugmentationConfig, check_audio_config, is_one_second, n_frames, n_samples
 
 
 class AudioProcessor:
@@ -117,10 +117,10 @@ class AudioProcessor:
             return ops.logmel(pcm, normalize)
         return ops.logmel_frames(pcm, self._n, normalize)
 
-    def _one_second_only(self, what):
-        if not is_one_second(self.config):
-            raise NotImplementedError(f"{what} at DURATION {self.config.DURATION}: not supported yet (training and augmentation run "
-                                      "1 s clips only; other durations are inference only, augment=False)")
+    def _check_augment(self):
+        if n_frames(self.config) > 32:
+            raise NotImplementedError(f"augmentation at DURATION {self.config.DURATION}: not supported yet (augmentation and training take "
+                                      f"clips of at most 32 frames, DURATION <= 1.0; longer clips are inference only, augment=False)")
 
     def draw_augment_plan(self, config=AugmentationConfig, length=None):
         """The random draws of augment_audio (:103-123) in the reference's order -> one plan dict.
@@ -143,8 +143,9 @@ class AudioProcessor:
         return plan
 
     def augment_batch(self, pcm, plans=None, config=AugmentationConfig) -> torch.Tensor:
-        """pcm [B, 16000] (ndarray or tensor) -> augmented device tensor [B, 16000]; one plan per clip (drawn here if None)."""
-        self._one_second_only("augmentation")
+        """pcm [B, N] (ndarray or tensor) -> augmented device tensor [B, N]; one plan per clip (drawn here if None).
+        N = 16000 at 1 s; any configured clip length of at most 32 frames (DURATION 0.25 .. 1.0)."""
+        self._check_augment()
         t = torch.as_tensor(pcm, dtype=torch.float32)
         if t.device.type != "cuda":
             t = t.to(self._dev(), non_blocking=True)
@@ -153,18 +154,18 @@ class AudioProcessor:
         return ops.augment(t, plans)
 
     def augment_audio(self, audio, config=AugmentationConfig):
-        """[16000] samples -> augmented float32 ndarray [16000] (reference :103-123), on the GPU."""
-        self._one_second_only("augmentation")
+        """[N] samples -> augmented float32 ndarray [N] (reference :103-123), on the GPU (N = 16000 at 1 s)."""
+        self._check_augment()
         a = np.ascontiguousarray(audio, dtype=np.float32)
-        if a.shape != (int(self.config.SAMPLE_RATE * self.config.DURATION),):
-            raise ValueError(f"augment_audio takes exactly one padded clip of 16000 samples, got {a.shape}")
+        if a.shape != (self._n,):
+            raise ValueError(f"augment_audio takes exactly one padded clip of {self._n} samples, got {a.shape}")
         return self.augment_batch(a[None, :], config=config)[0].cpu().numpy()
 
     def process_audio_file(self, file_path, augment=False):
         """load -> normalise over the whole file -> random crop / zero pad -> (augment) -> log-mel (:125-138), all on the GPU:
         native reader -> K0 -> (KA) -> K1.  The random draws are python `random`'s in the reference's order (crop, then augmentation)."""
         if augment:
-            self._one_second_only("augmentation")
+            self._check_augment()
         pcm, ok = self.load_clips_gpu([file_path])
         if not bool(ok[0]):
             return None

@@ -271,7 +271,7 @@ int ww_logmel_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, in
 
 int64_t ww_augment_workspace_bytes(int64_t n_clips) {
     if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
-    return augment_workspace_bytes(n_clips);
+    return augment_workspace_bytes(n_clips, kClip);
 }
 
 int ww_augment_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, const ww_augment_plan* plans_host,
@@ -283,7 +283,7 @@ int ww_augment_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, c
     if ((reinterpret_cast<uintptr_t>(out_dev) & 15) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
         return fail(WW_EINVAL, "out_dev must be 16-byte and workspace_dev 256-byte aligned");
     if (int rc = require_gfx950()) return rc;
-    return launch_augment(pcm_dev, n_clips, clip_stride, plans_host, out_dev, kClip, workspace_dev, static_cast<hipStream_t>(stream));
+    return launch_augment(pcm_dev, n_clips, clip_stride, kClip, plans_host, out_dev, kClip, workspace_dev, static_cast<hipStream_t>(stream));
 }
 
 int64_t ww_augment_record_bytes(void) { return augment_record_bytes(); }
@@ -292,7 +292,7 @@ int ww_augment_plans_prepare(const ww_augment_plan* plans_host, int64_t n_clips,
     if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
     if (n_clips == 0) return WW_OK;
     if (!plans_host || !records_host) return fail(WW_EINVAL, "null plan / record pointer");
-    return augment_prepare(plans_host, n_clips, records_host, nullptr, nullptr);
+    return augment_prepare(plans_host, n_clips, kClip, records_host, nullptr, nullptr);
 }
 
 int ww_augment_records_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, const void* records_dev, float* out_dev,
@@ -304,7 +304,64 @@ int ww_augment_records_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_s
     if ((reinterpret_cast<uintptr_t>(out_dev) & 15) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255) || (reinterpret_cast<uintptr_t>(records_dev) & 7))
         return fail(WW_EINVAL, "out_dev must be 16-byte, workspace_dev 256-byte and records_dev 8-byte aligned");
     if (int rc = require_gfx950()) return rc;
-    return launch_augment_records(pcm_dev, n_clips, clip_stride, records_dev, true, true, out_dev, kClip, workspace_dev, static_cast<hipStream_t>(stream));
+    return launch_augment_records(pcm_dev, n_clips, clip_stride, kClip, records_dev, true, true, out_dev, kClip, workspace_dev,
+                                  static_cast<hipStream_t>(stream));
+}
+
+// ---- augmentation of clips of n_samples in [WW_MIN_CLIP_SAMPLES, WW_AUG_MAX_SAMPLES] (the 1 s entry points above are unchanged) ----
+static int check_aug_samples(int64_t n_samples) {
+    if (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_AUG_MAX_SAMPLES)
+        return fail(WW_EINVAL, "n_samples %lld: augmentation takes %d..%d samples (0.25 s .. 32 frames at 16 kHz)", (long long)n_samples,
+                    WW_MIN_CLIP_SAMPLES, WW_AUG_MAX_SAMPLES);
+    return WW_OK;
+}
+static int check_aug_rows(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* plans, float* out_dev,
+                          int64_t out_stride, void* workspace_dev) {
+    if (int rc = check_aug_samples(n_samples)) return rc;
+    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (n_clips == 0) return WW_OK;
+    if (!pcm_dev || !plans || !out_dev || !workspace_dev) return fail(WW_EINVAL, "null pcm / plan / output / workspace pointer");
+    if (n_clips > 1 && (clip_stride < n_samples || out_stride < n_samples))
+        return fail(WW_EINVAL, "clip_stride %lld / out_stride %lld < n_samples %lld", (long long)clip_stride, (long long)out_stride,
+                    (long long)n_samples);
+    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 15) || (n_clips > 1 && (clip_stride & 3)))
+        return fail(WW_EINVAL, "pcm must be 16-byte aligned with clip_stride %% 4 == 0 (got %p, %lld)", (const void*)pcm_dev, (long long)clip_stride);
+    if ((reinterpret_cast<uintptr_t>(out_dev) & 3) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
+        return fail(WW_EINVAL, "out_dev must be 4-byte and workspace_dev 256-byte aligned");
+    return WW_OK;
+}
+
+int64_t ww_augment_n_workspace_bytes(int64_t n_clips, int64_t n_samples) {
+    if (int rc = check_aug_samples(n_samples)) return rc;
+    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    return augment_workspace_bytes(n_clips, n_samples);
+}
+
+int ww_augment_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
+                     float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream) {
+    if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, plans_host, out_dev, out_stride, workspace_dev)) return rc;
+    if (n_clips == 0) return WW_OK;
+    if (int rc = require_gfx950()) return rc;
+    return launch_augment(pcm_dev, n_clips, clip_stride, n_samples, plans_host, out_dev, out_stride, workspace_dev,
+                          static_cast<hipStream_t>(stream));
+}
+
+int ww_augment_plans_prepare_n(const ww_augment_plan* plans_host, int64_t n_clips, int64_t n_samples, void* records_host) {
+    if (int rc = check_aug_samples(n_samples)) return rc;
+    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (n_clips == 0) return WW_OK;
+    if (!plans_host || !records_host) return fail(WW_EINVAL, "null plan / record pointer");
+    return augment_prepare(plans_host, n_clips, n_samples, records_host, nullptr, nullptr);
+}
+
+int ww_augment_records_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* records_dev,
+                             float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream) {
+    if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, records_dev, out_dev, out_stride, workspace_dev)) return rc;
+    if (n_clips == 0) return WW_OK;
+    if (reinterpret_cast<uintptr_t>(records_dev) & 7) return fail(WW_EINVAL, "records_dev must be 8-byte aligned");
+    if (int rc = require_gfx950()) return rc;
+    return launch_augment_records(pcm_dev, n_clips, clip_stride, n_samples, records_dev, true, true, out_dev, out_stride, workspace_dev,
+                                  static_cast<hipStream_t>(stream));
 }
 
 int64_t ww_cnn_scratch_bytes(int64_t n, int32_t n_conv) { return cnn_scratch_bytes(n, n_conv); }

@@ -18,6 +18,13 @@
 //                     for librosa's soxr_hq (absent third-party library; parity unpinned)
 //   noise_kernel      + sigma * normal(seed, i), the build's counter-based generator (splitmix64 -> Box-Muller)
 // Clips whose plan switches a transform off skip its kernels (their blocks copy the data through).
+//
+// Clip length: every kernel is a template on kN, the samples per clip -- 16000 (the 1 s entry points, a compile-time constant as before)
+// or 0 (run-time `n`, 4000 <= n <= 16383: the *_n entry points), T = 1 + n / 512 <= 32 STFT frames.  At run-time n the work-buffer
+// rows (bufA / bufB) are padded to a multiple of four floats for the float4 accesses; the padding is never used as a sample (stft_pv
+// loads it and zeroes it).
+// Each kernel forms L (samples per clip) and row (floats per work-buffer row) as `kN ? kN : ...` in place, so the 1 s instance folds them
+// to the constants it always had and compiles to the same code as before.
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -27,8 +34,8 @@
 
 namespace ww {
 
-constexpr int kAugFrames = kFrames;                 // STFT frames of a 16000-sample clip (1 + 16000/512 = 32)
-constexpr int kAugMaxOut = 46;                      // phase-vocoder output steps: ceil(32 / rate), rate >= 32/46
+constexpr int kAugFrames = kFrames;                 // STFT frames of a 16000-sample clip (1 + 16000/512 = 32), the most any length has
+constexpr int kAugMaxOut = 46;                      // phase-vocoder output steps: ceil(32 / rate), rate >= 32/46 (for every clip length)
 constexpr int kAugYStride = 25600;                  // stretched-clip scratch row
 constexpr int kSpec = kBins;                        // 1025 complex bins per spectrum row
 
@@ -44,21 +51,37 @@ struct AugDev {            // one per clip, derived on the host from ww_augment_
 };
 
 // ------------------------------------------------------------------------------------------------
+template <int kN>
 __global__ __launch_bounds__(256) void roll_kernel(const float* __restrict__ in, int64_t stride, const AugDev* __restrict__ plan,
-                                                   float* __restrict__ out) {
+                                                   float* __restrict__ out, int n) {
+    const int L = kN ? kN : n, row = kN ? kN : (n + 3) & ~3;
     const int clip = blockIdx.y;
-    const int i = 4 * (blockIdx.x * 256 + threadIdx.x);          // four outputs per thread: one 16-byte store (kClip % 4 == 0)
-    if (i >= kClip) return;
+    const int i = 4 * (blockIdx.x * 256 + threadIdx.x);          // four outputs per thread: one 16-byte store (row % 4 == 0)
+    if (i >= L) return;
     const float* __restrict__ x = in + int64_t(clip) * stride;
-    int src = i - plan[clip].shift;
-    src += src < 0 ? kClip : 0;
     float4 v;
-    if (src + 3 < kClip) { v.x = x[src]; v.y = x[src + 1]; v.z = x[src + 2]; v.w = x[src + 3]; }
-    else {                                                       // the wrap falls inside this group of four
-        v.x = x[src]; v.y = x[src + 1 < kClip ? src + 1 : src + 1 - kClip];
-        v.z = x[src + 2 < kClip ? src + 2 : src + 2 - kClip]; v.w = x[src + 3 - kClip];
+    if constexpr (kN != 0) {
+        int src = i - plan[clip].shift;
+        src += src < 0 ? kN : 0;
+        if (src + 3 < kN) { v.x = x[src]; v.y = x[src + 1]; v.z = x[src + 2]; v.w = x[src + 3]; }
+        else {                                                   // the wrap falls inside this group of four
+            v.x = x[src]; v.y = x[src + 1 < kN ? src + 1 : src + 1 - kN];
+            v.z = x[src + 2 < kN ? src + 2 : src + 2 - kN]; v.w = x[src + 3 - kN];
+        }
+    } else {
+        // the shift is reduced again against this n (records prepared for another length stay inside the row); the row's last group
+        // of four may pass its end: those outputs are the padding (zero), nothing past the row is read
+        int src = i - plan[clip].shift % L;
+        src += src < 0 ? L : 0;
+        float* pv = &v.x;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            int s = src + q;
+            s -= s >= L ? L : 0;
+            pv[q] = i + q < L ? x[s] : 0.f;
+        }
     }
-    *reinterpret_cast<float4*>(out + int64_t(clip) * kClip + i) = v;
+    *reinterpret_cast<float4*>(out + int64_t(clip) * row + i) = v;
 }
 
 // atan2 for the vocoder: a = min/max in [0, 1], atan(a) = a P(a^2) (degree 8 in a^2, |err| <= 1.2e-7 in float32 evaluation -- the size of
@@ -115,18 +138,21 @@ __device__ __forceinline__ void pv_sincos(float acc, float& sn, float& cs) {
 // transformed into a ring of eight LDS slabs and split IN PLACE into their spectrum column (a lane reads Z[k], Z[1024-k] and writes
 // D[k], D[1024-k] back to the same two slots; D[1024] takes the slab's spare slot), then every thread advances its bins' vocoder state
 // over the output steps whose two columns are there.  A step reads columns i0, i0 + 1 with i0 non-decreasing, so round r + 1 may
-// overwrite the columns of round r - 1 (two barriers per round).
+// overwrite the columns of round r - 1 (two barriers per round).  ceil(T / 4) rounds: a last round that is only partly inside the clip
+// transforms frames >= T too, but no step reads them -- the vocoder sees zero columns past T - 1, as librosa's padded D.
 constexpr int kStftPvLds = 8 * fft::kSlabFloats * int(sizeof(float));                    // 65,664 B: two workgroups per CU
 
+template <int kN>
 __global__ __launch_bounds__(256) void stft_pv_kernel(const float* __restrict__ x, const AugDev* __restrict__ plan, int which,
-                                                      const LogmelTables* __restrict__ tb, float2* __restrict__ S) {
+                                                      const LogmelTables* __restrict__ tb, float2* __restrict__ S, int n) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int clip = blockIdx.x, tid = threadIdx.x;
     const int n_out = which == 0 ? plan[clip].p_out : plan[clip].s_out;
     if (n_out == 0) return;
     const double rate = which == 0 ? plan[clip].p_rate : plan[clip].s_rate;
     const int lane = tid & 63, wave = tid >> 6;
-    const float* xc = x + int64_t(clip) * kClip;
+    const int L = kN ? kN : n, row = kN ? kN : (n + 3) & ~3, T = 1 + L / kHop;      // T = kAugFrames at 1 s
+    const float* xc = x + int64_t(clip) * row;
     const float4* win4 = reinterpret_cast<const float4*>(&tb->window[0]);
     float2* Sc = S + int64_t(clip) * kAugMaxOut * kSpec;
     constexpr int kB = 5;                                        // bins tid + 256 b; b = 4 is bin 1024 (thread 0 only)
@@ -134,7 +160,7 @@ __global__ __launch_bounds__(256) void stft_pv_kernel(const float* __restrict__ 
 #pragma unroll
     for (int b = 0; b < kB; ++b) { acc[b] = 0.f; m0[b] = 0.f; a0[b] = 0.f; m1[b] = 0.f; a1[b] = 0.f; }
     int have = -2, t = 0;
-    for (int r = 0; r < kAugFrames / 4; ++r) {
+    for (int r = 0; r < (T + 3) / 4; ++r) {
         {
             const int frame = 4 * r + wave;
             float* slab = lds + (frame & 7) * fft::kSlabFloats;
@@ -143,8 +169,19 @@ __global__ __launch_bounds__(256) void stft_pv_kernel(const float* __restrict__ 
             const int base = frame * kHop - kNfft / 2 + 4 * lane;
 #pragma unroll
             for (int n1 = 0; n1 < 8; ++n1) {
-                const int idx = base + 256 * n1;
-                const float4 s = (idx >= 0 && idx < kClip) ? *reinterpret_cast<const float4*>(xc + idx) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const int idx = base + 256 * n1;                 // a multiple of 4
+                float4 s;
+                if constexpr (kN != 0) {
+                    s = (idx >= 0 && idx < kN) ? *reinterpret_cast<const float4*>(xc + idx) : make_float4(0.f, 0.f, 0.f, 0.f);
+                } else {
+                    // the rows are padded to a multiple of 4, so a group that starts inside the row is one 16-byte load within it; its
+                    // lanes past L (the padding) are replaced by zeros -- selected, never used as samples (a branchy partial load here
+                    // took 1.43 instead of 1.11 ms per 4096 clips at T = 32)
+                    s = (idx >= 0 && idx < L) ? *reinterpret_cast<const float4*>(xc + idx) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    s.y = idx + 1 < L ? s.y : 0.f;
+                    s.z = idx + 2 < L ? s.z : 0.f;
+                    s.w = idx + 3 < L ? s.w : 0.f;
+                }
                 const float4 w = win4[64 * n1 + lane];
                 za[n1] = make_float2(s.x * w.x, s.y * w.y);
                 zb[n1] = make_float2(s.z * w.z, s.w * w.w);
@@ -180,7 +217,7 @@ __global__ __launch_bounds__(256) void stft_pv_kernel(const float* __restrict__ 
             for (; t < n_out; ++t) {
                 const double step = double(t) * rate;
                 const int i0 = int(step);
-                if ((i0 + 1 < kAugFrames ? i0 + 1 : kAugFrames - 1) > last) break;      // this step's columns come with a later round
+                if ((i0 + 1 < T ? i0 + 1 : T - 1) > last) break;                  // this step's columns come with a later round
                 const double alpha = step - double(i0);
                 const bool fresh0 = i0 != have && i0 != have + 1, fresh1 = i0 != have;
                 const float2* c0 = reinterpret_cast<const float2*>(lds + (i0 & 7) * fft::kSlabFloats);
@@ -193,11 +230,11 @@ __global__ __launch_bounds__(256) void stft_pv_kernel(const float* __restrict__ 
                         if (fresh1) {
                             if (!fresh0) { m0[b] = m1[b]; a0[b] = a1[b]; }
                             else {
-                                const float2 v = i0 < kAugFrames ? c0[fft::zpos(k)] : make_float2(0.f, 0.f);
+                                const float2 v = i0 < T ? c0[fft::zpos(k)] : make_float2(0.f, 0.f);
                                 m0[b] = pv_abs(v);
                                 a0[b] = pv_atan2(v.y, v.x);
                             }
-                            const float2 v = i0 + 1 < kAugFrames ? c1[fft::zpos(k)] : make_float2(0.f, 0.f);
+                            const float2 v = i0 + 1 < T ? c1[fft::zpos(k)] : make_float2(0.f, 0.f);
                             m1[b] = pv_abs(v);
                             a1[b] = pv_atan2(v.y, v.x);
                         }
@@ -226,22 +263,24 @@ constexpr int kIstftLds = kIstftSlabs * fft::kSlabFloats * int(sizeof(float));  
 // Four frames per round (one per wave) into a ring of eight slabs.  A sample of the padded signal in hop segment s is
 // covered by frames s-3..s, so after round r the segments 4r..4r+3 are complete: they are summed straight from the
 // slabs in frame order (librosa's order), normalised and stored -- no overlap-add buffer, two barriers per round.
+template <int kN>
 __global__ __launch_bounds__(256) void istft_kernel(const float2* __restrict__ S, const AugDev* __restrict__ plan, int which,
                                                     const LogmelTables* __restrict__ tb, const float* __restrict__ passthru,
-                                                    float* __restrict__ dst, int64_t dst_stride) {
+                                                    float* __restrict__ dst, int64_t dst_stride, int n_rt) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int clip = blockIdx.x, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int n_out = which == 0 ? plan[clip].p_out : plan[clip].s_out;
+    const int L = kN ? kN : n_rt, row = kN ? kN : (n_rt + 3) & ~3;
     float* out = dst + int64_t(clip) * dst_stride;
     if (n_out == 0) {
         if (passthru)
-            for (int i = tid; i < kClip; i += 256) out[i] = passthru[int64_t(clip) * kClip + i];
+            for (int i = tid; i < L; i += 256) out[i] = passthru[int64_t(clip) * row + i];
         return;
     }
     const int length = which == 0 ? plan[clip].p_len : plan[clip].s_len;
     const int crop = which == 0 ? 0 : plan[clip].crop;
-    const int dst_len = which == 0 ? length : kClip;
+    const int dst_len = which == 0 ? length : L;
     int n_frames = (length + kNfft + kHop - 1) / kHop;           // ceil((length + n_fft) / hop)
     n_frames = n_frames < n_out ? n_frames : n_out;
     const float2* Sc = S + int64_t(clip) * kAugMaxOut * kSpec;
@@ -316,14 +355,16 @@ constexpr int kResampleLds = 150 * 1024;
 // one 16-byte global load.  Same weights, same fused multiply-adds in the same order: the results are bit-identical to the round-2 kernel.
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));       // four consecutive samples at a 4-byte aligned address
 
+template <int kN>
 __global__ __launch_bounds__(1024) void resample_kernel(const float* __restrict__ Y, const AugDev* __restrict__ plan,
                                                         const LogmelTables* __restrict__ tb, const float* __restrict__ passthru,
-                                                        float* __restrict__ out) {
+                                                        float* __restrict__ out, int n_rt) {
     extern __shared__ __attribute__((aligned(16))) float P[];   // [step + 2][R]
     const int clip = blockIdx.x, tid = threadIdx.x;
-    float* o = out + int64_t(clip) * kClip;
+    const int L = kN ? kN : n_rt, row = kN ? kN : (n_rt + 3) & ~3;
+    float* o = out + int64_t(clip) * row;
     if (plan[clip].p_out == 0) {
-        for (int i = tid; i < kClip; i += 1024) o[i] = passthru[int64_t(clip) * kClip + i];
+        for (int i = tid; i < L; i += 1024) o[i] = passthru[int64_t(clip) * row + i];
         return;
     }
     const double ratio = plan[clip].p_ratio;
@@ -346,7 +387,7 @@ __global__ __launch_bounds__(1024) void resample_kernel(const float* __restrict_
     const int n_orig = plan[clip].p_len, n_res = plan[clip].p_res;
     const float* y = Y + int64_t(clip) * kAugYStride;
     const double inv = 1.0 / ratio;
-    for (int t = tid; t < kClip; t += 1024) {
+    for (int t = tid; t < L; t += 1024) {
         // positions and table fractions in float64 (t / ratio needs ~15 integer + 9 fraction bits); the ~140 products per
         // output are float32 FMAs in two independent chains (left wing, right wing), each in tap order.  The two wings advance in
         // lock-step while both have taps left (round 3: twice the loads in flight per wave -- the kernel waits on its table and sample
@@ -437,12 +478,14 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
 // Four samples per thread (float4 in, float4 out).  The uniforms are the hash generator's exact 32-bit words; Box-Muller runs in float32
 // (round 2: float64 log / sqrt / cos, 0.35 ms per 4096 clips for a 0.5 GB stream; the float32 form is bound by that stream).  Against the
 // float64 evaluation the normal deviate moves by <= 3e-7 of sigma, four orders under the augmentation tests' tolerance.
+template <int kN>
 __global__ __launch_bounds__(256) void noise_kernel(const float* __restrict__ in, const AugDev* __restrict__ plan,
-                                                    float* __restrict__ out, int64_t out_stride) {
+                                                    float* __restrict__ out, int64_t out_stride, int n) {
+    const int L = kN ? kN : n, row = kN ? kN : (n + 3) & ~3;
     const int clip = blockIdx.y;
     const int i = 4 * (blockIdx.x * 256 + threadIdx.x);
-    if (i >= kClip) return;
-    float4 v = *reinterpret_cast<const float4*>(in + int64_t(clip) * kClip + i);
+    if (i >= L) return;
+    float4 v = *reinterpret_cast<const float4*>(in + int64_t(clip) * row + i);          // (padding lanes are not stored)
     const float sigma = plan[clip].sigma;
     if (sigma != 0.f) {
         const uint64_t seed = plan[clip].seed;
@@ -460,15 +503,30 @@ __global__ __launch_bounds__(256) void noise_kernel(const float* __restrict__ in
         }
     }
     float* o = out + int64_t(clip) * out_stride + i;
-    if ((out_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) *reinterpret_cast<float4*>(o) = v;
-    else { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+    if constexpr (kN != 0) {
+        if ((out_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) *reinterpret_cast<float4*>(o) = v;
+        else { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+    } else {
+        if (i + 3 < L && (out_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) *reinterpret_cast<float4*>(o) = v;
+        else {
+            o[0] = v.x;
+            if (i + 1 < L) o[1] = v.y;
+            if (i + 2 < L) o[2] = v.z;
+            if (i + 3 < L) o[3] = v.w;
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
 static int64_t up256(int64_t b) { return (b + 255) & ~int64_t(255); }
 
-int64_t augment_workspace_bytes(int64_t n) {
-    return up256(n * int64_t(sizeof(AugDev))) + 2 * up256(n * int64_t(kClip) * 4) + up256(n * int64_t(kAugMaxOut) * kSpec * 8) +
+static int64_t aug_row_host(int64_t n_samples) { return (n_samples + 3) & ~int64_t(3); }
+
+// The spectrogram and stretched-clip scratch keep their 1 s strides at every length: both are sized by the rate bounds, which do not
+// change with the length (round(16383 / (32 / 46)) = 23551 <= kAugYStride)
+int64_t augment_workspace_bytes(int64_t n, int64_t n_samples) {
+    const int64_t row = aug_row_host(n_samples);
+    return up256(n * int64_t(sizeof(AugDev))) + 2 * up256(n * row * 4) + up256(n * int64_t(kAugMaxOut) * kSpec * 8) +
            up256(n * int64_t(kAugYStride) * 4);
 }
 
@@ -484,29 +542,34 @@ static std::mutex g_stage_mu;
 static PlanStage g_stage[16][2];
 static int g_stage_next[16] = {};
 
-// plans -> the per-clip records the kernels read (librosa's lengths are host arithmetic: len(np.arange), round, ceil)
-int augment_prepare(const ww_augment_plan* plans_host, int64_t n, void* records_host, int* any_pitch_out, int* any_stretch_out) {
+// plans -> the per-clip records the kernels read (librosa's lengths are host arithmetic: len(np.arange), round, ceil), for clips of
+// n_samples = N samples, T = 1 + N / 512 frames.  The rate bounds are the 1 s ones at every N (ceil(32 / rate) <= kAugMaxOut: the scratch
+// strides and the resampler's LDS table are sized by them); the upper bound is ceil(T / rate) >= 2.
+int augment_prepare(const ww_augment_plan* plans_host, int64_t n, int64_t n_samples, void* records_host, int* any_pitch_out,
+                    int* any_stretch_out) {
     AugDev* host = static_cast<AugDev*>(records_host);
+    const int N = int(n_samples), T = 1 + N / kHop;
     bool any_pitch = false, any_stretch = false;
     for (int64_t c = 0; c < n; ++c) {
         const ww_augment_plan& p = plans_host[c];
         AugDev d = {};
-        int64_t sh = int64_t(p.shift) % kClip;
-        d.shift = int32_t(sh < 0 ? sh + kClip : sh);
+        int64_t sh = int64_t(p.shift) % N;
+        d.shift = int32_t(sh < 0 ? sh + N : sh);
         d.sigma = p.noise_sigma;
         d.seed = p.noise_seed;
         if (!(p.noise_sigma >= 0.f)) return fail(WW_EINVAL, "plan %lld: noise_sigma must be >= 0", (long long)c);
-        auto steps = [](double rate) { return int(std::ceil(double(kAugFrames) / rate)); };
+        auto steps = [T](double rate) { return int(std::ceil(double(T) / rate)); };
         auto check = [&](double rate, const char* what) {
-            if (!(rate > 0.0) || steps(rate) > kAugMaxOut || steps(rate) < 2)
-                return fail(WW_EUNSUPPORTED, "plan %lld: %s rate %g outside [%g, 32)", (long long)c, what, rate, double(kAugFrames) / kAugMaxOut);
+            if (!(rate > 0.0) || int(std::ceil(double(kAugFrames) / rate)) > kAugMaxOut || steps(rate) < 2)
+                return fail(WW_EUNSUPPORTED, "plan %lld: %s rate %g outside [%g, %d) for clips of %d samples", (long long)c, what, rate,
+                            double(kAugFrames) / kAugMaxOut, T, N);
             return int(WW_OK);
         };
         if (p.pitch_rate != 0.0) {
             if (int rc = check(p.pitch_rate, "pitch")) return rc;
             d.p_rate = p.pitch_rate;
             d.p_out = steps(p.pitch_rate);
-            d.p_len = int32_t(std::nearbyint(double(kClip) / p.pitch_rate));      // Python round(): half to even
+            d.p_len = int32_t(std::nearbyint(double(N) / p.pitch_rate));          // Python round(): half to even
             d.p_ratio = double(WW_SAMPLE_RATE) / (double(WW_SAMPLE_RATE) / p.pitch_rate);
             d.p_res = int32_t(std::ceil(double(d.p_len) * d.p_ratio));
             any_pitch = true;
@@ -515,10 +578,10 @@ int augment_prepare(const ww_augment_plan* plans_host, int64_t n, void* records_
             if (int rc = check(p.stretch_rate, "stretch")) return rc;
             d.s_rate = p.stretch_rate;
             d.s_out = steps(p.stretch_rate);
-            d.s_len = int32_t(std::nearbyint(double(kClip) / p.stretch_rate));
-            const int over = d.s_len > kClip ? d.s_len - kClip : 0;
+            d.s_len = int32_t(std::nearbyint(double(N) / p.stretch_rate));
+            const int over = d.s_len > N ? d.s_len - N : 0;
             if (p.crop_start < 0 || p.crop_start > over)
-                return fail(WW_EINVAL, "plan %lld: crop_start %d outside [0, %d]", (long long)c, p.crop_start, over);
+                return fail(WW_EINVAL, "plan %lld: crop_start %d outside [0, %d] for clips of %d samples", (long long)c, p.crop_start, over, N);
             d.crop = p.crop_start;
             any_stretch = true;
         }
@@ -532,16 +595,16 @@ int64_t augment_record_bytes() { return int64_t(sizeof(AugDev)); }
 
 // The kernels alone, on records already in device memory: nothing but launches on `stream` (capturable into a hipGraph).  A stage whose
 // flag is off for a clip copies that clip through, so both stages may always be launched (what a captured graph must do).
-int launch_augment_records(const float* pcm, int64_t n, int64_t stride, const void* records_dev, bool any_pitch, bool any_stretch, float* out,
-                           int64_t out_stride, void* workspace, hipStream_t stream) {
-    if (n == 0) return WW_OK;
+template <int kN>
+static int launch_records(const float* pcm, int64_t n, int64_t stride, int n_samples, const AugDev* plan, bool any_pitch, bool any_stretch,
+                          float* out, int64_t out_stride, void* workspace, hipStream_t stream) {
     const LogmelTables* tb = device_tables();
     if (!tb) return WW_EHIP;
-    const AugDev* plan = static_cast<const AugDev*>(records_dev);
+    const int64_t row = aug_row_host(n_samples);
     char* w = static_cast<char*>(workspace);
     w += up256(n * int64_t(sizeof(AugDev)));                        // (the slot ww_augment_f32 copies its records into)
-    float* bufA = reinterpret_cast<float*>(w); w += up256(n * int64_t(kClip) * 4);
-    float* bufB = reinterpret_cast<float*>(w); w += up256(n * int64_t(kClip) * 4);
+    float* bufA = reinterpret_cast<float*>(w); w += up256(n * row * 4);
+    float* bufB = reinterpret_cast<float*>(w); w += up256(n * row * 4);
     float2* S = reinterpret_cast<float2*>(w); w += up256(n * int64_t(kAugMaxOut) * kSpec * 8);
     float* Y = reinterpret_cast<float*>(w);
     {
@@ -551,39 +614,50 @@ int launch_augment_records(const float* pcm, int64_t n, int64_t stride, const vo
         int dev = 0;
         WW_HIP(hipGetDevice(&dev));
         if (dev >= 0 && dev < 64 && !attr[dev]) {
-            WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kIstftLds));
-            WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stft_pv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kStftPvLds));
-            WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(resample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kResampleLds));
+            WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(istft_kernel<kN>), hipFuncAttributeMaxDynamicSharedMemorySize, kIstftLds));
+            WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stft_pv_kernel<kN>), hipFuncAttributeMaxDynamicSharedMemorySize, kStftPvLds));
+            WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(resample_kernel<kN>), hipFuncAttributeMaxDynamicSharedMemorySize, kResampleLds));
             attr[dev] = true;
         }
     }
-    const dim3 egrid((kClip / 4 + 255) / 256, unsigned(n));
-    hipLaunchKernelGGL(roll_kernel, egrid, dim3(256), 0, stream, pcm, stride, plan, bufA);
+    const int nn = n_samples;
+    const dim3 egrid(unsigned((row / 4 + 255) / 256), unsigned(n));
+    hipLaunchKernelGGL(roll_kernel<kN>, egrid, dim3(256), 0, stream, pcm, stride, plan, bufA, nn);
     float* cur = bufA;
     float* other = bufB;
     if (any_pitch) {
-        hipLaunchKernelGGL(stft_pv_kernel, dim3(unsigned(n)), dim3(256), kStftPvLds, stream, cur, plan, 0, tb, S);
-        hipLaunchKernelGGL(istft_kernel, dim3(unsigned(n)), dim3(256), kIstftLds, stream, S, plan, 0, tb,
-                           static_cast<const float*>(nullptr), Y, int64_t(kAugYStride));
-        hipLaunchKernelGGL(resample_kernel, dim3(unsigned(n)), dim3(1024), kResampleLds, stream, Y, plan, tb, cur, other);
+        hipLaunchKernelGGL(stft_pv_kernel<kN>, dim3(unsigned(n)), dim3(256), kStftPvLds, stream, cur, plan, 0, tb, S, nn);
+        hipLaunchKernelGGL(istft_kernel<kN>, dim3(unsigned(n)), dim3(256), kIstftLds, stream, S, plan, 0, tb,
+                           static_cast<const float*>(nullptr), Y, int64_t(kAugYStride), nn);
+        hipLaunchKernelGGL(resample_kernel<kN>, dim3(unsigned(n)), dim3(1024), kResampleLds, stream, Y, plan, tb, cur, other, nn);
         float* t = cur; cur = other; other = t;
     }
     if (any_stretch) {
-        hipLaunchKernelGGL(stft_pv_kernel, dim3(unsigned(n)), dim3(256), kStftPvLds, stream, cur, plan, 1, tb, S);
-        hipLaunchKernelGGL(istft_kernel, dim3(unsigned(n)), dim3(256), kIstftLds, stream, S, plan, 1, tb, cur, other, int64_t(kClip));
+        hipLaunchKernelGGL(stft_pv_kernel<kN>, dim3(unsigned(n)), dim3(256), kStftPvLds, stream, cur, plan, 1, tb, S, nn);
+        hipLaunchKernelGGL(istft_kernel<kN>, dim3(unsigned(n)), dim3(256), kIstftLds, stream, S, plan, 1, tb, cur, other, row, nn);
         float* t = cur; cur = other; other = t;
     }
-    hipLaunchKernelGGL(noise_kernel, dim3((kClip / 4 + 255) / 256, unsigned(n)), dim3(256), 0, stream, cur, plan, out, out_stride);
+    hipLaunchKernelGGL(noise_kernel<kN>, egrid, dim3(256), 0, stream, cur, plan, out, out_stride, nn);
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
 
-int launch_augment(const float* pcm, int64_t n, int64_t stride, const ww_augment_plan* plans_host, float* out,
+// 16000 samples run the compile-time 1 s instance (the kernels the 1 s entry points always ran), every other length the run-time one
+int launch_augment_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, bool any_pitch,
+                           bool any_stretch, float* out, int64_t out_stride, void* workspace, hipStream_t stream) {
+    if (n == 0) return WW_OK;
+    const AugDev* plan = static_cast<const AugDev*>(records_dev);
+    if (n_samples == kClip)
+        return launch_records<kClip>(pcm, n, stride, kClip, plan, any_pitch, any_stretch, out, out_stride, workspace, stream);
+    return launch_records<0>(pcm, n, stride, int(n_samples), plan, any_pitch, any_stretch, out, out_stride, workspace, stream);
+}
+
+int launch_augment(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host, float* out,
                    int64_t out_stride, void* workspace, hipStream_t stream) {
     if (n == 0) return WW_OK;
     std::vector<AugDev> host(static_cast<size_t>(n));
     int any_pitch = 0, any_stretch = 0;
-    if (int rc = augment_prepare(plans_host, n, host.data(), &any_pitch, &any_stretch)) return rc;
+    if (int rc = augment_prepare(plans_host, n, n_samples, host.data(), &any_pitch, &any_stretch)) return rc;
     AugDev* plan = reinterpret_cast<AugDev*>(workspace);
     {
         int dev = 0;
@@ -606,7 +680,7 @@ int launch_augment(const float* pcm, int64_t n, int64_t stride, const ww_augment
         WW_HIP(hipEventRecord(st.ev, stream));
         st.in_use = true;
     }
-    return launch_augment_records(pcm, n, stride, plan, any_pitch != 0, any_stretch != 0, out, out_stride, workspace, stream);
+    return launch_augment_records(pcm, n, stride, n_samples, plan, any_pitch != 0, any_stretch != 0, out, out_stride, workspace, stream);
 }
 
 }  // namespace ww

@@ -121,13 +121,15 @@ int launch_logmel_frames(const float* pcm, int64_t n_clips, int64_t clip_stride,
 // quiet bands sit on the f32 FFT's rounding floor are redone in f64)
 int logmel_math_mode();
 void set_logmel_math_mode(int mode);
-int launch_augment(const float* pcm, int64_t n, int64_t stride, const ww_augment_plan* plans_host, float* out,
+// augmentation of clips of n_samples samples: 16000 (the 1 s entry points) or 4000 .. 16383 (the *_n entry points; the callers check the range)
+int launch_augment(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host, float* out,
                    int64_t out_stride, void* workspace, hipStream_t stream);
-int64_t augment_workspace_bytes(int64_t n);
-int augment_prepare(const ww_augment_plan* plans_host, int64_t n, void* records_host, int* any_pitch_out, int* any_stretch_out);
+int64_t augment_workspace_bytes(int64_t n, int64_t n_samples);
+int augment_prepare(const ww_augment_plan* plans_host, int64_t n, int64_t n_samples, void* records_host, int* any_pitch_out,
+                    int* any_stretch_out);
 int64_t augment_record_bytes();
-int launch_augment_records(const float* pcm, int64_t n, int64_t stride, const void* records_dev, bool any_pitch, bool any_stretch, float* out,
-                           int64_t out_stride, void* workspace, hipStream_t stream);
+int launch_augment_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, bool any_pitch,
+                           bool any_stretch, float* out, int64_t out_stride, void* workspace, hipStream_t stream);
 void build_kaiser_best(float* out /*[32769]*/);
 int sync_timeouts(unsigned int* count);   // bounded LDS-counter waits that expired (must be 0)
 int launch_cnn_pool(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch,

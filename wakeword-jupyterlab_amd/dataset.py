@@ -1,19 +1,20 @@
 """WakewordDataset drop-in (reference: /root/reference/wakeword_training_script.py:187-216, notebook cell 9).
 
-`dataset[idx]` returns `(FloatTensor [1, 80, 32], LongTensor [1])` exactly like the reference.  Because a
+`dataset[idx]` returns `(FloatTensor [1, 80, T], LongTensor [1])` exactly like the reference (T = 32 at 1 s).  Because a
 GPU-backed `__getitem__` must not initialise HIP inside forked DataLoader workers, the per-item call is
 meant for `num_workers=0`; the fast path is `loader(batch_size, shuffle)` (and `batches(batch_size)`, the same in file
 order): the library's reader threads feed kernels K0 / KA / K1 once per batch, yielding device tensors with
-`default_collate`'s shapes (`data [B,1,80,32]`, `target [B,1]`) -- the drop-in for the reference's
+`default_collate`'s shapes (`data [B,1,80,T]`, `target [B,1]`) -- the drop-in for the reference's
 `DataLoader(dataset, batch_size=16, shuffle=True, num_workers=2)` line.
 
 One deliberate deviation: when a file fails to load the reference substitutes `np.zeros((80, 31))`
 (:210-211), whose width (31) differs from real items (32) and makes `default_collate` raise.  Here the
 substitute is zeros of the real width, [80, 32] -- or [80, T] for a processor configured with another DURATION
-(0.25 .. 2 s, inference: items and batches are [1, 80, T] / [B, 1, 80, T], T = 1 + int(16000 * DURATION) // 512).
+(0.25 .. 2 s: items and batches are [1, 80, T] / [B, 1, 80, T], T = 1 + int(16000 * DURATION) // 512).
 
 `augment=True` (the training split, :456) runs AudioProcessor.augment_audio's transforms on the GPU (kernels KA)
-between decode and log-mel: per item in `__getitem__`, per batch in `batches()`.
+between decode and log-mel: per item in `__getitem__`, per batch in `batches()`.  Augmentation, and so the training split, takes
+DURATION 0.25 .. 1.0 (T = 8 .. 32); longer clips serve inference only (augment=False).
 """
 from __future__ import annotations
 
@@ -54,7 +55,7 @@ class WakewordDataset(Dataset):
         return torch.FloatTensor(np.asarray(mel_spec, dtype=np.float32)).unsqueeze(0), torch.LongTensor([self.labels[idx]])
 
     def batches(self, batch_size=16):
-        """Yield (data [B,1,80,32] on the GPU, target [B,1] on the GPU) in file order: the host only reads bytes;
+        """Yield (data [B,1,80,T] on the GPU, target [B,1] on the GPU) in file order: the host only reads bytes;
         decode / resample / normalise / crop run in kernel K0, log-mel in K1."""
         return iter(GpuBatchLoader(self, batch_size, shuffle=False))
 
@@ -62,7 +63,7 @@ class WakewordDataset(Dataset):
         """What `DataLoader(dataset, batch_size=.., shuffle=.., num_workers=2)` is to the reference's loops
         (/root/reference/wakeword_training_script.py:461-463), without worker processes: an iterable with `len()`, re-iterable
         (a new permutation per epoch when shuffle=True, drawn from torch's generator like RandomSampler: `torch.manual_seed`
-        repeats it), yielding `(data [B,1,80,32], target [B,1])` on the GPU.  Files are read by the library's reader threads into
+        repeats it), yielding `(data [B,1,80,T], target [B,1])` on the GPU (T = 32 at 1 s).  Files are read by the library's reader threads into
         pinned staging, decoded (K0), augmented when the dataset says so (KA) and turned into log-mel (K1) one batch at a time."""
         return GpuBatchLoader(self, batch_size, shuffle=shuffle, drop_last=drop_last)
 

@@ -101,6 +101,11 @@ def _check_pcm(pcm: torch.Tensor) -> torch.Tensor:
     if pcm.shape[1] == 0 or pcm.shape[1] > CLIP_SAMPLES:
         raise ValueError(f"pcm: {pcm.shape[1]} samples per clip; the front-end takes 1..{CLIP_SAMPLES} "
                          "(crop longer clips on the host, pad_or_truncate wakeword_training_script.py:78-83)")
+    return _aligned_rows(pcm)
+
+
+def _aligned_rows(pcm: torch.Tensor) -> torch.Tensor:
+    """The rows as the native entry points take them: 16-byte aligned, row stride a multiple of 4 floats (copied only when needed)."""
     if pcm.stride(1) != 1 or (pcm.shape[0] > 1 and pcm.stride(0) % 4) or pcm.data_ptr() % 16:
         pcm = pcm.contiguous()
         if pcm.shape[1] % 4 and pcm.shape[0] > 1:      # row stride must be a multiple of 4 floats
@@ -519,17 +524,22 @@ if _os.environ.get("WW_LOGMEL_MATH"):
 
 
 # ---- KA: augmentation ------------------------------------------------------------------
+AUG_MAX_SAMPLES = 16383                 # T = 1 + N // 512 <= 32 frames: the clip lengths training takes (4000 .. 16383 samples)
+
+
 def augment(pcm: torch.Tensor, plans) -> torch.Tensor:
-    """pcm [B, 16000] float32 on the GPU + one plan per clip -> augmented [B, 16000] (ww_augment_f32).
+    """pcm [B, N] float32 on the GPU + one plan per clip -> augmented [B, N], N = 16000 (ww_augment_f32) or any N in 4000..16383
+    (ww_augment_n_f32; the plans' shift is taken mod N and crop lies in [0, round(N / rate) - N]).
 
     `plans`: a ctypes array of _native.AugmentPlan, or a list of dicts with the keys of oracle-style plans
     (shift, n_steps | pitch_rate, rate, crop, sigma, seed); see AudioProcessor.draw_augment_plan."""
     import ctypes as C
     if pcm.device.type != "cuda":
         raise RuntimeError("augment: pcm must live on the MI355X (no CPU fallback)")
-    if pcm.dtype != torch.float32 or pcm.dim() != 2 or pcm.shape[1] != 16000:
-        raise ValueError(f"augment: expected float32 [B, 16000], got {pcm.dtype} {tuple(pcm.shape)}")
-    pcm = pcm.contiguous()
+    if pcm.dtype != torch.float32 or pcm.dim() != 2 or not MIN_CLIP_SAMPLES <= pcm.shape[1] <= AUG_MAX_SAMPLES:
+        raise ValueError(f"augment: expected float32 [B, N], N in {MIN_CLIP_SAMPLES}..{AUG_MAX_SAMPLES}, got {pcm.dtype} {tuple(pcm.shape)}")
+    N = int(pcm.shape[1])
+    pcm = pcm.contiguous() if N == CLIP_SAMPLES else _aligned_rows(pcm)
     B = pcm.shape[0]
     if not isinstance(plans, C.Array):
         arr = (nat.AugmentPlan * max(1, B))()
@@ -547,13 +557,19 @@ def augment(pcm: torch.Tensor, plans) -> torch.Tensor:
         plans = arr
     elif len(plans) < B:
         raise ValueError(f"augment: {len(plans)} plans for {B} clips")
-    out = torch.empty_like(pcm)
+    out = torch.empty((B, N), device=pcm.device, dtype=torch.float32)
     if B == 0:
         return out
     with torch.cuda.device(pcm.device):
-        ws_bytes = nat.check(nat.lib.ww_augment_workspace_bytes(B))
-        ws = torch.empty(ws_bytes, device=pcm.device, dtype=torch.uint8)
-        nat.check(nat.lib.ww_augment_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0), plans, C.c_void_p(out.data_ptr()),
-                                         C.c_void_p(ws.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if N == CLIP_SAMPLES:
+            ws_bytes = nat.check(nat.lib.ww_augment_workspace_bytes(B))
+            ws = torch.empty(ws_bytes, device=pcm.device, dtype=torch.uint8)
+            nat.check(nat.lib.ww_augment_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0), plans, C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(ws.data_ptr()), stream))
+        else:
+            ws = torch.empty(nat.check(nat.lib.ww_augment_n_workspace_bytes(B, N)), device=pcm.device, dtype=torch.uint8)
+            nat.check(nat.lib.ww_augment_n_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, plans,
+                                               C.c_void_p(out.data_ptr()), N, C.c_void_p(ws.data_ptr()), stream))
         ws.record_stream(torch.cuda.current_stream())
     return out
