@@ -273,6 +273,44 @@ WW_API int ww_augment_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_
 WW_API int ww_augment_plans_prepare_n(const ww_augment_plan* plans_host, int64_t n_clips, int64_t n_samples, void* records_host);
 WW_API int ww_augment_records_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* records_dev,
                                     float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream);
+/* Background noise at a random SNR, mixed in after time_stretch + crop and before the Gaussian noise (additions only; no existing call,
+ * struct or record changes).  The bank is one float32 device buffer of bank_len samples holding every noise file back to back.  Per clip:
+ *   seg[j] = bank[file_offset + (start + j) mod file_len], j < N        (a file shorter than the clip repeats)
+ *   Ex = sum x^2 over the clip, En = sum seg^2                           (float64, in a fixed order that depends on N alone)
+ *   g = sqrt(Ex / (En * 10^(snr_db / 10))), out = fmaf(g, seg, x)       (nothing is added when Ex or En is 0)
+ * -- the SNR as named: 10 log10(Ex / sum (g seg)^2) = snr_db.  Every call below returns WW_EINVAL before any launch for an enabled clip
+ * with file_len <= 0, a file or start outside the bank, or a non-finite snr_db; clips with enabled = 0 are not looked at. */
+typedef struct ww_augment_bg {
+    int64_t file_offset;  /* the file's first sample in the bank */
+    int64_t file_len;     /* the file's samples, > 0; file_offset + file_len <= bank_len */
+    int64_t start;        /* segment start within the file, [0, file_len) */
+    float snr_db;         /* finite */
+    int32_t enabled;      /* 0 = no background for this clip */
+} ww_augment_bg;
+/* ww_augment_n_f32 with background, at N = 16000 or WW_MIN_CLIP_SAMPLES..WW_AUG_MAX_SAMPLES (rows and strides as there); bg_host [n_clips]
+ * in host memory; workspace_dev >= ww_augment_bg_workspace_bytes(n_clips, N).  With every enabled = 0 the results equal
+ * ww_augment_n_f32's (and at N = 16000 ww_augment_f32's) bit for bit. */
+WW_API int64_t ww_augment_bg_workspace_bytes(int64_t n_clips, int64_t n_samples);
+WW_API int ww_augment_bg_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
+                             const ww_augment_bg* bg_host, const float* bank_dev, int64_t bank_len, float* out_dev, int64_t out_stride,
+                             void* workspace_dev, ww_stream_t stream);
+/* The same in two halves, for hipGraph capture (as ww_augment_plans_prepare_n / ww_augment_records_n_f32): records are
+ * ww_augment_bg_record_bytes() per clip, laid out as [n_clips] augmentation records followed by [n_clips] background records, valid for
+ * the N and the bank length they were prepared for (a background record that does not lie inside bank_len at launch mixes nothing).
+ * The launch always ends in the mix kernel.  Results equal ww_augment_bg_f32's bit for bit. */
+WW_API int64_t ww_augment_bg_record_bytes(void);
+WW_API int ww_augment_bg_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, int64_t n_clips, int64_t n_samples,
+                                 int64_t bank_len, void* records_host);
+WW_API int ww_augment_bg_records_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* records_dev,
+                                     const float* bank_dev, int64_t bank_len, float* out_dev, int64_t out_stride, void* workspace_dev,
+                                     ww_stream_t stream);
+/* The mix alone (no other transform, no Gaussian noise), e.g. for noisy evaluation sets at a fixed SNR: clips of N = WW_MIN_CLIP_SAMPLES ..
+ * WW_MAX_CLIP_SAMPLES samples, rows at pcm_dev + i*clip_stride and out_dev + i*out_stride (4-byte aligned, strides >= N; out may alias
+ * pcm row for row); workspace_dev >= ww_mix_background_workspace_bytes(n_clips), 256-byte aligned. */
+WW_API int64_t ww_mix_background_workspace_bytes(int64_t n_clips);
+WW_API int ww_mix_background_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_bg* bg_host,
+                                 const float* bank_dev, int64_t bank_len, float* out_dev, int64_t out_stride, void* workspace_dev,
+                                 ww_stream_t stream);
 /* The resampler's half-window (32769 floats: 64 zero crossings x 512 + 1) on the host, for checking on a CPU. */
 WW_API int ww_kaiser_best_host(float* out_host);
 

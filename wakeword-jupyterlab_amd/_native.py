@@ -74,6 +74,13 @@ class AugmentPlan(C.Structure):
     ]
 
 
+class AugmentBg(C.Structure):
+    """struct ww_augment_bg (include/wakeword_amd.h): one clip's background segment."""
+    _fields_ = [
+        ("file_offset", C.c_int64), ("file_len", C.c_int64), ("start", C.c_int64), ("snr_db", C.c_float), ("enabled", C.c_int32),
+    ]
+
+
 FMT_S16, FMT_S24, FMT_S32, FMT_F32, FMT_U8, FMT_F64, FMT_FLAC = 1, 2, 3, 4, 5, 6, 7
 WAV_STATUS = {1: "ok", -1: "cannot open", -2: "not a RIFF/WAVE or FLAC file",
               -3: "missing fmt/data chunk, or a damaged FLAC stream (STREAMINFO, frame header or CRC)", -4: "unsupported WAV / FLAC encoding",
@@ -121,6 +128,16 @@ PROTOTYPES = {
     "ww_augment_plans_prepare_n": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "ww_augment_records_n_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_void_p]),
+    "ww_augment_bg_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "ww_augment_bg_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(AugmentPlan), C.POINTER(AugmentBg), C.c_void_p,
+                                    C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ww_augment_bg_record_bytes": (C.c_int64, []),
+    "ww_augment_bg_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "ww_augment_bg_records_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                            C.c_int64, C.c_void_p, C.c_void_p]),
+    "ww_mix_background_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "ww_mix_background_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(AugmentBg), C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_int64, C.c_void_p, C.c_void_p]),
     "ww_kaiser_best_host": (C.c_int, [C.c_void_p]),
     "ww_logmel_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "ww_packed_weights_floats": (C.c_int64, [C.c_int32]),

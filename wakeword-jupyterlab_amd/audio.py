@@ -14,6 +14,7 @@ T <= 32 (DURATION 0.25 .. 1.0, N = 4000 .. 16000 samples), and refuses longer cl
 
   augment_audio(audio)        -> time shift / pitch shift / time stretch / noise, each with probability 0.8
                                  (random draws from python `random` in the reference's order)  <- HIP kernels KA
+  set_background_noise(paths) -> background noise at a random SNR, mixed in after the stretch (background.py; not in the reference)
 `load_audio` / `process_audio_file` read the file with the library's native reader (csrc/ww_files.cpp) and decode, mix down and
 resample it on the GPU (kernel K0: scipy.signal.resample_poly's Kaiser design -- NOT librosa's soxr resampler, an absent third-party
 library: parity unpinned) -- the same code path as the batched loaders, one file at a time.  PCM / float WAV and FLAC.
@@ -49,44 +50,12 @@ class AudioProcessor:
         bad file).  Native reader, then ONE upload of the file's bytes and ONE K0 launch over all its 1 s windows (descriptors that share the
         byte offset and differ in crop_start; without normalisation K0 computes a window's samples only): linear in the file's length
         (round 3 uploaded and resampled the whole file once per second of it).  No normalisation, no crop."""
-        import ctypes as C
-        from . import _native as nat
-        from .files import CLIP_SAMPLES, DESC_DTYPE
         rd = self.gpu_reader(1)                                   # raises without a GPU: a missing device is not a bad file
         try:
-            slot = rd.next_slot()
-            try:
-                descs, status = rd.read([file_path], slot)
-            except nat.NativeError as e:
-                if e.code != nat.WW_ENOSPACE:
-                    raise
-                rd.regrow(1, int(e.needed * 1.25) + 4096)
-                slot = rd.next_slot()
-                descs, status = rd.read([file_path], slot)
-            if status[0] != 1:
-                raise ValueError(nat.WAV_STATUS.get(int(status[0]), int(status[0])))
-            n_out = int(-(-(int(descs["n_frames"][0]) * int(descs["up"][0])) // max(1, int(descs["down"][0]))))
-            if n_out == 0:
+            samples = decode_whole_file(rd, file_path, self._dev())
+            if samples is None:
                 return np.zeros(0, dtype=np.float32)
-            n_win = -(-n_out // CLIP_SAMPLES)
-            dev = self._dev()
-            with torch.cuda.device(dev):
-                stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-                if int(descs["format"][0]) == nat.FMT_FLAC:
-                    # FLAC: the reader uploads the frames and decodes them on the device; K0 then reads the float32 samples it points at
-                    staged = np.zeros(1, dtype=DESC_DTYPE)
-                    raw_p = C.c_void_p()
-                    nat.check(nat.lib.ww_wav_batch_stage(rd._h, slot, stream, C.byref(raw_p), staged.ctypes.data))
-                    src, raw_dev = staged, None
-                else:
-                    raw_dev = torch.from_numpy(rd.staging(slot)).to(dev)
-                    src, raw_p = descs[:1], C.c_void_p(raw_dev.data_ptr())
-                win = np.repeat(np.asarray(src), n_win)                          # a copy: same bytes, same filter, one window each
-                win["crop_start"] = np.arange(n_win, dtype=np.int64) * CLIP_SAMPLES
-                descs_dev = torch.from_numpy(win.view(np.uint8).reshape(n_win, DESC_DTYPE.itemsize)).to(dev)
-                out = torch.empty((n_win, CLIP_SAMPLES), device=dev, dtype=torch.float32)
-                nat.check(nat.lib.ww_decode_resample(raw_p, C.c_void_p(descs_dev.data_ptr()), n_win, 0, C.c_void_p(out.data_ptr()), stream))
-                audio = out.reshape(-1)[:n_out].cpu().numpy()      # (synchronises: the slot's device buffer is free again)
+            audio = samples.cpu().numpy()      # (synchronises: the slot's device buffer is free again)
             return np.ascontiguousarray(audio, dtype=np.float32)
         except Exception as e:                                             # reference: print and return None (:66-71)
             print(f"Error loading {file_path}: {e}")
@@ -140,7 +109,36 @@ class AudioProcessor:
         if random.random() < config.AUGMENTATION_PROB:
             plan["sigma"] = float(config.NOISE_FACTOR)
             plan["seed"] = random.getrandbits(32)
+        # background noise: drawn only with a bank attached (set_background_noise), after the reference's draws; a plan without
+        # background keeps exactly the reference's keys
+        bank = getattr(self, "_background", None)
+        prob = getattr(config, "BACKGROUND_PROB", 0.0)
+        if bank is not None and prob > 0 and random.random() < prob:
+            f = random.randrange(bank.n_files)
+            plan["bg_file"] = f
+            plan["bg_start"] = random.randrange(int(bank.lengths[f]))
+            plan["snr_db"] = random.uniform(config.BACKGROUND_SNR_MIN, config.BACKGROUND_SNR_MAX)
         return plan
+
+    def set_background_noise(self, paths_or_bank, max_seconds=None):
+        """Attach a background noise bank: a background.BackgroundNoiseBank, or the paths / directory to build one from (WAV and FLAC,
+        decoded whole on this processor's device; `max_seconds` caps the audio it keeps).  From then on every augmentation of this
+        processor -- augment_audio, augment_batch, process_audio_file(augment=True), WakewordDataset(augment=True) per item and through
+        loader() / batches() -- mixes a random file's segment into a clip with probability BACKGROUND_PROB, at an SNR drawn uniformly in
+        [BACKGROUND_SNR_MIN, BACKGROUND_SNR_MAX] dB.  `None` detaches the bank.  Returns the bank (or None)."""
+        from .background import BackgroundNoiseBank
+        if paths_or_bank is None:
+            self._background = None
+        elif isinstance(paths_or_bank, BackgroundNoiseBank):
+            self._background = paths_or_bank
+        else:
+            self._background = BackgroundNoiseBank(paths_or_bank, device=self._dev(), max_seconds=max_seconds)
+        return self._background
+
+    @property
+    def background_noise(self):
+        """The attached background.BackgroundNoiseBank, or None."""
+        return getattr(self, "_background", None)
 
     def augment_batch(self, pcm, plans=None, config=AugmentationConfig) -> torch.Tensor:
         """pcm [B, N] (ndarray or tensor) -> augmented device tensor [B, N]; one plan per clip (drawn here if None).
@@ -151,7 +149,7 @@ class AudioProcessor:
             t = t.to(self._dev(), non_blocking=True)
         if plans is None:
             plans = [self.draw_augment_plan(config, t.shape[1]) for _ in range(t.shape[0])]
-        return ops.augment(t, plans)
+        return ops.augment(t, plans, bank=getattr(self, "_background", None))
 
     def augment_audio(self, audio, config=AugmentationConfig):
         """[N] samples -> augmented float32 ndarray [N] (reference :103-123), on the GPU (N = 16000 at 1 s)."""
@@ -204,3 +202,50 @@ class AudioProcessor:
         elif self._reader.max_clips < batch_size:
             self._reader.regrow(batch_size, batch_size * 65536)
         return self._reader
+
+
+def decode_whole_file(rd, file_path, dev, before_read=None):
+    """One file, whole, through the native reader `rd` and K0 -> 1-D float32 device tensor of its samples at 16 kHz mono (None for a file
+    of no samples); raises on an unreadable file.  ONE upload of the file's bytes and ONE K0 launch over all its 1 s windows (descriptors
+    that share the byte offset and differ in crop_start; without normalisation K0 computes a window's samples only), enqueued on the
+    current stream.  `before_read(slot)` runs before the reader writes a slot's staging (a caller that does not synchronise between files
+    waits there for the work that last read the slot).  AudioProcessor.load_audio and background.BackgroundNoiseBank share it."""
+    import ctypes as C
+    from . import _native as nat
+    from .files import CLIP_SAMPLES, DESC_DTYPE
+
+    def read():
+        slot = rd.next_slot()
+        if before_read is not None:
+            before_read(slot)
+        return slot, rd.read([file_path], slot)
+    try:
+        slot, (descs, status) = read()
+    except nat.NativeError as e:
+        if e.code != nat.WW_ENOSPACE:
+            raise
+        rd.regrow(1, int(e.needed * 1.25) + 4096)
+        slot, (descs, status) = read()
+    if status[0] != 1:
+        raise ValueError(nat.WAV_STATUS.get(int(status[0]), int(status[0])))
+    n_out = int(-(-(int(descs["n_frames"][0]) * int(descs["up"][0])) // max(1, int(descs["down"][0]))))
+    if n_out == 0:
+        return None
+    n_win = -(-n_out // CLIP_SAMPLES)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if int(descs["format"][0]) == nat.FMT_FLAC:
+            # FLAC: the reader uploads the frames and decodes them on the device; K0 then reads the float32 samples it points at
+            staged = np.zeros(1, dtype=DESC_DTYPE)
+            raw_p = C.c_void_p()
+            nat.check(nat.lib.ww_wav_batch_stage(rd._h, slot, stream, C.byref(raw_p), staged.ctypes.data))
+            src, raw_dev = staged, None
+        else:
+            raw_dev = torch.from_numpy(rd.staging(slot)).to(dev)
+            src, raw_p = descs[:1], C.c_void_p(raw_dev.data_ptr())
+        win = np.repeat(np.asarray(src), n_win)                          # a copy: same bytes, same filter, one window each
+        win["crop_start"] = np.arange(n_win, dtype=np.int64) * CLIP_SAMPLES
+        descs_dev = torch.from_numpy(win.view(np.uint8).reshape(n_win, DESC_DTYPE.itemsize)).to(dev)
+        out = torch.empty((n_win, CLIP_SAMPLES), device=dev, dtype=torch.float32)
+        nat.check(nat.lib.ww_decode_resample(raw_p, C.c_void_p(descs_dev.data_ptr()), n_win, 0, C.c_void_p(out.data_ptr()), stream))
+    return out.reshape(-1)[:n_out]

@@ -25,6 +25,11 @@ class AugmentationConfig:
     PITCH_SHIFT_MAX = 3
     SPEED_CHANGE_MIN = 0.7
     SPEED_CHANGE_MAX = 1.3
+    # background noise (AudioProcessor.set_background_noise): mixed with this probability at an SNR drawn uniformly in [MIN, MAX] dB
+    # (MS-SNSD's noisyspeech_synthesizer.cfg bounds); used only when the processor has a noise bank attached
+    BACKGROUND_PROB = 0.8
+    BACKGROUND_SNR_MIN = 0.0
+    BACKGROUND_SNR_MAX = 40.0
 
 
 class ModelConfig:            # WakewordModel (3 convs)

@@ -4,6 +4,7 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <vector>
 
 #include <atomic>
 
@@ -362,6 +363,91 @@ int ww_augment_records_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip
     if (int rc = require_gfx950()) return rc;
     return launch_augment_records(pcm_dev, n_clips, clip_stride, n_samples, records_dev, true, true, out_dev, out_stride, workspace_dev,
                                   static_cast<hipStream_t>(stream));
+}
+
+// ---- background noise (the augmentation lengths above; the standalone mix at every inference length) ----
+static int check_bg_args(int64_t n_clips, const ww_augment_bg* bg_host, const float* bank_dev, int64_t bank_len) {
+    if (n_clips == 0) return WW_OK;
+    if (!bg_host) return fail(WW_EINVAL, "null bg pointer");
+    if (bank_len < 0) return fail(WW_EINVAL, "bank_len %lld < 0", (long long)bank_len);
+    bool any = false;
+    for (int64_t c = 0; c < n_clips && !any; ++c) any = bg_host[c].enabled != 0;
+    if (any && !bank_dev) return fail(WW_EINVAL, "null bank pointer");
+    return WW_OK;
+}
+
+int64_t ww_augment_bg_workspace_bytes(int64_t n_clips, int64_t n_samples) {
+    if (int rc = check_aug_samples(n_samples)) return rc;
+    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    return augment_bg_workspace_bytes(n_clips, n_samples);
+}
+
+int ww_augment_bg_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
+                      const ww_augment_bg* bg_host, const float* bank_dev, int64_t bank_len, float* out_dev, int64_t out_stride,
+                      void* workspace_dev, ww_stream_t stream) {
+    if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, plans_host, out_dev, out_stride, workspace_dev)) return rc;
+    if (n_clips == 0) return WW_OK;
+    if (int rc = check_bg_args(n_clips, bg_host, bank_dev, bank_len)) return rc;
+    {   // every refusal before anything is launched (the launcher prepares the same records again)
+        std::vector<char> rec(size_t(n_clips) * size_t(augment_bg_record_bytes()));
+        if (int rc = augment_bg_prepare(plans_host, bg_host, n_clips, n_samples, bank_len, rec.data(), nullptr, nullptr, nullptr)) return rc;
+    }
+    if (int rc = require_gfx950()) return rc;
+    return launch_augment_bg(pcm_dev, n_clips, clip_stride, n_samples, plans_host, bg_host, bank_dev, bank_len, out_dev, out_stride,
+                             workspace_dev, static_cast<hipStream_t>(stream));
+}
+
+int64_t ww_augment_bg_record_bytes(void) { return augment_bg_record_bytes(); }
+
+int ww_augment_bg_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, int64_t n_clips, int64_t n_samples,
+                          int64_t bank_len, void* records_host) {
+    if (int rc = check_aug_samples(n_samples)) return rc;
+    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (n_clips == 0) return WW_OK;
+    if (!plans_host || !bg_host || !records_host) return fail(WW_EINVAL, "null plan / bg / record pointer");
+    if (bank_len < 0) return fail(WW_EINVAL, "bank_len %lld < 0", (long long)bank_len);
+    return augment_bg_prepare(plans_host, bg_host, n_clips, n_samples, bank_len, records_host, nullptr, nullptr, nullptr);
+}
+
+int ww_augment_bg_records_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* records_dev,
+                              const float* bank_dev, int64_t bank_len, float* out_dev, int64_t out_stride, void* workspace_dev,
+                              ww_stream_t stream) {
+    if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, records_dev, out_dev, out_stride, workspace_dev)) return rc;
+    if (n_clips == 0) return WW_OK;
+    if (reinterpret_cast<uintptr_t>(records_dev) & 7) return fail(WW_EINVAL, "records_dev must be 8-byte aligned");
+    if (bank_len < 0 || (bank_len > 0 && !bank_dev)) return fail(WW_EINVAL, "bank: null pointer or bank_len %lld < 0", (long long)bank_len);
+    if (int rc = require_gfx950()) return rc;
+    return launch_augment_bg_records(pcm_dev, n_clips, clip_stride, n_samples, records_dev, true, true, bank_dev, bank_len, out_dev, out_stride,
+                                     workspace_dev, static_cast<hipStream_t>(stream));
+}
+
+int64_t ww_mix_background_workspace_bytes(int64_t n_clips) {
+    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    return mix_background_workspace_bytes(n_clips);
+}
+
+int ww_mix_background_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_bg* bg_host,
+                          const float* bank_dev, int64_t bank_len, float* out_dev, int64_t out_stride, void* workspace_dev,
+                          ww_stream_t stream) {
+    if (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_MAX_CLIP_SAMPLES)
+        return fail(WW_EINVAL, "n_samples %lld: the mix takes %d..%d samples (0.25 .. 2 s at 16 kHz)", (long long)n_samples,
+                    WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES);
+    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (n_clips == 0) return WW_OK;
+    if (!pcm_dev || !out_dev || !workspace_dev) return fail(WW_EINVAL, "null pcm / output / workspace pointer");
+    if (n_clips > 1 && (clip_stride < n_samples || out_stride < n_samples))
+        return fail(WW_EINVAL, "clip_stride %lld / out_stride %lld < n_samples %lld", (long long)clip_stride, (long long)out_stride,
+                    (long long)n_samples);
+    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 3) || (reinterpret_cast<uintptr_t>(out_dev) & 3) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
+        return fail(WW_EINVAL, "pcm_dev / out_dev must be 4-byte and workspace_dev 256-byte aligned");
+    if (int rc = check_bg_args(n_clips, bg_host, bank_dev, bank_len)) return rc;
+    {
+        std::vector<char> rec(size_t(mix_background_workspace_bytes(n_clips)));
+        if (int rc = background_prepare(bg_host, n_clips, bank_len, rec.data(), nullptr)) return rc;
+    }
+    if (int rc = require_gfx950()) return rc;
+    return launch_mix_background(pcm_dev, n_clips, clip_stride, n_samples, bg_host, bank_dev, bank_len, out_dev, out_stride, workspace_dev,
+                                 static_cast<hipStream_t>(stream));
 }
 
 int64_t ww_cnn_scratch_bytes(int64_t n, int32_t n_conv) { return cnn_scratch_bytes(n, n_conv); }

@@ -17,6 +17,8 @@
 //   resample_kernel   windowed-sinc interpolation at t = i / ratio (resampy 'kaiser_best' table in LDS, float32 MACs): the stand-in
 //                     for librosa's soxr_hq (absent third-party library; parity unpinned)
 //   noise_kernel      + sigma * normal(seed, i), the build's counter-based generator (splitmix64 -> Box-Muller)
+//   mix_kernel        background noise at an SNR, then the same Gaussian noise: one workgroup per clip (whole-clip energies first);
+//                     replaces noise_kernel in a batch where some clip has background on
 // Clips whose plan switches a transform off skip its kernels (their blocks copy the data through).
 //
 // Clip length: every kernel is a template on kN, the samples per clip -- 16000 (the 1 s entry points, a compile-time constant as before)
@@ -475,9 +477,24 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
-// Four samples per thread (float4 in, float4 out).  The uniforms are the hash generator's exact 32-bit words; Box-Muller runs in float32
+// The Gaussian noise generator, shared by noise_kernel and mix_kernel: the per-clip keys of the hash generator, and the normal deviate of
+// sample i (j = i + 1 in the counter).  The uniforms are the hash generator's exact 32-bit words; Box-Muller runs in float32
 // (round 2: float64 log / sqrt / cos, 0.35 ms per 4096 clips for a 0.5 GB stream; the float32 form is bound by that stream).  Against the
 // float64 evaluation the normal deviate moves by <= 3e-7 of sigma, four orders under the augmentation tests' tolerance.
+__device__ __forceinline__ void noise_keys(uint64_t seed, uint64_t& k1, uint64_t& k2) {
+    k1 = mix64(seed * 0x9E3779B97F4A7C15ull + 1ull * 0xD1B54A32D192ED03ull + 0x2545F4914F6CDD1Dull);
+    k2 = mix64(seed * 0x9E3779B97F4A7C15ull + 2ull * 0xD1B54A32D192ED03ull + 0x2545F4914F6CDD1Dull);
+}
+
+__device__ __forceinline__ float noise_normal(uint64_t k1, uint64_t k2, int i) {
+    const uint64_t j = uint64_t(i) + 1ull;
+    const uint32_t w1 = uint32_t(mix64(k1 + j * 0x9E3779B97F4A7C15ull) >> 32), w2 = uint32_t(mix64(k2 + j * 0x9E3779B97F4A7C15ull) >> 32);
+    const float u1 = (float(w1 >> 8) + (float(w1 & 0xffu) + 0.5f) * (1.0f / 256.0f)) * (1.0f / 16777216.0f);   // (w1 + 0.5) / 2^32 to float32
+    const float u2 = (float(w2 >> 8) + float(w2 & 0xffu) * (1.0f / 256.0f)) * (1.0f / 16777216.0f) + (0.5f / 4294967296.0f);
+    return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+}
+
+// Four samples per thread (float4 in, float4 out).
 template <int kN>
 __global__ __launch_bounds__(256) void noise_kernel(const float* __restrict__ in, const AugDev* __restrict__ plan,
                                                     float* __restrict__ out, int64_t out_stride, int n) {
@@ -488,19 +505,11 @@ __global__ __launch_bounds__(256) void noise_kernel(const float* __restrict__ in
     float4 v = *reinterpret_cast<const float4*>(in + int64_t(clip) * row + i);          // (padding lanes are not stored)
     const float sigma = plan[clip].sigma;
     if (sigma != 0.f) {
-        const uint64_t seed = plan[clip].seed;
-        const uint64_t k1 = mix64(seed * 0x9E3779B97F4A7C15ull + 1ull * 0xD1B54A32D192ED03ull + 0x2545F4914F6CDD1Dull);
-        const uint64_t k2 = mix64(seed * 0x9E3779B97F4A7C15ull + 2ull * 0xD1B54A32D192ED03ull + 0x2545F4914F6CDD1Dull);
+        uint64_t k1, k2;
+        noise_keys(plan[clip].seed, k1, k2);
         float* pv = &v.x;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint64_t j = uint64_t(i + q) + 1ull;
-            const uint32_t w1 = uint32_t(mix64(k1 + j * 0x9E3779B97F4A7C15ull) >> 32), w2 = uint32_t(mix64(k2 + j * 0x9E3779B97F4A7C15ull) >> 32);
-            const float u1 = (float(w1 >> 8) + (float(w1 & 0xffu) + 0.5f) * (1.0f / 256.0f)) * (1.0f / 16777216.0f);   // (w1 + 0.5) / 2^32 to float32
-            const float u2 = (float(w2 >> 8) + float(w2 & 0xffu) * (1.0f / 256.0f)) * (1.0f / 16777216.0f) + (0.5f / 4294967296.0f);
-            const float nrm = sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
-            pv[q] = fmaf(sigma, nrm, pv[q]);
-        }
+        for (int q = 0; q < 4; ++q) pv[q] = fmaf(sigma, noise_normal(k1, k2, i + q), pv[q]);
     }
     float* o = out + int64_t(clip) * out_stride + i;
     if constexpr (kN != 0) {
@@ -513,6 +522,86 @@ __global__ __launch_bounds__(256) void noise_kernel(const float* __restrict__ in
             if (i + 1 < L) o[1] = v.y;
             if (i + 2 < L) o[2] = v.z;
             if (i + 3 < L) o[3] = v.w;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Background noise at a random SNR (MS-SNSD's snr_mixer with the SNR as named): one workgroup of 1024 threads per clip, one pass.
+//   seg[j] = bank[off + (start + j) mod len], j < L            (a file shorter than the clip repeats)
+//   Ex = sum x^2, En = sum seg^2                                (float64: per thread in index order, wave-64 butterfly, then the 16 wave
+//                                                                sums in wave order -- a fixed order that depends on L alone)
+//   g = sqrt(Ex / (En * 10^(snr/10))), out = fma(g, seg, x)    (nothing is added when Ex or En is 0)
+// then (kNoise) + sigma * normal(seed, i) through noise_kernel's generator; the standalone mix has no Gaussian noise.  Sample i of the clip is
+// i = tid + 1024 k, k < kPer: the clip and its segment stay in registers between the reduction and the store.
+struct BgDev {             // one per clip, derived on the host from ww_augment_bg
+    int64_t off;           // the file's first sample in the bank
+    int64_t len;           // the file's samples; 0 = no background for this clip
+    int64_t start;         // segment start, [0, len)
+    double snr_lin;        // 10^(snr_db / 10)
+};
+constexpr int kMixThreads = 1024;
+
+template <int kN, int kPer, bool kNoise>
+__global__ __launch_bounds__(kMixThreads) void mix_kernel(const float* __restrict__ in, int64_t in_stride, const AugDev* __restrict__ plan,
+                                                          const BgDev* __restrict__ bg, const float* __restrict__ bank, int64_t bank_len,
+                                                          float* __restrict__ out, int64_t out_stride, int n) {
+    __shared__ double red[2][kMixThreads / 64];
+    __shared__ float gain;
+    const int L = kN ? kN : n;
+    const int clip = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ x = in + int64_t(clip) * in_stride;
+    float xv[kPer], sv[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        const int i = tid + kMixThreads * k;
+        xv[k] = i < L ? x[i] : 0.f;
+        sv[k] = 0.f;
+    }
+    const BgDev b = bg[clip];
+    // a record that does not lie inside the bank (prepared against another one) mixes nothing
+    const bool on = b.len > 0 && b.off >= 0 && b.off <= bank_len - b.len && b.start >= 0 && b.start < b.len;
+    if (on) {
+        const float* __restrict__ f = bank + b.off;
+        int64_t p = (b.start + tid) % b.len;
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) {
+            if (tid + kMixThreads * k < L) sv[k] = f[p];
+            p += kMixThreads;
+            if (p >= b.len) p = b.len >= kMixThreads ? p - b.len : p % b.len;
+        }
+        double ex = 0.0, en = 0.0;
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) {
+            ex = fma(double(xv[k]), double(xv[k]), ex);
+            en = fma(double(sv[k]), double(sv[k]), en);
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            ex += __shfl_xor(ex, m, 64);
+            en += __shfl_xor(en, m, 64);
+        }
+        if ((tid & 63) == 0) { red[0][tid >> 6] = ex; red[1][tid >> 6] = en; }
+        __syncthreads();
+        if (tid == 0) {
+            double sx = 0.0, sn = 0.0;
+            for (int w = 0; w < kMixThreads / 64; ++w) { sx += red[0][w]; sn += red[1][w]; }
+            gain = (sx > 0.0 && sn > 0.0) ? float(sqrt(sx / (sn * b.snr_lin))) : 0.f;
+        }
+        __syncthreads();
+    }
+    const float g = on ? gain : 0.f;
+    const float sigma = kNoise ? plan[clip].sigma : 0.f;
+    uint64_t k1 = 0, k2 = 0;
+    if (kNoise && sigma != 0.f) noise_keys(plan[clip].seed, k1, k2);
+    float* __restrict__ o = out + int64_t(clip) * out_stride;
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        const int i = tid + kMixThreads * k;
+        if (i < L) {
+            float v = g != 0.f ? fmaf(g, sv[k], xv[k]) : xv[k];
+            if (kNoise && sigma != 0.f) v = fmaf(sigma, noise_normal(k1, k2, i), v);
+            o[i] = v;
         }
     }
 }
@@ -595,9 +684,11 @@ int64_t augment_record_bytes() { return int64_t(sizeof(AugDev)); }
 
 // The kernels alone, on records already in device memory: nothing but launches on `stream` (capturable into a hipGraph).  A stage whose
 // flag is off for a clip copies that clip through, so both stages may always be launched (what a captured graph must do).
+// With `bg` (background records) the last launch is mix_kernel, which adds the background and then the same Gaussian noise.
 template <int kN>
 static int launch_records(const float* pcm, int64_t n, int64_t stride, int n_samples, const AugDev* plan, bool any_pitch, bool any_stretch,
-                          float* out, int64_t out_stride, void* workspace, hipStream_t stream) {
+                          float* out, int64_t out_stride, void* workspace, hipStream_t stream, const BgDev* bg = nullptr,
+                          const float* bank = nullptr, int64_t bank_len = 0) {
     const LogmelTables* tb = device_tables();
     if (!tb) return WW_EHIP;
     const int64_t row = aug_row_host(n_samples);
@@ -637,7 +728,11 @@ static int launch_records(const float* pcm, int64_t n, int64_t stride, int n_sam
         hipLaunchKernelGGL(istft_kernel<kN>, dim3(unsigned(n)), dim3(256), kIstftLds, stream, S, plan, 1, tb, cur, other, row, nn);
         float* t = cur; cur = other; other = t;
     }
-    hipLaunchKernelGGL(noise_kernel<kN>, egrid, dim3(256), 0, stream, cur, plan, out, out_stride, nn);
+    if (bg)
+        hipLaunchKernelGGL((mix_kernel<kN, 16, true>), dim3(unsigned(n)), dim3(kMixThreads), 0, stream, cur, row, plan, bg, bank, bank_len, out,
+                           out_stride, nn);
+    else
+        hipLaunchKernelGGL(noise_kernel<kN>, egrid, dim3(256), 0, stream, cur, plan, out, out_stride, nn);
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
@@ -681,6 +776,151 @@ int launch_augment(const float* pcm, int64_t n, int64_t stride, int64_t n_sample
         st.in_use = true;
     }
     return launch_augment_records(pcm, n, stride, n_samples, plan, any_pitch != 0, any_stretch != 0, out, out_stride, workspace, stream);
+}
+
+
+// ---- background noise -------------------------------------------------------------------------------------------------------------------
+int64_t augment_bg_record_bytes() { return int64_t(sizeof(AugDev) + sizeof(BgDev)); }
+
+int64_t augment_bg_workspace_bytes(int64_t n, int64_t n_samples) {
+    return augment_workspace_bytes(n, n_samples) + up256(n * int64_t(sizeof(BgDev)));
+}
+
+// ww_augment_bg -> BgDev, refusing a segment outside the bank, an empty file and a non-finite SNR (clips with enabled = 0: a zero record)
+int background_prepare(const ww_augment_bg* bg_host, int64_t n, int64_t bank_len, void* records_host, int* any_bg_out) {
+    BgDev* host = static_cast<BgDev*>(records_host);
+    bool any = false;
+    for (int64_t c = 0; c < n; ++c) {
+        const ww_augment_bg& b = bg_host[c];
+        BgDev d = {};
+        if (b.enabled) {
+            if (b.file_len <= 0) return fail(WW_EINVAL, "bg %lld: file_len %lld must be > 0", (long long)c, (long long)b.file_len);
+            if (b.file_offset < 0 || bank_len < 0 || b.file_offset > bank_len - b.file_len)
+                return fail(WW_EINVAL, "bg %lld: file [%lld, +%lld) outside the bank of %lld samples", (long long)c, (long long)b.file_offset,
+                            (long long)b.file_len, (long long)bank_len);
+            if (b.start < 0 || b.start >= b.file_len)
+                return fail(WW_EINVAL, "bg %lld: start %lld outside [0, %lld)", (long long)c, (long long)b.start, (long long)b.file_len);
+            if (!std::isfinite(b.snr_db)) return fail(WW_EINVAL, "bg %lld: snr_db must be finite", (long long)c);
+            d.off = b.file_offset;
+            d.len = b.file_len;
+            d.start = b.start;
+            d.snr_lin = std::pow(10.0, double(b.snr_db) / 10.0);
+            any = true;
+        }
+        host[c] = d;
+    }
+    if (any_bg_out) *any_bg_out = any;
+    return WW_OK;
+}
+
+// records = [n] AugDev, then [n] BgDev (ww_augment_bg_record_bytes() per clip)
+int augment_bg_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, int64_t n, int64_t n_samples, int64_t bank_len,
+                       void* records_host, int* any_pitch_out, int* any_stretch_out, int* any_bg_out) {
+    if (int rc = background_prepare(bg_host, n, bank_len, static_cast<char*>(records_host) + n * int64_t(sizeof(AugDev)), any_bg_out)) return rc;
+    return augment_prepare(plans_host, n, n_samples, records_host, any_pitch_out, any_stretch_out);
+}
+
+// Pinned staging for the background calls' records, as PlanStage (two slots per device, each guarded by an event) but sized in bytes;
+// `pieces` consecutive ranges of the staged bytes go to their own device addresses
+struct ByteStage {
+    void* host = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+    bool in_use = false;
+};
+static std::mutex g_bstage_mu;
+static ByteStage g_bstage[16][2];
+static int g_bstage_next[16] = {};
+
+static int stage_to_device(const void* src, const size_t* sizes, void* const* dst, int pieces, hipStream_t stream) {
+    size_t total = 0;
+    for (int i = 0; i < pieces; ++i) total += sizes[i];
+    int dev = 0;
+    WW_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 16) return fail(WW_EUNSUPPORTED, "device ordinal %d out of range", dev);
+    std::lock_guard<std::mutex> lock(g_bstage_mu);
+    ByteStage& st = g_bstage[dev][g_bstage_next[dev]];
+    g_bstage_next[dev] ^= 1;
+    if (st.in_use) WW_HIP(hipEventSynchronize(st.ev));
+    if (st.cap < total) {
+        if (st.host) WW_HIP(hipHostFree(st.host));
+        st.host = nullptr;
+        st.cap = 0;
+        WW_HIP(hipHostMalloc(&st.host, total, hipHostMallocDefault));
+        st.cap = total;
+    }
+    if (!st.ev) WW_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+    std::memcpy(st.host, src, total);
+    size_t at = 0;
+    for (int i = 0; i < pieces; ++i) {
+        WW_HIP(hipMemcpyAsync(dst[i], static_cast<char*>(st.host) + at, sizes[i], hipMemcpyHostToDevice, stream));
+        at += sizes[i];
+    }
+    WW_HIP(hipEventRecord(st.ev, stream));
+    st.in_use = true;
+    return WW_OK;
+}
+
+int launch_augment_bg_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, bool any_pitch,
+                              bool any_stretch, const float* bank, int64_t bank_len, float* out, int64_t out_stride, void* workspace,
+                              hipStream_t stream) {
+    if (n == 0) return WW_OK;
+    const AugDev* plan = static_cast<const AugDev*>(records_dev);
+    const BgDev* bg = reinterpret_cast<const BgDev*>(static_cast<const char*>(records_dev) + n * int64_t(sizeof(AugDev)));
+    if (n_samples == kClip)
+        return launch_records<kClip>(pcm, n, stride, kClip, plan, any_pitch, any_stretch, out, out_stride, workspace, stream, bg, bank, bank_len);
+    return launch_records<0>(pcm, n, stride, int(n_samples), plan, any_pitch, any_stretch, out, out_stride, workspace, stream, bg, bank,
+                             bank_len);
+}
+
+// The direct call: the records staged into the workspace (AugDev in the slot launch_augment uses, BgDev past augment_workspace_bytes); a
+// batch without background runs launch_augment's launches (noise_kernel last), one with background ends in mix_kernel instead
+int launch_augment_bg(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host,
+                      const ww_augment_bg* bg_host, const float* bank, int64_t bank_len, float* out, int64_t out_stride, void* workspace,
+                      hipStream_t stream) {
+    if (n == 0) return WW_OK;
+    const size_t rb = size_t(n) * sizeof(AugDev), bb = size_t(n) * sizeof(BgDev);
+    std::vector<char> host(rb + bb);
+    int any_pitch = 0, any_stretch = 0, any_bg = 0;
+    if (int rc = augment_bg_prepare(plans_host, bg_host, n, n_samples, bank_len, host.data(), &any_pitch, &any_stretch, &any_bg)) return rc;
+    AugDev* plan = static_cast<AugDev*>(workspace);
+    BgDev* bg = reinterpret_cast<BgDev*>(static_cast<char*>(workspace) + augment_workspace_bytes(n, n_samples));
+    const size_t sizes[2] = {rb, bb};
+    void* const dst[2] = {plan, bg};
+    if (int rc = stage_to_device(host.data(), sizes, dst, any_bg ? 2 : 1, stream)) return rc;
+    if (n_samples == kClip)
+        return launch_records<kClip>(pcm, n, stride, kClip, plan, any_pitch != 0, any_stretch != 0, out, out_stride, workspace, stream,
+                                     any_bg ? bg : nullptr, bank, bank_len);
+    return launch_records<0>(pcm, n, stride, int(n_samples), plan, any_pitch != 0, any_stretch != 0, out, out_stride, workspace, stream,
+                             any_bg ? bg : nullptr, bank, bank_len);
+}
+
+int64_t mix_background_workspace_bytes(int64_t n) { return up256(n * int64_t(sizeof(BgDev))); }
+
+// The mix alone (no Gaussian noise) on clips of 4000 .. 32000 samples: 16000 runs the 1 s instance, up to 16384 the run-time one with 16
+// samples per thread, longer clips 32 per thread
+int launch_mix_background(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_bg* bg_host, const float* bank,
+                          int64_t bank_len, float* out, int64_t out_stride, void* workspace, hipStream_t stream) {
+    if (n == 0) return WW_OK;
+    std::vector<BgDev> host(static_cast<size_t>(n));
+    if (int rc = background_prepare(bg_host, n, bank_len, host.data(), nullptr)) return rc;
+    BgDev* bg = static_cast<BgDev*>(workspace);
+    const size_t sizes[1] = {size_t(n) * sizeof(BgDev)};
+    void* const dst[1] = {bg};
+    if (int rc = stage_to_device(host.data(), sizes, dst, 1, stream)) return rc;
+    const int nn = int(n_samples);
+    const AugDev* no_plan = nullptr;
+    if (n_samples == kClip)
+        hipLaunchKernelGGL((mix_kernel<kClip, 16, false>), dim3(unsigned(n)), dim3(kMixThreads), 0, stream, pcm, stride, no_plan, bg, bank, bank_len,
+                           out, out_stride, nn);
+    else if (n_samples <= 16 * kMixThreads)
+        hipLaunchKernelGGL((mix_kernel<0, 16, false>), dim3(unsigned(n)), dim3(kMixThreads), 0, stream, pcm, stride, no_plan, bg, bank, bank_len, out,
+                           out_stride, nn);
+    else
+        hipLaunchKernelGGL((mix_kernel<0, 32, false>), dim3(unsigned(n)), dim3(kMixThreads), 0, stream, pcm, stride, no_plan, bg, bank, bank_len, out,
+                           out_stride, nn);
+    WW_HIP(hipGetLastError());
+    return WW_OK;
 }
 
 }  // namespace ww

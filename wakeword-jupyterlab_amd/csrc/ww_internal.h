@@ -130,6 +130,21 @@ int augment_prepare(const ww_augment_plan* plans_host, int64_t n, int64_t n_samp
 int64_t augment_record_bytes();
 int launch_augment_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, bool any_pitch,
                            bool any_stretch, float* out, int64_t out_stride, void* workspace, hipStream_t stream);
+// background noise (ww_augment.hip): the callers check N and the pointers; the bg records are checked here, before any launch
+int64_t augment_bg_workspace_bytes(int64_t n, int64_t n_samples);
+int64_t augment_bg_record_bytes();
+int background_prepare(const ww_augment_bg* bg_host, int64_t n, int64_t bank_len, void* records_host, int* any_bg_out);
+int augment_bg_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, int64_t n, int64_t n_samples, int64_t bank_len,
+                       void* records_host, int* any_pitch_out, int* any_stretch_out, int* any_bg_out);
+int launch_augment_bg(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host,
+                      const ww_augment_bg* bg_host, const float* bank, int64_t bank_len, float* out, int64_t out_stride, void* workspace,
+                      hipStream_t stream);
+int launch_augment_bg_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, bool any_pitch,
+                              bool any_stretch, const float* bank, int64_t bank_len, float* out, int64_t out_stride, void* workspace,
+                              hipStream_t stream);
+int64_t mix_background_workspace_bytes(int64_t n);
+int launch_mix_background(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_bg* bg_host, const float* bank,
+                          int64_t bank_len, float* out, int64_t out_stride, void* workspace, hipStream_t stream);
 void build_kaiser_best(float* out /*[32769]*/);
 int sync_timeouts(unsigned int* count);   // bounded LDS-counter waits that expired (must be 0)
 int launch_cnn_pool(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch,

@@ -527,12 +527,15 @@ if _os.environ.get("WW_LOGMEL_MATH"):
 AUG_MAX_SAMPLES = 16383                 # T = 1 + N // 512 <= 32 frames: the clip lengths training takes (4000 .. 16383 samples)
 
 
-def augment(pcm: torch.Tensor, plans) -> torch.Tensor:
+def augment(pcm: torch.Tensor, plans, bank=None) -> torch.Tensor:
     """pcm [B, N] float32 on the GPU + one plan per clip -> augmented [B, N], N = 16000 (ww_augment_f32) or any N in 4000..16383
     (ww_augment_n_f32; the plans' shift is taken mod N and crop lies in [0, round(N / rate) - N]).
 
     `plans`: a ctypes array of _native.AugmentPlan, or a list of dicts with the keys of oracle-style plans
-    (shift, n_steps | pitch_rate, rate, crop, sigma, seed); see AudioProcessor.draw_augment_plan."""
+    (shift, n_steps | pitch_rate, rate, crop, sigma, seed); see AudioProcessor.draw_augment_plan.
+    With a background.BackgroundNoiseBank, dict plans that carry `bg_file`, `bg_start` and `snr_db` get that file's segment mixed in after
+    the stretch and before the Gaussian noise (ww_augment_bg_f32); clips without those keys, and a batch where no plan has them, give
+    exactly what they give without a bank."""
     import ctypes as C
     if pcm.device.type != "cuda":
         raise RuntimeError("augment: pcm must live on the MI355X (no CPU fallback)")
@@ -541,7 +544,10 @@ def augment(pcm: torch.Tensor, plans) -> torch.Tensor:
     N = int(pcm.shape[1])
     pcm = pcm.contiguous() if N == CLIP_SAMPLES else _aligned_rows(pcm)
     B = pcm.shape[0]
+    bg_plans = None
     if not isinstance(plans, C.Array):
+        if bank is not None and any("bg_file" in p for p in plans):
+            bg_plans = plans
         arr = (nat.AugmentPlan * max(1, B))()
         if len(plans) != B:
             raise ValueError(f"augment: {len(plans)} plans for {B} clips")
@@ -557,12 +563,19 @@ def augment(pcm: torch.Tensor, plans) -> torch.Tensor:
         plans = arr
     elif len(plans) < B:
         raise ValueError(f"augment: {len(plans)} plans for {B} clips")
+    bg = _bg_array(bg_plans, bank, B) if bank is not None and bg_plans else None
     out = torch.empty((B, N), device=pcm.device, dtype=torch.float32)
     if B == 0:
         return out
     with torch.cuda.device(pcm.device):
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if N == CLIP_SAMPLES:
+        if bg is not None:
+            _check_bank(bank, pcm.device)
+            ws = torch.empty(nat.check(nat.lib.ww_augment_bg_workspace_bytes(B, N)), device=pcm.device, dtype=torch.uint8)
+            nat.check(nat.lib.ww_augment_bg_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, plans, bg,
+                                                C.c_void_p(bank.data.data_ptr()), bank.data.numel(), C.c_void_p(out.data_ptr()), N,
+                                                C.c_void_p(ws.data_ptr()), stream))
+        elif N == CLIP_SAMPLES:
             ws_bytes = nat.check(nat.lib.ww_augment_workspace_bytes(B))
             ws = torch.empty(ws_bytes, device=pcm.device, dtype=torch.uint8)
             nat.check(nat.lib.ww_augment_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0), plans, C.c_void_p(out.data_ptr()),
@@ -571,5 +584,59 @@ def augment(pcm: torch.Tensor, plans) -> torch.Tensor:
             ws = torch.empty(nat.check(nat.lib.ww_augment_n_workspace_bytes(B, N)), device=pcm.device, dtype=torch.uint8)
             nat.check(nat.lib.ww_augment_n_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, plans,
                                                C.c_void_p(out.data_ptr()), N, C.c_void_p(ws.data_ptr()), stream))
+        ws.record_stream(torch.cuda.current_stream())
+    return out
+
+
+def _check_bank(bank, device) -> None:
+    data = getattr(bank, "data", None)
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.float32 or data.dim() != 1:
+        raise TypeError("bank: expected a background.BackgroundNoiseBank")
+    if data.device != device:
+        raise ValueError(f"bank: lives on {data.device}, the clips on {device}")
+
+
+def _bg_array(plans, bank, B):
+    """Plans (dicts with bg_file / bg_start / snr_db, or without them: no background) -> ctypes array of _native.AugmentBg."""
+    bg = (nat.AugmentBg * max(1, B))()
+    for i, p in enumerate(plans):
+        if p.get("bg_file") is None:
+            continue
+        f = int(p["bg_file"])
+        if not 0 <= f < bank.n_files:
+            raise ValueError(f"bg_file {f}: the bank holds {bank.n_files} files")
+        b = bg[i]
+        b.file_offset, b.file_len = int(bank.offsets[f]), int(bank.lengths[f])
+        b.start, b.snr_db, b.enabled = int(p.get("bg_start", 0)), float(p["snr_db"]), 1
+    return bg
+
+
+def mix_background(pcm: torch.Tensor, bank, files, starts, snr_db) -> torch.Tensor:
+    """The background mix alone (ww_mix_background_f32): pcm [B, N] float32 on the GPU, N in 4000..32000 (every inference length) ->
+    [B, N] with clip i + bank file `files[i]` from sample `starts[i]` (wrapping around the file) at `snr_db[i]` dB (a scalar applies to
+    every clip).  A negative file index leaves that clip as it is.  For noisy evaluation sets at a fixed SNR."""
+    import ctypes as C
+    if pcm.device.type != "cuda":
+        raise RuntimeError("mix_background: pcm must live on the MI355X (no CPU fallback)")
+    if pcm.dtype != torch.float32 or pcm.dim() != 2 or not MIN_CLIP_SAMPLES <= pcm.shape[1] <= MAX_CLIP_SAMPLES:
+        raise ValueError(f"mix_background: expected float32 [B, N], N in {MIN_CLIP_SAMPLES}..{MAX_CLIP_SAMPLES}, got {pcm.dtype} "
+                         f"{tuple(pcm.shape)}")
+    _check_bank(bank, pcm.device)
+    B, N = int(pcm.shape[0]), int(pcm.shape[1])
+    if pcm.stride(1) != 1:
+        pcm = pcm.contiguous()
+    files, starts = np.broadcast_to(np.asarray(files, dtype=np.int64), (B,)), np.broadcast_to(np.asarray(starts, dtype=np.int64), (B,))
+    snr = np.broadcast_to(np.asarray(snr_db, dtype=np.float64), (B,))
+    plans = [{} if files[i] < 0 else {"bg_file": int(files[i]), "bg_start": int(starts[i]), "snr_db": float(snr[i])} for i in range(B)]
+    bg = _bg_array(plans, bank, B)
+    out = torch.empty((B, N), device=pcm.device, dtype=torch.float32)
+    if B == 0:
+        return out
+    with torch.cuda.device(pcm.device):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ws = torch.empty(nat.check(nat.lib.ww_mix_background_workspace_bytes(B)), device=pcm.device, dtype=torch.uint8)
+        nat.check(nat.lib.ww_mix_background_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, bg,
+                                                C.c_void_p(bank.data.data_ptr()), bank.data.numel(), C.c_void_p(out.data_ptr()), N,
+                                                C.c_void_p(ws.data_ptr()), stream))
         ws.record_stream(torch.cuda.current_stream())
     return out
