@@ -473,19 +473,26 @@ WW_API int ww_train_bit_images(const void* workspace_dev, int64_t n, int32_t n_c
 WW_API int ww_set_train_math(int mode);
 WW_API int ww_get_train_math(void);
 
-/* ---- streaming: sliding 1 s window, one hop per step, many microphones ------------------------ */
+/* ---- streaming: sliding window of 0.25 .. 1 s, one hop per step, many microphones ------------- */
 /* Semantics per window = predict_wakeword (wakeword_training.ipynb cell 19): normalise the last
- * 16000 samples, log-mel, forward, softmax, p[wakeword].  The reference has no streaming code;
+ * N samples, log-mel, forward, softmax, p[wakeword].  The reference has no streaming code;
  * this is that function applied to every hop of every microphone.
  * The per-hop step (ring append -> K1 -> K2 -> K3 -> softmax) is captured once into a hipGraph and
  * replayed by ww_streamer_step. */
 typedef struct ww_streamer ww_streamer;
+/* A 1 s window: ww_streamer_create_n(n_mics, hop_samples, 16000, ...). */
 WW_API int ww_streamer_create(int32_t n_mics, int32_t hop_samples, const float* packed_dev, int32_t n_conv,
                        ww_stream_t stream, ww_streamer** out);
+/* A window of n_samples = N samples: 16000, or WW_MIN_CLIP_SAMPLES <= N <= WW_AUG_MAX_SAMPLES (0.25 s .. 32 frames, the lengths
+ * the model trains at; T = 1 + N / 512 in [8, 32]); any other N is WW_EUNSUPPORTED.  hop_samples must be a multiple of 4 that
+ * divides N (WW_EINVAL otherwise), which keeps N and the ring position multiples of 4.  The length is checked before the hop,
+ * and both before any HIP call.  Each hop recomputes the T frames of the whole window. */
+WW_API int ww_streamer_create_n(int32_t n_mics, int32_t hop_samples, int32_t n_samples, const float* packed_dev, int32_t n_conv,
+                                ww_stream_t stream, ww_streamer** out);
 /* hop_dev [n_mics][hop_samples] new samples; prob_dev [n_mics] softmax p(wakeword) of the window
  * ending at this hop; logits_dev (may be NULL) [n_mics][2]. */
 WW_API int ww_streamer_step(ww_streamer* s, const float* hop_dev, float* prob_dev, float* logits_dev);
-/* Copy of the current 1 s window of every mic, oldest sample first: [n_mics][16000] (for tests). */
+/* Copy of the current window of every mic, oldest sample first: [n_mics][N] (for tests). */
 WW_API int ww_streamer_window(ww_streamer* s, float* window_dev);
 WW_API int ww_streamer_destroy(ww_streamer* s);
 

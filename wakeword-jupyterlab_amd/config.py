@@ -57,7 +57,7 @@ MIN_DURATION, MAX_DURATION = 0.25, 2.0          # other clip lengths: 4,000 .. 3
 
 def check_audio_config(cfg) -> None:
     """The kernels are built for the reference constants, at DURATION 1.0 for everything and at any DURATION in [0.25, 2.0] for inference;
-    training and augmentation take DURATION 0.25 .. 1.0 (T <= 32 frames), streaming stays 1 s only.  Refuse anything else loudly."""
+    training, augmentation and streaming take DURATION 0.25 .. 1.0 (T <= 32 frames).  Refuse anything else loudly."""
     want = {k: getattr(AudioConfig, k) for k in ("SAMPLE_RATE", "N_MELS", "N_FFT", "HOP_LENGTH", "WIN_LENGTH", "FMIN", "FMAX")}
     got = {k: getattr(cfg, k, None) for k in want}
     dur = float(getattr(cfg, "DURATION", 1.0))

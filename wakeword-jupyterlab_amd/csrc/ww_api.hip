@@ -93,11 +93,12 @@ struct Workspace {
     void* scratch;
     int64_t total;
 };
-static Workspace carve(void* base, int64_t n, int n_conv) {
+// `width`: the mel frames per clip (kFrames for 1 s; the streamer's T <= 32 for shorter windows)
+static Workspace carve(void* base, int64_t n, int n_conv, int width = kFrames) {
     Workspace w{};
     char* p = static_cast<char*>(base);
     int64_t o = 0;
-    w.logmel = reinterpret_cast<float*>(p + o); o += align256(n * kMels * kFrames * int64_t(sizeof(float)));
+    w.logmel = reinterpret_cast<float*>(p + o); o += align256(n * kMels * width * int64_t(sizeof(float)));
     w.pooled = reinterpret_cast<float*>(p + o); o += align256(n * 128 * int64_t(sizeof(float)));
     w.scratch = p + o; o += align256(cnn_scratch_bytes(n, n_conv));
     w.total = o;
@@ -135,9 +136,10 @@ using namespace ww;
 // --------------------------------------------------------------------------------------------------
 struct ww_streamer {
     int n_mics, hop, n_conv;
+    int n_samples, n_frames;   // window N (16000 at 1 s) and its T = 1 + N / 512 mel frames
     const float* packed;
     hipStream_t stream;
-    float* ring;         // [n_mics][16000]
+    float* ring;         // [n_mics][n_samples]
     int32_t* pos;        // device: [0] index of the oldest sample (== next write position), [1] append-kernel ticket
     void* workspace;
     hipGraph_t graph;
@@ -152,32 +154,32 @@ struct ww_streamer {
 // reads `pos` before it writes samples and takes a ticket after; the workgroup that draws the last ticket knows all
 // others are past their read of `pos` and publishes pos + hop for the kernels that follow in the graph.
 __global__ void ring_append_kernel(float* __restrict__ ring, int32_t* __restrict__ pos_p, uint32_t* __restrict__ ticket,
-                                   const float* __restrict__ hop, int n_mics, int hop_len) {
+                                   const float* __restrict__ hop, int n_mics, int hop_len, int ring_len) {
     const int pos = *reinterpret_cast<volatile int32_t*>(pos_p);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_mics * hop_len; i += gridDim.x * blockDim.x) {
         const int m = i / hop_len, k = i - m * hop_len;
         int at = pos + k;
-        if (at >= kClip) at -= kClip;
-        ring[int64_t(m) * kClip + at] = hop[i];
+        if (at >= ring_len) at -= ring_len;
+        ring[int64_t(m) * ring_len + at] = hop[i];
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence();
         if (atomicInc(ticket, gridDim.x - 1) == gridDim.x - 1) {     // wraps to 0: ready for the next replay
             const int p = pos + hop_len;
-            *pos_p = p >= kClip ? p - kClip : p;
+            *pos_p = p >= ring_len ? p - ring_len : p;
         }
     }
 }
 __global__ void ring_unroll_kernel(const float* __restrict__ ring, const int32_t* __restrict__ pos_p,
-                                   float* __restrict__ out, int n_mics) {
+                                   float* __restrict__ out, int n_mics, int ring_len) {
     const int pos = *pos_p;
-    for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < int64_t(n_mics) * kClip;
+    for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < int64_t(n_mics) * ring_len;
          i += int64_t(gridDim.x) * blockDim.x) {
-        const int m = int(i / kClip), k = int(i - int64_t(m) * kClip);
+        const int m = int(i / ring_len), k = int(i - int64_t(m) * ring_len);
         int at = pos + k;
-        if (at >= kClip) at -= kClip;
-        out[i] = ring[int64_t(m) * kClip + at];
+        if (at >= ring_len) at -= ring_len;
+        out[i] = ring[int64_t(m) * ring_len + at];
     }
 }
 
@@ -185,11 +187,13 @@ static int streamer_enqueue(ww_streamer* s, const float* hop_dev, float* prob_de
     const int threads = 256;
     const int blocks = (s->n_mics * s->hop + threads - 1) / threads;
     hipLaunchKernelGGL(ring_append_kernel, dim3(blocks), dim3(threads), 0, s->stream, s->ring, s->pos,
-                       reinterpret_cast<uint32_t*>(s->pos + 1), hop_dev, s->n_mics, s->hop);
+                       reinterpret_cast<uint32_t*>(s->pos + 1), hop_dev, s->n_mics, s->hop, s->n_samples);
     WW_HIP(hipGetLastError());
-    Workspace w = carve(s->workspace, s->n_mics, s->n_conv);
-    if (int rc = launch_logmel(s->ring, s->n_mics, kClip, kClip, 1, s->pos, kClip, w.logmel, s->stream)) return rc;
-    if (int rc = launch_cnn_pool(w.logmel, s->n_mics, kFrames, s->packed, s->n_conv, w.scratch, w.pooled, s->stream)) return rc;
+    // N = 16000 (T = 32) is launch_logmel's 1 s ring kernel with the same arguments as ever; other N the 64-frame tile in ring form
+    const int N = s->n_samples;
+    Workspace w = carve(s->workspace, s->n_mics, s->n_conv, s->n_frames);
+    if (int rc = launch_logmel_frames(s->ring, s->n_mics, N, N, N, 1, s->pos, N, w.logmel, s->stream)) return rc;
+    if (int rc = launch_cnn_pool(w.logmel, s->n_mics, s->n_frames, s->packed, s->n_conv, w.scratch, w.pooled, s->stream)) return rc;
     return launch_lstm_fc(w.pooled, s->n_mics, s->packed, s->n_conv, logits_dev, prob_dev, s->stream);
 }
 
@@ -657,25 +661,31 @@ int ww_train_backward_f32(const float* mel_dev, int64_t n, int32_t width, const 
     return train_backward(mel_dev, n, width, params, dlogits_dev, mode, workspace_dev, workspace_bytes, grads, static_cast<hipStream_t>(stream));
 }
 
-int ww_streamer_create(int32_t n_mics, int32_t hop_samples, const float* packed_dev, int32_t n_conv,
-                       ww_stream_t stream, ww_streamer** out) {
+int ww_streamer_create_n(int32_t n_mics, int32_t hop_samples, int32_t n_samples, const float* packed_dev, int32_t n_conv,
+                         ww_stream_t stream, ww_streamer** out) {
     if (!out) return fail(WW_EINVAL, "null out pointer");
     *out = nullptr;
     if (n_mics < 1 || n_mics > (1 << 20)) return fail(WW_EINVAL, "n_mics %d out of range", n_mics);
-    if (hop_samples < 4 || hop_samples > kClip || (hop_samples & 3) || (kClip % hop_samples))
-        return fail(WW_EINVAL, "hop_samples %d: must be a multiple of 4 that divides %d", hop_samples, kClip);
-    if (int rc = check_model(n_mics, kFrames, packed_dev, n_conv)) return rc;
+    const int N = n_samples;
+    if (N != kClip && (N < WW_MIN_CLIP_SAMPLES || N > WW_AUG_MAX_SAMPLES))
+        return fail(WW_EUNSUPPORTED, "n_samples %d: streaming windows take %d..%d samples (0.25 .. 1 s, at most 32 frames) or %d", N,
+                    WW_MIN_CLIP_SAMPLES, WW_AUG_MAX_SAMPLES, kClip);
+    if (hop_samples < 4 || hop_samples > N || (hop_samples & 3) || (N % hop_samples))
+        return fail(WW_EINVAL, "hop_samples %d: must be a multiple of 4 that divides %d", hop_samples, N);
+    const int T = 1 + N / kHop;
+    if (int rc = check_model(n_mics, T, packed_dev, n_conv)) return rc;
     if (!device_tables()) return WW_EHIP;   // also the gfx950 check; must precede graph capture
     ww_streamer* s = new (std::nothrow) ww_streamer();
     if (!s) return fail(WW_EHIP, "out of host memory");
     s->n_mics = n_mics; s->hop = hop_samples; s->n_conv = n_conv; s->packed = packed_dev;
+    s->n_samples = N; s->n_frames = T;
     s->stream = static_cast<hipStream_t>(stream);
-    const int64_t ws = carve(nullptr, n_mics, n_conv).total;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->ring), sizeof(float) * int64_t(n_mics) * kClip);
+    const int64_t ws = carve(nullptr, n_mics, n_conv, T).total;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->ring), sizeof(float) * int64_t(n_mics) * N);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->pos), 16);
     if (e == hipSuccess) e = hipMalloc(&s->workspace, size_t(ws));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->own_logits), sizeof(float) * 2 * n_mics);
-    if (e == hipSuccess) e = hipMemsetAsync(s->ring, 0, sizeof(float) * int64_t(n_mics) * kClip, s->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->ring, 0, sizeof(float) * int64_t(n_mics) * N, s->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s->pos, 0, 16, s->stream);
     if (e != hipSuccess) {
         ww_streamer_destroy(s);
@@ -683,6 +693,11 @@ int ww_streamer_create(int32_t n_mics, int32_t hop_samples, const float* packed_
     }
     *out = s;
     return WW_OK;
+}
+
+int ww_streamer_create(int32_t n_mics, int32_t hop_samples, const float* packed_dev, int32_t n_conv,
+                       ww_stream_t stream, ww_streamer** out) {
+    return ww_streamer_create_n(n_mics, hop_samples, kClip, packed_dev, n_conv, stream, out);
 }
 
 int ww_streamer_step(ww_streamer* s, const float* hop_dev, float* prob_dev, float* logits_dev) {
@@ -709,7 +724,7 @@ int ww_streamer_step(ww_streamer* s, const float* hop_dev, float* prob_dev, floa
 
 int ww_streamer_window(ww_streamer* s, float* window_dev) {
     if (!s || !window_dev) return fail(WW_EINVAL, "null argument");
-    hipLaunchKernelGGL(ring_unroll_kernel, dim3(1024), dim3(256), 0, s->stream, s->ring, s->pos, window_dev, s->n_mics);
+    hipLaunchKernelGGL(ring_unroll_kernel, dim3(1024), dim3(256), 0, s->stream, s->ring, s->pos, window_dev, s->n_mics, s->n_samples);
     WW_HIP(hipGetLastError());
     return WW_OK;
 }

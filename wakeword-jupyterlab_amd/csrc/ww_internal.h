@@ -117,6 +117,9 @@ int launch_logmel(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_
 // any clip length: rows of n_samples (<= 32000; clip_len <= n_samples valid), T = 1 + n_samples / 512 frames in [8, 63] -> [n][80][T]
 int launch_logmel_frames(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples, int normalize,
                          float* logmel, hipStream_t stream);
+// the same over streaming rings of ring_len = clip_len = n_samples samples per row (a multiple of 4), window start *ring_pos (device)
+int launch_logmel_frames(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples, int normalize,
+                         const int32_t* ring_pos, int64_t ring_len, float* logmel, hipStream_t stream);
 // log-mel arithmetic: 0 = f32 FFT, 1 = f64 FFT (what the reference's numpy.fft.rfft is), 2 = auto (f32, then the clips whose
 // quiet bands sit on the f32 FFT's rounding floor are redone in f64)
 int logmel_math_mode();

@@ -37,7 +37,7 @@ static_assert(kPartialInSlab + kPieces <= kSlab, "piece sums must fit behind the
 // WAVES = 8: the latency form for batches of at most one clip per CU (streaming): a clip's 32 frames take 4 rounds
 //            instead of 8, one 83 KB workgroup per CU.
 // FR: the frames the mel tile holds.  FR = 32 (kFrames) is the 1 s kernel; FR = 64 takes any T = 1 + n_samples / 512 in [8, 63]
-// (ww_logmel_frames_f32), computing ceil(T / WAVES) rounds of frames and using the first T.
+// (ww_logmel_frames_f32; in ring form the streamer's windows of T < 32), computing ceil(T / WAVES) rounds of frames and using the first T.
 template <int WAVES, int FR = kFrames>
 struct K1Layout {
     static constexpr int kWaves = WAVES;
@@ -1005,15 +1005,12 @@ static int launch_logmel_w(const float* pcm, int64_t n_clips, int64_t clip_strid
     const int64_t resident = int64_t(device_cu_count()) * L::kBlocksPerCu;   // what LDS and VGPRs admit per CU
     const int grid = int(n_clips < resident ? n_clips : resident);
     const size_t lds_bytes = sizeof(float) * L::kLdsFloats;
-    if constexpr (FR != kFrames)      // long clips: no ring form
+    if (ring_pos)
+        hipLaunchKernelGGL((logmel_kernel<true, WAVES, FR>), dim3(grid), dim3(L::kThreads), lds_bytes, stream, pcm, clip_stride, int(clip_len),
+                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark, n_frames);
+    else
         hipLaunchKernelGGL((logmel_kernel<false, WAVES, FR>), dim3(grid), dim3(L::kThreads), lds_bytes, stream, pcm, clip_stride, int(clip_len),
                            int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark, n_frames);
-    else if (ring_pos)
-        hipLaunchKernelGGL((logmel_kernel<true, WAVES>), dim3(grid), dim3(L::kThreads), lds_bytes, stream, pcm, clip_stride, int(clip_len),
-                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark, kFrames);
-    else
-        hipLaunchKernelGGL((logmel_kernel<false, WAVES>), dim3(grid), dim3(L::kThreads), lds_bytes, stream, pcm, clip_stride, int(clip_len),
-                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark, kFrames);
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
@@ -1025,15 +1022,12 @@ static int launch_logmel64(const float* pcm, int64_t n_clips, int64_t clip_strid
     const int64_t resident = K64Layout<FR>::kBlocksPerCu * int64_t(device_cu_count());      // two 80 KB workgroups per CU (FR 32)
     const int grid = int(n_clips < resident ? n_clips : resident);
     const size_t lds_bytes = sizeof(float) * K64Layout<FR>::kLdsFloats;
-    if constexpr (FR != kFrames)
+    if (ring_pos)
+        hipLaunchKernelGGL((logmel64_kernel<true, ONLY_FLAGGED, FR>), dim3(grid), dim3(256), lds_bytes, stream, pcm, clip_stride, int(clip_len),
+                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, n_frames);
+    else
         hipLaunchKernelGGL((logmel64_kernel<false, ONLY_FLAGGED, FR>), dim3(grid), dim3(256), lds_bytes, stream, pcm, clip_stride, int(clip_len),
                            int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, n_frames);
-    else if (ring_pos)
-        hipLaunchKernelGGL((logmel64_kernel<true, ONLY_FLAGGED>), dim3(grid), dim3(256), lds_bytes, stream, pcm, clip_stride, int(clip_len),
-                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, kFrames);
-    else
-        hipLaunchKernelGGL((logmel64_kernel<false, ONLY_FLAGGED>), dim3(grid), dim3(256), lds_bytes, stream, pcm, clip_stride, int(clip_len),
-                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, kFrames);
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
@@ -1059,8 +1053,12 @@ static int logmel_opt_in_lds() {
     WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, b64));
     const int c4 = int(sizeof(float) * K1Layout<4, 64>::kLdsFloats), c8 = int(sizeof(float) * K1Layout<8, 64>::kLdsFloats);
     const int c64 = int(sizeof(float) * K64Layout<64>::kLdsFloats);
+    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<true, 4, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c4));
     WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<false, 4, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c4));
+    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<true, 8, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c8));
     WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<false, 8, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c8));
+    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<true, true, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c64));
+    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<true, false, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c64));
     WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<false, true, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c64));
     WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<false, false, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c64));
     done[dev] = true;
@@ -1089,25 +1087,31 @@ int launch_logmel(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_
 
 // Any clip length (ww_logmel_frames_f32): rows of n_samples (clip_len valid, the rest zero), T = 1 + n_samples / 512 frames, [n][80][T].
 // T = 32 is the 1 s kernel itself (bit for bit); every other T runs the 64-frame instances, in the same three arithmetics.
+// Ring form (streaming windows of n_samples): sample i of row c at pcm[c * clip_stride + (*ring_pos + i) mod ring_len], ring_len = clip_len
+// = n_samples, a multiple of 4 like *ring_pos (the frame loads are float4).
 int launch_logmel_frames(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples, int normalize,
-                         float* logmel, hipStream_t stream) {
+                         const int32_t* ring_pos, int64_t ring_len, float* logmel, hipStream_t stream) {
     const int T = int(1 + n_samples / kHop);
-    if (T == kFrames) return launch_logmel(pcm, n_clips, clip_stride, clip_len, normalize, nullptr, 0, logmel, stream);
+    if (T == kFrames) return launch_logmel(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, stream);
     if (n_clips == 0) return WW_OK;
     const LogmelTables* tb = device_tables();
     if (!tb) return WW_EHIP;
     if (int rc = logmel_opt_in_lds()) return rc;
     const int mode = logmel_math_mode();
     if (mode == WW_LOGMEL_MATH_F64)
-        return launch_logmel64<false, 64>(pcm, n_clips, clip_stride, clip_len, normalize, nullptr, 0, logmel, tb, stream, T);
+        return launch_logmel64<false, 64>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, stream, T);
     const int mark = mode == WW_LOGMEL_MATH_AUTO;
     int rc;
     if (n_clips <= device_cu_count())
-        rc = launch_logmel_w<8, 64>(pcm, n_clips, clip_stride, clip_len, normalize, nullptr, 0, logmel, tb, mark, stream, T);
+        rc = launch_logmel_w<8, 64>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, mark, stream, T);
     else
-        rc = launch_logmel_w<4, 64>(pcm, n_clips, clip_stride, clip_len, normalize, nullptr, 0, logmel, tb, mark, stream, T);
+        rc = launch_logmel_w<4, 64>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, mark, stream, T);
     if (rc != WW_OK || !mark) return rc;
-    return launch_logmel64<true, 64>(pcm, n_clips, clip_stride, clip_len, normalize, nullptr, 0, logmel, tb, stream, T);
+    return launch_logmel64<true, 64>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, stream, T);
+}
+int launch_logmel_frames(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples, int normalize,
+                         float* logmel, hipStream_t stream) {
+    return launch_logmel_frames(pcm, n_clips, clip_stride, clip_len, n_samples, normalize, nullptr, 0, logmel, stream);
 }
 
 }  // namespace ww

@@ -1,8 +1,9 @@
 """Streaming sliding-window detection: many microphones, one hop per step, hipGraph-replayed.
 
 The reference has no streaming code; the per-window semantics are `predict_wakeword` (notebook cell 19,
-wakeword_training.ipynb:871-893): peak-normalise the last 1 s, log-mel, forward, softmax, p[1] >= 0.8.
-Per hop this keeps a 16000-sample ring per microphone in HBM, appends the hop, recomputes the whole window
+wakeword_training.ipynb:871-893): peak-normalise the last N samples, log-mel, forward, softmax, p[1] >= 0.8.
+The window is the model's clip length, N = int(16000 * DURATION) for DURATION in [0.25, 1] (T = 1 + N // 512 <= 32 frames: the
+lengths the model trains at).  Per hop this keeps an N-sample ring per microphone in HBM, appends the hop, recomputes the whole window
 (frames cannot be reused across 10 ms hops: the 512-sample STFT grid realigns only every 2560 samples and
 `ref=np.max` is per window -- SURVEY.md section 7) and replays one captured hipGraph:
 ring append -> K1 -> K2 -> K3 (+softmax).
@@ -14,15 +15,18 @@ import ctypes as C
 import torch
 
 from . import _native as nat
-from .config import CLIP_SAMPLES
+from .config import CLIP_SAMPLES, N_FRAMES
 
 
 class StreamingDetector:
     def __init__(self, model, n_mics: int = 256, hop_samples: int = 160, threshold: float = 0.8, device=None):
         if model.training:
             raise NotImplementedError("call model.eval() first")
-        if getattr(model, "_n_samples", CLIP_SAMPLES) != CLIP_SAMPLES:
-            raise NotImplementedError(f"streaming runs 1 s windows only; this model is built for clips of {model._n_samples} samples")
+        n = int(getattr(model, "_n_samples", CLIP_SAMPLES))
+        if 1 + n // 512 > N_FRAMES:
+            raise NotImplementedError(f"streaming runs windows of 0.25 .. 1 s (at most {N_FRAMES} frames); this model is built for clips "
+                                      f"of {n} samples")
+        self.window_samples = n                        # N: the window every hop is scored on
         self.device = torch.device(device) if device is not None else model.fc.weight.device
         if self.device.type != "cuda":
             raise RuntimeError("StreamingDetector needs the model on the MI355X (no CPU path)")
@@ -35,8 +39,8 @@ class StreamingDetector:
         self.logits = torch.zeros((self.n_mics, 2), device=self.device, dtype=torch.float32)
         handle = C.c_void_p()
         with torch.cuda.device(self.device):
-            nat.check(nat.lib.ww_streamer_create(self.n_mics, self.hop, C.c_void_p(self._packed.data_ptr()), self._n_conv,
-                                                 C.c_void_p(self._stream.cuda_stream), C.byref(handle)))
+            nat.check(nat.lib.ww_streamer_create_n(self.n_mics, self.hop, self.window_samples, C.c_void_p(self._packed.data_ptr()),
+                                                   self._n_conv, C.c_void_p(self._stream.cuda_stream), C.byref(handle)))
         self._h = handle
 
     @property
@@ -63,8 +67,8 @@ class StreamingDetector:
         return self.prob >= self.threshold
 
     def window(self) -> torch.Tensor:
-        """Current 1 s window of every microphone, oldest sample first: [n_mics, 16000]."""
-        out = torch.empty((self.n_mics, CLIP_SAMPLES), device=self.device, dtype=torch.float32)
+        """Current window of every microphone, oldest sample first: [n_mics, window_samples]."""
+        out = torch.empty((self.n_mics, self.window_samples), device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
             nat.check(nat.lib.ww_streamer_window(self._h, C.c_void_p(out.data_ptr())))
         self._stream.synchronize()
