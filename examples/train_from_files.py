@@ -4,11 +4,13 @@ AudioProcessor / WakewordModel -> WakewordDataset x 3 (training split augmented)
 epochs (the loop bodies of WakewordTrainer, :241-289) -> best / final checkpoints.  Only the imports differ from the reference's script:
 every class and `DataLoader` come from `wakeword_jupyterlab_amd`; criterion, optimiser and scheduler are torch's.
 
-    PYTHONPATH=. python examples/train_from_files.py [--epochs 10] [--data DIR] [--lr 1e-4] [--duration 1.0] [--background DIR]
+    PYTHONPATH=. python examples/train_from_files.py [--epochs 10] [--data DIR] [--lr 1e-4] [--duration 1.0] [--background DIR] [--rir DIR]
 
 --duration sets AudioConfig.DURATION (0.25 .. 1.0: the clip lengths augmentation and training take).
 --background DIR (the notebook's `background_noise/`) decodes the WAV / FLAC files there into a noise bank on the GPU; the training
 split then mixes them into its clips at a random SNR (AudioProcessor.set_background_noise).
+--rir DIR decodes the room impulse responses (WAV / FLAC) there into a bank of spectra on the GPU; the training split then reverberates
+half its clips with a random one before the background (AudioProcessor.set_room_impulse_responses).
 """
 import argparse
 import glob
@@ -64,6 +66,7 @@ def main():
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--duration", type=float, default=AudioConfig.DURATION, help="clip length in seconds, 0.25 .. 1.0")
     ap.add_argument("--background", default=None, help="directory of background noise files (WAV / FLAC) mixed into the training clips")
+    ap.add_argument("--rir", default=None, help="directory of room impulse responses (WAV / FLAC) convolved with the training clips")
     ap.add_argument("--background-max-seconds", type=float, default=None, help="cap on the background audio kept on the GPU")
     a = ap.parse_args()
     device = torch.device("cuda")
@@ -82,6 +85,9 @@ def main():
         bank = processor.set_background_noise(a.background, max_seconds=a.background_max_seconds)
         st = bank.stats
         print(f"Background noise: {bank} -- built at {st['audio_seconds_per_second']:.0f} s of audio/s, {st['files_per_second']:.0f} files/s")
+    if a.rir:
+        rirs = processor.set_room_impulse_responses(a.rir)
+        print(f"Room impulse responses: {rirs} -- built at {rirs.stats['files_per_second']:.0f} files/s")
     model = WakewordModel(audio_config=audio_config).to(device)
     print(f"Parameters: {sum(p.numel() for p in model.parameters()):,}")
     train_loader = DataLoader(WakewordDataset(w_tr, n_tr, processor, augment=True), batch_size=a.batch_size, shuffle=True, num_workers=2)

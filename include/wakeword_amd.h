@@ -311,6 +311,52 @@ WW_API int64_t ww_mix_background_workspace_bytes(int64_t n_clips);
 WW_API int ww_mix_background_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_bg* bg_host,
                                  const float* bank_dev, int64_t bank_len, float* out_dev, int64_t out_stride, void* workspace_dev,
                                  ww_stream_t stream);
+/* Reverberation with a room impulse response (RIR), after time_stretch + crop and before the background mix (additions only).  A bank
+ * holds each RIR as the spectrum of its kept taps h (at most WW_RIR_MAX_TAPS, direct path at dpos), zero-padded to WW_RIR_FFT_SIZE:
+ * WW_RIR_SPECTRUM_BINS complex float32 values (float pairs) per RIR, in the library's own order.  Per clip of N samples:
+ *   y[i] = sum_k h[k] x[i + dpos - k], i < N              (x zero outside [0, N): a linear convolution advanced by the direct path)
+ *   out = g y, g = sqrt(Ex / Ey)                          (float64 sums of x^2 and y^2 in a fixed order; g = 1 when either is 0)
+ * Every call below returns WW_EINVAL before any launch for an enabled clip whose index lies outside [0, n_rirs), whose taps lie outside
+ * [1, WW_RIR_MAX_TAPS] or whose dpos lies outside [0, taps); clips with enabled = 0 are not looked at and pass through unchanged. */
+#define WW_RIR_MAX_TAPS 16384
+#define WW_RIR_FFT_SIZE 32768
+#define WW_RIR_SPECTRUM_BINS 16385
+typedef struct ww_augment_rir {
+    int64_t index;        /* the RIR's spectrum in the bank, [0, n_rirs) */
+    int32_t dpos;         /* direct-path position within the kept taps, [0, taps) */
+    int32_t taps;         /* kept taps of that RIR, 1 .. WW_RIR_MAX_TAPS */
+    int32_t enabled;      /* 0 = no reverb for this clip */
+    int32_t reserved;     /* 0 */
+} ww_augment_rir;
+/* Bank build: spectra_dev [n_rirs][WW_RIR_SPECTRUM_BINS][2] from the taps of RIR r at taps_dev + offsets_host[r], lengths_host[r] of them
+ * (1 .. WW_RIR_MAX_TAPS, inside taps_len); workspace_dev >= ww_rir_spectra_workspace_bytes(n_rirs), 256-byte aligned. */
+WW_API int64_t ww_rir_spectra_workspace_bytes(int64_t n_rirs);
+WW_API int ww_rir_spectra_f32(const float* taps_dev, int64_t taps_len, const int64_t* offsets_host, const int32_t* lengths_host, int64_t n_rirs,
+                              float* spectra_dev, void* workspace_dev, ww_stream_t stream);
+/* ww_augment_bg_f32 with reverb (bg_host may be NULL: no background); spectra_dev holds n_rirs spectra; workspace_dev >=
+ * ww_augment_rir_workspace_bytes(n_clips, N).  With every rir enabled = 0 the results equal ww_augment_bg_f32's (bg_host NULL:
+ * ww_augment_n_f32's) bit for bit. */
+WW_API int64_t ww_augment_rir_workspace_bytes(int64_t n_clips, int64_t n_samples);
+WW_API int ww_augment_rir_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
+                              const ww_augment_bg* bg_host, const float* bank_dev, int64_t bank_len, const ww_augment_rir* rir_host,
+                              const float* spectra_dev, int64_t n_rirs, float* out_dev, int64_t out_stride, void* workspace_dev,
+                              ww_stream_t stream);
+/* The same in two halves, for hipGraph capture: records are ww_augment_rir_record_bytes() per clip, laid out as [n_clips] augmentation,
+ * [n_clips] background and [n_clips] reverb records (bg_host may be NULL), valid for the N, bank length and n_rirs they were prepared
+ * for (a reverb record outside n_rirs at launch passes its clip through).  The launch always runs the reverb and the mix kernels.
+ * Results equal ww_augment_rir_f32's bit for bit. */
+WW_API int64_t ww_augment_rir_record_bytes(void);
+WW_API int ww_augment_rir_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, const ww_augment_rir* rir_host,
+                                  int64_t n_clips, int64_t n_samples, int64_t bank_len, int64_t n_rirs, void* records_host);
+WW_API int ww_augment_rir_records_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* records_dev,
+                                      const float* bank_dev, int64_t bank_len, const float* spectra_dev, int64_t n_rirs, float* out_dev,
+                                      int64_t out_stride, void* workspace_dev, ww_stream_t stream);
+/* The reverb alone (no other transform), e.g. for reverberant evaluation sets: clips of N = WW_MIN_CLIP_SAMPLES .. WW_MAX_CLIP_SAMPLES
+ * samples, rows at pcm_dev + i*clip_stride and out_dev + i*out_stride (4-byte aligned, strides >= N; out may alias pcm row for row);
+ * workspace_dev >= ww_reverb_workspace_bytes(n_clips), 256-byte aligned. */
+WW_API int64_t ww_reverb_workspace_bytes(int64_t n_clips);
+WW_API int ww_reverb_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_rir* rir_host,
+                         const float* spectra_dev, int64_t n_rirs, float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream);
 /* The resampler's half-window (32769 floats: 64 zero crossings x 512 + 1) on the host, for checking on a CPU. */
 WW_API int ww_kaiser_best_host(float* out_host);
 

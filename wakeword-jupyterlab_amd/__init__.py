@@ -15,12 +15,13 @@ from . import config, synth  # noqa: F401  (no native dependency)
 def __getattr__(name):
     # lazy: `import wakeword_jupyterlab_amd` must work on a box where only host utilities are needed
     import importlib
-    if name in ("ops", "model", "audio", "dataset", "streaming", "inference", "distributed", "_native", "background"):
+    if name in ("ops", "model", "audio", "dataset", "streaming", "inference", "distributed", "_native", "background", "reverb"):
         return importlib.import_module(f"{__name__}.{name}")
     lazy = {"AudioProcessor": "audio", "WakewordDataset": "dataset", "DataLoader": "dataset", "SimpleWakewordModel": "model",
             "WakewordModel": "model", "StreamingDetector": "streaming", "predict_wakeword": "inference",
             "evaluate": "inference", "AudioConfig": "config", "ModelConfig": "config", "Config": "config",
-            "AugmentationConfig": "config", "BackgroundNoiseBank": "background"}
+            "AugmentationConfig": "config", "BackgroundNoiseBank": "background",
+            "ImpulseResponseBank": "reverb"}
     if name in lazy:
         return getattr(importlib.import_module(f"{__name__}.{lazy[name]}"), name)
     raise AttributeError(name)

@@ -81,6 +81,16 @@ class AugmentBg(C.Structure):
     ]
 
 
+class AugmentRir(C.Structure):
+    """struct ww_augment_rir (include/wakeword_amd.h): one clip's room impulse response."""
+    _fields_ = [
+        ("index", C.c_int64), ("dpos", C.c_int32), ("taps", C.c_int32), ("enabled", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+RIR_MAX_TAPS, RIR_FFT_SIZE, RIR_SPECTRUM_BINS = 16384, 32768, 16385
+
+
 FMT_S16, FMT_S24, FMT_S32, FMT_F32, FMT_U8, FMT_F64, FMT_FLAC = 1, 2, 3, 4, 5, 6, 7
 WAV_STATUS = {1: "ok", -1: "cannot open", -2: "not a RIFF/WAVE or FLAC file",
               -3: "missing fmt/data chunk, or a damaged FLAC stream (STREAMINFO, frame header or CRC)", -4: "unsupported WAV / FLAC encoding",
@@ -138,6 +148,18 @@ PROTOTYPES = {
     "ww_mix_background_workspace_bytes": (C.c_int64, [C.c_int64]),
     "ww_mix_background_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(AugmentBg), C.c_void_p, C.c_int64, C.c_void_p,
                                         C.c_int64, C.c_void_p, C.c_void_p]),
+    "ww_rir_spectra_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "ww_rir_spectra_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_augment_rir_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "ww_augment_rir_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(AugmentPlan), C.POINTER(AugmentBg), C.c_void_p,
+                                     C.c_int64, C.POINTER(AugmentRir), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ww_augment_rir_record_bytes": (C.c_int64, []),
+    "ww_augment_rir_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "ww_augment_rir_records_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ww_reverb_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "ww_reverb_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(AugmentRir), C.c_void_p, C.c_int64, C.c_void_p,
+                                C.c_int64, C.c_void_p, C.c_void_p]),
     "ww_kaiser_best_host": (C.c_int, [C.c_void_p]),
     "ww_logmel_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "ww_packed_weights_floats": (C.c_int64, [C.c_int32]),

@@ -15,6 +15,7 @@ T <= 32 (DURATION 0.25 .. 1.0, N = 4000 .. 16000 samples), and refuses longer cl
   augment_audio(audio)        -> time shift / pitch shift / time stretch / noise, each with probability 0.8
                                  (random draws from python `random` in the reference's order)  <- HIP kernels KA
   set_background_noise(paths) -> background noise at a random SNR, mixed in after the stretch (background.py; not in the reference)
+  set_room_impulse_responses(paths) -> reverberation with a random room impulse response, before the background (reverb.py; idem)
 `load_audio` / `process_audio_file` read the file with the library's native reader (csrc/ww_files.cpp) and decode, mix down and
 resample it on the GPU (kernel K0: scipy.signal.resample_poly's Kaiser design -- NOT librosa's soxr resampler, an absent third-party
 library: parity unpinned) -- the same code path as the batched loaders, one file at a time.  PCM / float WAV and FLAC.
@@ -118,6 +119,11 @@ class AudioProcessor:
             plan["bg_file"] = f
             plan["bg_start"] = random.randrange(int(bank.lengths[f]))
             plan["snr_db"] = random.uniform(config.BACKGROUND_SNR_MIN, config.BACKGROUND_SNR_MAX)
+        # reverberation: drawn only with an RIR bank attached (set_room_impulse_responses), after the background draws
+        rirs = getattr(self, "_rirs", None)
+        rir_prob = getattr(config, "RIR_PROB", 0.0)
+        if rirs is not None and rir_prob > 0 and random.random() < rir_prob:
+            plan["rir"] = random.randrange(rirs.n_rirs)
         return plan
 
     def set_background_noise(self, paths_or_bank, max_seconds=None):
@@ -140,6 +146,26 @@ class AudioProcessor:
         """The attached background.BackgroundNoiseBank, or None."""
         return getattr(self, "_background", None)
 
+    def set_room_impulse_responses(self, paths_or_bank):
+        """Attach a room impulse response bank: a reverb.ImpulseResponseBank, or the paths / directory to build one from (WAV and FLAC,
+        decoded whole on this processor's device, only their spectra kept).  From then on every augmentation of this processor --
+        augment_audio, augment_batch, process_audio_file(augment=True), WakewordDataset(augment=True) per item and through the package
+        DataLoader -- convolves a clip with a random RIR with probability RIR_PROB, after the stretch and before the background noise,
+        keeping the keyword where it was and the clip's energy.  `None` detaches the bank.  Returns the bank (or None)."""
+        from .reverb import ImpulseResponseBank
+        if paths_or_bank is None:
+            self._rirs = None
+        elif isinstance(paths_or_bank, ImpulseResponseBank):
+            self._rirs = paths_or_bank
+        else:
+            self._rirs = ImpulseResponseBank(paths_or_bank, device=self._dev())
+        return self._rirs
+
+    @property
+    def room_impulse_responses(self):
+        """The attached reverb.ImpulseResponseBank, or None."""
+        return getattr(self, "_rirs", None)
+
     def augment_batch(self, pcm, plans=None, config=AugmentationConfig) -> torch.Tensor:
         """pcm [B, N] (ndarray or tensor) -> augmented device tensor [B, N]; one plan per clip (drawn here if None).
         N = 16000 at 1 s; any configured clip length of at most 32 frames (DURATION 0.25 .. 1.0)."""
@@ -149,7 +175,10 @@ class AudioProcessor:
             t = t.to(self._dev(), non_blocking=True)
         if plans is None:
             plans = [self.draw_augment_plan(config, t.shape[1]) for _ in range(t.shape[0])]
-        return ops.augment(t, plans, bank=getattr(self, "_background", None))
+        rirs = getattr(self, "_rirs", None)
+        if rirs is None:                                      # (the call without an RIR bank is the one it always was)
+            return ops.augment(t, plans, bank=getattr(self, "_background", None))
+        return ops.augment(t, plans, bank=getattr(self, "_background", None), rirs=rirs)
 
     def augment_audio(self, audio, config=AugmentationConfig):
         """[N] samples -> augmented float32 ndarray [N] (reference :103-123), on the GPU (N = 16000 at 1 s)."""

@@ -30,6 +30,9 @@ class AugmentationConfig:
     BACKGROUND_PROB = 0.8
     BACKGROUND_SNR_MIN = 0.0
     BACKGROUND_SNR_MAX = 40.0
+    # reverberation (AudioProcessor.set_room_impulse_responses): a random RIR of the bank with this probability, before the background;
+    # 0.5 (half the clips stay close-talk) is this project's choice, not a published recipe's
+    RIR_PROB = 0.5
 
 
 class ModelConfig:            # WakewordModel (3 convs)

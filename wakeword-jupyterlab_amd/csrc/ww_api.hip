@@ -454,6 +454,123 @@ int ww_mix_background_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_st
                                  static_cast<hipStream_t>(stream));
 }
 
+// ---- reverberation (the augmentation lengths above; the standalone reverb at every inference length) ----
+static int check_rir_args(int64_t n_clips, const ww_augment_rir* rir_host, const float* spectra_dev, int64_t n_rirs) {
+    if (n_clips == 0) return WW_OK;
+    if (!rir_host) return fail(WW_EINVAL, "null rir pointer");
+    if (n_rirs < 0) return fail(WW_EINVAL, "n_rirs %lld < 0", (long long)n_rirs);
+    bool any = false;
+    for (int64_t c = 0; c < n_clips && !any; ++c) any = rir_host[c].enabled != 0;
+    if (any && !spectra_dev) return fail(WW_EINVAL, "null spectra pointer");
+    if (reinterpret_cast<uintptr_t>(spectra_dev) & 7) return fail(WW_EINVAL, "spectra_dev must be 8-byte aligned");
+    return WW_OK;
+}
+
+int64_t ww_rir_spectra_workspace_bytes(int64_t n_rirs) {
+    if (n_rirs < 0 || n_rirs > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_rirs %lld out of range", (long long)n_rirs);
+    return rir_spectra_workspace_bytes(n_rirs);
+}
+
+int ww_rir_spectra_f32(const float* taps_dev, int64_t taps_len, const int64_t* offsets_host, const int32_t* lengths_host, int64_t n_rirs,
+                       float* spectra_dev, void* workspace_dev, ww_stream_t stream) {
+    if (n_rirs < 0 || n_rirs > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_rirs %lld out of range", (long long)n_rirs);
+    if (n_rirs == 0) return WW_OK;
+    if (!taps_dev || !offsets_host || !lengths_host || !spectra_dev || !workspace_dev)
+        return fail(WW_EINVAL, "null taps / offsets / lengths / spectra / workspace pointer");
+    if ((reinterpret_cast<uintptr_t>(taps_dev) & 3) || (reinterpret_cast<uintptr_t>(spectra_dev) & 7) ||
+        (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
+        return fail(WW_EINVAL, "taps_dev must be 4-byte, spectra_dev 8-byte and workspace_dev 256-byte aligned");
+    if (taps_len < 0) return fail(WW_EINVAL, "taps_len %lld < 0", (long long)taps_len);
+    for (int64_t r = 0; r < n_rirs; ++r)      // every refusal before anything is launched (the launcher checks the same again)
+        if (lengths_host[r] < 1 || lengths_host[r] > WW_RIR_MAX_TAPS || offsets_host[r] < 0 || offsets_host[r] > taps_len - lengths_host[r])
+            return fail(WW_EINVAL, "rir %lld: taps [%lld, +%d) outside the buffer of %lld or not 1..%d", (long long)r, (long long)offsets_host[r],
+                        lengths_host[r], (long long)taps_len, WW_RIR_MAX_TAPS);
+    if (int rc = require_gfx950()) return rc;
+    return launch_rir_spectra(taps_dev, taps_len, offsets_host, lengths_host, n_rirs, spectra_dev, workspace_dev,
+                              static_cast<hipStream_t>(stream));
+}
+
+int64_t ww_augment_rir_workspace_bytes(int64_t n_clips, int64_t n_samples) {
+    if (int rc = check_aug_samples(n_samples)) return rc;
+    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    return augment_rir_workspace_bytes(n_clips, n_samples);
+}
+
+int ww_augment_rir_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
+                       const ww_augment_bg* bg_host, const float* bank_dev, int64_t bank_len, const ww_augment_rir* rir_host,
+                       const float* spectra_dev, int64_t n_rirs, float* out_dev, int64_t out_stride, void* workspace_dev,
+                       ww_stream_t stream) {
+    if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, plans_host, out_dev, out_stride, workspace_dev)) return rc;
+    if (n_clips == 0) return WW_OK;
+    if (bg_host)
+        if (int rc = check_bg_args(n_clips, bg_host, bank_dev, bank_len)) return rc;
+    if (int rc = check_rir_args(n_clips, rir_host, spectra_dev, n_rirs)) return rc;
+    {   // every refusal before anything is launched (the launcher prepares the same records again)
+        std::vector<char> rec(size_t(n_clips) * size_t(augment_rir_record_bytes()));
+        if (int rc = augment_rir_prepare(plans_host, bg_host, rir_host, n_clips, n_samples, bank_len, n_rirs, rec.data(), nullptr, nullptr,
+                                         nullptr, nullptr))
+            return rc;
+    }
+    if (int rc = require_gfx950()) return rc;
+    return launch_augment_rir(pcm_dev, n_clips, clip_stride, n_samples, plans_host, bg_host, bank_dev, bank_len, rir_host, spectra_dev, n_rirs,
+                              out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream));
+}
+
+int64_t ww_augment_rir_record_bytes(void) { return augment_rir_record_bytes(); }
+
+int ww_augment_rir_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, const ww_augment_rir* rir_host, int64_t n_clips,
+                           int64_t n_samples, int64_t bank_len, int64_t n_rirs, void* records_host) {
+    if (int rc = check_aug_samples(n_samples)) return rc;
+    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (n_clips == 0) return WW_OK;
+    if (!plans_host || !rir_host || !records_host) return fail(WW_EINVAL, "null plan / rir / record pointer");
+    if (bank_len < 0 || n_rirs < 0) return fail(WW_EINVAL, "bank_len %lld / n_rirs %lld < 0", (long long)bank_len, (long long)n_rirs);
+    return augment_rir_prepare(plans_host, bg_host, rir_host, n_clips, n_samples, bank_len, n_rirs, records_host, nullptr, nullptr, nullptr,
+                               nullptr);
+}
+
+int ww_augment_rir_records_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* records_dev,
+                               const float* bank_dev, int64_t bank_len, const float* spectra_dev, int64_t n_rirs, float* out_dev,
+                               int64_t out_stride, void* workspace_dev, ww_stream_t stream) {
+    if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, records_dev, out_dev, out_stride, workspace_dev)) return rc;
+    if (n_clips == 0) return WW_OK;
+    if (reinterpret_cast<uintptr_t>(records_dev) & 7) return fail(WW_EINVAL, "records_dev must be 8-byte aligned");
+    if (bank_len < 0 || (bank_len > 0 && !bank_dev)) return fail(WW_EINVAL, "bank: null pointer or bank_len %lld < 0", (long long)bank_len);
+    if (n_rirs < 0 || (n_rirs > 0 && !spectra_dev) || (reinterpret_cast<uintptr_t>(spectra_dev) & 7))
+        return fail(WW_EINVAL, "spectra: null or unaligned pointer, or n_rirs %lld < 0", (long long)n_rirs);
+    if (int rc = require_gfx950()) return rc;
+    return launch_augment_rir_records(pcm_dev, n_clips, clip_stride, n_samples, records_dev, bank_dev, bank_len, spectra_dev, n_rirs, out_dev,
+                                      out_stride, workspace_dev, static_cast<hipStream_t>(stream));
+}
+
+int64_t ww_reverb_workspace_bytes(int64_t n_clips) {
+    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    return reverb_workspace_bytes(n_clips);
+}
+
+int ww_reverb_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_rir* rir_host,
+                  const float* spectra_dev, int64_t n_rirs, float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream) {
+    if (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_MAX_CLIP_SAMPLES)
+        return fail(WW_EINVAL, "n_samples %lld: the reverb takes %d..%d samples (0.25 .. 2 s at 16 kHz)", (long long)n_samples,
+                    WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES);
+    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (n_clips == 0) return WW_OK;
+    if (!pcm_dev || !out_dev || !workspace_dev) return fail(WW_EINVAL, "null pcm / output / workspace pointer");
+    if (n_clips > 1 && (clip_stride < n_samples || out_stride < n_samples))
+        return fail(WW_EINVAL, "clip_stride %lld / out_stride %lld < n_samples %lld", (long long)clip_stride, (long long)out_stride,
+                    (long long)n_samples);
+    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 3) || (reinterpret_cast<uintptr_t>(out_dev) & 3) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
+        return fail(WW_EINVAL, "pcm_dev / out_dev must be 4-byte and workspace_dev 256-byte aligned");
+    if (int rc = check_rir_args(n_clips, rir_host, spectra_dev, n_rirs)) return rc;
+    {
+        std::vector<char> rec(size_t(reverb_workspace_bytes(n_clips)));
+        if (int rc = rir_prepare(rir_host, n_clips, n_rirs, rec.data(), nullptr)) return rc;
+    }
+    if (int rc = require_gfx950()) return rc;
+    return launch_reverb(pcm_dev, n_clips, clip_stride, n_samples, rir_host, spectra_dev, n_rirs, out_dev, out_stride, workspace_dev,
+                         static_cast<hipStream_t>(stream));
+}
+
 int64_t ww_cnn_scratch_bytes(int64_t n, int32_t n_conv) { return cnn_scratch_bytes(n, n_conv); }
 
 int ww_cnn_pool_f32(const float* mel_dev, int64_t n, int32_t width, const float* packed_dev, int32_t n_conv,

@@ -17,6 +17,8 @@
 //   resample_kernel   windowed-sinc interpolation at t = i / ratio (resampy 'kaiser_best' table in LDS, float32 MACs): the stand-in
 //                     for librosa's soxr_hq (absent third-party library; parity unpinned)
 //   noise_kernel      + sigma * normal(seed, i), the build's counter-based generator (splitmix64 -> Box-Muller)
+//   reverb_kernel     (ww_reverb.hip) the clip convolved with a room impulse response, energy kept: one workgroup per clip; runs
+//                     between the stretch and the mix in a batch where some clip has reverb on
 //   mix_kernel        background noise at an SNR, then the same Gaussian noise: one workgroup per clip (whole-clip energies first);
 //                     replaces noise_kernel in a batch where some clip has background on
 // Clips whose plan switches a transform off skip its kernels (their blocks copy the data through).
@@ -684,11 +686,13 @@ int64_t augment_record_bytes() { return int64_t(sizeof(AugDev)); }
 
 // The kernels alone, on records already in device memory: nothing but launches on `stream` (capturable into a hipGraph).  A stage whose
 // flag is off for a clip copies that clip through, so both stages may always be launched (what a captured graph must do).
-// With `bg` (background records) the last launch is mix_kernel, which adds the background and then the same Gaussian noise.
+// With `rir` (reverb records) reverb_kernel (ww_reverb.hip) runs after the stretch; with `bg` (background records) the last launch is
+// mix_kernel, which adds the background and then the same Gaussian noise.
 template <int kN>
 static int launch_records(const float* pcm, int64_t n, int64_t stride, int n_samples, const AugDev* plan, bool any_pitch, bool any_stretch,
                           float* out, int64_t out_stride, void* workspace, hipStream_t stream, const BgDev* bg = nullptr,
-                          const float* bank = nullptr, int64_t bank_len = 0) {
+                          const float* bank = nullptr, int64_t bank_len = 0, const RirDev* rir = nullptr, const float* spectra = nullptr,
+                          int64_t n_rirs = 0) {
     const LogmelTables* tb = device_tables();
     if (!tb) return WW_EHIP;
     const int64_t row = aug_row_host(n_samples);
@@ -726,6 +730,10 @@ static int launch_records(const float* pcm, int64_t n, int64_t stride, int n_sam
     if (any_stretch) {
         hipLaunchKernelGGL(stft_pv_kernel<kN>, dim3(unsigned(n)), dim3(256), kStftPvLds, stream, cur, plan, 1, tb, S, nn);
         hipLaunchKernelGGL(istft_kernel<kN>, dim3(unsigned(n)), dim3(256), kIstftLds, stream, S, plan, 1, tb, cur, other, row, nn);
+        float* t = cur; cur = other; other = t;
+    }
+    if (rir) {
+        if (int rc = launch_reverb_records(cur, row, n, nn, rir, reinterpret_cast<const float2*>(spectra), n_rirs, other, row, stream)) return rc;
         float* t = cur; cur = other; other = t;
     }
     if (bg)
@@ -832,7 +840,7 @@ static std::mutex g_bstage_mu;
 static ByteStage g_bstage[16][2];
 static int g_bstage_next[16] = {};
 
-static int stage_to_device(const void* src, const size_t* sizes, void* const* dst, int pieces, hipStream_t stream) {
+int stage_to_device(const void* src, const size_t* sizes, void* const* dst, int pieces, hipStream_t stream) {
     size_t total = 0;
     for (int i = 0; i < pieces; ++i) total += sizes[i];
     int dev = 0;
@@ -921,6 +929,70 @@ int launch_mix_background(const float* pcm, int64_t n, int64_t stride, int64_t n
                            out_stride, nn);
     WW_HIP(hipGetLastError());
     return WW_OK;
+}
+
+// ---- background + reverb ----------------------------------------------------------------------------------------------------------------
+int64_t augment_rir_record_bytes() { return int64_t(sizeof(AugDev) + sizeof(BgDev) + sizeof(RirDev)); }
+
+int64_t augment_rir_workspace_bytes(int64_t n, int64_t n_samples) {
+    return augment_bg_workspace_bytes(n, n_samples) + up256(n * int64_t(sizeof(RirDev)));
+}
+
+// records = [n] AugDev, [n] BgDev, [n] RirDev (ww_augment_rir_record_bytes() per clip); bg_host NULL = no background
+int augment_rir_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, const ww_augment_rir* rir_host, int64_t n,
+                        int64_t n_samples, int64_t bank_len, int64_t n_rirs, void* records_host, int* any_pitch_out, int* any_stretch_out,
+                        int* any_bg_out, int* any_rir_out) {
+    char* rec = static_cast<char*>(records_host);
+    if (int rc = rir_prepare(rir_host, n, n_rirs, rec + n * int64_t(sizeof(AugDev) + sizeof(BgDev)), any_rir_out)) return rc;
+    if (bg_host) {
+        if (int rc = background_prepare(bg_host, n, bank_len, rec + n * int64_t(sizeof(AugDev)), any_bg_out)) return rc;
+    } else {
+        std::memset(rec + n * int64_t(sizeof(AugDev)), 0, size_t(n) * sizeof(BgDev));
+        if (any_bg_out) *any_bg_out = 0;
+    }
+    return augment_prepare(plans_host, n, n_samples, records_host, any_pitch_out, any_stretch_out);
+}
+
+int launch_augment_rir_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, const float* bank,
+                               int64_t bank_len, const float* spectra, int64_t n_rirs, float* out, int64_t out_stride, void* workspace,
+                               hipStream_t stream) {
+    if (n == 0) return WW_OK;
+    const char* rec = static_cast<const char*>(records_dev);
+    const AugDev* plan = reinterpret_cast<const AugDev*>(rec);
+    const BgDev* bg = reinterpret_cast<const BgDev*>(rec + n * int64_t(sizeof(AugDev)));
+    const RirDev* rir = reinterpret_cast<const RirDev*>(rec + n * int64_t(sizeof(AugDev) + sizeof(BgDev)));
+    if (n_samples == kClip)
+        return launch_records<kClip>(pcm, n, stride, kClip, plan, true, true, out, out_stride, workspace, stream, bg, bank, bank_len, rir,
+                                     spectra, n_rirs);
+    return launch_records<0>(pcm, n, stride, int(n_samples), plan, true, true, out, out_stride, workspace, stream, bg, bank, bank_len, rir,
+                             spectra, n_rirs);
+}
+
+// The direct call: AugDev and BgDev staged as launch_augment_bg stages them, RirDev past augment_bg_workspace_bytes; a stage no clip
+// uses is not launched (with every reverb off the launches are launch_augment_bg's)
+int launch_augment_rir(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host,
+                       const ww_augment_bg* bg_host, const float* bank, int64_t bank_len, const ww_augment_rir* rir_host, const float* spectra,
+                       int64_t n_rirs, float* out, int64_t out_stride, void* workspace, hipStream_t stream) {
+    if (n == 0) return WW_OK;
+    const size_t rb = size_t(n) * sizeof(AugDev), bb = size_t(n) * sizeof(BgDev), vb = size_t(n) * sizeof(RirDev);
+    std::vector<char> host(rb + bb + vb);
+    int any_pitch = 0, any_stretch = 0, any_bg = 0, any_rir = 0;
+    if (int rc = augment_rir_prepare(plans_host, bg_host, rir_host, n, n_samples, bank_len, n_rirs, host.data(), &any_pitch, &any_stretch,
+                                     &any_bg, &any_rir))
+        return rc;
+    AugDev* plan = static_cast<AugDev*>(workspace);
+    BgDev* bg = reinterpret_cast<BgDev*>(static_cast<char*>(workspace) + augment_workspace_bytes(n, n_samples));
+    RirDev* rir = reinterpret_cast<RirDev*>(static_cast<char*>(workspace) + augment_bg_workspace_bytes(n, n_samples));
+    const size_t sizes[3] = {rb, bb, vb};
+    void* const dst[3] = {plan, bg, rir};
+    if (int rc = stage_to_device(host.data(), sizes, dst, 3, stream)) return rc;
+    const BgDev* bgp = any_bg ? bg : nullptr;
+    const RirDev* rp = any_rir ? rir : nullptr;
+    if (n_samples == kClip)
+        return launch_records<kClip>(pcm, n, stride, kClip, plan, any_pitch != 0, any_stretch != 0, out, out_stride, workspace, stream, bgp, bank,
+                                     bank_len, rp, spectra, n_rirs);
+    return launch_records<0>(pcm, n, stride, int(n_samples), plan, any_pitch != 0, any_stretch != 0, out, out_stride, workspace, stream, bgp,
+                             bank, bank_len, rp, spectra, n_rirs);
 }
 
 }  // namespace ww

@@ -148,6 +148,36 @@ int launch_augment_bg_records(const float* pcm, int64_t n, int64_t stride, int64
 int64_t mix_background_workspace_bytes(int64_t n);
 int launch_mix_background(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_bg* bg_host, const float* bank,
                           int64_t bank_len, float* out, int64_t out_stride, void* workspace, hipStream_t stream);
+// pinned staging of host records into device memory (ww_augment.hip): `pieces` consecutive byte ranges of src to their own addresses
+int stage_to_device(const void* src, const size_t* sizes, void* const* dst, int pieces, hipStream_t stream);
+// reverberation (ww_reverb.hip): the callers check N and the pointers; the rir records are checked here, before any launch
+struct RirDev {            // one per clip, derived on the host from ww_augment_rir
+    int64_t index;         // the RIR's spectrum; -1 = no reverb for this clip
+    int32_t dpos;          // direct-path position within the kept taps
+    int32_t pad_;
+};
+int64_t rir_record_bytes();
+int rir_prepare(const ww_augment_rir* rir_host, int64_t n, int64_t n_rirs, void* records_host, int* any_out);
+int launch_reverb_records(const float* in, int64_t in_stride, int64_t n, int n_samples, const RirDev* rir, const float2* spectra,
+                          int64_t n_rirs, float* out, int64_t out_stride, hipStream_t stream);
+int64_t reverb_workspace_bytes(int64_t n);
+int launch_reverb(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_rir* rir_host, const float* spectra,
+                  int64_t n_rirs, float* out, int64_t out_stride, void* workspace, hipStream_t stream);
+int64_t rir_spectra_workspace_bytes(int64_t n_rirs);
+int launch_rir_spectra(const float* taps, int64_t taps_len, const int64_t* offsets_host, const int32_t* lengths_host, int64_t n_rirs,
+                       float* spectra, void* workspace, hipStream_t stream);
+// KA with background and reverb (ww_augment.hip)
+int64_t augment_rir_workspace_bytes(int64_t n, int64_t n_samples);
+int64_t augment_rir_record_bytes();
+int augment_rir_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, const ww_augment_rir* rir_host, int64_t n,
+                        int64_t n_samples, int64_t bank_len, int64_t n_rirs, void* records_host, int* any_pitch_out, int* any_stretch_out,
+                        int* any_bg_out, int* any_rir_out);
+int launch_augment_rir(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host,
+                       const ww_augment_bg* bg_host, const float* bank, int64_t bank_len, const ww_augment_rir* rir_host, const float* spectra,
+                       int64_t n_rirs, float* out, int64_t out_stride, void* workspace, hipStream_t stream);
+int launch_augment_rir_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, const float* bank,
+                               int64_t bank_len, const float* spectra, int64_t n_rirs, float* out, int64_t out_stride, void* workspace,
+                               hipStream_t stream);
 void build_kaiser_best(float* out /*[32769]*/);
 int sync_timeouts(unsigned int* count);   // bounded LDS-counter waits that expired (must be 0)
 int launch_cnn_pool(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch,

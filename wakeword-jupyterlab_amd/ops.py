@@ -527,7 +527,7 @@ if _os.environ.get("WW_LOGMEL_MATH"):
 AUG_MAX_SAMPLES = 16383                 # T = 1 + N // 512 <= 32 frames: the clip lengths training takes (4000 .. 16383 samples)
 
 
-def augment(pcm: torch.Tensor, plans, bank=None) -> torch.Tensor:
+def augment(pcm: torch.Tensor, plans, bank=None, rirs=None) -> torch.Tensor:
     """pcm [B, N] float32 on the GPU + one plan per clip -> augmented [B, N], N = 16000 (ww_augment_f32) or any N in 4000..16383
     (ww_augment_n_f32; the plans' shift is taken mod N and crop lies in [0, round(N / rate) - N]).
 
@@ -535,7 +535,9 @@ def augment(pcm: torch.Tensor, plans, bank=None) -> torch.Tensor:
     (shift, n_steps | pitch_rate, rate, crop, sigma, seed); see AudioProcessor.draw_augment_plan.
     With a background.BackgroundNoiseBank, dict plans that carry `bg_file`, `bg_start` and `snr_db` get that file's segment mixed in after
     the stretch and before the Gaussian noise (ww_augment_bg_f32); clips without those keys, and a batch where no plan has them, give
-    exactly what they give without a bank."""
+    exactly what they give without a bank.
+    With a reverb.ImpulseResponseBank (`rirs`), dict plans that carry `rir` get that room impulse response after the stretch and before
+    the background (ww_augment_rir_f32); clips without the key, and a batch where no plan has it, give exactly what they give without."""
     import ctypes as C
     if pcm.device.type != "cuda":
         raise RuntimeError("augment: pcm must live on the MI355X (no CPU fallback)")
@@ -544,10 +546,12 @@ def augment(pcm: torch.Tensor, plans, bank=None) -> torch.Tensor:
     N = int(pcm.shape[1])
     pcm = pcm.contiguous() if N == CLIP_SAMPLES else _aligned_rows(pcm)
     B = pcm.shape[0]
-    bg_plans = None
+    bg_plans = rir_plans = None
     if not isinstance(plans, C.Array):
         if bank is not None and any("bg_file" in p for p in plans):
             bg_plans = plans
+        if rirs is not None and any(p.get("rir") is not None for p in plans):
+            rir_plans = plans
         arr = (nat.AugmentPlan * max(1, B))()
         if len(plans) != B:
             raise ValueError(f"augment: {len(plans)} plans for {B} clips")
@@ -564,12 +568,22 @@ def augment(pcm: torch.Tensor, plans, bank=None) -> torch.Tensor:
     elif len(plans) < B:
         raise ValueError(f"augment: {len(plans)} plans for {B} clips")
     bg = _bg_array(bg_plans, bank, B) if bank is not None and bg_plans else None
+    rir = _rir_array(rir_plans, rirs, B) if rirs is not None and rir_plans else None
     out = torch.empty((B, N), device=pcm.device, dtype=torch.float32)
     if B == 0:
         return out
     with torch.cuda.device(pcm.device):
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if bg is not None:
+        if rir is not None:
+            _check_rirs(rirs, pcm.device)
+            if bg is not None:
+                _check_bank(bank, pcm.device)
+            ws = torch.empty(nat.check(nat.lib.ww_augment_rir_workspace_bytes(B, N)), device=pcm.device, dtype=torch.uint8)
+            nat.check(nat.lib.ww_augment_rir_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, plans, bg,
+                                                 C.c_void_p(bank.data.data_ptr()) if bg is not None else None,
+                                                 bank.data.numel() if bg is not None else 0, rir, C.c_void_p(rirs.spectra.data_ptr()),
+                                                 rirs.n_rirs, C.c_void_p(out.data_ptr()), N, C.c_void_p(ws.data_ptr()), stream))
+        elif bg is not None:
             _check_bank(bank, pcm.device)
             ws = torch.empty(nat.check(nat.lib.ww_augment_bg_workspace_bytes(B, N)), device=pcm.device, dtype=torch.uint8)
             nat.check(nat.lib.ww_augment_bg_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, plans, bg,
@@ -638,5 +652,55 @@ def mix_background(pcm: torch.Tensor, bank, files, starts, snr_db) -> torch.Tens
         nat.check(nat.lib.ww_mix_background_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, bg,
                                                 C.c_void_p(bank.data.data_ptr()), bank.data.numel(), C.c_void_p(out.data_ptr()), N,
                                                 C.c_void_p(ws.data_ptr()), stream))
+        ws.record_stream(torch.cuda.current_stream())
+    return out
+
+
+def _check_rirs(rirs, device) -> None:
+    spectra = getattr(rirs, "spectra", None)
+    if not isinstance(spectra, torch.Tensor) or spectra.dtype != torch.float32 or spectra.dim() != 3 or not spectra.is_contiguous():
+        raise TypeError("rirs: expected a reverb.ImpulseResponseBank")
+    if spectra.device != device:
+        raise ValueError(f"rirs: lives on {spectra.device}, the clips on {device}")
+
+
+def _rir_array(plans, rirs, B):
+    """Plans (dicts with `rir`, or without it: no reverb) -> ctypes array of _native.AugmentRir."""
+    arr = (nat.AugmentRir * max(1, B))()
+    for i, p in enumerate(plans):
+        r = p.get("rir")
+        if r is None:
+            continue
+        r = int(r)
+        if not 0 <= r < rirs.n_rirs:
+            raise ValueError(f"rir {r}: the bank holds {rirs.n_rirs} impulse responses")
+        a = arr[i]
+        a.index, a.dpos, a.taps, a.enabled = r, int(rirs.dpos[r]), int(rirs.lengths[r]), 1
+    return arr
+
+
+def reverb(pcm: torch.Tensor, rirs, index) -> torch.Tensor:
+    """The reverb alone (ww_reverb_f32): pcm [B, N] float32 on the GPU, N in 4000..32000 (every inference length) -> [B, N] with clip i
+    convolved with bank RIR `index[i]` (a scalar applies to every clip), advanced by its direct-path delay and rescaled to the clip's
+    energy.  A negative index leaves that clip as it is.  For reverberant evaluation sets."""
+    if pcm.device.type != "cuda":
+        raise RuntimeError("reverb: pcm must live on the MI355X (no CPU fallback)")
+    if pcm.dtype != torch.float32 or pcm.dim() != 2 or not MIN_CLIP_SAMPLES <= pcm.shape[1] <= MAX_CLIP_SAMPLES:
+        raise ValueError(f"reverb: expected float32 [B, N], N in {MIN_CLIP_SAMPLES}..{MAX_CLIP_SAMPLES}, got {pcm.dtype} {tuple(pcm.shape)}")
+    _check_rirs(rirs, pcm.device)
+    B, N = int(pcm.shape[0]), int(pcm.shape[1])
+    if pcm.stride(1) != 1:
+        pcm = pcm.contiguous()
+    idx = np.broadcast_to(np.asarray(index, dtype=np.int64), (B,))
+    rir = _rir_array([{} if idx[i] < 0 else {"rir": int(idx[i])} for i in range(B)], rirs, B)
+    out = torch.empty((B, N), device=pcm.device, dtype=torch.float32)
+    if B == 0:
+        return out
+    with torch.cuda.device(pcm.device):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ws = torch.empty(nat.check(nat.lib.ww_reverb_workspace_bytes(B)), device=pcm.device, dtype=torch.uint8)
+        nat.check(nat.lib.ww_reverb_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, rir,
+                                        C.c_void_p(rirs.spectra.data_ptr()), rirs.n_rirs, C.c_void_p(out.data_ptr()), N,
+                                        C.c_void_p(ws.data_ptr()), stream))
         ws.record_stream(torch.cuda.current_stream())
     return out
