@@ -542,6 +542,23 @@ WW_API int ww_streamer_step(ww_streamer* s, const float* hop_dev, float* prob_de
 WW_API int ww_streamer_window(ww_streamer* s, float* window_dev);
 WW_API int ww_streamer_destroy(ww_streamer* s);
 
+/* A streamer fed at the microphone's own rate, sample format and channel count.  sample_rate: any rate K0 takes (1000 .. 384000 Hz);
+ * format: WW_FMT_S16, S24, S32, F32, U8 or F64 (not FLAC); channels: 1 .. 8, frames interleaved as in a WAV data chunk.  With
+ * (up, down) = ww_resample_taps_host(sample_rate), hop_frames * up must be a multiple of down and the 16 kHz hop
+ * hop_frames * up / down must satisfy ww_streamer_create_n's rule (a multiple of 4 that divides N).  The window length is checked
+ * first (WW_EUNSUPPORTED), then rate, format, channels and hop (WW_EINVAL), all before any HIP call.
+ * The window holds exactly what K0 computes, without normalisation, for a file of every frame pushed so far (bit for bit: the same
+ * conversion, the same filter, the same fused multiply-add order), delayed by ww_streamer_latency() samples at 16 kHz: the
+ * outputs whose filter still reaches frames that have not arrived.  At (16000, WW_FMT_F32, 1) this is ww_streamer_create_n's
+ * streamer, the same graph node for node. */
+WW_API int ww_streamer_create_input(int32_t n_mics, int32_t hop_frames, int32_t sample_rate, int32_t format, int32_t channels,
+                                    int32_t n_samples, const float* packed_dev, int32_t n_conv, ww_stream_t stream, ww_streamer** out);
+/* hop_dev [n_mics][hop_frames][channels] in the streamer's sample format, aligned to its sample size (1 byte for U8 and S24);
+ * prob_dev and logits_dev as for ww_streamer_step.  Also takes a streamer of ww_streamer_create_n (float32 mono hops). */
+WW_API int ww_streamer_step_input(ww_streamer* s, const void* hop_dev, float* prob_dev, float* logits_dev);
+/* D: the 16 kHz samples the window lags the input by (0 at 16 kHz); a negative WW_E* for a null handle. */
+WW_API int ww_streamer_latency(const ww_streamer* s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,10 @@ PROTOTYPES = {
     "ww_streamer_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_streamer_window": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ww_streamer_destroy": (C.c_int, [C.c_void_p]),
+    "ww_streamer_create_input": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ww_streamer_step_input": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_streamer_latency": (C.c_int, [C.c_void_p]),
 }
 
 

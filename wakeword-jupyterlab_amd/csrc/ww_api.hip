@@ -140,11 +140,14 @@ struct ww_streamer {
     const float* packed;
     hipStream_t stream;
     float* ring;         // [n_mics][n_samples]
-    int32_t* pos;        // device: [0] index of the oldest sample (== next write position), [1] append-kernel ticket
+    int32_t* pos;        // device: [0] index of the oldest sample (== next write position), [1] append-kernel ticket,
+                         // [2], [3] the input-format kernel's history parity and hop count
+    bool input;          // hops in the microphone's own format (ww_streamer_create_input other than 16 kHz float32 mono)
+    StreamInput in;      // its rate, format, channels, filter table and history
     void* workspace;
     hipGraph_t graph;
     hipGraphExec_t exec;
-    const float* cap_hop;
+    const void* cap_hop;
     float* cap_prob;
     float* cap_logits;
     float* own_logits;   // used when the caller passes logits_dev == NULL
@@ -183,12 +186,17 @@ __global__ void ring_unroll_kernel(const float* __restrict__ ring, const int32_t
     }
 }
 
-static int streamer_enqueue(ww_streamer* s, const float* hop_dev, float* prob_dev, float* logits_dev) {
-    const int threads = 256;
-    const int blocks = (s->n_mics * s->hop + threads - 1) / threads;
-    hipLaunchKernelGGL(ring_append_kernel, dim3(blocks), dim3(threads), 0, s->stream, s->ring, s->pos,
-                       reinterpret_cast<uint32_t*>(s->pos + 1), hop_dev, s->n_mics, s->hop, s->n_samples);
-    WW_HIP(hipGetLastError());
+static int streamer_enqueue(ww_streamer* s, const void* hop_dev, float* prob_dev, float* logits_dev) {
+    if (s->input) {
+        // convert + resample the hop into the ring (ww_decode.hip), in place of the float32 16 kHz append
+        if (int rc = launch_stream_input(s->in, hop_dev, s->n_mics, s->ring, s->pos, s->n_samples, s->stream)) return rc;
+    } else {
+        const int threads = 256;
+        const int blocks = (s->n_mics * s->hop + threads - 1) / threads;
+        hipLaunchKernelGGL(ring_append_kernel, dim3(blocks), dim3(threads), 0, s->stream, s->ring, s->pos,
+                           reinterpret_cast<uint32_t*>(s->pos + 1), static_cast<const float*>(hop_dev), s->n_mics, s->hop, s->n_samples);
+        WW_HIP(hipGetLastError());
+    }
     // N = 16000 (T = 32) is launch_logmel's 1 s ring kernel with the same arguments as ever; other N the 64-frame tile in ring form
     const int N = s->n_samples;
     Workspace w = carve(s->workspace, s->n_mics, s->n_conv, s->n_frames);
@@ -778,17 +786,10 @@ int ww_train_backward_f32(const float* mel_dev, int64_t n, int32_t width, const 
     return train_backward(mel_dev, n, width, params, dlogits_dev, mode, workspace_dev, workspace_bytes, grads, static_cast<hipStream_t>(stream));
 }
 
-int ww_streamer_create_n(int32_t n_mics, int32_t hop_samples, int32_t n_samples, const float* packed_dev, int32_t n_conv,
-                         ww_stream_t stream, ww_streamer** out) {
-    if (!out) return fail(WW_EINVAL, "null out pointer");
-    *out = nullptr;
-    if (n_mics < 1 || n_mics > (1 << 20)) return fail(WW_EINVAL, "n_mics %d out of range", n_mics);
+// in: nullptr for float32 16 kHz mono hops (ww_streamer_create_n), else the checked input format
+static int streamer_create(int32_t n_mics, int32_t hop_samples, int32_t n_samples, const StreamInput* in, const float* packed_dev,
+                           int32_t n_conv, ww_stream_t stream, ww_streamer** out) {
     const int N = n_samples;
-    if (N != kClip && (N < WW_MIN_CLIP_SAMPLES || N > WW_AUG_MAX_SAMPLES))
-        return fail(WW_EUNSUPPORTED, "n_samples %d: streaming windows take %d..%d samples (0.25 .. 1 s, at most 32 frames) or %d", N,
-                    WW_MIN_CLIP_SAMPLES, WW_AUG_MAX_SAMPLES, kClip);
-    if (hop_samples < 4 || hop_samples > N || (hop_samples & 3) || (N % hop_samples))
-        return fail(WW_EINVAL, "hop_samples %d: must be a multiple of 4 that divides %d", hop_samples, N);
     const int T = 1 + N / kHop;
     if (int rc = check_model(n_mics, T, packed_dev, n_conv)) return rc;
     if (!device_tables()) return WW_EHIP;   // also the gfx950 check; must precede graph capture
@@ -797,6 +798,7 @@ int ww_streamer_create_n(int32_t n_mics, int32_t hop_samples, int32_t n_samples,
     s->n_mics = n_mics; s->hop = hop_samples; s->n_conv = n_conv; s->packed = packed_dev;
     s->n_samples = N; s->n_frames = T;
     s->stream = static_cast<hipStream_t>(stream);
+    if (in) { s->input = true; s->in = *in; }
     const int64_t ws = carve(nullptr, n_mics, n_conv, T).total;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->ring), sizeof(float) * int64_t(n_mics) * N);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->pos), 16);
@@ -808,8 +810,45 @@ int ww_streamer_create_n(int32_t n_mics, int32_t hop_samples, int32_t n_samples,
         ww_streamer_destroy(s);
         return fail(WW_EHIP, "streamer allocation failed: %s", hipGetErrorString(e));
     }
+    if (in) {
+        if (int rc = stream_input_alloc(&s->in, n_mics, s->stream)) {
+            ww_streamer_destroy(s);
+            return rc;
+        }
+    }
     *out = s;
     return WW_OK;
+}
+
+static int check_streamer_window(int32_t n_mics, int32_t n_samples) {
+    if (n_mics < 1 || n_mics > (1 << 20)) return fail(WW_EINVAL, "n_mics %d out of range", n_mics);
+    const int N = n_samples;
+    if (N != kClip && (N < WW_MIN_CLIP_SAMPLES || N > WW_AUG_MAX_SAMPLES))
+        return fail(WW_EUNSUPPORTED, "n_samples %d: streaming windows take %d..%d samples (0.25 .. 1 s, at most 32 frames) or %d", N,
+                    WW_MIN_CLIP_SAMPLES, WW_AUG_MAX_SAMPLES, kClip);
+    return WW_OK;
+}
+
+int ww_streamer_create_n(int32_t n_mics, int32_t hop_samples, int32_t n_samples, const float* packed_dev, int32_t n_conv,
+                         ww_stream_t stream, ww_streamer** out) {
+    if (!out) return fail(WW_EINVAL, "null out pointer");
+    *out = nullptr;
+    if (int rc = check_streamer_window(n_mics, n_samples)) return rc;
+    const int N = n_samples;
+    if (hop_samples < 4 || hop_samples > N || (hop_samples & 3) || (N % hop_samples))
+        return fail(WW_EINVAL, "hop_samples %d: must be a multiple of 4 that divides %d", hop_samples, N);
+    return streamer_create(n_mics, hop_samples, n_samples, nullptr, packed_dev, n_conv, stream, out);
+}
+
+int ww_streamer_create_input(int32_t n_mics, int32_t hop_frames, int32_t sample_rate, int32_t format, int32_t channels, int32_t n_samples,
+                             const float* packed_dev, int32_t n_conv, ww_stream_t stream, ww_streamer** out) {
+    if (!out) return fail(WW_EINVAL, "null out pointer");
+    *out = nullptr;
+    if (int rc = check_streamer_window(n_mics, n_samples)) return rc;
+    StreamInput in{};
+    if (int rc = stream_input_check(sample_rate, format, channels, hop_frames, n_samples, &in)) return rc;
+    const bool plain = sample_rate == WW_SAMPLE_RATE && format == WW_FMT_F32 && channels == 1;   // today's streamer, node for node
+    return streamer_create(n_mics, in.hop_out, n_samples, plain ? nullptr : &in, packed_dev, n_conv, stream, out);
 }
 
 int ww_streamer_create(int32_t n_mics, int32_t hop_samples, const float* packed_dev, int32_t n_conv,
@@ -817,9 +856,7 @@ int ww_streamer_create(int32_t n_mics, int32_t hop_samples, const float* packed_
     return ww_streamer_create_n(n_mics, hop_samples, kClip, packed_dev, n_conv, stream, out);
 }
 
-int ww_streamer_step(ww_streamer* s, const float* hop_dev, float* prob_dev, float* logits_dev) {
-    if (!s || !hop_dev || !prob_dev) return fail(WW_EINVAL, "null argument");
-    if (reinterpret_cast<uintptr_t>(hop_dev) & 3) return fail(WW_EINVAL, "hop_dev must be float-aligned");
+static int streamer_replay(ww_streamer* s, const void* hop_dev, float* prob_dev, float* logits_dev) {
     float* lg = logits_dev ? logits_dev : s->own_logits;
     if (!s->exec || s->cap_hop != hop_dev || s->cap_prob != prob_dev || s->cap_logits != lg) {
         // (re)capture: the I/O pointers are baked into the graph's kernel nodes
@@ -839,6 +876,26 @@ int ww_streamer_step(ww_streamer* s, const float* hop_dev, float* prob_dev, floa
     return WW_OK;
 }
 
+int ww_streamer_step(ww_streamer* s, const float* hop_dev, float* prob_dev, float* logits_dev) {
+    if (!s || !hop_dev || !prob_dev) return fail(WW_EINVAL, "null argument");
+    if (reinterpret_cast<uintptr_t>(hop_dev) & 3) return fail(WW_EINVAL, "hop_dev must be float-aligned");
+    if (s->input) return fail(WW_EINVAL, "this streamer takes hops at %d Hz in format %d: use ww_streamer_step_input", s->in.rate, s->in.format);
+    return streamer_replay(s, hop_dev, prob_dev, logits_dev);
+}
+
+int ww_streamer_step_input(ww_streamer* s, const void* hop_dev, float* prob_dev, float* logits_dev) {
+    if (!s || !hop_dev || !prob_dev) return fail(WW_EINVAL, "null argument");
+    const int bytes = s->input ? sample_bytes(s->in.format) : 4;
+    const int align = bytes == 3 ? 1 : bytes;                   // S24: packed 3-byte samples, read byte by byte
+    if (reinterpret_cast<uintptr_t>(hop_dev) & (align - 1)) return fail(WW_EINVAL, "hop_dev must be aligned to %d bytes", align);
+    return streamer_replay(s, hop_dev, prob_dev, logits_dev);
+}
+
+int ww_streamer_latency(const ww_streamer* s) {
+    if (!s) return fail(WW_EINVAL, "null argument");
+    return s->input ? s->in.latency : 0;
+}
+
 int ww_streamer_window(ww_streamer* s, float* window_dev) {
     if (!s || !window_dev) return fail(WW_EINVAL, "null argument");
     hipLaunchKernelGGL(ring_unroll_kernel, dim3(1024), dim3(256), 0, s->stream, s->ring, s->pos, window_dev, s->n_mics, s->n_samples);
@@ -854,6 +911,7 @@ int ww_streamer_destroy(ww_streamer* s) {
     if (s->pos) (void)hipFree(s->pos);
     if (s->workspace) (void)hipFree(s->workspace);
     if (s->own_logits) (void)hipFree(s->own_logits);
+    stream_input_free(&s->in);
     delete s;
     return WW_OK;
 }

@@ -311,6 +311,210 @@ __global__ __launch_bounds__(256) void decode_resample_kernel(const uint8_t* __r
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// Streaming at the microphone's rate: K0's filter, one hop at a time
+// ---------------------------------------------------------------------------------------------
+// Output j of K0 is the fma chain over input frames i in [max(0, ceil((c - lh + 1) / up)), floor(c / up)], c = (j + n_pre_remove) * down -
+// n_pre_pad, tap c - i * up.  A hop of hop_in frames starting at frame b = k * hop_in (k hops before it) completes the outputs whose last
+// frame is in the hop: with hop_in * up == hop_out * down these are j = k * hop_out - D + q, q in [0, hop_out), D = n_pre_remove - 1, and
+// c = b * up + (q + 1) * down - n_pre_pad.  Relative to b the frame range and the first tap depend on q alone: one table for every hop.
+int sample_bytes(int format) {
+    switch (format) {
+        case WW_FMT_U8: return 1;
+        case WW_FMT_S16: return 2;
+        case WW_FMT_S24: return 3;
+        case WW_FMT_S32: case WW_FMT_F32: return 4;
+        case WW_FMT_F64: return 8;
+        default: return 0;
+    }
+}
+
+constexpr int kStreamThreads = 256;
+constexpr int kStreamSpan = 4096;       // at most this many mono input frames per output block, in LDS
+constexpr int kStreamLds = kRsTaps + kRsSpan;   // floats of LDS: K0's 64,512 B budget for the taps and the block's frames
+constexpr int kStreamHopsCap = 1 << 20; // pos[3] saturates here: k * hop_in is then past any history length
+
+static int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+static void stream_table(const StreamInput& si, std::vector<int32_t>& tab) {
+    const int npp = si.down - (si.lh / 2) % si.down;
+    tab.assign(3 * size_t(si.hop_out), 0);
+    for (int q = 0; q < si.hop_out; ++q) {
+        const int64_t cr = int64_t(q + 1) * si.down - npp;                         // c - b * up, >= 1
+        const int64_t lo = -floor_div(-(cr - si.lh + 1), si.up), hi = cr / si.up;  // ceil, floor
+        tab[q] = int32_t(lo);
+        tab[si.hop_out + q] = int32_t(cr - lo * si.up);
+        tab[2 * si.hop_out + q] = int32_t(hi - lo + 1);
+    }
+}
+
+int stream_input_check(int rate, int format, int channels, int hop_in, int n_samples, StreamInput* si) {
+    if (rate < 1000 || rate > 384000) return fail(WW_EINVAL, "sample_rate %d: expected 1000..384000 Hz", rate);
+    if (sample_bytes(format) == 0) return fail(WW_EINVAL, "format %d: expected a PCM WW_FMT_* (S16, S24, S32, F32, U8, F64; not FLAC)", format);
+    if (channels < 1 || channels > 8) return fail(WW_EINVAL, "channels %d: expected 1..8", channels);
+    int up = 1, down = 1, half_len = 0;
+    resample_taps_host(rate, nullptr, 0, &up, &down, &half_len);
+    const bool plain = up == 1 && down == 1;
+    const int64_t prod = int64_t(hop_in) * up;
+    const int64_t hop_out = prod / down;
+    if (hop_in < 1 || prod % down || hop_out < 4 || hop_out > n_samples || (hop_out & 3) || (n_samples % hop_out))
+        return fail(WW_EINVAL, "hop_frames %d at %d Hz: hop_frames * %d / %d must be a whole multiple of 4 that divides %d", hop_in, rate, up,
+                    down, n_samples);
+    StreamInput r{};
+    r.rate = rate; r.format = format; r.channels = channels; r.hop_in = hop_in; r.hop_out = int(hop_out);
+    r.up = up; r.down = down; r.lh = plain ? 0 : 2 * half_len + 1;
+    if (!plain) {
+        const int npp = down - half_len % down;
+        r.latency = (half_len + npp) / down - 1;
+        std::vector<int32_t> tab;
+        stream_table(r, tab);
+        r.hist = -tab[0] > 0 ? -tab[0] : 0;
+        // the largest block of consecutive outputs (a fixed count, the last block may be shorter) whose input frames fit the LDS span
+        auto span_of = [&](int b) {
+            int64_t w = 0;
+            for (int q0 = 0; q0 < r.hop_out; q0 += b) {
+                const int q1 = (q0 + b < r.hop_out ? q0 + b : r.hop_out) - 1;
+                const int64_t s = int64_t(tab[q1]) + tab[2 * r.hop_out + q1] - tab[q0];
+                w = s > w ? s : w;
+            }
+            return w;
+        };
+        int b = r.hop_out;
+        while (b > 1 && span_of(b) > kStreamSpan) b = b > 64 ? b - 64 : b - 1;
+        if (span_of(b) > kStreamSpan) return fail(WW_EINVAL, "sample_rate %d: one output's filter spans more than %d frames", rate, kStreamSpan);
+        r.block = b;
+        r.span = int(span_of(b));
+    }
+    *si = r;
+    return WW_OK;
+}
+
+int stream_input_alloc(StreamInput* si, int n_mics, hipStream_t stream) {
+    if (si->up == 1 && si->down == 1) return WW_OK;
+    ResampleFilter f;
+    if (int rc = get_filter(si->rate, &f)) return rc;
+    si->taps = f.taps_dev;
+    std::vector<int32_t> tab;
+    stream_table(*si, tab);
+    const size_t hist_bytes = sizeof(float) * 2 * size_t(n_mics) * size_t(si->hist > 0 ? si->hist : 1);
+    WW_HIP(hipMalloc(reinterpret_cast<void**>(&si->table), sizeof(int32_t) * tab.size()));
+    WW_HIP(hipMemcpy(si->table, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice));
+    WW_HIP(hipMalloc(reinterpret_cast<void**>(&si->history), hist_bytes));
+    WW_HIP(hipMemsetAsync(si->history, 0, hist_bytes, stream));
+    return WW_OK;
+}
+
+void stream_input_free(StreamInput* si) {
+    if (si->table) (void)hipFree(si->table);
+    if (si->history) (void)hipFree(si->history);
+    si->table = nullptr;
+    si->history = nullptr;
+}
+
+struct StreamArgs {
+    const uint8_t* hop;
+    const float* taps;
+    const int32_t* table;
+    float* history;
+    float* ring;
+    int32_t* pos;
+    int n_mics, ring_len, hop_in, hop_out, up, lh, latency, hist, block, channels, format, frame_bytes;
+};
+
+// One workgroup per microphone: it alone reads and writes that microphone's history, so the only cross-workgroup state is pos[], which
+// advances under ring_append_kernel's ticket protocol.  The history is ping-pong: this hop reads half pos[2] and writes the other.
+// Every output is resample_lds_kernel's fma chain -- from 0.f, ascending input frame, descending tap -- over the same frames (those before
+// the stream's first frame left out, as K0 leaves out those before a file's start) converted by the same sample_mono: bit for bit K0.
+template <bool kTapsInLds>
+__global__ __launch_bounds__(kStreamThreads) void stream_input_kernel(StreamArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float si_lds[];
+    const int tid = threadIdx.x;
+    const int pos = *reinterpret_cast<volatile int32_t*>(a.pos);
+    const int par = *reinterpret_cast<volatile int32_t*>(a.pos + 2);
+    const int k = *reinterpret_cast<volatile int32_t*>(a.pos + 3);
+    for (int m = blockIdx.x; m < a.n_mics; m += gridDim.x) {
+        const uint8_t* __restrict__ p = a.hop + int64_t(m) * a.hop_in * a.frame_bytes;
+        float* __restrict__ r = a.ring + int64_t(m) * a.ring_len;
+        if (a.lh == 0) {                                          // 16 kHz: K0 takes no filter, only the conversion
+            for (int q = tid; q < a.hop_out; q += kStreamThreads) {
+                int at = pos + q;
+                if (at >= a.ring_len) at -= a.ring_len;
+                r[at] = sample_mono(p, q, a.channels, a.format);
+            }
+            continue;
+        }
+        const float* __restrict__ h_old = a.history + (int64_t(par) * a.n_mics + m) * a.hist;
+        float* __restrict__ h_new = a.history + (int64_t(par ^ 1) * a.n_mics + m) * a.hist;
+        float* tapsL = si_lds;
+        float* xs = si_lds + (kTapsInLds ? a.lh : 0);
+        const float* __restrict__ taps = kTapsInLds ? tapsL : a.taps;
+        if (kTapsInLds) {
+            __syncthreads();                                      // (a previous microphone of this workgroup is done with the LDS)
+            for (int i = tid; i < a.lh; i += kStreamThreads) tapsL[i] = a.taps[i];
+        }
+        const int64_t base = int64_t(k) * a.hop_in;               // the hop's first frame in the stream (saturated: past the history)
+        const int64_t j0 = int64_t(k) * a.hop_out - a.latency;    // its first output
+        const int32_t* __restrict__ t_off = a.table;
+        const int32_t* __restrict__ t_tap = a.table + a.hop_out;
+        const int32_t* __restrict__ t_cnt = a.table + 2 * a.hop_out;
+        for (int q0 = 0; q0 < a.hop_out; q0 += a.block) {
+            const int q1 = q0 + a.block < a.hop_out ? q0 + a.block : a.hop_out;
+            const int s_lo = t_off[q0], s_hi = t_off[q1 - 1] + t_cnt[q1 - 1];   // frames [s_lo, s_hi) relative to the hop
+            __syncthreads();
+            for (int i = s_lo + tid; i < s_hi; i += kStreamThreads)
+                xs[i - s_lo] = i < 0 ? h_old[a.hist + i] : sample_mono(p, i, a.channels, a.format);
+            __syncthreads();
+            for (int q = q0 + tid; q < q1; q += kStreamThreads) {
+                float y = 0.f;
+                if (j0 + q >= 0) {                                // negative j: the window's left zero padding
+                    int i = t_off[q], t = t_tap[q], n = t_cnt[q];
+                    if (base + i < 0) {                           // frames before the stream's first: not in the sum (K0's i_lo >= 0)
+                        const int skip = int(-(base + i));
+                        i += skip; t -= skip * a.up; n -= skip;
+                    }
+                    const float* __restrict__ x = xs + (i - s_lo);
+#pragma unroll 8
+                    for (int u = 0; u < n; ++u, t -= a.up) y = fmaf(x[u], taps[t], y);
+                }
+                int at = pos + q;
+                if (at >= a.ring_len) at -= a.ring_len;
+                r[at] = y;
+            }
+        }
+        // the next hop's history: the last `hist` frames of (history, hop), from the other half
+        for (int q = tid; q < a.hist; q += kStreamThreads) {
+            const int i = a.hop_in - a.hist + q;
+            h_new[q] = i < 0 ? h_old[a.hist + i] : sample_mono(p, i, a.channels, a.format);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        __threadfence();
+        if (atomicInc(reinterpret_cast<uint32_t*>(a.pos + 1), gridDim.x - 1) == gridDim.x - 1) {   // the last workgroup: all have read pos
+            const int np = pos + a.hop_out;
+            a.pos[0] = np >= a.ring_len ? np - a.ring_len : np;
+            a.pos[2] = par ^ 1;
+            a.pos[3] = k < kStreamHopsCap ? k + 1 : k;
+        }
+    }
+}
+
+int launch_stream_input(const StreamInput& si, const void* hop, int n_mics, float* ring, int32_t* pos, int ring_len, hipStream_t stream) {
+    StreamArgs a{static_cast<const uint8_t*>(hop), si.taps, si.table, si.history, ring, pos, n_mics, ring_len, si.hop_in, si.hop_out, si.up,
+                 si.lh, si.latency, si.hist, si.block, si.channels, si.format, si.channels * sample_bytes(si.format)};
+    // every microphone reads every tap once or more per hop: in LDS whenever they fit beside the hop's frames (a hop's span is far
+    // shorter than K0's 7,168-frame blocks, so the 11.025 kHz filter's 12,801 taps fit here; K0 reads them from global memory)
+    const int grid = n_mics;
+    if (si.lh > 0 && si.lh + si.span <= kStreamLds) {
+        hipLaunchKernelGGL(stream_input_kernel<true>, dim3(grid), dim3(kStreamThreads), (si.lh + si.span) * sizeof(float), stream, a);
+    } else {
+        hipLaunchKernelGGL(stream_input_kernel<false>, dim3(grid), dim3(kStreamThreads), si.span * sizeof(float), stream, a);
+    }
+    WW_HIP(hipGetLastError());
+    return WW_OK;
+}
+
 }  // namespace ww
 
 using namespace ww;

@@ -264,6 +264,30 @@ __attribute__((visibility("default"))) int launch_flac_decode(uint8_t* raw_dev, 
                        hipStream_t stream);
 int flac_errors(unsigned int* count);
 
+// ---------------------------------------------------------------------------------------------
+// streaming at the microphone's rate, format and channel count (ww_decode.hip, beside K0 whose filter and conversion it shares)
+// ---------------------------------------------------------------------------------------------
+struct StreamInput {
+    int rate, format, channels, hop_in, hop_out;
+    int up, down, lh;         // K0's filter for `rate` (up == down == 1 at 16 kHz: no filter)
+    int latency;              // D: the window lags the input by D samples at 16 kHz
+    int hist;                 // P: mono frames before a hop that its outputs still read (kept per mic between hops)
+    int block;                // outputs per LDS block (their input span fits kStreamSpan frames)
+    int span;                 // the longest such span: LDS frames per workgroup
+    const float* taps;        // device, K0's cached filter (not owned)
+    int32_t* table;           // device [3][hop_out]: first input frame relative to the hop, first tap, tap count
+    float* history;           // device [2][n_mics][hist]: ping-pong by the parity the kernel keeps in pos[2]
+};
+// Host only, no HIP call: checks rate, format, channels and hop (WW_EINVAL naming the field) and fills the scalar fields.
+int stream_input_check(int rate, int format, int channels, int hop_in, int n_samples, StreamInput* si);
+// Allocates the table and the zeroed history on `stream` (after stream_input_check).
+int stream_input_alloc(StreamInput* si, int n_mics, hipStream_t stream);
+void stream_input_free(StreamInput* si);
+// One hop: converts and resamples hop [n_mics][hop_in][channels] into the ring and advances pos (the ring_append_kernel protocol:
+// pos[0] ring position, pos[1] ticket; plus pos[2] history parity and pos[3] hops so far, saturating).
+int launch_stream_input(const StreamInput& si, const void* hop, int n_mics, float* ring, int32_t* pos, int ring_len, hipStream_t stream);
+int sample_bytes(int format);   // bytes per sample of a WW_FMT_* PCM format (0 for FLAC and unknown)
+
 int require_gfx950();
 int device_cu_count();   // CUs of the current device (256 on MI355X); cached
 

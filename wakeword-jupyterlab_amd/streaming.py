@@ -7,19 +7,30 @@ lengths the model trains at).  Per hop this keeps an N-sample ring per microphon
 (frames cannot be reused across 10 ms hops: the 512-sample STFT grid realigns only every 2560 samples and
 `ref=np.max` is per window -- SURVEY.md section 7) and replays one captured hipGraph:
 ring append -> K1 -> K2 -> K3 (+softmax).
+
+Hops may also come at the microphone's own rate, sample format and channel count (`sample_rate`, `dtype`, `channels`): the graph's first
+node then converts, mixes to mono and resamples the hop to 16 kHz with K0's filter (bit for bit what the file path computes for a
+recording of the same frames), `latency_samples` 16 kHz samples behind the input.
 """
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 
 import torch
 
 from . import _native as nat
 from .config import CLIP_SAMPLES, N_FRAMES
 
+# hop dtypes and the K0 sample format each is read as
+_FORMATS = {torch.float32: nat.FMT_F32, torch.int16: nat.FMT_S16}
+
 
 class StreamingDetector:
-    def __init__(self, model, n_mics: int = 256, hop_samples: int = 160, threshold: float = 0.8, device=None):
+    def __init__(self, model, n_mics: int = 256, hop_samples: int = 160, threshold: float = 0.8, device=None, *,
+                 sample_rate: int = 16000, channels: int = 1, dtype: torch.dtype = torch.float32):
+        """hop_samples counts input frames at `sample_rate`; `dtype` (float32, or int16 read as PCM-16) and `channels` (1 .. 8,
+        interleaved) are the hop's.  The window, `prob`, `logits` and `detections()` are at 16 kHz whatever the input."""
         if model.training:
             raise NotImplementedError("call model.eval() first")
         n = int(getattr(model, "_n_samples", CLIP_SAMPLES))
@@ -27,6 +38,8 @@ class StreamingDetector:
             raise NotImplementedError(f"streaming runs windows of 0.25 .. 1 s (at most {N_FRAMES} frames); this model is built for clips "
                                       f"of {n} samples")
         self.window_samples = n                        # N: the window every hop is scored on
+        self.sample_rate, self.channels, self.dtype = self._check_input(n, int(hop_samples), sample_rate, channels, dtype)
+        self._input = (self.sample_rate, self.dtype, self.channels) != (16000, torch.float32, 1)
         self.device = torch.device(device) if device is not None else model.fc.weight.device
         if self.device.type != "cuda":
             raise RuntimeError("StreamingDetector needs the model on the MI355X (no CPU path)")
@@ -34,22 +47,57 @@ class StreamingDetector:
         self._packed = model.packed_weights()          # keep alive: the graph holds its pointer
         self._n_conv = model._n_conv
         self._stream = torch.cuda.Stream(device=self.device)
-        self.hop_buf = torch.zeros((self.n_mics, self.hop), device=self.device, dtype=torch.float32)
+        shape = (self.n_mics, self.hop) if self.channels == 1 else (self.n_mics, self.hop, self.channels)
+        self.hop_buf = torch.zeros(shape, device=self.device, dtype=self.dtype)
         self.prob = torch.zeros(self.n_mics, device=self.device, dtype=torch.float32)
         self.logits = torch.zeros((self.n_mics, 2), device=self.device, dtype=torch.float32)
         handle = C.c_void_p()
         with torch.cuda.device(self.device):
-            nat.check(nat.lib.ww_streamer_create_n(self.n_mics, self.hop, self.window_samples, C.c_void_p(self._packed.data_ptr()),
-                                                   self._n_conv, C.c_void_p(self._stream.cuda_stream), C.byref(handle)))
+            if self._input:
+                nat.check(nat.lib.ww_streamer_create_input(self.n_mics, self.hop, self.sample_rate, _FORMATS[self.dtype], self.channels,
+                                                           self.window_samples, C.c_void_p(self._packed.data_ptr()), self._n_conv,
+                                                           C.c_void_p(self._stream.cuda_stream), C.byref(handle)))
+            else:
+                nat.check(nat.lib.ww_streamer_create_n(self.n_mics, self.hop, self.window_samples, C.c_void_p(self._packed.data_ptr()),
+                                                       self._n_conv, C.c_void_p(self._stream.cuda_stream), C.byref(handle)))
         self._h = handle
+        self.latency_samples = int(nat.lib.ww_streamer_latency(handle))   # D: the window lags the input by D samples at 16 kHz
+
+    @staticmethod
+    def _check_input(n, hop, sample_rate, channels, dtype):
+        """The input format, checked without a device: (sample_rate, channels, dtype) or TypeError / ValueError."""
+        if dtype not in _FORMATS:
+            raise TypeError(f"dtype {dtype}: hops are torch.float32 or torch.int16")
+        for name, v in (("sample_rate", sample_rate), ("channels", channels)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                raise TypeError(f"{name} must be an integer, got {type(v).__name__}")
+        sample_rate, channels = int(sample_rate), int(channels)
+        if not 1000 <= sample_rate <= 384000:
+            raise ValueError(f"sample_rate {sample_rate}: expected 1000 .. 384000 Hz")
+        if not 1 <= channels <= 8:
+            raise ValueError(f"channels {channels}: expected 1 .. 8")
+        if (sample_rate, dtype, channels) != (16000, torch.float32, 1):
+            # the library's rule (ww_streamer_create_input), checked here so that a bad hop never reaches a device
+            up, down = C.c_int32(), C.c_int32()
+            nat.lib.ww_resample_taps_host(sample_rate, None, 0, C.byref(up), C.byref(down), None)
+            out = hop * up.value // down.value
+            if hop < 1 or hop * up.value % down.value or out < 4 or out % 4 or out > n or n % out:
+                raise ValueError(f"hop_samples {hop} at {sample_rate} Hz: hop_samples * {up.value} / {down.value} samples at 16 kHz must "
+                                 f"be a whole multiple of 4 that divides the window of {n}")
+        return sample_rate, channels, dtype
 
     @property
     def stream(self) -> torch.cuda.Stream:
         return self._stream
 
     def step(self, hop: torch.Tensor | None = None) -> torch.Tensor:
-        """Push one hop [n_mics, hop_samples] (or reuse whatever is in `hop_buf`) and enqueue the graph.
-        Returns `self.prob` (softmax p(wakeword) per mic), valid once `self.stream` has caught up."""
+        """Push one hop [n_mics, hop_samples] (or [n_mics, hop_samples, channels]; or reuse whatever is in `hop_buf`) and enqueue the
+        graph.  Returns `self.prob` (softmax p(wakeword) per mic), valid once `self.stream` has caught up."""
+        if hop is not None and self._input:
+            if hop.dtype != self.dtype:
+                raise TypeError(f"hop dtype {hop.dtype}: this detector takes {self.dtype}")
+            if tuple(hop.shape) != tuple(self.hop_buf.shape):
+                raise ValueError(f"hop shape {tuple(hop.shape)}: expected {tuple(self.hop_buf.shape)}")
         if hop is not None:
             if hop.device.type == "cuda":
                 # `hop` was produced on the caller's stream: order our stream behind it before reading it
@@ -58,8 +106,12 @@ class StreamingDetector:
             with torch.cuda.stream(self._stream):
                 self.hop_buf.copy_(hop, non_blocking=True)
         with torch.cuda.device(self.device):
-            nat.check(nat.lib.ww_streamer_step(self._h, C.c_void_p(self.hop_buf.data_ptr()), C.c_void_p(self.prob.data_ptr()),
-                                               C.c_void_p(self.logits.data_ptr())))
+            if self._input:
+                nat.check(nat.lib.ww_streamer_step_input(self._h, C.c_void_p(self.hop_buf.data_ptr()), C.c_void_p(self.prob.data_ptr()),
+                                                         C.c_void_p(self.logits.data_ptr())))
+            else:
+                nat.check(nat.lib.ww_streamer_step(self._h, C.c_void_p(self.hop_buf.data_ptr()), C.c_void_p(self.prob.data_ptr()),
+                                                   C.c_void_p(self.logits.data_ptr())))
         return self.prob
 
     def detections(self) -> torch.Tensor:
