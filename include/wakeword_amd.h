@@ -452,6 +452,34 @@ WW_API int ww_forward_pcm_frames_f32(const float* pcm_dev, int64_t n_clips, int6
                                      int normalize, const float* packed_dev, int32_t n_conv, void* workspace_dev, float* logits_dev,
                                      ww_stream_t stream);
 
+/* ---- long recordings: overlapping windows, events, thresholds ------------ */
+/* Logits (and, if prob_dev is not NULL, softmax p(wakeword) as the streamer writes it) of n_windows windows of n_samples samples
+ * (16000, or WW_MIN_CLIP_SAMPLES..WW_MAX_CLIP_SAMPLES) read in place from one signal: window k is the row at signal_dev + k * hop.
+ * Rows may overlap: 4 <= hop <= n_samples, hop % 4 == 0, signal_dev 16-byte aligned, and the caller's buffer holds
+ * (n_windows - 1) * hop + n_samples samples.  Nothing on the way writes the signal.  Bit for bit ww_forward_pcm_f32 (N = 16000) /
+ * ww_forward_pcm_frames_f32 (other N) of the same windows copied out as rows.  workspace_dev: ww_forward_windows_workspace_bytes()
+ * bytes, 256-byte aligned; workspace_bytes is its size. */
+WW_API int64_t ww_forward_windows_workspace_bytes(int64_t n_windows, int64_t n_samples, int32_t n_conv);
+WW_API int ww_forward_windows_f32(const float* signal_dev, int64_t n_windows, int64_t hop, int64_t n_samples, int normalize,
+                                  const float* packed_dev, int32_t n_conv, void* workspace_dev, int64_t workspace_bytes, float* logits_dev,
+                                  float* prob_dev, ww_stream_t stream);
+/* Event counts of n_segs recordings at n_thr thresholds.  prob_dev [n_windows] float32 per-window scores, segment g being windows
+ * seg_offsets_dev[g] .. seg_offsets_dev[g + 1] - 1 (int64, non-decreasing, seg_offsets_dev[0] = 0, n_windows = seg_offsets_dev[n_segs];
+ * the host reads nothing of it, the caller passes n_windows).  q = p where finite, else 0; s_k = the float64 mean of the segment's last
+ * min(k, smooth) q values summed in ascending order (1 <= smooth <= 256); window k fires iff s_k >= (double)theta and no window of the
+ * segment fired in the refractory windows before it (0 <= refractory <= 2^30).  counts_dev [n_segs][n_thr] int64; fired_dev (may be
+ * NULL; only with n_thr == 1) [n_windows] uint8 0/1.  thresholds_dev [n_thr] float32, 1 <= n_thr <= 65536.
+ * workspace_dev: ww_events_workspace_bytes(n_windows) bytes, 16-byte aligned. */
+WW_API int64_t ww_events_workspace_bytes(int64_t n_windows);
+WW_API int ww_events_sweep_f32(const float* prob_dev, const int64_t* seg_offsets_dev, int64_t n_segs, int64_t n_windows, int32_t smooth,
+                               int64_t refractory, const float* thresholds_dev, int32_t n_thr, int64_t* counts_dev, uint8_t* fired_dev,
+                               void* workspace_dev, int64_t workspace_bytes, ww_stream_t stream);
+/* The same rule one hop at a time for n_mics streams (StreamingDetector): state_dev of ww_events_state_bytes(n_mics, smooth) bytes,
+ * 16-byte aligned, zeroed before the first hop; each call appends prob_dev [n_mics] and writes fired_dev [n_mics] uint8 0/1. */
+WW_API int64_t ww_events_state_bytes(int32_t n_mics, int32_t smooth);
+WW_API int ww_events_step_f32(const float* prob_dev, int32_t n_mics, int32_t smooth, float threshold, int64_t refractory, void* state_dev,
+                              uint8_t* fired_dev, ww_stream_t stream);
+
 /* ---- training step ----------------------------------------------------- */
 /* Replaces, for one batch, `output = model(data)` in train mode and `loss.backward()` of the reference's training loops
  * (wakeword_training/train_wakeword.py:109-115; WakewordTrainer.train_epoch, wakeword_training_script.py:241-267) for

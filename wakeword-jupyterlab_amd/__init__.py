@@ -15,13 +15,14 @@ from . import config, synth  # noqa: F401  (no native dependency)
 def __getattr__(name):
     # lazy: `import wakeword_jupyterlab_amd` must work on a box where only host utilities are needed
     import importlib
-    if name in ("ops", "model", "audio", "dataset", "streaming", "inference", "distributed", "_native", "background", "reverb"):
+    if name in ("ops", "model", "audio", "dataset", "streaming", "inference", "distributed", "_native", "background", "reverb",
+                "scan"):
         return importlib.import_module(f"{__name__}.{name}")
     lazy = {"AudioProcessor": "audio", "WakewordDataset": "dataset", "DataLoader": "dataset", "SimpleWakewordModel": "model",
             "WakewordModel": "model", "StreamingDetector": "streaming", "predict_wakeword": "inference",
             "evaluate": "inference", "AudioConfig": "config", "ModelConfig": "config", "Config": "config",
             "AugmentationConfig": "config", "BackgroundNoiseBank": "background",
-            "ImpulseResponseBank": "reverb"}
+            "ImpulseResponseBank": "reverb", "scan_files": "scan", "det_curve": "scan", "Scan": "scan"}
     if name in lazy:
         return getattr(importlib.import_module(f"{__name__}.{lazy[name]}"), name)
     raise AttributeError(name)

@@ -176,6 +176,14 @@ PROTOTYPES = {
     "ww_workspace_frames_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
     "ww_forward_pcm_frames_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int32, C.c_void_p,
                                             C.c_void_p, C.c_void_p]),
+    "ww_forward_windows_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    "ww_forward_windows_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_events_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "ww_events_sweep_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ww_events_state_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "ww_events_step_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_train_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "ww_train_forward_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(TrainParams), C.c_float, C.c_float, C.c_uint64, C.c_int32,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

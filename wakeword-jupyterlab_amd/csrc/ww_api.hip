@@ -708,6 +708,101 @@ int ww_forward_pcm_frames_f32(const float* pcm_dev, int64_t n_clips, int64_t cli
     return launch_lstm_fc(pooled, n_clips, packed_dev, n_conv, logits_dev, nullptr, st);
 }
 
+// ---- long recordings: overlapping windows of one signal, and events over their scores ----
+// The log-mel kernels (logmel_kernel, logmel64_kernel in all three arithmetics) only read the input, each clip through a buffer
+// descriptor of its own at pcm + c * clip_stride; every write goes to the workspace, indexed by clip.  So rows may overlap here, and
+// the chain is the one ww_forward_pcm_frames_f32 runs (at N = 16000 the 1 s kernels, as ww_forward_pcm_f32 does).
+static int64_t windows_workspace_bytes(int64_t n, int64_t n_samples, int32_t n_conv) {
+    const int T = int(1 + n_samples / kHop);
+    return align256(n * kMels * T * int64_t(sizeof(float))) + align256(n * 128 * int64_t(sizeof(float))) +
+           align256(wide_scratch_bytes(n, T, n_conv));
+}
+
+int64_t ww_forward_windows_workspace_bytes(int64_t n_windows, int64_t n_samples, int32_t n_conv) {
+    if (n_windows < 0 || n_windows > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_windows %lld out of range", (long long)n_windows);
+    if (n_conv != 2 && n_conv != 3) return fail(WW_EINVAL, "n_conv must be 2 or 3, got %d", n_conv);
+    if (n_samples != kClip && (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_MAX_CLIP_SAMPLES))
+        return fail(WW_EINVAL, "n_samples %lld: expected %d..%d", (long long)n_samples, WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES);
+    return windows_workspace_bytes(n_windows, n_samples, n_conv);
+}
+
+int ww_forward_windows_f32(const float* signal_dev, int64_t n_windows, int64_t hop, int64_t n_samples, int normalize,
+                           const float* packed_dev, int32_t n_conv, void* workspace_dev, int64_t workspace_bytes, float* logits_dev,
+                           float* prob_dev, ww_stream_t stream) {
+    if (n_windows < 0 || n_windows > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_windows %lld: expected 0..%d", (long long)n_windows, 1 << 24);
+    if (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_MAX_CLIP_SAMPLES)
+        return fail(WW_EINVAL, "n_samples %lld: expected %d..%d (0.25 s .. 2 s at 16 kHz)", (long long)n_samples, WW_MIN_CLIP_SAMPLES,
+                    WW_MAX_CLIP_SAMPLES);
+    if (hop < 4 || hop > n_samples || (hop & 3))
+        return fail(WW_EINVAL, "hop %lld: expected a multiple of 4 in 4..n_samples (%lld)", (long long)hop, (long long)n_samples);
+    if (n_conv != 2 && n_conv != 3) return fail(WW_EINVAL, "n_conv must be 2 or 3, got %d", n_conv);
+    if (n_windows == 0) return WW_OK;
+    if (!signal_dev || (reinterpret_cast<uintptr_t>(signal_dev) & 15)) return fail(WW_EINVAL, "signal_dev must be a 16-byte aligned device pointer");
+    if (!packed_dev || (reinterpret_cast<uintptr_t>(packed_dev) & 15)) return fail(WW_EINVAL, "packed_dev must be a 16-byte aligned device pointer");
+    if (!logits_dev) return fail(WW_EINVAL, "logits_dev is null");
+    if (!workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 255)) return fail(WW_EINVAL, "workspace_dev must be 256-byte aligned");
+    const int64_t need = windows_workspace_bytes(n_windows, n_samples, n_conv);
+    if (workspace_bytes < need)
+        return fail(WW_EINVAL, "workspace_bytes %lld < %lld needed", (long long)workspace_bytes, (long long)need);
+    if (int rc = require_gfx950()) return rc;
+    const int T = int(1 + n_samples / kHop);
+    char* p = static_cast<char*>(workspace_dev);
+    float* logmel = reinterpret_cast<float*>(p);
+    p += align256(n_windows * kMels * T * int64_t(sizeof(float)));
+    float* pooled = reinterpret_cast<float*>(p);
+    p += align256(n_windows * 128 * int64_t(sizeof(float)));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = launch_logmel_frames(signal_dev, n_windows, hop, n_samples, n_samples, normalize, logmel, st)) return rc;
+    if (int rc = cnn_pool_any(logmel, n_windows, T, packed_dev, n_conv, p, pooled, st)) return rc;
+    return launch_lstm_fc(pooled, n_windows, packed_dev, n_conv, logits_dev, prob_dev, st);
+}
+
+int64_t ww_events_workspace_bytes(int64_t n_windows) {
+    if (n_windows < 0 || n_windows > (int64_t(1) << 40)) return fail(WW_EINVAL, "n_windows %lld out of range", (long long)n_windows);
+    return align256(n_windows * int64_t(sizeof(double)));
+}
+
+int ww_events_sweep_f32(const float* prob_dev, const int64_t* seg_offsets_dev, int64_t n_segs, int64_t n_windows, int32_t smooth,
+                        int64_t refractory, const float* thresholds_dev, int32_t n_thr, int64_t* counts_dev, uint8_t* fired_dev,
+                        void* workspace_dev, int64_t workspace_bytes, ww_stream_t stream) {
+    if (n_segs < 0 || n_segs > (int64_t(1) << 30)) return fail(WW_EINVAL, "n_segs %lld out of range", (long long)n_segs);
+    if (n_windows < 0 || n_windows > (int64_t(1) << 40)) return fail(WW_EINVAL, "n_windows %lld out of range", (long long)n_windows);
+    if (smooth < 1 || smooth > 256) return fail(WW_EINVAL, "smooth %d: expected 1..256 windows", smooth);
+    if (refractory < 0 || refractory > (int64_t(1) << 30)) return fail(WW_EINVAL, "refractory %lld: expected 0..2^30 windows", (long long)refractory);
+    if (n_thr < 1 || n_thr > 65536) return fail(WW_EINVAL, "n_thr %d: expected 1..65536 thresholds", n_thr);
+    if (fired_dev && n_thr != 1) return fail(WW_EINVAL, "fired_dev: per-window flags need exactly one threshold (n_thr %d)", n_thr);
+    if (n_segs == 0) return WW_OK;
+    if (!seg_offsets_dev || (reinterpret_cast<uintptr_t>(seg_offsets_dev) & 7)) return fail(WW_EINVAL, "seg_offsets_dev must be an 8-byte aligned device pointer");
+    if (!thresholds_dev || (reinterpret_cast<uintptr_t>(thresholds_dev) & 3)) return fail(WW_EINVAL, "thresholds_dev must be a 4-byte aligned device pointer");
+    if (!counts_dev || (reinterpret_cast<uintptr_t>(counts_dev) & 7)) return fail(WW_EINVAL, "counts_dev must be an 8-byte aligned device pointer");
+    if (n_windows > 0 && !prob_dev) return fail(WW_EINVAL, "prob_dev is null");
+    if (!workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 15)) return fail(WW_EINVAL, "workspace_dev must be 16-byte aligned");
+    if (workspace_bytes < n_windows * int64_t(sizeof(double)))
+        return fail(WW_EINVAL, "workspace_bytes %lld < %lld needed", (long long)workspace_bytes, (long long)(n_windows * int64_t(sizeof(double))));
+    if (int rc = require_gfx950()) return rc;
+    return launch_events_sweep(prob_dev, seg_offsets_dev, int(n_segs), n_windows, smooth, refractory, thresholds_dev, n_thr, counts_dev,
+                               fired_dev, static_cast<double*>(workspace_dev), static_cast<hipStream_t>(stream));
+}
+
+int64_t ww_events_state_bytes(int32_t n_mics, int32_t smooth) {
+    if (n_mics < 1 || n_mics > (1 << 20)) return fail(WW_EINVAL, "n_mics %d out of range", n_mics);
+    if (smooth < 1 || smooth > 256) return fail(WW_EINVAL, "smooth %d: expected 1..256 windows", smooth);
+    return 16 * int64_t(n_mics) + align256(int64_t(n_mics) * smooth * int64_t(sizeof(float)));
+}
+
+int ww_events_step_f32(const float* prob_dev, int32_t n_mics, int32_t smooth, float threshold, int64_t refractory, void* state_dev,
+                       uint8_t* fired_dev, ww_stream_t stream) {
+    if (n_mics < 1 || n_mics > (1 << 20)) return fail(WW_EINVAL, "n_mics %d out of range", n_mics);
+    if (smooth < 1 || smooth > 256) return fail(WW_EINVAL, "smooth %d: expected 1..256 windows", smooth);
+    if (refractory < 0 || refractory > (int64_t(1) << 30)) return fail(WW_EINVAL, "refractory %lld: expected 0..2^30 windows", (long long)refractory);
+    if (!(threshold > 0.f && threshold <= 1.f)) return fail(WW_EINVAL, "threshold %g: expected 0 < threshold <= 1", double(threshold));
+    if (!prob_dev || (reinterpret_cast<uintptr_t>(prob_dev) & 3)) return fail(WW_EINVAL, "prob_dev must be a 4-byte aligned device pointer");
+    if (!state_dev || (reinterpret_cast<uintptr_t>(state_dev) & 15)) return fail(WW_EINVAL, "state_dev must be a 16-byte aligned device pointer");
+    if (!fired_dev) return fail(WW_EINVAL, "fired_dev is null");
+    if (int rc = require_gfx950()) return rc;
+    return launch_events_step(prob_dev, n_mics, smooth, threshold, refractory, state_dev, fired_dev, static_cast<hipStream_t>(stream));
+}
+
 static int check_train(const float* mel, int64_t n, int32_t width, const ww_train_params* p, const void* ws) {
     if (n < 1 || n > (int64_t(1) << 24)) return fail(WW_EINVAL, "training batch %lld out of range", (long long)n);
     if (width < 1 || width > WW_MAX_WIDTH) return fail(WW_EUNSUPPORTED, "mel width %d: the conv kernels take 1..%d frames", width, WW_MAX_WIDTH);

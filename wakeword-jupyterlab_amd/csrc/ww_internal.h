@@ -120,6 +120,12 @@ int launch_logmel_frames(const float* pcm, int64_t n_clips, int64_t clip_stride,
 // the same over streaming rings of ring_len = clip_len = n_samples samples per row (a multiple of 4), window start *ring_pos (device)
 int launch_logmel_frames(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples, int normalize,
                          const int32_t* ring_pos, int64_t ring_len, float* logmel, hipStream_t stream);
+// events on continuous audio (ww_events.hip): smooth per segment into s_work [n_windows] float64, then count events per (segment,
+// threshold) into counts [n_segs][n_thr] (and, with n_thr == 1, one fired byte per window); the per-hop form for the streamer
+int launch_events_sweep(const float* prob, const int64_t* offsets, int n_segs, int64_t n_windows, int smooth, int64_t refractory,
+                        const float* thresholds, int n_thr, int64_t* counts, uint8_t* fired, double* s_work, hipStream_t stream);
+int launch_events_step(const float* prob, int n_mics, int smooth, float threshold, int64_t refractory, void* state, uint8_t* fired,
+                       hipStream_t stream);
 // log-mel arithmetic: 0 = f32 FFT, 1 = f64 FFT (what the reference's numpy.fft.rfft is), 2 = auto (f32, then the clips whose
 // quiet bands sit on the f32 FFT's rounding floor are redone in f64)
 int logmel_math_mode();

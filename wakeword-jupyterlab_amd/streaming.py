@@ -28,9 +28,13 @@ _FORMATS = {torch.float32: nat.FMT_F32, torch.int16: nat.FMT_S16}
 
 class StreamingDetector:
     def __init__(self, model, n_mics: int = 256, hop_samples: int = 160, threshold: float = 0.8, device=None, *,
-                 sample_rate: int = 16000, channels: int = 1, dtype: torch.dtype = torch.float32):
+                 sample_rate: int = 16000, channels: int = 1, dtype: torch.dtype = torch.float32, smooth=None, refractory_s=None):
         """hop_samples counts input frames at `sample_rate`; `dtype` (float32, or int16 read as PCM-16) and `channels` (1 .. 8,
-        interleaved) are the hop's.  The window, `prob`, `logits` and `detections()` are at 16 kHz whatever the input."""
+        interleaved) are the hop's.  The window, `prob`, `logits` and `detections()` are at 16 kHz whatever the input.
+        `smooth` (windows, 1 .. 256) / `refractory_s` (seconds): with either set (the other then defaults to 1 window / 1.0 s, as in
+        scan.Scan.events), every step also runs the event rule of INTEGRATION.md section 3f per microphone -- the mean of the last
+        `smooth` probabilities (NaN counting as 0) against `threshold`, at most one event per refractory period -- and detections()
+        returns its flags.  With both None, detections() is `prob >= threshold`."""
         if model.training:
             raise NotImplementedError("call model.eval() first")
         n = int(getattr(model, "_n_samples", CLIP_SAMPLES))
@@ -39,6 +43,14 @@ class StreamingDetector:
                                       f"of {n} samples")
         self.window_samples = n                        # N: the window every hop is scored on
         self.sample_rate, self.channels, self.dtype = self._check_input(n, int(hop_samples), sample_rate, channels, dtype)
+        self._events = smooth is not None or refractory_s is not None
+        if self._events:
+            from .scan import _check_smooth, refractory_windows
+            self.smooth = _check_smooth(1 if smooth is None else smooth)
+            self.refractory_s = 1.0 if refractory_s is None else refractory_s
+            if not 0.0 < float(threshold) <= 1.0:
+                raise ValueError(f"threshold {threshold!r}: events need 0 < threshold <= 1")
+            self._refractory = refractory_windows(self.refractory_s, self._hop16(int(hop_samples), sample_rate))
         self._input = (self.sample_rate, self.dtype, self.channels) != (16000, torch.float32, 1)
         self.device = torch.device(device) if device is not None else model.fc.weight.device
         if self.device.type != "cuda":
@@ -61,7 +73,21 @@ class StreamingDetector:
                 nat.check(nat.lib.ww_streamer_create_n(self.n_mics, self.hop, self.window_samples, C.c_void_p(self._packed.data_ptr()),
                                                        self._n_conv, C.c_void_p(self._stream.cuda_stream), C.byref(handle)))
         self._h = handle
+        if self._events:
+            self._ev_state = torch.zeros(nat.check(nat.lib.ww_events_state_bytes(self.n_mics, self.smooth)), device=self.device,
+                                         dtype=torch.uint8)
+            self._fired = torch.zeros(self.n_mics, device=self.device, dtype=torch.bool)
+            self._stream.wait_stream(torch.cuda.current_stream(self.device))      # the zeroed state before the first step
         self.latency_samples = int(nat.lib.ww_streamer_latency(handle))   # D: the window lags the input by D samples at 16 kHz
+
+    @staticmethod
+    def _hop16(hop, sample_rate):
+        """The hop in 16 kHz samples: one window per hop."""
+        if int(sample_rate) == 16000:
+            return max(1, hop)
+        up, down = C.c_int32(), C.c_int32()
+        nat.lib.ww_resample_taps_host(int(sample_rate), None, 0, C.byref(up), C.byref(down), None)
+        return max(1, hop * up.value // down.value)
 
     @staticmethod
     def _check_input(n, hop, sample_rate, channels, dtype):
@@ -112,10 +138,17 @@ class StreamingDetector:
             else:
                 nat.check(nat.lib.ww_streamer_step(self._h, C.c_void_p(self.hop_buf.data_ptr()), C.c_void_p(self.prob.data_ptr()),
                                                    C.c_void_p(self.logits.data_ptr())))
+            if self._events:
+                # its own launch on the detector's stream, after the graph replay (the captured graph is unchanged)
+                nat.check(nat.lib.ww_events_step_f32(C.c_void_p(self.prob.data_ptr()), self.n_mics, self.smooth, C.c_float(self.threshold),
+                                                     self._refractory, C.c_void_p(self._ev_state.data_ptr()),
+                                                     C.c_void_p(self._fired.data_ptr()), C.c_void_p(self._stream.cuda_stream)))
         return self.prob
 
     def detections(self) -> torch.Tensor:
         self._stream.synchronize()
+        if self._events:
+            return self._fired.clone()
         return self.prob >= self.threshold
 
     def window(self) -> torch.Tensor:
