@@ -273,6 +273,21 @@ WW_API int ww_augment_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_
 WW_API int ww_augment_plans_prepare_n(const ww_augment_plan* plans_host, int64_t n_clips, int64_t n_samples, void* records_host);
 WW_API int ww_augment_records_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* records_dev,
                                     float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream);
+/* Diagnostic: where the calls above leave their intermediates in workspace_dev, for n_clips clips of n_samples (16000 or the *_n range).
+ * Byte offsets from workspace_dev and byte strides; the library sizes the workspace and places its buffers from this same function.
+ *   records  [n_clips] per-clip records of record_bytes (ww_augment_record_bytes())
+ *   buf_a    [n_clips] rows of row_bytes: the rolled input (rows padded with zeros to four floats)
+ *   buf_b    [n_clips] rows of row_bytes: the resampled clips after a batch with pitch only, the cropped / zero-padded inverse STFT
+ *            after a batch with stretch only (a batch with both: buf_a holds the stretch's output, buf_b its input)
+ *   spec     [n_clips][46][1025] complex float32: the phase vocoder's output columns of the LAST vocoder pass that ran
+ *   y        [n_clips] rows of y_clip_bytes: the pitch pass's inverse STFT, its first round(N / pitch_rate) samples
+ * Nothing else is promised about the workspace's contents. */
+typedef struct ww_augment_layout {
+    int64_t records, buf_a, buf_b, spec, y;                       /* offsets */
+    int64_t record_bytes, row_bytes, spec_clip_bytes, spec_step_bytes, y_clip_bytes;   /* strides */
+    int64_t total_bytes;                                          /* = ww_augment_n_workspace_bytes(n_clips, n_samples) */
+} ww_augment_layout;
+WW_API int ww_augment_workspace_layout(int64_t n_clips, int64_t n_samples, ww_augment_layout* layout_out);
 /* Background noise at a random SNR, mixed in after time_stretch + crop and before the Gaussian noise (additions only; no existing call,
  * struct or record changes).  The bank is one float32 device buffer of bank_len samples holding every noise file back to back.  Per clip:
  *   seg[j] = bank[file_offset + (start + j) mod file_len], j < N        (a file shorter than the clip repeats)

@@ -172,6 +172,105 @@ def resample(x, ratio):
     return y.astype(np.float32)
 
 
+# ---- float64 stage entry points: each takes its stage's input explicitly (tests/test_gpu_augment_stages.py) ----------------------------
+# The functions above keep librosa's float32 / complex64 types (the existing tests pin them); these are the same operations in float64
+# throughout, so that one kernel stage can be compared on the input the kernel itself had.
+def stft64(y):
+    """stft(y) without the complex64 rounding -> complex128 [1025, 1 + len(y)//512]."""
+    yp = np.pad(np.asarray(y, dtype=np.float64), (N_FFT // 2, N_FFT // 2), mode="constant")
+    n_frames = 1 + (len(yp) - N_FFT) // HOP
+    w = hann()
+    return np.stack([np.fft.rfft(w * yp[t * HOP:t * HOP + N_FFT]) for t in range(n_frames)], axis=1)
+
+
+def pv_steps(D, rate):
+    """The per-step quantities of phase_vocoder(D, rate) in float64, without its float32 accumulator: for output step t,
+    i0 [n_out] and alpha [n_out]; c0, c1 = |D[:, i0]|, |D[:, i0 + 1]| (zero columns past the last); mag = (1 - alpha) c0 + alpha c1;
+    turns = (angle(D[:, i0 + 1]) - angle(D[:, i0]) - phi_advance) / 2 pi before it is wrapped; advance = phi_advance + wrapped dphase
+    (what one step adds to the accumulator); acc = the float64 accumulator BEFORE step t (acc[:, 0] = angle(D[:, 0]))."""
+    rate = float(rate)
+    D = np.asarray(D, dtype=np.complex128)
+    n_bins, n_in = D.shape
+    steps = np.arange(0, n_in, rate, dtype=np.float64)
+    i0 = steps.astype(np.int64)
+    alpha = np.mod(steps, 1.0)
+    Dp = np.pad(D, ((0, 0), (0, 2)), mode="constant")
+    phi = HOP * (np.arange(n_bins, dtype=np.float64) * (2.0 * np.pi) / N_FFT)
+    c0, c1 = Dp[:, i0], Dp[:, i0 + 1]
+    a0, a1 = np.abs(c0), np.abs(c1)
+    turns = ((np.angle(c1) - np.angle(c0)) - phi[:, None]) / (2.0 * np.pi)
+    advance = phi[:, None] + 2.0 * np.pi * (turns - np.round(turns))
+    acc = np.angle(D[:, :1]) + np.concatenate([np.zeros((n_bins, 1)), np.cumsum(advance, axis=1)[:, :-1]], axis=1)
+    return {"i0": i0, "alpha": alpha, "c0": a0, "c1": a1, "mag": (1.0 - alpha) * a0 + alpha * a1, "turns": turns, "advance": advance,
+            "acc": acc}
+
+
+def istft64(S, length):
+    """istft(S, length) with the window product, the overlap-add and the window sum-square in float64 (librosa's `length`, centre trim
+    and `> tiny` rule) -> float64 [length]."""
+    S = np.asarray(S, dtype=np.complex128)
+    n_frames = min(S.shape[1], int(math.ceil((length + N_FFT) / HOP)))
+    w = hann()
+    full = np.zeros(N_FFT + HOP * (n_frames - 1))
+    wss = np.zeros_like(full)
+    for t in range(n_frames):
+        full[t * HOP:t * HOP + N_FFT] += w * np.fft.irfft(S[:, t], n=N_FFT)
+        wss[t * HOP:t * HOP + N_FFT] += w * w
+    y, ws = np.zeros(length), np.zeros(length)
+    seg = full[N_FFT // 2:N_FFT // 2 + length]
+    y[:len(seg)] = seg
+    seg = wss[N_FFT // 2:N_FFT // 2 + length]
+    ws[:len(seg)] = seg
+    ok = ws > np.finfo(np.float32).tiny
+    y[ok] /= ws[ok]
+    return y
+
+
+def resample_terms(x, ratio, weights=None):
+    """resample(x, ratio) in float64 throughout, with what bounds a float32 evaluation of it: per output t
+    (y [n_out] float64, absum = sum_i |w_i x_i| over both wings, i_max, k_max: the taps of the left and right wing; -1 where
+    int(t / ratio) >= len(x) and the output is zero).  `weights(win, delta, idx, eta)` replaces the interpolated table weight
+    win[idx] + eta * delta[idx] (the tests restate faults of the table lookup through it)."""
+    x = np.asarray(x, dtype=np.float64)
+    win = kaiser_best_table()
+    num_table = 1 << KB_PRECISION
+    scale = min(1.0, ratio)
+    if ratio < 1.0:
+        win = win * ratio
+    delta = np.append(np.diff(win), 0.0)
+    if weights is None:
+        weights = lambda win, delta, idx, eta: win[idx] + eta * delta[idx]           # noqa: E731
+    index_step = int(scale * num_table)
+    n_out = int(math.ceil(len(x) * ratio))
+    nwin, n_orig = len(win), len(x)
+    y, absum = np.zeros(n_out), np.zeros(n_out)
+    i_maxs, k_maxs = np.full(n_out, -1, np.int64), np.full(n_out, -1, np.int64)
+    for t in range(n_out):
+        time_register = t * (1.0 / ratio)
+        n = int(time_register)
+        if n >= n_orig:
+            continue
+        frac = scale * (time_register - n)
+        for wing in (0, 1):
+            index_frac = frac * num_table
+            offset = int(index_frac)
+            eta = index_frac - offset
+            if wing == 0:
+                cnt = min(n + 1, (nwin - offset) // index_step)
+                xs = x[n - np.arange(cnt)]
+                i_maxs[t] = cnt
+            else:
+                cnt = min(n_orig - n - 1, (nwin - offset) // index_step)
+                xs = x[n + 1 + np.arange(cnt)]
+                k_maxs[t] = cnt
+            idx = offset + index_step * np.arange(cnt)
+            terms = weights(win, delta, idx, eta) * xs
+            y[t] += terms.sum()
+            absum[t] += np.abs(terms).sum()
+            frac = scale - frac
+    return y, absum, i_maxs, k_maxs
+
+
 def pitch_rate(n_steps):
     return 2.0 ** (-float(n_steps) / 12.0)
 

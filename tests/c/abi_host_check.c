@@ -42,6 +42,16 @@ int main(int argc, char** argv) {
     CHECK(ww_packed_weights_floats(2) > 0 && ww_packed_weights_floats(3) > ww_packed_weights_floats(2));
     CHECK(ww_packed_weights_floats(4) == WW_EINVAL && strstr(ww_last_error(), "n_conv") != NULL);
     CHECK(ww_workspace_bytes(16, 2) > 0 && ww_cnn_scratch_bytes(16, 2) == 0 && ww_augment_workspace_bytes(16) > 0);
+    {   /* the workspace's layout is the size function's: regions in order, 256-byte aligned, ending at the size */
+        ww_augment_layout lay;
+        CHECK(ww_augment_workspace_layout(16, 16000, &lay) == WW_OK && lay.total_bytes == ww_augment_workspace_bytes(16));
+        CHECK(ww_augment_workspace_layout(3, 5001, &lay) == WW_OK && lay.total_bytes == ww_augment_n_workspace_bytes(3, 5001));
+        CHECK(lay.records == 0 && lay.buf_a >= 3 * lay.record_bytes && lay.buf_b >= lay.buf_a + 3 * lay.row_bytes);
+        CHECK(lay.spec >= lay.buf_b + 3 * lay.row_bytes && lay.y >= lay.spec + 3 * lay.spec_clip_bytes);
+        CHECK(lay.total_bytes >= lay.y + 3 * lay.y_clip_bytes && lay.row_bytes == 5004 * 4 && lay.record_bytes == ww_augment_record_bytes());
+        CHECK((lay.buf_a | lay.buf_b | lay.spec | lay.y | lay.total_bytes) % 256 == 0);
+        CHECK(ww_augment_workspace_layout(3, 3999, &lay) == WW_EINVAL && ww_augment_workspace_layout(3, 5001, NULL) == WW_EINVAL);
+    }
     /* argument errors are reported before the device is touched */
     CHECK(ww_logmel_f32(NULL, 4, 16000, 16000, 1, NULL, NULL) == WW_EINVAL);
     CHECK(ww_logmel_f32((const float*)16, 4, 16000, 20000, 1, (float*)16, NULL) == WW_EINVAL);

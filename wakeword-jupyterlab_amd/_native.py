@@ -74,6 +74,12 @@ class AugmentPlan(C.Structure):
     ]
 
 
+class AugmentLayout(C.Structure):
+    """struct ww_augment_layout (include/wakeword_amd.h): byte offsets and strides of the augmentation workspace's regions."""
+    _fields_ = [(k, C.c_int64) for k in ("records", "buf_a", "buf_b", "spec", "y", "record_bytes", "row_bytes", "spec_clip_bytes",
+                                         "spec_step_bytes", "y_clip_bytes", "total_bytes")]
+
+
 class AugmentBg(C.Structure):
     """struct ww_augment_bg (include/wakeword_amd.h): one clip's background segment."""
     _fields_ = [
@@ -133,6 +139,7 @@ PROTOTYPES = {
     "ww_augment_plans_prepare": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "ww_augment_records_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_augment_n_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "ww_augment_workspace_layout": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(AugmentLayout)]),
     "ww_augment_n_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(AugmentPlan), C.c_void_p, C.c_int64, C.c_void_p,
                                    C.c_void_p]),
     "ww_augment_plans_prepare_n": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),

@@ -350,6 +350,15 @@ int64_t ww_augment_n_workspace_bytes(int64_t n_clips, int64_t n_samples) {
     return augment_workspace_bytes(n_clips, n_samples);
 }
 
+int ww_augment_workspace_layout(int64_t n_clips, int64_t n_samples, ww_augment_layout* layout_out) {
+    if (n_samples != kClip)
+        if (int rc = check_aug_samples(n_samples)) return rc;
+    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (!layout_out) return fail(WW_EINVAL, "null layout pointer");
+    *layout_out = augment_workspace_layout(n_clips, n_samples);
+    return WW_OK;
+}
+
 int ww_augment_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
                      float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream) {
     if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, plans_host, out_dev, out_stride, workspace_dev)) return rc;

@@ -613,13 +613,26 @@ static int64_t up256(int64_t b) { return (b + 255) & ~int64_t(255); }
 
 static int64_t aug_row_host(int64_t n_samples) { return (n_samples + 3) & ~int64_t(3); }
 
-// The spectrogram and stretched-clip scratch keep their 1 s strides at every length: both are sized by the rate bounds, which do not
-// change with the length (round(16383 / (32 / 46)) = 23551 <= kAugYStride)
-int64_t augment_workspace_bytes(int64_t n, int64_t n_samples) {
-    const int64_t row = aug_row_host(n_samples);
-    return up256(n * int64_t(sizeof(AugDev))) + 2 * up256(n * row * 4) + up256(n * int64_t(kAugMaxOut) * kSpec * 8) +
-           up256(n * int64_t(kAugYStride) * 4);
+// The workspace's regions, in bytes -- the one definition: the size below, launch_records and the diagnostic ww_augment_workspace_layout
+// all read it.  The spectrogram and stretched-clip scratch keep their 1 s strides at every length: both are sized by the rate bounds,
+// which do not change with the length (round(16383 / (32 / 46)) = 23551 <= kAugYStride)
+ww_augment_layout augment_workspace_layout(int64_t n, int64_t n_samples) {
+    ww_augment_layout l = {};
+    l.row_bytes = aug_row_host(n_samples) * 4;
+    l.spec_step_bytes = int64_t(kSpec) * 8;
+    l.spec_clip_bytes = int64_t(kAugMaxOut) * l.spec_step_bytes;
+    l.y_clip_bytes = int64_t(kAugYStride) * 4;
+    l.record_bytes = int64_t(sizeof(AugDev));
+    l.records = 0;                                                  // (the slot ww_augment_f32 copies its records into)
+    l.buf_a = l.records + up256(n * l.record_bytes);
+    l.buf_b = l.buf_a + up256(n * l.row_bytes);
+    l.spec = l.buf_b + up256(n * l.row_bytes);
+    l.y = l.spec + up256(n * l.spec_clip_bytes);
+    l.total_bytes = l.y + up256(n * l.y_clip_bytes);
+    return l;
 }
+
+int64_t augment_workspace_bytes(int64_t n, int64_t n_samples) { return augment_workspace_layout(n, n_samples).total_bytes; }
 
 // Pinned staging for the per-clip records: two slots per device, each guarded by an event, so the call can return as soon as the
 // copy and the kernels are enqueued (round 1 synchronised the stream because the records lived in a pageable vector).
@@ -695,13 +708,13 @@ static int launch_records(const float* pcm, int64_t n, int64_t stride, int n_sam
                           int64_t n_rirs = 0) {
     const LogmelTables* tb = device_tables();
     if (!tb) return WW_EHIP;
-    const int64_t row = aug_row_host(n_samples);
+    const ww_augment_layout lay = augment_workspace_layout(n, n_samples);
+    const int64_t row = lay.row_bytes / 4;
     char* w = static_cast<char*>(workspace);
-    w += up256(n * int64_t(sizeof(AugDev)));                        // (the slot ww_augment_f32 copies its records into)
-    float* bufA = reinterpret_cast<float*>(w); w += up256(n * row * 4);
-    float* bufB = reinterpret_cast<float*>(w); w += up256(n * row * 4);
-    float2* S = reinterpret_cast<float2*>(w); w += up256(n * int64_t(kAugMaxOut) * kSpec * 8);
-    float* Y = reinterpret_cast<float*>(w);
+    float* bufA = reinterpret_cast<float*>(w + lay.buf_a);
+    float* bufB = reinterpret_cast<float*>(w + lay.buf_b);
+    float2* S = reinterpret_cast<float2*>(w + lay.spec);
+    float* Y = reinterpret_cast<float*>(w + lay.y);
     {
         static std::mutex mu;
         static bool attr[64] = {};

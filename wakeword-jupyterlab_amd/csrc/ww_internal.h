@@ -134,6 +134,7 @@ void set_logmel_math_mode(int mode);
 int launch_augment(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host, float* out,
                    int64_t out_stride, void* workspace, hipStream_t stream);
 int64_t augment_workspace_bytes(int64_t n, int64_t n_samples);
+ww_augment_layout augment_workspace_layout(int64_t n, int64_t n_samples);
 int augment_prepare(const ww_augment_plan* plans_host, int64_t n, int64_t n_samples, void* records_host, int* any_pitch_out,
                     int* any_stretch_out);
 int64_t augment_record_bytes();

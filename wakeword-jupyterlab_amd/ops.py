@@ -527,6 +527,28 @@ if _os.environ.get("WW_LOGMEL_MATH"):
 AUG_MAX_SAMPLES = 16383                 # T = 1 + N // 512 <= 32 frames: the clip lengths training takes (4000 .. 16383 samples)
 
 
+def _plans_array(plans, B):
+    """A ctypes array of _native.AugmentPlan as it is, a list of dict plans converted to one."""
+    import ctypes as C
+    if isinstance(plans, C.Array):
+        if len(plans) < B:
+            raise ValueError(f"augment: {len(plans)} plans for {B} clips")
+        return plans
+    arr = (nat.AugmentPlan * max(1, B))()
+    if len(plans) != B:
+        raise ValueError(f"augment: {len(plans)} plans for {B} clips")
+    for i, p in enumerate(plans):
+        a = arr[i]
+        a.shift = int(p.get("shift", 0))
+        a.crop_start = int(p.get("crop", 0))
+        n_steps = p.get("n_steps")
+        a.pitch_rate = float(p["pitch_rate"]) if p.get("pitch_rate") else (2.0 ** (-float(n_steps) / 12.0) if n_steps is not None else 0.0)
+        a.stretch_rate = float(p["rate"]) if p.get("rate") else 0.0
+        a.noise_sigma = float(p.get("sigma", 0.0))
+        a.noise_seed = int(p.get("seed", 0)) & 0xFFFFFFFF
+    return arr
+
+
 def augment(pcm: torch.Tensor, plans, bank=None, rirs=None) -> torch.Tensor:
     """pcm [B, N] float32 on the GPU + one plan per clip -> augmented [B, N], N = 16000 (ww_augment_f32) or any N in 4000..16383
     (ww_augment_n_f32; the plans' shift is taken mod N and crop lies in [0, round(N / rate) - N]).
@@ -552,21 +574,7 @@ def augment(pcm: torch.Tensor, plans, bank=None, rirs=None) -> torch.Tensor:
             bg_plans = plans
         if rirs is not None and any(p.get("rir") is not None for p in plans):
             rir_plans = plans
-        arr = (nat.AugmentPlan * max(1, B))()
-        if len(plans) != B:
-            raise ValueError(f"augment: {len(plans)} plans for {B} clips")
-        for i, p in enumerate(plans):
-            a = arr[i]
-            a.shift = int(p.get("shift", 0))
-            a.crop_start = int(p.get("crop", 0))
-            n_steps = p.get("n_steps")
-            a.pitch_rate = float(p["pitch_rate"]) if p.get("pitch_rate") else (2.0 ** (-float(n_steps) / 12.0) if n_steps is not None else 0.0)
-            a.stretch_rate = float(p["rate"]) if p.get("rate") else 0.0
-            a.noise_sigma = float(p.get("sigma", 0.0))
-            a.noise_seed = int(p.get("seed", 0)) & 0xFFFFFFFF
-        plans = arr
-    elif len(plans) < B:
-        raise ValueError(f"augment: {len(plans)} plans for {B} clips")
+    plans = _plans_array(plans, B)
     bg = _bg_array(bg_plans, bank, B) if bank is not None and bg_plans else None
     rir = _rir_array(rir_plans, rirs, B) if rirs is not None and rir_plans else None
     out = torch.empty((B, N), device=pcm.device, dtype=torch.float32)
@@ -600,6 +608,73 @@ def augment(pcm: torch.Tensor, plans, bank=None, rirs=None) -> torch.Tensor:
                                                C.c_void_p(out.data_ptr()), N, C.c_void_p(ws.data_ptr()), stream))
         ws.record_stream(torch.cuda.current_stream())
     return out
+
+
+# the per-clip record of csrc/ww_augment.hip (AugDev), ww_augment_record_bytes() bytes each
+AUG_RECORD_DTYPE = [("shift", "<i4"), ("crop", "<i4"), ("p_out", "<i4"), ("p_len", "<i4"), ("p_res", "<i4"), ("s_out", "<i4"),
+                    ("s_len", "<i4"), ("seed", "<u4"), ("p_rate", "<f8"), ("p_ratio", "<f8"), ("s_rate", "<f8"), ("sigma", "<f4"), ("pad", "<f4")]
+
+
+def augment_stages(pcm: torch.Tensor, plans, poison: bool = False) -> dict:
+    """Diagnostic: ops.augment(pcm, plans) with the kernel chain's intermediates, viewed from the workspace of this call through
+    ww_augment_workspace_layout and cut to each clip's real sizes.  One vocoder pass only: a batch whose plans turn on both pitch and
+    stretch is refused (the second pass overwrites S), and so are background and reverb keys.  Returns
+        "records"  numpy structured array [B] (AUG_RECORD_DTYPE): what the kernels read for each clip
+        "rolled"   [B, row] the work buffer the STFT reads: np.roll of the input, rows padded with zeros to four floats
+        "S"        list of complex64 [steps, 1025]: the vocoder's output columns (steps = p_out or s_out; 0 rows for a clip with the pass off)
+        "Y"        list of float32 [p_len]: the pitch pass's inverse STFT before resampling (empty for stretch batches and pitch-off clips)
+        "Y_tail"   list of float32 [4]: the four floats past Y (never written; with `poison` they stay NaN)
+        "stage"    [B, row] the chain's last work buffer: the resampled clips (pitch batch), the cropped / zero-padded inverse STFT
+                   (stretch batch), the rolled input (neither)
+        "out"      [B, N] the call's result (the stage plus the plans' Gaussian noise)
+    `poison` fills the workspace with float32 NaN before the call: whatever a kernel reads without having written it shows in the output."""
+    import ctypes as C
+
+    import numpy as np
+    if pcm.device.type != "cuda":
+        raise RuntimeError("augment_stages: pcm must live on the MI355X (no CPU fallback)")
+    if pcm.dtype != torch.float32 or pcm.dim() != 2 or not MIN_CLIP_SAMPLES <= pcm.shape[1] <= AUG_MAX_SAMPLES or pcm.shape[0] < 1:
+        raise ValueError(f"augment_stages: expected float32 [B >= 1, N], N in {MIN_CLIP_SAMPLES}..{AUG_MAX_SAMPLES}, got {pcm.dtype} {tuple(pcm.shape)}")
+    if not isinstance(plans, C.Array) and any(k in p for p in plans for k in ("bg_file", "rir")):
+        raise ValueError("augment_stages: background and reverb are not staged")
+    N = int(pcm.shape[1])
+    pcm = pcm.contiguous() if N == CLIP_SAMPLES else _aligned_rows(pcm)
+    B = pcm.shape[0]
+    plans = _plans_array(plans, B)
+    any_pitch = any(plans[i].pitch_rate != 0.0 for i in range(B))
+    any_stretch = any(plans[i].stretch_rate != 0.0 for i in range(B))
+    if any_pitch and any_stretch:
+        raise ValueError("augment_stages: the batch turns on both pitch and stretch; the stretch pass overwrites the pitch pass's S")
+    lay = nat.AugmentLayout()
+    nat.check(nat.lib.ww_augment_workspace_layout(B, N, C.byref(lay)))
+    out = torch.empty((B, N), device=pcm.device, dtype=torch.float32)
+    with torch.cuda.device(pcm.device):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ws = torch.empty(lay.total_bytes, device=pcm.device, dtype=torch.uint8)
+        if poison:
+            ws.view(torch.float32).fill_(float("nan"))
+        if N == CLIP_SAMPLES:
+            assert lay.total_bytes == nat.check(nat.lib.ww_augment_workspace_bytes(B))
+            nat.check(nat.lib.ww_augment_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0), plans, C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(ws.data_ptr()), stream))
+        else:
+            assert lay.total_bytes == nat.check(nat.lib.ww_augment_n_workspace_bytes(B, N))
+            nat.check(nat.lib.ww_augment_n_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, plans,
+                                               C.c_void_p(out.data_ptr()), N, C.c_void_p(ws.data_ptr()), stream))
+        torch.cuda.current_stream().synchronize()
+
+    def region(off, stride, dtype=torch.float32):
+        return ws[off:off + B * stride].view(dtype).view(B, -1)
+    rec = np.frombuffer(ws[lay.records:lay.records + B * lay.record_bytes].cpu().numpy().tobytes(), dtype=np.dtype(AUG_RECORD_DTYPE))
+    assert rec.itemsize == lay.record_bytes
+    buf_a, buf_b = region(lay.buf_a, lay.row_bytes), region(lay.buf_b, lay.row_bytes)
+    spec = torch.view_as_complex(region(lay.spec, lay.spec_clip_bytes).view(B, -1, lay.spec_step_bytes // 8, 2))
+    y = region(lay.y, lay.y_clip_bytes)
+    steps = [int(r["p_out"] if any_pitch else r["s_out"]) for r in rec]
+    return {"records": rec, "rolled": buf_a, "S": [spec[i, :steps[i]] for i in range(B)],
+            "Y": [y[i, :int(rec[i]["p_len"]) if rec[i]["p_out"] else 0] for i in range(B)],
+            "Y_tail": [y[i, int(rec[i]["p_len"]):int(rec[i]["p_len"]) + 4] for i in range(B)],
+            "stage": buf_b if (any_pitch or any_stretch) else buf_a, "out": out}
 
 
 def _check_bank(bank, device) -> None:
