@@ -549,6 +549,31 @@ WW_API int ww_train_packed_image(const void* workspace_dev, int64_t n, int32_t n
  * mask_last_dev [n][80][32][C/8] bytes, bit c of the position = [relu(last conv)[c] > 0] (C = 64 | 128, byte cb = channels 8 cb ..), in canonical
  * order (the kernels' own image holds the accumulator ballots); sign1_dev [n][80][32] words, bit c = [relu(conv1)[c] > 0]. */
 WW_API int ww_train_bit_images(const void* workspace_dev, int64_t n, int32_t n_conv, uint8_t* mask_last_dev, uint32_t* sign1_dev, ww_stream_t stream);
+/* Diagnostic, read-only: one intermediate of the step that last ran on this workspace (after its backward for the d... stages), copied to
+ * out_dev; out_floats must be the stage's size.  train_math must be the arithmetic the workspace's forward ran under: a workspace no
+ * forward of this process is on record for, or one written under the other arithmetic, is WW_EINVAL, and so is a stage that the model /
+ * arithmetic does not keep, or a stage the backward writes (DHD1 .. DZ2) when no backward has run on the workspace since its last forward.
+ * Shapes (H = 256, C = 64 | 128 channels of the last conv):
+ *   POOLED [n][C]   GATES0/1 [4][n][H], planes sigmoid i, tanh g, sigmoid o, tanh c   HD0/1 [n][H] (LSTM outputs times their dropout factors)
+ *   DHD1, DHD0 [n][H]   DG1, DG0 [n][4H] in torch's gate-row order i, f, g, o   DPOOLED, GP [n][C] (GP = DPOOLED / (80 width))
+ *   DZ2 [n][80][64][32] (3-conv model: d loss / d conv2 pre-activation; under F16X3 decoded from the f16 halves with the per-clip scale applied)
+ *   MID2 [n][80][64][32] relu(conv2) (F32; F16X3: 3-conv model only)   MID3 [n][80][128][32] relu(conv3) (F32, 3-conv model) */
+#define WW_TRAIN_STAGE_POOLED 0
+#define WW_TRAIN_STAGE_GATES0 1
+#define WW_TRAIN_STAGE_GATES1 2
+#define WW_TRAIN_STAGE_HD0 3
+#define WW_TRAIN_STAGE_HD1 4
+#define WW_TRAIN_STAGE_DHD1 5
+#define WW_TRAIN_STAGE_DG1 6
+#define WW_TRAIN_STAGE_DHD0 7
+#define WW_TRAIN_STAGE_DG0 8
+#define WW_TRAIN_STAGE_DPOOLED 9
+#define WW_TRAIN_STAGE_GP 10
+#define WW_TRAIN_STAGE_DZ2 11
+#define WW_TRAIN_STAGE_MID2 12
+#define WW_TRAIN_STAGE_MID3 13
+WW_API int ww_train_stage(const void* workspace_dev, int64_t n, int32_t n_conv, int32_t train_math, int32_t stage, float* out_dev,
+                          int64_t out_floats, ww_stream_t stream);
 /* Arithmetic of the training step's convolution kernels (the head is always exact fp32); ww_set_train_math sets the process-wide DEFAULT that
  * WW_TRAIN_MATH_DEFAULT resolves to:
  *   WW_TRAIN_MATH_F32    exact fp32 matrix instructions throughout (v_mfma_f32_32x32x2_f32)

@@ -57,6 +57,9 @@ int main(int argc, char** argv) {
     CHECK(ww_logmel_f32((const float*)16, 4, 16000, 20000, 1, (float*)16, NULL) == WW_EINVAL);
     CHECK(ww_set_conv_math(7) == WW_EINVAL && ww_get_conv_math() == WW_CONV_MATH_F16X3);
     CHECK(ww_train_workspace_bytes(64, 2, WW_TRAIN_MATH_F16X3) < ww_train_workspace_bytes(64, 2, WW_TRAIN_MATH_F32));
+    /* the stage diagnostic refuses a workspace no forward is on record for, before the device is touched */
+    CHECK(ww_train_stage((const void*)256, 4, 2, WW_TRAIN_MATH_F32, WW_TRAIN_STAGE_GP, (float*)16, 4 * 64, NULL) == WW_EINVAL);
+    CHECK(strstr(ww_last_error(), "on record") != NULL);
     CHECK(ww_set_conv_math_thread(WW_CONV_MATH_F32) == WW_OK && ww_get_conv_math() == WW_CONV_MATH_F32);
     CHECK(ww_set_conv_math_thread(WW_MATH_INHERIT) == WW_OK && ww_get_conv_math() == WW_CONV_MATH_F16X3);
     /* the batch WAV reader from C, host-only mode (no GPU): one file written here, read back through the thread pool */

@@ -237,6 +237,20 @@ def test_training_workspace_size_is_checked_against_the_mode_of_the_call():
         assert nat.lib.ww_train_forward_f32(*args, 1, base, small, base, None) == nat.WW_ENODEVICE
 
 
+def test_train_stage_refuses_a_workspace_it_has_no_forward_on_record_for():
+    """ww_train_stage reads a workspace's regions by the layout of the arithmetic its forward ran under: without a forward on record
+    (or under another arithmetic, or for a backward stage before the backward: tests/test_gpu_train_stages.py::
+    test_stages_of_another_arithmetic_or_before_the_backward_are_refused) it is WW_EINVAL before anything is launched, as are bad arguments."""
+    fake = np.zeros(1024, np.float32)
+    base = (fake.ctypes.data + 255) // 256 * 256
+    for math in (0, 1, -1):
+        assert nat.lib.ww_train_stage(base, 4, 2, math, 10, base, 4 * 64, None) == nat.WW_EINVAL
+        assert b"on record" in nat.lib.ww_last_error()
+    assert nat.lib.ww_train_stage(base, 4, 2, 7, 10, base, 4 * 64, None) == nat.WW_EINVAL            # unknown arithmetic
+    assert nat.lib.ww_train_stage(None, 4, 2, 0, 10, base, 4 * 64, None) == nat.WW_EINVAL
+    assert nat.lib.ww_train_stage(base, 4, 4, 0, 10, base, 4 * 64, None) == nat.WW_EINVAL
+
+
 def test_argument_checks_come_before_device_checks():
     buf = np.zeros(16, np.float32)
     assert nat.lib.ww_logmel_f32(buf.ctypes.data, 1, 16000, 20000, 1, buf.ctypes.data, None) == nat.WW_EINVAL

@@ -872,6 +872,20 @@ int ww_train_bit_images(const void* workspace_dev, int64_t n, int32_t n_conv, ui
     return train_bit_images(workspace_dev, n, n_conv, mask_last_dev, sign1_dev, static_cast<hipStream_t>(stream));
 }
 
+int ww_train_stage(const void* workspace_dev, int64_t n, int32_t n_conv, int32_t train_math, int32_t stage, float* out_dev, int64_t out_floats,
+                   ww_stream_t stream) {
+    if (!workspace_dev || !out_dev || n < 1 || n > (int64_t(1) << 24) || (n_conv != 2 && n_conv != 3)) return fail(WW_EINVAL, "ww_train_stage: bad arguments");
+    int mode;
+    if (int rc = resolve_train_math(train_math, &mode)) return rc;
+    if (int rc = train_stage_mode_check(workspace_dev, mode)) return rc;
+    const int64_t floats = train_stage_floats(n, n_conv, mode, stage);
+    if (floats < 0) return fail(WW_EINVAL, "ww_train_stage: unknown stage %d", stage);
+    if (floats == 0) return fail(WW_EINVAL, "ww_train_stage: stage %d is not kept by the %d-conv model under train math %d", stage, n_conv, mode);
+    if (out_floats != floats) return fail(WW_EINVAL, "ww_train_stage: stage %d holds %lld floats, the output has %lld", stage, (long long)floats, (long long)out_floats);
+    if (int rc = require_gfx950()) return rc;
+    return train_stage(workspace_dev, n, n_conv, mode, stage, out_dev, static_cast<hipStream_t>(stream));
+}
+
 int ww_train_backward_f32(const float* mel_dev, int64_t n, int32_t width, const ww_train_params* params, const float* dlogits_dev,
                           int32_t train_math, void* workspace_dev, int64_t workspace_bytes, const ww_train_grads* grads, ww_stream_t stream) {
     int mode;

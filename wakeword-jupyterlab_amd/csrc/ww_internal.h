@@ -209,6 +209,10 @@ int train_masks(const void* workspace, int64_t n, int n_conv, float* mask0, floa
 int train_packed_image(const void* workspace, int64_t n, int n_conv, float* img, hipStream_t st);
 int train_bit_images(const void* workspace, int64_t n, int n_conv, uint8_t* mask_last, uint32_t* sign1, hipStream_t st);
 int launch_decode_mask_image(const uint32_t* img, int64_t n, int C, uint8_t* out, hipStream_t st);
+int train_stage_mode_check(const void* workspace, int mode);
+int64_t train_stage_floats(int64_t n, int n_conv, int mode, int stage);
+int train_stage(const void* workspace, int64_t n, int n_conv, int mode, int stage, float* out, hipStream_t st);
+int launch_decode_channels_last(const float* src, const float* scale /*nullable*/, int64_t n, float* out, hipStream_t st);
 int train_backward(const float* mel, int64_t n, int width, const ww_train_params* p, const float* dlogits, int mode, void* workspace,
                    int64_t workspace_bytes, const ww_train_grads* g, hipStream_t st);
 

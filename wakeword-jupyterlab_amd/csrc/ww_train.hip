@@ -625,13 +625,13 @@ static int64_t a256(int64_t floats) { return (floats * 4 + 255) / 256 * 64; }   
 // diagnostics) of a step must not run under another one.  Host-side note per workspace pointer, written by train_forward; a backward
 // under a different mode fails with WW_EINVAL instead of reading bit images that are not there.  (Bounded: the newest 64 workspaces.)
 static std::mutex g_ws_mu;
-static struct { const void* ws; int mode; } g_ws_mode[64];
+static struct { const void* ws; int mode; bool bwd; } g_ws_mode[64];   // bwd: a backward has run since the last forward (diagnostics)
 static int g_ws_next = 0;
 static void note_workspace_mode(const void* ws, int mode) {
     std::lock_guard<std::mutex> lock(g_ws_mu);
     for (auto& e : g_ws_mode)
-        if (e.ws == ws) { e.mode = mode; return; }
-    g_ws_mode[g_ws_next] = {ws, mode};
+        if (e.ws == ws) { e.mode = mode; e.bwd = false; return; }
+    g_ws_mode[g_ws_next] = {ws, mode, false};
     g_ws_next = (g_ws_next + 1) % 64;
 }
 static int workspace_mode(const void* ws) {            // -1: unknown (never seen, or evicted)
@@ -639,6 +639,18 @@ static int workspace_mode(const void* ws) {            // -1: unknown (never see
     for (auto& e : g_ws_mode)
         if (e.ws == ws && ws != nullptr) return e.mode;
     return -1;
+}
+
+static void note_workspace_backward(const void* ws) {
+    std::lock_guard<std::mutex> lock(g_ws_mu);
+    for (auto& e : g_ws_mode)
+        if (e.ws == ws && ws != nullptr) e.bwd = true;
+}
+static bool workspace_backward_done(const void* ws) {
+    std::lock_guard<std::mutex> lock(g_ws_mu);
+    for (auto& e : g_ws_mode)
+        if (e.ws == ws && ws != nullptr) return e.bwd;
+    return false;
 }
 
 static TrainWs carve_train(void* base, int64_t n, int n_conv, int mode) {
@@ -716,6 +728,64 @@ int train_bit_images(const void* workspace, int64_t n, int n_conv, uint8_t* mask
     TrainWs w = carve_train(const_cast<void*>(workspace), n, n_conv, workspace_mode(workspace));
     if (int rc = launch_decode_mask_image(w.maskbits, n, n_conv == 3 ? 128 : 64, mask_last, st)) return rc;
     WW_HIP(hipMemcpyAsync(sign1, w.bits1, sizeof(uint32_t) * n * kTH * kTW, hipMemcpyDeviceToDevice, st));
+    return WW_OK;
+}
+
+// test / diagnostic: one intermediate of the step that last ran on this workspace (ww_train_stage: the header lists stages and shapes).
+// Read-only: copies out of the regions carve_train names; the conv-shaped ones come out as [n][80][C][32] whatever the arithmetic kept.
+int train_stage_mode_check(const void* workspace, int mode) {
+    const int noted = workspace_mode(workspace);
+    if (noted < 0) return fail(WW_EINVAL, "ww_train_stage: no training forward is on record for this workspace");
+    if (noted != mode)
+        return fail(WW_EINVAL, "ww_train_stage: the forward of this workspace ran under train math %d, its stages are asked under %d", noted, mode);
+    return WW_OK;
+}
+int64_t train_stage_floats(int64_t n, int n_conv, int mode, int stage) {
+    const int64_t c_last = n_conv == 3 ? 128 : 64;
+    const bool split = mode == WW_TRAIN_MATH_F16X3;
+    switch (stage) {
+        case WW_TRAIN_STAGE_POOLED: case WW_TRAIN_STAGE_DPOOLED: case WW_TRAIN_STAGE_GP: return n * c_last;
+        case WW_TRAIN_STAGE_GATES0: case WW_TRAIN_STAGE_GATES1: case WW_TRAIN_STAGE_DG1: case WW_TRAIN_STAGE_DG0: return 4 * n * kHidden;
+        case WW_TRAIN_STAGE_HD0: case WW_TRAIN_STAGE_HD1: case WW_TRAIN_STAGE_DHD1: case WW_TRAIN_STAGE_DHD0: return n * kHidden;
+        case WW_TRAIN_STAGE_DZ2: return n_conv == 3 ? n * kTH * 64 * kTW : 0;
+        case WW_TRAIN_STAGE_MID2: return (!split || n_conv == 3) ? n * kTH * 64 * kTW : 0;
+        case WW_TRAIN_STAGE_MID3: return (!split && n_conv == 3) ? n * kTH * 128 * kTW : 0;
+        default: return -1;
+    }
+}
+int train_stage(const void* workspace, int64_t n, int n_conv, int mode, int stage, float* out, hipStream_t st) {
+    if (int rc = train_stage_mode_check(workspace, mode)) return rc;
+    const TrainWs w = carve_train(const_cast<void*>(workspace), n, n_conv, mode);
+    const int64_t floats = train_stage_floats(n, n_conv, mode, stage);
+    if (floats <= 0) return fail(WW_EINVAL, "ww_train_stage: stage %d is not kept by the %d-conv model under train math %d", stage, n_conv, mode);
+    const bool of_backward = (stage >= WW_TRAIN_STAGE_DHD1 && stage <= WW_TRAIN_STAGE_DZ2);
+    if (of_backward && !workspace_backward_done(workspace))
+        return fail(WW_EINVAL, "ww_train_stage: stage %d is written by the backward, and none has run on this workspace since its last forward", stage);
+    const bool split = mode == WW_TRAIN_MATH_F16X3;
+    const float* src = nullptr;
+    switch (stage) {
+        case WW_TRAIN_STAGE_POOLED: src = w.pooled; break;
+        case WW_TRAIN_STAGE_GATES0: src = w.gates0; break;
+        case WW_TRAIN_STAGE_GATES1: src = w.gates1; break;
+        case WW_TRAIN_STAGE_HD0: src = w.hd0; break;
+        case WW_TRAIN_STAGE_HD1: src = w.hd1; break;
+        case WW_TRAIN_STAGE_DHD1: src = w.dhd1; break;
+        case WW_TRAIN_STAGE_DG1: src = w.dg1; break;
+        case WW_TRAIN_STAGE_DHD0: src = w.dhd0; break;
+        case WW_TRAIN_STAGE_DG0: src = w.dg0; break;
+        case WW_TRAIN_STAGE_DPOOLED: src = w.dpooled; break;
+        case WW_TRAIN_STAGE_GP: src = w.gp; break;
+        case WW_TRAIN_STAGE_DZ2:                            // split: f16 records [row][column][64 hi | 64 lo] of dz2 2^-edz, 2^edz per clip
+            if (split) return launch_decode_channels_last(w.dz2, dgrad_h_dzs(w.dgh, n), n, out, st);
+            src = w.dz2; break;
+        case WW_TRAIN_STAGE_MID2:                           // split: float32 [row][column][64]
+            if (split) return launch_decode_channels_last(w.mid2, nullptr, n, out, st);
+            src = w.mid2; break;
+        case WW_TRAIN_STAGE_MID3: src = w.mid3; break;
+        default: break;
+    }
+    if (src == nullptr) return fail(WW_EINVAL, "ww_train_stage: unknown stage %d", stage);
+    WW_HIP(hipMemcpyAsync(out, src, sizeof(float) * size_t(floats), hipMemcpyDeviceToDevice, st));
     return WW_OK;
 }
 
@@ -848,7 +918,9 @@ int train_backward(const float* mel, int64_t n, int width, const ww_train_params
         hipLaunchKernelGGL((conv_dgrad_kernel<32, 64, false, true>), dim3(grid), dim3(256), kDg2Lds, st,
                            mel, static_cast<const float*>(nullptr), w.mid2, w.gp, N, width, w1, b1, w.dgrad2_b_op, w.partial);
     WW_HIP(hipGetLastError());
-    return reduce_to(w, grid, kDgPartial, 32 * 9, g->conv_weight[0], g->conv_bias[0], 32, st);
+    if (int rc = reduce_to(w, grid, kDgPartial, 32 * 9, g->conv_weight[0], g->conv_bias[0], 32, st)) return rc;
+    note_workspace_backward(workspace);
+    return WW_OK;
 }
 
 }  // namespace ww

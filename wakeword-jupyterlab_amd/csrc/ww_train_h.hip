@@ -1301,6 +1301,29 @@ int launch_decode_mask_image(const uint32_t* img, int64_t n, int C, uint8_t* out
     return WW_OK;
 }
 
+// test / diagnostic: a 64-channel channels-last image as plain float32 out[b][row][c][col].  scale == nullptr: src is float32
+// [n][80][32][64] (relu(conv2) of the 3-conv model); else src holds the f16 records [n][80][32][64 hi | 64 lo] of dz2 2^-edz and
+// scale[b] = 2^edz: (hi + lo) is exact in float32 (lo is the rounding remainder of hi), and so is the power of two.
+__global__ void decode_channels_last_kernel(const void* __restrict__ src, const float* __restrict__ scale, int64_t n, float* __restrict__ out) {
+    const int64_t total = n * kTH * 64 * kTW;
+    for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < total; i += int64_t(gridDim.x) * blockDim.x) {
+        const int col = int(i % kTW), c = int((i / kTW) % 64);
+        const int64_t brow = i / (int64_t(kTW) * 64);                 // b * 80 + row
+        const int64_t pos = brow * kTW + col;
+        if (scale == nullptr) {
+            out[i] = static_cast<const float*>(src)[pos * 64 + c];
+        } else {
+            const _Float16* rec = static_cast<const _Float16*>(src) + pos * 128;
+            out[i] = (static_cast<float>(rec[c]) + static_cast<float>(rec[64 + c])) * scale[brow / kTH];
+        }
+    }
+}
+int launch_decode_channels_last(const float* src, const float* scale, int64_t n, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(decode_channels_last_kernel, dim3(1024), dim3(256), 0, st, static_cast<const void*>(src), scale, n, out);
+    WW_HIP(hipGetLastError());
+    return WW_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------

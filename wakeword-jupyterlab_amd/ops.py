@@ -429,6 +429,41 @@ def train_last_masks(n: int):
     return m0, m1
 
 
+_TRAIN_STAGES = ("pooled", "gates0", "gates1", "hd0", "hd1", "dhd1", "dg1", "dhd0", "dg0", "dpooled", "gp", "dz2", "mid2", "mid3")   # WW_TRAIN_STAGE_*
+
+
+def train_stages(train_math: str, names=None) -> dict:
+    """Diagnostic, read-only: the intermediates of the newest kept training workspace, {name: float32 tensor}.
+      pooled [n,C]; gates0/1 [4,n,256] (planes sigmoid i, tanh g, sigmoid o, tanh c); hd0/1 [n,256]   -- written by the forward
+      dhd1, dhd0 [n,256]; dg1, dg0 [n,1024] (torch's i,f,g,o rows); dpooled, gp [n,C]                  -- written by the backward
+      3-conv model: dz2 [n,64,80,32] (backward; split mode: decoded, per-clip scales applied)
+      mid2 [n,64,80,32] / mid3 [n,128,80,32] where the arithmetic keeps them (forward)
+    `train_math` must name the arithmetic the step ran under: the library refuses a workspace it has no forward on record for
+    or whose forward ran under the other one, and the backward's stages until the backward has run.
+    `names` restricts the copy to some stages (mid2 is 2.7 GB at 4096 clips)."""
+    if train_math not in TRAIN_MATH:
+        raise ValueError(f"train math {train_math!r}: expected one of {sorted(TRAIN_MATH)}")
+    ws, n, nc = _last_workspace(), _TrainStep.last_n, _TrainStep.last_n_conv
+    C_last, split = c_last(nc), train_math == "f16x3"
+    shapes = {"pooled": (n, C_last), "gates0": (4, n, 256), "gates1": (4, n, 256), "hd0": (n, 256), "hd1": (n, 256), "dhd1": (n, 256),
+              "dg1": (n, 1024), "dhd0": (n, 256), "dg0": (n, 1024), "dpooled": (n, C_last), "gp": (n, C_last)}
+    if nc == 3:
+        shapes["dz2"] = (n, 80, 64, 32)
+    if nc == 3 or not split:
+        shapes["mid2"] = (n, 80, 64, 32)
+    if nc == 3 and not split:
+        shapes["mid3"] = (n, 80, 128, 32)
+    out = {}
+    with torch.cuda.device(ws.device):
+        for name, shape in shapes.items():
+            if names is not None and name not in names:
+                continue
+            t = torch.empty(shape, device=ws.device, dtype=torch.float32)
+            nat.check(nat.lib.ww_train_stage(_ptr(ws), n, nc, TRAIN_MATH[train_math], _TRAIN_STAGES.index(name), _ptr(t), t.numel(), _stream()))
+            out[name] = t.permute(0, 2, 1, 3) if len(shape) == 4 else t          # [n, C, 80, 32] view
+    return out
+
+
 def train_last_packed_image() -> torch.Tensor:
     """Diagnostic: the packed image the most recent split-precision training forward of the 2-conv model wrote on the device."""
     ws = _last_workspace()
