@@ -54,6 +54,24 @@ CASES = [  # (name, sr, seconds, channels, bits, fmt)
 ]
 
 
+def _own_input_stage_check(row, samples, sr, start, normalize, what):
+    """The resampler stage of tests/test_gpu_decode_stages.py on this row: float64 over K0's own float32 mono and float32 taps, bound
+    b[j] = n[j] u A[j] + 2^-149.  Normalised rows: out = fl(g / pg) with |g - y| <= b and |pg - py| <= B = max b (peaks over the whole
+    file), so |out - y / py| <= (b + B |y| / py) / (py - B) + u |out|."""
+    import k0_cases as k0
+    t, up, down, hl = k0.taps(sr)
+    _, x32 = decode_oracle.mono_f64(samples.reshape(-1), decode_oracle.FMT_F32, samples.shape[1])
+    y, A, n = decode_oracle.resample_own_input(x32, t, up, down, hl)
+    b = decode_oracle.stage_bound(A, n)
+    if normalize:
+        py, B = np.abs(y).max(), b.max()
+        b = (b + B * np.abs(y) / py) / (py - B) + decode_oracle.U32 * np.abs(y) / (py - B)
+        y = y / py
+    v = min(16000, len(y) - start)
+    err = np.abs(row[:v].astype(np.float64) - y[start:start + v])
+    assert (err <= b[start:start + v]).all(), (what, float((err / b[start:start + v]).max()))
+
+
 def test_gpu_decode_matches_oracle(tmp_path):
     proc = AudioProcessor()
     paths = []
@@ -85,6 +103,8 @@ def test_gpu_decode_matches_oracle(tmp_path):
             assert err <= (2e-7 if sr == 16000 else 5e-6), (p, err)   # exact conversion at 16 kHz; f32 filter sums otherwise
             if normalize:
                 assert abs(np.abs(ref).max() - 1.0) < 1e-6 or n_out > 16000
+            if sr != 16000:
+                _own_input_stage_check(out[i], samples, sr, start, normalize, p)
 
 
 def test_dataset_batches_with_gpu_decode_feed_the_model(tmp_path):
