@@ -243,6 +243,46 @@ def test_records_path_is_graph_capturable_and_bitwise_equal(bank, n):
     assert torch.equal(out, ops.augment(x, batches[-1]))
 
 
+@pytest.mark.parametrize("n", (4000, 16000))
+def test_families_share_the_staging_slots(n):
+    """Plain, background and reverb calls stage their records through the same two pinned slots per device.  Six calls back to back on
+    one stream without a synchronise in between (the third grows its slot, if nothing larger ran in the process before, while earlier
+    copies may still be in flight) give what each gives alone; and a batch without background or reverb gives the same bits through
+    every direct entry point."""
+    rng = np.random.default_rng(8)
+    files = [(rng.standard_normal(m) * 0.2).astype(np.float32) for m in (5000, 700)]
+    bgbank = BackgroundNoiseBank.from_buffer(torch.from_numpy(np.concatenate(files)).to(DEV), [len(f) for f in files])
+    rirs = ImpulseResponseBank.from_taps([reverb_ref.decaying_rir(L, d, seed=L) for L, d in ((300, 5), (6000, 80))], device=DEV)
+    x = torch.from_numpy(_clips(5, n, start=20)).to(DEV)
+    prng = random.Random(n)
+    calls = [(B, _draw(prng, n, B, p_bg, p_rir, bgbank, rirs.n_rirs)) for B, p_bg, p_rir in
+             ((2, 0.0, 0.0), (2, 1.0, 0.0), (5, 1.0, 1.0), (2, 0.0, 0.0), (2, 1.0, 0.0), (5, 1.0, 1.0))]
+    assert calls[0][1] != calls[3][1] and calls[1][1] != calls[4][1] and calls[2][1] != calls[5][1]
+    together = [ops.augment(x[:B], plans, bank=bgbank, rirs=rirs) for B, plans in calls]
+    torch.cuda.synchronize()
+    for (B, plans), got in zip(calls, together):
+        alone = ops.augment(x[:B], plans, bank=bgbank, rirs=rirs)
+        torch.cuda.synchronize()
+        assert torch.equal(got, alone)
+
+    B = 3
+    plans = _draw(prng, n, B, 0.0, 0.0, None, 0)
+    want = ops.augment(x[:B], plans)
+    xa = ops._aligned_rows(x[:B])
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ws = torch.empty(int(nat.lib.ww_augment_rir_workspace_bytes(B, n)), dtype=torch.uint8, device=DEV)
+    bg_off, rir_off = (nat.AugmentBg * B)(), (nat.AugmentRir * B)()
+    outs = [torch.empty_like(want) for _ in range(3)]
+    nat.check(nat.lib.ww_augment_n_f32(xa.data_ptr(), B, xa.stride(0), n, _plan_array(plans), outs[0].data_ptr(), n, ws.data_ptr(), stream))
+    nat.check(nat.lib.ww_augment_bg_f32(xa.data_ptr(), B, xa.stride(0), n, _plan_array(plans), bg_off, bgbank.data.data_ptr(),
+                                        bgbank.data.numel(), outs[1].data_ptr(), n, ws.data_ptr(), stream))
+    nat.check(nat.lib.ww_augment_rir_f32(xa.data_ptr(), B, xa.stride(0), n, _plan_array(plans), None, None, 0, rir_off,
+                                         rirs.spectra.data_ptr(), rirs.n_rirs, outs[2].data_ptr(), n, ws.data_ptr(), stream))
+    torch.cuda.synchronize()
+    for out in outs:
+        assert torch.equal(out, want)
+
+
 def _float_wav(samples, rate):
     raw = np.asarray(samples, "<f4").tobytes()
     fmt = struct.pack("<HHIIHH", 3, 1, rate, rate * 4, 4, 32)

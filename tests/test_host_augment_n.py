@@ -104,6 +104,18 @@ def test_n_samples_outside_the_range_is_refused_before_any_launch():
     assert nat.lib.ww_augment_n_workspace_bytes(7, 5001) < nat.lib.ww_augment_workspace_bytes(7)
 
 
+def test_a_bad_plan_is_refused_before_the_device_check():
+    """The plain calls prepare their records before they look for a GPU, as the background and reverb calls do: a negative noise_sigma
+    is WW_EINVAL on a machine without one, not WW_ENODEVICE."""
+    dummy = C.c_void_p(1 << 20)                                    # never dereferenced: the checks come first
+    plans = _plans([{}, {"sigma": -1.0}])
+    assert nat.lib.ww_augment_f32(dummy, 2, 16000, plans, dummy, dummy, None) == nat.WW_EINVAL
+    assert "plan 1: noise_sigma" in nat.lib.ww_last_error().decode()
+    for n in (4000, 16000, 16383):
+        assert nat.lib.ww_augment_n_f32(dummy, 2, (n + 3) & ~3, n, plans, dummy, n, dummy, None) == nat.WW_EINVAL
+        assert "plan 1: noise_sigma" in nat.lib.ww_last_error().decode()
+
+
 @pytest.mark.parametrize("n", NS)
 def test_rates_keep_the_one_second_bounds_at_every_length(n):
     T = 1 + n // 512

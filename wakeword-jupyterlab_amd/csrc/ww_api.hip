@@ -282,43 +282,60 @@ int ww_logmel_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, in
                          static_cast<hipStream_t>(stream));
 }
 
-int64_t ww_augment_workspace_bytes(int64_t n_clips) {
+static int check_n_clips(int64_t n_clips) {
     if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
-    return augment_workspace_bytes(n_clips, kClip);
+    return WW_OK;
+}
+
+// Every direct augmentation call after its argument checks: the records prepared once (every refusal before the device check and any
+// launch), then staged and launched
+static int augment_direct(const AugCall& call, unsigned parts, const ww_augment_plan* plans_host, const ww_augment_bg* bg_host,
+                          const ww_augment_rir* rir_host) {
+    std::vector<char> rec(size_t(call.n * augment_record_bytes(parts)));
+    AugStages st;
+    if (int rc = augment_prepare(plans_host, bg_host, rir_host, call.n, call.n_samples, call.bank_len, call.n_rirs, parts, rec.data(), &st))
+        return rc;
+    if (int rc = require_gfx950()) return rc;
+    return launch_augment(call, rec.data(), parts, st);
+}
+
+int64_t ww_augment_workspace_bytes(int64_t n_clips) {
+    if (int rc = check_n_clips(n_clips)) return rc;
+    return augment_workspace_bytes(n_clips, kClip, 0);
 }
 
 int ww_augment_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, const ww_augment_plan* plans_host,
                    float* out_dev, void* workspace_dev, ww_stream_t stream) {
-    if (n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (int rc = check_n_clips(n_clips)) return rc;
     if (int rc = check_pcm(pcm_dev, n_clips, clip_stride, kClip)) return rc;
     if (n_clips == 0) return WW_OK;
     if (!plans_host || !out_dev || !workspace_dev) return fail(WW_EINVAL, "null plan / output / workspace pointer");
     if ((reinterpret_cast<uintptr_t>(out_dev) & 15) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
         return fail(WW_EINVAL, "out_dev must be 16-byte and workspace_dev 256-byte aligned");
-    if (int rc = require_gfx950()) return rc;
-    return launch_augment(pcm_dev, n_clips, clip_stride, kClip, plans_host, out_dev, kClip, workspace_dev, static_cast<hipStream_t>(stream));
+    return augment_direct({pcm_dev, n_clips, clip_stride, kClip, out_dev, kClip, workspace_dev, static_cast<hipStream_t>(stream)}, 0, plans_host,
+                          nullptr, nullptr);
 }
 
-int64_t ww_augment_record_bytes(void) { return augment_record_bytes(); }
+int64_t ww_augment_record_bytes(void) { return augment_record_bytes(0); }
 
 int ww_augment_plans_prepare(const ww_augment_plan* plans_host, int64_t n_clips, void* records_host) {
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (int rc = check_n_clips(n_clips)) return rc;
     if (n_clips == 0) return WW_OK;
     if (!plans_host || !records_host) return fail(WW_EINVAL, "null plan / record pointer");
-    return augment_prepare(plans_host, n_clips, kClip, records_host, nullptr, nullptr);
+    return augment_prepare(plans_host, nullptr, nullptr, n_clips, kClip, 0, 0, 0, records_host, nullptr);
 }
 
 int ww_augment_records_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, const void* records_dev, float* out_dev,
                            void* workspace_dev, ww_stream_t stream) {
-    if (n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (int rc = check_n_clips(n_clips)) return rc;
     if (int rc = check_pcm(pcm_dev, n_clips, clip_stride, kClip)) return rc;
     if (n_clips == 0) return WW_OK;
     if (!records_dev || !out_dev || !workspace_dev) return fail(WW_EINVAL, "null record / output / workspace pointer");
     if ((reinterpret_cast<uintptr_t>(out_dev) & 15) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255) || (reinterpret_cast<uintptr_t>(records_dev) & 7))
         return fail(WW_EINVAL, "out_dev must be 16-byte, workspace_dev 256-byte and records_dev 8-byte aligned");
     if (int rc = require_gfx950()) return rc;
-    return launch_augment_records(pcm_dev, n_clips, clip_stride, kClip, records_dev, true, true, out_dev, kClip, workspace_dev,
-                                  static_cast<hipStream_t>(stream));
+    return launch_augment_records({pcm_dev, n_clips, clip_stride, kClip, out_dev, kClip, workspace_dev, static_cast<hipStream_t>(stream)},
+                                  records_dev, 0);
 }
 
 // ---- augmentation of clips of n_samples in [WW_MIN_CLIP_SAMPLES, WW_AUG_MAX_SAMPLES] (the 1 s entry points above are unchanged) ----
@@ -328,32 +345,46 @@ static int check_aug_samples(int64_t n_samples) {
                     WW_MIN_CLIP_SAMPLES, WW_AUG_MAX_SAMPLES);
     return WW_OK;
 }
-static int check_aug_rows(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* plans, float* out_dev,
-                          int64_t out_stride, void* workspace_dev) {
+static int check_aug_sizes(int64_t n_clips, int64_t n_samples) {
     if (int rc = check_aug_samples(n_samples)) return rc;
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
-    if (n_clips == 0) return WW_OK;
-    if (!pcm_dev || !plans || !out_dev || !workspace_dev) return fail(WW_EINVAL, "null pcm / plan / output / workspace pointer");
-    if (n_clips > 1 && (clip_stride < n_samples || out_stride < n_samples))
-        return fail(WW_EINVAL, "clip_stride %lld / out_stride %lld < n_samples %lld", (long long)clip_stride, (long long)out_stride,
-                    (long long)n_samples);
-    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 15) || (n_clips > 1 && (clip_stride & 3)))
-        return fail(WW_EINVAL, "pcm must be 16-byte aligned with clip_stride %% 4 == 0 (got %p, %lld)", (const void*)pcm_dev, (long long)clip_stride);
-    if ((reinterpret_cast<uintptr_t>(out_dev) & 3) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
+    return check_n_clips(n_clips);
+}
+// `plans`: the host plans of a direct call, or the device records of a *_records call
+static int check_aug_rows(const AugCall& c, const void* plans) {
+    if (int rc = check_aug_sizes(c.n, c.n_samples)) return rc;
+    if (c.n == 0) return WW_OK;
+    if (!c.pcm || !plans || !c.out || !c.workspace) return fail(WW_EINVAL, "null pcm / plan / output / workspace pointer");
+    if (c.n > 1 && (c.stride < c.n_samples || c.out_stride < c.n_samples))
+        return fail(WW_EINVAL, "clip_stride %lld / out_stride %lld < n_samples %lld", (long long)c.stride, (long long)c.out_stride,
+                    (long long)c.n_samples);
+    if ((reinterpret_cast<uintptr_t>(c.pcm) & 15) || (c.n > 1 && (c.stride & 3)))
+        return fail(WW_EINVAL, "pcm must be 16-byte aligned with clip_stride %% 4 == 0 (got %p, %lld)", (const void*)c.pcm, (long long)c.stride);
+    if ((reinterpret_cast<uintptr_t>(c.out) & 3) || (reinterpret_cast<uintptr_t>(c.workspace) & 255))
         return fail(WW_EINVAL, "out_dev must be 4-byte and workspace_dev 256-byte aligned");
     return WW_OK;
 }
+// The *_records calls of the lengths above: the checks, then nothing but launches
+static int augment_records(const AugCall& c, const void* records_dev, unsigned parts) {
+    if (int rc = check_aug_rows(c, records_dev)) return rc;
+    if (c.n == 0) return WW_OK;
+    if (reinterpret_cast<uintptr_t>(records_dev) & 7) return fail(WW_EINVAL, "records_dev must be 8-byte aligned");
+    if ((parts & kAugBg) && (c.bank_len < 0 || (c.bank_len > 0 && !c.bank)))
+        return fail(WW_EINVAL, "bank: null pointer or bank_len %lld < 0", (long long)c.bank_len);
+    if ((parts & kAugRir) && (c.n_rirs < 0 || (c.n_rirs > 0 && !c.spectra) || (reinterpret_cast<uintptr_t>(c.spectra) & 7)))
+        return fail(WW_EINVAL, "spectra: null or unaligned pointer, or n_rirs %lld < 0", (long long)c.n_rirs);
+    if (int rc = require_gfx950()) return rc;
+    return launch_augment_records(c, records_dev, parts);
+}
 
 int64_t ww_augment_n_workspace_bytes(int64_t n_clips, int64_t n_samples) {
-    if (int rc = check_aug_samples(n_samples)) return rc;
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
-    return augment_workspace_bytes(n_clips, n_samples);
+    if (int rc = check_aug_sizes(n_clips, n_samples)) return rc;
+    return augment_workspace_bytes(n_clips, n_samples, 0);
 }
 
 int ww_augment_workspace_layout(int64_t n_clips, int64_t n_samples, ww_augment_layout* layout_out) {
     if (n_samples != kClip)
         if (int rc = check_aug_samples(n_samples)) return rc;
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (int rc = check_n_clips(n_clips)) return rc;
     if (!layout_out) return fail(WW_EINVAL, "null layout pointer");
     *layout_out = augment_workspace_layout(n_clips, n_samples);
     return WW_OK;
@@ -361,29 +392,23 @@ int ww_augment_workspace_layout(int64_t n_clips, int64_t n_samples, ww_augment_l
 
 int ww_augment_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
                      float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream) {
-    if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, plans_host, out_dev, out_stride, workspace_dev)) return rc;
+    const AugCall c = {pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream)};
+    if (int rc = check_aug_rows(c, plans_host)) return rc;
     if (n_clips == 0) return WW_OK;
-    if (int rc = require_gfx950()) return rc;
-    return launch_augment(pcm_dev, n_clips, clip_stride, n_samples, plans_host, out_dev, out_stride, workspace_dev,
-                          static_cast<hipStream_t>(stream));
+    return augment_direct(c, 0, plans_host, nullptr, nullptr);
 }
 
 int ww_augment_plans_prepare_n(const ww_augment_plan* plans_host, int64_t n_clips, int64_t n_samples, void* records_host) {
-    if (int rc = check_aug_samples(n_samples)) return rc;
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (int rc = check_aug_sizes(n_clips, n_samples)) return rc;
     if (n_clips == 0) return WW_OK;
     if (!plans_host || !records_host) return fail(WW_EINVAL, "null plan / record pointer");
-    return augment_prepare(plans_host, n_clips, n_samples, records_host, nullptr, nullptr);
+    return augment_prepare(plans_host, nullptr, nullptr, n_clips, n_samples, 0, 0, 0, records_host, nullptr);
 }
 
 int ww_augment_records_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* records_dev,
                              float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream) {
-    if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, records_dev, out_dev, out_stride, workspace_dev)) return rc;
-    if (n_clips == 0) return WW_OK;
-    if (reinterpret_cast<uintptr_t>(records_dev) & 7) return fail(WW_EINVAL, "records_dev must be 8-byte aligned");
-    if (int rc = require_gfx950()) return rc;
-    return launch_augment_records(pcm_dev, n_clips, clip_stride, n_samples, records_dev, true, true, out_dev, out_stride, workspace_dev,
-                                  static_cast<hipStream_t>(stream));
+    return augment_records({pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream)},
+                           records_dev, 0);
 }
 
 // ---- background noise (the augmentation lengths above; the standalone mix at every inference length) ----
@@ -398,77 +423,73 @@ static int check_bg_args(int64_t n_clips, const ww_augment_bg* bg_host, const fl
 }
 
 int64_t ww_augment_bg_workspace_bytes(int64_t n_clips, int64_t n_samples) {
-    if (int rc = check_aug_samples(n_samples)) return rc;
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
-    return augment_bg_workspace_bytes(n_clips, n_samples);
+    if (int rc = check_aug_sizes(n_clips, n_samples)) return rc;
+    return augment_workspace_bytes(n_clips, n_samples, kAugBg);
 }
 
 int ww_augment_bg_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
                       const ww_augment_bg* bg_host, const float* bank_dev, int64_t bank_len, float* out_dev, int64_t out_stride,
                       void* workspace_dev, ww_stream_t stream) {
-    if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, plans_host, out_dev, out_stride, workspace_dev)) return rc;
+    const AugCall c = {pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream), bank_dev,
+                       bank_len};
+    if (int rc = check_aug_rows(c, plans_host)) return rc;
     if (n_clips == 0) return WW_OK;
     if (int rc = check_bg_args(n_clips, bg_host, bank_dev, bank_len)) return rc;
-    {   // every refusal before anything is launched (the launcher prepares the same records again)
-        std::vector<char> rec(size_t(n_clips) * size_t(augment_bg_record_bytes()));
-        if (int rc = augment_bg_prepare(plans_host, bg_host, n_clips, n_samples, bank_len, rec.data(), nullptr, nullptr, nullptr)) return rc;
-    }
-    if (int rc = require_gfx950()) return rc;
-    return launch_augment_bg(pcm_dev, n_clips, clip_stride, n_samples, plans_host, bg_host, bank_dev, bank_len, out_dev, out_stride,
-                             workspace_dev, static_cast<hipStream_t>(stream));
+    return augment_direct(c, kAugBg, plans_host, bg_host, nullptr);
 }
 
-int64_t ww_augment_bg_record_bytes(void) { return augment_bg_record_bytes(); }
+int64_t ww_augment_bg_record_bytes(void) { return augment_record_bytes(kAugBg); }
 
 int ww_augment_bg_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, int64_t n_clips, int64_t n_samples,
                           int64_t bank_len, void* records_host) {
-    if (int rc = check_aug_samples(n_samples)) return rc;
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (int rc = check_aug_sizes(n_clips, n_samples)) return rc;
     if (n_clips == 0) return WW_OK;
     if (!plans_host || !bg_host || !records_host) return fail(WW_EINVAL, "null plan / bg / record pointer");
     if (bank_len < 0) return fail(WW_EINVAL, "bank_len %lld < 0", (long long)bank_len);
-    return augment_bg_prepare(plans_host, bg_host, n_clips, n_samples, bank_len, records_host, nullptr, nullptr, nullptr);
+    return augment_prepare(plans_host, bg_host, nullptr, n_clips, n_samples, bank_len, 0, kAugBg, records_host, nullptr);
 }
 
 int ww_augment_bg_records_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* records_dev,
                               const float* bank_dev, int64_t bank_len, float* out_dev, int64_t out_stride, void* workspace_dev,
                               ww_stream_t stream) {
-    if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, records_dev, out_dev, out_stride, workspace_dev)) return rc;
-    if (n_clips == 0) return WW_OK;
-    if (reinterpret_cast<uintptr_t>(records_dev) & 7) return fail(WW_EINVAL, "records_dev must be 8-byte aligned");
-    if (bank_len < 0 || (bank_len > 0 && !bank_dev)) return fail(WW_EINVAL, "bank: null pointer or bank_len %lld < 0", (long long)bank_len);
-    if (int rc = require_gfx950()) return rc;
-    return launch_augment_bg_records(pcm_dev, n_clips, clip_stride, n_samples, records_dev, true, true, bank_dev, bank_len, out_dev, out_stride,
-                                     workspace_dev, static_cast<hipStream_t>(stream));
+    return augment_records({pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream), bank_dev,
+                            bank_len},
+                           records_dev, kAugBg);
+}
+
+// The standalone mix and reverb: rows of every inference length, 4-byte aligned (`what` names the call in the n_samples refusal)
+static int check_rows_4(const AugCall& c, const char* what) {
+    if (c.n_samples < WW_MIN_CLIP_SAMPLES || c.n_samples > WW_MAX_CLIP_SAMPLES)
+        return fail(WW_EINVAL, "n_samples %lld: the %s takes %d..%d samples (0.25 .. 2 s at 16 kHz)", (long long)c.n_samples, what,
+                    WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES);
+    if (int rc = check_n_clips(c.n)) return rc;
+    if (c.n == 0) return WW_OK;
+    if (!c.pcm || !c.out || !c.workspace) return fail(WW_EINVAL, "null pcm / output / workspace pointer");
+    if (c.n > 1 && (c.stride < c.n_samples || c.out_stride < c.n_samples))
+        return fail(WW_EINVAL, "clip_stride %lld / out_stride %lld < n_samples %lld", (long long)c.stride, (long long)c.out_stride,
+                    (long long)c.n_samples);
+    if ((reinterpret_cast<uintptr_t>(c.pcm) & 3) || (reinterpret_cast<uintptr_t>(c.out) & 3) || (reinterpret_cast<uintptr_t>(c.workspace) & 255))
+        return fail(WW_EINVAL, "pcm_dev / out_dev must be 4-byte and workspace_dev 256-byte aligned");
+    return WW_OK;
 }
 
 int64_t ww_mix_background_workspace_bytes(int64_t n_clips) {
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (int rc = check_n_clips(n_clips)) return rc;
     return mix_background_workspace_bytes(n_clips);
 }
 
 int ww_mix_background_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_bg* bg_host,
                           const float* bank_dev, int64_t bank_len, float* out_dev, int64_t out_stride, void* workspace_dev,
                           ww_stream_t stream) {
-    if (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_MAX_CLIP_SAMPLES)
-        return fail(WW_EINVAL, "n_samples %lld: the mix takes %d..%d samples (0.25 .. 2 s at 16 kHz)", (long long)n_samples,
-                    WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES);
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    const AugCall c = {pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream), bank_dev,
+                       bank_len};
+    if (int rc = check_rows_4(c, "mix")) return rc;
     if (n_clips == 0) return WW_OK;
-    if (!pcm_dev || !out_dev || !workspace_dev) return fail(WW_EINVAL, "null pcm / output / workspace pointer");
-    if (n_clips > 1 && (clip_stride < n_samples || out_stride < n_samples))
-        return fail(WW_EINVAL, "clip_stride %lld / out_stride %lld < n_samples %lld", (long long)clip_stride, (long long)out_stride,
-                    (long long)n_samples);
-    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 3) || (reinterpret_cast<uintptr_t>(out_dev) & 3) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
-        return fail(WW_EINVAL, "pcm_dev / out_dev must be 4-byte and workspace_dev 256-byte aligned");
     if (int rc = check_bg_args(n_clips, bg_host, bank_dev, bank_len)) return rc;
-    {
-        std::vector<char> rec(size_t(mix_background_workspace_bytes(n_clips)));
-        if (int rc = background_prepare(bg_host, n_clips, bank_len, rec.data(), nullptr)) return rc;
-    }
+    std::vector<char> rec(size_t(mix_background_workspace_bytes(n_clips)));
+    if (int rc = background_prepare(bg_host, n_clips, bank_len, rec.data(), nullptr)) return rc;
     if (int rc = require_gfx950()) return rc;
-    return launch_mix_background(pcm_dev, n_clips, clip_stride, n_samples, bg_host, bank_dev, bank_len, out_dev, out_stride, workspace_dev,
-                                 static_cast<hipStream_t>(stream));
+    return launch_mix_background(c, rec.data());
 }
 
 // ---- reverberation (the augmentation lengths above; the standalone reverb at every inference length) ----
@@ -508,84 +529,59 @@ int ww_rir_spectra_f32(const float* taps_dev, int64_t taps_len, const int64_t* o
 }
 
 int64_t ww_augment_rir_workspace_bytes(int64_t n_clips, int64_t n_samples) {
-    if (int rc = check_aug_samples(n_samples)) return rc;
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
-    return augment_rir_workspace_bytes(n_clips, n_samples);
+    if (int rc = check_aug_sizes(n_clips, n_samples)) return rc;
+    return augment_workspace_bytes(n_clips, n_samples, kAugBg | kAugRir);
 }
 
 int ww_augment_rir_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
                        const ww_augment_bg* bg_host, const float* bank_dev, int64_t bank_len, const ww_augment_rir* rir_host,
                        const float* spectra_dev, int64_t n_rirs, float* out_dev, int64_t out_stride, void* workspace_dev,
                        ww_stream_t stream) {
-    if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, plans_host, out_dev, out_stride, workspace_dev)) return rc;
+    const AugCall c = {pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream), bank_dev,
+                       bank_len, spectra_dev, n_rirs};
+    if (int rc = check_aug_rows(c, plans_host)) return rc;
     if (n_clips == 0) return WW_OK;
     if (bg_host)
         if (int rc = check_bg_args(n_clips, bg_host, bank_dev, bank_len)) return rc;
     if (int rc = check_rir_args(n_clips, rir_host, spectra_dev, n_rirs)) return rc;
-    {   // every refusal before anything is launched (the launcher prepares the same records again)
-        std::vector<char> rec(size_t(n_clips) * size_t(augment_rir_record_bytes()));
-        if (int rc = augment_rir_prepare(plans_host, bg_host, rir_host, n_clips, n_samples, bank_len, n_rirs, rec.data(), nullptr, nullptr,
-                                         nullptr, nullptr))
-            return rc;
-    }
-    if (int rc = require_gfx950()) return rc;
-    return launch_augment_rir(pcm_dev, n_clips, clip_stride, n_samples, plans_host, bg_host, bank_dev, bank_len, rir_host, spectra_dev, n_rirs,
-                              out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream));
+    return augment_direct(c, kAugBg | kAugRir, plans_host, bg_host, rir_host);
 }
 
-int64_t ww_augment_rir_record_bytes(void) { return augment_rir_record_bytes(); }
+int64_t ww_augment_rir_record_bytes(void) { return augment_record_bytes(kAugBg | kAugRir); }
 
 int ww_augment_rir_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, const ww_augment_rir* rir_host, int64_t n_clips,
                            int64_t n_samples, int64_t bank_len, int64_t n_rirs, void* records_host) {
-    if (int rc = check_aug_samples(n_samples)) return rc;
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (int rc = check_aug_sizes(n_clips, n_samples)) return rc;
     if (n_clips == 0) return WW_OK;
     if (!plans_host || !rir_host || !records_host) return fail(WW_EINVAL, "null plan / rir / record pointer");
     if (bank_len < 0 || n_rirs < 0) return fail(WW_EINVAL, "bank_len %lld / n_rirs %lld < 0", (long long)bank_len, (long long)n_rirs);
-    return augment_rir_prepare(plans_host, bg_host, rir_host, n_clips, n_samples, bank_len, n_rirs, records_host, nullptr, nullptr, nullptr,
-                               nullptr);
+    return augment_prepare(plans_host, bg_host, rir_host, n_clips, n_samples, bank_len, n_rirs, kAugBg | kAugRir, records_host, nullptr);
 }
 
 int ww_augment_rir_records_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const void* records_dev,
                                const float* bank_dev, int64_t bank_len, const float* spectra_dev, int64_t n_rirs, float* out_dev,
                                int64_t out_stride, void* workspace_dev, ww_stream_t stream) {
-    if (int rc = check_aug_rows(pcm_dev, n_clips, clip_stride, n_samples, records_dev, out_dev, out_stride, workspace_dev)) return rc;
-    if (n_clips == 0) return WW_OK;
-    if (reinterpret_cast<uintptr_t>(records_dev) & 7) return fail(WW_EINVAL, "records_dev must be 8-byte aligned");
-    if (bank_len < 0 || (bank_len > 0 && !bank_dev)) return fail(WW_EINVAL, "bank: null pointer or bank_len %lld < 0", (long long)bank_len);
-    if (n_rirs < 0 || (n_rirs > 0 && !spectra_dev) || (reinterpret_cast<uintptr_t>(spectra_dev) & 7))
-        return fail(WW_EINVAL, "spectra: null or unaligned pointer, or n_rirs %lld < 0", (long long)n_rirs);
-    if (int rc = require_gfx950()) return rc;
-    return launch_augment_rir_records(pcm_dev, n_clips, clip_stride, n_samples, records_dev, bank_dev, bank_len, spectra_dev, n_rirs, out_dev,
-                                      out_stride, workspace_dev, static_cast<hipStream_t>(stream));
+    return augment_records({pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream), bank_dev,
+                            bank_len, spectra_dev, n_rirs},
+                           records_dev, kAugBg | kAugRir);
 }
 
 int64_t ww_reverb_workspace_bytes(int64_t n_clips) {
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (int rc = check_n_clips(n_clips)) return rc;
     return reverb_workspace_bytes(n_clips);
 }
 
 int ww_reverb_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_rir* rir_host,
                   const float* spectra_dev, int64_t n_rirs, float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream) {
-    if (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_MAX_CLIP_SAMPLES)
-        return fail(WW_EINVAL, "n_samples %lld: the reverb takes %d..%d samples (0.25 .. 2 s at 16 kHz)", (long long)n_samples,
-                    WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES);
-    if (n_clips < 0 || n_clips > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    const AugCall c = {pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream), nullptr, 0,
+                       spectra_dev, n_rirs};
+    if (int rc = check_rows_4(c, "reverb")) return rc;
     if (n_clips == 0) return WW_OK;
-    if (!pcm_dev || !out_dev || !workspace_dev) return fail(WW_EINVAL, "null pcm / output / workspace pointer");
-    if (n_clips > 1 && (clip_stride < n_samples || out_stride < n_samples))
-        return fail(WW_EINVAL, "clip_stride %lld / out_stride %lld < n_samples %lld", (long long)clip_stride, (long long)out_stride,
-                    (long long)n_samples);
-    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 3) || (reinterpret_cast<uintptr_t>(out_dev) & 3) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
-        return fail(WW_EINVAL, "pcm_dev / out_dev must be 4-byte and workspace_dev 256-byte aligned");
     if (int rc = check_rir_args(n_clips, rir_host, spectra_dev, n_rirs)) return rc;
-    {
-        std::vector<char> rec(size_t(reverb_workspace_bytes(n_clips)));
-        if (int rc = rir_prepare(rir_host, n_clips, n_rirs, rec.data(), nullptr)) return rc;
-    }
+    std::vector<char> rec(size_t(reverb_workspace_bytes(n_clips)));
+    if (int rc = rir_prepare(rir_host, n_clips, n_rirs, rec.data(), nullptr)) return rc;
     if (int rc = require_gfx950()) return rc;
-    return launch_reverb(pcm_dev, n_clips, clip_stride, n_samples, rir_host, spectra_dev, n_rirs, out_dev, out_stride, workspace_dev,
-                         static_cast<hipStream_t>(stream));
+    return launch_reverb(c, rec.data());
 }
 
 int64_t ww_cnn_scratch_bytes(int64_t n, int32_t n_conv) { return cnn_scratch_bytes(n, n_conv); }

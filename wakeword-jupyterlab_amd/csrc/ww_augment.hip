@@ -609,8 +609,6 @@ __global__ __launch_bounds__(kMixThreads) void mix_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
-static int64_t up256(int64_t b) { return (b + 255) & ~int64_t(255); }
-
 static int64_t aug_row_host(int64_t n_samples) { return (n_samples + 3) & ~int64_t(3); }
 
 // The workspace's regions, in bytes -- the one definition: the size below, launch_records and the diagnostic ww_augment_workspace_layout
@@ -623,7 +621,7 @@ ww_augment_layout augment_workspace_layout(int64_t n, int64_t n_samples) {
     l.spec_clip_bytes = int64_t(kAugMaxOut) * l.spec_step_bytes;
     l.y_clip_bytes = int64_t(kAugYStride) * 4;
     l.record_bytes = int64_t(sizeof(AugDev));
-    l.records = 0;                                                  // (the slot ww_augment_f32 copies its records into)
+    l.records = 0;                                                  // (the slot the direct calls copy their AugDev records into)
     l.buf_a = l.records + up256(n * l.record_bytes);
     l.buf_b = l.buf_a + up256(n * l.row_bytes);
     l.spec = l.buf_b + up256(n * l.row_bytes);
@@ -632,28 +630,70 @@ ww_augment_layout augment_workspace_layout(int64_t n, int64_t n_samples) {
     return l;
 }
 
-int64_t augment_workspace_bytes(int64_t n, int64_t n_samples) { return augment_workspace_layout(n, n_samples).total_bytes; }
+// Where the BgDev and RirDev arrays of `parts` lie behind `first` bytes: packed behind the [n] AugDev of a records buffer, or in
+// 256-byte-rounded slots behind the plain workspace.  The one definition of both orders: the sizes, the prepare and the launchers read it.
+struct PartOffsets { int64_t bg, rir, end; };
+static PartOffsets part_offsets(int64_t first, int64_t n, unsigned parts, bool slots) {
+    const int64_t b = n * int64_t(sizeof(BgDev)), r = n * int64_t(sizeof(RirDev));
+    PartOffsets o;
+    o.bg = first;
+    o.rir = o.bg + (parts & kAugBg ? (slots ? up256(b) : b) : 0);
+    o.end = o.rir + (parts & kAugRir ? (slots ? up256(r) : r) : 0);
+    return o;
+}
+static PartOffsets record_offsets(int64_t n, unsigned parts) { return part_offsets(n * int64_t(sizeof(AugDev)), n, parts, false); }
+static PartOffsets slot_offsets(int64_t n, int64_t n_samples, unsigned parts) {
+    return part_offsets(augment_workspace_layout(n, n_samples).total_bytes, n, parts, true);
+}
 
-// Pinned staging for the per-clip records: two slots per device, each guarded by an event, so the call can return as soon as the
-// copy and the kernels are enqueued (round 1 synchronised the stream because the records lived in a pageable vector).
-struct PlanStage {
-    AugDev* host = nullptr;
-    size_t cap = 0;
-    hipEvent_t ev = nullptr;
-    bool in_use = false;
-};
-static std::mutex g_stage_mu;
-static PlanStage g_stage[16][2];
-static int g_stage_next[16] = {};
+int64_t augment_record_bytes(unsigned parts) { return record_offsets(1, parts).end; }
+int64_t augment_workspace_bytes(int64_t n, int64_t n_samples, unsigned parts) { return slot_offsets(n, n_samples, parts).end; }
 
+// ww_augment_bg -> BgDev, refusing a segment outside the bank, an empty file and a non-finite SNR (clips with enabled = 0: a zero record)
+int background_prepare(const ww_augment_bg* bg_host, int64_t n, int64_t bank_len, void* records_host, bool* any_out) {
+    BgDev* host = static_cast<BgDev*>(records_host);
+    bool any = false;
+    for (int64_t c = 0; c < n; ++c) {
+        const ww_augment_bg& b = bg_host[c];
+        BgDev d = {};
+        if (b.enabled) {
+            if (b.file_len <= 0) return fail(WW_EINVAL, "bg %lld: file_len %lld must be > 0", (long long)c, (long long)b.file_len);
+            if (b.file_offset < 0 || bank_len < 0 || b.file_offset > bank_len - b.file_len)
+                return fail(WW_EINVAL, "bg %lld: file [%lld, +%lld) outside the bank of %lld samples", (long long)c, (long long)b.file_offset,
+                            (long long)b.file_len, (long long)bank_len);
+            if (b.start < 0 || b.start >= b.file_len)
+                return fail(WW_EINVAL, "bg %lld: start %lld outside [0, %lld)", (long long)c, (long long)b.start, (long long)b.file_len);
+            if (!std::isfinite(b.snr_db)) return fail(WW_EINVAL, "bg %lld: snr_db must be finite", (long long)c);
+            d.off = b.file_offset;
+            d.len = b.file_len;
+            d.start = b.start;
+            d.snr_lin = std::pow(10.0, double(b.snr_db) / 10.0);
+            any = true;
+        }
+        host[c] = d;
+    }
+    if (any_out) *any_out = any;
+    return WW_OK;
+}
+
+// The records of `parts`, in the order rir, bg, plans (the first refusal of a batch with several faults is the first of that order).
 // plans -> the per-clip records the kernels read (librosa's lengths are host arithmetic: len(np.arange), round, ceil), for clips of
 // n_samples = N samples, T = 1 + N / 512 frames.  The rate bounds are the 1 s ones at every N (ceil(32 / rate) <= kAugMaxOut: the scratch
 // strides and the resampler's LDS table are sized by them); the upper bound is ceil(T / rate) >= 2.
-int augment_prepare(const ww_augment_plan* plans_host, int64_t n, int64_t n_samples, void* records_host, int* any_pitch_out,
-                    int* any_stretch_out) {
-    AugDev* host = static_cast<AugDev*>(records_host);
+int augment_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, const ww_augment_rir* rir_host, int64_t n,
+                    int64_t n_samples, int64_t bank_len, int64_t n_rirs, unsigned parts, void* records_host, AugStages* stages_out) {
+    char* rec = static_cast<char*>(records_host);
+    const PartOffsets at = record_offsets(n, parts);
+    AugStages st = {};
+    if (parts & kAugRir)
+        if (int rc = rir_prepare(rir_host, n, n_rirs, rec + at.rir, &st.rir)) return rc;
+    if ((parts & kAugBg) && bg_host) {
+        if (int rc = background_prepare(bg_host, n, bank_len, rec + at.bg, &st.bg)) return rc;
+    } else if (parts & kAugBg) {
+        std::memset(rec + at.bg, 0, size_t(n) * sizeof(BgDev));
+    }
+    AugDev* host = reinterpret_cast<AugDev*>(rec);
     const int N = int(n_samples), T = 1 + N / kHop;
-    bool any_pitch = false, any_stretch = false;
     for (int64_t c = 0; c < n; ++c) {
         const ww_augment_plan& p = plans_host[c];
         AugDev d = {};
@@ -676,7 +716,7 @@ int augment_prepare(const ww_augment_plan* plans_host, int64_t n, int64_t n_samp
             d.p_len = int32_t(std::nearbyint(double(N) / p.pitch_rate));          // Python round(): half to even
             d.p_ratio = double(WW_SAMPLE_RATE) / (double(WW_SAMPLE_RATE) / p.pitch_rate);
             d.p_res = int32_t(std::ceil(double(d.p_len) * d.p_ratio));
-            any_pitch = true;
+            st.pitch = true;
         }
         if (p.stretch_rate != 0.0) {
             if (int rc = check(p.stretch_rate, "stretch")) return rc;
@@ -687,30 +727,27 @@ int augment_prepare(const ww_augment_plan* plans_host, int64_t n, int64_t n_samp
             if (p.crop_start < 0 || p.crop_start > over)
                 return fail(WW_EINVAL, "plan %lld: crop_start %d outside [0, %d] for clips of %d samples", (long long)c, p.crop_start, over, N);
             d.crop = p.crop_start;
-            any_stretch = true;
+            st.stretch = true;
         }
         host[c] = d;
     }
-    if (any_pitch_out) *any_pitch_out = any_pitch;
-    if (any_stretch_out) *any_stretch_out = any_stretch;
+    if (stages_out) *stages_out = st;
     return WW_OK;
 }
-int64_t augment_record_bytes() { return int64_t(sizeof(AugDev)); }
 
-// The kernels alone, on records already in device memory: nothing but launches on `stream` (capturable into a hipGraph).  A stage whose
-// flag is off for a clip copies that clip through, so both stages may always be launched (what a captured graph must do).
-// With `rir` (reverb records) reverb_kernel (ww_reverb.hip) runs after the stretch; with `bg` (background records) the last launch is
-// mix_kernel, which adds the background and then the same Gaussian noise.
+// The kernels alone, on records already in device memory: nothing but launches on the call's stream (capturable into a hipGraph).  A
+// stage whose flag is off for a clip copies that clip through, so both vocoder stages may always be launched (what a captured graph must
+// do).  With `rir` (reverb records) reverb_kernel (ww_reverb.hip) runs after the stretch; with `bg` (background records) the last launch
+// is mix_kernel, which adds the background and then the same Gaussian noise, otherwise noise_kernel.
 template <int kN>
-static int launch_records(const float* pcm, int64_t n, int64_t stride, int n_samples, const AugDev* plan, bool any_pitch, bool any_stretch,
-                          float* out, int64_t out_stride, void* workspace, hipStream_t stream, const BgDev* bg = nullptr,
-                          const float* bank = nullptr, int64_t bank_len = 0, const RirDev* rir = nullptr, const float* spectra = nullptr,
-                          int64_t n_rirs = 0) {
+static int launch_records(const AugCall& c, const AugDev* plan, const BgDev* bg, const RirDev* rir, bool any_pitch, bool any_stretch) {
     const LogmelTables* tb = device_tables();
     if (!tb) return WW_EHIP;
-    const ww_augment_layout lay = augment_workspace_layout(n, n_samples);
+    const int64_t n = c.n;
+    const hipStream_t stream = c.stream;
+    const ww_augment_layout lay = augment_workspace_layout(n, c.n_samples);
     const int64_t row = lay.row_bytes / 4;
-    char* w = static_cast<char*>(workspace);
+    char* w = static_cast<char*>(c.workspace);
     float* bufA = reinterpret_cast<float*>(w + lay.buf_a);
     float* bufB = reinterpret_cast<float*>(w + lay.buf_b);
     float2* S = reinterpret_cast<float2*>(w + lay.spec);
@@ -728,9 +765,9 @@ static int launch_records(const float* pcm, int64_t n, int64_t stride, int n_sam
             attr[dev] = true;
         }
     }
-    const int nn = n_samples;
+    const int nn = int(c.n_samples);
     const dim3 egrid(unsigned((row / 4 + 255) / 256), unsigned(n));
-    hipLaunchKernelGGL(roll_kernel<kN>, egrid, dim3(256), 0, stream, pcm, stride, plan, bufA, nn);
+    hipLaunchKernelGGL(roll_kernel<kN>, egrid, dim3(256), 0, stream, c.pcm, c.stride, plan, bufA, nn);
     float* cur = bufA;
     float* other = bufB;
     if (any_pitch) {
@@ -746,103 +783,37 @@ static int launch_records(const float* pcm, int64_t n, int64_t stride, int n_sam
         float* t = cur; cur = other; other = t;
     }
     if (rir) {
-        if (int rc = launch_reverb_records(cur, row, n, nn, rir, reinterpret_cast<const float2*>(spectra), n_rirs, other, row, stream)) return rc;
+        if (int rc = launch_reverb_records(cur, row, n, nn, rir, reinterpret_cast<const float2*>(c.spectra), c.n_rirs, other, row, stream))
+            return rc;
         float* t = cur; cur = other; other = t;
     }
     if (bg)
-        hipLaunchKernelGGL((mix_kernel<kN, 16, true>), dim3(unsigned(n)), dim3(kMixThreads), 0, stream, cur, row, plan, bg, bank, bank_len, out,
-                           out_stride, nn);
+        hipLaunchKernelGGL((mix_kernel<kN, 16, true>), dim3(unsigned(n)), dim3(kMixThreads), 0, stream, cur, row, plan, bg, c.bank, c.bank_len,
+                           c.out, c.out_stride, nn);
     else
-        hipLaunchKernelGGL(noise_kernel<kN>, egrid, dim3(256), 0, stream, cur, plan, out, out_stride, nn);
+        hipLaunchKernelGGL(noise_kernel<kN>, egrid, dim3(256), 0, stream, cur, plan, c.out, c.out_stride, nn);
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
 
-// 16000 samples run the compile-time 1 s instance (the kernels the 1 s entry points always ran), every other length the run-time one
-int launch_augment_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, bool any_pitch,
-                           bool any_stretch, float* out, int64_t out_stride, void* workspace, hipStream_t stream) {
-    if (n == 0) return WW_OK;
-    const AugDev* plan = static_cast<const AugDev*>(records_dev);
-    if (n_samples == kClip)
-        return launch_records<kClip>(pcm, n, stride, kClip, plan, any_pitch, any_stretch, out, out_stride, workspace, stream);
-    return launch_records<0>(pcm, n, stride, int(n_samples), plan, any_pitch, any_stretch, out, out_stride, workspace, stream);
+// 16000 samples run the compile-time 1 s instance (the kernels the 1 s entry points always ran), every other length the run-time one.
+// bg / rir NULL: that stage is not launched
+static int launch_arrays(const AugCall& c, const void* plan, const void* bg, const void* rir, bool any_pitch, bool any_stretch) {
+    if (c.n == 0) return WW_OK;
+    const AugDev* p = static_cast<const AugDev*>(plan);
+    const BgDev* b = static_cast<const BgDev*>(bg);
+    const RirDev* r = static_cast<const RirDev*>(rir);
+    return c.n_samples == kClip ? launch_records<kClip>(c, p, b, r, any_pitch, any_stretch) : launch_records<0>(c, p, b, r, any_pitch, any_stretch);
 }
 
-int launch_augment(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host, float* out,
-                   int64_t out_stride, void* workspace, hipStream_t stream) {
-    if (n == 0) return WW_OK;
-    std::vector<AugDev> host(static_cast<size_t>(n));
-    int any_pitch = 0, any_stretch = 0;
-    if (int rc = augment_prepare(plans_host, n, n_samples, host.data(), &any_pitch, &any_stretch)) return rc;
-    AugDev* plan = reinterpret_cast<AugDev*>(workspace);
-    {
-        int dev = 0;
-        WW_HIP(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 16) return fail(WW_EUNSUPPORTED, "device ordinal %d out of range", dev);
-        std::lock_guard<std::mutex> lock(g_stage_mu);
-        PlanStage& st = g_stage[dev][g_stage_next[dev]];
-        g_stage_next[dev] ^= 1;
-        if (st.in_use) WW_HIP(hipEventSynchronize(st.ev));          // the copy that last read this slot (two calls ago) must be done
-        if (st.cap < size_t(n)) {
-            if (st.host) WW_HIP(hipHostFree(st.host));
-            st.host = nullptr;
-            st.cap = 0;
-            WW_HIP(hipHostMalloc(reinterpret_cast<void**>(&st.host), size_t(n) * sizeof(AugDev), hipHostMallocDefault));
-            st.cap = size_t(n);
-        }
-        if (!st.ev) WW_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
-        std::memcpy(st.host, host.data(), size_t(n) * sizeof(AugDev));
-        WW_HIP(hipMemcpyAsync(plan, st.host, size_t(n) * sizeof(AugDev), hipMemcpyHostToDevice, stream));
-        WW_HIP(hipEventRecord(st.ev, stream));
-        st.in_use = true;
-    }
-    return launch_augment_records(pcm, n, stride, n_samples, plan, any_pitch != 0, any_stretch != 0, out, out_stride, workspace, stream);
+int launch_augment_records(const AugCall& c, const void* records_dev, unsigned parts) {
+    const char* rec = static_cast<const char*>(records_dev);
+    const PartOffsets at = record_offsets(c.n, parts);
+    return launch_arrays(c, rec, parts & kAugBg ? rec + at.bg : nullptr, parts & kAugRir ? rec + at.rir : nullptr, true, true);
 }
 
-
-// ---- background noise -------------------------------------------------------------------------------------------------------------------
-int64_t augment_bg_record_bytes() { return int64_t(sizeof(AugDev) + sizeof(BgDev)); }
-
-int64_t augment_bg_workspace_bytes(int64_t n, int64_t n_samples) {
-    return augment_workspace_bytes(n, n_samples) + up256(n * int64_t(sizeof(BgDev)));
-}
-
-// ww_augment_bg -> BgDev, refusing a segment outside the bank, an empty file and a non-finite SNR (clips with enabled = 0: a zero record)
-int background_prepare(const ww_augment_bg* bg_host, int64_t n, int64_t bank_len, void* records_host, int* any_bg_out) {
-    BgDev* host = static_cast<BgDev*>(records_host);
-    bool any = false;
-    for (int64_t c = 0; c < n; ++c) {
-        const ww_augment_bg& b = bg_host[c];
-        BgDev d = {};
-        if (b.enabled) {
-            if (b.file_len <= 0) return fail(WW_EINVAL, "bg %lld: file_len %lld must be > 0", (long long)c, (long long)b.file_len);
-            if (b.file_offset < 0 || bank_len < 0 || b.file_offset > bank_len - b.file_len)
-                return fail(WW_EINVAL, "bg %lld: file [%lld, +%lld) outside the bank of %lld samples", (long long)c, (long long)b.file_offset,
-                            (long long)b.file_len, (long long)bank_len);
-            if (b.start < 0 || b.start >= b.file_len)
-                return fail(WW_EINVAL, "bg %lld: start %lld outside [0, %lld)", (long long)c, (long long)b.start, (long long)b.file_len);
-            if (!std::isfinite(b.snr_db)) return fail(WW_EINVAL, "bg %lld: snr_db must be finite", (long long)c);
-            d.off = b.file_offset;
-            d.len = b.file_len;
-            d.start = b.start;
-            d.snr_lin = std::pow(10.0, double(b.snr_db) / 10.0);
-            any = true;
-        }
-        host[c] = d;
-    }
-    if (any_bg_out) *any_bg_out = any;
-    return WW_OK;
-}
-
-// records = [n] AugDev, then [n] BgDev (ww_augment_bg_record_bytes() per clip)
-int augment_bg_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, int64_t n, int64_t n_samples, int64_t bank_len,
-                       void* records_host, int* any_pitch_out, int* any_stretch_out, int* any_bg_out) {
-    if (int rc = background_prepare(bg_host, n, bank_len, static_cast<char*>(records_host) + n * int64_t(sizeof(AugDev)), any_bg_out)) return rc;
-    return augment_prepare(plans_host, n, n_samples, records_host, any_pitch_out, any_stretch_out);
-}
-
-// Pinned staging for the background calls' records, as PlanStage (two slots per device, each guarded by an event) but sized in bytes;
-// `pieces` consecutive ranges of the staged bytes go to their own device addresses
+// Pinned staging for host records: two slots per device, each guarded by an event, so a call can return as soon as its copies and
+// kernels are enqueued.  Every call family shares the slots.
 struct ByteStage {
     void* host = nullptr;
     size_t cap = 0;
@@ -853,7 +824,7 @@ static std::mutex g_bstage_mu;
 static ByteStage g_bstage[16][2];
 static int g_bstage_next[16] = {};
 
-int stage_to_device(const void* src, const size_t* sizes, void* const* dst, int pieces, hipStream_t stream) {
+int stage_to_device(const void* const* src, const size_t* sizes, void* const* dst, int pieces, hipStream_t stream) {
     size_t total = 0;
     for (int i = 0; i < pieces; ++i) total += sizes[i];
     int dev = 0;
@@ -862,7 +833,7 @@ int stage_to_device(const void* src, const size_t* sizes, void* const* dst, int 
     std::lock_guard<std::mutex> lock(g_bstage_mu);
     ByteStage& st = g_bstage[dev][g_bstage_next[dev]];
     g_bstage_next[dev] ^= 1;
-    if (st.in_use) WW_HIP(hipEventSynchronize(st.ev));
+    if (st.in_use) WW_HIP(hipEventSynchronize(st.ev));             // the copies that last read this slot (two calls ago) must be done
     if (st.cap < total) {
         if (st.host) WW_HIP(hipHostFree(st.host));
         st.host = nullptr;
@@ -871,9 +842,9 @@ int stage_to_device(const void* src, const size_t* sizes, void* const* dst, int 
         st.cap = total;
     }
     if (!st.ev) WW_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
-    std::memcpy(st.host, src, total);
     size_t at = 0;
     for (int i = 0; i < pieces; ++i) {
+        std::memcpy(static_cast<char*>(st.host) + at, src[i], sizes[i]);
         WW_HIP(hipMemcpyAsync(dst[i], static_cast<char*>(st.host) + at, sizes[i], hipMemcpyHostToDevice, stream));
         at += sizes[i];
     }
@@ -882,130 +853,48 @@ int stage_to_device(const void* src, const size_t* sizes, void* const* dst, int 
     return WW_OK;
 }
 
-int launch_augment_bg_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, bool any_pitch,
-                              bool any_stretch, const float* bank, int64_t bank_len, float* out, int64_t out_stride, void* workspace,
-                              hipStream_t stream) {
-    if (n == 0) return WW_OK;
-    const AugDev* plan = static_cast<const AugDev*>(records_dev);
-    const BgDev* bg = reinterpret_cast<const BgDev*>(static_cast<const char*>(records_dev) + n * int64_t(sizeof(AugDev)));
-    if (n_samples == kClip)
-        return launch_records<kClip>(pcm, n, stride, kClip, plan, any_pitch, any_stretch, out, out_stride, workspace, stream, bg, bank, bank_len);
-    return launch_records<0>(pcm, n, stride, int(n_samples), plan, any_pitch, any_stretch, out, out_stride, workspace, stream, bg, bank,
-                             bank_len);
-}
-
-// The direct call: the records staged into the workspace (AugDev in the slot launch_augment uses, BgDev past augment_workspace_bytes); a
-// batch without background runs launch_augment's launches (noise_kernel last), one with background ends in mix_kernel instead
-int launch_augment_bg(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host,
-                      const ww_augment_bg* bg_host, const float* bank, int64_t bank_len, float* out, int64_t out_stride, void* workspace,
-                      hipStream_t stream) {
-    if (n == 0) return WW_OK;
-    const size_t rb = size_t(n) * sizeof(AugDev), bb = size_t(n) * sizeof(BgDev);
-    std::vector<char> host(rb + bb);
-    int any_pitch = 0, any_stretch = 0, any_bg = 0;
-    if (int rc = augment_bg_prepare(plans_host, bg_host, n, n_samples, bank_len, host.data(), &any_pitch, &any_stretch, &any_bg)) return rc;
-    AugDev* plan = static_cast<AugDev*>(workspace);
-    BgDev* bg = reinterpret_cast<BgDev*>(static_cast<char*>(workspace) + augment_workspace_bytes(n, n_samples));
-    const size_t sizes[2] = {rb, bb};
-    void* const dst[2] = {plan, bg};
-    if (int rc = stage_to_device(host.data(), sizes, dst, any_bg ? 2 : 1, stream)) return rc;
-    if (n_samples == kClip)
-        return launch_records<kClip>(pcm, n, stride, kClip, plan, any_pitch != 0, any_stretch != 0, out, out_stride, workspace, stream,
-                                     any_bg ? bg : nullptr, bank, bank_len);
-    return launch_records<0>(pcm, n, stride, int(n_samples), plan, any_pitch != 0, any_stretch != 0, out, out_stride, workspace, stream,
-                             any_bg ? bg : nullptr, bank, bank_len);
+// The direct calls: a stage no clip uses is neither staged nor launched, so a batch without background or reverb is one copy and the
+// plain launches (noise_kernel last) through every entry point
+int launch_augment(const AugCall& c, const void* records_host, unsigned parts, AugStages st) {
+    if (c.n == 0) return WW_OK;
+    const char* h = static_cast<const char*>(records_host);
+    char* w = static_cast<char*>(c.workspace);
+    const PartOffsets from = record_offsets(c.n, parts), to = slot_offsets(c.n, c.n_samples, parts);
+    const size_t n = size_t(c.n);
+    const void* src[3] = {h};
+    size_t sizes[3] = {n * sizeof(AugDev)};
+    void* dst[3] = {w};
+    int pieces = 1;
+    if (st.bg) { src[pieces] = h + from.bg; sizes[pieces] = n * sizeof(BgDev); dst[pieces++] = w + to.bg; }
+    if (st.rir) { src[pieces] = h + from.rir; sizes[pieces] = n * sizeof(RirDev); dst[pieces++] = w + to.rir; }
+    if (int rc = stage_to_device(src, sizes, dst, pieces, c.stream)) return rc;
+    return launch_arrays(c, w, st.bg ? w + to.bg : nullptr, st.rir ? w + to.rir : nullptr, st.pitch, st.stretch);
 }
 
 int64_t mix_background_workspace_bytes(int64_t n) { return up256(n * int64_t(sizeof(BgDev))); }
 
 // The mix alone (no Gaussian noise) on clips of 4000 .. 32000 samples: 16000 runs the 1 s instance, up to 16384 the run-time one with 16
 // samples per thread, longer clips 32 per thread
-int launch_mix_background(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_bg* bg_host, const float* bank,
-                          int64_t bank_len, float* out, int64_t out_stride, void* workspace, hipStream_t stream) {
-    if (n == 0) return WW_OK;
-    std::vector<BgDev> host(static_cast<size_t>(n));
-    if (int rc = background_prepare(bg_host, n, bank_len, host.data(), nullptr)) return rc;
-    BgDev* bg = static_cast<BgDev*>(workspace);
-    const size_t sizes[1] = {size_t(n) * sizeof(BgDev)};
-    void* const dst[1] = {bg};
-    if (int rc = stage_to_device(host.data(), sizes, dst, 1, stream)) return rc;
-    const int nn = int(n_samples);
+int launch_mix_background(const AugCall& c, const void* records_host) {
+    if (c.n == 0) return WW_OK;
+    BgDev* bg = static_cast<BgDev*>(c.workspace);
+    const size_t bytes = size_t(c.n) * sizeof(BgDev);
+    void* const dst = bg;
+    if (int rc = stage_to_device(&records_host, &bytes, &dst, 1, c.stream)) return rc;
+    const int nn = int(c.n_samples);
     const AugDev* no_plan = nullptr;
-    if (n_samples == kClip)
-        hipLaunchKernelGGL((mix_kernel<kClip, 16, false>), dim3(unsigned(n)), dim3(kMixThreads), 0, stream, pcm, stride, no_plan, bg, bank, bank_len,
-                           out, out_stride, nn);
-    else if (n_samples <= 16 * kMixThreads)
-        hipLaunchKernelGGL((mix_kernel<0, 16, false>), dim3(unsigned(n)), dim3(kMixThreads), 0, stream, pcm, stride, no_plan, bg, bank, bank_len, out,
-                           out_stride, nn);
+    const dim3 grid = dim3(unsigned(c.n)), block = dim3(kMixThreads);
+    if (c.n_samples == kClip)
+        hipLaunchKernelGGL((mix_kernel<kClip, 16, false>), grid, block, 0, c.stream, c.pcm, c.stride, no_plan, bg, c.bank, c.bank_len, c.out,
+                           c.out_stride, nn);
+    else if (c.n_samples <= 16 * kMixThreads)
+        hipLaunchKernelGGL((mix_kernel<0, 16, false>), grid, block, 0, c.stream, c.pcm, c.stride, no_plan, bg, c.bank, c.bank_len, c.out,
+                           c.out_stride, nn);
     else
-        hipLaunchKernelGGL((mix_kernel<0, 32, false>), dim3(unsigned(n)), dim3(kMixThreads), 0, stream, pcm, stride, no_plan, bg, bank, bank_len, out,
-                           out_stride, nn);
+        hipLaunchKernelGGL((mix_kernel<0, 32, false>), grid, block, 0, c.stream, c.pcm, c.stride, no_plan, bg, c.bank, c.bank_len, c.out,
+                           c.out_stride, nn);
     WW_HIP(hipGetLastError());
     return WW_OK;
-}
-
-// ---- background + reverb ----------------------------------------------------------------------------------------------------------------
-int64_t augment_rir_record_bytes() { return int64_t(sizeof(AugDev) + sizeof(BgDev) + sizeof(RirDev)); }
-
-int64_t augment_rir_workspace_bytes(int64_t n, int64_t n_samples) {
-    return augment_bg_workspace_bytes(n, n_samples) + up256(n * int64_t(sizeof(RirDev)));
-}
-
-// records = [n] AugDev, [n] BgDev, [n] RirDev (ww_augment_rir_record_bytes() per clip); bg_host NULL = no background
-int augment_rir_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, const ww_augment_rir* rir_host, int64_t n,
-                        int64_t n_samples, int64_t bank_len, int64_t n_rirs, void* records_host, int* any_pitch_out, int* any_stretch_out,
-                        int* any_bg_out, int* any_rir_out) {
-    char* rec = static_cast<char*>(records_host);
-    if (int rc = rir_prepare(rir_host, n, n_rirs, rec + n * int64_t(sizeof(AugDev) + sizeof(BgDev)), any_rir_out)) return rc;
-    if (bg_host) {
-        if (int rc = background_prepare(bg_host, n, bank_len, rec + n * int64_t(sizeof(AugDev)), any_bg_out)) return rc;
-    } else {
-        std::memset(rec + n * int64_t(sizeof(AugDev)), 0, size_t(n) * sizeof(BgDev));
-        if (any_bg_out) *any_bg_out = 0;
-    }
-    return augment_prepare(plans_host, n, n_samples, records_host, any_pitch_out, any_stretch_out);
-}
-
-int launch_augment_rir_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, const float* bank,
-                               int64_t bank_len, const float* spectra, int64_t n_rirs, float* out, int64_t out_stride, void* workspace,
-                               hipStream_t stream) {
-    if (n == 0) return WW_OK;
-    const char* rec = static_cast<const char*>(records_dev);
-    const AugDev* plan = reinterpret_cast<const AugDev*>(rec);
-    const BgDev* bg = reinterpret_cast<const BgDev*>(rec + n * int64_t(sizeof(AugDev)));
-    const RirDev* rir = reinterpret_cast<const RirDev*>(rec + n * int64_t(sizeof(AugDev) + sizeof(BgDev)));
-    if (n_samples == kClip)
-        return launch_records<kClip>(pcm, n, stride, kClip, plan, true, true, out, out_stride, workspace, stream, bg, bank, bank_len, rir,
-                                     spectra, n_rirs);
-    return launch_records<0>(pcm, n, stride, int(n_samples), plan, true, true, out, out_stride, workspace, stream, bg, bank, bank_len, rir,
-                             spectra, n_rirs);
-}
-
-// The direct call: AugDev and BgDev staged as launch_augment_bg stages them, RirDev past augment_bg_workspace_bytes; a stage no clip
-// uses is not launched (with every reverb off the launches are launch_augment_bg's)
-int launch_augment_rir(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host,
-                       const ww_augment_bg* bg_host, const float* bank, int64_t bank_len, const ww_augment_rir* rir_host, const float* spectra,
-                       int64_t n_rirs, float* out, int64_t out_stride, void* workspace, hipStream_t stream) {
-    if (n == 0) return WW_OK;
-    const size_t rb = size_t(n) * sizeof(AugDev), bb = size_t(n) * sizeof(BgDev), vb = size_t(n) * sizeof(RirDev);
-    std::vector<char> host(rb + bb + vb);
-    int any_pitch = 0, any_stretch = 0, any_bg = 0, any_rir = 0;
-    if (int rc = augment_rir_prepare(plans_host, bg_host, rir_host, n, n_samples, bank_len, n_rirs, host.data(), &any_pitch, &any_stretch,
-                                     &any_bg, &any_rir))
-        return rc;
-    AugDev* plan = static_cast<AugDev*>(workspace);
-    BgDev* bg = reinterpret_cast<BgDev*>(static_cast<char*>(workspace) + augment_workspace_bytes(n, n_samples));
-    RirDev* rir = reinterpret_cast<RirDev*>(static_cast<char*>(workspace) + augment_bg_workspace_bytes(n, n_samples));
-    const size_t sizes[3] = {rb, bb, vb};
-    void* const dst[3] = {plan, bg, rir};
-    if (int rc = stage_to_device(host.data(), sizes, dst, 3, stream)) return rc;
-    const BgDev* bgp = any_bg ? bg : nullptr;
-    const RirDev* rp = any_rir ? rir : nullptr;
-    if (n_samples == kClip)
-        return launch_records<kClip>(pcm, n, stride, kClip, plan, any_pitch != 0, any_stretch != 0, out, out_stride, workspace, stream, bgp, bank,
-                                     bank_len, rp, spectra, n_rirs);
-    return launch_records<0>(pcm, n, stride, int(n_samples), plan, any_pitch != 0, any_stretch != 0, out, out_stride, workspace, stream, bgp,
-                             bank, bank_len, rp, spectra, n_rirs);
 }
 
 }  // namespace ww

@@ -130,61 +130,54 @@ int launch_events_step(const float* prob, int n_mics, int smooth, float threshol
 // quiet bands sit on the f32 FFT's rounding floor are redone in f64)
 int logmel_math_mode();
 void set_logmel_math_mode(int mode);
-// augmentation of clips of n_samples samples: 16000 (the 1 s entry points) or 4000 .. 16383 (the *_n entry points; the callers check the range)
-int launch_augment(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host, float* out,
-                   int64_t out_stride, void* workspace, hipStream_t stream);
-int64_t augment_workspace_bytes(int64_t n, int64_t n_samples);
+// ---- augmentation host path (ww_augment.hip, ww_reverb.hip): the entry points check N and the pointers, the prepare functions check the
+// per-clip entries, both before any launch.  n_samples = 16000 (the 1 s entry points) or 4000 .. 16383 (the *_n, bg and rir ones).
+inline int64_t up256(int64_t b) { return (b + 255) & ~int64_t(255); }
+// Which record arrays a call carries.  A records buffer is [n] AugDev, then [n] BgDev with kAugBg, then [n] RirDev with kAugRir, back to
+// back; the workspace is the plain workspace followed by a 256-byte-rounded slot for each of the two in the same order.
+enum : unsigned { kAugBg = 1, kAugRir = 2 };
+int64_t augment_record_bytes(unsigned parts);                                    // per clip
+int64_t augment_workspace_bytes(int64_t n, int64_t n_samples, unsigned parts);
 ww_augment_layout augment_workspace_layout(int64_t n, int64_t n_samples);
-int augment_prepare(const ww_augment_plan* plans_host, int64_t n, int64_t n_samples, void* records_host, int* any_pitch_out,
-                    int* any_stretch_out);
-int64_t augment_record_bytes();
-int launch_augment_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, bool any_pitch,
-                           bool any_stretch, float* out, int64_t out_stride, void* workspace, hipStream_t stream);
-// background noise (ww_augment.hip): the callers check N and the pointers; the bg records are checked here, before any launch
-int64_t augment_bg_workspace_bytes(int64_t n, int64_t n_samples);
-int64_t augment_bg_record_bytes();
-int background_prepare(const ww_augment_bg* bg_host, int64_t n, int64_t bank_len, void* records_host, int* any_bg_out);
-int augment_bg_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, int64_t n, int64_t n_samples, int64_t bank_len,
-                       void* records_host, int* any_pitch_out, int* any_stretch_out, int* any_bg_out);
-int launch_augment_bg(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host,
-                      const ww_augment_bg* bg_host, const float* bank, int64_t bank_len, float* out, int64_t out_stride, void* workspace,
-                      hipStream_t stream);
-int launch_augment_bg_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, bool any_pitch,
-                              bool any_stretch, const float* bank, int64_t bank_len, float* out, int64_t out_stride, void* workspace,
-                              hipStream_t stream);
-int64_t mix_background_workspace_bytes(int64_t n);
-int launch_mix_background(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_bg* bg_host, const float* bank,
-                          int64_t bank_len, float* out, int64_t out_stride, void* workspace, hipStream_t stream);
-// pinned staging of host records into device memory (ww_augment.hip): `pieces` consecutive byte ranges of src to their own addresses
-int stage_to_device(const void* src, const size_t* sizes, void* const* dst, int pieces, hipStream_t stream);
-// reverberation (ww_reverb.hip): the callers check N and the pointers; the rir records are checked here, before any launch
+struct AugStages { bool pitch, stretch, bg, rir; };    // the stages that some clip of the batch uses
+struct AugCall {           // the device side of one call; bank / spectra stay zero where the call has none
+    const float* pcm;
+    int64_t n, stride, n_samples;
+    float* out;
+    int64_t out_stride;
+    void* workspace;
+    hipStream_t stream;
+    const float* bank;
+    int64_t bank_len;
+    const float* spectra;
+    int64_t n_rirs;
+};
 struct RirDev {            // one per clip, derived on the host from ww_augment_rir
     int64_t index;         // the RIR's spectrum; -1 = no reverb for this clip
     int32_t dpos;          // direct-path position within the kept taps
     int32_t pad_;
 };
-int64_t rir_record_bytes();
-int rir_prepare(const ww_augment_rir* rir_host, int64_t n, int64_t n_rirs, void* records_host, int* any_out);
+int background_prepare(const ww_augment_bg* bg_host, int64_t n, int64_t bank_len, void* records_host, bool* any_out);
+int rir_prepare(const ww_augment_rir* rir_host, int64_t n, int64_t n_rirs, void* records_host, bool* any_out);
+// plans (+ bg with kAugBg, + rir with kAugRir) -> a records buffer of `parts`; bg_host NULL with kAugBg: zero records, no background
+int augment_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, const ww_augment_rir* rir_host, int64_t n,
+                    int64_t n_samples, int64_t bank_len, int64_t n_rirs, unsigned parts, void* records_host, AugStages* stages_out);
+// launches only, on a records buffer of `parts` in device memory: both vocoder stages, the reverb with kAugRir, mix_kernel last with kAugBg
+int launch_augment_records(const AugCall& c, const void* records_dev, unsigned parts);
+// a prepared records buffer in host memory -> the workspace's slots (only the arrays a stage in `st` reads), then the stages in `st`
+int launch_augment(const AugCall& c, const void* records_host, unsigned parts, AugStages st);
+// pinned staging of host records into device memory (ww_augment.hip): `pieces` byte ranges, each to its own address
+int stage_to_device(const void* const* src, const size_t* sizes, void* const* dst, int pieces, hipStream_t stream);
+// the standalone mix and reverb on prepared host records ([n] BgDev / [n] RirDev), staged into the workspace
+int64_t mix_background_workspace_bytes(int64_t n);
+int launch_mix_background(const AugCall& c, const void* records_host);
 int launch_reverb_records(const float* in, int64_t in_stride, int64_t n, int n_samples, const RirDev* rir, const float2* spectra,
                           int64_t n_rirs, float* out, int64_t out_stride, hipStream_t stream);
 int64_t reverb_workspace_bytes(int64_t n);
-int launch_reverb(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_rir* rir_host, const float* spectra,
-                  int64_t n_rirs, float* out, int64_t out_stride, void* workspace, hipStream_t stream);
+int launch_reverb(const AugCall& c, const void* records_host);
 int64_t rir_spectra_workspace_bytes(int64_t n_rirs);
 int launch_rir_spectra(const float* taps, int64_t taps_len, const int64_t* offsets_host, const int32_t* lengths_host, int64_t n_rirs,
                        float* spectra, void* workspace, hipStream_t stream);
-// KA with background and reverb (ww_augment.hip)
-int64_t augment_rir_workspace_bytes(int64_t n, int64_t n_samples);
-int64_t augment_rir_record_bytes();
-int augment_rir_prepare(const ww_augment_plan* plans_host, const ww_augment_bg* bg_host, const ww_augment_rir* rir_host, int64_t n,
-                        int64_t n_samples, int64_t bank_len, int64_t n_rirs, void* records_host, int* any_pitch_out, int* any_stretch_out,
-                        int* any_bg_out, int* any_rir_out);
-int launch_augment_rir(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_plan* plans_host,
-                       const ww_augment_bg* bg_host, const float* bank, int64_t bank_len, const ww_augment_rir* rir_host, const float* spectra,
-                       int64_t n_rirs, float* out, int64_t out_stride, void* workspace, hipStream_t stream);
-int launch_augment_rir_records(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const void* records_dev, const float* bank,
-                               int64_t bank_len, const float* spectra, int64_t n_rirs, float* out, int64_t out_stride, void* workspace,
-                               hipStream_t stream);
 void build_kaiser_best(float* out /*[32769]*/);
 int sync_timeouts(unsigned int* count);   // bounded LDS-counter waits that expired (must be 0)
 int launch_cnn_pool(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch,

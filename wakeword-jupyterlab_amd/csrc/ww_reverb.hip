@@ -230,12 +230,8 @@ __global__ __launch_bounds__(kRvThreads) void reverb_kernel(const float* in, int
 }
 
 // ------------------------------------------------------------------------------------------------
-static int64_t up256(int64_t b) { return (b + 255) & ~int64_t(255); }
-
-int64_t rir_record_bytes() { return int64_t(sizeof(RirDev)); }
-
 // ww_augment_rir -> RirDev, refusing an index outside the bank and a direct path outside the kept taps (enabled = 0: index -1)
-int rir_prepare(const ww_augment_rir* rir_host, int64_t n, int64_t n_rirs, void* records_host, int* any_out) {
+int rir_prepare(const ww_augment_rir* rir_host, int64_t n, int64_t n_rirs, void* records_host, bool* any_out) {
     RirDev* host = static_cast<RirDev*>(records_host);
     bool any = false;
     for (int64_t c = 0; c < n; ++c) {
@@ -276,17 +272,14 @@ int launch_reverb_records(const float* in, int64_t in_stride, int64_t n, int n_s
 
 int64_t reverb_workspace_bytes(int64_t n) { return up256(n * int64_t(sizeof(RirDev))); }
 
-int launch_reverb(const float* pcm, int64_t n, int64_t stride, int64_t n_samples, const ww_augment_rir* rir_host, const float* spectra,
-                  int64_t n_rirs, float* out, int64_t out_stride, void* workspace, hipStream_t stream) {
-    if (n == 0) return WW_OK;
-    std::vector<RirDev> host(static_cast<size_t>(n));
-    if (int rc = rir_prepare(rir_host, n, n_rirs, host.data(), nullptr)) return rc;
-    RirDev* rec = static_cast<RirDev*>(workspace);
-    const size_t sizes[1] = {size_t(n) * sizeof(RirDev)};
-    void* const dst[1] = {rec};
-    if (int rc = stage_to_device(host.data(), sizes, dst, 1, stream)) return rc;
-    return launch_reverb_records(pcm, stride, n, int(n_samples), rec, reinterpret_cast<const float2*>(spectra), n_rirs, out, out_stride,
-                                 stream);
+int launch_reverb(const AugCall& c, const void* records_host) {
+    if (c.n == 0) return WW_OK;
+    RirDev* rec = static_cast<RirDev*>(c.workspace);
+    const size_t bytes = size_t(c.n) * sizeof(RirDev);
+    void* const dst = rec;
+    if (int rc = stage_to_device(&records_host, &bytes, &dst, 1, c.stream)) return rc;
+    return launch_reverb_records(c.pcm, c.stride, c.n, int(c.n_samples), rec, reinterpret_cast<const float2*>(c.spectra), c.n_rirs, c.out,
+                                 c.out_stride, c.stream);
 }
 
 int64_t rir_spectra_workspace_bytes(int64_t n_rirs) { return up256(n_rirs * int64_t(sizeof(RirSrc))); }
@@ -307,9 +300,10 @@ int launch_rir_spectra(const float* taps, int64_t taps_len, const int64_t* offse
     const LogmelTables* tb = device_tables();
     if (!tb) return WW_EHIP;
     RirSrc* src = static_cast<RirSrc*>(workspace);
-    const size_t sizes[1] = {size_t(n_rirs) * sizeof(RirSrc)};
-    void* const dst[1] = {src};
-    if (int rc = stage_to_device(host.data(), sizes, dst, 1, stream)) return rc;
+    const void* const from = host.data();
+    const size_t bytes = size_t(n_rirs) * sizeof(RirSrc);
+    void* const dst = src;
+    if (int rc = stage_to_device(&from, &bytes, &dst, 1, stream)) return rc;
     hipLaunchKernelGGL(rir_spectrum_kernel, dim3(unsigned(n_rirs)), dim3(kRvThreads), 0, stream, taps, src, tb,
                        reinterpret_cast<float2*>(spectra));
     WW_HIP(hipGetLastError());

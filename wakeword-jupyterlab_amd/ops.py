@@ -585,16 +585,16 @@ def _plans_array(plans, B):
 
 
 def augment(pcm: torch.Tensor, plans, bank=None, rirs=None) -> torch.Tensor:
-    """pcm [B, N] float32 on the GPU + one plan per clip -> augmented [B, N], N = 16000 (ww_augment_f32) or any N in 4000..16383
-    (ww_augment_n_f32; the plans' shift is taken mod N and crop lies in [0, round(N / rate) - N]).
+    """pcm [B, N] float32 on the GPU + one plan per clip -> augmented [B, N], N in 4000..16383 (ww_augment_rir_f32 for every batch; the
+    plans' shift is taken mod N and crop lies in [0, round(N / rate) - N]).
 
     `plans`: a ctypes array of _native.AugmentPlan, or a list of dicts with the keys of oracle-style plans
     (shift, n_steps | pitch_rate, rate, crop, sigma, seed); see AudioProcessor.draw_augment_plan.
     With a background.BackgroundNoiseBank, dict plans that carry `bg_file`, `bg_start` and `snr_db` get that file's segment mixed in after
-    the stretch and before the Gaussian noise (ww_augment_bg_f32); clips without those keys, and a batch where no plan has them, give
+    the stretch and before the Gaussian noise; clips without those keys, and a batch where no plan has them, give
     exactly what they give without a bank.
     With a reverb.ImpulseResponseBank (`rirs`), dict plans that carry `rir` get that room impulse response after the stretch and before
-    the background (ww_augment_rir_f32); clips without the key, and a batch where no plan has it, give exactly what they give without."""
+    the background; clips without the key, and a batch where no plan has it, give exactly what they give without."""
     import ctypes as C
     if pcm.device.type != "cuda":
         raise RuntimeError("augment: pcm must live on the MI355X (no CPU fallback)")
@@ -610,37 +610,26 @@ def augment(pcm: torch.Tensor, plans, bank=None, rirs=None) -> torch.Tensor:
         if rirs is not None and any(p.get("rir") is not None for p in plans):
             rir_plans = plans
     plans = _plans_array(plans, B)
-    bg = _bg_array(bg_plans, bank, B) if bank is not None and bg_plans else None
-    rir = _rir_array(rir_plans, rirs, B) if rirs is not None and rir_plans else None
+    bg = _bg_array(bg_plans, bank, B) if bg_plans else None
+    rir = _rir_array(rir_plans or (), rirs, B)
     out = torch.empty((B, N), device=pcm.device, dtype=torch.float32)
     if B == 0:
         return out
+    # one native call for every batch: without background bg is NULL, without reverb every rir entry is off, and a stage that no clip
+    # uses is neither copied nor launched
+    bank_ptr = spectra_ptr = None
+    bank_len = n_rirs = 0
+    if rir_plans:
+        _check_rirs(rirs, pcm.device)
+        spectra_ptr, n_rirs = C.c_void_p(rirs.spectra.data_ptr()), rirs.n_rirs
+    if bg is not None:
+        _check_bank(bank, pcm.device)
+        bank_ptr, bank_len = C.c_void_p(bank.data.data_ptr()), bank.data.numel()
     with torch.cuda.device(pcm.device):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if rir is not None:
-            _check_rirs(rirs, pcm.device)
-            if bg is not None:
-                _check_bank(bank, pcm.device)
-            ws = torch.empty(nat.check(nat.lib.ww_augment_rir_workspace_bytes(B, N)), device=pcm.device, dtype=torch.uint8)
-            nat.check(nat.lib.ww_augment_rir_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, plans, bg,
-                                                 C.c_void_p(bank.data.data_ptr()) if bg is not None else None,
-                                                 bank.data.numel() if bg is not None else 0, rir, C.c_void_p(rirs.spectra.data_ptr()),
-                                                 rirs.n_rirs, C.c_void_p(out.data_ptr()), N, C.c_void_p(ws.data_ptr()), stream))
-        elif bg is not None:
-            _check_bank(bank, pcm.device)
-            ws = torch.empty(nat.check(nat.lib.ww_augment_bg_workspace_bytes(B, N)), device=pcm.device, dtype=torch.uint8)
-            nat.check(nat.lib.ww_augment_bg_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, plans, bg,
-                                                C.c_void_p(bank.data.data_ptr()), bank.data.numel(), C.c_void_p(out.data_ptr()), N,
-                                                C.c_void_p(ws.data_ptr()), stream))
-        elif N == CLIP_SAMPLES:
-            ws_bytes = nat.check(nat.lib.ww_augment_workspace_bytes(B))
-            ws = torch.empty(ws_bytes, device=pcm.device, dtype=torch.uint8)
-            nat.check(nat.lib.ww_augment_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0), plans, C.c_void_p(out.data_ptr()),
-                                             C.c_void_p(ws.data_ptr()), stream))
-        else:
-            ws = torch.empty(nat.check(nat.lib.ww_augment_n_workspace_bytes(B, N)), device=pcm.device, dtype=torch.uint8)
-            nat.check(nat.lib.ww_augment_n_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, plans,
-                                               C.c_void_p(out.data_ptr()), N, C.c_void_p(ws.data_ptr()), stream))
+        ws = torch.empty(nat.check(nat.lib.ww_augment_rir_workspace_bytes(B, N)), device=pcm.device, dtype=torch.uint8)
+        nat.check(nat.lib.ww_augment_rir_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, plans, bg, bank_ptr, bank_len,
+                                             rir, spectra_ptr, n_rirs, C.c_void_p(out.data_ptr()), N, C.c_void_p(ws.data_ptr()),
+                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         ws.record_stream(torch.cuda.current_stream())
     return out
 
@@ -688,14 +677,9 @@ def augment_stages(pcm: torch.Tensor, plans, poison: bool = False) -> dict:
         ws = torch.empty(lay.total_bytes, device=pcm.device, dtype=torch.uint8)
         if poison:
             ws.view(torch.float32).fill_(float("nan"))
-        if N == CLIP_SAMPLES:
-            assert lay.total_bytes == nat.check(nat.lib.ww_augment_workspace_bytes(B))
-            nat.check(nat.lib.ww_augment_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0), plans, C.c_void_p(out.data_ptr()),
-                                             C.c_void_p(ws.data_ptr()), stream))
-        else:
-            assert lay.total_bytes == nat.check(nat.lib.ww_augment_n_workspace_bytes(B, N))
-            nat.check(nat.lib.ww_augment_n_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, plans,
-                                               C.c_void_p(out.data_ptr()), N, C.c_void_p(ws.data_ptr()), stream))
+        assert lay.total_bytes == nat.check(nat.lib.ww_augment_n_workspace_bytes(B, N))
+        nat.check(nat.lib.ww_augment_n_f32(C.c_void_p(pcm.data_ptr()), B, pcm.stride(0) if B > 1 else N, N, plans,
+                                           C.c_void_p(out.data_ptr()), N, C.c_void_p(ws.data_ptr()), stream))
         torch.cuda.current_stream().synchronize()
 
     def region(off, stride, dtype=torch.float32):
