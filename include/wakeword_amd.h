@@ -495,6 +495,46 @@ WW_API int64_t ww_events_state_bytes(int32_t n_mics, int32_t smooth);
 WW_API int ww_events_step_f32(const float* prob_dev, int32_t n_mics, int32_t smooth, float threshold, int64_t refractory, void* state_dev,
                               uint8_t* fired_dev, ww_stream_t stream);
 
+/* ---- training clips in device memory ---------------------------------- */
+/* A bank is one float32 device buffer audio_dev [total_samples] holding its entries back to back.
+ * ww_bank_peaks_f32: peaks_dev[e] = the fmaxf-fold from 0.0f of fabsf(x) over entry e = samples offsets_dev[e] .. offsets_dev[e + 1] - 1
+ * -- what K0 (ww_decode_resample with normalize) divides a file by: a NaN sample is ignored, an empty entry gives 0, an Inf gives Inf.
+ * offsets_dev [n_entries + 1] int64 in device memory, non-decreasing, offsets_dev[0] = 0, offsets_dev[n_entries] <= total_samples
+ * (ww_events_sweep_f32's convention; nothing at or past total_samples is read, whatever the table says).  The call zeroes peaks_dev
+ * [n_entries] on the stream itself; its cost is linear in total_samples however the samples are split into entries, and the result does
+ * not depend on the order the workgroups arrive in.  audio_dev / peaks_dev 4-byte, offsets_dev 8-byte aligned. */
+WW_API int ww_bank_peaks_f32(const float* audio_dev, int64_t total_samples, const int64_t* offsets_dev, int64_t n_entries, float* peaks_dev,
+                             ww_stream_t stream);
+/* ww_bank_gather_f32: windows of N = n_samples samples cut from entries into rows of a batch.  For item i, row r = row, j in [0, N):
+ *   v[j] = audio[offset + start + j] where 0 <= start + j < length; elsewhere out[r][j] is exactly +0.0f and is never divided
+ *   WW_BANK_NORM_NONE    out = v
+ *   WW_BANK_NORM_ENTRY   out = v / peak on the in-entry samples (IEEE division, K0's `o[w] / peak`: peak == 0 gives NaN there, as K0 does)
+ *   WW_BANK_NORM_WINDOW  p = the fmaxf-fold from 0.0f of |v| over the window's in-entry samples, out = v / p; with p == 0 the row is all
+ *                        zeros, NOT NaN -- a deliberate deviation from ENTRY: this is the normalisation the detector applies to every
+ *                        window of a recording, where silent stretches are ordinary and must not poison a training step
+ * out_dev [n_rows][out_stride] float32; rows that no item names, and the columns from N to out_stride, are not written.  items_host
+ * [n_items] in host memory, checked before any HIP call (WW_EINVAL naming the field): N in WW_MIN_CLIP_SAMPLES..WW_MAX_CLIP_SAMPLES,
+ * out_stride >= N, offset >= 0, length >= 0, offset + length <= total_samples, -N <= start <= length, a known norm, peak not negative,
+ * 0 <= row < n_rows and no row named twice.  The items are staged through the library's pinned memory into workspace_dev
+ * (>= ww_bank_gather_workspace_bytes(n_items), 256-byte aligned); the call is asynchronous on `stream` and cannot be captured into a
+ * graph.  audio_dev / out_dev 4-byte aligned; entries and windows may start at any sample, and total_samples may exceed 2^31. */
+#define WW_BANK_NORM_NONE 0
+#define WW_BANK_NORM_ENTRY 1
+#define WW_BANK_NORM_WINDOW 2
+typedef struct ww_bank_item {
+    int64_t offset; /* the entry's first sample in audio_dev */
+    int64_t length; /* the entry's samples, >= 0 */
+    int64_t start;  /* window start in entry coordinates, -N <= start <= length */
+    float peak;     /* the divisor of WW_BANK_NORM_ENTRY (ww_bank_peaks_f32's value for the entry), >= 0 */
+    int32_t row;    /* output row, 0 <= row < n_rows */
+    int32_t norm;   /* WW_BANK_NORM_* */
+    int32_t reserved;
+} ww_bank_item;     /* 40 bytes */
+WW_API int64_t ww_bank_gather_workspace_bytes(int64_t n_items);
+WW_API int ww_bank_gather_f32(const float* audio_dev, int64_t total_samples, const ww_bank_item* items_host, int64_t n_items,
+                              int64_t n_samples, float* out_dev, int64_t n_rows, int64_t out_stride, void* workspace_dev,
+                              ww_stream_t stream);
+
 /* ---- training step ----------------------------------------------------- */
 /* Replaces, for one batch, `output = model(data)` in train mode and `loss.backward()` of the reference's training loops
  * (wakeword_training/train_wakeword.py:109-115; WakewordTrainer.train_epoch, wakeword_training_script.py:241-267) for

@@ -94,6 +94,15 @@ class AugmentRir(C.Structure):
     ]
 
 
+class BankItem(C.Structure):
+    """struct ww_bank_item (include/wakeword_amd.h): one window of a bank entry and the output row it goes to."""
+    _fields_ = [
+        ("offset", C.c_int64), ("length", C.c_int64), ("start", C.c_int64), ("peak", C.c_float), ("row", C.c_int32), ("norm", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+BANK_NORM_NONE, BANK_NORM_ENTRY, BANK_NORM_WINDOW = 0, 1, 2
 RIR_MAX_TAPS, RIR_FFT_SIZE, RIR_SPECTRUM_BINS = 16384, 32768, 16385
 
 
@@ -191,6 +200,10 @@ PROTOTYPES = {
                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ww_events_state_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "ww_events_step_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_bank_peaks_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ww_bank_gather_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "ww_bank_gather_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                     C.c_void_p]),
     "ww_train_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "ww_train_forward_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(TrainParams), C.c_float, C.c_float, C.c_uint64, C.c_int32,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -67,6 +67,12 @@ class WakewordDataset(Dataset):
         pinned staging, decoded (K0), augmented when the dataset says so (KA) and turned into log-mel (K1) one batch at a time."""
         return GpuBatchLoader(self, batch_size, shuffle=shuffle, drop_last=drop_last)
 
+    def cache(self):
+        """This dataset's files decoded once into device memory: a bank.ClipBank whose `loader(..., augment=self.augment)` yields what
+        `loader()` yields, without touching a file again."""
+        from .bank import ClipBank
+        return ClipBank.from_dataset(self)
+
 
 class GpuBatchLoader:
     def __init__(self, dataset, batch_size=16, shuffle=False, drop_last=False):
@@ -150,4 +156,14 @@ def DataLoader(dataset, batch_size=1, shuffle=False, *args, num_workers=0, drop_
         if batch_size is None:
             raise NotImplementedError("DataLoader(WakewordDataset, batch_size=None): unbatched loading is dataset[i]")
         return dataset.loader(batch_size=batch_size, shuffle=bool(shuffle), drop_last=bool(drop_last))
+    from .bank import ClipBank
+    if isinstance(dataset, ClipBank):                  # the same refusals; `augment=` goes through to bank.loader
+        augment = bool(kwargs.pop("augment", False))
+        unsupported = [k for k in ("sampler", "batch_sampler", "collate_fn") if kwargs.get(k) is not None]
+        if args or unsupported:
+            raise NotImplementedError("DataLoader(ClipBank, ...): positional extras / " + ", ".join(unsupported or ["sampler"]) +
+                                      " are not supported -- the batch is assembled on the GPU (bank.loader)")
+        if batch_size is None:
+            raise NotImplementedError("DataLoader(ClipBank, batch_size=None): unbatched loading is bank.gather")
+        return dataset.loader(batch_size=batch_size, shuffle=bool(shuffle), drop_last=bool(drop_last), augment=augment)
     return torch.utils.data.DataLoader(dataset, batch_size, shuffle, *args, num_workers=num_workers, drop_last=drop_last, **kwargs)
