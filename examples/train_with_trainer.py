@@ -1,0 +1,65 @@
+#!/usr/bin/env python3
+"""The reference's `main()` (wakeword_training_script.py:395-495) with its own training class: sample data -> file lists -> split ->
+AudioProcessor / WakewordModel -> WakewordTrainer(model, device).train(train_loader, val_loader, epochs) -> best / final checkpoints.
+The training files live in a ClipBank on the GPU and every batch runs forward, cross-entropy, backward and
+Adam as HIP kernels without a wait on the device (section 3h); the epoch's loss and accuracy are read once per epoch.
+
+    PYTHONPATH=. python examples/train_with_trainer.py [--epochs 10] [--data DIR] [--duration 1.0] [--background DIR] [--max-grad-norm 1.0]
+"""
+import argparse
+import glob
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from train_from_files import split  # noqa: E402
+from wakeword_jupyterlab_amd import (AudioConfig, AudioProcessor, DataLoader, TrainingConfig, WakewordDataset, WakewordModel,  # noqa: E402
+                                     WakewordTrainer)
+from wakeword_jupyterlab_amd.synth import create_sample_data  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--epochs", type=int, default=TrainingConfig.EPOCHS)
+    ap.add_argument("--data", default=".")
+    ap.add_argument("--lr", type=float, default=TrainingConfig.LEARNING_RATE)
+    ap.add_argument("--batch-size", type=int, default=TrainingConfig.BATCH_SIZE)
+    ap.add_argument("--duration", type=float, default=AudioConfig.DURATION, help="clip length in seconds, 0.25 .. 1.0")
+    ap.add_argument("--background", default=None, help="directory of background noise files (WAV / FLAC) mixed into the training clips")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm after the backward (default: off)")
+    a = ap.parse_args()
+    device = torch.device("cuda")
+    print(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
+    wdir, ndir = os.path.join(a.data, "wakeword_data"), os.path.join(a.data, "negative_data")
+    if not os.path.exists(wdir) or len(os.listdir(wdir)) == 0:
+        create_sample_data(a.data)
+    wake = [f for ext in ("*.wav", "*.flac") for f in glob.glob(os.path.join(wdir, ext))]
+    neg = [f for ext in ("*.wav", "*.flac") for f in glob.glob(os.path.join(ndir, ext))]
+    print(f"Wakeword files: {len(wake)}   Negative files: {len(neg)}")
+    w_tr, w_va, w_te = split(wake)
+    n_tr, n_va, n_te = split(neg)
+    audio_config = type("AudioConfig", (AudioConfig,), {"DURATION": a.duration})
+    config = type("TrainingConfig", (TrainingConfig,), {"LEARNING_RATE": a.lr, "BATCH_SIZE": a.batch_size, "EPOCHS": a.epochs})
+    processor = AudioProcessor(audio_config)
+    if a.background:
+        processor.set_background_noise(a.background)
+    model = WakewordModel(audio_config=audio_config).to(device)
+    print(f"Parameters: {sum(p.numel() for p in model.parameters()):,}")
+    bank = WakewordDataset(w_tr, n_tr, processor, augment=True).cache()           # every training file decoded once, onto the GPU
+    print(bank)
+    train_loader = DataLoader(bank, batch_size=config.BATCH_SIZE, shuffle=True, augment=True)
+    val_loader = DataLoader(WakewordDataset(w_va, n_va, processor, augment=False).cache(), batch_size=config.BATCH_SIZE, shuffle=False)
+    test_loader = DataLoader(WakewordDataset(w_te, n_te, processor, augment=False).cache(), batch_size=config.BATCH_SIZE, shuffle=False)
+    trainer = WakewordTrainer(model, device, config, checkpoint_path=os.path.join(a.data, "best_wakeword_model.pth"),
+                              max_grad_norm=a.max_grad_norm)
+    best = trainer.train(train_loader, val_loader, config.EPOCHS)
+    _, test_acc = trainer.validate(test_loader)
+    print(f"Best validation accuracy: {best:.2f}%   Test accuracy: {test_acc:.2f}%")
+    torch.save({"model_state_dict": model.state_dict(), "best_val_acc": best, "device": str(device)},
+               os.path.join(a.data, "final_wakeword_model.pth"))
+
+
+if __name__ == "__main__":
+    main()

@@ -627,6 +627,56 @@ WW_API int ww_train_stage(const void* workspace_dev, int64_t n, int32_t n_conv, 
 WW_API int ww_set_train_math(int mode);
 WW_API int ww_get_train_math(void);
 
+/* ---- loss, metrics and optimiser of the training loop ------------------ */
+/* What WakewordTrainer.train_epoch (wakeword_training_script.py:241-267) does around forward and backward, as three kernels: nothing
+ * here waits for the device, and every sum has one fixed order and uses no float atomics, so results repeat bit for bit from run to run.
+ *
+ * ww_ce_loss_f32: CrossEntropyLoss (mean reduction) over two classes, its gradient and the loop's running metrics.  Per clip, in float64:
+ *   lse = max + log(exp(z0 - max) + exp(z1 - max)), loss = lse - z[y], prediction = 1 iff z1 > z0 (a tie gives 0, as torch.max(output, 1)).
+ *   dlogits_dev [n][2] (NULL: the validation form, nothing is written) = (softmax - onehot) / n, rounded once: ww_train_backward_f32's input.
+ *   loss_dev [1] (NULL allowed) = the batch mean: lane sums over fixed stripes of the batch, folded in a fixed order that does not depend
+ *   on the launch geometry, in float64, rounded once to float32.
+ *   stats_dev (NULL allowed): one lane adds this batch to the record, in stream order (calls on one stream serialise; calls on
+ *   different streams must not share a record).  A label outside {0, 1} adds nothing to the loss or the gradient (its dlogits are
+ *   exactly zero) and is counted in bad_labels; a clip with a non-finite logit is counted in nonfinite (its loss is what IEEE
+ *   arithmetic makes of it, as in torch).  logits_dev [n][2] float32, labels_dev [n] int64; n in 1..2^30; 4-byte (labels, stats: 8-byte) alignment. */
+typedef struct ww_loss_stats {
+    double loss_sum;    /* sum of the batch means as float32 values: the reference's `running_loss += loss.item()` */
+    int64_t correct;    /* clips whose prediction equals a valid label */
+    int64_t total;      /* clips seen (`total += target.size(0)`) */
+    int64_t batches;    /* calls */
+    int64_t bad_labels; /* labels outside {0, 1} */
+    int64_t nonfinite;  /* clips with an Inf or NaN logit */
+} ww_loss_stats;        /* 48 bytes, DEVICE memory; zero it before an epoch */
+WW_API int ww_ce_loss_f32(const float* logits_dev, const int64_t* labels_dev, int64_t n, float* dlogits_dev, float* loss_dev,
+                          ww_loss_stats* stats_dev, ww_stream_t stream);
+/* ww_adam_step_f32: one launch of torch's single-tensor Adam (no amsgrad, no maximize) over up to WW_ADAM_MAX_TENSORS tensors.  The table
+ * is read on the HOST and travels in the kernel arguments: nothing is uploaded.
+ *   g' = g * scale + weight_decay * p;  m += (g' - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g'^2;
+ *   p -= (lr / (1 - beta1^step)) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * with the bias corrections computed on the host in double.  scale = *grad_scale_dev, read by the kernel (NULL: 1) -- ww_grad_norm_f32
+ * writes it, so clipping costs no host wait.  Two entries may share one g (bias_ih and bias_hh have the same gradient); the p, m and v
+ * ranges of the table must not overlap one another.  p, g, m, v: device pointers, 4-byte aligned (16-byte accesses where the four share
+ * their phase on the 16-byte grid).  Checked before any HIP call (WW_EINVAL naming the field): 1 <= n_tensors <= 16, n >= 1, no null
+ * pointer, finite lr >= 0, betas in [0, 1), finite eps > 0, finite weight_decay >= 0, step >= 1. */
+#define WW_ADAM_MAX_TENSORS 16
+typedef struct ww_adam_tensor {
+    float* p;       /* parameter, updated in place */
+    const float* g; /* gradient, read only */
+    float* m;       /* exp_avg */
+    float* v;       /* exp_avg_sq */
+    int64_t n;      /* elements */
+} ww_adam_tensor;   /* 40 bytes */
+WW_API int ww_adam_step_f32(const ww_adam_tensor* tensors_host, int64_t n_tensors, double lr, double beta1, double beta2, double eps,
+                            double weight_decay, int64_t step, const float* grad_scale_dev, ww_stream_t stream);
+/* ww_grad_norm_f32: *norm_dev = the L2 norm over every g of the table (an entry counts once per entry, as clip_grad_norm_ counts a
+ * gradient once per parameter), float64 partial sums over 4096 elements each in a fixed order in element coordinates, added by a second
+ * kernel; *scale_dev = min(1, max_norm / (norm + 1e-6)), clip_grad_norm_'s coefficient.  Only g and n of the entries are read.
+ * workspace_dev: >= ww_grad_norm_workspace_bytes(...) bytes, 256-byte aligned.  max_norm > 0 (infinity: the norm alone). */
+WW_API int64_t ww_grad_norm_workspace_bytes(const ww_adam_tensor* tensors_host, int64_t n_tensors);
+WW_API int ww_grad_norm_f32(const ww_adam_tensor* tensors_host, int64_t n_tensors, double max_norm, double* norm_dev, float* scale_dev,
+                            void* workspace_dev, ww_stream_t stream);
+
 /* ---- streaming: sliding window of 0.25 .. 1 s, one hop per step, many microphones ------------- */
 /* Semantics per window = predict_wakeword (wakeword_training.ipynb cell 19): normalise the last
  * N samples, log-mel, forward, softmax, p[wakeword].  The reference has no streaming code;

@@ -16,13 +16,14 @@ def __getattr__(name):
     # lazy: `import wakeword_jupyterlab_amd` must work on a box where only host utilities are needed
     import importlib
     if name in ("ops", "model", "audio", "dataset", "streaming", "inference", "distributed", "_native", "background", "reverb",
-                "scan", "bank"):
+                "scan", "bank", "optim", "trainer"):
         return importlib.import_module(f"{__name__}.{name}")
     lazy = {"AudioProcessor": "audio", "WakewordDataset": "dataset", "DataLoader": "dataset", "SimpleWakewordModel": "model",
             "WakewordModel": "model", "StreamingDetector": "streaming", "predict_wakeword": "inference",
             "evaluate": "inference", "AudioConfig": "config", "ModelConfig": "config", "Config": "config",
             "AugmentationConfig": "config", "BackgroundNoiseBank": "background", "ClipBank": "bank",
-            "ImpulseResponseBank": "reverb", "scan_files": "scan", "det_curve": "scan", "Scan": "scan"}
+            "ImpulseResponseBank": "reverb", "scan_files": "scan", "det_curve": "scan", "Scan": "scan", "TrainingConfig": "config", "FusedAdam": "optim",
+            "WakewordTrainer": "trainer"}
     if name in lazy:
         return getattr(importlib.import_module(f"{__name__}.{lazy[name]}"), name)
     raise AttributeError(name)

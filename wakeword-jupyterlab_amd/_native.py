@@ -103,6 +103,20 @@ class BankItem(C.Structure):
 
 
 BANK_NORM_NONE, BANK_NORM_ENTRY, BANK_NORM_WINDOW = 0, 1, 2
+
+
+class LossStats(C.Structure):
+    """struct ww_loss_stats (include/wakeword_amd.h): the running metrics of an epoch, kept in device memory."""
+    _fields_ = [("loss_sum", C.c_double), ("correct", C.c_int64), ("total", C.c_int64), ("batches", C.c_int64), ("bad_labels", C.c_int64),
+                ("nonfinite", C.c_int64)]
+
+
+class AdamTensor(C.Structure):
+    """struct ww_adam_tensor (include/wakeword_amd.h): one entry of the Adam / gradient-norm table, DEVICE pointers."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
+
+
+ADAM_MAX_TENSORS = 16
 RIR_MAX_TAPS, RIR_FFT_SIZE, RIR_SPECTRUM_BINS = 16384, 32768, 16385
 
 
@@ -209,6 +223,11 @@ PROTOTYPES = {
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ww_train_backward_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(TrainParams), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
                                         C.POINTER(TrainGrads), C.c_void_p]),
+    "ww_ce_loss_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_adam_step_f32": (C.c_int, [C.POINTER(AdamTensor), C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
+                                   C.c_void_p, C.c_void_p]),
+    "ww_grad_norm_workspace_bytes": (C.c_int64, [C.POINTER(AdamTensor), C.c_int64]),
+    "ww_grad_norm_f32": (C.c_int, [C.POINTER(AdamTensor), C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_train_masks": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_train_packed_image": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "ww_train_bit_images": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -3,7 +3,8 @@
 AudioConfig / ModelConfig : /root/reference/wakeword_training_script.py:29-43 (dup notebook cell 3)
 Config                    : /root/reference/wakeword_training/train_wakeword.py:16-25
 AugmentationConfig        : /root/reference/wakeword_training_script.py:52-58
-Only the fields the accelerated path reads are kept (training hyper-parameters are out of scope).
+TrainingConfig            : /root/reference/wakeword_training_script.py:45-50 (read by trainer.WakewordTrainer)
+Only the fields the accelerated path reads are kept.
 """
 
 
@@ -40,6 +41,14 @@ class ModelConfig:            # WakewordModel (3 convs)
     NUM_LAYERS = 2
     DROPOUT = 0.6
     NUM_CLASSES = 2
+
+
+class TrainingConfig:         # WakewordTrainer
+    BATCH_SIZE = 16
+    LEARNING_RATE = 0.0001
+    EPOCHS = 10
+    VALIDATION_SPLIT = 0.2
+    TEST_SPLIT = 0.1
 
 
 class Config:                 # SimpleWakewordModel (2 convs)

@@ -1,0 +1,389 @@
+// What sits between the training forward and backward kernels and after them: cross-entropy with its
+// gradient and the epoch's running metrics, a multi-tensor Adam step, and the global gradient norm that clips it.
+//   ce_loss_kernel      one workgroup: per clip the loss and d loss / d logits in float64, the batch mean summed in a fixed order,
+//                       one lane updates the ww_loss_stats record (stream order serialises the calls: no atomics)
+//   adam_kernel         one launch over up to 16 tensors, the table in the kernel arguments; torch's single-tensor Adam arithmetic
+//   grad_norm_kernel    float64 partial sums of g^2 per 4096 elements; grad_norm_finish_kernel adds them and writes norm and clip scale
+// All three are memory- and latency-bound.  No float atomics anywhere: every sum has one order, so results repeat bit for bit.
+#include <cmath>
+
+#include "ww_internal.h"
+
+namespace ww {
+
+// ---------------------------------------------------------------------------------------------
+// cross-entropy, two classes
+// ---------------------------------------------------------------------------------------------
+constexpr int kCeThreads = 256;
+
+struct CeClip { double loss, d0, d1; int correct, bad, nonfinite; };
+
+// One clip in float64: lse = max + log(exp(z0 - max) + exp(z1 - max)), loss = lse - z[y], d = softmax - onehot (the caller divides by n).
+__device__ __forceinline__ CeClip ce_clip(float z0f, float z1f, int64_t y) {
+    CeClip r;
+    const double z0 = double(z0f), z1 = double(z1f);
+    const double m = z0 > z1 ? z0 : z1;
+    const double e0 = exp(z0 - m), e1 = exp(z1 - m), s = e0 + e1;
+    const bool valid = y == 0 || y == 1;
+    const double lse = m + log(s);
+    r.loss = valid ? lse - (y == 1 ? z1 : z0) : 0.0;
+    r.d0 = valid ? e0 / s - (y == 0 ? 1.0 : 0.0) : 0.0;
+    r.d1 = valid ? e1 / s - (y == 1 ? 1.0 : 0.0) : 0.0;
+    const int pred = z1f > z0f ? 1 : 0;                     // a tie gives class 0, as torch.max(output, 1) does
+    r.correct = valid && int64_t(pred) == y;
+    r.bad = !valid;
+    r.nonfinite = !(isfinite(z0f) && isfinite(z1f));
+    return r;
+}
+
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+__device__ __forceinline__ int wave_sum(int x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+
+// Lane t owns the clip pairs t, t + 256, ...: a pair is 16 bytes of logits and 16 bytes of labels.  Its float64 sum runs over its clips
+// in rising order; the 256 lane sums are folded by the butterfly of wave_sum and the four wave sums are added in wave order -- an order
+// set by kCeThreads alone.  The pointers need 4-byte (labels: 8-byte) alignment only; the 16-byte accesses are taken where they are aligned.
+__global__ __launch_bounds__(kCeThreads) void ce_loss_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int64_t n,
+                                                             float* __restrict__ dlogits, float* __restrict__ loss_out,
+                                                             ww_loss_stats* __restrict__ stats) {
+    __shared__ double red_loss[kCeThreads / 64];
+    __shared__ int red_cnt[3][kCeThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool z_wide = (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
+    const bool y_wide = (reinterpret_cast<uintptr_t>(labels) & 15) == 0;
+    const bool d_wide = (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;
+    const double inv_n = 1.0 / double(n);
+    const int64_t pairs = (n + 1) >> 1;
+    double loss = 0.0;
+    int correct = 0, bad = 0, nonfinite = 0;
+    for (int64_t p = tid; p < pairs; p += kCeThreads) {
+        const int64_t i = 2 * p;
+        const bool two = i + 1 < n;
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        int64_t y[2] = {0, 0};
+        if (two && z_wide) {
+            const float4 v = *reinterpret_cast<const float4*>(logits + 2 * i);
+            z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
+        } else {
+            z[0] = logits[2 * i]; z[1] = logits[2 * i + 1];
+            if (two) { z[2] = logits[2 * i + 2]; z[3] = logits[2 * i + 3]; }
+        }
+        if (two && y_wide) {
+            const longlong2 v = *reinterpret_cast<const longlong2*>(labels + i);
+            y[0] = v.x; y[1] = v.y;
+        } else {
+            y[0] = labels[i];
+            if (two) y[1] = labels[i + 1];
+        }
+        const CeClip a = ce_clip(z[0], z[1], y[0]);
+        loss += a.loss; correct += a.correct; bad += a.bad; nonfinite += a.nonfinite;
+        float d[4] = {float(a.d0 * inv_n), float(a.d1 * inv_n), 0.f, 0.f};
+        if (two) {
+            const CeClip b = ce_clip(z[2], z[3], y[1]);
+            loss += b.loss; correct += b.correct; bad += b.bad; nonfinite += b.nonfinite;
+            d[2] = float(b.d0 * inv_n); d[3] = float(b.d1 * inv_n);
+        }
+        if (dlogits) {
+            if (two && d_wide) {
+                *reinterpret_cast<float4*>(dlogits + 2 * i) = make_float4(d[0], d[1], d[2], d[3]);
+            } else {
+                dlogits[2 * i] = d[0]; dlogits[2 * i + 1] = d[1];
+                if (two) { dlogits[2 * i + 2] = d[2]; dlogits[2 * i + 3] = d[3]; }
+            }
+        }
+    }
+    loss = wave_sum(loss); correct = wave_sum(correct); bad = wave_sum(bad); nonfinite = wave_sum(nonfinite);
+    if (lane == 0) { red_loss[wave] = loss; red_cnt[0][wave] = correct; red_cnt[1][wave] = bad; red_cnt[2][wave] = nonfinite; }
+    __syncthreads();
+    if (tid == 0) {
+        double total = red_loss[0];
+        int c = red_cnt[0][0], b = red_cnt[1][0], f = red_cnt[2][0];
+#pragma unroll
+        for (int w = 1; w < kCeThreads / 64; ++w) { total += red_loss[w]; c += red_cnt[0][w]; b += red_cnt[1][w]; f += red_cnt[2][w]; }
+        const float mean = float(total * inv_n);            // rounded once
+        if (loss_out) *loss_out = mean;
+        if (stats) {
+            stats->loss_sum += double(mean);                // what `running_loss += loss.item()` adds
+            stats->correct += c;
+            stats->total += n;
+            stats->batches += 1;
+            stats->bad_labels += b;
+            stats->nonfinite += f;
+        }
+    }
+}
+
+int launch_ce_loss(const float* logits, const int64_t* labels, int64_t n, float* dlogits, float* loss, ww_loss_stats* stats, hipStream_t stream) {
+    hipLaunchKernelGGL(ce_loss_kernel, dim3(1), dim3(kCeThreads), 0, stream, logits, labels, n, dlogits, loss, stats);
+    WW_HIP(hipGetLastError());
+    return WW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the tensor table of the Adam and norm kernels: by value in the kernel arguments
+// ---------------------------------------------------------------------------------------------
+constexpr int kMaxTensors = WW_ADAM_MAX_TENSORS;
+struct TensorTable {
+    ww_adam_tensor t[kMaxTensors];
+    int32_t first_block[kMaxTensors + 1];                   // prefix sums of the tensors' block counts
+    int32_t n_tensors;
+};
+
+// The tensor a block belongs to: the largest k with first_block[k] <= block (n_tensors <= 16: a linear scan over scalars).
+__device__ __forceinline__ int tensor_of(const TensorTable& tab, int block) {
+    int k = 0;
+    for (int j = 1; j < tab.n_tensors; ++j) k = tab.first_block[j] <= block ? j : k;
+    return k;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Adam
+// ---------------------------------------------------------------------------------------------
+constexpr int kAdamThreads = 256;
+constexpr int kAdamChunk = kAdamThreads * 4;                // one 16-byte vector per thread
+
+struct AdamScalars { float lr_c1, inv_c2_sqrt, eps, omb1, beta2, omb2, weight_decay; };   // lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t), ...
+
+// torch's single-tensor Adam (no amsgrad, no maximize):  g' = g scale + wd p;  m += (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g'^2;
+// p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float scale, const AdamScalars& s) {
+    g = g * scale + s.weight_decay * p;
+    m = m + (g - m) * s.omb1;
+    v = s.beta2 * v + s.omb2 * g * g;
+    const float denom = sqrtf(v) * s.inv_c2_sqrt + s.eps;
+    p = p - s.lr_c1 * (m / denom);
+}
+
+// A block owns 256 vectors of one tensor.  Vectors are laid on the 16-byte grid of the ADDRESSES: with a = the phase of p in floats,
+// vector q holds the elements 4 q - a .. 4 q - a + 3, so a tensor that starts between grid lines gets a scalar head and tail and 16-byte
+// accesses between them -- when p, g, m and v share the phase (views cut the same way do); otherwise every element goes alone.
+__global__ __launch_bounds__(kAdamThreads) void adam_kernel(const TensorTable tab, const AdamScalars s, const float* __restrict__ grad_scale) {
+    const int k = tensor_of(tab, int(blockIdx.x));
+    const ww_adam_tensor t = tab.t[k];
+    const float scale = grad_scale ? *grad_scale : 1.0f;
+    const int a = int((reinterpret_cast<uintptr_t>(t.p) >> 2) & 3);
+    const bool same = a == int((reinterpret_cast<uintptr_t>(t.g) >> 2) & 3) && a == int((reinterpret_cast<uintptr_t>(t.m) >> 2) & 3) &&
+                      a == int((reinterpret_cast<uintptr_t>(t.v) >> 2) & 3);
+    const int shift = same ? a : 0;
+    const int64_t q = int64_t(int(blockIdx.x) - tab.first_block[k]) * kAdamThreads + threadIdx.x;
+    const int64_t e0 = 4 * q - shift;                       // first element of this thread's vector
+    if (e0 >= t.n) return;
+    if (same && e0 >= 0 && e0 + 4 <= t.n) {
+        float4 p = *reinterpret_cast<const float4*>(t.p + e0);
+        const float4 g = *reinterpret_cast<const float4*>(t.g + e0);
+        float4 m = *reinterpret_cast<const float4*>(t.m + e0);
+        float4 v = *reinterpret_cast<const float4*>(t.v + e0);
+        adam_one(p.x, g.x, m.x, v.x, scale, s);
+        adam_one(p.y, g.y, m.y, v.y, scale, s);
+        adam_one(p.z, g.z, m.z, v.z, scale, s);
+        adam_one(p.w, g.w, m.w, v.w, scale, s);
+        *reinterpret_cast<float4*>(t.p + e0) = p;
+        *reinterpret_cast<float4*>(t.m + e0) = m;
+        *reinterpret_cast<float4*>(t.v + e0) = v;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t e = e0 + j;
+        if (e < 0 || e >= t.n) continue;
+        float p = t.p[e], m = t.m[e], v = t.v[e];
+        adam_one(p, t.g[e], m, v, scale, s);
+        t.p[e] = p; t.m[e] = m; t.v[e] = v;
+    }
+}
+
+// Blocks of `chunk` elements per tensor (+3: the phase shift can push the last elements into one more vector).
+static int fill_table(const ww_adam_tensor* tensors, int n_tensors, int chunk, TensorTable* tab) {
+    int64_t blocks = 0;
+    for (int k = 0; k < n_tensors; ++k) {
+        tab->t[k] = tensors[k];
+        tab->first_block[k] = int32_t(blocks);
+        blocks += (tensors[k].n + 3 + chunk - 1) / chunk;
+        if (blocks > (int64_t(1) << 30)) return fail(WW_EUNSUPPORTED, "tensors[%d].n: the table needs more than 2^30 blocks", k);
+    }
+    for (int k = n_tensors; k <= kMaxTensors; ++k) tab->first_block[k] = int32_t(blocks);
+    for (int k = n_tensors; k < kMaxTensors; ++k) tab->t[k] = ww_adam_tensor{nullptr, nullptr, nullptr, nullptr, 0};
+    tab->n_tensors = n_tensors;
+    return WW_OK;
+}
+
+int launch_adam(const ww_adam_tensor* tensors, int n_tensors, const AdamScalars& s, const float* grad_scale, hipStream_t stream) {
+    TensorTable tab;
+    if (int rc = fill_table(tensors, n_tensors, kAdamChunk, &tab)) return rc;
+    hipLaunchKernelGGL(adam_kernel, dim3(unsigned(tab.first_block[kMaxTensors])), dim3(kAdamThreads), 0, stream, tab, s, grad_scale);
+    WW_HIP(hipGetLastError());
+    return WW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// global L2 norm of the table's gradients, and the clip scale
+// ---------------------------------------------------------------------------------------------
+constexpr int kNormThreads = 256;
+constexpr int kNormVecs = 4;
+constexpr int kNormChunk = kNormThreads * kNormVecs * 4;    // 4096 elements per partial sum
+
+// partial[block] = sum of g^2 over elements [4096 c, 4096 c + 4096) of the block's tensor, in float64: thread t adds its elements
+// 4 (t + 256 j) .. + 3, j = 0 .. 3, in rising order, then the butterfly and the wave order of ce_loss_kernel.  The order is in ELEMENT
+// coordinates, so it does not move with the pointer's alignment (a g off the 16-byte grid is read one float at a time).
+__global__ __launch_bounds__(kNormThreads) void grad_norm_kernel(const TensorTable tab, double* __restrict__ partial) {
+    __shared__ double red[kNormThreads / 64];
+    const int k = tensor_of(tab, int(blockIdx.x));
+    const float* __restrict__ g = tab.t[k].g;
+    const int64_t n = tab.t[k].n;
+    const bool wide = (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+    const int64_t base = int64_t(int(blockIdx.x) - tab.first_block[k]) * kNormChunk;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < kNormVecs; ++j) {
+        const int64_t e0 = base + 4 * int64_t(tid + kNormThreads * j);
+        float x[4] = {0.f, 0.f, 0.f, 0.f};
+        if (wide && e0 + 4 <= n) {
+            const float4 v = *reinterpret_cast<const float4*>(g + e0);
+            x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (e0 + i < n) x[i] = g[e0 + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc += double(x[i]) * double(x[i]);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (tid == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// One workgroup: thread t adds the partials t, t + 256, ... in rising order; same fold.  scale = min(1, max_norm / (norm + 1e-6)).
+__global__ __launch_bounds__(kNormThreads) void grad_norm_finish_kernel(const double* __restrict__ partial, int n_partial, double max_norm,
+                                                                        double* __restrict__ norm_out, float* __restrict__ scale_out) {
+    __shared__ double red[kNormThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double acc = 0.0;
+    for (int i = tid; i < n_partial; i += kNormThreads) acc += partial[i];
+    acc = wave_sum(acc);
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        const double norm = sqrt(((red[0] + red[1]) + red[2]) + red[3]);
+        const double coef = max_norm / (norm + 1e-6);
+        *norm_out = norm;
+        *scale_out = float(coef < 1.0 ? coef : 1.0);        // a NaN norm leaves the gradients unscaled: they carry the NaN themselves
+    }
+}
+
+static int64_t norm_blocks(const ww_adam_tensor* tensors, int n_tensors) {
+    int64_t blocks = 0;
+    for (int k = 0; k < n_tensors; ++k) blocks += (tensors[k].n + 3 + kNormChunk - 1) / kNormChunk;
+    return blocks;
+}
+
+int launch_grad_norm(const ww_adam_tensor* tensors, int n_tensors, double max_norm, double* norm, float* scale, void* workspace, hipStream_t stream) {
+    TensorTable tab;
+    if (int rc = fill_table(tensors, n_tensors, kNormChunk, &tab)) return rc;
+    const int blocks = tab.first_block[kMaxTensors];
+    double* partial = static_cast<double*>(workspace);
+    hipLaunchKernelGGL(grad_norm_kernel, dim3(unsigned(blocks)), dim3(kNormThreads), 0, stream, tab, partial);
+    WW_HIP(hipGetLastError());
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(kNormThreads), 0, stream, partial, blocks, max_norm, norm, scale);
+    WW_HIP(hipGetLastError());
+    return WW_OK;
+}
+
+// Host checks of a table, before any HIP call.  `state`: p, m and v are read and written (Adam); the norm reads g alone.
+static int check_table(const ww_adam_tensor* tensors, int64_t n_tensors, bool state) {
+    if (n_tensors < 1 || n_tensors > kMaxTensors) return fail(WW_EINVAL, "n_tensors %lld: expected 1..%d", (long long)n_tensors, kMaxTensors);
+    if (!tensors) return fail(WW_EINVAL, "null tensors pointer");
+    for (int k = 0; k < int(n_tensors); ++k) {
+        const ww_adam_tensor& t = tensors[k];
+        if (t.n <= 0 || t.n > (int64_t(1) << 40)) return fail(WW_EINVAL, "tensors[%d].n %lld: expected 1..2^40", k, (long long)t.n);
+        if (!t.g || (state && (!t.p || !t.m || !t.v))) return fail(WW_EINVAL, "tensors[%d]: null p / g / m / v pointer", k);
+        if ((reinterpret_cast<uintptr_t>(t.g) & 3) ||
+            (state && ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.m) | reinterpret_cast<uintptr_t>(t.v)) & 3)))
+            return fail(WW_EINVAL, "tensors[%d]: p / g / m / v must be 4-byte aligned", k);
+    }
+    if (!state) return WW_OK;
+    // p, m and v are written: no two of the 3 n_tensors ranges may overlap (g is only read and may be shared)
+    const float* lo[3 * kMaxTensors];
+    int cnt = 0;
+    int64_t len[3 * kMaxTensors];
+    for (int k = 0; k < int(n_tensors); ++k)
+        for (const float* ptr : {static_cast<const float*>(tensors[k].p), static_cast<const float*>(tensors[k].m), static_cast<const float*>(tensors[k].v)}) {
+            lo[cnt] = ptr; len[cnt] = tensors[k].n; ++cnt;
+        }
+    for (int i = 0; i < cnt; ++i)
+        for (int j = i + 1; j < cnt; ++j) {
+            const uintptr_t a0 = reinterpret_cast<uintptr_t>(lo[i]), a1 = a0 + uintptr_t(len[i]) * 4;
+            const uintptr_t b0 = reinterpret_cast<uintptr_t>(lo[j]), b1 = b0 + uintptr_t(len[j]) * 4;
+            if (a0 < b1 && b0 < a1) return fail(WW_EINVAL, "tensors[%d] and tensors[%d]: p / m / v ranges overlap", i / 3, j / 3);
+        }
+    return WW_OK;
+}
+
+}  // namespace ww
+
+using namespace ww;
+
+extern "C" {
+
+int ww_ce_loss_f32(const float* logits_dev, const int64_t* labels_dev, int64_t n, float* dlogits_dev, float* loss_dev, ww_loss_stats* stats_dev,
+                   ww_stream_t stream) {
+    if (n <= 0 || n > (int64_t(1) << 30)) return fail(WW_EINVAL, "n %lld: expected 1..2^30", (long long)n);
+    if (!logits_dev || !labels_dev) return fail(WW_EINVAL, "null logits / labels pointer");
+    if ((reinterpret_cast<uintptr_t>(logits_dev) & 3) || (reinterpret_cast<uintptr_t>(dlogits_dev) & 3) || (reinterpret_cast<uintptr_t>(loss_dev) & 3))
+        return fail(WW_EINVAL, "logits_dev / dlogits_dev / loss_dev must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(labels_dev) & 7) || (reinterpret_cast<uintptr_t>(stats_dev) & 7))
+        return fail(WW_EINVAL, "labels_dev / stats_dev must be 8-byte aligned");
+    if (int rc = require_gfx950()) return rc;
+    return launch_ce_loss(logits_dev, labels_dev, n, dlogits_dev, loss_dev, stats_dev, static_cast<hipStream_t>(stream));
+}
+
+int ww_adam_step_f32(const ww_adam_tensor* tensors_host, int64_t n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
+                     int64_t step, const float* grad_scale_dev, ww_stream_t stream) {
+    if (!(lr >= 0.0) || std::isinf(lr)) return fail(WW_EINVAL, "lr %g: expected a finite value >= 0", lr);
+    if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail(WW_EINVAL, "beta1 %g: expected [0, 1)", beta1);
+    if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail(WW_EINVAL, "beta2 %g: expected [0, 1)", beta2);
+    if (!(eps > 0.0) || std::isinf(eps)) return fail(WW_EINVAL, "eps %g: expected a finite value > 0", eps);
+    if (!(weight_decay >= 0.0) || std::isinf(weight_decay)) return fail(WW_EINVAL, "weight_decay %g: expected a finite value >= 0", weight_decay);
+    if (step < 1) return fail(WW_EINVAL, "step %lld: expected >= 1", (long long)step);
+    if (int rc = check_table(tensors_host, n_tensors, true)) return rc;
+    if (reinterpret_cast<uintptr_t>(grad_scale_dev) & 3) return fail(WW_EINVAL, "grad_scale_dev must be 4-byte aligned");
+    // the bias corrections in double, as torch computes them, then one rounding to the kernel's float32
+    const double c1 = 1.0 - std::pow(beta1, double(step)), c2 = 1.0 - std::pow(beta2, double(step));
+    AdamScalars s;
+    s.lr_c1 = float(lr / c1);
+    s.inv_c2_sqrt = float(1.0 / std::sqrt(c2));
+    s.eps = float(eps);
+    s.omb1 = float(1.0 - beta1);
+    s.beta2 = float(beta2);
+    s.omb2 = float(1.0 - beta2);
+    s.weight_decay = float(weight_decay);
+    if (int rc = require_gfx950()) return rc;
+    return launch_adam(tensors_host, int(n_tensors), s, grad_scale_dev, static_cast<hipStream_t>(stream));
+}
+
+int64_t ww_grad_norm_workspace_bytes(const ww_adam_tensor* tensors_host, int64_t n_tensors) {
+    if (int rc = check_table(tensors_host, n_tensors, false)) return rc;
+    return up256(norm_blocks(tensors_host, int(n_tensors)) * int64_t(sizeof(double)));
+}
+
+int ww_grad_norm_f32(const ww_adam_tensor* tensors_host, int64_t n_tensors, double max_norm, double* norm_dev, float* scale_dev, void* workspace_dev,
+                     ww_stream_t stream) {
+    if (!(max_norm > 0.0)) return fail(WW_EINVAL, "max_norm %g: expected > 0 (infinity: measure without clipping)", max_norm);
+    if (int rc = check_table(tensors_host, n_tensors, false)) return rc;
+    if (!norm_dev || !scale_dev || !workspace_dev) return fail(WW_EINVAL, "null norm / scale / workspace pointer");
+    if ((reinterpret_cast<uintptr_t>(norm_dev) & 7) || (reinterpret_cast<uintptr_t>(scale_dev) & 3) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
+        return fail(WW_EINVAL, "norm_dev must be 8-byte, scale_dev 4-byte and workspace_dev 256-byte aligned");
+    if (int rc = require_gfx950()) return rc;
+    return launch_grad_norm(tensors_host, int(n_tensors), max_norm, norm_dev, scale_dev, workspace_dev, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -798,3 +798,131 @@ def reverb(pcm: torch.Tensor, rirs, index) -> torch.Tensor:
                                         C.c_void_p(ws.data_ptr()), stream))
         ws.record_stream(torch.cuda.current_stream())
     return out
+
+
+# ---- loss, metrics and optimiser of the training loop (csrc/ww_optim.hip) ---------------------------------
+LOSS_STATS_FIELDS = ("loss_sum", "correct", "total", "batches", "bad_labels", "nonfinite")
+
+
+def new_loss_stats(device) -> torch.Tensor:
+    """A zeroed ww_loss_stats record in device memory: six 8-byte words (the first a float64); `stats.zero_()` starts a new epoch."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"loss stats on {device}: this path has no CPU implementation")
+    return torch.zeros(len(LOSS_STATS_FIELDS), device=device, dtype=torch.int64)
+
+
+def _check_stats(stats, like: torch.Tensor) -> None:
+    if (not isinstance(stats, torch.Tensor) or stats.dtype != torch.int64 or stats.shape != (len(LOSS_STATS_FIELDS),)
+            or not stats.is_contiguous()):
+        raise TypeError("stats: expected the record ops.new_loss_stats() makes (int64 [6], contiguous)")
+    if stats.device != like.device:
+        raise RuntimeError(f"stats on {stats.device}, logits on {like.device}")
+
+
+def read_loss_stats(stats: torch.Tensor) -> dict:
+    """The record on the host: {loss_sum: float, correct, total, batches, bad_labels, nonfinite: int}.  One device-to-host copy."""
+    host = stats.cpu()
+    out = {k: int(v) for k, v in zip(LOSS_STATS_FIELDS[1:], host[1:].tolist())}
+    out["loss_sum"] = float(host[:1].view(torch.float64).item())
+    return out
+
+
+def _check_ce(logits, labels):
+    _require_cuda_f32(logits, "logits")
+    if logits.dim() != 2 or logits.shape[1] != 2 or logits.shape[0] == 0 or not logits.is_contiguous():
+        raise ValueError(f"logits: expected contiguous [n >= 1, 2], got {tuple(logits.shape)}")
+    if not isinstance(labels, torch.Tensor):
+        raise TypeError(f"labels: expected a torch.Tensor, got {type(labels).__name__}")
+    if labels.dtype != torch.int64:
+        raise TypeError(f"labels: expected int64, got {labels.dtype}")
+    if labels.device != logits.device:
+        raise RuntimeError(f"labels on {labels.device}, logits on {logits.device}")
+    if labels.dim() == 2 and labels.shape[1] == 1:
+        labels = labels[:, 0]                                # the reference squeezes [B, 1] targets
+    if labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+        raise ValueError(f"labels: expected [{logits.shape[0]}] or [{logits.shape[0]}, 1], got {tuple(labels.shape)}")
+    return labels if labels.stride(0) == 1 or labels.shape[0] == 1 else labels.contiguous()
+
+
+def ce_loss_into(logits, labels, dlogits, loss, stats) -> None:
+    """ww_ce_loss_f32 on caller-owned outputs (each may be None); `labels` as _check_ce returns them.  Allocates nothing."""
+    with torch.cuda.device(logits.device):
+        nat.check(nat.lib.ww_ce_loss_f32(_ptr(logits), _ptr(labels), logits.shape[0], None if dlogits is None else _ptr(dlogits),
+                                         None if loss is None else _ptr(loss), None if stats is None else _ptr(stats), _stream()))
+
+
+def ce_loss(logits: torch.Tensor, labels: torch.Tensor, stats=None, grad: bool = True):
+    """CrossEntropyLoss (mean) over two classes: (loss [] float32, dlogits [n, 2] = (softmax - onehot) / n, or None with grad=False).
+    logits [n, 2] float32 and labels [n] or [n, 1] int64 on the GPU.  `stats` (ops.new_loss_stats) accumulates the batch mean, the correct
+    predictions and the counts of bad labels and non-finite logits on the device; nothing here waits for it."""
+    labels = _check_ce(logits, labels)
+    if stats is not None:
+        _check_stats(stats, logits)
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    dlogits = torch.empty_like(logits) if grad else None
+    ce_loss_into(logits, labels, dlogits, loss, stats)
+    return loss, dlogits
+
+
+def adam_table(params, grads, exp_avgs, exp_avg_sqs):
+    """Four equally long lists of float32 GPU tensors -> a ctypes array of _native.AdamTensor (at most 16 entries).  A grads-only table
+    (the other three None) is what grad_norm reads."""
+    n = len(grads)
+    if not 1 <= n <= nat.ADAM_MAX_TENSORS:
+        raise ValueError(f"{n} tensors: one launch takes 1..{nat.ADAM_MAX_TENSORS}")
+    cols = [grads if c is None else c for c in (params, grads, exp_avgs, exp_avg_sqs)]
+    if any(len(c) != n for c in cols):
+        raise ValueError("params, grads, exp_avgs and exp_avg_sqs differ in length")
+    tab = (nat.AdamTensor * n)()
+    for k, (p, g, m, v) in enumerate(zip(*cols)):
+        for name, t in (("param", p), ("grad", g), ("exp_avg", m), ("exp_avg_sq", v)):
+            _require_cuda_f32(t, f"{name} {k}")
+            if not t.is_contiguous():
+                raise RuntimeError(f"{name} {k} is not contiguous")
+            if t.numel() != p.numel() or t.device != p.device:
+                raise ValueError(f"{name} {k}: {t.numel()} elements on {t.device}, its parameter has {p.numel()} on {p.device}")
+        if p.numel() == 0:
+            raise ValueError(f"param {k} is empty")
+        tab[k].p, tab[k].g, tab[k].m, tab[k].v, tab[k].n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+    return tab
+
+
+def adam_launch(table, device, lr, betas, eps, weight_decay, step, grad_scale=None) -> None:
+    """ww_adam_step_f32 on a prepared adam_table (FusedAdam and the trainer keep theirs between steps).  Allocates nothing."""
+    with torch.cuda.device(device):
+        nat.check(nat.lib.ww_adam_step_f32(table, len(table), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                           int(step), None if grad_scale is None else _ptr(grad_scale), _stream()))
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, *, lr, betas, eps, weight_decay, step, grad_scale=None) -> None:
+    """One launch of torch's single-tensor Adam over up to 16 tensors, in place (ww_adam_step_f32).  `step` is the 1-based count of this
+    update; `grad_scale` (float32 [1] on the GPU, grad_norm's scale) multiplies every gradient inside the kernel.  The parameters are
+    written behind autograd's back: their version counters do not move (optim.FusedAdam bumps them)."""
+    tab = adam_table(params, grads, exp_avgs, exp_avg_sqs)
+    if grad_scale is not None:
+        _require_cuda_f32(grad_scale, "grad_scale")
+        if grad_scale.numel() != 1 or grad_scale.device != grads[0].device:
+            raise ValueError("grad_scale: expected one float32 on the gradients' device")
+    adam_launch(tab, grads[0].device, lr, betas, eps, weight_decay, step, grad_scale)
+
+
+def grad_norm_workspace(table, device) -> torch.Tensor:
+    return torch.empty(max(256, nat.check(nat.lib.ww_grad_norm_workspace_bytes(table, len(table)))), device=device, dtype=torch.uint8)
+
+
+def grad_norm_launch(table, device, max_norm, norm, scale, workspace) -> None:
+    """ww_grad_norm_f32 on a prepared table and caller-owned outputs.  Allocates nothing."""
+    with torch.cuda.device(device):
+        nat.check(nat.lib.ww_grad_norm_f32(table, len(table), float(max_norm), _ptr(norm), _ptr(scale), _ptr(workspace), _stream()))
+
+
+def grad_norm(grads, max_norm: float):
+    """(norm float64 [1], scale float32 [1]) on the GPU: the global L2 norm over `grads` (up to 16 float32 tensors) and clip_grad_norm_'s
+    coefficient min(1, max_norm / (norm + 1e-6)); adam_step(grad_scale=scale) applies it without a host wait."""
+    tab = adam_table(None, grads, None, None)
+    device = grads[0].device
+    norm = torch.empty(1, device=device, dtype=torch.float64)
+    scale = torch.empty(1, device=device, dtype=torch.float32)
+    grad_norm_launch(tab, device, max_norm, norm, scale, grad_norm_workspace(tab, device))
+    return norm, scale

@@ -1,0 +1,252 @@
+"""WakewordTrainer: the reference's training class (wakeword_training_script.py:219-348, notebook cell 9) with the whole batch on HIP.
+
+Same constructor, attributes and methods -- `criterion`, `optimizer`, `scheduler`, the four history lists, `patience`, `best_val_acc`,
+`epochs_no_improve`; `train_epoch`, `validate`, `train` -- and the same checkpoint dict.  What differs is what a batch costs: `step` calls
+the C entry points directly, train forward -> cross-entropy (loss, gradient, running metrics) -> backward -> optional gradient-norm clip
+-> Adam, without autograd, without a torch kernel in between, without a device-to-host copy and, after the first call at a batch size,
+without an allocation.  The epoch's loss and accuracy are kept on the device and read once, at the end of the epoch.
+
+One deliberate difference: the reference calls `clip_grad_norm_` BEFORE `backward()`, where it clips the previous batch's gradients or
+nothing, so the default here is no clipping; `max_grad_norm=1.0` gives the clip the call meant, after the
+backward.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import warnings
+
+import torch
+import torch.nn as nn
+
+from . import _native as nat
+from . import ops
+from .config import TrainingConfig
+from .model import SimpleWakewordModel, WakewordModel
+from .optim import FusedAdam
+
+
+class WakewordTrainer:
+    def __init__(self, model, device, config=TrainingConfig, *, checkpoint_path="best_wakeword_model.pth", max_grad_norm=None):
+        if not isinstance(model, (SimpleWakewordModel, WakewordModel)):
+            raise TypeError(f"WakewordTrainer drives the HIP training kernels of SimpleWakewordModel and WakewordModel; got {type(model).__name__}")
+        if any(p.device.type != "cuda" for p in model.parameters()):
+            raise TypeError("WakewordTrainer: the model's parameters are on the CPU; this path has no CPU implementation (model.to('cuda'))")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"max_grad_norm {max_grad_norm}: expected a positive number or None")
+        self.model = model
+        self.device = device
+        self.config = config
+        self.checkpoint_path = checkpoint_path
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+
+        self.criterion = nn.CrossEntropyLoss().to(device)             # the reference's attribute; `step` computes the same loss in ww_ce_loss_f32
+        self.optimizer = FusedAdam(model.parameters(), lr=config.LEARNING_RATE, weight_decay=1e-5)
+        self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="max", factor=0.5, patience=5)
+
+        self.train_losses = []
+        self.val_losses = []
+        self.train_accuracies = []
+        self.val_accuracies = []
+
+        self.patience = 10
+        self.best_val_acc = 0.0
+        self.epochs_no_improve = 0
+
+        # ---- persistent device state of `step` ----
+        self._n_conv = model._n_conv
+        self._keys = ops._train_keys(self._n_conv)
+        named = dict(model.named_parameters())
+        self._params = [named[k] for k in self._keys]
+        for p in self._params:
+            ops._require_cuda_f32(p, "parameter")
+            if not p.is_contiguous():
+                raise RuntimeError("WakewordTrainer: a parameter is not contiguous")
+        self._dev = self._params[0].device
+        self._grads = {}
+        self._bind_grads()
+        self.train_stats = ops.new_loss_stats(self._dev)
+        self.val_stats = ops.new_loss_stats(self._dev)
+        self.last_loss = torch.zeros((), device=self._dev, dtype=torch.float32)       # the newest batch's mean loss, on the device
+        self._cap = 0                                                                  # clips the batch buffers hold
+        self._logits = self._dlogits = None
+        self._ws = None
+        self._norm = self._scale = self._norm_ws = self._norm_tables = None
+        if self.max_grad_norm is not None:
+            self._norm = torch.zeros(1, device=self._dev, dtype=torch.float64)
+            self._scale = torch.ones(1, device=self._dev, dtype=torch.float32)
+
+    # ---- gradients: one persistent buffer per parameter, bound once ----
+    def _bind_grads(self) -> None:
+        """p.grad of every parameter is a buffer the backward kernel writes.  bias_hh_l*.grad IS bias_ih_l*.grad (the two gradients are
+        equal); weight_hh_l*.grad is zeroed here and never written (h0 = 0 makes it exactly zero) -- Adam's weight decay still reaches
+        weight_hh through it, as in the reference."""
+        for k, p in zip(self._keys, self._params):
+            if k.startswith("lstm.bias_hh"):
+                continue
+            if k not in self._grads:
+                self._grads[k] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            p.grad = self._grads[k]
+        for k, p in zip(self._keys, self._params):
+            if k.startswith("lstm.bias_hh"):
+                p.grad = self._grads[k.replace("bias_hh", "bias_ih")]
+        g = self._grads
+        tg = nat.TrainGrads()
+        for i in range(self._n_conv):
+            tg.conv_weight[i], tg.conv_bias[i] = g[f"conv{i + 1}.weight"].data_ptr(), g[f"conv{i + 1}.bias"].data_ptr()
+        for layer in range(2):
+            tg.lstm_weight_ih[layer], tg.lstm_bias[layer] = g[f"lstm.weight_ih_l{layer}"].data_ptr(), g[f"lstm.bias_ih_l{layer}"].data_ptr()
+        tg.fc_weight, tg.fc_bias = g["fc.weight"].data_ptr(), g["fc.bias"].data_ptr()
+        self._tg = tg
+        self._tp = ops._train_params_struct(self._params, self._n_conv)
+        self._tp_key = tuple(p.data_ptr() for p in self._params)
+
+    def _grads_bound(self) -> bool:
+        for k, p in zip(self._keys, self._params):
+            if p.grad is not self._grads[k.replace("bias_hh", "bias_ih")]:
+                return False
+        return self._tp_key == tuple(p.data_ptr() for p in self._params)
+
+    def _norm_step(self) -> None:
+        """Global L2 norm over every parameter's gradient (a bias gradient counts for both its parameters, as clip_grad_norm_ counts
+        it) -> self._norm and self._scale, on the device.  The two models have 14 and 16 parameters: one table."""
+        if self._norm_tables is None:
+            self._norm_tables = ops.adam_table(None, [p.grad for p in self._params], None, None)
+            self._norm_ws = ops.grad_norm_workspace(self._norm_tables, self._dev)
+        ops.grad_norm_launch(self._norm_tables, self._dev, self.max_grad_norm, self._norm, self._scale, self._norm_ws)
+
+    def _target(self, target, B):
+        if not isinstance(target, torch.Tensor):
+            raise TypeError(f"target: expected a torch.Tensor, got {type(target).__name__}")
+        if target.device != self._dev:
+            target = target.to(self._dev)
+        if target.dtype != torch.int64:
+            if target.dtype.is_floating_point or target.dtype == torch.bool:
+                raise TypeError(f"target: expected integer class labels, got {target.dtype}")
+            target = target.to(torch.int64)
+        if target.dim() == 2 and target.shape[1] == 1:
+            target = target[:, 0]
+        if target.dim() != 1 or target.shape[0] != B:
+            raise ValueError(f"target: expected [{B}] or [{B}, 1], got {tuple(target.shape)}")
+        return target if target.stride(0) == 1 or B == 1 else target.contiguous()
+
+    def step(self, data, target) -> torch.Tensor:
+        """One training batch: data [B, 1, 80, T <= 32] float32 and target [B] or [B, 1] int64, both on the GPU (tensors elsewhere, or of
+        another integer type, are copied first).  Returns the batch's mean loss as a 0-d tensor ON THE DEVICE (self.last_loss, overwritten
+        by the next step); the running metrics are in self.train_stats.  The model must be in train mode."""
+        if not self.model.training:
+            raise RuntimeError("WakewordTrainer.step: the model is in eval mode (train_epoch calls model.train())")
+        if isinstance(data, torch.Tensor) and data.device != self._dev:
+            data = data.to(self._dev)
+        if isinstance(data, torch.Tensor) and data.dim() == 4 and data.shape[3] > 32:
+            raise NotImplementedError(f"training at T = {data.shape[3]} frames is not supported yet: the training kernels take 1..32 "
+                                      "(clips of up to 1 s); clips of up to 2 s run in eval mode only")
+        x = ops._check_x(data)
+        B, T = x.shape[0], x.shape[3]
+        if B == 0:
+            raise ValueError("empty training batch")
+        y = self._target(target, B)
+        if not self._grads_bound():                          # optimizer.zero_grad() or a .to(): bind the buffers again
+            self._bind_grads()
+            self._norm_tables = None
+        # the dropout seed exactly as _CnnLstm.forward draws it: one randint from torch's CPU generator
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        math = nat.lib.ww_get_train_math()                   # resolved once: query, forward and backward of this step get this value
+        need = nat.check(nat.lib.ww_train_workspace_bytes(B, self._n_conv, math))
+        with torch.cuda.device(self._dev):
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None                              # release before growing
+                self._ws = torch.empty(need, device=self._dev, dtype=torch.uint8)
+            if B > self._cap:
+                self._logits = torch.empty((B, 2), device=self._dev, dtype=torch.float32)
+                self._dlogits = torch.empty((B, 2), device=self._dev, dtype=torch.float32)
+                self._cap = B
+            stream = ops._stream()
+            m = self.model
+            nat.check(nat.lib.ww_train_forward_f32(ops._ptr(x), B, T, C.byref(self._tp), float(m.lstm.dropout), float(m.dropout.p),
+                                                   seed & (2 ** 64 - 1), math, ops._ptr(self._ws), self._ws.numel(), ops._ptr(self._logits),
+                                                   stream))
+            nat.check(nat.lib.ww_ce_loss_f32(ops._ptr(self._logits), ops._ptr(y), B, ops._ptr(self._dlogits), ops._ptr(self.last_loss),
+                                             ops._ptr(self.train_stats), stream))
+            nat.check(nat.lib.ww_train_backward_f32(ops._ptr(x), B, T, C.byref(self._tp), ops._ptr(self._dlogits), math, ops._ptr(self._ws),
+                                                    self._ws.numel(), C.byref(self._tg), stream))
+            if self.max_grad_norm is not None:
+                self._norm_step()
+        self.optimizer.step(grad_scale=self._scale if self.max_grad_norm is not None else None)
+        return self.last_loss
+
+    @property
+    def last_logits(self) -> torch.Tensor:
+        """The newest step's train-mode logits [B, 2] (a view of the persistent buffer, overwritten by the next step)."""
+        return self._logits
+
+    def _finish_epoch(self, stats, what):
+        s = ops.read_loss_stats(stats)                       # the epoch's one device-to-host copy
+        if s["bad_labels"] > 0:
+            raise ValueError(f"{what}: {s['bad_labels']} of {s['total']} labels lie outside {{0, 1}} (they were left out of loss and gradient)")
+        if s["nonfinite"] > 0:
+            warnings.warn(f"{what}: {s['nonfinite']} of {s['total']} clips had a non-finite logit", RuntimeWarning, stacklevel=3)
+        if s["batches"] == 0:
+            raise ValueError(f"{what}: the loader gave no batch")
+        return s["loss_sum"] / s["batches"], 100.0 * s["correct"] / s["total"]
+
+    def train_epoch(self, train_loader):
+        self.model.train()
+        self.train_stats.zero_()
+        for data, target in train_loader:
+            self.step(data, target)
+        return self._finish_epoch(self.train_stats, "train_epoch")
+
+    def validate(self, val_loader):
+        self.model.eval()
+        self.val_stats.zero_()
+        with torch.no_grad():
+            for data, target in val_loader:
+                if data.device != self._dev:
+                    data = data.to(self._dev)
+                output = self.model(data)
+                y = self._target(target, output.shape[0])
+                ops.ce_loss_into(output, y, None, None, self.val_stats)
+        return self._finish_epoch(self.val_stats, "validate")
+
+    def train(self, train_loader, val_loader, epochs):
+        print(f"Starting training for {epochs} epochs...")
+        print(f"Using device: {self.device}")
+        print(f"Learning rate: {self.config.LEARNING_RATE}")
+        print(f"Batch size: {self.config.BATCH_SIZE}")
+
+        self.best_val_acc = 0.0
+        self.epochs_no_improve = 0
+        epoch = -1
+        for epoch in range(epochs):
+            print(f"\nEpoch {epoch + 1}/{epochs}")
+            print(f"GPU Memory: {torch.cuda.memory_allocated() / 1e6:.1f}MB allocated, {torch.cuda.memory_reserved() / 1e6:.1f}MB reserved")
+
+            train_loss, train_acc = self.train_epoch(train_loader)
+            val_loss, val_acc = self.validate(val_loader)
+            self.train_losses.append(train_loss)
+            self.val_losses.append(val_loss)
+            self.train_accuracies.append(train_acc)
+            self.val_accuracies.append(val_acc)
+            print(f"Train Loss: {train_loss:.4f}, Train Acc: {train_acc:.2f}%")
+            print(f"Val Loss: {val_loss:.4f}, Val Acc: {val_acc:.2f}%")
+
+            self.scheduler.step(val_acc)
+
+            if val_acc > self.best_val_acc:
+                self.best_val_acc = val_acc
+                self.epochs_no_improve = 0
+                torch.save({"epoch": epoch, "model_state_dict": self.model.state_dict(), "optimizer_state_dict": self.optimizer.state_dict(),
+                            "val_acc": val_acc, "train_acc": train_acc, "train_loss": train_loss, "val_loss": val_loss}, self.checkpoint_path)
+                print(f"New best model saved! Validation accuracy: {val_acc:.2f}%")
+            else:
+                self.epochs_no_improve += 1
+
+            if self.epochs_no_improve >= self.patience:
+                print(f"\nEarly stopping triggered! No improvement for {self.patience} epochs.")
+                print(f"Best validation accuracy: {self.best_val_acc:.2f}%")
+                break
+
+        print("\nTraining completed!")
+        print(f"Best validation accuracy: {self.best_val_acc:.2f}%")
+        print(f"Total epochs trained: {epoch + 1}")
+        return self.best_val_acc
