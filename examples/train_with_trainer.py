@@ -5,6 +5,7 @@ The training files live in a ClipBank on the GPU and
 Adam as HIP kernels without a wait on the device (section 3h); the epoch's loss and accuracy are read once per epoch.
 
     PYTHONPATH=. python examples/train_with_trainer.py [--epochs 10] [--data DIR] [--duration 1.0] [--background DIR] [--max-grad-norm 1.0]
+                                                        [--spec-augment]
 """
 import argparse
 import glob
@@ -15,8 +16,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from train_from_files import split  # noqa: E402
-from wakeword_jupyterlab_amd import (AudioConfig, AudioProcessor, DataLoader, TrainingConfig, WakewordDataset, WakewordModel,  # noqa: E402
-                                     WakewordTrainer)
+from wakeword_jupyterlab_amd import (AudioConfig, AudioProcessor, DataLoader, SpecAugmentConfig, TrainingConfig, WakewordDataset,  # noqa: E402
+                                     WakewordModel, WakewordTrainer)
 from wakeword_jupyterlab_amd.synth import create_sample_data  # noqa: E402
 
 
@@ -29,6 +30,7 @@ def main():
     ap.add_argument("--duration", type=float, default=AudioConfig.DURATION, help="clip length in seconds, 0.25 .. 1.0")
     ap.add_argument("--background", default=None, help="directory of background noise files (WAV / FLAC) mixed into the training clips")
     ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm after the backward (default: off)")
+    ap.add_argument("--spec-augment", action="store_true", help="mask blocks of mel bins and frames of every training batch (SpecAugment)")
     a = ap.parse_args()
     device = torch.device("cuda")
     print(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
@@ -45,6 +47,8 @@ def main():
     processor = AudioProcessor(audio_config)
     if a.background:
         processor.set_background_noise(a.background)
+    if a.spec_augment:
+        processor.set_spec_augment(SpecAugmentConfig)                             # training loader only: the others run with augment=False
     model = WakewordModel(audio_config=audio_config).to(device)
     print(f"Parameters: {sum(p.numel() for p in model.parameters()):,}")
     bank = WakewordDataset(w_tr, n_tr, processor, augment=True).cache()           # every training file decoded once, onto the GPU

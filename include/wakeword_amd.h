@@ -397,6 +397,46 @@ WW_API int ww_logmel_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_str
 WW_API int ww_logmel_frames_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples,
                                 int normalize, float* logmel_dev, ww_stream_t stream);
 
+/* ---- SpecAugment: time and frequency masks on log-mel batches ------------- */
+/* The one augmentation on the feature side of K1 (the reference has none): blocks of mel bands and blocks of frames of a clip are
+ * replaced by one fill value.  mel_in / mel_out [n][80][width] float32 as K1 writes them, width = 1 .. WW_MAX_FRAMES, 16-byte aligned.
+ * Each clip has one record of WW_SPEC_RECORD_INT16 int16 (ww_spec_augment_record_bytes() = 32 bytes, 16-byte aligned):
+ *   [f_start, f_width] x WW_SPEC_MAX_MASKS, then [t_start, t_width] x WW_SPEC_MAX_MASKS; a width of 0 means no mask.
+ * Position (row, col) of a clip is masked iff row lies in any [f_start, f_start + f_width) or col in any [t_start, t_start + t_width).
+ * Masks may overlap and may cover the whole clip; what a record names outside the clip masks nothing.
+ * Unmasked positions keep the input's bits.  Every masked position of a clip gets the same fill value:
+ *   WW_SPEC_FILL_MEAN   the mean over all 80 width values of the clip BEFORE masking: float64 sums in an order that width alone fixes
+ *                       (never the clip's place in the batch or n), rounded once to float32 -- within one float32 ulp of the exact mean
+ *   WW_SPEC_FILL_MIN    the clip's minimum before masking (an fminf fold: a NaN is passed over)
+ *   WW_SPEC_FILL_VALUE  fill_value
+ * mel_out == mel_in is allowed: a clip without masks is then neither read nor written, only masked positions are written, and
+ * WW_SPEC_FILL_VALUE reads nothing of the clip.  Buffers that overlap in any other way are WW_EINVAL.
+ * Records: records_dev [n][16] filled by the caller, or NULL = drawn inside the kernel from a counter-based generator (splitmix64, the
+ * stream of the training step's dropout masks), so that a batch costs the host one 64-bit seed.  With uint64 wrapping arithmetic:
+ *   r(c, j) = fmix64(seed + 0x9E3779B97F4A7C15 * (32 c + j + 1))     fmix64: x ^= x >> 30, x *= 0xBF58476D1CE4E5B9, x ^= x >> 27,
+ *                                                                            x *= 0x94D049BB133111EB, x ^= x >> 31
+ *   int_in(r, m) = ((r >> 32) * (m + 1)) >> 32                       an integer in 0 .. m
+ *   j = 0           u = float(r >> 40) * 2^-24; the clip is masked at all iff u < prob, otherwise its record is all zeros
+ *   j = 1 + 2 i, 2 + 2 i   frequency mask i < n_freq: f_width = int_in(r, freq_max), f_start = int_in(r', 80 - f_width)
+ *   j = 9 + 2 i, 10 + 2 i  time mask i < n_time:      t_width = int_in(r, time_max), t_start = int_in(r', width - t_width)
+ * c is the clip's index in the batch: clip c's record does not depend on n.  ww_spec_augment_draw writes exactly those records (what a
+ * caller or a test reads the plans back through, as ww_train_masks is for dropout).
+ * Both launches are asynchronous, allocate and copy nothing and are capturable; n == 0 is WW_OK without a launch.  Checked before any
+ * HIP call: width outside 1 .. WW_MAX_FRAMES (WW_EUNSUPPORTED); n outside 0 .. 2^30, a null or misaligned pointer, n_freq or n_time
+ * outside 0 .. WW_SPEC_MAX_MASKS, freq_max outside 0 .. 80, time_max outside 0 .. width, prob outside [0, 1], an unknown fill mode,
+ * partially overlapping buffers (WW_EINVAL).  The generator's arguments are checked with records_dev given too (pass zeros). */
+#define WW_SPEC_MAX_MASKS 4
+#define WW_SPEC_RECORD_INT16 16
+#define WW_SPEC_FILL_MEAN 0
+#define WW_SPEC_FILL_MIN 1
+#define WW_SPEC_FILL_VALUE 2
+WW_API int64_t ww_spec_augment_record_bytes(void);
+WW_API int ww_spec_augment_draw(uint64_t seed, int64_t n, int32_t width, float prob, int32_t n_freq, int32_t freq_max, int32_t n_time,
+                                int32_t time_max, int16_t* records_dev, ww_stream_t stream);
+WW_API int ww_spec_augment_f32(const float* mel_in, float* mel_out, int64_t n, int32_t width, const int16_t* records_dev, uint64_t seed,
+                               float prob, int32_t n_freq, int32_t freq_max, int32_t n_time, int32_t time_max, int32_t fill_mode,
+                               float fill_value, ww_stream_t stream);
+
 /* ---- weights ------------------------------------------------------------------------------ */
 /* The reference state_dict (train_wakeword.py:28-36 / wakeword_training_script.py:141-165) as
  * host pointers in torch layout.  conv3_* are NULL for SimpleWakewordModel.  weight_hh_l* are not

@@ -21,7 +21,7 @@ def __getattr__(name):
     lazy = {"AudioProcessor": "audio", "WakewordDataset": "dataset", "DataLoader": "dataset", "SimpleWakewordModel": "model",
             "WakewordModel": "model", "StreamingDetector": "streaming", "predict_wakeword": "inference",
             "evaluate": "inference", "AudioConfig": "config", "ModelConfig": "config", "Config": "config",
-            "AugmentationConfig": "config", "BackgroundNoiseBank": "background", "ClipBank": "bank",
+            "AugmentationConfig": "config", "SpecAugmentConfig": "config", "BackgroundNoiseBank": "background", "ClipBank": "bank",
             "ImpulseResponseBank": "reverb", "scan_files": "scan", "det_curve": "scan", "Scan": "scan", "TrainingConfig": "config", "FusedAdam": "optim",
             "WakewordTrainer": "trainer"}
     if name in lazy:

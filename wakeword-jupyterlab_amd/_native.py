@@ -103,6 +103,8 @@ class BankItem(C.Structure):
 
 
 BANK_NORM_NONE, BANK_NORM_ENTRY, BANK_NORM_WINDOW = 0, 1, 2
+SPEC_RECORD_INT16 = 16
+SPEC_FILL_MEAN, SPEC_FILL_MIN, SPEC_FILL_VALUE = 0, 1, 2
 
 
 class LossStats(C.Structure):
@@ -218,6 +220,11 @@ PROTOTYPES = {
     "ww_bank_gather_workspace_bytes": (C.c_int64, [C.c_int64]),
     "ww_bank_gather_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                      C.c_void_p]),
+    "ww_spec_augment_record_bytes": (C.c_int64, []),
+    "ww_spec_augment_draw": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_void_p]),
+    "ww_spec_augment_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_uint64, C.c_float, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "ww_train_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "ww_train_forward_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(TrainParams), C.c_float, C.c_float, C.c_uint64, C.c_int32,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

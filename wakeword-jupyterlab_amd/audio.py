@@ -16,6 +16,7 @@ T <= 32 (DURATION 0.25 .. 1.0, N = 4000 .. 16000 samples), and refuses longer cl
                                  (random draws from python `random` in the reference's order)  <- HIP kernels KA
   set_background_noise(paths) -> background noise at a random SNR, mixed in after the stretch (background.py; not in the reference)
   set_room_impulse_responses(paths) -> reverberation with a random room impulse response, before the background (reverb.py; idem)
+  set_spec_augment(config)    -> SpecAugment: blocks of mel bins and of frames masked on the log-mel batch, after K1 (idem)
 `load_audio` / `process_audio_file` read the file with the library's native reader (csrc/ww_files.cpp) and decode, mix down and
 resample it on the GPU (kernel K0: scipy.signal.resample_poly's Kaiser design -- NOT librosa's soxr resampler, an absent third-party
 library: parity unpinned) -- the same code path as the batched loaders, one file at a time.  PCM / float WAV and FLAC.
@@ -166,6 +167,39 @@ class AudioProcessor:
         """The attached reverb.ImpulseResponseBank, or None."""
         return getattr(self, "_rirs", None)
 
+    def set_spec_augment(self, config):
+        """Turn SpecAugment on (a config.SpecAugmentConfig, or a class with its fields; validated here) or off (`None`, the default).
+        From then on everything of this processor that augments -- process_audio_file(augment=True), WakewordDataset(augment=True) per
+        item and through loader() / batches(), ClipBank loaders with augment=True -- follows the log-mel with one in-place masking
+        launch whose seed is one `random.getrandbits(64)` per batch, drawn after augment_batch's draws.  Nothing that runs with
+        augment=False draws or launches anything more.  Returns the config (or None)."""
+        if config is not None:
+            from .config import check_spec_augment_config
+            check_spec_augment_config(config)
+        self._spec_augment = config
+        return config
+
+    @property
+    def spec_augment(self):
+        """The SpecAugment config in force, or None."""
+        return getattr(self, "_spec_augment", None)
+
+    def spec_augment_batch(self, mel, plans=None, seed=None, inplace=False) -> torch.Tensor:
+        """mel [B, 1, 80, T] or [B, 80, T] on the GPU -> the masked batch, with the config in force (config.SpecAugmentConfig when none
+        is set).  `plans`: a list of {"freq": [(start, width), ...], "time": [...]} per clip (ops.pack_spec_plans); else the records
+        are drawn on the device from `seed`, which is `random.getrandbits(64)` when not given."""
+        from .config import SpecAugmentConfig
+        config = self.spec_augment or SpecAugmentConfig
+        out = mel if inplace else None
+        if plans is not None:
+            if seed is not None:
+                raise ValueError("spec_augment_batch: give `plans` or `seed`, not both")
+            records = torch.from_numpy(ops.pack_spec_plans(plans, mel.shape[-1])).to(mel.device)
+            return ops.spec_augment(mel, records=records, config=config, out=out)
+        if seed is None:
+            seed = random.getrandbits(64)
+        return ops.spec_augment(mel, seed=seed, config=config, out=out)
+
     def augment_batch(self, pcm, plans=None, config=AugmentationConfig) -> torch.Tensor:
         """pcm [B, N] (ndarray or tensor) -> augmented device tensor [B, N]; one plan per clip (drawn here if None).
         N = 16000 at 1 s; any configured clip length of at most 32 frames (DURATION 0.25 .. 1.0)."""
@@ -190,7 +224,8 @@ class AudioProcessor:
 
     def process_audio_file(self, file_path, augment=False):
         """load -> normalise over the whole file -> random crop / zero pad -> (augment) -> log-mel (:125-138), all on the GPU:
-        native reader -> K0 -> (KA) -> K1.  The random draws are python `random`'s in the reference's order (crop, then augmentation)."""
+        native reader -> K0 -> (KA) -> K1 -> (SpecAugment, when set_spec_augment is on).  The random draws are python `random`'s in
+        the reference's order (crop, then augmentation, then the masking seed)."""
         if augment:
             self._check_augment()
         pcm, ok = self.load_clips_gpu([file_path])
@@ -198,7 +233,10 @@ class AudioProcessor:
             return None
         if augment:
             pcm = self.augment_batch(pcm)
-        return self.mel_batch(pcm, normalize=False)[0, 0].cpu().numpy()
+        mel = self.mel_batch(pcm, normalize=False)
+        if augment and self.spec_augment is not None:
+            self.spec_augment_batch(mel, inplace=True)
+        return mel[0, 0].cpu().numpy()
 
     # ---- batched form ---------------------------------------------------------------------------
     def mel_batch(self, pcm, normalize: bool = True) -> torch.Tensor:

@@ -361,7 +361,8 @@ class ClipBank:
 class BankLoader:
     """One epoch = the bank's items (ClipBank.item_entries), in order or in a fresh `torch.randperm` per epoch.  Per batch, in this order:
     the starts of its items in batch order (python `random`), the gather, `processor.augment_batch` when augmenting (which draws its
-    plans), `processor.mel_batch(pcm, normalize=False)`, rows of placeholders set to 0.0 -- the draw order of the file loader, so a
+    plans), `processor.mel_batch(pcm, normalize=False)`, `processor.spec_augment_batch(data, inplace=True)` when augmenting with
+    `processor.set_spec_augment` on (which draws its seed), rows of placeholders set to 0.0 -- the draw order of the file loader, so a
     seeded epoch over the same files yields the same batches bit for bit."""
 
     def __init__(self, bank, batch_size=16, shuffle=False, drop_last=False, augment=False):
@@ -393,6 +394,8 @@ class BankLoader:
             if self.augment:
                 pcm = proc.augment_batch(pcm)
             data = proc.mel_batch(pcm, normalize=False)
+            if self.augment and getattr(proc, "spec_augment", None) is not None:
+                proc.spec_augment_batch(data, inplace=True)
             bad = ~bank.ok[entries]
             if bad.any():
                 data[torch.from_numpy(bad).to(data.device)] = 0.0

@@ -36,6 +36,44 @@ class AugmentationConfig:
     RIR_PROB = 0.5
 
 
+class SpecAugmentConfig:
+    """Time and frequency masks on the log-mel batch (AudioProcessor.set_spec_augment; not in the reference).  These values are this
+    project's choices, not a published recipe's: a clip is masked at all with PROB, then gets FREQ_MASKS bands of 0 .. FREQ_MASK_MAX mel
+    bins and TIME_MASKS blocks of 0 .. int(TIME_MASK_MAX_FRACTION * T) frames (4 frames at T = 32, 1 at T = 8, 7 at T = 63)."""
+    PROB = 0.8
+    FREQ_MASKS = 2
+    FREQ_MASK_MAX = 12
+    TIME_MASKS = 2
+    TIME_MASK_MAX_FRACTION = 0.125
+    FILL = "mean"             # "mean" or "min" of the clip before masking, or a float
+
+
+SPEC_MAX_MASKS = 4            # masks per axis one record holds (csrc/ww_specaug.hip)
+
+
+def check_spec_augment_config(cfg) -> None:
+    """ValueError for what the masking kernel refuses: PROB outside [0, 1], more than 4 masks per axis, a band wider than the 80 mel
+    bins, a fraction outside [0, 1] (a block wider than the clip), a FILL that is neither "mean", "min" nor a number."""
+    import math
+    prob, frac = float(cfg.PROB), float(cfg.TIME_MASK_MAX_FRACTION)
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"SpecAugment PROB {cfg.PROB}: expected a probability in [0, 1]")
+    for name in ("FREQ_MASKS", "TIME_MASKS"):
+        v = getattr(cfg, name)
+        if int(v) != v or not 0 <= v <= SPEC_MAX_MASKS:
+            raise ValueError(f"SpecAugment {name} {v}: expected an integer in 0..{SPEC_MAX_MASKS}")
+    if int(cfg.FREQ_MASK_MAX) != cfg.FREQ_MASK_MAX or not 0 <= cfg.FREQ_MASK_MAX <= AudioConfig.N_MELS:
+        raise ValueError(f"SpecAugment FREQ_MASK_MAX {cfg.FREQ_MASK_MAX}: expected an integer in 0..{AudioConfig.N_MELS}")
+    if not 0.0 <= frac <= 1.0:
+        raise ValueError(f"SpecAugment TIME_MASK_MAX_FRACTION {cfg.TIME_MASK_MAX_FRACTION}: expected a fraction in [0, 1]")
+    fill = cfg.FILL
+    if isinstance(fill, str):
+        if fill not in ("mean", "min"):
+            raise ValueError(f"SpecAugment FILL {fill!r}: expected 'mean', 'min' or a float")
+    elif isinstance(fill, bool) or not isinstance(fill, (int, float)) or math.isnan(float(fill)):
+        raise ValueError(f"SpecAugment FILL {fill!r}: expected 'mean', 'min' or a float")
+
+
 class ModelConfig:            # WakewordModel (3 convs)
     HIDDEN_SIZE = 256
     NUM_LAYERS = 2

@@ -584,6 +584,49 @@ int ww_reverb_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, in
     return launch_reverb(c, rec.data());
 }
 
+// SpecAugment: what the draw and the masking call share, all of it before any HIP call
+static int check_spec(int64_t n, int32_t width, float prob, int32_t n_freq, int32_t freq_max, int32_t n_time, int32_t time_max) {
+    if (width < 1 || width > WW_MAX_FRAMES) return fail(WW_EUNSUPPORTED, "width %d: mel images of 1..%d frames", width, WW_MAX_FRAMES);
+    if (n < 0 || n > (int64_t(1) << 30)) return fail(WW_EINVAL, "n %lld out of range", (long long)n);
+    if (!(prob >= 0.f && prob <= 1.f)) return fail(WW_EINVAL, "prob %g outside [0, 1]", double(prob));
+    if (n_freq < 0 || n_freq > WW_SPEC_MAX_MASKS || n_time < 0 || n_time > WW_SPEC_MAX_MASKS)
+        return fail(WW_EINVAL, "n_freq %d / n_time %d: 0..%d masks per axis", n_freq, n_time, WW_SPEC_MAX_MASKS);
+    if (freq_max < 0 || freq_max > WW_N_MELS) return fail(WW_EINVAL, "freq_max %d outside 0..%d", freq_max, WW_N_MELS);
+    if (time_max < 0 || time_max > width) return fail(WW_EINVAL, "time_max %d outside 0..width = %d", time_max, width);
+    return WW_OK;
+}
+
+int64_t ww_spec_augment_record_bytes(void) { return WW_SPEC_RECORD_INT16 * int64_t(sizeof(int16_t)); }
+
+int ww_spec_augment_draw(uint64_t seed, int64_t n, int32_t width, float prob, int32_t n_freq, int32_t freq_max, int32_t n_time,
+                         int32_t time_max, int16_t* records_dev, ww_stream_t stream) {
+    if (int rc = check_spec(n, width, prob, n_freq, freq_max, n_time, time_max)) return rc;
+    if (n == 0) return WW_OK;
+    if (!records_dev) return fail(WW_EINVAL, "null records pointer");
+    if (reinterpret_cast<uintptr_t>(records_dev) & 15) return fail(WW_EINVAL, "records_dev must be 16-byte aligned");
+    if (int rc = require_gfx950()) return rc;
+    const SpecDraw d = {seed, prob, n_freq, freq_max, n_time, time_max};
+    return launch_spec_draw(d, n, width, records_dev, static_cast<hipStream_t>(stream));
+}
+
+int ww_spec_augment_f32(const float* mel_in, float* mel_out, int64_t n, int32_t width, const int16_t* records_dev, uint64_t seed, float prob,
+                        int32_t n_freq, int32_t freq_max, int32_t n_time, int32_t time_max, int32_t fill_mode, float fill_value,
+                        ww_stream_t stream) {
+    if (int rc = check_spec(n, width, prob, n_freq, freq_max, n_time, time_max)) return rc;
+    if (fill_mode != WW_SPEC_FILL_MEAN && fill_mode != WW_SPEC_FILL_MIN && fill_mode != WW_SPEC_FILL_VALUE)
+        return fail(WW_EINVAL, "unknown fill mode %d", fill_mode);
+    if (n == 0) return WW_OK;
+    if (!mel_in || !mel_out) return fail(WW_EINVAL, "null mel pointer");
+    const uintptr_t a = reinterpret_cast<uintptr_t>(mel_in), b = reinterpret_cast<uintptr_t>(mel_out);
+    if ((a & 15) || (b & 15) || (reinterpret_cast<uintptr_t>(records_dev) & 15))
+        return fail(WW_EINVAL, "mel_in, mel_out and records_dev must be 16-byte aligned");
+    const uintptr_t bytes = uintptr_t(n) * WW_N_MELS * uintptr_t(width) * sizeof(float);
+    if (a != b && a < b + bytes && b < a + bytes) return fail(WW_EINVAL, "mel_in and mel_out overlap partially: pass the same buffer or disjoint ones");
+    if (int rc = require_gfx950()) return rc;
+    const SpecDraw d = {seed, prob, n_freq, freq_max, n_time, time_max};
+    return launch_spec_augment(mel_in, mel_out, n, width, records_dev, d, fill_mode, fill_value, static_cast<hipStream_t>(stream));
+}
+
 int64_t ww_cnn_scratch_bytes(int64_t n, int32_t n_conv) { return cnn_scratch_bytes(n, n_conv); }
 
 int ww_cnn_pool_f32(const float* mel_dev, int64_t n, int32_t width, const float* packed_dev, int32_t n_conv,

@@ -179,6 +179,16 @@ int64_t rir_spectra_workspace_bytes(int64_t n_rirs);
 int launch_rir_spectra(const float* taps, int64_t taps_len, const int64_t* offsets_host, const int32_t* lengths_host, int64_t n_rirs,
                        float* spectra, void* workspace, hipStream_t stream);
 void build_kaiser_best(float* out /*[32769]*/);
+// SpecAugment on log-mel batches (ww_specaug.hip): what the generator needs to draw a clip's record
+struct SpecDraw {
+    uint64_t seed;
+    float prob;
+    int32_t n_freq, freq_max, n_time, time_max;
+};
+int launch_spec_draw(const SpecDraw& d, int64_t n, int T, int16_t* records, hipStream_t stream);
+// records NULL: drawn from `d` inside the kernel; in == out or disjoint (the entry point checks)
+int launch_spec_augment(const float* in, float* out, int64_t n, int T, const int16_t* records, const SpecDraw& d, int mode, float fill_value,
+                        hipStream_t stream);
 int sync_timeouts(unsigned int* count);   // bounded LDS-counter waits that expired (must be 0)
 int launch_cnn_pool(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch,
                     float* pooled, hipStream_t stream);

@@ -3,7 +3,7 @@
 // torch.library (no Meta kernel: FakeTensor tracing / torch.compile of the drop-in modules could not work, and every call paid Python
 // dispatch); this translation unit replaces them.  It is host code only: it validates tensors, allocates outputs with ATen and calls
 //   ww_logmel_f32 / ww_cnn_pool_f32 / ww_lstm_fc_f32 / ww_model_forward_f32 / ww_forward_pcm_f32      (include/wakeword_amd.h)
-// and, for clips of 0.25 s to 2 s, ww_logmel_frames_f32 / ww_cnn_pool_wide_f32 / ww_forward_pcm_frames_f32
+// and, for clips of 0.25 s to 2 s, ww_logmel_frames_f32 / ww_cnn_pool_wide_f32 / ww_forward_pcm_frames_f32, and ww_spec_augment_f32
 // on torch's current HIP stream.  The ww_* functions are neither linked nor looked up by name: the Python package hands their ADDRESSES in
 // (ww_torch_bind, from the ctypes handle of libwakeword_amd.so or of the build named by WW_LIB_OVERRIDE), so nothing enters the global
 // symbol scope -- several builds of the library can live in one process (scripts/ab_kernels.py) without interposing each other's kernels.
@@ -39,8 +39,9 @@ struct Abi {
     decltype(&::ww_cnn_pool_wide_f32) cnn_pool_wide_f32 = nullptr;
     decltype(&::ww_workspace_frames_bytes) workspace_frames_bytes = nullptr;
     decltype(&::ww_forward_pcm_frames_f32) forward_pcm_frames_f32 = nullptr;
+    decltype(&::ww_spec_augment_f32) spec_augment_f32 = nullptr;
 } abi;
-constexpr int kAbiEntries = 14;
+constexpr int kAbiEntries = 15;
 const Abi& bound() {
     TORCH_CHECK(abi.forward_pcm_f32 != nullptr, "wakeword_amd: the operators are not bound to libwakeword_amd.so (import wakeword_jupyterlab_amd does it)");
     return abi;
@@ -59,6 +60,7 @@ const Abi& bound() {
 #define ww_cnn_pool_wide_f32 bound().cnn_pool_wide_f32
 #define ww_workspace_frames_bytes bound().workspace_frames_bytes
 #define ww_forward_pcm_frames_f32 bound().forward_pcm_frames_f32
+#define ww_spec_augment_f32 bound().spec_augment_f32
 
 void* stream_of(const at::Tensor& t) { return static_cast<void*>(c10::hip::getCurrentHIPStream(t.device().index()).stream()); }
 
@@ -228,6 +230,32 @@ at::Tensor forward_pcm_frames_cuda(const at::Tensor& pcm_in, const at::Tensor& p
     return logits;
 }
 
+// SpecAugment, out of place: mel [B, 1, 80, T] or [B, 80, T], records int16 [B, 16] on the same device
+void check_spec_shapes(const at::Tensor& mel, const at::Tensor& records) {
+    TORCH_CHECK(mel.scalar_type() == at::kFloat, "mel: expected float32, got ", mel.scalar_type());
+    TORCH_CHECK((mel.dim() == 4 && mel.size(1) == 1 && mel.size(2) == kMels) || (mel.dim() == 3 && mel.size(1) == kMels),
+                "mel: expected [B, 1, ", kMels, ", T] or [B, ", kMels, ", T], got ", mel.sizes());
+    const int64_t T = mel.size(mel.dim() - 1);
+    TORCH_CHECK_NOT_IMPLEMENTED(T >= 1 && T <= kMaxFrames, "mel: T = ", T, " frames; the masking kernel takes 1..", kMaxFrames);
+    TORCH_CHECK(records.scalar_type() == at::kShort && records.dim() == 2 && records.size(0) == mel.size(0) && records.size(1) == WW_SPEC_RECORD_INT16,
+                "records: expected int16 [", mel.size(0), ", ", WW_SPEC_RECORD_INT16, "], got ", records.scalar_type(), " ", records.sizes());
+    TORCH_CHECK(records.device() == mel.device(), "records on ", records.device(), ", mel on ", mel.device());
+}
+
+at::Tensor spec_augment_cuda(const at::Tensor& mel_in, const at::Tensor& records_in, int64_t fill_mode, double fill_value) {
+    require_cuda_f32(mel_in, "mel");
+    check_spec_shapes(mel_in, records_in);
+    TORCH_CHECK(fill_mode >= WW_SPEC_FILL_MEAN && fill_mode <= WW_SPEC_FILL_VALUE, "fill_mode ", fill_mode, ": 0 = mean, 1 = min, 2 = fill_value");
+    const at::Tensor mel = mel_in.contiguous();
+    at::Tensor records = records_in.contiguous();
+    if (reinterpret_cast<uintptr_t>(records.data_ptr()) % 16) records = records.clone();
+    at::Tensor out = at::empty_like(mel);
+    c10::DeviceGuard guard(mel.device());
+    check_rc(ww_spec_augment_f32(mel.data_ptr<float>(), out.data_ptr<float>(), mel.size(0), int32_t(mel.size(mel.dim() - 1)), records.data_ptr<int16_t>(),
+                                 0, 0.f, 0, 0, 0, 0, int32_t(fill_mode), float(fill_value), stream_of(mel)), "spec_augment");
+    return out;
+}
+
 // ---------------------------------------------------------------- Meta kernels: shapes only (FakeTensor / torch.compile tracing)
 at::Tensor logmel_meta(const at::Tensor& pcm, bool) {
     TORCH_CHECK(pcm.dim() == 2 && pcm.size(1) >= 1 && pcm.size(1) <= kClip, "pcm: expected [B, 1..", kClip, "], got ", pcm.sizes());
@@ -269,6 +297,12 @@ at::Tensor forward_pcm_frames_meta(const at::Tensor& pcm, const at::Tensor&, int
     return at::empty({pcm.size(0), 2}, pcm.options().dtype(at::kFloat));
 }
 
+at::Tensor spec_augment_meta(const at::Tensor& mel, const at::Tensor& records, int64_t fill_mode, double) {
+    check_spec_shapes(mel, records);
+    TORCH_CHECK(fill_mode >= WW_SPEC_FILL_MEAN && fill_mode <= WW_SPEC_FILL_VALUE, "fill_mode ", fill_mode, ": 0 = mean, 1 = min, 2 = fill_value");
+    return at::empty(mel.sizes(), mel.options());
+}
+
 // ---------------------------------------------------------------- CPU: there is none
 [[noreturn]] void no_cpu(const char* name) {
     TORCH_CHECK(false, "wakeword_amd::", name, ": no CPU implementation exists (HIP/gfx950 only); move the tensors to the GPU");
@@ -281,6 +315,7 @@ at::Tensor forward_pcm_cpu(const at::Tensor&, const at::Tensor&, int64_t, bool) 
 at::Tensor logmel_frames_cpu(const at::Tensor&, int64_t, bool) { no_cpu("logmel_frames"); }
 at::Tensor cnn_pool_wide_cpu(const at::Tensor&, const at::Tensor&, int64_t) { no_cpu("cnn_pool_wide"); }
 at::Tensor forward_pcm_frames_cpu(const at::Tensor&, const at::Tensor&, int64_t, int64_t, bool) { no_cpu("forward_pcm_frames"); }
+at::Tensor spec_augment_cpu(const at::Tensor&, const at::Tensor&, int64_t, double) { no_cpu("spec_augment"); }
 
 }  // namespace
 
@@ -298,10 +333,11 @@ at::Tensor forward_pcm_frames_cpu(const at::Tensor&, const at::Tensor&, int64_t,
 #undef ww_cnn_pool_wide_f32
 #undef ww_workspace_frames_bytes
 #undef ww_forward_pcm_frames_f32
+#undef ww_spec_augment_f32
 
 // fns[kAbiEntries]: addresses of ww_last_error, ww_packed_weights_floats, ww_cnn_scratch_bytes, ww_workspace_bytes, ww_logmel_f32,
 // ww_cnn_pool_f32, ww_lstm_fc_f32, ww_model_forward_f32, ww_forward_pcm_f32, ww_logmel_frames_f32, ww_cnn_wide_scratch_bytes, ww_cnn_pool_wide_f32,
-// ww_workspace_frames_bytes, ww_forward_pcm_frames_f32 of ONE build of libwakeword_amd.so.  Returns 0, or -1 on a bad table.
+// ww_workspace_frames_bytes, ww_forward_pcm_frames_f32, ww_spec_augment_f32 of ONE build of libwakeword_amd.so.  Returns 0, or -1 on a bad table.
 extern "C" __attribute__((visibility("default"))) int ww_torch_bind(const void* const* fns, int n) {
     if (!fns || n != kAbiEntries) return -1;
     for (int i = 0; i < n; ++i)
@@ -320,6 +356,7 @@ extern "C" __attribute__((visibility("default"))) int ww_torch_bind(const void* 
     abi.cnn_pool_wide_f32 = reinterpret_cast<decltype(abi.cnn_pool_wide_f32)>(const_cast<void*>(fns[11]));
     abi.workspace_frames_bytes = reinterpret_cast<decltype(abi.workspace_frames_bytes)>(const_cast<void*>(fns[12]));
     abi.forward_pcm_frames_f32 = reinterpret_cast<decltype(abi.forward_pcm_frames_f32)>(const_cast<void*>(fns[13]));
+    abi.spec_augment_f32 = reinterpret_cast<decltype(abi.spec_augment_f32)>(const_cast<void*>(fns[14]));
     return 0;
 }
 
@@ -332,6 +369,7 @@ TORCH_LIBRARY(wakeword_amd, m) {
     m.def("logmel_frames(Tensor pcm, int n_samples, bool normalize=True) -> Tensor");
     m.def("cnn_pool_wide(Tensor x, Tensor packed, int n_conv) -> Tensor");
     m.def("forward_pcm_frames(Tensor pcm, Tensor packed, int n_conv, int n_samples, bool normalize=True) -> Tensor");
+    m.def("spec_augment(Tensor mel, Tensor records, int fill_mode, float fill_value) -> Tensor");
 }
 TORCH_LIBRARY_IMPL(wakeword_amd, CUDA, m) {
     m.impl("logmel", &logmel_cuda);
@@ -342,6 +380,7 @@ TORCH_LIBRARY_IMPL(wakeword_amd, CUDA, m) {
     m.impl("logmel_frames", &logmel_frames_cuda);
     m.impl("cnn_pool_wide", &cnn_pool_wide_cuda);
     m.impl("forward_pcm_frames", &forward_pcm_frames_cuda);
+    m.impl("spec_augment", &spec_augment_cuda);
 }
 TORCH_LIBRARY_IMPL(wakeword_amd, Meta, m) {
     m.impl("logmel", &logmel_meta);
@@ -352,6 +391,7 @@ TORCH_LIBRARY_IMPL(wakeword_amd, Meta, m) {
     m.impl("logmel_frames", &logmel_frames_meta);
     m.impl("cnn_pool_wide", &cnn_pool_wide_meta);
     m.impl("forward_pcm_frames", &forward_pcm_frames_meta);
+    m.impl("spec_augment", &spec_augment_meta);
 }
 TORCH_LIBRARY_IMPL(wakeword_amd, CPU, m) {
     m.impl("logmel", &logmel_cpu);
@@ -362,4 +402,5 @@ TORCH_LIBRARY_IMPL(wakeword_amd, CPU, m) {
     m.impl("logmel_frames", &logmel_frames_cpu);
     m.impl("cnn_pool_wide", &cnn_pool_wide_cpu);
     m.impl("forward_pcm_frames", &forward_pcm_frames_cpu);
+    m.impl("spec_augment", &spec_augment_cpu);
 }

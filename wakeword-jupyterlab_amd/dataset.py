@@ -13,7 +13,8 @@ substitute is zeros of the real width, [80, 32] -- or [80, T] for a processor co
 (0.25 .. 2 s: items and batches are [1, 80, T] / [B, 1, 80, T], T = 1 + int(16000 * DURATION) // 512).
 
 `augment=True` (the training split, :456) runs AudioProcessor.augment_audio's transforms on the GPU (kernels KA)
-between decode and log-mel: per item in `__getitem__`, per batch in `batches()`.  Augmentation, and so the training split, takes
+between decode and log-mel: per item in `__getitem__`, per batch in `batches()`; with `processor.set_spec_augment(config)` it also masks
+blocks of mel bins and frames of the log-mel batch, in place, after K1.  Augmentation, and so the training split, takes
 DURATION 0.25 .. 1.0 (T = 8 .. 32); longer clips serve inference only (augment=False).
 """
 from __future__ import annotations
@@ -132,6 +133,8 @@ class GpuBatchLoader:
             if ds.augment:
                 pcm_dev = ds.processor.augment_batch(pcm_dev)          # process_audio_file :134-135
             data = ds.processor.mel_batch(pcm_dev, normalize=False)
+            if ds.augment and getattr(ds.processor, "spec_augment", None) is not None:
+                ds.processor.spec_augment_batch(data, inplace=True)    # one seed per batch, drawn after augment_batch's plans
             if not ok.all():
                 ds.unreadable += int((~ok).sum())
                 print(f"WakewordDataset: {int((~ok).sum())} unreadable file(s) in this batch served as zeros "

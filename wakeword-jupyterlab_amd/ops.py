@@ -199,7 +199,7 @@ def _forward_pcm_impl(pcm: torch.Tensor, packed: torch.Tensor, n_conv: int, norm
 # section 7 step 2).  The CUDA kernels validate, allocate with ATen and call the C ABI on torch's current stream; the Meta kernels give
 # shapes only (FakeTensor / torch.compile tracing of the drop-in modules); the CPU kernels refuse.  Rounds 1-3 registered the Python
 # functions above through torch.library; those stay as plain functions (`_logmel_impl` ...: tests and the raw launches of bench.py's legs).
-# The library does not link libwakeword_amd.so: it is handed the addresses of the fourteen C ABI functions it calls.
+# The library does not link libwakeword_amd.so: it is handed the addresses of the fifteen C ABI functions it calls.
 # No fallback: without the compiled library the package does not import.
 import os as _os_ops
 
@@ -212,7 +212,7 @@ torch.ops.load_library(TORCH_LIB_PATH)
 _TORCH_BIND_ORDER = ("ww_last_error", "ww_packed_weights_floats", "ww_cnn_scratch_bytes", "ww_workspace_bytes", "ww_logmel_f32",
                      "ww_cnn_pool_f32", "ww_lstm_fc_f32", "ww_model_forward_f32", "ww_forward_pcm_f32",
                      "ww_logmel_frames_f32", "ww_cnn_wide_scratch_bytes", "ww_cnn_pool_wide_f32", "ww_workspace_frames_bytes",
-                     "ww_forward_pcm_frames_f32")
+                     "ww_forward_pcm_frames_f32", "ww_spec_augment_f32")
 _torch_lib = C.CDLL(TORCH_LIB_PATH)
 _table = (C.c_void_p * len(_TORCH_BIND_ORDER))(*[C.cast(getattr(nat.lib, _n), C.c_void_p).value for _n in _TORCH_BIND_ORDER])
 if _torch_lib.ww_torch_bind(_table, len(_TORCH_BIND_ORDER)) != 0:
@@ -926,3 +926,94 @@ def grad_norm(grads, max_norm: float):
     scale = torch.empty(1, device=device, dtype=torch.float32)
     grad_norm_launch(tab, device, max_norm, norm, scale, grad_norm_workspace(tab, device))
     return norm, scale
+
+
+# ---- SpecAugment: time and frequency masks on log-mel batches (csrc/ww_specaug.hip) ----------------------
+from .config import SPEC_MAX_MASKS, SpecAugmentConfig, check_spec_augment_config  # noqa: E402
+
+
+def _spec_args(config, T: int):
+    """(prob, n_freq, freq_max, n_time, time_max, fill_mode, fill_value) as ww_spec_augment_f32 takes them, for images of T frames."""
+    check_spec_augment_config(config)
+    fill = config.FILL
+    if isinstance(fill, str):
+        mode, value = {"mean": nat.SPEC_FILL_MEAN, "min": nat.SPEC_FILL_MIN}[fill], 0.0
+    else:
+        mode, value = nat.SPEC_FILL_VALUE, float(fill)
+    return (float(config.PROB), int(config.FREQ_MASKS), int(config.FREQ_MASK_MAX), int(config.TIME_MASKS),
+            int(float(config.TIME_MASK_MAX_FRACTION) * T), mode, value)
+
+
+def _check_frames(T: int, what: str) -> None:
+    if not 1 <= int(T) <= MAX_FRAMES:
+        raise NotImplementedError(f"{what}: T = {T} frames; the masking kernel takes 1..{MAX_FRAMES} (2 s clips give 63)")
+
+
+def spec_augment_records(seed: int, B: int, T: int, config=SpecAugmentConfig, device=None) -> torch.Tensor:
+    """The records `spec_augment(mel, seed=seed, config=config)` applies to a batch of B images of T frames: int16 [B, 16] on the device,
+    [f_start, f_width] x 4 then [t_start, t_width] x 4 per clip (ww_spec_augment_draw).  Clip c's record does not depend on B."""
+    _check_frames(T, "spec_augment_records")
+    if B < 0:
+        raise ValueError(f"spec_augment_records: B = {B}")
+    prob, n_freq, freq_max, n_time, time_max, _, _ = _spec_args(config, int(T))
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"spec_augment_records on {device}: this path has no CPU implementation")
+    records = torch.empty((B, nat.SPEC_RECORD_INT16), device=device, dtype=torch.int16)
+    with torch.cuda.device(device):
+        nat.check(nat.lib.ww_spec_augment_draw(int(seed) & (2 ** 64 - 1), B, int(T), prob, n_freq, freq_max, n_time, time_max, _ptr(records),
+                                               _stream()))
+    return records
+
+
+def pack_spec_plans(plans, T: int) -> np.ndarray:
+    """A list of {"freq": [(start, width), ...], "time": [(start, width), ...]} (either key may be missing), one per clip ->
+    numpy int16 [B, 16] in the kernel's record layout.  ValueError for more than 4 masks per axis, a negative start or width, or a
+    mask that ends past the 80 mel bins or the T frames."""
+    out = np.zeros((len(plans), nat.SPEC_RECORD_INT16), dtype=np.int16)
+    for i, plan in enumerate(plans):
+        for key, base, size in (("freq", 0, N_MELS), ("time", 2 * SPEC_MAX_MASKS, int(T))):
+            masks = list(plan.get(key, ()))
+            if len(masks) > SPEC_MAX_MASKS:
+                raise ValueError(f"plan {i}: {len(masks)} {key} masks; a record holds {SPEC_MAX_MASKS}")
+            for k, (start, width) in enumerate(masks):
+                if int(start) != start or int(width) != width or start < 0 or width < 0 or start + width > size:
+                    raise ValueError(f"plan {i}: {key} mask ({start}, {width}) does not lie inside 0..{size}")
+                out[i, base + 2 * k], out[i, base + 2 * k + 1] = int(start), int(width)
+    return out
+
+
+def spec_augment(mel: torch.Tensor, records=None, *, seed=None, config=SpecAugmentConfig, out=None) -> torch.Tensor:
+    """mel float32 [B, 1, 80, T] or [B, 80, T] on the GPU, contiguous, T <= 63 -> the same shape with blocks of mel bins and of frames
+    replaced by the clip's mean, its minimum or a constant (config.FILL).  Exactly one of `records` (int16 [B, 16] on the device:
+    spec_augment_records, or pack_spec_plans uploaded) and `seed` (the records are drawn inside the kernel from `config`) is given.
+    `out=mel` masks in place; any other `out` is a contiguous tensor like mel that does not overlap it."""
+    if not isinstance(mel, torch.Tensor):
+        raise TypeError(f"mel: expected a torch.Tensor, got {type(mel).__name__}")
+    if mel.device.type != "cuda":
+        raise RuntimeError(f"mel is on {mel.device}: this path has no CPU implementation; move it to the MI355X (`.cuda()`)")
+    if mel.dtype != torch.float32 or not ((mel.dim() == 4 and mel.shape[1] == 1 and mel.shape[2] == N_MELS) or
+                                          (mel.dim() == 3 and mel.shape[1] == N_MELS)) or not mel.is_contiguous():
+        raise ValueError(f"mel: expected contiguous float32 [B, 1, {N_MELS}, T] or [B, {N_MELS}, T], got {mel.dtype} {tuple(mel.shape)}")
+    B, T = int(mel.shape[0]), int(mel.shape[-1])
+    _check_frames(T, "mel")
+    if (records is None) == (seed is None):
+        raise ValueError("spec_augment: give exactly one of `records` and `seed`")
+    prob, n_freq, freq_max, n_time, time_max, mode, value = _spec_args(config, T)
+    if records is not None:
+        if (not isinstance(records, torch.Tensor) or records.dtype != torch.int16 or tuple(records.shape) != (B, nat.SPEC_RECORD_INT16)
+                or records.device != mel.device):
+            raise ValueError(f"records: expected int16 [{B}, {nat.SPEC_RECORD_INT16}] on {mel.device}")
+        records = records.contiguous()
+        if records.data_ptr() % 16:
+            records = records.clone()
+        prob, n_freq, freq_max, n_time, time_max, seed = 0.0, 0, 0, 0, 0, 0
+    if out is None:
+        out = torch.empty_like(mel)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != mel.shape or out.device != mel.device
+          or not out.is_contiguous()):
+        raise ValueError("out: expected a contiguous float32 tensor of mel's shape on mel's device")
+    with torch.cuda.device(mel.device):
+        nat.check(nat.lib.ww_spec_augment_f32(_ptr(mel), _ptr(out), B, T, None if records is None else _ptr(records), int(seed) & (2 ** 64 - 1),
+                                              prob, n_freq, freq_max, n_time, time_max, mode, value, _stream()))
+    return out
