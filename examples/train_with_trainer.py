@@ -2,10 +2,12 @@
 """The reference's `main()` (wakeword_training_script.py:395-495) with its own training class: sample data -> file lists -> split ->
 AudioProcessor / WakewordModel -> WakewordTrainer(model, device).train(train_loader, val_loader, epochs) -> best / final checkpoints.
 The training files live in a ClipBank on the GPU and every batch runs forward, cross-entropy, backward and
-Adam as HIP kernels without a wait on the device (section 3h); the epoch's loss and accuracy are read once per epoch.
+Adam as HIP kernels without a wait on the device (section 3h); the epoch's loss and accuracy are read once per epoch.  It ends as the
+notebook's evaluation cell does (cell 17): accuracy, weighted precision / recall / F1, the confusion matrix and the classification report
+of the test set -- from counters kept on the device (section 3j) -- and, beyond the reference, the operating point at 0.8, AUC and EER.
 
     PYTHONPATH=. python examples/train_with_trainer.py [--epochs 10] [--data DIR] [--duration 1.0] [--background DIR] [--max-grad-norm 1.0]
-                                                        [--spec-augment]
+                                                        [--spec-augment] [--monitor val_acc|val_f1|val_auc]
 """
 import argparse
 import glob
@@ -31,6 +33,8 @@ def main():
     ap.add_argument("--background", default=None, help="directory of background noise files (WAV / FLAC) mixed into the training clips")
     ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm after the backward (default: off)")
     ap.add_argument("--spec-augment", action="store_true", help="mask blocks of mel bins and frames of every training batch (SpecAugment)")
+    ap.add_argument("--monitor", default="val_acc", choices=("val_acc", "val_f1", "val_auc"),
+                    help="what the scheduler, the best checkpoint and early stopping follow (default: the reference's validation accuracy)")
     a = ap.parse_args()
     device = torch.device("cuda")
     print(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
@@ -57,10 +61,23 @@ def main():
     val_loader = DataLoader(WakewordDataset(w_va, n_va, processor, augment=False).cache(), batch_size=config.BATCH_SIZE, shuffle=False)
     test_loader = DataLoader(WakewordDataset(w_te, n_te, processor, augment=False).cache(), batch_size=config.BATCH_SIZE, shuffle=False)
     trainer = WakewordTrainer(model, device, config, checkpoint_path=os.path.join(a.data, "best_wakeword_model.pth"),
-                              max_grad_norm=a.max_grad_norm)
+                              max_grad_norm=a.max_grad_norm, monitor=a.monitor, thresholds=(0.8,))
     best = trainer.train(train_loader, val_loader, config.EPOCHS)
     _, test_acc = trainer.validate(test_loader)
     print(f"Best validation accuracy: {best:.2f}%   Test accuracy: {test_acc:.2f}%")
+    report = trainer.val_report                                                   # of the validate just above: the test set, read once
+    s = report.summary()
+    print("\nTest Set Performance:")
+    print(f"   Accuracy: {s['accuracy']:.4f}\n   Precision: {s['precision']:.4f}\n   Recall: {s['recall']:.4f}\n   F1-Score: {s['f1']:.4f}")
+    print(f"\nConfusion Matrix (rows: actual Negative, Wakeword; columns: predicted):\n{report.confusion}")
+    print("\nClassification Report:")
+    print(report.classification_report(target_names=("Negative", "Wakeword")))
+    at = report.at(0.8)
+    print(f"At threshold 0.80: {at['tp']} detected, {at['fn']} missed, {at['fp']} false accepts of {at['fp'] + at['tn']} negatives "
+          f"(FPR {at['fpr']:.4f}, FNR {at['fnr']:.4f})")
+    if report.support.min() > 0:
+        print(f"ROC AUC: {report.auc:.4f} (+- {report.auc_bound:.1e} from binning)   EER: {report.eer:.4f}   "
+              f"threshold for FPR <= 1 %: {report.threshold_for(0.01):.4f}")
     torch.save({"model_state_dict": model.state_dict(), "best_val_acc": best, "device": str(device)},
                os.path.join(a.data, "final_wakeword_model.pth"))
 

@@ -717,6 +717,56 @@ WW_API int64_t ww_grad_norm_workspace_bytes(const ww_adam_tensor* tensors_host, 
 WW_API int ww_grad_norm_f32(const ww_adam_tensor* tensors_host, int64_t n_tensors, double max_norm, double* norm_dev, float* scale_dev,
                             void* workspace_dev, ww_stream_t stream);
 
+/* ---- clip evaluation: confusion, operating points and a margin histogram as device counters ---------- */
+/* What notebook cell 17 collects clip by clip on the host (`all_preds.extend(predicted.cpu().numpy())`) kept as integer counters in
+ * device memory: one launch per batch adds the batch to the record in stream order, nothing waits for the device, and the record is read
+ * once.  Accuracy, precision / recall / F1, the confusion matrix, a ROC curve, AUC, EER and "the threshold for a false-positive rate"
+ * are all functions of these integers (metrics.py).  Every sum is an integer sum: the record after a set of clips does not depend on the
+ * batch size, the launch geometry or the order of the clips.
+ *
+ * Per clip, with z = logits [2] float32, y = label int64 and the margin d = z1 - z0 (ONE float32 subtraction):
+ *   y outside {0, 1}        bad_labels += 1 and nothing else (total counts it: total = clips seen, as ww_loss_stats.total).
+ *   argmax[y][pred] += 1    pred = 1 iff z1 > z0; a tie or a NaN gives 0 -- ww_ce_loss_f32's rule, so (argmax[0][0] + argmax[1][1]) is
+ *                           its `correct` integer for integer.
+ *   d NaN or +-inf          nonfinite += 1 (it is counted in argmax too) and none of the margin counters below.
+ *   at[k][y][fired] += 1    for each of the n_thresholds operating points: fired = 1 iff d >= margin[k], compared in float32.
+ *                           margin[k] = (float)log(p / (1 - p)) of the probability threshold p, evaluated in double
+ *                           (ww_clip_metrics_margin_host).  d >= margin is softmax(z)[1] >= p except within rounding of the boundary:
+ *                           the rule is defined on the margin, where float32 still resolves p beyond 0.9999999.
+ *   hist[y][bin] += 1       bin = clamp((int)floorf((d + 32.0f) * 64.0f), 0, 4095): bins 1/64 wide over [-32, 32), the end bins take
+ *                           everything beyond.  The multiply by 64 is exact, so float32 arithmetic anywhere reproduces the bin bit for bit.
+ * One workgroup per call; a call's histogram is built in LDS (integer LDS adds) and one lane per touched bin adds it to the record with
+ * a plain read-modify-write: calls on one stream serialise, calls on different streams must not share a record.  No float atomics, no
+ * global atomics.
+ *
+ * ww_clip_metrics_init writes the margins of thresholds_host [n_thresholds] (each in (0, 1); they travel in the kernel arguments, the
+ * host array is free on return) and zeroes every counter; ww_clip_metrics_reset zeroes the counters and keeps the margins.
+ * ww_clip_metrics_update_f32 is a pure launch: no allocation, no copy, no synchronise, capturable; n == 0 returns WW_OK without a launch.
+ * logits_dev [n][2] float32, 8-byte aligned; labels_dev [n] int64; state_dev: ww_clip_metrics_bytes() bytes, 8-byte aligned; n in 0..2^30.
+ * Checked before any HIP call (WW_EINVAL naming the field): n < 0, null or misaligned pointers, n_thresholds outside
+ * 0..WW_METRICS_MAX_THRESHOLDS, a threshold outside (0, 1) or NaN. */
+#define WW_METRICS_MAX_THRESHOLDS 8
+#define WW_METRICS_BINS 4096
+typedef struct ww_clip_metrics {
+    int64_t argmax[2][2];                              /* [label][prediction at argmax]: [[tn, fp], [fn, tp]] */
+    int64_t total;                                     /* clips seen, bad labels included */
+    int64_t batches;                                   /* calls with n > 0 */
+    int64_t bad_labels;                                /* labels outside {0, 1} */
+    int64_t nonfinite;                                 /* valid-label clips whose margin is NaN or +-inf */
+    int64_t at[WW_METRICS_MAX_THRESHOLDS][2][2];       /* [k][label][fired at margin[k]] */
+    int64_t hist[2][WW_METRICS_BINS];                  /* [label][bin of the margin] */
+    float margin[WW_METRICS_MAX_THRESHOLDS];           /* the operating points, unused entries 0 */
+    int32_t n_thresholds;
+    int32_t reserved;
+} ww_clip_metrics;                                     /* 65896 bytes, DEVICE memory */
+WW_API int64_t ww_clip_metrics_bytes(void);
+/* NaN (and ww_last_error names p) for p outside (0, 1). */
+WW_API float ww_clip_metrics_margin_host(float p);
+WW_API int ww_clip_metrics_init(ww_clip_metrics* state_dev, const float* thresholds_host, int32_t n_thresholds, ww_stream_t stream);
+WW_API int ww_clip_metrics_reset(ww_clip_metrics* state_dev, ww_stream_t stream);
+WW_API int ww_clip_metrics_update_f32(const float* logits_dev, const int64_t* labels_dev, int64_t n, ww_clip_metrics* state_dev,
+                                      ww_stream_t stream);
+
 /* ---- streaming: sliding window of 0.25 .. 1 s, one hop per step, many microphones ------------- */
 /* Semantics per window = predict_wakeword (wakeword_training.ipynb cell 19): normalise the last
  * N samples, log-mel, forward, softmax, p[wakeword].  The reference has no streaming code;

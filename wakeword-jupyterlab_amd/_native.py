@@ -119,6 +119,15 @@ class AdamTensor(C.Structure):
 
 
 ADAM_MAX_TENSORS = 16
+METRICS_MAX_THRESHOLDS, METRICS_BINS = 8, 4096
+
+
+class ClipMetrics(C.Structure):
+    """struct ww_clip_metrics (include/wakeword_amd.h): the counters of a clip evaluation, kept in device memory."""
+    _fields_ = [("argmax", C.c_int64 * 2 * 2), ("total", C.c_int64), ("batches", C.c_int64), ("bad_labels", C.c_int64),
+                ("nonfinite", C.c_int64), ("at", C.c_int64 * 2 * 2 * METRICS_MAX_THRESHOLDS), ("hist", C.c_int64 * METRICS_BINS * 2),
+                ("margin", C.c_float * METRICS_MAX_THRESHOLDS), ("n_thresholds", C.c_int32), ("reserved", C.c_int32)]
+
 RIR_MAX_TAPS, RIR_FFT_SIZE, RIR_SPECTRUM_BINS = 16384, 32768, 16385
 
 
@@ -235,6 +244,11 @@ PROTOTYPES = {
                                    C.c_void_p, C.c_void_p]),
     "ww_grad_norm_workspace_bytes": (C.c_int64, [C.POINTER(AdamTensor), C.c_int64]),
     "ww_grad_norm_f32": (C.c_int, [C.POINTER(AdamTensor), C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_clip_metrics_bytes": (C.c_int64, []),
+    "ww_clip_metrics_margin_host": (C.c_float, [C.c_float]),
+    "ww_clip_metrics_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ww_clip_metrics_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ww_clip_metrics_update_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ww_train_masks": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_train_packed_image": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "ww_train_bit_images": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

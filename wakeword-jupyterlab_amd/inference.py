@@ -5,6 +5,9 @@
   predict_wakeword(path, model, processor, device, threshold=0.8)
                                     <- notebook cell 19 (wakeword_training.ipynb:871-893)
   evaluate_pcm(model, pcm, batch)   the same loop fed with PCM already in HBM (bench / multi-GPU path)
+  evaluate_report(model, loader)    cell 17's loop with its counters kept on the device: one launch per batch, one copy at the end,
+                                    a metrics.ClipReport (confusion, sklearn's report, ROC, AUC, EER, operating points) as the result
+  evaluate_report_pcm(model, pcm, batch, labels)   the same from PCM and labels already in HBM
 """
 from __future__ import annotations
 
@@ -59,3 +62,44 @@ def evaluate_pcm(model, pcm: torch.Tensor, batch_size: int = 4096, normalize: bo
             outs.append(model.forward_pcm(pcm[s:s + batch_size], normalize))
     logits = torch.cat(outs) if outs else torch.empty((0, 2), device=pcm.device)
     return logits, (torch.max(logits, 1)[1] if len(logits) else torch.empty(0, dtype=torch.long, device=pcm.device))
+
+
+def _report_labels(target, n: int, device) -> torch.Tensor:
+    if not isinstance(target, torch.Tensor):
+        target = torch.as_tensor(target)
+    if target.dtype.is_floating_point or target.dtype == torch.bool:
+        raise TypeError(f"labels: expected integer class labels, got {target.dtype}")
+    target = target.to(device=device, dtype=torch.int64).reshape(-1)
+    if target.shape[0] != n:
+        raise ValueError(f"labels: expected {n} labels for {n} clips, got {target.shape[0]}")
+    return target
+
+
+def evaluate_report(model, loader, device=None, thresholds=(0.8,)):
+    """Notebook cell 17's loop without its per-batch copies: every batch's logits and labels go into a ww_clip_metrics record on the
+    device (one launch, in stream order) and the record is read once, after the last batch.  Returns a metrics.ClipReport: `.confusion`,
+    `.classification_report()`, `.summary()` are cell 17's numbers; `.at(p)` for each p of `thresholds`, `.roc()`, `.auc`, `.eer` and
+    `.threshold_for(max_fpr)` answer the deployment question.  `loader` yields (data [B,1,80,T], target [B,1] or [B])."""
+    from . import ops
+    model.eval()
+    device = torch.device(device) if device is not None else next(model.parameters()).device
+    state = ops.new_clip_metrics(device, thresholds)
+    with torch.no_grad():
+        for data, target in loader:
+            output = model(data.to(device))
+            ops.clip_metrics_update(output, _report_labels(target, output.shape[0], device), state)
+    return ops.read_clip_metrics(state)
+
+
+def evaluate_report_pcm(model, pcm: torch.Tensor, batch_size: int = 4096, labels=None, thresholds=(0.8,), normalize: bool = True):
+    """`evaluate_report` for PCM [N, n<=16000] and labels [N] already on the device, in batches of `batch_size`."""
+    from . import ops
+    if labels is None:
+        raise TypeError("evaluate_report_pcm: labels [N] are required (a report needs the truth)")
+    model.eval()
+    labels = _report_labels(labels, pcm.shape[0], pcm.device)
+    state = ops.new_clip_metrics(pcm.device, thresholds)
+    with torch.no_grad():
+        for s in range(0, pcm.shape[0], batch_size):
+            ops.clip_metrics_update(model.forward_pcm(pcm[s:s + batch_size], normalize), labels[s:s + batch_size], state)
+    return ops.read_clip_metrics(state)

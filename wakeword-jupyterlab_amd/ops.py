@@ -865,6 +865,88 @@ def ce_loss(logits: torch.Tensor, labels: torch.Tensor, stats=None, grad: bool =
     return loss, dlogits
 
 
+# ---- clip evaluation as device counters (csrc/ww_metrics.hip) ---------------------------------------------
+class ClipMetricsState:
+    """A ww_clip_metrics record in device memory (`buffer`, int64 words) with the probability thresholds it was made for and their float32
+    margins as the library computed them."""
+    __slots__ = ("buffer", "thresholds", "margins")
+
+    def __init__(self, buffer, thresholds, margins):
+        self.buffer, self.thresholds, self.margins = buffer, thresholds, margins
+
+    @property
+    def device(self):
+        return self.buffer.device
+
+
+def new_clip_metrics(device, thresholds=(0.8,)) -> ClipMetricsState:
+    """A zeroed evaluation record on `device` with up to 8 operating points, each a probability in (0, 1)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"clip metrics on {device}: this path has no CPU implementation")
+    thresholds = tuple(float(p) for p in thresholds)
+    if len(thresholds) > nat.METRICS_MAX_THRESHOLDS:
+        raise ValueError(f"thresholds: at most {nat.METRICS_MAX_THRESHOLDS} operating points, got {len(thresholds)}")
+    for p in thresholds:
+        if not 0.0 < float(np.float32(p)) < 1.0:
+            raise ValueError(f"thresholds: {p!r} is not a probability in (0, 1)")
+    if len(set(np.float32(p) for p in thresholds)) != len(thresholds):
+        raise ValueError(f"thresholds: {thresholds} repeats an operating point")
+    nbytes = nat.check(nat.lib.ww_clip_metrics_bytes())
+    assert nbytes == C.sizeof(nat.ClipMetrics) and nbytes % 8 == 0
+    margins = np.array([nat.lib.ww_clip_metrics_margin_host(p) for p in thresholds], np.float32)
+    host = (C.c_float * max(1, len(thresholds)))(*thresholds)
+    with torch.cuda.device(device):
+        buf = torch.empty(nbytes // 8, device=device, dtype=torch.int64)
+        nat.check(nat.lib.ww_clip_metrics_init(_ptr(buf), host, len(thresholds), _stream()))
+    return ClipMetricsState(buf, thresholds, margins)
+
+
+def _check_metrics_state(state, like=None) -> None:
+    if not isinstance(state, ClipMetricsState):
+        raise TypeError(f"state: expected what ops.new_clip_metrics() makes, got {type(state).__name__}")
+    if like is not None and state.device != like.device:
+        raise RuntimeError(f"state on {state.device}, logits on {like.device}")
+
+
+def clip_metrics_update_into(logits, labels, state) -> None:
+    """ww_clip_metrics_update_f32 on checked arguments (`labels` as _check_ce returns them): one launch, nothing else."""
+    with torch.cuda.device(logits.device):
+        nat.check(nat.lib.ww_clip_metrics_update_f32(_ptr(logits), _ptr(labels), logits.shape[0], _ptr(state.buffer), _stream()))
+
+
+def clip_metrics_update(logits: torch.Tensor, labels: torch.Tensor, state: ClipMetricsState) -> None:
+    """Add a batch to the record: logits [n, 2] float32 and labels [n] or [n, 1] int64 on the GPU (the checks of `ce_loss`).  One launch
+    in stream order; nothing waits for the device."""
+    labels = _check_ce(logits, labels)
+    _check_metrics_state(state, logits)
+    clip_metrics_update_into(logits, labels, state)
+
+
+def reset_clip_metrics(state: ClipMetricsState) -> None:
+    """Zero the counters and keep the operating points."""
+    _check_metrics_state(state)
+    with torch.cuda.device(state.device):
+        nat.check(nat.lib.ww_clip_metrics_reset(_ptr(state.buffer), _stream()))
+
+
+def read_clip_metrics(state: ClipMetricsState):
+    """The record on the host as a metrics.ClipReport.  The one device-to-host copy of an evaluation."""
+    from .metrics import ClipReport
+    _check_metrics_state(state)
+    host = state.buffer.cpu().numpy()
+    rec = nat.ClipMetrics.from_buffer_copy(host.tobytes())
+    k = int(rec.n_thresholds)
+    margins = np.ctypeslib.as_array(rec.margin).copy()[:k]
+    if k != len(state.thresholds) or not np.array_equal(margins, state.margins):
+        raise RuntimeError("the record's operating points are not the ones it was made with: was the buffer overwritten?")
+    report = ClipReport.from_counts(np.ctypeslib.as_array(rec.argmax).copy(), hist=np.ctypeslib.as_array(rec.hist).copy(), margins=margins,
+                                    at=np.ctypeslib.as_array(rec.at).copy()[:k], bad_labels=int(rec.bad_labels),
+                                    nonfinite=int(rec.nonfinite), thresholds=state.thresholds)
+    report.clips_seen, report.batches = int(rec.total), int(rec.batches)
+    return report
+
+
 def adam_table(params, grads, exp_avgs, exp_avg_sqs):
     """Four equally long lists of float32 GPU tensors -> a ctypes array of _native.AdamTensor (at most 16 entries).  A grads-only table
     (the other three None) is what grad_norm reads."""

@@ -6,6 +6,11 @@ the C entry points directly, train forward -> cross-entropy (loss, gradient, run
 -> Adam, without autograd, without a torch kernel in between, without a device-to-host copy and, after the first call at a batch size,
 without an allocation.  The epoch's loss and accuracy are kept on the device and read once, at the end of the epoch.
 
+`validate` also keeps a clip-evaluation record on the device (ops.new_clip_metrics: confusion, operating points, margin histogram; one
+more launch per batch, no wait); `trainer.val_report` reads it, lazily, as a metrics.ClipReport.  `monitor=` chooses what the scheduler,
+the best checkpoint and early stopping follow: "val_acc" (the reference's behaviour, the default), "val_f1" (the wake-word class's F1
+at argmax, times 100) or "val_auc" (the ROC AUC of the margins, times 100).
+
 One deliberate difference: the reference calls `clip_grad_norm_` BEFORE `backward()`, where it clips the previous batch's gradients or
 nothing, so the default here is no clipping; `max_grad_norm=1.0` gives the clip the call meant, after the
 backward.
@@ -25,14 +30,22 @@ from .model import SimpleWakewordModel, WakewordModel
 from .optim import FusedAdam
 
 
+MONITORS = ("val_acc", "val_f1", "val_auc")
+MONITOR_NAMES = {"val_acc": "Acc", "val_f1": "F1", "val_auc": "AUC"}
+
+
 class WakewordTrainer:
-    def __init__(self, model, device, config=TrainingConfig, *, checkpoint_path="best_wakeword_model.pth", max_grad_norm=None):
+    def __init__(self, model, device, config=TrainingConfig, *, checkpoint_path="best_wakeword_model.pth", max_grad_norm=None,
+                 monitor="val_acc", thresholds=(0.8,)):
         if not isinstance(model, (SimpleWakewordModel, WakewordModel)):
             raise TypeError(f"WakewordTrainer drives the HIP training kernels of SimpleWakewordModel and WakewordModel; got {type(model).__name__}")
         if any(p.device.type != "cuda" for p in model.parameters()):
             raise TypeError("WakewordTrainer: the model's parameters are on the CPU; this path has no CPU implementation (model.to('cuda'))")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError(f"max_grad_norm {max_grad_norm}: expected a positive number or None")
+        if monitor not in MONITORS:
+            raise ValueError(f"monitor {monitor!r}: expected one of {MONITORS}")
+        self.monitor = monitor
         self.model = model
         self.device = device
         self.config = config
@@ -51,6 +64,8 @@ class WakewordTrainer:
         self.patience = 10
         self.best_val_acc = 0.0
         self.epochs_no_improve = 0
+        self.monitor_history = []                                      # the monitored value of every epoch of `train`
+        self.best_monitor = 0.0
 
         # ---- persistent device state of `step` ----
         self._n_conv = model._n_conv
@@ -66,6 +81,9 @@ class WakewordTrainer:
         self._bind_grads()
         self.train_stats = ops.new_loss_stats(self._dev)
         self.val_stats = ops.new_loss_stats(self._dev)
+        self.val_metrics = ops.new_clip_metrics(self._dev, thresholds)
+        self._val_report = None
+        self._validated = False
         self.last_loss = torch.zeros((), device=self._dev, dtype=torch.float32)       # the newest batch's mean loss, on the device
         self._cap = 0                                                                  # clips the batch buffers hold
         self._logits = self._dlogits = None
@@ -199,6 +217,9 @@ class WakewordTrainer:
     def validate(self, val_loader):
         self.model.eval()
         self.val_stats.zero_()
+        ops.reset_clip_metrics(self.val_metrics)
+        self._val_report = None
+        self._validated = True
         with torch.no_grad():
             for data, target in val_loader:
                 if data.device != self._dev:
@@ -206,7 +227,27 @@ class WakewordTrainer:
                 output = self.model(data)
                 y = self._target(target, output.shape[0])
                 ops.ce_loss_into(output, y, None, None, self.val_stats)
+                ops.clip_metrics_update_into(output, y, self.val_metrics)
         return self._finish_epoch(self.val_stats, "validate")
+
+    @property
+    def val_report(self):
+        """The newest `validate` as a metrics.ClipReport, read from the device on first access (one copy) and kept until the next one."""
+        if not self._validated:
+            raise RuntimeError("WakewordTrainer.val_report: validate() has not run yet")
+        if self._val_report is None:
+            self._val_report = ops.read_clip_metrics(self.val_metrics)
+        return self._val_report
+
+    def _monitored(self, val_acc):
+        if self.monitor == "val_acc":
+            return val_acc                                   # no copy: the report stays on the device unless somebody reads it
+        if self.monitor == "val_f1":
+            return 100.0 * self.val_report.f1
+        auc = self.val_report.auc
+        if auc != auc:
+            raise ValueError("monitor='val_auc': the validation set needs clips of both classes with finite logits")
+        return 100.0 * auc
 
     def train(self, train_loader, val_loader, epochs):
         print(f"Starting training for {epochs} epochs...")
@@ -215,6 +256,7 @@ class WakewordTrainer:
         print(f"Batch size: {self.config.BATCH_SIZE}")
 
         self.best_val_acc = 0.0
+        self.best_monitor = 0.0
         self.epochs_no_improve = 0
         epoch = -1
         for epoch in range(epochs):
@@ -230,10 +272,16 @@ class WakewordTrainer:
             print(f"Train Loss: {train_loss:.4f}, Train Acc: {train_acc:.2f}%")
             print(f"Val Loss: {val_loss:.4f}, Val Acc: {val_acc:.2f}%")
 
-            self.scheduler.step(val_acc)
+            monitored = self._monitored(val_acc)
+            self.monitor_history.append(monitored)
+            if self.monitor != "val_acc":
+                print(f"Val {MONITOR_NAMES[self.monitor]}: {monitored:.2f}%")
 
-            if val_acc > self.best_val_acc:
-                self.best_val_acc = val_acc
+            self.scheduler.step(monitored)
+
+            if monitored > self.best_monitor:
+                self.best_monitor = monitored
+                self.best_val_acc = val_acc                  # the accuracy of the best epoch by the monitor
                 self.epochs_no_improve = 0
                 torch.save({"epoch": epoch, "model_state_dict": self.model.state_dict(), "optimizer_state_dict": self.optimizer.state_dict(),
                             "val_acc": val_acc, "train_acc": train_acc, "train_loss": train_loss, "val_loss": val_loss}, self.checkpoint_path)
