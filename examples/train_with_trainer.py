@@ -8,6 +8,11 @@ of the test set -- from counters kept on the device (section 3j) -- and, beyond 
 
     PYTHONPATH=. python examples/train_with_trainer.py [--epochs 10] [--data DIR] [--duration 1.0] [--background DIR] [--max-grad-norm 1.0]
                                                         [--spec-augment] [--monitor val_acc|val_f1|val_auc]
+                                                        [--class-weights balanced|W0,W1] [--label-smoothing E] [--focal-gamma G]
+                                                        [--positive-fraction F]
+
+Imbalanced data (section 3k): `--class-weights balanced` weighs the classes by the training split's counts, `--label-smoothing` and
+`--focal-gamma` choose the loss of the fused step, `--positive-fraction 0.5` makes every training epoch half wake-word items.
 """
 import argparse
 import glob
@@ -18,9 +23,25 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from train_from_files import split  # noqa: E402
-from wakeword_jupyterlab_amd import (AudioConfig, AudioProcessor, DataLoader, SpecAugmentConfig, TrainingConfig, WakewordDataset,  # noqa: E402
-                                     WakewordModel, WakewordTrainer)
+from wakeword_jupyterlab_amd import (AudioConfig, AudioProcessor, DataLoader, FocalLoss, SpecAugmentConfig, TrainingConfig,  # noqa: E402
+                                     WakewordDataset, WakewordModel, WakewordTrainer, balanced_class_weights)
 from wakeword_jupyterlab_amd.synth import create_sample_data  # noqa: E402
+
+
+def criterion(a, n_negative, n_positive):
+    """The loss the flags name, or None for the trainer's default nn.CrossEntropyLoss()."""
+    weight = None
+    if a.class_weights == "balanced":
+        weight = balanced_class_weights([0] * n_negative + [1] * n_positive)
+    elif a.class_weights is not None:
+        weight = torch.tensor([float(v) for v in a.class_weights.split(",")])
+    if a.focal_gamma is not None:
+        if a.label_smoothing:
+            raise SystemExit("--focal-gamma and --label-smoothing exclude one another")
+        return FocalLoss(a.focal_gamma, weight=weight)
+    if weight is None and not a.label_smoothing:
+        return None
+    return torch.nn.CrossEntropyLoss(weight=weight, label_smoothing=a.label_smoothing)
 
 
 def main():
@@ -35,6 +56,12 @@ def main():
     ap.add_argument("--spec-augment", action="store_true", help="mask blocks of mel bins and frames of every training batch (SpecAugment)")
     ap.add_argument("--monitor", default="val_acc", choices=("val_acc", "val_f1", "val_auc"),
                     help="what the scheduler, the best checkpoint and early stopping follow (default: the reference's validation accuracy)")
+    ap.add_argument("--class-weights", default=None, metavar="balanced|W0,W1",
+                    help="class weights of the loss: 'balanced' (n / (2 n_c) over the training split) or two numbers, negative then wake word")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, help="label smoothing of the cross-entropy, in [0, 1]")
+    ap.add_argument("--focal-gamma", type=float, default=None, help="train with the focal loss of this gamma instead of cross-entropy")
+    ap.add_argument("--positive-fraction", type=float, default=None,
+                    help="share of wake-word items in every training epoch, in (0, 1) (default: the files as they are)")
     a = ap.parse_args()
     device = torch.device("cuda")
     print(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
@@ -57,11 +84,13 @@ def main():
     print(f"Parameters: {sum(p.numel() for p in model.parameters()):,}")
     bank = WakewordDataset(w_tr, n_tr, processor, augment=True).cache()           # every training file decoded once, onto the GPU
     print(bank)
-    train_loader = DataLoader(bank, batch_size=config.BATCH_SIZE, shuffle=True, augment=True)
+    train_loader = DataLoader(bank, batch_size=config.BATCH_SIZE, shuffle=True, augment=True, positive_fraction=a.positive_fraction)
     val_loader = DataLoader(WakewordDataset(w_va, n_va, processor, augment=False).cache(), batch_size=config.BATCH_SIZE, shuffle=False)
     test_loader = DataLoader(WakewordDataset(w_te, n_te, processor, augment=False).cache(), batch_size=config.BATCH_SIZE, shuffle=False)
+    crit = criterion(a, len(n_tr), len(w_tr))
     trainer = WakewordTrainer(model, device, config, checkpoint_path=os.path.join(a.data, "best_wakeword_model.pth"),
-                              max_grad_norm=a.max_grad_norm, monitor=a.monitor, thresholds=(0.8,))
+                              max_grad_norm=a.max_grad_norm, monitor=a.monitor, thresholds=(0.8,), criterion=crit.to(device) if crit is not None else None)
+    print(f"Criterion: {trainer.criterion}")
     best = trainer.train(train_loader, val_loader, config.EPOCHS)
     _, test_acc = trainer.validate(test_loader)
     print(f"Best validation accuracy: {best:.2f}%   Test accuracy: {test_acc:.2f}%")

@@ -690,6 +690,39 @@ typedef struct ww_loss_stats {
 } ww_loss_stats;        /* 48 bytes, DEVICE memory; zero it before an epoch */
 WW_API int ww_ce_loss_f32(const float* logits_dev, const int64_t* labels_dev, int64_t n, float* dlogits_dev, float* loss_dev,
                           ww_loss_stats* stats_dev, ww_stream_t stream);
+/* ww_ce_loss_ex_f32: the loss for imbalanced data -- ww_ce_loss_f32 with class weights, label smoothing,
+ * ignore_index, a sum reduction and the focal loss.  One launch, no atomics, every sum in one fixed order; the options are read on the
+ * HOST and travel by value in the kernel arguments, like the Adam table: nothing is uploaded.  Per clip in float64, with p = softmax(z),
+ * y the label, w = class_weight, eps = label_smoothing, g = focal_gamma:
+ *   y == ignore_index    tested FIRST (so ignore_index may be 0 or 1): nothing is added to loss, gradient or denominator; not a bad label.
+ *   other y outside {0, 1}   as in ww_ce_loss_f32 (no loss, zero gradient, bad_labels += 1) and left out of the denominator too.
+ *   WW_LOSS_CE     torch's F.cross_entropy(weight=w, label_smoothing=eps, ignore_index=):
+ *                    l = (1 - eps) w[y] (-log p_y) + (eps / 2) sum_c w[c] (-log p_c)
+ *                    dl/dz_k = (1 - eps) w[y] (p_k - [k == y]) + (eps / 2) ((w0 + w1) p_k - w[k])
+ *                  WW_REDUCE_MEAN divides the sum of l and every gradient by W = sum over counted clips of w[y]; WW_REDUCE_SUM by 1.
+ *   WW_LOSS_FOCAL  Lin et al. as torchvision reduces it, with q = the OTHER class's softmax term (never 1 - p_y):
+ *                    l = w[y] q^g (-log p_y);  dl/dz_y = w[y] (g p_y q^g log p_y - q^(g+1));  dl/dz_other = -dl/dz_y
+ *                  WW_REDUCE_MEAN divides by the NUMBER of counted clips.  label_smoothing must be 0.
+ *   a denominator of 0 under WW_REDUCE_MEAN (every clip ignored, or only zero-weight classes present): the loss is NaN, as in torch, but
+ *   every dlogits entry is exactly 0 -- unlike torch, whose gradient is NaN there: such a batch must not poison the weights.
+ * Prediction, `correct` (an ignored clip is not correct) and `total += n` are ww_ce_loss_f32's; loss_sum adds the float32 value written to
+ * loss_dev, the batch mean or the batch sum.  With unit weights, eps = 0 and nothing ignored the results have ww_ce_loss_f32's bits.
+ * Pointers and n as for ww_ce_loss_f32.  Checked before any HIP call (WW_EINVAL naming the field): finite class_weight >= 0,
+ * label_smoothing in [0, 1] (0 for the focal loss), finite focal_gamma >= 0, kind, reduction. */
+#define WW_LOSS_CE 0
+#define WW_LOSS_FOCAL 1
+#define WW_REDUCE_MEAN 0
+#define WW_REDUCE_SUM 1
+typedef struct ww_loss_opts {
+    double class_weight[2]; /* finite, >= 0 */
+    double label_smoothing; /* [0, 1] */
+    double focal_gamma;     /* >= 0; read by WW_LOSS_FOCAL only */
+    int64_t ignore_index;   /* torch's default is -100 */
+    int32_t kind;           /* WW_LOSS_CE or WW_LOSS_FOCAL */
+    int32_t reduction;      /* WW_REDUCE_MEAN or WW_REDUCE_SUM */
+} ww_loss_opts;             /* 48 bytes, HOST memory */
+WW_API int ww_ce_loss_ex_f32(const float* logits_dev, const int64_t* labels_dev, int64_t n, const ww_loss_opts* opts_host, float* dlogits_dev,
+                             float* loss_dev, ww_loss_stats* stats_dev, ww_stream_t stream);
 /* ww_adam_step_f32: one launch of torch's single-tensor Adam (no amsgrad, no maximize) over up to WW_ADAM_MAX_TENSORS tensors.  The table
  * is read on the HOST and travels in the kernel arguments: nothing is uploaded.
  *   g' = g * scale + weight_decay * p;  m += (g' - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g'^2;

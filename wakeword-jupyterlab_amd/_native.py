@@ -113,6 +113,16 @@ class LossStats(C.Structure):
                 ("nonfinite", C.c_int64)]
 
 
+class LossOpts(C.Structure):
+    """struct ww_loss_opts (include/wakeword_amd.h): what ww_ce_loss_ex_f32 computes, HOST memory."""
+    _fields_ = [("class_weight", C.c_double * 2), ("label_smoothing", C.c_double), ("focal_gamma", C.c_double), ("ignore_index", C.c_int64),
+                ("kind", C.c_int32), ("reduction", C.c_int32)]
+
+
+LOSS_CE, LOSS_FOCAL = 0, 1
+REDUCE_MEAN, REDUCE_SUM = 0, 1
+
+
 class AdamTensor(C.Structure):
     """struct ww_adam_tensor (include/wakeword_amd.h): one entry of the Adam / gradient-norm table, DEVICE pointers."""
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
@@ -240,6 +250,7 @@ PROTOTYPES = {
     "ww_train_backward_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(TrainParams), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
                                         C.POINTER(TrainGrads), C.c_void_p]),
     "ww_ce_loss_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_ce_loss_ex_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(LossOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_adam_step_f32": (C.c_int, [C.POINTER(AdamTensor), C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
                                    C.c_void_p, C.c_void_p]),
     "ww_grad_norm_workspace_bytes": (C.c_int64, [C.POINTER(AdamTensor), C.c_int64]),

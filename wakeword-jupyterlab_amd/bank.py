@@ -24,6 +24,7 @@ import torch
 
 from . import _native as nat
 from .config import AudioConfig, n_samples
+from .sampling import balanced_order, check_positive_fraction
 
 # struct ww_bank_item as a numpy record (include/wakeword_amd.h)
 ITEM_DTYPE = np.dtype([("offset", "<i8"), ("length", "<i8"), ("start", "<i8"), ("peak", "<f4"), ("row", "<i4"), ("norm", "<i4"),
@@ -352,10 +353,11 @@ class ClipBank:
                                                      out.stride(0), _ptr(ws), stream))
         return out
 
-    def loader(self, batch_size=16, shuffle=False, drop_last=False, augment=False):
+    def loader(self, batch_size=16, shuffle=False, drop_last=False, augment=False, positive_fraction=None):
         """What `dataset.loader(batch_size, shuffle, drop_last)` is, fed from device memory: re-iterable, with len() and order(),
-        yielding `(data [B,1,80,T], target [B,1])` on the device.  `augment=True` runs processor.augment_batch on every batch."""
-        return BankLoader(self, batch_size, shuffle=shuffle, drop_last=drop_last, augment=augment)
+        yielding `(data [B,1,80,T], target [B,1])` on the device.  `augment=True` runs processor.augment_batch on every batch;
+        `positive_fraction=f` fixes the share of wake-word items of every epoch, as in dataset.loader."""
+        return BankLoader(self, batch_size, shuffle=shuffle, drop_last=drop_last, augment=augment, positive_fraction=positive_fraction)
 
 
 class BankLoader:
@@ -365,9 +367,10 @@ class BankLoader:
     `processor.set_spec_augment` on (which draws its seed), rows of placeholders set to 0.0 -- the draw order of the file loader, so a
     seeded epoch over the same files yields the same batches bit for bit."""
 
-    def __init__(self, bank, batch_size=16, shuffle=False, drop_last=False, augment=False):
+    def __init__(self, bank, batch_size=16, shuffle=False, drop_last=False, augment=False, positive_fraction=None):
         if batch_size < 1:
             raise ValueError("batch_size must be positive")
+        self.positive_fraction = check_positive_fraction(positive_fraction, bool(shuffle))
         if augment:
             bank.processor._check_augment()
         self.bank, self.batch_size, self.shuffle, self.drop_last, self.augment = bank, int(batch_size), bool(shuffle), bool(drop_last), bool(augment)
@@ -377,9 +380,13 @@ class BankLoader:
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
     def order(self):
-        """Item order of one epoch (a fresh permutation from torch's default generator when shuffling)."""
+        """Item order of one epoch (a fresh permutation from torch's default generator when shuffling; with positive_fraction the
+        class-balanced draw of sampling.balanced_order over the items' labels)."""
         n = self.bank.n_items
-        idx = torch.randperm(n).tolist() if self.shuffle else list(range(n))
+        if self.positive_fraction is not None:
+            idx = balanced_order(self.bank.labels[self.bank.item_entries()], self.positive_fraction).tolist()
+        else:
+            idx = torch.randperm(n).tolist() if self.shuffle else list(range(n))
         return idx[: len(self) * self.batch_size] if self.drop_last else idx
 
     def __iter__(self):

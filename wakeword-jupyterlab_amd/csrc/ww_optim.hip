@@ -2,6 +2,8 @@
 // gradient and the epoch's running metrics, a multi-tensor Adam step, and the global gradient norm that clips it.
 //   ce_loss_kernel      one workgroup: per clip the loss and d loss / d logits in float64, the batch mean summed in a fixed order,
 //                       one lane updates the ww_loss_stats record (stream order serialises the calls: no atomics)
+//   ce_loss_ex_kernel   the same shape with class weights, label smoothing, ignore_index, a sum reduction and the focal loss (section 3k):
+//                       under the mean a pass over the labels alone first gives the denominator
 //   adam_kernel         one launch over up to 16 tensors, the table in the kernel arguments; torch's single-tensor Adam arithmetic
 //   grad_norm_kernel    float64 partial sums of g^2 per 4096 elements; grad_norm_finish_kernel adds them and writes norm and clip scale
 // All three are memory- and latency-bound.  No float atomics anywhere: every sum has one order, so results repeat bit for bit.
@@ -122,6 +124,164 @@ __global__ __launch_bounds__(kCeThreads) void ce_loss_kernel(const float* __rest
 
 int launch_ce_loss(const float* logits, const int64_t* labels, int64_t n, float* dlogits, float* loss, ww_loss_stats* stats, hipStream_t stream) {
     hipLaunchKernelGGL(ce_loss_kernel, dim3(1), dim3(kCeThreads), 0, stream, logits, labels, n, dlogits, loss, stats);
+    WW_HIP(hipGetLastError());
+    return WW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// cross-entropy with class weights, label smoothing and ignore_index, and focal loss
+// ---------------------------------------------------------------------------------------------
+// One clip in float64, NOT yet divided by the mean's denominator.  A clip counts (`valid`) with a label in {0, 1} that is not
+// ignore_index (the ignore test comes first, so ignore_index may be 0 or 1).  With unit weights, no smoothing and the cross-entropy kind
+// the loss and the gradient have the bits of ce_clip.
+struct ExClip { double loss, d0, d1; int correct, bad, nonfinite; };
+
+__device__ __forceinline__ ExClip ex_clip(float z0f, float z1f, int64_t y, const ww_loss_opts& o) {
+    ExClip r;
+    const double z0 = double(z0f), z1 = double(z1f);
+    const double m = z0 > z1 ? z0 : z1;
+    const double e0 = exp(z0 - m), e1 = exp(z1 - m), s = e0 + e1;
+    const bool ignored = y == o.ignore_index;
+    const bool valid = !ignored && (y == 0 || y == 1);
+    const double lse = m + log(s);
+    const double p0 = e0 / s, p1 = e1 / s;
+    const double w0 = o.class_weight[0], w1 = o.class_weight[1];
+    const double wy = y == 1 ? w1 : w0;
+    const double nly = lse - (y == 1 ? z1 : z0);            // -log p_y
+    double loss, d0, d1;
+    if (o.kind == WW_LOSS_FOCAL) {
+        const double py = y == 1 ? p1 : p0, q = y == 1 ? p0 : p1;      // q = the OTHER class's softmax term, never 1 - p_y
+        const double qg = exp(-o.focal_gamma * (lse - (y == 1 ? z0 : z1)));    // q^gamma from log q = z_other - lse: one exp, and 1 at gamma = 0
+        loss = wy * qg * nly;
+        const double dy = wy * (-o.focal_gamma * py * qg * nly - qg * q);
+        d0 = y == 0 ? dy : -dy;
+        d1 = y == 1 ? dy : -dy;
+    } else {
+        const double eps = o.label_smoothing, keep = (1.0 - eps) * wy, half = 0.5 * eps;
+        loss = keep * nly + half * (w0 * (lse - z0) + w1 * (lse - z1));
+        d0 = keep * (p0 - (y == 0 ? 1.0 : 0.0)) + half * ((w0 + w1) * p0 - w0);
+        d1 = keep * (p1 - (y == 1 ? 1.0 : 0.0)) + half * ((w0 + w1) * p1 - w1);
+    }
+    r.loss = valid ? loss : 0.0;
+    r.d0 = valid ? d0 : 0.0;
+    r.d1 = valid ? d1 : 0.0;
+    const int pred = z1f > z0f ? 1 : 0;
+    r.correct = valid && int64_t(pred) == y;
+    r.bad = !ignored && !valid;
+    r.nonfinite = !(isfinite(z0f) && isfinite(z1f));
+    return r;
+}
+
+// ce_loss_kernel's shape -- one workgroup, lane t owns the clip pairs t, t + 256, ..., the same fold -- with a pass over the labels alone
+// in front of it under the mean reduction: the weighted mean divides every gradient by W = n0 w0 + n1 w1, and two integer counts give W
+// exactly before the first gradient is written.  The options travel by value in the kernel arguments.
+__global__ __launch_bounds__(kCeThreads) void ce_loss_ex_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int64_t n,
+                                                                const ww_loss_opts o, float* __restrict__ dlogits, float* __restrict__ loss_out,
+                                                                ww_loss_stats* __restrict__ stats) {
+    __shared__ double red_loss[kCeThreads / 64];
+    __shared__ int red_cnt[3][kCeThreads / 64];
+    __shared__ int red_cls[2][kCeThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool z_wide = (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
+    const bool y_wide = (reinterpret_cast<uintptr_t>(labels) & 15) == 0;
+    const bool d_wide = (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;
+    const int64_t pairs = (n + 1) >> 1;
+    const bool mean = o.reduction == WW_REDUCE_MEAN;
+    double inv = 1.0;                                       // 1 / denominator; 0 when the denominator is 0: such a batch moves no weight
+    bool empty = false;
+    if (mean) {
+        int c0 = 0, c1 = 0;
+        for (int64_t p = tid; p < pairs; p += kCeThreads) {
+            const int64_t i = 2 * p;
+            const bool two = i + 1 < n;
+            int64_t y[2] = {o.ignore_index, o.ignore_index};
+            if (two && y_wide) {
+                const longlong2 v = *reinterpret_cast<const longlong2*>(labels + i);
+                y[0] = v.x; y[1] = v.y;
+            } else {
+                y[0] = labels[i];
+                if (two) y[1] = labels[i + 1];
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const bool counted = y[j] != o.ignore_index;
+                c0 += counted && y[j] == 0;
+                c1 += counted && y[j] == 1;
+            }
+        }
+        c0 = wave_sum(c0); c1 = wave_sum(c1);
+        if (lane == 0) { red_cls[0][wave] = c0; red_cls[1][wave] = c1; }
+        __syncthreads();
+        int64_t n0 = 0, n1 = 0;
+#pragma unroll
+        for (int w = 0; w < kCeThreads / 64; ++w) { n0 += red_cls[0][w]; n1 += red_cls[1][w]; }
+        const double denom = o.kind == WW_LOSS_FOCAL ? double(n0 + n1) : double(n0) * o.class_weight[0] + double(n1) * o.class_weight[1];
+        empty = !(denom > 0.0);
+        inv = empty ? 0.0 : 1.0 / denom;
+    }
+    double loss = 0.0;
+    int correct = 0, bad = 0, nonfinite = 0;
+    for (int64_t p = tid; p < pairs; p += kCeThreads) {
+        const int64_t i = 2 * p;
+        const bool two = i + 1 < n;
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        int64_t y[2] = {0, 0};
+        if (two && z_wide) {
+            const float4 v = *reinterpret_cast<const float4*>(logits + 2 * i);
+            z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
+        } else {
+            z[0] = logits[2 * i]; z[1] = logits[2 * i + 1];
+            if (two) { z[2] = logits[2 * i + 2]; z[3] = logits[2 * i + 3]; }
+        }
+        if (two && y_wide) {
+            const longlong2 v = *reinterpret_cast<const longlong2*>(labels + i);
+            y[0] = v.x; y[1] = v.y;
+        } else {
+            y[0] = labels[i];
+            if (two) y[1] = labels[i + 1];
+        }
+        const ExClip a = ex_clip(z[0], z[1], y[0], o);
+        loss += a.loss; correct += a.correct; bad += a.bad; nonfinite += a.nonfinite;
+        float d[4] = {float(a.d0 * inv), float(a.d1 * inv), 0.f, 0.f};
+        if (two) {
+            const ExClip b = ex_clip(z[2], z[3], y[1], o);
+            loss += b.loss; correct += b.correct; bad += b.bad; nonfinite += b.nonfinite;
+            d[2] = float(b.d0 * inv); d[3] = float(b.d1 * inv);
+        }
+        if (empty) d[0] = d[1] = d[2] = d[3] = 0.f;         // not 0 x NaN
+        if (dlogits) {
+            if (two && d_wide) {
+                *reinterpret_cast<float4*>(dlogits + 2 * i) = make_float4(d[0], d[1], d[2], d[3]);
+            } else {
+                dlogits[2 * i] = d[0]; dlogits[2 * i + 1] = d[1];
+                if (two) { dlogits[2 * i + 2] = d[2]; dlogits[2 * i + 3] = d[3]; }
+            }
+        }
+    }
+    loss = wave_sum(loss); correct = wave_sum(correct); bad = wave_sum(bad); nonfinite = wave_sum(nonfinite);
+    if (lane == 0) { red_loss[wave] = loss; red_cnt[0][wave] = correct; red_cnt[1][wave] = bad; red_cnt[2][wave] = nonfinite; }
+    __syncthreads();
+    if (tid == 0) {
+        double total = red_loss[0];
+        int c = red_cnt[0][0], b = red_cnt[1][0], f = red_cnt[2][0];
+#pragma unroll
+        for (int w = 1; w < kCeThreads / 64; ++w) { total += red_loss[w]; c += red_cnt[0][w]; b += red_cnt[1][w]; f += red_cnt[2][w]; }
+        const float value = empty ? __builtin_nanf("") : float(total * inv);      // a mean over nothing is NaN, as in torch; rounded once
+        if (loss_out) *loss_out = value;
+        if (stats) {
+            stats->loss_sum += double(value);
+            stats->correct += c;
+            stats->total += n;
+            stats->batches += 1;
+            stats->bad_labels += b;
+            stats->nonfinite += f;
+        }
+    }
+}
+
+int launch_ce_loss_ex(const float* logits, const int64_t* labels, int64_t n, const ww_loss_opts& opts, float* dlogits, float* loss,
+                      ww_loss_stats* stats, hipStream_t stream) {
+    hipLaunchKernelGGL(ce_loss_ex_kernel, dim3(1), dim3(kCeThreads), 0, stream, logits, labels, n, opts, dlogits, loss, stats);
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
@@ -344,6 +504,30 @@ int ww_ce_loss_f32(const float* logits_dev, const int64_t* labels_dev, int64_t n
         return fail(WW_EINVAL, "labels_dev / stats_dev must be 8-byte aligned");
     if (int rc = require_gfx950()) return rc;
     return launch_ce_loss(logits_dev, labels_dev, n, dlogits_dev, loss_dev, stats_dev, static_cast<hipStream_t>(stream));
+}
+
+int ww_ce_loss_ex_f32(const float* logits_dev, const int64_t* labels_dev, int64_t n, const ww_loss_opts* opts_host, float* dlogits_dev,
+                      float* loss_dev, ww_loss_stats* stats_dev, ww_stream_t stream) {
+    if (n <= 0 || n > (int64_t(1) << 30)) return fail(WW_EINVAL, "n %lld: expected 1..2^30", (long long)n);
+    if (!logits_dev || !labels_dev) return fail(WW_EINVAL, "null logits / labels pointer");
+    if (!opts_host) return fail(WW_EINVAL, "null opts_host pointer");
+    if ((reinterpret_cast<uintptr_t>(logits_dev) & 3) || (reinterpret_cast<uintptr_t>(dlogits_dev) & 3) || (reinterpret_cast<uintptr_t>(loss_dev) & 3))
+        return fail(WW_EINVAL, "logits_dev / dlogits_dev / loss_dev must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(labels_dev) & 7) || (reinterpret_cast<uintptr_t>(stats_dev) & 7))
+        return fail(WW_EINVAL, "labels_dev / stats_dev must be 8-byte aligned");
+    const ww_loss_opts o = *opts_host;
+    for (int c = 0; c < 2; ++c)
+        if (!(o.class_weight[c] >= 0.0) || std::isinf(o.class_weight[c]))
+            return fail(WW_EINVAL, "class_weight[%d] %g: expected a finite value >= 0", c, o.class_weight[c]);
+    if (!(o.label_smoothing >= 0.0 && o.label_smoothing <= 1.0)) return fail(WW_EINVAL, "label_smoothing %g: expected [0, 1]", o.label_smoothing);
+    if (!(o.focal_gamma >= 0.0) || std::isinf(o.focal_gamma)) return fail(WW_EINVAL, "focal_gamma %g: expected a finite value >= 0", o.focal_gamma);
+    if (o.kind != WW_LOSS_CE && o.kind != WW_LOSS_FOCAL) return fail(WW_EINVAL, "kind %d: expected WW_LOSS_CE or WW_LOSS_FOCAL", int(o.kind));
+    if (o.reduction != WW_REDUCE_MEAN && o.reduction != WW_REDUCE_SUM)
+        return fail(WW_EINVAL, "reduction %d: expected WW_REDUCE_MEAN or WW_REDUCE_SUM", int(o.reduction));
+    if (o.kind == WW_LOSS_FOCAL && o.label_smoothing != 0.0)
+        return fail(WW_EINVAL, "label_smoothing %g: the focal loss takes none", o.label_smoothing);
+    if (int rc = require_gfx950()) return rc;
+    return launch_ce_loss_ex(logits_dev, labels_dev, n, o, dlogits_dev, loss_dev, stats_dev, static_cast<hipStream_t>(stream));
 }
 
 int ww_adam_step_f32(const ww_adam_tensor* tensors_host, int64_t n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,

@@ -24,6 +24,7 @@ import torch
 from torch.utils.data import Dataset
 
 from .config import n_frames
+from .sampling import balanced_order, check_positive_fraction
 
 
 class WakewordDataset(Dataset):
@@ -60,13 +61,15 @@ class WakewordDataset(Dataset):
         decode / resample / normalise / crop run in kernel K0, log-mel in K1."""
         return iter(GpuBatchLoader(self, batch_size, shuffle=False))
 
-    def loader(self, batch_size=16, shuffle=False, drop_last=False):
+    def loader(self, batch_size=16, shuffle=False, drop_last=False, positive_fraction=None):
         """What `DataLoader(dataset, batch_size=.., shuffle=.., num_workers=2)` is to the reference's loops
         (/root/reference/wakeword_training_script.py:461-463), without worker processes: an iterable with `len()`, re-iterable
         (a new permutation per epoch when shuffle=True, drawn from torch's generator like RandomSampler: `torch.manual_seed`
         repeats it), yielding `(data [B,1,80,T], target [B,1])` on the GPU (T = 32 at 1 s).  Files are read by the library's reader threads into
-        pinned staging, decoded (K0), augmented when the dataset says so (KA) and turned into log-mel (K1) one batch at a time."""
-        return GpuBatchLoader(self, batch_size, shuffle=shuffle, drop_last=drop_last)
+        pinned staging, decoded (K0), augmented when the dataset says so (KA) and turned into log-mel (K1) one batch at a time.
+        `positive_fraction=f` in (0, 1), with shuffle=True: every epoch keeps its length and holds that share of wake-word items
+        (sampling.balanced_order); None, the default, leaves the order as it was."""
+        return GpuBatchLoader(self, batch_size, shuffle=shuffle, drop_last=drop_last, positive_fraction=positive_fraction)
 
     def cache(self):
         """This dataset's files decoded once into device memory: a bank.ClipBank whose `loader(..., augment=self.augment)` yields what
@@ -76,10 +79,11 @@ class WakewordDataset(Dataset):
 
 
 class GpuBatchLoader:
-    def __init__(self, dataset, batch_size=16, shuffle=False, drop_last=False):
+    def __init__(self, dataset, batch_size=16, shuffle=False, drop_last=False, positive_fraction=None):
         if batch_size < 1:
             raise ValueError("batch_size must be positive")
         self.dataset, self.batch_size, self.shuffle, self.drop_last = dataset, int(batch_size), bool(shuffle), bool(drop_last)
+        self.positive_fraction = check_positive_fraction(positive_fraction, self.shuffle)
         self._encoded = None
 
     def __len__(self):
@@ -87,9 +91,13 @@ class GpuBatchLoader:
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
     def order(self):
-        """Index order of one epoch (a fresh permutation from torch's default generator when shuffling)."""
+        """Index order of one epoch (a fresh permutation from torch's default generator when shuffling; with positive_fraction the
+        class-balanced draw of sampling.balanced_order)."""
         n = len(self.dataset)
-        idx = torch.randperm(n).tolist() if self.shuffle else list(range(n))
+        if self.positive_fraction is not None:
+            idx = balanced_order(self.dataset.labels, self.positive_fraction).tolist()
+        else:
+            idx = torch.randperm(n).tolist() if self.shuffle else list(range(n))
         return idx[: len(self) * self.batch_size] if self.drop_last else idx
 
     def __iter__(self):
@@ -144,13 +152,14 @@ class GpuBatchLoader:
             yield data, target
 
 
-def DataLoader(dataset, batch_size=1, shuffle=False, *args, num_workers=0, drop_last=False, **kwargs):
+def DataLoader(dataset, batch_size=1, shuffle=False, *args, num_workers=0, drop_last=False, positive_fraction=None, **kwargs):
     """Drop-in for the name the reference imports (`from torch.utils.data import Dataset, DataLoader`,
     /root/reference/wakeword_training_script.py:9): with it the script's loader lines (:461-463,
     `DataLoader(train_dataset, batch_size=16, shuffle=True, num_workers=2)`) run unchanged.  For a WakewordDataset it returns
     `dataset.loader(batch_size, shuffle, drop_last)` -- `num_workers` is accepted and not used: the library's reader threads and the GPU
     kernels do what the worker processes did (a forked worker could not touch the GPU anyway).  Any other dataset goes to torch's
-    DataLoader untouched.  A sampler / batch_sampler / collate_fn on a WakewordDataset is refused (the batch is built on the GPU)."""
+    DataLoader untouched.  A sampler / batch_sampler / collate_fn on a WakewordDataset is refused (the batch is built on the GPU);
+    `positive_fraction=` is what a WeightedRandomSampler would be used for here: it goes through to `dataset.loader` / `bank.loader`."""
     if isinstance(dataset, WakewordDataset):
         unsupported = [k for k in ("sampler", "batch_sampler", "collate_fn") if kwargs.get(k) is not None]
         if args or unsupported:
@@ -158,7 +167,7 @@ def DataLoader(dataset, batch_size=1, shuffle=False, *args, num_workers=0, drop_
                                       " are not supported -- the batch is assembled on the GPU (dataset.loader)")
         if batch_size is None:
             raise NotImplementedError("DataLoader(WakewordDataset, batch_size=None): unbatched loading is dataset[i]")
-        return dataset.loader(batch_size=batch_size, shuffle=bool(shuffle), drop_last=bool(drop_last))
+        return dataset.loader(batch_size=batch_size, shuffle=bool(shuffle), drop_last=bool(drop_last), positive_fraction=positive_fraction)
     from .bank import ClipBank
     if isinstance(dataset, ClipBank):                  # the same refusals; `augment=` goes through to bank.loader
         augment = bool(kwargs.pop("augment", False))
@@ -168,5 +177,8 @@ def DataLoader(dataset, batch_size=1, shuffle=False, *args, num_workers=0, drop_
                                       " are not supported -- the batch is assembled on the GPU (bank.loader)")
         if batch_size is None:
             raise NotImplementedError("DataLoader(ClipBank, batch_size=None): unbatched loading is bank.gather")
-        return dataset.loader(batch_size=batch_size, shuffle=bool(shuffle), drop_last=bool(drop_last), augment=augment)
+        return dataset.loader(batch_size=batch_size, shuffle=bool(shuffle), drop_last=bool(drop_last), augment=augment,
+                              positive_fraction=positive_fraction)
+    if positive_fraction is not None:
+        raise NotImplementedError("DataLoader(..., positive_fraction=): only a WakewordDataset or a ClipBank has the labels to balance")
     return torch.utils.data.DataLoader(dataset, batch_size, shuffle, *args, num_workers=num_workers, drop_last=drop_last, **kwargs)

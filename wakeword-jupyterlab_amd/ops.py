@@ -845,23 +845,57 @@ def _check_ce(logits, labels):
     return labels if labels.stride(0) == 1 or labels.shape[0] == 1 else labels.contiguous()
 
 
-def ce_loss_into(logits, labels, dlogits, loss, stats) -> None:
-    """ww_ce_loss_f32 on caller-owned outputs (each may be None); `labels` as _check_ce returns them.  Allocates nothing."""
+def loss_opts(weight=None, label_smoothing=0.0, ignore_index=-100, reduction="mean", focal_gamma=None):
+    """The loss options as the struct ww_ce_loss_ex_f32 takes (nat.LossOpts, host memory), or None when every option is at its default:
+    the plain ww_ce_loss_f32 call.  ValueError / NotImplementedError (reduction="none") before any device call (loss.check_options)."""
+    from .loss import check_options
+    w, eps, ignore, reduction, gamma = check_options(weight, label_smoothing, ignore_index, reduction, focal_gamma)
+    if w is None and eps == 0.0 and ignore == -100 and reduction == "mean" and gamma is None:
+        return None
+    o = nat.LossOpts()
+    o.class_weight[0], o.class_weight[1] = w if w is not None else (1.0, 1.0)
+    o.label_smoothing, o.focal_gamma, o.ignore_index = eps, 0.0 if gamma is None else gamma, ignore
+    o.kind = nat.LOSS_CE if gamma is None else nat.LOSS_FOCAL
+    o.reduction = nat.REDUCE_MEAN if reduction == "mean" else nat.REDUCE_SUM
+    return o
+
+
+def ce_loss_into(logits, labels, dlogits, loss, stats, *, weight=None, label_smoothing=0.0, ignore_index=-100, reduction="mean",
+                 focal_gamma=None, opts=None) -> None:
+    """ww_ce_loss_f32 -- or, with any loss option given, ww_ce_loss_ex_f32 -- on caller-owned outputs (each may be None); `labels` as
+    _check_ce returns them.  `opts`: what ops.loss_opts() made of the options, built once by a caller that launches per batch (it wins
+    over the keywords).  Allocates nothing on the device."""
+    if opts is None:
+        opts = loss_opts(weight, label_smoothing, ignore_index, reduction, focal_gamma)
     with torch.cuda.device(logits.device):
-        nat.check(nat.lib.ww_ce_loss_f32(_ptr(logits), _ptr(labels), logits.shape[0], None if dlogits is None else _ptr(dlogits),
-                                         None if loss is None else _ptr(loss), None if stats is None else _ptr(stats), _stream()))
+        if opts is None:
+            nat.check(nat.lib.ww_ce_loss_f32(_ptr(logits), _ptr(labels), logits.shape[0], None if dlogits is None else _ptr(dlogits),
+                                             None if loss is None else _ptr(loss), None if stats is None else _ptr(stats), _stream()))
+        else:
+            nat.check(nat.lib.ww_ce_loss_ex_f32(_ptr(logits), _ptr(labels), logits.shape[0], C.byref(opts),
+                                                None if dlogits is None else _ptr(dlogits), None if loss is None else _ptr(loss),
+                                                None if stats is None else _ptr(stats), _stream()))
 
 
-def ce_loss(logits: torch.Tensor, labels: torch.Tensor, stats=None, grad: bool = True):
+def ce_loss(logits: torch.Tensor, labels: torch.Tensor, stats=None, grad: bool = True, *, weight=None, label_smoothing=0.0,
+            ignore_index=-100, reduction="mean", focal_gamma=None):
     """CrossEntropyLoss (mean) over two classes: (loss [] float32, dlogits [n, 2] = (softmax - onehot) / n, or None with grad=False).
     logits [n, 2] float32 and labels [n] or [n, 1] int64 on the GPU.  `stats` (ops.new_loss_stats) accumulates the batch mean, the correct
-    predictions and the counts of bad labels and non-finite logits on the device; nothing here waits for it."""
+    predictions and the counts of bad labels and non-finite logits on the device; nothing here waits for it.
+
+    The keyword-only options are those of F.cross_entropy: `weight` (two floats or a tensor of two),
+    `label_smoothing`, `ignore_index`, `reduction` ("mean" or "sum"; "none" raises NotImplementedError); `focal_gamma` (a number) turns
+    the loss into the focal loss of loss.FocalLoss.  A bad value raises ValueError before any device call.  With every option at its
+    default this is the ww_ce_loss_f32 call it always was, and a label of -100 is then a BAD label like any other outside {0, 1}; as soon
+    as one option differs from its default, labels equal to `ignore_index` (-100 unless said otherwise) are ignored as torch ignores
+    them.  When the mean's denominator is 0 the loss is NaN, as in torch, and the gradient is all zeros, unlike torch's."""
+    opts = loss_opts(weight, label_smoothing, ignore_index, reduction, focal_gamma)
     labels = _check_ce(logits, labels)
     if stats is not None:
         _check_stats(stats, logits)
     loss = torch.empty((), device=logits.device, dtype=torch.float32)
     dlogits = torch.empty_like(logits) if grad else None
-    ce_loss_into(logits, labels, dlogits, loss, stats)
+    ce_loss_into(logits, labels, dlogits, loss, stats, opts=opts)
     return loss, dlogits
 
 

@@ -2,7 +2,7 @@
 
 Same constructor, attributes and methods -- `criterion`, `optimizer`, `scheduler`, the four history lists, `patience`, `best_val_acc`,
 `epochs_no_improve`; `train_epoch`, `validate`, `train` -- and the same checkpoint dict.  What differs is what a batch costs: `step` calls
-the C entry points directly, train forward -> cross-entropy (loss, gradient, running metrics) -> backward -> optional gradient-norm clip
+the C entry points directly, train forward -> the loss `criterion` names (loss, gradient, running metrics) -> backward -> optional gradient-norm clip
 -> Adam, without autograd, without a torch kernel in between, without a device-to-host copy and, after the first call at a batch size,
 without an allocation.  The epoch's loss and accuracy are kept on the device and read once, at the end of the epoch.
 
@@ -36,7 +36,7 @@ MONITOR_NAMES = {"val_acc": "Acc", "val_f1": "F1", "val_auc": "AUC"}
 
 class WakewordTrainer:
     def __init__(self, model, device, config=TrainingConfig, *, checkpoint_path="best_wakeword_model.pth", max_grad_norm=None,
-                 monitor="val_acc", thresholds=(0.8,)):
+                 monitor="val_acc", thresholds=(0.8,), criterion=None):
         if not isinstance(model, (SimpleWakewordModel, WakewordModel)):
             raise TypeError(f"WakewordTrainer drives the HIP training kernels of SimpleWakewordModel and WakewordModel; got {type(model).__name__}")
         if any(p.device.type != "cuda" for p in model.parameters()):
@@ -52,7 +52,8 @@ class WakewordTrainer:
         self.checkpoint_path = checkpoint_path
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
 
-        self.criterion = nn.CrossEntropyLoss().to(device)             # the reference's attribute; `step` computes the same loss in ww_ce_loss_f32
+        # the reference's attribute; `step` and `validate` compute the same loss in ww_ce_loss_f32 / ww_ce_loss_ex_f32 (the property below)
+        self.criterion = nn.CrossEntropyLoss().to(device) if criterion is None else criterion
         self.optimizer = FusedAdam(model.parameters(), lr=config.LEARNING_RATE, weight_decay=1e-5)
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="max", factor=0.5, patience=5)
 
@@ -92,6 +93,29 @@ class WakewordTrainer:
         if self.max_grad_norm is not None:
             self._norm = torch.zeros(1, device=self._dev, dtype=torch.float64)
             self._scale = torch.ones(1, device=self._dev, dtype=torch.float32)
+
+    # ---- the loss: what `criterion` holds is what the fused step computes ----
+    @property
+    def criterion(self):
+        """The loss of `step` and `validate`: an nn.CrossEntropyLoss (weight, label_smoothing, ignore_index, reduction "mean" or "sum") or
+        a loss.FocalLoss (gamma, weight, ignore_index, reduction).  Assigning reads these attributes ONCE and copies the weight to the host
+        (one device-to-host copy, at the assignment, not in the step): a later in-place change of the module or of its weight tensor is
+        not seen until the criterion is assigned again.  Anything else raises TypeError, reduction="none" NotImplementedError -- at the
+        assignment; nothing is silently ignored.  The default nn.CrossEntropyLoss() runs the plain ww_ce_loss_f32 launch, under which a
+        label of -100 is a bad label; under any other criterion labels equal to its ignore_index are ignored."""
+        return self._criterion
+
+    @criterion.setter
+    def criterion(self, module):
+        from .loss import FocalLoss
+        if isinstance(module, FocalLoss):
+            opts = ops.loss_opts(module.weight, 0.0, module.ignore_index, module.reduction, module.gamma)
+        elif type(module) is nn.CrossEntropyLoss:
+            opts = ops.loss_opts(module.weight, module.label_smoothing, module.ignore_index, module.reduction, None)
+        else:
+            raise TypeError(f"WakewordTrainer.criterion: the fused step computes nn.CrossEntropyLoss or FocalLoss, not {type(module).__name__} "
+                            "(a hand-written loop over ops.train_forward can use any loss)")
+        self._criterion, self._loss_opts = module, opts
 
     # ---- gradients: one persistent buffer per parameter, bound once ----
     def _bind_grads(self) -> None:
@@ -183,8 +207,12 @@ class WakewordTrainer:
             nat.check(nat.lib.ww_train_forward_f32(ops._ptr(x), B, T, C.byref(self._tp), float(m.lstm.dropout), float(m.dropout.p),
                                                    seed & (2 ** 64 - 1), math, ops._ptr(self._ws), self._ws.numel(), ops._ptr(self._logits),
                                                    stream))
-            nat.check(nat.lib.ww_ce_loss_f32(ops._ptr(self._logits), ops._ptr(y), B, ops._ptr(self._dlogits), ops._ptr(self.last_loss),
-                                             ops._ptr(self.train_stats), stream))
+            if self._loss_opts is None:
+                nat.check(nat.lib.ww_ce_loss_f32(ops._ptr(self._logits), ops._ptr(y), B, ops._ptr(self._dlogits), ops._ptr(self.last_loss),
+                                                 ops._ptr(self.train_stats), stream))
+            else:
+                nat.check(nat.lib.ww_ce_loss_ex_f32(ops._ptr(self._logits), ops._ptr(y), B, C.byref(self._loss_opts), ops._ptr(self._dlogits),
+                                                    ops._ptr(self.last_loss), ops._ptr(self.train_stats), stream))
             nat.check(nat.lib.ww_train_backward_f32(ops._ptr(x), B, T, C.byref(self._tp), ops._ptr(self._dlogits), math, ops._ptr(self._ws),
                                                     self._ws.numel(), C.byref(self._tg), stream))
             if self.max_grad_norm is not None:
@@ -226,7 +254,7 @@ class WakewordTrainer:
                     data = data.to(self._dev)
                 output = self.model(data)
                 y = self._target(target, output.shape[0])
-                ops.ce_loss_into(output, y, None, None, self.val_stats)
+                ops.ce_loss_into(output, y, None, None, self.val_stats, opts=self._loss_opts)
                 ops.clip_metrics_update_into(output, y, self.val_metrics)
         return self._finish_epoch(self.val_stats, "validate")
 
