@@ -2,9 +2,12 @@
 """The flow of examples/train_from_files.py with the training files kept in device memory: `train_dataset.cache()` decodes every file
 once into a ClipBank, `bank.loader(..., augment=True)` then builds each batch on the GPU without touching a
 file again, and one mining round adds the negative windows the trained model still fires on (`det_curve` -> `scan_files` ->
-`hard_negatives` -> `bank.add_pcm`) before the last epochs.
+`hard_negatives` -> `bank.add_pcm`) before the last epochs.  `--audit` prints what the bank holds (levels, clipping, silent and
+overlong clips, duplicates, files shared with the validation list) and `--crop active` draws the window of a
+clip longer than `--duration` around its active region instead of uniformly.
 
     PYTHONPATH=. python examples/train_from_bank.py [--epochs 6] [--mine-after 3] [--data DIR] [--lr 1e-4] [--duration 1.0] [--background DIR]
+                                                    [--audit] [--crop active]
 """
 import argparse
 import glob
@@ -32,6 +35,8 @@ def main():
     ap.add_argument("--duration", type=float, default=AudioConfig.DURATION, help="clip length in seconds, 0.25 .. 1.0")
     ap.add_argument("--background", default=None, help="directory of background noise files (WAV / FLAC) mixed into the training clips")
     ap.add_argument("--fa-per-hour", type=float, default=0.5, help="the operating point the mining threshold is taken from")
+    ap.add_argument("--audit", action="store_true", help="print the audit of the training bank, and its overlap with the validation bank")
+    ap.add_argument("--crop", default=None, choices=["active"], help="draw the windows of long clips around their active region")
     a = ap.parse_args()
     device = torch.device("cuda")
     wdir, ndir = os.path.join(a.data, "wakeword_data"), os.path.join(a.data, "negative_data")
@@ -49,8 +54,14 @@ def main():
     bank = WakewordDataset(w_tr, n_tr, processor, augment=True).cache()           # every training file decoded once, onto the GPU
     st = bank.stats
     print(f"{bank} -- built at {st['files_per_second']:.0f} files/s, {st['audio_seconds_per_second']:.0f} s of audio/s")
-    train_loader = DataLoader(bank, batch_size=a.batch_size, shuffle=True, augment=True)
-    val_loader = DataLoader(WakewordDataset(w_va, n_va, processor, augment=False).cache(), batch_size=a.batch_size, shuffle=False)
+    val_bank = WakewordDataset(w_va, n_va, processor, augment=False).cache()
+    if a.audit:
+        audit = bank.audit()
+        print(audit.report())
+        print(f"duplicate groups: {audit.duplicates()}")
+        print(f"entries shared with the validation list (train, validation): {audit.duplicates(other=val_bank.audit())}")
+    train_loader = bank.loader(a.batch_size, shuffle=True, augment=True, crop=a.crop)
+    val_loader = DataLoader(val_bank, batch_size=a.batch_size, shuffle=False)
     criterion = nn.CrossEntropyLoss().to(device)
     optimizer = optim.Adam(model.parameters(), lr=a.lr, weight_decay=1e-5)
     for epoch in range(a.epochs):

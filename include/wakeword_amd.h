@@ -575,6 +575,63 @@ WW_API int ww_bank_gather_f32(const float* audio_dev, int64_t total_samples, con
                               int64_t n_samples, float* out_dev, int64_t n_rows, int64_t out_stride, void* workspace_dev,
                               ww_stream_t stream);
 
+/* ---- audit of a bank -------------------------------------------------- */
+/* ww_bank_audit_f32: one pass over audio_dev [total_samples] and one record per entry e = samples offsets[e] .. offsets[e + 1] - 1
+ * (len = their number, i = a sample's index in its entry, x its value, bits its float32 bit pattern).  This comment is the definition
+ * of every field; the other documents point here.  A sample is non-finite when its exponent bits are all ones (Inf or NaN).
+ *   nonfinite   the number of non-finite samples
+ *   sum, sumsq  float64 sums of x and of x * x (exact in float64) over the finite samples; a non-finite sample adds 0
+ *   clipped     the number of finite samples with fabsf(x) >= clip_level
+ *   peak        ww_bank_peaks_f32's value for the entry, bit for bit: the fmaxf-fold from 0.0f of fabsf(x).  So a NaN adds nothing, and
+ *               an Inf -- the one case where a non-finite sample shows outside `nonfinite` -- gives Inf, the divisor the gather uses
+ *   hash        content hash, 64 bits: the wrapping uint64 sum over ALL samples of mix(bits, i), so partial sums combine in any order
+ *               and the value does not depend on where the entry lies.  With uint32 wrapping arithmetic, lo = i mod 2^32, hi = i >> 32:
+ *                 fmix32(x): x ^= x >> 16, x *= 0x85EBCA6B, x ^= x >> 13, x *= 0xC2B2AE35, x ^= x >> 16
+ *                 m  = lo * 0x9E3779B1
+ *                 k1 = bits ^ m ^ (hi * 0x85EBCA77)
+ *                 k2 = bits + rotl32(m, 15) + hi * 0xC2B2AE3D + 0x27D4EB2F
+ *                 mix(bits, i) = fmix32(k1) | fmix32(k2) << 32
+ *               -0.0f and +0.0f differ, NaN payloads count.  An empty entry hashes to 0.  Equal (len, hash) is a filter for equal
+ *               entries, not a proof: compare the samples before acting on it.
+ *   active_start, active_end   the extent [a, b) of librosa.effects.trim(frame_length = 2048, hop_length = 512, centred, zero
+ *               padded), stated in energies.  Hop block h of an entry is its samples [512 h, 512 h + 512), S[h] its float64 sum of
+ *               squares as above, 0 for a block outside the entry.  Frame t, 0 <= t <= len / 512 (integer division), has energy
+ *                 E_t = ((S[t - 2] + S[t - 1]) + S[t]) + S[t + 1]                     float64, added in that order
+ *               and is active when E_max = max_t E_t > 0 and E_t > E_max * ratio, ratio = 10^(-top_db / 10) computed by the caller.
+ *               a = 512 t_first, b = min(len, 512 (t_last + 1)) over the active frames; (0, 0) without one; (0, len) when
+ *               nonfinite > 0.  This is librosa's rule (rms_t^2 = E_t / 2048, ref = max) except where librosa clamps an rms below
+ *               1e-5 before taking the logarithm: there librosa treats a quieter frame as rms 1e-5, and this rule does not.
+ *   max_frame_energy   E_max
+ * sum and sumsq are added in a fixed order that depends on len alone: within a hop block lane l of 64 adds the samples 4 l .. 4 l + 3
+ * and 256 + 4 l .. 256 + 4 l + 3 in that order and the lanes are added in a fixed xor tree; the blocks are then added in index order.
+ * There are no float atomics, so every field is the same bits from run to run and wherever the entry lies in memory; sum and sumsq
+ * differ from the exact sums by at most len * 2^-52 * sum |terms|.
+ * offsets_dev [n_entries + 1] int64 in device memory and offsets_host the same values in host memory (the hop table is built from
+ * them): non-decreasing, offsets[0] >= 0, offsets[n_entries] <= total_samples; nothing outside an entry is read, and nothing at or
+ * past total_samples whatever the device table says.  stats_dev [n_entries] (8-byte aligned), every record written.  workspace_dev:
+ * >= ww_bank_audit_workspace_bytes(total_samples, n_entries) bytes, 256-byte aligned.  The hop table is staged through the library's
+ * pinned memory; the call is asynchronous on `stream` and cannot be captured into a graph.  Checked before any HIP call (WW_EINVAL):
+ * total_samples < 0, n_entries outside 0 .. 2^30, clip_level <= 0 or NaN, ratio outside (0, 1], the offsets as above, a null or
+ * misaligned pointer.  n_entries == 0 is WW_OK without a launch. */
+#define WW_AUDIT_HOP 512
+#define WW_AUDIT_FRAME 2048
+typedef struct ww_bank_entry_stats {
+    double sum;
+    double sumsq;
+    double max_frame_energy;
+    int64_t active_start;
+    int64_t active_end;
+    uint64_t hash;
+    int64_t clipped;
+    int64_t nonfinite;
+    float peak;
+    int32_t reserved;
+} ww_bank_entry_stats; /* 72 bytes */
+WW_API int64_t ww_bank_audit_workspace_bytes(int64_t total_samples, int64_t n_entries);
+WW_API int ww_bank_audit_f32(const float* audio_dev, int64_t total_samples, const int64_t* offsets_dev, const int64_t* offsets_host,
+                             int64_t n_entries, float clip_level, double ratio, ww_bank_entry_stats* stats_dev, void* workspace_dev,
+                             ww_stream_t stream);
+
 /* ---- training step ----------------------------------------------------- */
 /* Replaces, for one batch, `output = model(data)` in train mode and `loss.backward()` of the reference's training loops
  * (wakeword_training/train_wakeword.py:109-115; WakewordTrainer.train_epoch, wakeword_training_script.py:241-267) for

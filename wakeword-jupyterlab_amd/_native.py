@@ -103,6 +103,17 @@ class BankItem(C.Structure):
 
 
 BANK_NORM_NONE, BANK_NORM_ENTRY, BANK_NORM_WINDOW = 0, 1, 2
+
+
+class BankEntryStats(C.Structure):
+    """struct ww_bank_entry_stats (include/wakeword_amd.h): what ww_bank_audit_f32 writes per entry, DEVICE memory."""
+    _fields_ = [
+        ("sum", C.c_double), ("sumsq", C.c_double), ("max_frame_energy", C.c_double), ("active_start", C.c_int64), ("active_end", C.c_int64),
+        ("hash", C.c_uint64), ("clipped", C.c_int64), ("nonfinite", C.c_int64), ("peak", C.c_float), ("reserved", C.c_int32),
+    ]
+
+
+AUDIT_HOP, AUDIT_FRAME = 512, 2048
 SPEC_RECORD_INT16 = 16
 SPEC_FILL_MEAN, SPEC_FILL_MIN, SPEC_FILL_VALUE = 0, 1, 2
 
@@ -239,6 +250,9 @@ PROTOTYPES = {
     "ww_bank_gather_workspace_bytes": (C.c_int64, [C.c_int64]),
     "ww_bank_gather_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                      C.c_void_p]),
+    "ww_bank_audit_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "ww_bank_audit_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_double, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
     "ww_spec_augment_record_bytes": (C.c_int64, []),
     "ww_spec_augment_draw": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_void_p]),

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .audit import STATS_DTYPE, BankAudit, active_start_range, check_crop, top_db_ratio
 from .config import AudioConfig, n_samples
 from .sampling import balanced_order, check_positive_fraction
 
@@ -62,7 +63,8 @@ class ClipBank:
       add_recordings(paths | Scan, label=0, windows_per_epoch=None)   stream entries
       ClipBank.from_dataset(ds) / ds.cache()        clip entries in ds.files order with ds.labels
       gather(entries, starts=None, normalize="entry")   -> [B, N] on the device: the kernel, exposed
-      loader(batch_size, shuffle, drop_last, augment)   the drop-in for dataset.loader()
+      loader(batch_size, shuffle, drop_last, augment)   the drop-in for dataset.loader(); crop="active" keeps windows on the sound
+      audit(top_db, clip_level)                     -> BankAudit: levels, clipping, non-finite samples, active extent, content hash
 
     The bank is a list of segments: one 1-D float32 device tensor each, its entries back to back; segments are never concatenated
     with each other, and a batch whose items touch k segments costs k gather launches into disjoint rows.  Per entry (numpy, host):
@@ -82,6 +84,7 @@ class ClipBank:
         self.kinds = np.zeros(0, np.int8)
         self.windows = np.zeros(0, np.int64)                 # items per epoch (1 for a clip)
         self._items = None
+        self._audits = {}                                    # (top_db, clip_level) -> BankAudit, until a segment is added
         self.stats = {"files": 0, "unreadable": 0, "audio_seconds": 0.0, "wall_seconds": 0.0, "audio_seconds_per_second": 0.0,
                       "files_per_second": 0.0}
 
@@ -121,6 +124,7 @@ class ClipBank:
         self.kinds = np.concatenate([self.kinds, np.full(n, kind, np.int8)])
         self.windows = np.concatenate([self.windows, np.asarray(windows, np.int64)])
         self._items = None
+        self._audits = {}
         return range(self.n_entries - n, self.n_entries)
 
     def _decode(self, paths):
@@ -275,15 +279,64 @@ class ClipBank:
             self._items = np.concatenate([clips, np.repeat(streams, self.windows[streams])]).astype(np.int64)
         return self._items
 
+    def entry_samples(self, e) -> torch.Tensor:
+        """Entry e's samples: a view of its segment, on the device."""
+        e = int(e)
+        if not 0 <= e < self.n_entries:
+            raise ValueError(f"entry {e} outside [0, {self.n_entries})")
+        return self.segments[int(self._seg[e])][int(self._off[e]):int(self._off[e] + self.lengths[e])]
+
+    # ---- audit ----------------------------------------------------------------------------------
+    def audit(self, top_db=60.0, clip_level=0.999) -> BankAudit:
+        """One pass over every segment on the device (ww_bank_audit_f32: one call per segment, one copy to the host) -> BankAudit.
+        `top_db`: a frame is active when its energy lies within top_db of the entry's loudest frame (librosa.effects.trim's rule);
+        `clip_level`: |x| at or above it counts as clipped.  The result is kept until a segment is added."""
+        ratio = top_db_ratio(top_db)
+        clip_level = float(np.float32(clip_level))
+        if not clip_level > 0.0:
+            raise ValueError(f"clip_level {clip_level!r}: expected > 0")
+        key = (float(top_db), clip_level)
+        if key not in self._audits:
+            parts = []
+            for s, data in enumerate(self.segments):
+                e = np.flatnonzero(self._seg == s)
+                if e.size == 0:
+                    continue
+                table = np.ascontiguousarray(np.concatenate([self._off[e], [self._off[e[-1]] + self.lengths[e[-1]]]]), dtype=np.int64)
+                with torch.cuda.device(data.device):
+                    off = torch.from_numpy(table).to(data.device)
+                    out = torch.empty(e.size * STATS_DTYPE.itemsize, device=data.device, dtype=torch.uint8)
+                    ws = torch.empty(max(256, nat.check(nat.lib.ww_bank_audit_workspace_bytes(data.numel(), e.size))), device=data.device,
+                                     dtype=torch.uint8)
+                    nat.check(nat.lib.ww_bank_audit_f32(_ptr(data), data.numel(), _ptr(off), table.ctypes.data, e.size, clip_level, ratio,
+                                                        _ptr(out), _ptr(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                parts.append(out)
+            if parts:
+                stats = torch.cat(parts).cpu().numpy().view(STATS_DTYPE).copy()       # segments hold their entries in bank order
+            else:
+                stats = np.zeros(0, STATS_DTYPE)
+            self._audits[key] = BankAudit(stats, self.lengths.copy(), self.n_samples, self.labels.copy(), self.ok.copy(), self.kinds.copy(),
+                                          bank=self, top_db=top_db, clip_level=clip_level)
+        return self._audits[key]
+
     # ---- use ------------------------------------------------------------------------------------
-    def draw_starts(self, entries) -> np.ndarray:
+    def draw_starts(self, entries, crop=None) -> np.ndarray:
         """The window start of each item, in order, with python `random` (pad_or_truncate's rule): random.randint(0, len - N) where
-        len > N, else 0 and no draw (placeholders have length 0)."""
+        len > N, else 0 and no draw (placeholders have length 0).  crop="active": a clip entry's start is drawn from the range that
+        keeps the window on its active region (audit.active_start_range over `self.audit()`); one draw per entry with len > N either
+        way, and stream entries keep the uniform rule."""
         N = self.n_samples
         starts = np.zeros(len(entries), np.int64)
         lengths = self.lengths[entries]
+        if check_crop(crop) is None:
+            for i in np.flatnonzero(lengths > N):
+                starts[i] = random.randint(0, int(lengths[i]) - N)
+            return starts
+        au = self.audit()
+        clip = self.kinds[entries] == CLIP
+        lo, hi = active_start_range(lengths, np.where(clip, au.active_start[entries], 0), np.where(clip, au.active_end[entries], 0), N)
         for i in np.flatnonzero(lengths > N):
-            starts[i] = random.randint(0, int(lengths[i]) - N)
+            starts[i] = random.randint(int(lo[i]), int(hi[i]))
         return starts
 
     def gather(self, entries, starts=None, normalize="entry", out=None, rows=None) -> torch.Tensor:
@@ -353,23 +406,26 @@ class ClipBank:
                                                      out.stride(0), _ptr(ws), stream))
         return out
 
-    def loader(self, batch_size=16, shuffle=False, drop_last=False, augment=False, positive_fraction=None):
+    def loader(self, batch_size=16, shuffle=False, drop_last=False, augment=False, positive_fraction=None, crop=None):
         """What `dataset.loader(batch_size, shuffle, drop_last)` is, fed from device memory: re-iterable, with len() and order(),
         yielding `(data [B,1,80,T], target [B,1])` on the device.  `augment=True` runs processor.augment_batch on every batch;
-        `positive_fraction=f` fixes the share of wake-word items of every epoch, as in dataset.loader."""
-        return BankLoader(self, batch_size, shuffle=shuffle, drop_last=drop_last, augment=augment, positive_fraction=positive_fraction)
+        `positive_fraction=f` fixes the share of wake-word items of every epoch, as in dataset.loader.  `crop="active"` draws the
+        window of a clip entry longer than the clip around its active region (draw_starts), instead of uniformly."""
+        return BankLoader(self, batch_size, shuffle=shuffle, drop_last=drop_last, augment=augment, positive_fraction=positive_fraction,
+                          crop=crop)
 
 
 class BankLoader:
     """One epoch = the bank's items (ClipBank.item_entries), in order or in a fresh `torch.randperm` per epoch.  Per batch, in this order:
-    the starts of its items in batch order (python `random`), the gather, `processor.augment_batch` when augmenting (which draws its
+    the starts of its items in batch order (python `random`; `crop="active"` changes their range, not their number), the gather, `processor.augment_batch` when augmenting (which draws its
     plans), `processor.mel_batch(pcm, normalize=False)`, `processor.spec_augment_batch(data, inplace=True)` when augmenting with
     `processor.set_spec_augment` on (which draws its seed), rows of placeholders set to 0.0 -- the draw order of the file loader, so a
     seeded epoch over the same files yields the same batches bit for bit."""
 
-    def __init__(self, bank, batch_size=16, shuffle=False, drop_last=False, augment=False, positive_fraction=None):
+    def __init__(self, bank, batch_size=16, shuffle=False, drop_last=False, augment=False, positive_fraction=None, crop=None):
         if batch_size < 1:
             raise ValueError("batch_size must be positive")
+        self.crop = check_crop(crop)
         self.positive_fraction = check_positive_fraction(positive_fraction, bool(shuffle))
         if augment:
             bank.processor._check_augment()
@@ -396,7 +452,7 @@ class BankLoader:
         window = np.where(bank.kinds == STREAM, nat.BANK_NORM_WINDOW, nat.BANK_NORM_ENTRY).astype(np.int32)
         for s in range(0, idx.size, self.batch_size):
             entries = item_entries[idx[s:s + self.batch_size]]
-            starts = bank.draw_starts(entries)
+            starts = bank.draw_starts(entries) if self.crop is None else bank.draw_starts(entries, self.crop)
             pcm = bank._gather(entries, starts, window[entries])
             if self.augment:
                 pcm = proc.augment_batch(pcm)
