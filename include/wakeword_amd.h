@@ -15,6 +15,8 @@
  *     therefore capturable into a hipGraph once ww_init() has run on the device (exception, stated
  *     at the function: ww_augment_f32 / ww_augment_n_f32 read their plans from host memory and are not capturable; the two-call
  *     forms ww_augment_plans_prepare(_n) + ww_augment_records(_n)_f32 are).
+ *   - a `workspace_dev` / `scratch_dev` buffer is the caller's, of at least the size its query returns; the library writes nothing past
+ *     that size.  Unless a function says otherwise (state that must be zeroed or initialised first) its content on entry is unspecified.
  *   - return value: WW_OK (0) or a negative WW_E* code; ww_last_error() gives the message of the
  *     calling thread's most recent failure.  Nothing falls back to a CPU path: without a usable
  *     gfx950 device every launch function fails with WW_ENODEVICE.
@@ -248,7 +250,7 @@ WW_API int64_t ww_augment_workspace_bytes(int64_t n_clips);
 /* pcm_dev [n_clips] rows of 16000 samples at pcm_dev + i*clip_stride (16-byte aligned, clip_stride % 4 == 0);
  * plans_host [n_clips] in HOST memory: read before the call returns (staged through pinned memory owned by the library, so
  * the call is asynchronous on `stream`; it is not graph-capturable); out_dev [n_clips][16000], may alias pcm_dev;
- * workspace_dev >= ww_augment_workspace_bytes(n_clips), 256-byte aligned. */
+ * workspace_dev >= ww_augment_workspace_bytes(n_clips), 256-byte aligned. Its content on entry is unspecified and no result depends on it. */
 WW_API int ww_augment_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, const ww_augment_plan* plans_host,
                    float* out_dev, void* workspace_dev, ww_stream_t stream);
 /* The same in two halves, for hipGraph capture: ww_augment_plans_prepare turns the plans into the fixed-size records the kernels read
@@ -303,7 +305,7 @@ typedef struct ww_augment_bg {
     int32_t enabled;      /* 0 = no background for this clip */
 } ww_augment_bg;
 /* ww_augment_n_f32 with background, at N = 16000 or WW_MIN_CLIP_SAMPLES..WW_AUG_MAX_SAMPLES (rows and strides as there); bg_host [n_clips]
- * in host memory; workspace_dev >= ww_augment_bg_workspace_bytes(n_clips, N).  With every enabled = 0 the results equal
+ * in host memory; workspace_dev >= ww_augment_bg_workspace_bytes(n_clips, N). Its content on entry is unspecified and no result depends on it.  With every enabled = 0 the results equal
  * ww_augment_n_f32's (and at N = 16000 ww_augment_f32's) bit for bit. */
 WW_API int64_t ww_augment_bg_workspace_bytes(int64_t n_clips, int64_t n_samples);
 WW_API int ww_augment_bg_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
@@ -321,7 +323,7 @@ WW_API int ww_augment_bg_records_f32(const float* pcm_dev, int64_t n_clips, int6
                                      ww_stream_t stream);
 /* The mix alone (no other transform, no Gaussian noise), e.g. for noisy evaluation sets at a fixed SNR: clips of N = WW_MIN_CLIP_SAMPLES ..
  * WW_MAX_CLIP_SAMPLES samples, rows at pcm_dev + i*clip_stride and out_dev + i*out_stride (4-byte aligned, strides >= N; out may alias
- * pcm row for row); workspace_dev >= ww_mix_background_workspace_bytes(n_clips), 256-byte aligned. */
+ * pcm row for row); workspace_dev >= ww_mix_background_workspace_bytes(n_clips), 256-byte aligned. Its content on entry is unspecified and no result depends on it. */
 WW_API int64_t ww_mix_background_workspace_bytes(int64_t n_clips);
 WW_API int ww_mix_background_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_bg* bg_host,
                                  const float* bank_dev, int64_t bank_len, float* out_dev, int64_t out_stride, void* workspace_dev,
@@ -344,12 +346,12 @@ typedef struct ww_augment_rir {
     int32_t reserved;     /* 0 */
 } ww_augment_rir;
 /* Bank build: spectra_dev [n_rirs][WW_RIR_SPECTRUM_BINS][2] from the taps of RIR r at taps_dev + offsets_host[r], lengths_host[r] of them
- * (1 .. WW_RIR_MAX_TAPS, inside taps_len); workspace_dev >= ww_rir_spectra_workspace_bytes(n_rirs), 256-byte aligned. */
+ * (1 .. WW_RIR_MAX_TAPS, inside taps_len); workspace_dev >= ww_rir_spectra_workspace_bytes(n_rirs), 256-byte aligned. Its content on entry is unspecified and no result depends on it. */
 WW_API int64_t ww_rir_spectra_workspace_bytes(int64_t n_rirs);
 WW_API int ww_rir_spectra_f32(const float* taps_dev, int64_t taps_len, const int64_t* offsets_host, const int32_t* lengths_host, int64_t n_rirs,
                               float* spectra_dev, void* workspace_dev, ww_stream_t stream);
 /* ww_augment_bg_f32 with reverb (bg_host may be NULL: no background); spectra_dev holds n_rirs spectra; workspace_dev >=
- * ww_augment_rir_workspace_bytes(n_clips, N).  With every rir enabled = 0 the results equal ww_augment_bg_f32's (bg_host NULL:
+ * ww_augment_rir_workspace_bytes(n_clips, N). Its content on entry is unspecified and no result depends on it.  With every rir enabled = 0 the results equal ww_augment_bg_f32's (bg_host NULL:
  * ww_augment_n_f32's) bit for bit. */
 WW_API int64_t ww_augment_rir_workspace_bytes(int64_t n_clips, int64_t n_samples);
 WW_API int ww_augment_rir_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
@@ -368,7 +370,7 @@ WW_API int ww_augment_rir_records_f32(const float* pcm_dev, int64_t n_clips, int
                                       int64_t out_stride, void* workspace_dev, ww_stream_t stream);
 /* The reverb alone (no other transform), e.g. for reverberant evaluation sets: clips of N = WW_MIN_CLIP_SAMPLES .. WW_MAX_CLIP_SAMPLES
  * samples, rows at pcm_dev + i*clip_stride and out_dev + i*out_stride (4-byte aligned, strides >= N; out may alias pcm row for row);
- * workspace_dev >= ww_reverb_workspace_bytes(n_clips), 256-byte aligned. */
+ * workspace_dev >= ww_reverb_workspace_bytes(n_clips), 256-byte aligned. Its content on entry is unspecified and no result depends on it. */
 WW_API int64_t ww_reverb_workspace_bytes(int64_t n_clips);
 WW_API int ww_reverb_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_rir* rir_host,
                          const float* spectra_dev, int64_t n_rirs, float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream);
@@ -465,7 +467,7 @@ WW_API int ww_pack_weights_host(const ww_state_dict* sd, float* packed_host);
  * (train_wakeword.py:39-41 / wakeword_training_script.py:170-173).
  *   mel_dev    [n][80][width]   (the [B,1,80,T] model input), 1 <= width <= 32
  *   pooled_dev [n][C_last]      C_last = 64 (n_conv 2) or 128 (n_conv 3)
- *   scratch_dev  n_conv 3 only: ww_cnn_scratch_bytes(n, 3) bytes; may be NULL for n_conv 2 */
+ *   scratch_dev  n_conv 3 only: ww_cnn_scratch_bytes(n, 3) bytes; may be NULL for n_conv 2. Its content on entry is unspecified and no result depends on it. */
 WW_API int64_t ww_cnn_scratch_bytes(int64_t n, int32_t n_conv);
 WW_API int ww_cnn_pool_f32(const float* mel_dev, int64_t n, int32_t width, const float* packed_dev,
                     int32_t n_conv, void* scratch_dev, float* pooled_dev, ww_stream_t stream);
@@ -476,7 +478,7 @@ WW_API int ww_cnn_pool_f32(const float* mel_dev, int64_t n, int32_t width, const
  * second kernel sums a clip's tiles in a fixed order (results do not depend on the batch).  Arithmetic: ww_set_conv_math (WW_CONV_MATH_F32
  * or WW_CONV_MATH_F16X3, whose range exponents are then chosen per tile); WW_CONV_MATH_F16X3_DIRECT has no tiled form: widths > 32 return
  * WW_EUNSUPPORTED under it.
- * scratch_dev: ww_cnn_wide_scratch_bytes(n, width, n_conv) bytes, 256-byte aligned (may be NULL only where ww_cnn_pool_f32 allows it). */
+ * scratch_dev: ww_cnn_wide_scratch_bytes(n, width, n_conv) bytes, 256-byte aligned (may be NULL only where ww_cnn_pool_f32 allows it). Its content on entry is unspecified and no result depends on it. */
 WW_API int64_t ww_cnn_wide_scratch_bytes(int64_t n, int32_t width, int32_t n_conv);
 WW_API int ww_cnn_pool_wide_f32(const float* mel_dev, int64_t n, int32_t width, const float* packed_dev, int32_t n_conv,
                                 void* scratch_dev, float* pooled_dev, ww_stream_t stream);
@@ -490,18 +492,19 @@ WW_API int ww_lstm_fc_f32(const float* pooled_dev, int64_t n, const float* packe
 
 /* ---- composed entry points ----------------------------------------------------------------- */
 /* model.forward(x): SimpleWakewordModel.forward train_wakeword.py:38-49 /
- * WakewordModel.forward wakeword_training_script.py:167-184.  workspace >= ww_workspace_bytes. */
+ * WakewordModel.forward wakeword_training_script.py:167-184.  workspace >= ww_workspace_bytes. Its content on entry is unspecified and no result depends on it. */
 WW_API int64_t ww_workspace_bytes(int64_t n, int32_t n_conv);
 WW_API int ww_model_forward_f32(const float* mel_dev, int64_t n, int32_t width, const float* packed_dev,
                          int32_t n_conv, void* workspace_dev, float* logits_dev, ww_stream_t stream);
 /* PCM -> logits: the eval loop body of wakeword_training.ipynb cell 17 / validate()
- * wakeword_training_script.py:269-289 with the Dataset's mel path folded in (K1 -> K2 -> K3). */
+ * wakeword_training_script.py:269-289 with the Dataset's mel path folded in (K1 -> K2 -> K3).  workspace_dev as for
+ * ww_model_forward_f32. Its content on entry is unspecified and no result depends on it. */
 WW_API int ww_forward_pcm_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len,
                        int normalize, const float* packed_dev, int32_t n_conv, void* workspace_dev,
                        float* logits_dev, ww_stream_t stream);
 
 /* PCM -> logits for any clip length: ww_logmel_frames_f32 -> ww_cnn_pool_wide_f32 -> ww_lstm_fc_f32 (arguments as there);
- * workspace_dev: ww_workspace_frames_bytes(n_clips, n_samples, n_conv) bytes, 256-byte aligned. */
+ * workspace_dev: ww_workspace_frames_bytes(n_clips, n_samples, n_conv) bytes, 256-byte aligned. Its content on entry is unspecified and no result depends on it. */
 WW_API int64_t ww_workspace_frames_bytes(int64_t n, int64_t n_samples, int32_t n_conv);
 WW_API int ww_forward_pcm_frames_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples,
                                      int normalize, const float* packed_dev, int32_t n_conv, void* workspace_dev, float* logits_dev,
@@ -513,7 +516,7 @@ WW_API int ww_forward_pcm_frames_f32(const float* pcm_dev, int64_t n_clips, int6
  * Rows may overlap: 4 <= hop <= n_samples, hop % 4 == 0, signal_dev 16-byte aligned, and the caller's buffer holds
  * (n_windows - 1) * hop + n_samples samples.  Nothing on the way writes the signal.  Bit for bit ww_forward_pcm_f32 (N = 16000) /
  * ww_forward_pcm_frames_f32 (other N) of the same windows copied out as rows.  workspace_dev: ww_forward_windows_workspace_bytes()
- * bytes, 256-byte aligned; workspace_bytes is its size. */
+ * bytes, 256-byte aligned; workspace_bytes is its size. Its content on entry is unspecified and no result depends on it. */
 WW_API int64_t ww_forward_windows_workspace_bytes(int64_t n_windows, int64_t n_samples, int32_t n_conv);
 WW_API int ww_forward_windows_f32(const float* signal_dev, int64_t n_windows, int64_t hop, int64_t n_samples, int normalize,
                                   const float* packed_dev, int32_t n_conv, void* workspace_dev, int64_t workspace_bytes, float* logits_dev,
@@ -524,7 +527,7 @@ WW_API int ww_forward_windows_f32(const float* signal_dev, int64_t n_windows, in
  * min(k, smooth) q values summed in ascending order (1 <= smooth <= 256); window k fires iff s_k >= (double)theta and no window of the
  * segment fired in the refractory windows before it (0 <= refractory <= 2^30).  counts_dev [n_segs][n_thr] int64; fired_dev (may be
  * NULL; only with n_thr == 1) [n_windows] uint8 0/1.  thresholds_dev [n_thr] float32, 1 <= n_thr <= 65536.
- * workspace_dev: ww_events_workspace_bytes(n_windows) bytes, 16-byte aligned. */
+ * workspace_dev: ww_events_workspace_bytes(n_windows) bytes, 16-byte aligned. Its content on entry is unspecified and no result depends on it. */
 WW_API int64_t ww_events_workspace_bytes(int64_t n_windows);
 WW_API int ww_events_sweep_f32(const float* prob_dev, const int64_t* seg_offsets_dev, int64_t n_segs, int64_t n_windows, int32_t smooth,
                                int64_t refractory, const float* thresholds_dev, int32_t n_thr, int64_t* counts_dev, uint8_t* fired_dev,
@@ -556,7 +559,7 @@ WW_API int ww_bank_peaks_f32(const float* audio_dev, int64_t total_samples, cons
  * [n_items] in host memory, checked before any HIP call (WW_EINVAL naming the field): N in WW_MIN_CLIP_SAMPLES..WW_MAX_CLIP_SAMPLES,
  * out_stride >= N, offset >= 0, length >= 0, offset + length <= total_samples, -N <= start <= length, a known norm, peak not negative,
  * 0 <= row < n_rows and no row named twice.  The items are staged through the library's pinned memory into workspace_dev
- * (>= ww_bank_gather_workspace_bytes(n_items), 256-byte aligned); the call is asynchronous on `stream` and cannot be captured into a
+ * (>= ww_bank_gather_workspace_bytes(n_items), 256-byte aligned; its content on entry is unspecified and no result depends on it); the call is asynchronous on `stream` and cannot be captured into a
  * graph.  audio_dev / out_dev 4-byte aligned; entries and windows may start at any sample, and total_samples may exceed 2^31. */
 #define WW_BANK_NORM_NONE 0
 #define WW_BANK_NORM_ENTRY 1
@@ -609,7 +612,7 @@ WW_API int ww_bank_gather_f32(const float* audio_dev, int64_t total_samples, con
  * offsets_dev [n_entries + 1] int64 in device memory and offsets_host the same values in host memory (the hop table is built from
  * them): non-decreasing, offsets[0] >= 0, offsets[n_entries] <= total_samples; nothing outside an entry is read, and nothing at or
  * past total_samples whatever the device table says.  stats_dev [n_entries] (8-byte aligned), every record written.  workspace_dev:
- * >= ww_bank_audit_workspace_bytes(total_samples, n_entries) bytes, 256-byte aligned.  The hop table is staged through the library's
+ * >= ww_bank_audit_workspace_bytes(total_samples, n_entries) bytes, 256-byte aligned. Its content on entry is unspecified and no result depends on it.  The hop table is staged through the library's
  * pinned memory; the call is asynchronous on `stream` and cannot be captured into a graph.  Checked before any HIP call (WW_EINVAL):
  * total_samples < 0, n_entries outside 0 .. 2^30, clip_level <= 0 or NaN, ratio outside (0, 1], the offsets as above, a null or
  * misaligned pointer.  n_entries == 0 is WW_OK without a launch. */
@@ -669,7 +672,8 @@ typedef struct ww_train_grads {  /* outputs, overwritten (not accumulated) */
 #define WW_TRAIN_MATH_DEFAULT (-1)
 WW_API int64_t ww_train_workspace_bytes(int64_t n, int32_t n_conv, int32_t train_math);
 /* mel_dev [n][80][width]; p_lstm / p_fc: drop probabilities (0 = eval-mode arithmetic); workspace_dev: workspace_bytes >=
- * ww_train_workspace_bytes bytes, 256-byte aligned, must stay untouched until the matching ww_train_backward_f32 has run; logits_dev [n][2]. */
+ * ww_train_workspace_bytes bytes, 256-byte aligned, must stay untouched until the matching ww_train_backward_f32 has run; logits_dev [n][2].
+ * The workspace's content on entry to the forward is unspecified and no result depends on it. */
 WW_API int ww_train_forward_f32(const float* mel_dev, int64_t n, int32_t width, const ww_train_params* params, float p_lstm,
                                 float p_fc, uint64_t seed, int32_t train_math, void* workspace_dev, int64_t workspace_bytes,
                                 float* logits_dev, ww_stream_t stream);
@@ -802,7 +806,7 @@ WW_API int ww_adam_step_f32(const ww_adam_tensor* tensors_host, int64_t n_tensor
 /* ww_grad_norm_f32: *norm_dev = the L2 norm over every g of the table (an entry counts once per entry, as clip_grad_norm_ counts a
  * gradient once per parameter), float64 partial sums over 4096 elements each in a fixed order in element coordinates, added by a second
  * kernel; *scale_dev = min(1, max_norm / (norm + 1e-6)), clip_grad_norm_'s coefficient.  Only g and n of the entries are read.
- * workspace_dev: >= ww_grad_norm_workspace_bytes(...) bytes, 256-byte aligned.  max_norm > 0 (infinity: the norm alone). */
+ * workspace_dev: >= ww_grad_norm_workspace_bytes(...) bytes, 256-byte aligned. Its content on entry is unspecified and no result depends on it.  max_norm > 0 (infinity: the norm alone). */
 WW_API int64_t ww_grad_norm_workspace_bytes(const ww_adam_tensor* tensors_host, int64_t n_tensors);
 WW_API int ww_grad_norm_f32(const ww_adam_tensor* tensors_host, int64_t n_tensors, double max_norm, double* norm_dev, float* scale_dev,
                             void* workspace_dev, ww_stream_t stream);
