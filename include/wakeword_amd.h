@@ -861,6 +861,71 @@ WW_API int ww_clip_metrics_reset(ww_clip_metrics* state_dev, ww_stream_t stream)
 WW_API int ww_clip_metrics_update_f32(const float* logits_dev, const int64_t* labels_dev, int64_t n, ww_clip_metrics* state_dev,
                                       ww_stream_t stream);
 
+/* ---- clip ledger: a per-clip training record as device integers ---------------------------------------- */
+/* Which clips does the model never learn, which does it keep forgetting, which labels are probably wrong?  All of it follows from the
+ * margin of the ASSIGNED class at every visit of a clip: its mean over training (the area under the margin; negative for likely label
+ * errors), its spread, and the epochs in which the clip was classified wrongly.  A ledger keeps that per bank entry in device memory:
+ * one launch per batch scatters the batch's rows into it in stream order, nothing waits for the device, and it is read once.
+ *
+ * A ledger is ONE device buffer: a ww_ledger_header followed by n_entries ww_ledger_entry records, ww_clip_ledger_bytes(n_entries)
+ * = 64 + 56 n_entries bytes, 8-byte aligned.
+ *
+ * Per row i of a call, with z = logits [2] float32, y = label int64 and e = entry int64:
+ *   always                  rows += 1
+ *   e < 0                   skipped += 1 and nothing else: a caller marks placeholder rows this way.
+ *   e >= n_entries          bad_entries += 1 and NO write to any record.  Compared as int64 against the n_entries ARGUMENT (the kernel
+ *                           never reads a device value to decide where it may write): e = 2^32 + 1 is out of range, not entry 1.
+ *   y outside {0, 1}        bad_labels += 1 and nothing else.
+ * otherwise, on record e:
+ *   d = z1 - z0             ONE float32 subtraction; pred = 1 iff z1 > z0 (a tie or a NaN gives 0: ww_ce_loss_f32's rule); m = y ? d : -d,
+ *                           the margin of the assigned class.
+ *   seen += 1; correct += (pred == y)
+ *   epoch >= 0              seen_epochs |= 1 << epoch, and when pred != y also wrong_epochs |= 1 << epoch (64-bit shifts)
+ *   m NaN or +-inf          the record's nonfinite += 1 and the header's nonfinite += 1; none of the margin fields below
+ *   m finite                Q = (int32)rintf(fminf(fmaxf(m, -64.f), 64.f) * 65536.f): the margin in units of 2^-16, clamped to +-64.  The
+ *                           multiply is exact and rintf rounds half to even, so float32 arithmetic anywhere reproduces Q bit for bit.
+ *                           sum_q += Q; sum_q2 += (uint64)((int64)Q * Q); min_q = min(min_q, Q); max_q = max(max_q, Q)
+ * The header's updates += 1 once per call with n > 0.
+ *
+ * One lane per row, workgroups of 256, ceil(n / 256) workgroups.  A batch may name an entry more than once and its rows are spread over
+ * workgroups, so the records are updated with INTEGER global atomics at device scope (add, min, max, or): each is commutative and
+ * associative, so the ledger after a set of rows does not depend on row order, batch split, launch geometry or run.  No float atomics,
+ * no compare-and-swap loops.  The header counters are counted per wave with ballots: one atomic per wave and counter.  Calls on one
+ * stream serialise; nothing is promised for two streams that share a ledger.
+ *
+ * ww_clip_ledger_init writes the header and clears every record (min_q = INT32_MAX, max_q = INT32_MIN, the rest 0); it does not depend on
+ * what the buffer held.  ww_clip_ledger_update_f32 is a pure launch: no allocation, no copy, no synchronise, capturable; n == 0 returns
+ * WW_OK without a launch.  logits_dev [n][2] float32, labels_dev [n] and entries_dev [n] int64; epoch in 0..63, or -1 for "no epoch bit".
+ * Checked before any HIP call (WW_EINVAL naming the field): null pointers; logits_dev, labels_dev, entries_dev or ledger_dev not 8-byte
+ * aligned; n outside 0..2^30; n_entries outside 0..2^28; epoch outside -1..63.  ww_clip_ledger_bytes returns WW_EINVAL for n_entries
+ * outside 0..2^28. */
+typedef struct ww_ledger_header {
+    int64_t n_entries;      /* as given to ww_clip_ledger_init; for the reader, never read by a kernel */
+    int64_t updates;        /* calls with n > 0 */
+    int64_t rows;           /* rows seen, whatever became of them */
+    int64_t skipped;        /* rows with e < 0 */
+    int64_t bad_entries;    /* rows with e >= n_entries */
+    int64_t bad_labels;     /* rows of a valid entry with a label outside {0, 1} */
+    int64_t nonfinite;      /* scored rows whose margin is NaN or +-inf */
+    int64_t reserved;
+} ww_ledger_header;         /* 64 bytes, DEVICE memory */
+typedef struct ww_ledger_entry {
+    int64_t sum_q;          /* sum of Q over the finite visits */
+    uint64_t sum_q2;        /* sum of Q * Q */
+    uint64_t seen_epochs;   /* bit k: visited in epoch k */
+    uint64_t wrong_epochs;  /* bit k: classified wrongly at some visit of epoch k */
+    int32_t seen;           /* visits, non-finite ones included */
+    int32_t correct;        /* visits with pred == y */
+    int32_t nonfinite;      /* visits with a non-finite margin */
+    int32_t min_q;          /* INT32_MAX until a finite visit */
+    int32_t max_q;          /* INT32_MIN until a finite visit */
+    int32_t reserved;
+} ww_ledger_entry;          /* 56 bytes, DEVICE memory */
+WW_API int64_t ww_clip_ledger_bytes(int64_t n_entries);
+WW_API int ww_clip_ledger_init(void* ledger_dev, int64_t n_entries, ww_stream_t stream);
+WW_API int ww_clip_ledger_update_f32(const float* logits_dev, const int64_t* labels_dev, const int64_t* entries_dev, int64_t n, int32_t epoch,
+                                     void* ledger_dev, int64_t n_entries, ww_stream_t stream);
+
 /* ---- streaming: sliding window of 0.25 .. 1 s, one hop per step, many microphones ------------- */
 /* Semantics per window = predict_wakeword (wakeword_training.ipynb cell 19): normalise the last
  * N samples, log-mel, forward, softmax, p[wakeword].  The reference has no streaming code;

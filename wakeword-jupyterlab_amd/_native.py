@@ -149,6 +149,21 @@ class ClipMetrics(C.Structure):
                 ("nonfinite", C.c_int64), ("at", C.c_int64 * 2 * 2 * METRICS_MAX_THRESHOLDS), ("hist", C.c_int64 * METRICS_BINS * 2),
                 ("margin", C.c_float * METRICS_MAX_THRESHOLDS), ("n_thresholds", C.c_int32), ("reserved", C.c_int32)]
 
+
+class LedgerHeader(C.Structure):
+    """struct ww_ledger_header (include/wakeword_amd.h): the counters in front of a clip ledger's records, DEVICE memory."""
+    _fields_ = [(k, C.c_int64) for k in ("n_entries", "updates", "rows", "skipped", "bad_entries", "bad_labels", "nonfinite", "reserved")]
+
+
+class LedgerEntry(C.Structure):
+    """struct ww_ledger_entry (include/wakeword_amd.h): one bank entry's record of a clip ledger, DEVICE memory."""
+    _fields_ = [("sum_q", C.c_int64), ("sum_q2", C.c_uint64), ("seen_epochs", C.c_uint64), ("wrong_epochs", C.c_uint64),
+                ("seen", C.c_int32), ("correct", C.c_int32), ("nonfinite", C.c_int32), ("min_q", C.c_int32), ("max_q", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+LEDGER_MAX_ENTRIES, LEDGER_MAX_EPOCHS = 1 << 28, 64
+
 RIR_MAX_TAPS, RIR_FFT_SIZE, RIR_SPECTRUM_BINS = 16384, 32768, 16385
 
 
@@ -274,6 +289,9 @@ PROTOTYPES = {
     "ww_clip_metrics_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "ww_clip_metrics_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ww_clip_metrics_update_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ww_clip_ledger_bytes": (C.c_int64, [C.c_int64]),
+    "ww_clip_ledger_init": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "ww_clip_ledger_update_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "ww_train_masks": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_train_packed_image": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "ww_train_bit_images": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

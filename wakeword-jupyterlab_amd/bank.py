@@ -406,13 +406,38 @@ class ClipBank:
                                                      out.stride(0), _ptr(ws), stream))
         return out
 
-    def loader(self, batch_size=16, shuffle=False, drop_last=False, augment=False, positive_fraction=None, crop=None):
+    def loader(self, batch_size=16, shuffle=False, drop_last=False, augment=False, positive_fraction=None, crop=None, entries=None):
         """What `dataset.loader(batch_size, shuffle, drop_last)` is, fed from device memory: re-iterable, with len() and order(),
         yielding `(data [B,1,80,T], target [B,1])` on the device.  `augment=True` runs processor.augment_batch on every batch;
         `positive_fraction=f` fixes the share of wake-word items of every epoch, as in dataset.loader.  `crop="active"` draws the
-        window of a clip entry longer than the clip around its active region (draw_starts), instead of uniformly."""
+        window of a clip entry longer than the clip around its active region (draw_starts), instead of uniformly.  `entries`: a
+        boolean mask [n_entries] or a strictly increasing list of entry indices restricts the epoch to the items of those entries, in
+        the same relative order -- len(), order(), positive_fraction and drop_last act on the subset; what a bank built from those
+        entries alone would yield, bit for bit.  With the writable `labels` this is how what a ledger.ClipLedger found is dropped or
+        relabelled without rebuilding the bank.  After every batch `loader.last_entries` names the bank entry of each row."""
         return BankLoader(self, batch_size, shuffle=shuffle, drop_last=drop_last, augment=augment, positive_fraction=positive_fraction,
-                          crop=crop)
+                          crop=crop, entries=entries)
+
+    def select_entries(self, entries) -> np.ndarray:
+        """A boolean mask [n_entries] or a strictly increasing list of entry indices -> the indices (int64, ascending).  ValueError for a
+        mask of another length, an index outside the bank, an order that is not strictly increasing or an empty selection."""
+        sel = np.asarray(entries)
+        if sel.ndim != 1:
+            raise ValueError("entries: expected a boolean mask [n_entries] or a 1-D list of entry indices")
+        if sel.dtype == bool:
+            if sel.size != self.n_entries:
+                raise ValueError(f"entries: a mask of {sel.size} values for a bank of {self.n_entries} entries")
+            sel = np.flatnonzero(sel)
+        elif sel.size and sel.dtype.kind not in "iu":
+            raise ValueError("entries: expected a boolean mask [n_entries] or a 1-D list of entry indices")
+        sel = sel.astype(np.int64)
+        if sel.size == 0:
+            raise ValueError("entries: the selection is empty")
+        if sel.min() < 0 or sel.max() >= self.n_entries:
+            raise ValueError(f"entries: an index lies outside [0, {self.n_entries})")
+        if (np.diff(sel) <= 0).any():
+            raise ValueError("entries: the indices must be strictly increasing")
+        return sel
 
 
 class BankLoader:
@@ -420,9 +445,11 @@ class BankLoader:
     the starts of its items in batch order (python `random`; `crop="active"` changes their range, not their number), the gather, `processor.augment_batch` when augmenting (which draws its
     plans), `processor.mel_batch(pcm, normalize=False)`, `processor.spec_augment_batch(data, inplace=True)` when augmenting with
     `processor.set_spec_augment` on (which draws its seed), rows of placeholders set to 0.0 -- the draw order of the file loader, so a
-    seeded epoch over the same files yields the same batches bit for bit."""
+    seeded epoch over the same files yields the same batches bit for bit.  `entries` (ClipBank.select_entries) keeps only the items of
+    those entries.  `last_entries`: the bank entry of every row of the newest batch (host int64; -1 for a placeholder row, served as
+    zeros), set before the batch is yielded -- what a ledger.ClipLedger scatters by; nothing on the device is spent on it."""
 
-    def __init__(self, bank, batch_size=16, shuffle=False, drop_last=False, augment=False, positive_fraction=None, crop=None):
+    def __init__(self, bank, batch_size=16, shuffle=False, drop_last=False, augment=False, positive_fraction=None, crop=None, entries=None):
         if batch_size < 1:
             raise ValueError("batch_size must be positive")
         self.crop = check_crop(crop)
@@ -430,24 +457,31 @@ class BankLoader:
         if augment:
             bank.processor._check_augment()
         self.bank, self.batch_size, self.shuffle, self.drop_last, self.augment = bank, int(batch_size), bool(shuffle), bool(drop_last), bool(augment)
+        self.entries = None if entries is None else bank.select_entries(entries)
+        self.last_entries = None
+
+    def item_entries(self) -> np.ndarray:
+        """The entry of every item of this loader's epoch: the bank's, restricted to `entries`."""
+        items = self.bank.item_entries()
+        return items if self.entries is None else items[np.isin(items, self.entries)]
 
     def __len__(self):
-        n = self.bank.n_items
+        n = self.bank.n_items if self.entries is None else int(self.item_entries().size)
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
     def order(self):
         """Item order of one epoch (a fresh permutation from torch's default generator when shuffling; with positive_fraction the
         class-balanced draw of sampling.balanced_order over the items' labels)."""
-        n = self.bank.n_items
+        n = self.bank.n_items if self.entries is None else int(self.item_entries().size)
         if self.positive_fraction is not None:
-            idx = balanced_order(self.bank.labels[self.bank.item_entries()], self.positive_fraction).tolist()
+            idx = balanced_order(self.bank.labels[self.item_entries()], self.positive_fraction).tolist()
         else:
             idx = torch.randperm(n).tolist() if self.shuffle else list(range(n))
         return idx[: len(self) * self.batch_size] if self.drop_last else idx
 
     def __iter__(self):
         bank, proc = self.bank, self.bank.processor
-        item_entries = bank.item_entries()
+        item_entries = self.item_entries()
         idx = np.asarray(self.order(), dtype=np.int64)
         window = np.where(bank.kinds == STREAM, nat.BANK_NORM_WINDOW, nat.BANK_NORM_ENTRY).astype(np.int32)
         for s in range(0, idx.size, self.batch_size):
@@ -463,4 +497,5 @@ class BankLoader:
             if bad.any():
                 data[torch.from_numpy(bad).to(data.device)] = 0.0
             target = torch.from_numpy(bank.labels[entries]).to(data.device).unsqueeze(1)
+            self.last_entries = np.where(bad, -1, entries).astype(np.int64)
             yield data, target

@@ -68,7 +68,9 @@ class WakewordDataset(Dataset):
         repeats it), yielding `(data [B,1,80,T], target [B,1])` on the GPU (T = 32 at 1 s).  Files are read by the library's reader threads into
         pinned staging, decoded (K0), augmented when the dataset says so (KA) and turned into log-mel (K1) one batch at a time.
         `positive_fraction=f` in (0, 1), with shuffle=True: every epoch keeps its length and holds that share of wake-word items
-        (sampling.balanced_order); None, the default, leaves the order as it was."""
+        (sampling.balanced_order); None, the default, leaves the order as it was.
+        After every batch `loader.last_entries` holds each row's index into `files` (host int64, -1 for an unreadable file): what a
+        ledger.ClipLedger scatters by."""
         return GpuBatchLoader(self, batch_size, shuffle=shuffle, drop_last=drop_last, positive_fraction=positive_fraction)
 
     def cache(self):
@@ -85,6 +87,7 @@ class GpuBatchLoader:
         self.dataset, self.batch_size, self.shuffle, self.drop_last = dataset, int(batch_size), bool(shuffle), bool(drop_last)
         self.positive_fraction = check_positive_fraction(positive_fraction, self.shuffle)
         self._encoded = None
+        self.last_entries = None          # per row of the newest batch: its index into dataset.files (host int64; -1 where unreadable)
 
     def __len__(self):
         n = len(self.dataset)
@@ -149,6 +152,7 @@ class GpuBatchLoader:
                       f"({ds.unreadable} so far), e.g. {files[s + int(np.argmin(ok))]}")
                 data[torch.from_numpy(~ok).to(dev)] = 0.0
             target = torch.tensor(labels[s:e], dtype=torch.long, device=dev).unsqueeze(1)
+            self.last_entries = np.where(np.asarray(ok, bool), np.asarray(idx[s:e], np.int64), -1).astype(np.int64)
             yield data, target
 
 

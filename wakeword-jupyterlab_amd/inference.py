@@ -75,11 +75,14 @@ def _report_labels(target, n: int, device) -> torch.Tensor:
     return target
 
 
-def evaluate_report(model, loader, device=None, thresholds=(0.8,)):
+def evaluate_report(model, loader, device=None, thresholds=(0.8,), ledger=None):
     """Notebook cell 17's loop without its per-batch copies: every batch's logits and labels go into a ww_clip_metrics record on the
     device (one launch, in stream order) and the record is read once, after the last batch.  Returns a metrics.ClipReport: `.confusion`,
     `.classification_report()`, `.summary()` are cell 17's numbers; `.at(p)` for each p of `thresholds`, `.roc()`, `.auc`, `.eer` and
-    `.threshold_for(max_fpr)` answer the deployment question.  `loader` yields (data [B,1,80,T], target [B,1] or [B])."""
+    `.threshold_for(max_fpr)` answer the deployment question.  `loader` yields (data [B,1,80,T], target [B,1] or [B]).  `ledger` (a
+    ledger.ClipLedger): the same pass also scatters every row into it by the loader's `last_entries` (bank.loader, dataset.loader), under
+    the ledger's current epoch -- on a fresh ledger no epoch bit is set, and `ledger.read().misclassified()` names the clips behind the
+    confusion matrix."""
     from . import ops
     model.eval()
     device = torch.device(device) if device is not None else next(model.parameters()).device
@@ -87,7 +90,13 @@ def evaluate_report(model, loader, device=None, thresholds=(0.8,)):
     with torch.no_grad():
         for data, target in loader:
             output = model(data.to(device))
-            ops.clip_metrics_update(output, _report_labels(target, output.shape[0], device), state)
+            labels = _report_labels(target, output.shape[0], device)
+            ops.clip_metrics_update(output, labels, state)
+            if ledger is not None:
+                entries = getattr(loader, "last_entries", None)
+                if entries is None:
+                    raise TypeError(f"evaluate_report(ledger=): {type(loader).__name__} has no `last_entries` to name its rows by")
+                ledger.update(entries, output, labels)
     return ops.read_clip_metrics(state)
 
 

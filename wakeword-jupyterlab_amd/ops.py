@@ -981,6 +981,83 @@ def read_clip_metrics(state: ClipMetricsState):
     return report
 
 
+# ---- clip ledger: a per-clip training record as device integers (csrc/ww_ledger.hip) ----------------------
+class ClipLedgerState:
+    """A clip ledger in device memory: `buffer` (int64 words: a ww_ledger_header, then `n_entries` ww_ledger_entry records)."""
+    __slots__ = ("buffer", "n_entries")
+
+    def __init__(self, buffer, n_entries):
+        self.buffer, self.n_entries = buffer, n_entries
+
+    @property
+    def device(self):
+        return self.buffer.device
+
+
+def new_clip_ledger(device, n_entries) -> ClipLedgerState:
+    """A cleared ledger of `n_entries` records (0..2^28) on `device`."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"clip ledger on {device}: this path has no CPU implementation")
+    if isinstance(n_entries, bool) or int(n_entries) != n_entries or not 0 <= int(n_entries) <= nat.LEDGER_MAX_ENTRIES:
+        raise ValueError(f"n_entries {n_entries!r}: expected an integer in 0..2^28")
+    n_entries = int(n_entries)
+    nbytes = nat.check(nat.lib.ww_clip_ledger_bytes(n_entries))
+    assert nbytes == C.sizeof(nat.LedgerHeader) + n_entries * C.sizeof(nat.LedgerEntry) and nbytes % 8 == 0
+    with torch.cuda.device(device):
+        state = ClipLedgerState(torch.empty(nbytes // 8, device=device, dtype=torch.int64), n_entries)
+    clip_ledger_reset(state)
+    return state
+
+
+def _check_ledger_state(state, like=None) -> None:
+    if not isinstance(state, ClipLedgerState):
+        raise TypeError(f"state: expected what ops.new_clip_ledger() makes, got {type(state).__name__}")
+    if like is not None and state.device != like.device:
+        raise RuntimeError(f"ledger on {state.device}, logits on {like.device}")
+
+
+def clip_ledger_reset(state: ClipLedgerState) -> None:
+    """ww_clip_ledger_init: the header written and every record cleared, whatever the buffer held."""
+    _check_ledger_state(state)
+    with torch.cuda.device(state.device):
+        nat.check(nat.lib.ww_clip_ledger_init(_ptr(state.buffer), state.n_entries, _stream()))
+
+
+def clip_ledger_update_into(logits, labels, entries, state, epoch=-1) -> None:
+    """ww_clip_ledger_update_f32 on checked arguments (`labels` as _check_ce returns them, `entries` int64 [n] on the device, unit
+    stride): one launch, nothing else."""
+    with torch.cuda.device(logits.device):
+        nat.check(nat.lib.ww_clip_ledger_update_f32(_ptr(logits), _ptr(labels), _ptr(entries), logits.shape[0], int(epoch),
+                                                    _ptr(state.buffer), state.n_entries, _stream()))
+
+
+def clip_ledger_update(logits: torch.Tensor, labels: torch.Tensor, entries: torch.Tensor, state: ClipLedgerState, epoch: int = -1) -> None:
+    """Add a batch to the ledger: logits [n, 2] float32, labels [n] or [n, 1] int64 (the checks of `ce_loss`) and entries [n] int64, all
+    on the GPU; `epoch` in 0..63, or -1 for no epoch bit.  A negative entry is skipped, one >= n_entries is counted in `bad_entries`
+    and written nowhere.  One launch in stream order; nothing waits for the device."""
+    labels = _check_ce(logits, labels)
+    _check_ledger_state(state, logits)
+    if not isinstance(entries, torch.Tensor) or entries.dtype != torch.int64:
+        raise TypeError("entries: expected an int64 torch.Tensor")
+    if entries.device != logits.device:
+        raise RuntimeError(f"entries on {entries.device}, logits on {logits.device}")
+    if entries.dim() != 1 or entries.shape[0] != logits.shape[0]:
+        raise ValueError(f"entries: expected [{logits.shape[0]}], got {tuple(entries.shape)}")
+    if isinstance(epoch, bool) or int(epoch) != epoch or not -1 <= int(epoch) < nat.LEDGER_MAX_EPOCHS:
+        raise ValueError(f"epoch {epoch!r}: expected 0..63, or -1 for no epoch bit")
+    if entries.stride(0) != 1 and entries.shape[0] != 1:
+        entries = entries.contiguous()
+    clip_ledger_update_into(logits, labels, entries, state, epoch)
+
+
+def read_clip_ledger(state: ClipLedgerState):
+    """The ledger on the host as a ledger.LedgerReport.  One device-to-host copy."""
+    from .ledger import LedgerReport
+    _check_ledger_state(state)
+    return LedgerReport.from_buffer(state.buffer.cpu().numpy(), state.n_entries)
+
+
 def adam_table(params, grads, exp_avgs, exp_avg_sqs):
     """Four equally long lists of float32 GPU tensors -> a ctypes array of _native.AdamTensor (at most 16 entries).  A grads-only table
     (the other three None) is what grad_norm reads."""

@@ -11,6 +11,11 @@ more launch per batch, no wait); `trainer.val_report` reads it, lazily, as a met
 the best checkpoint and early stopping follow: "val_acc" (the reference's behaviour, the default), "val_f1" (the wake-word class's F1
 at argmax, times 100) or "val_auc" (the ROC AUC of the margins, times 100).
 
+`ledger=` / `val_ledger=` (ledger.ClipLedger, also assignable as attributes) keep a per-clip record: `train_epoch` opens the ledger's next
+epoch and scatters every step's train-mode logits by the loader's `last_entries`, `validate` does the same into `val_ledger` with the
+eval-mode logits -- one more launch per batch, no wait.  With both None a step issues exactly the launches it
+always issued.
+
 One deliberate difference: the reference calls `clip_grad_norm_` BEFORE `backward()`, where it clips the previous batch's gradients or
 nothing, so the default here is no clipping; `max_grad_norm=1.0` gives the clip the call meant, after the
 backward.
@@ -36,7 +41,7 @@ MONITOR_NAMES = {"val_acc": "Acc", "val_f1": "F1", "val_auc": "AUC"}
 
 class WakewordTrainer:
     def __init__(self, model, device, config=TrainingConfig, *, checkpoint_path="best_wakeword_model.pth", max_grad_norm=None,
-                 monitor="val_acc", thresholds=(0.8,), criterion=None):
+                 monitor="val_acc", thresholds=(0.8,), criterion=None, ledger=None, val_ledger=None):
         if not isinstance(model, (SimpleWakewordModel, WakewordModel)):
             raise TypeError(f"WakewordTrainer drives the HIP training kernels of SimpleWakewordModel and WakewordModel; got {type(model).__name__}")
         if any(p.device.type != "cuda" for p in model.parameters()):
@@ -51,6 +56,8 @@ class WakewordTrainer:
         self.config = config
         self.checkpoint_path = checkpoint_path
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.ledger = ledger                                           # ledger.ClipLedger or None: the per-clip record of train_epoch
+        self.val_ledger = val_ledger                                   # ... and of validate
 
         # the reference's attribute; `step` and `validate` compute the same loss in ww_ce_loss_f32 / ww_ce_loss_ex_f32 (the property below)
         self.criterion = nn.CrossEntropyLoss().to(device) if criterion is None else criterion
@@ -171,10 +178,21 @@ class WakewordTrainer:
             raise ValueError(f"target: expected [{B}] or [{B}, 1], got {tuple(target.shape)}")
         return target if target.stride(0) == 1 or B == 1 else target.contiguous()
 
-    def step(self, data, target) -> torch.Tensor:
+    @staticmethod
+    def _entries_of(loader):
+        """The bank entries (or file indices) of the batch `loader` has just yielded."""
+        entries = getattr(loader, "last_entries", None)
+        if entries is None:
+            raise TypeError(f"a ledger needs a loader that names its rows: {type(loader).__name__} has no `last_entries` "
+                            "(bank.loader() and dataset.loader() set it; a hand-written loop passes step(..., entries=))")
+        return entries
+
+    def step(self, data, target, entries=None) -> torch.Tensor:
         """One training batch: data [B, 1, 80, T <= 32] float32 and target [B] or [B, 1] int64, both on the GPU (tensors elsewhere, or of
         another integer type, are copied first).  Returns the batch's mean loss as a 0-d tensor ON THE DEVICE (self.last_loss, overwritten
-        by the next step); the running metrics are in self.train_stats.  The model must be in train mode."""
+        by the next step); the running metrics are in self.train_stats.  The model must be in train mode.  `entries` [B] (a host integer
+        array or an int64 device tensor; train_epoch passes the loader's `last_entries`): with `self.ledger` set, the step's train-mode
+        logits and labels are added to it under these entries, one more launch after the optimiser's."""
         if not self.model.training:
             raise RuntimeError("WakewordTrainer.step: the model is in eval mode (train_epoch calls model.train())")
         if isinstance(data, torch.Tensor) and data.device != self._dev:
@@ -218,6 +236,8 @@ class WakewordTrainer:
             if self.max_grad_norm is not None:
                 self._norm_step()
         self.optimizer.step(grad_scale=self._scale if self.max_grad_norm is not None else None)
+        if entries is not None and self.ledger is not None:
+            self.ledger.update(entries, self._logits[:B], y)
         return self.last_loss
 
     @property
@@ -238,8 +258,10 @@ class WakewordTrainer:
     def train_epoch(self, train_loader):
         self.model.train()
         self.train_stats.zero_()
+        if self.ledger is not None:
+            self.ledger.begin_epoch()
         for data, target in train_loader:
-            self.step(data, target)
+            self.step(data, target, None if self.ledger is None else self._entries_of(train_loader))
         return self._finish_epoch(self.train_stats, "train_epoch")
 
     def validate(self, val_loader):
@@ -248,6 +270,8 @@ class WakewordTrainer:
         ops.reset_clip_metrics(self.val_metrics)
         self._val_report = None
         self._validated = True
+        if self.val_ledger is not None:
+            self.val_ledger.begin_epoch()
         with torch.no_grad():
             for data, target in val_loader:
                 if data.device != self._dev:
@@ -256,6 +280,8 @@ class WakewordTrainer:
                 y = self._target(target, output.shape[0])
                 ops.ce_loss_into(output, y, None, None, self.val_stats, opts=self._loss_opts)
                 ops.clip_metrics_update_into(output, y, self.val_metrics)
+                if self.val_ledger is not None:
+                    self.val_ledger.update(self._entries_of(val_loader), output, y)
         return self._finish_epoch(self.val_stats, "validate")
 
     @property
