@@ -106,6 +106,29 @@ def test_streaming_n_matches_oracle_and_forward_pcm(dev, arch, n, hop):
     det.close()
 
 
+@pytest.mark.parametrize("arch", ["simple", "full"])
+@pytest.mark.parametrize("n_mics", [1, 5])
+@pytest.mark.parametrize("n", [4000, 16000])
+def test_streamer_step_is_the_forward_chain_on_its_window(dev, arch, n_mics, n):
+    """The streamer shares its workspace layout and launch chain with the batch entry points: every hop until the ring is full, its
+    logits are, bit for bit, those of the batch call on the rows ww_streamer_window unrolls -- ops.forward_pcm at one second,
+    ops.forward_pcm_frames below.  One microphone (its stride is never used) and five (an odd batch)."""
+    sd = pkg.synth.make_state_dict(arch, seed=1234)
+    m = _model(arch, sd, dev, n)
+    hop = n // 10
+    streams = torch.from_numpy(_streams(n_mics, n, 900)).to(dev)
+    det = pkg.StreamingDetector(m, n_mics=n_mics, hop_samples=hop)
+    assert det.window_samples == n
+    packed = m.packed_weights()
+    for k in range(10):
+        det.step(streams[:, k * hop:(k + 1) * hop])
+        rows = det.window()                                            # waits for the detector's stream
+        assert torch.equal(rows[:, n - (k + 1) * hop:], streams[:, :(k + 1) * hop]) and not rows[:, :n - (k + 1) * hop].any()
+        direct = ops.forward_pcm(rows, packed, m._n_conv) if n == 16000 else ops.forward_pcm_frames(rows, packed, m._n_conv, n)
+        assert torch.equal(det.logits.view(torch.int32), direct.view(torch.int32)), (k, det.logits, direct)
+    det.close()
+
+
 @pytest.mark.parametrize("conv", ["f32", "f16x3", "f16x3d"])
 @pytest.mark.parametrize("mel", ["f32", "f64", "auto"])
 def test_streaming_n_arithmetics(dev, conv, mel):

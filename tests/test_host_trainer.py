@@ -112,6 +112,32 @@ def test_grad_norm_refuses_before_any_hip_call():
         assert L.ww_grad_norm_f32(_table(p=None, m=None, v=None), 2, 1.0, 16, 16, 256, None) == nat.WW_ENODEVICE
 
 
+@pytest.mark.parametrize("n_conv", [2, 3])
+def test_train_grads_struct_points_at_the_named_gradients(n_conv):
+    """ops.train_grads_struct, the one builder behind _TrainStep.backward and WakewordTrainer._bind_grads: every pointer field of
+    ww_train_grads is the address of the gradient of that name (data_ptr() needs no device).  The struct's per-layer bias gradient is
+    bias_ih's -- bias_hh shares it -- and weight_hh has no field: neither key is read, so neither tensor's address appears."""
+    from wakeword_jupyterlab_amd import ops
+    keys = ops._train_keys(n_conv)
+    grads = {k: torch.zeros(3 + i) for i, k in enumerate(keys)}                 # distinct storages, distinct addresses
+    assert len({g.data_ptr() for g in grads.values()}) == len(keys) == 10 + 2 * n_conv
+    tg = ops.train_grads_struct(grads, n_conv)
+    assert isinstance(tg, nat.TrainGrads)
+    want = {"conv_weight": [grads[f"conv{i + 1}.weight"].data_ptr() if i < n_conv else None for i in range(3)],
+            "conv_bias": [grads[f"conv{i + 1}.bias"].data_ptr() if i < n_conv else None for i in range(3)],
+            "lstm_weight_ih": [grads[f"lstm.weight_ih_l{layer}"].data_ptr() for layer in range(2)],
+            "lstm_bias": [grads[f"lstm.bias_ih_l{layer}"].data_ptr() for layer in range(2)],
+            "fc_weight": grads["fc.weight"].data_ptr(), "fc_bias": grads["fc.bias"].data_ptr()}
+    assert [name for name, _ in nat.TrainGrads._fields_] == list(want)
+    got = {name: list(getattr(tg, name)) if isinstance(want[name], list) else getattr(tg, name) for name in want}
+    assert got == want
+    unread = [k for k in keys if "weight_hh" in k or "bias_hh" in k]
+    assert len(unread) == 4
+    held = {p for v in got.values() for p in (v if isinstance(v, list) else [v])}
+    assert not held & {grads[k].data_ptr() for k in unread}
+    ops.train_grads_struct({k: g for k, g in grads.items() if k not in unread}, n_conv)        # ... and the builder does not ask for them
+
+
 def test_lazy_exports_and_training_config():
     from wakeword_jupyterlab_amd import config, optim, trainer
     assert pkg.WakewordTrainer is trainer.WakewordTrainer and pkg.FusedAdam is optim.FusedAdam and pkg.TrainingConfig is config.TrainingConfig

@@ -7,6 +7,8 @@ the size stay aligned.  `Guarded` is tested on a CPU tensor: alignment, `intact(
 into either guard is seen."""
 import ctypes as C
 import itertools
+import json
+import os
 
 import pytest
 import torch
@@ -80,6 +82,23 @@ def test_size_query_is_monotone_and_aligned(name):
             if i + 1 < len(grid):
                 up = args[:axis] + (grid[i + 1],) + args[axis + 1:]
                 assert values[up] >= v, f"{name}: {up} needs {values[up]} bytes, fewer than {args} ({v})"
+
+
+def test_forward_size_queries_agree_and_are_the_recorded_ones():
+    """One layout serves the forward path: ww_workspace_frames_bytes and ww_forward_windows_workspace_bytes are equal at every clip
+    length, and at one second both equal ww_workspace_bytes.  Each also equals the size recorded from the library of the commit before
+    the layouts were folded into one (tests/golden/forward_workspace_sizes.json, written by make_forward_workspace_sizes.py)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "forward_workspace_sizes.json")) as f:
+        recorded = json.load(f)
+    assert {k: len(v) for k, v in recorded.items()} == {"ww_workspace_bytes": len(NS) * 2, "ww_workspace_frames_bytes": len(NS) * len(SAMPLES) * 2,
+                                                        "ww_forward_windows_workspace_bytes": len(NS) * len(SAMPLES) * 2}
+    for n, s, c in itertools.product(NS, SAMPLES, (2, 3)):
+        frames, windows = L.ww_workspace_frames_bytes(n, s, c), L.ww_forward_windows_workspace_bytes(n, s, c)
+        assert frames == windows, (n, s, c, frames, windows)
+        assert frames == recorded["ww_workspace_frames_bytes"][f"{n},{s},{c}"], (n, s, c)
+        assert windows == recorded["ww_forward_windows_workspace_bytes"][f"{n},{s},{c}"], (n, s, c)
+        if s == 16000:
+            assert L.ww_workspace_bytes(n, c) == frames == recorded["ww_workspace_bytes"][f"{n},{c}"], (n, c)
 
 
 def test_augment_layout_tiles_the_queried_size():

@@ -28,24 +28,23 @@ class NativeError(RuntimeError):
         self.code = code
 
 
+# the model's parameters in torch layout, as ww_state_dict (host pointers) and ww_train_params (device pointers) both declare them
+_MODEL_FIELDS = [
+    ("n_conv", C.c_int32), ("hidden", C.c_int32),
+    ("conv_weight", C.c_void_p * 3), ("conv_bias", C.c_void_p * 3),
+    ("lstm_weight_ih", C.c_void_p * 2), ("lstm_bias_ih", C.c_void_p * 2), ("lstm_bias_hh", C.c_void_p * 2),
+    ("fc_weight", C.c_void_p), ("fc_bias", C.c_void_p),
+]
+
+
 class StateDict(C.Structure):
     """struct ww_state_dict (include/wakeword_amd.h)."""
-    _fields_ = [
-        ("n_conv", C.c_int32), ("hidden", C.c_int32),
-        ("conv_weight", C.c_void_p * 3), ("conv_bias", C.c_void_p * 3),
-        ("lstm_weight_ih", C.c_void_p * 2), ("lstm_bias_ih", C.c_void_p * 2), ("lstm_bias_hh", C.c_void_p * 2),
-        ("fc_weight", C.c_void_p), ("fc_bias", C.c_void_p),
-    ]
+    _fields_ = _MODEL_FIELDS
 
 
 class TrainParams(C.Structure):
     """struct ww_train_params: DEVICE pointers, torch layout."""
-    _fields_ = [
-        ("n_conv", C.c_int32), ("hidden", C.c_int32),
-        ("conv_weight", C.c_void_p * 3), ("conv_bias", C.c_void_p * 3),
-        ("lstm_weight_ih", C.c_void_p * 2), ("lstm_bias_ih", C.c_void_p * 2), ("lstm_bias_hh", C.c_void_p * 2),
-        ("fc_weight", C.c_void_p), ("fc_bias", C.c_void_p),
-    ]
+    _fields_ = _MODEL_FIELDS
 
 
 class TrainGrads(C.Structure):

@@ -84,38 +84,100 @@ static std::atomic<int> g_logmel_math{WW_LOGMEL_MATH_AUTO};
 int logmel_math_mode() { return t_logmel_math != WW_MATH_INHERIT ? t_logmel_math : g_logmel_math.load(std::memory_order_relaxed); }
 void set_logmel_math_mode(int mode) { g_logmel_math.store(mode, std::memory_order_relaxed); }
 
-static int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
-int64_t cnn_scratch_bytes(int64_t n, int n_conv);
+static int64_t wide_scratch_bytes(int64_t n, int32_t width, int32_t n_conv) {
+    return width <= WW_MAX_WIDTH ? cnn_scratch_bytes(n, n_conv) : cnn_wide_scratch_bytes(n, width, n_conv);
+}
 
-struct Workspace {
+// THE layout of the forward path's workspace: n log-mel images of T frames, n pooled rows, the conv stack's scratch.  Every size query
+// (base == nullptr) and every entry point that walks the workspace goes through here.
+struct ForwardWorkspace {
     float* logmel;
     float* pooled;
     void* scratch;
     int64_t total;
 };
-// `width`: the mel frames per clip (kFrames for 1 s; the streamer's T <= 32 for shorter windows)
-static Workspace carve(void* base, int64_t n, int n_conv, int width = kFrames) {
-    Workspace w{};
+static ForwardWorkspace forward_workspace(void* base, int64_t n, int T, int n_conv) {
+    ForwardWorkspace w{};
     char* p = static_cast<char*>(base);
     int64_t o = 0;
-    w.logmel = reinterpret_cast<float*>(p + o); o += align256(n * kMels * width * int64_t(sizeof(float)));
-    w.pooled = reinterpret_cast<float*>(p + o); o += align256(n * 128 * int64_t(sizeof(float)));
-    w.scratch = p + o; o += align256(cnn_scratch_bytes(n, n_conv));
+    w.logmel = reinterpret_cast<float*>(p + o); o += up256(n * kMels * T * int64_t(sizeof(float)));
+    w.pooled = reinterpret_cast<float*>(p + o); o += up256(n * 128 * int64_t(sizeof(float)));
+    w.scratch = p + o; o += up256(wide_scratch_bytes(n, T, n_conv));
     w.total = o;
     return w;
 }
+static int frames_of(int64_t n_samples) { return int(1 + n_samples / kHop); }
 
-static int check_pcm(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len) {
-    if (n_clips < 0 || n_clips > (int64_t(1) << 30)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
-    if (n_clips == 0) return WW_OK;
-    if (!pcm) return fail(WW_EINVAL, "null pcm pointer");
-    if (clip_len <= 0 || clip_len > kClip)
-        return fail(WW_EINVAL, "clip_len %lld: expected 1..%d samples (longer clips are cropped by the host, "
-                    "pad_or_truncate wakeword_training_script.py:78-83)", (long long)clip_len, kClip);
-    if (clip_stride < clip_len && n_clips > 1) return fail(WW_EINVAL, "clip_stride %lld < clip_len %lld", (long long)clip_stride, (long long)clip_len);
-    // a single clip has no second row: its stride is never used (any clip_len, e.g. 15999, is fine)
-    if ((reinterpret_cast<uintptr_t>(pcm) & 15) || (n_clips > 1 && (clip_stride & 3)))
-        return fail(WW_EINVAL, "pcm must be 16-byte aligned with clip_stride %% 4 == 0 (got %p, %lld)", (const void*)pcm, (long long)clip_stride);
+static int cnn_pool_any(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch, float* pooled,
+                        hipStream_t st) {
+    if (width <= WW_MAX_WIDTH) return launch_cnn_pool(mel, n, width, packed, n_conv, scratch, pooled, st);
+    return launch_cnn_pool_wide(mel, n, width, packed, n_conv, scratch, pooled, st);
+}
+// THE launch chain, mel -> logits (and prob where asked for): what ww_model_forward_f32 runs on the caller's mel images
+static int model_chain(const float* mel, int64_t n, int T, const float* packed, int n_conv, const ForwardWorkspace& w, float* logits,
+                       float* prob, hipStream_t st) {
+    if (int rc = cnn_pool_any(mel, n, T, packed, n_conv, w.scratch, w.pooled, st)) return rc;
+    return launch_lstm_fc(w.pooled, n, packed, n_conv, logits, prob, st);
+}
+// ... and pcm -> logits, rows of n_samples with clip_len valid samples: at n_samples = kClip launch for launch the 1 s chain
+// (launch_logmel_frames hands T = 32 to launch_logmel, cnn_pool_any T <= 32 to launch_cnn_pool).  ring_pos: the streamer's window start.
+static int forward_chain(const float* pcm, int64_t n, int64_t stride, int64_t clip_len, int64_t n_samples, int normalize,
+                         const int32_t* ring_pos, int64_t ring_len, const float* packed, int n_conv, const ForwardWorkspace& w,
+                         float* logits, float* prob, hipStream_t st) {
+    if (int rc = launch_logmel_frames(pcm, n, stride, clip_len, n_samples, normalize, ring_pos, ring_len, w.logmel, st)) return rc;
+    return model_chain(w.logmel, n, frames_of(n_samples), packed, n_conv, w, logits, prob, st);
+}
+
+// The pcm rows of every entry point that takes some.  The kinds of call differ in what they allow and in how they word a refusal:
+struct RowRule {
+    int align;                    // of the pcm base in bytes: 16 where rows are loaded as float4 (then clip_stride % 4 == 0 too), else 4
+    int64_t n_max, lo, hi;        // rows; samples per row (n_samples of the augmentation calls, the valid clip_len of the log-mel ones)
+    bool len_first;               // a length outside lo..hi is refused before n is looked at, else after the null check
+    const char* range;            // that refusal: printf form taking (long long samples, int lo, int hi)
+    const char* null;             // a missing pointer
+    const char* misaligned;       // pcm or clip_stride: printf form taking (const void* pcm, long long clip_stride)
+    const char* out_misaligned;   // out_dev or workspace_dev of the calls that write rows; nullptr for the calls that have none
+};
+constexpr RowRule kClipRows = {16, int64_t(1) << 30, 1, kClip, false,
+                               "clip_len %lld: expected %d..%d samples (longer clips are cropped by the host, pad_or_truncate "
+                               "wakeword_training_script.py:78-83)",
+                               "null pcm pointer", "pcm must be 16-byte aligned with clip_stride %% 4 == 0 (got %p, %lld)", nullptr};
+constexpr RowRule kFrameRows = {16, int64_t(1) << 30, 1, WW_MAX_CLIP_SAMPLES, false, "clip_len %lld: expected >= %d",
+                                "null pcm / output pointer", "pcm must be 16-byte aligned with clip_stride %% 4 == 0", nullptr};
+constexpr RowRule kAugRows = {16, int64_t(1) << 24, WW_MIN_CLIP_SAMPLES, WW_AUG_MAX_SAMPLES, true,
+                              "n_samples %lld: augmentation takes %d..%d samples (0.25 s .. 32 frames at 16 kHz)",
+                              "null pcm / plan / output / workspace pointer",
+                              "pcm must be 16-byte aligned with clip_stride %% 4 == 0 (got %p, %lld)",
+                              "out_dev must be 4-byte and workspace_dev 256-byte aligned"};
+// the standalone mix and reverb: rows of every inference length, 4-byte aligned (`range` names the call)
+constexpr RowRule rows_4(const char* range) {
+    return {4, int64_t(1) << 24, WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES, true, range, "null pcm / output / workspace pointer",
+            "pcm_dev / out_dev must be 4-byte and workspace_dev 256-byte aligned",
+            "pcm_dev / out_dev must be 4-byte and workspace_dev 256-byte aligned"};
+}
+constexpr RowRule kMixRows = rows_4("n_samples %lld: the mix takes %d..%d samples (0.25 .. 2 s at 16 kHz)");
+constexpr RowRule kReverbRows = rows_4("n_samples %lld: the reverb takes %d..%d samples (0.25 .. 2 s at 16 kHz)");
+
+// `c`: pcm, n, stride and n_samples (the length the rule bounds), and out / out_stride / workspace where the rule has output rows;
+// `others`: the call's remaining pointers are all there.  A single row has no second one: its stride is never looked at.
+static int check_rows(const RowRule& k, const AugCall& c, bool others = true) {
+    const bool bad_len = c.n_samples < k.lo || c.n_samples > k.hi;
+    if (k.len_first && bad_len) return fail(WW_EINVAL, k.range, (long long)c.n_samples, int(k.lo), int(k.hi));
+    if (c.n < 0 || c.n > k.n_max) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)c.n);
+    if (c.n == 0) return WW_OK;
+    if (!c.pcm || !others || (k.out_misaligned && (!c.out || !c.workspace))) return fail(WW_EINVAL, "%s", k.null);
+    if (bad_len) return fail(WW_EINVAL, k.range, (long long)c.n_samples, int(k.lo), int(k.hi));
+    if (k.out_misaligned) {
+        if (c.n > 1 && (c.stride < c.n_samples || c.out_stride < c.n_samples))
+            return fail(WW_EINVAL, "clip_stride %lld / out_stride %lld < n_samples %lld", (long long)c.stride, (long long)c.out_stride,
+                        (long long)c.n_samples);
+    } else if (c.n > 1 && c.stride < c.n_samples) {
+        return fail(WW_EINVAL, "clip_stride %lld < clip_len %lld", (long long)c.stride, (long long)c.n_samples);
+    }
+    if ((reinterpret_cast<uintptr_t>(c.pcm) & (k.align - 1)) || (k.align == 16 && c.n > 1 && (c.stride & 3)))
+        return fail(WW_EINVAL, k.misaligned, (const void*)c.pcm, (long long)c.stride);
+    if (k.out_misaligned && ((reinterpret_cast<uintptr_t>(c.out) & 3) || (reinterpret_cast<uintptr_t>(c.workspace) & 255)))
+        return fail(WW_EINVAL, "%s", k.out_misaligned);
     return WW_OK;
 }
 
@@ -199,10 +261,8 @@ static int streamer_enqueue(ww_streamer* s, const void* hop_dev, float* prob_dev
     }
     // N = 16000 (T = 32) is launch_logmel's 1 s ring kernel with the same arguments as ever; other N the 64-frame tile in ring form
     const int N = s->n_samples;
-    Workspace w = carve(s->workspace, s->n_mics, s->n_conv, s->n_frames);
-    if (int rc = launch_logmel_frames(s->ring, s->n_mics, N, N, N, 1, s->pos, N, w.logmel, s->stream)) return rc;
-    if (int rc = launch_cnn_pool(w.logmel, s->n_mics, s->n_frames, s->packed, s->n_conv, w.scratch, w.pooled, s->stream)) return rc;
-    return launch_lstm_fc(w.pooled, s->n_mics, s->packed, s->n_conv, logits_dev, prob_dev, s->stream);
+    return forward_chain(s->ring, s->n_mics, N, N, N, 1, s->pos, N, s->packed, s->n_conv,
+                         forward_workspace(s->workspace, s->n_mics, s->n_frames, s->n_conv), logits_dev, prob_dev, s->stream);
 }
 
 extern "C" {
@@ -275,7 +335,7 @@ int ww_device_info(int* n_cu, int* clock_khz, char* name, int name_len) {
 
 int ww_logmel_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int normalize,
                   float* logmel_dev, ww_stream_t stream) {
-    if (int rc = check_pcm(pcm_dev, n_clips, clip_stride, clip_len)) return rc;
+    if (int rc = check_rows(kClipRows, {pcm_dev, n_clips, clip_stride, clip_len})) return rc;
     if (n_clips > 0 && !logmel_dev) return fail(WW_EINVAL, "null output pointer");
     if (int rc = require_gfx950()) return rc;
     return launch_logmel(pcm_dev, n_clips, clip_stride, clip_len, normalize, nullptr, 0, logmel_dev,
@@ -307,7 +367,7 @@ int64_t ww_augment_workspace_bytes(int64_t n_clips) {
 int ww_augment_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, const ww_augment_plan* plans_host,
                    float* out_dev, void* workspace_dev, ww_stream_t stream) {
     if (int rc = check_n_clips(n_clips)) return rc;
-    if (int rc = check_pcm(pcm_dev, n_clips, clip_stride, kClip)) return rc;
+    if (int rc = check_rows(kClipRows, {pcm_dev, n_clips, clip_stride, kClip})) return rc;
     if (n_clips == 0) return WW_OK;
     if (!plans_host || !out_dev || !workspace_dev) return fail(WW_EINVAL, "null plan / output / workspace pointer");
     if ((reinterpret_cast<uintptr_t>(out_dev) & 15) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
@@ -328,7 +388,7 @@ int ww_augment_plans_prepare(const ww_augment_plan* plans_host, int64_t n_clips,
 int ww_augment_records_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, const void* records_dev, float* out_dev,
                            void* workspace_dev, ww_stream_t stream) {
     if (int rc = check_n_clips(n_clips)) return rc;
-    if (int rc = check_pcm(pcm_dev, n_clips, clip_stride, kClip)) return rc;
+    if (int rc = check_rows(kClipRows, {pcm_dev, n_clips, clip_stride, kClip})) return rc;
     if (n_clips == 0) return WW_OK;
     if (!records_dev || !out_dev || !workspace_dev) return fail(WW_EINVAL, "null record / output / workspace pointer");
     if ((reinterpret_cast<uintptr_t>(out_dev) & 15) || (reinterpret_cast<uintptr_t>(workspace_dev) & 255) || (reinterpret_cast<uintptr_t>(records_dev) & 7))
@@ -341,31 +401,16 @@ int ww_augment_records_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_s
 // ---- augmentation of clips of n_samples in [WW_MIN_CLIP_SAMPLES, WW_AUG_MAX_SAMPLES] (the 1 s entry points above are unchanged) ----
 static int check_aug_samples(int64_t n_samples) {
     if (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_AUG_MAX_SAMPLES)
-        return fail(WW_EINVAL, "n_samples %lld: augmentation takes %d..%d samples (0.25 s .. 32 frames at 16 kHz)", (long long)n_samples,
-                    WW_MIN_CLIP_SAMPLES, WW_AUG_MAX_SAMPLES);
+        return fail(WW_EINVAL, kAugRows.range, (long long)n_samples, WW_MIN_CLIP_SAMPLES, WW_AUG_MAX_SAMPLES);
     return WW_OK;
 }
 static int check_aug_sizes(int64_t n_clips, int64_t n_samples) {
     if (int rc = check_aug_samples(n_samples)) return rc;
     return check_n_clips(n_clips);
 }
-// `plans`: the host plans of a direct call, or the device records of a *_records call
-static int check_aug_rows(const AugCall& c, const void* plans) {
-    if (int rc = check_aug_sizes(c.n, c.n_samples)) return rc;
-    if (c.n == 0) return WW_OK;
-    if (!c.pcm || !plans || !c.out || !c.workspace) return fail(WW_EINVAL, "null pcm / plan / output / workspace pointer");
-    if (c.n > 1 && (c.stride < c.n_samples || c.out_stride < c.n_samples))
-        return fail(WW_EINVAL, "clip_stride %lld / out_stride %lld < n_samples %lld", (long long)c.stride, (long long)c.out_stride,
-                    (long long)c.n_samples);
-    if ((reinterpret_cast<uintptr_t>(c.pcm) & 15) || (c.n > 1 && (c.stride & 3)))
-        return fail(WW_EINVAL, "pcm must be 16-byte aligned with clip_stride %% 4 == 0 (got %p, %lld)", (const void*)c.pcm, (long long)c.stride);
-    if ((reinterpret_cast<uintptr_t>(c.out) & 3) || (reinterpret_cast<uintptr_t>(c.workspace) & 255))
-        return fail(WW_EINVAL, "out_dev must be 4-byte and workspace_dev 256-byte aligned");
-    return WW_OK;
-}
 // The *_records calls of the lengths above: the checks, then nothing but launches
 static int augment_records(const AugCall& c, const void* records_dev, unsigned parts) {
-    if (int rc = check_aug_rows(c, records_dev)) return rc;
+    if (int rc = check_rows(kAugRows, c, records_dev != nullptr)) return rc;
     if (c.n == 0) return WW_OK;
     if (reinterpret_cast<uintptr_t>(records_dev) & 7) return fail(WW_EINVAL, "records_dev must be 8-byte aligned");
     if ((parts & kAugBg) && (c.bank_len < 0 || (c.bank_len > 0 && !c.bank)))
@@ -393,7 +438,7 @@ int ww_augment_workspace_layout(int64_t n_clips, int64_t n_samples, ww_augment_l
 int ww_augment_n_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t n_samples, const ww_augment_plan* plans_host,
                      float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream) {
     const AugCall c = {pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream)};
-    if (int rc = check_aug_rows(c, plans_host)) return rc;
+    if (int rc = check_rows(kAugRows, c, plans_host != nullptr)) return rc;
     if (n_clips == 0) return WW_OK;
     return augment_direct(c, 0, plans_host, nullptr, nullptr);
 }
@@ -432,7 +477,7 @@ int ww_augment_bg_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride
                       void* workspace_dev, ww_stream_t stream) {
     const AugCall c = {pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream), bank_dev,
                        bank_len};
-    if (int rc = check_aug_rows(c, plans_host)) return rc;
+    if (int rc = check_rows(kAugRows, c, plans_host != nullptr)) return rc;
     if (n_clips == 0) return WW_OK;
     if (int rc = check_bg_args(n_clips, bg_host, bank_dev, bank_len)) return rc;
     return augment_direct(c, kAugBg, plans_host, bg_host, nullptr);
@@ -457,22 +502,6 @@ int ww_augment_bg_records_f32(const float* pcm_dev, int64_t n_clips, int64_t cli
                            records_dev, kAugBg);
 }
 
-// The standalone mix and reverb: rows of every inference length, 4-byte aligned (`what` names the call in the n_samples refusal)
-static int check_rows_4(const AugCall& c, const char* what) {
-    if (c.n_samples < WW_MIN_CLIP_SAMPLES || c.n_samples > WW_MAX_CLIP_SAMPLES)
-        return fail(WW_EINVAL, "n_samples %lld: the %s takes %d..%d samples (0.25 .. 2 s at 16 kHz)", (long long)c.n_samples, what,
-                    WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES);
-    if (int rc = check_n_clips(c.n)) return rc;
-    if (c.n == 0) return WW_OK;
-    if (!c.pcm || !c.out || !c.workspace) return fail(WW_EINVAL, "null pcm / output / workspace pointer");
-    if (c.n > 1 && (c.stride < c.n_samples || c.out_stride < c.n_samples))
-        return fail(WW_EINVAL, "clip_stride %lld / out_stride %lld < n_samples %lld", (long long)c.stride, (long long)c.out_stride,
-                    (long long)c.n_samples);
-    if ((reinterpret_cast<uintptr_t>(c.pcm) & 3) || (reinterpret_cast<uintptr_t>(c.out) & 3) || (reinterpret_cast<uintptr_t>(c.workspace) & 255))
-        return fail(WW_EINVAL, "pcm_dev / out_dev must be 4-byte and workspace_dev 256-byte aligned");
-    return WW_OK;
-}
-
 int64_t ww_mix_background_workspace_bytes(int64_t n_clips) {
     if (int rc = check_n_clips(n_clips)) return rc;
     return mix_background_workspace_bytes(n_clips);
@@ -483,7 +512,7 @@ int ww_mix_background_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_st
                           ww_stream_t stream) {
     const AugCall c = {pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream), bank_dev,
                        bank_len};
-    if (int rc = check_rows_4(c, "mix")) return rc;
+    if (int rc = check_rows(kMixRows, c)) return rc;
     if (n_clips == 0) return WW_OK;
     if (int rc = check_bg_args(n_clips, bg_host, bank_dev, bank_len)) return rc;
     std::vector<char> rec(size_t(mix_background_workspace_bytes(n_clips)));
@@ -539,7 +568,7 @@ int ww_augment_rir_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_strid
                        ww_stream_t stream) {
     const AugCall c = {pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream), bank_dev,
                        bank_len, spectra_dev, n_rirs};
-    if (int rc = check_aug_rows(c, plans_host)) return rc;
+    if (int rc = check_rows(kAugRows, c, plans_host != nullptr)) return rc;
     if (n_clips == 0) return WW_OK;
     if (bg_host)
         if (int rc = check_bg_args(n_clips, bg_host, bank_dev, bank_len)) return rc;
@@ -575,7 +604,7 @@ int ww_reverb_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, in
                   const float* spectra_dev, int64_t n_rirs, float* out_dev, int64_t out_stride, void* workspace_dev, ww_stream_t stream) {
     const AugCall c = {pcm_dev, n_clips, clip_stride, n_samples, out_dev, out_stride, workspace_dev, static_cast<hipStream_t>(stream), nullptr, 0,
                        spectra_dev, n_rirs};
-    if (int rc = check_rows_4(c, "reverb")) return rc;
+    if (int rc = check_rows(kReverbRows, c)) return rc;
     if (n_clips == 0) return WW_OK;
     if (int rc = check_rir_args(n_clips, rir_host, spectra_dev, n_rirs)) return rc;
     std::vector<char> rec(size_t(reverb_workspace_bytes(n_clips)));
@@ -647,7 +676,7 @@ int ww_lstm_fc_f32(const float* pooled_dev, int64_t n, const float* packed_dev, 
 
 int64_t ww_workspace_bytes(int64_t n, int32_t n_conv) {
     if (n < 0 || (n_conv != 2 && n_conv != 3)) return fail(WW_EINVAL, "bad workspace query");
-    return carve(nullptr, n, n_conv).total;
+    return forward_workspace(nullptr, n, kFrames, n_conv).total;
 }
 
 int ww_model_forward_f32(const float* mel_dev, int64_t n, int32_t width, const float* packed_dev, int32_t n_conv,
@@ -656,25 +685,21 @@ int ww_model_forward_f32(const float* mel_dev, int64_t n, int32_t width, const f
     if (n == 0) return WW_OK;
     if (!mel_dev || !logits_dev || !workspace_dev) return fail(WW_EINVAL, "null tensor / workspace pointer");
     if (int rc = require_gfx950()) return rc;
-    Workspace w = carve(workspace_dev, n, n_conv);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = launch_cnn_pool(mel_dev, n, width, packed_dev, n_conv, w.scratch, w.pooled, st)) return rc;
-    return launch_lstm_fc(w.pooled, n, packed_dev, n_conv, logits_dev, nullptr, st);
+    // the workspace of ww_workspace_bytes(): laid out for kFrames whatever the width
+    return model_chain(mel_dev, n, width, packed_dev, n_conv, forward_workspace(workspace_dev, n, kFrames, n_conv), logits_dev, nullptr,
+                       static_cast<hipStream_t>(stream));
 }
 
 int ww_forward_pcm_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int normalize,
                        const float* packed_dev, int32_t n_conv, void* workspace_dev, float* logits_dev,
                        ww_stream_t stream) {
-    if (int rc = check_pcm(pcm_dev, n_clips, clip_stride, clip_len)) return rc;
+    if (int rc = check_rows(kClipRows, {pcm_dev, n_clips, clip_stride, clip_len})) return rc;
     if (int rc = check_model(n_clips, kFrames, packed_dev, n_conv)) return rc;
     if (n_clips == 0) return WW_OK;
     if (!logits_dev || !workspace_dev) return fail(WW_EINVAL, "null logits / workspace pointer");
     if (int rc = require_gfx950()) return rc;
-    Workspace w = carve(workspace_dev, n_clips, n_conv);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = launch_logmel(pcm_dev, n_clips, clip_stride, clip_len, normalize, nullptr, 0, w.logmel, st)) return rc;
-    if (int rc = launch_cnn_pool(w.logmel, n_clips, kFrames, packed_dev, n_conv, w.scratch, w.pooled, st)) return rc;
-    return launch_lstm_fc(w.pooled, n_clips, packed_dev, n_conv, logits_dev, nullptr, st);
+    return forward_chain(pcm_dev, n_clips, clip_stride, clip_len, kClip, normalize, nullptr, 0, packed_dev, n_conv,
+                         forward_workspace(workspace_dev, n_clips, kFrames, n_conv), logits_dev, nullptr, static_cast<hipStream_t>(stream));
 }
 
 // ---- any clip length in [0.25 s, 2 s] (the 1 s entry points above are unchanged) ----
@@ -690,25 +715,12 @@ static int check_wide(int64_t n, int32_t width, const float* packed, int32_t n_c
     if (n > (int64_t(1) << 24)) return fail(WW_EINVAL, "batch %lld out of range", (long long)n);
     return check_model(n, width <= WW_MAX_WIDTH ? width : 1, packed, n_conv);
 }
-static int64_t wide_scratch_bytes(int64_t n, int32_t width, int32_t n_conv) {
-    return width <= WW_MAX_WIDTH ? cnn_scratch_bytes(n, n_conv) : cnn_wide_scratch_bytes(n, width, n_conv);
-}
-static int cnn_pool_any(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch, float* pooled,
-                        hipStream_t st) {
-    if (width <= WW_MAX_WIDTH) return launch_cnn_pool(mel, n, width, packed, n_conv, scratch, pooled, st);
-    return launch_cnn_pool_wide(mel, n, width, packed, n_conv, scratch, pooled, st);
-}
 
 int ww_logmel_frames_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples, int normalize,
                          float* logmel_dev, ww_stream_t stream) {
     if (int rc = check_samples(clip_len, n_samples)) return rc;
-    if (n_clips < 0 || n_clips > (int64_t(1) << 30)) return fail(WW_EINVAL, "n_clips %lld out of range", (long long)n_clips);
+    if (int rc = check_rows(kFrameRows, {pcm_dev, n_clips, clip_stride, clip_len}, logmel_dev != nullptr)) return rc;
     if (n_clips == 0) return WW_OK;
-    if (!pcm_dev || !logmel_dev) return fail(WW_EINVAL, "null pcm / output pointer");
-    if (clip_len <= 0) return fail(WW_EINVAL, "clip_len %lld: expected >= 1", (long long)clip_len);
-    if (clip_stride < clip_len && n_clips > 1) return fail(WW_EINVAL, "clip_stride %lld < clip_len %lld", (long long)clip_stride, (long long)clip_len);
-    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 15) || (n_clips > 1 && (clip_stride & 3)))
-        return fail(WW_EINVAL, "pcm must be 16-byte aligned with clip_stride %% 4 == 0");
     if (int rc = require_gfx950()) return rc;
     return launch_logmel_frames(pcm_dev, n_clips, clip_stride, clip_len, n_samples, normalize, logmel_dev, static_cast<hipStream_t>(stream));
 }
@@ -732,46 +744,33 @@ int ww_cnn_pool_wide_f32(const float* mel_dev, int64_t n, int32_t width, const f
 int64_t ww_workspace_frames_bytes(int64_t n, int64_t n_samples, int32_t n_conv) {
     if (n < 0 || (n_conv != 2 && n_conv != 3) || n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_MAX_CLIP_SAMPLES)
         return fail(WW_EINVAL, "bad workspace query");
-    const int T = int(1 + n_samples / kHop);
-    return align256(n * kMels * T * int64_t(sizeof(float))) + align256(n * 128 * int64_t(sizeof(float))) +
-           align256(wide_scratch_bytes(n, T, n_conv));
+    return forward_workspace(nullptr, n, frames_of(n_samples), n_conv).total;
 }
 
 int ww_forward_pcm_frames_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples, int normalize,
                               const float* packed_dev, int32_t n_conv, void* workspace_dev, float* logits_dev, ww_stream_t stream) {
     if (int rc = check_samples(clip_len, n_samples)) return rc;
-    const int T = int(1 + n_samples / kHop);
+    const int T = frames_of(n_samples);
     if (int rc = check_wide(n_clips, T, packed_dev, n_conv)) return rc;
     if (n_clips == 0) return WW_OK;
     if (!logits_dev || !workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 255))
         return fail(WW_EINVAL, "null logits pointer, or workspace not a 256-byte aligned pointer");
-    char* p = static_cast<char*>(workspace_dev);
-    float* logmel = reinterpret_cast<float*>(p);
-    p += align256(n_clips * kMels * T * int64_t(sizeof(float)));
-    float* pooled = reinterpret_cast<float*>(p);
-    p += align256(n_clips * 128 * int64_t(sizeof(float)));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = ww_logmel_frames_f32(pcm_dev, n_clips, clip_stride, clip_len, n_samples, normalize, logmel, stream)) return rc;
-    if (int rc = cnn_pool_any(logmel, n_clips, T, packed_dev, n_conv, p, pooled, st)) return rc;
-    return launch_lstm_fc(pooled, n_clips, packed_dev, n_conv, logits_dev, nullptr, st);
+    if (int rc = check_rows(kFrameRows, {pcm_dev, n_clips, clip_stride, clip_len})) return rc;
+    if (int rc = require_gfx950()) return rc;
+    return forward_chain(pcm_dev, n_clips, clip_stride, clip_len, n_samples, normalize, nullptr, 0, packed_dev, n_conv,
+                         forward_workspace(workspace_dev, n_clips, T, n_conv), logits_dev, nullptr, static_cast<hipStream_t>(stream));
 }
 
 // ---- long recordings: overlapping windows of one signal, and events over their scores ----
 // The log-mel kernels (logmel_kernel, logmel64_kernel in all three arithmetics) only read the input, each clip through a buffer
 // descriptor of its own at pcm + c * clip_stride; every write goes to the workspace, indexed by clip.  So rows may overlap here, and
 // the chain is the one ww_forward_pcm_frames_f32 runs (at N = 16000 the 1 s kernels, as ww_forward_pcm_f32 does).
-static int64_t windows_workspace_bytes(int64_t n, int64_t n_samples, int32_t n_conv) {
-    const int T = int(1 + n_samples / kHop);
-    return align256(n * kMels * T * int64_t(sizeof(float))) + align256(n * 128 * int64_t(sizeof(float))) +
-           align256(wide_scratch_bytes(n, T, n_conv));
-}
-
 int64_t ww_forward_windows_workspace_bytes(int64_t n_windows, int64_t n_samples, int32_t n_conv) {
     if (n_windows < 0 || n_windows > (int64_t(1) << 24)) return fail(WW_EINVAL, "n_windows %lld out of range", (long long)n_windows);
     if (n_conv != 2 && n_conv != 3) return fail(WW_EINVAL, "n_conv must be 2 or 3, got %d", n_conv);
     if (n_samples != kClip && (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_MAX_CLIP_SAMPLES))
         return fail(WW_EINVAL, "n_samples %lld: expected %d..%d", (long long)n_samples, WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES);
-    return windows_workspace_bytes(n_windows, n_samples, n_conv);
+    return forward_workspace(nullptr, n_windows, frames_of(n_samples), n_conv).total;
 }
 
 int ww_forward_windows_f32(const float* signal_dev, int64_t n_windows, int64_t hop, int64_t n_samples, int normalize,
@@ -789,25 +788,17 @@ int ww_forward_windows_f32(const float* signal_dev, int64_t n_windows, int64_t h
     if (!packed_dev || (reinterpret_cast<uintptr_t>(packed_dev) & 15)) return fail(WW_EINVAL, "packed_dev must be a 16-byte aligned device pointer");
     if (!logits_dev) return fail(WW_EINVAL, "logits_dev is null");
     if (!workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 255)) return fail(WW_EINVAL, "workspace_dev must be 256-byte aligned");
-    const int64_t need = windows_workspace_bytes(n_windows, n_samples, n_conv);
-    if (workspace_bytes < need)
-        return fail(WW_EINVAL, "workspace_bytes %lld < %lld needed", (long long)workspace_bytes, (long long)need);
+    const ForwardWorkspace w = forward_workspace(workspace_dev, n_windows, frames_of(n_samples), n_conv);
+    if (workspace_bytes < w.total)
+        return fail(WW_EINVAL, "workspace_bytes %lld < %lld needed", (long long)workspace_bytes, (long long)w.total);
     if (int rc = require_gfx950()) return rc;
-    const int T = int(1 + n_samples / kHop);
-    char* p = static_cast<char*>(workspace_dev);
-    float* logmel = reinterpret_cast<float*>(p);
-    p += align256(n_windows * kMels * T * int64_t(sizeof(float)));
-    float* pooled = reinterpret_cast<float*>(p);
-    p += align256(n_windows * 128 * int64_t(sizeof(float)));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = launch_logmel_frames(signal_dev, n_windows, hop, n_samples, n_samples, normalize, logmel, st)) return rc;
-    if (int rc = cnn_pool_any(logmel, n_windows, T, packed_dev, n_conv, p, pooled, st)) return rc;
-    return launch_lstm_fc(pooled, n_windows, packed_dev, n_conv, logits_dev, prob_dev, st);
+    return forward_chain(signal_dev, n_windows, hop, n_samples, n_samples, normalize, nullptr, 0, packed_dev, n_conv, w, logits_dev, prob_dev,
+                         static_cast<hipStream_t>(stream));
 }
 
 int64_t ww_events_workspace_bytes(int64_t n_windows) {
     if (n_windows < 0 || n_windows > (int64_t(1) << 40)) return fail(WW_EINVAL, "n_windows %lld out of range", (long long)n_windows);
-    return align256(n_windows * int64_t(sizeof(double)));
+    return up256(n_windows * int64_t(sizeof(double)));
 }
 
 int ww_events_sweep_f32(const float* prob_dev, const int64_t* seg_offsets_dev, int64_t n_segs, int64_t n_windows, int32_t smooth,
@@ -835,7 +826,7 @@ int ww_events_sweep_f32(const float* prob_dev, const int64_t* seg_offsets_dev, i
 int64_t ww_events_state_bytes(int32_t n_mics, int32_t smooth) {
     if (n_mics < 1 || n_mics > (1 << 20)) return fail(WW_EINVAL, "n_mics %d out of range", n_mics);
     if (smooth < 1 || smooth > 256) return fail(WW_EINVAL, "smooth %d: expected 1..256 windows", smooth);
-    return 16 * int64_t(n_mics) + align256(int64_t(n_mics) * smooth * int64_t(sizeof(float)));
+    return 16 * int64_t(n_mics) + up256(int64_t(n_mics) * smooth * int64_t(sizeof(float)));
 }
 
 int ww_events_step_f32(const float* prob_dev, int32_t n_mics, int32_t smooth, float threshold, int64_t refractory, void* state_dev,
@@ -947,7 +938,7 @@ int ww_train_backward_f32(const float* mel_dev, int64_t n, int32_t width, const 
 static int streamer_create(int32_t n_mics, int32_t hop_samples, int32_t n_samples, const StreamInput* in, const float* packed_dev,
                            int32_t n_conv, ww_stream_t stream, ww_streamer** out) {
     const int N = n_samples;
-    const int T = 1 + N / kHop;
+    const int T = frames_of(N);
     if (int rc = check_model(n_mics, T, packed_dev, n_conv)) return rc;
     if (!device_tables()) return WW_EHIP;   // also the gfx950 check; must precede graph capture
     ww_streamer* s = new (std::nothrow) ww_streamer();
@@ -956,7 +947,7 @@ static int streamer_create(int32_t n_mics, int32_t hop_samples, int32_t n_sample
     s->n_samples = N; s->n_frames = T;
     s->stream = static_cast<hipStream_t>(stream);
     if (in) { s->input = true; s->in = *in; }
-    const int64_t ws = carve(nullptr, n_mics, n_conv, T).total;
+    const int64_t ws = forward_workspace(nullptr, n_mics, T, n_conv).total;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->ring), sizeof(float) * int64_t(n_mics) * N);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->pos), 16);
     if (e == hipSuccess) e = hipMalloc(&s->workspace, size_t(ws));

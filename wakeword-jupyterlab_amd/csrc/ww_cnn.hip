@@ -1692,10 +1692,9 @@ static ColTiling col_tiling(int width, int n_conv) {
 }
 int cnn_wide_tiles(int width, int n_conv) { return col_tiling(width, n_conv).K; }
 
-static int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
 int64_t cnn_wide_scratch_bytes(int64_t n, int width, int n_conv) {
     const int64_t nv = n * col_tiling(width, n_conv).K;
-    return align256(nv * (n_conv == 3 ? 128 : 64) * int64_t(sizeof(float))) + cnn_scratch_bytes(nv, n_conv);
+    return up256(nv * (n_conv == 3 ? 128 : 64) * int64_t(sizeof(float))) + cnn_scratch_bytes(nv, n_conv);
 }
 
 // pooled[clip][c] = partial[clip K][c] + partial[clip K + 1][c] + ... in tile order: no atomics, the same bits for any batch or grid
@@ -1722,7 +1721,7 @@ int launch_cnn_pool_wide(const float* mel, int64_t n, int width, const float* pa
     const PackedLayout L = packed_layout(n_conv);
     if (int rc = opt_in_lds()) return rc;
     float* partial = static_cast<float*>(scratch);
-    char* rest = static_cast<char*>(scratch) + align256(nv64 * C * int64_t(sizeof(float)));
+    char* rest = static_cast<char*>(scratch) + up256(nv64 * C * int64_t(sizeof(float)));
     const int cus = device_cu_count();
     const int grid1 = nv < cus ? nv : cus;
     const int cmath = conv_math_mode();

@@ -21,6 +21,9 @@ int fail(int code, const char* fmt, ...);
                               __FILE__, __LINE__);                                           \
     } while (0)
 
+// THE rounding of every workspace region: sizes and offsets are multiples of 256 bytes
+inline int64_t up256(int64_t b) { return (b + 255) & ~int64_t(255); }
+
 // ---------------------------------------------------------------------------------------------
 // K1 tables (one image per device, built on the host in double precision)
 // ---------------------------------------------------------------------------------------------
@@ -132,7 +135,6 @@ int logmel_math_mode();
 void set_logmel_math_mode(int mode);
 // ---- augmentation host path (ww_augment.hip, ww_reverb.hip): the entry points check N and the pointers, the prepare functions check the
 // per-clip entries, both before any launch.  n_samples = 16000 (the 1 s entry points) or 4000 .. 16383 (the *_n, bg and rir ones).
-inline int64_t up256(int64_t b) { return (b + 255) & ~int64_t(255); }
 // Which record arrays a call carries.  A records buffer is [n] AugDev, then [n] BgDev with kAugBg, then [n] RirDev with kAugRir, back to
 // back; the workspace is the plain workspace followed by a 256-byte-rounded slot for each of the two in the same order.
 enum : unsigned { kAugBg = 1, kAugRir = 2 };
@@ -190,6 +192,7 @@ int launch_spec_draw(const SpecDraw& d, int64_t n, int T, int16_t* records, hipS
 int launch_spec_augment(const float* in, float* out, int64_t n, int T, const int16_t* records, const SpecDraw& d, int mode, float fill_value,
                         hipStream_t stream);
 int sync_timeouts(unsigned int* count);   // bounded LDS-counter waits that expired (must be 0)
+int64_t cnn_scratch_bytes(int64_t n, int n_conv);
 int launch_cnn_pool(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch,
                     float* pooled, hipStream_t stream);
 // K2 for 33..63 columns: column tiles of 32 run through the kernels above as virtual clips, each pooling the columns it owns (ww_cnn.hip)

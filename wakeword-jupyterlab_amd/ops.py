@@ -12,14 +12,18 @@ never synchronises and never falls back to a CPU implementation.
 from __future__ import annotations
 
 import ctypes as C
+import os
+import weakref
 
 import numpy as np
 import torch
 
 from . import _native as nat
-from .config import CLIP_SAMPLES, N_FRAMES, AudioConfig
+from .config import CLIP_SAMPLES, N_FRAMES, SPEC_MAX_MASKS, AudioConfig, SpecAugmentConfig, check_spec_augment_config
 
 N_MELS = AudioConfig.N_MELS
+MAX_FRAMES = 63                         # 1 + 32000 // 512
+MIN_CLIP_SAMPLES, MAX_CLIP_SAMPLES = 4000, 32000
 
 
 def _stream() -> C.c_void_p:
@@ -94,13 +98,47 @@ def n_conv_of_packed(packed: torch.Tensor) -> int:
 # ------------------------------------------------------------------------------------------------
 # raw launches (plain functions; the registered custom ops below wrap them)
 # ------------------------------------------------------------------------------------------------
-def _check_pcm(pcm: torch.Tensor) -> torch.Tensor:
+def frames_of(n_samples: int) -> int:
+    if not MIN_CLIP_SAMPLES <= int(n_samples) <= MAX_CLIP_SAMPLES:
+        raise NotImplementedError(f"clips of {n_samples} samples: the front-end takes {MIN_CLIP_SAMPLES}..{MAX_CLIP_SAMPLES} (0.25 s .. 2 s)")
+    return 1 + int(n_samples) // 512
+
+
+# The tensor checks, one each for pcm rows, mel images and pooled features: TypeError / ValueError / NotImplementedError before any device
+# call.  The public functions and the raw launches (`_*_impl`) share them; the compiled operators re-check with TORCH_CHECK -> RuntimeError.
+def _require_pcm(pcm, n_samples=None) -> None:
+    """pcm [B, 1..limit] float32 on the GPU; the limit is one second, or `n_samples` (0.25 s .. 2 s) for the *_frames functions."""
+    if n_samples is not None:
+        frames_of(n_samples)
     _require_cuda_f32(pcm, "pcm")
     if pcm.dim() != 2:
         raise ValueError(f"pcm: expected [B, samples], got {tuple(pcm.shape)}")
-    if pcm.shape[1] == 0 or pcm.shape[1] > CLIP_SAMPLES:
-        raise ValueError(f"pcm: {pcm.shape[1]} samples per clip; the front-end takes 1..{CLIP_SAMPLES} "
-                         "(crop longer clips on the host, pad_or_truncate wakeword_training_script.py:78-83)")
+    if pcm.shape[1] == 0 or pcm.shape[1] > (CLIP_SAMPLES if n_samples is None else n_samples):
+        raise ValueError(f"pcm: {pcm.shape[1]} samples per clip; " +
+                         (f"the front-end takes 1..{CLIP_SAMPLES} (crop longer clips on the host, pad_or_truncate "
+                          "wakeword_training_script.py:78-83)" if n_samples is None else
+                          f"this clip length takes 1..{n_samples} (crop longer clips on the host)"))
+
+
+def _require_x(x, max_frames: int = 32) -> None:
+    """x [B, 1, 80, 1..max_frames] float32 on the GPU: 32 frames for the conv kernels, MAX_FRAMES for their column-tiled form."""
+    _require_cuda_f32(x, "x")
+    if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != N_MELS:
+        raise ValueError(f"x: expected [B, 1, {N_MELS}, T], got {tuple(x.shape)}")
+    if not 1 <= x.shape[3] <= max_frames:
+        raise NotImplementedError(f"x: T = {x.shape[3]} frames; the conv kernels " +
+                                  ("are built for 1..32 (1 s clips give 32)" if max_frames == 32 else f"take 1..{max_frames} (2 s clips give 63)"))
+
+
+def _require_pooled(pooled, packed, n_conv) -> None:
+    _require_cuda_f32(pooled, "pooled")
+    _check_packed(packed, n_conv, pooled)
+    if pooled.dim() != 2 or pooled.shape[1] != c_last(n_conv):
+        raise ValueError(f"pooled: expected [B, {c_last(n_conv)}], got {tuple(pooled.shape)}")
+
+
+def _check_pcm(pcm: torch.Tensor) -> torch.Tensor:
+    _require_pcm(pcm)
     return _aligned_rows(pcm)
 
 
@@ -125,11 +163,7 @@ def _logmel_impl(pcm: torch.Tensor, normalize: bool = True) -> torch.Tensor:
 
 
 def _check_x(x: torch.Tensor) -> torch.Tensor:
-    _require_cuda_f32(x, "x")
-    if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != N_MELS:
-        raise ValueError(f"x: expected [B, 1, {N_MELS}, T], got {tuple(x.shape)}")
-    if not 1 <= x.shape[3] <= 32:
-        raise NotImplementedError(f"x: T = {x.shape[3]} frames; the conv kernels are built for 1..32 (1 s clips give 32)")
+    _require_x(x)
     return x.contiguous()
 
 
@@ -154,10 +188,7 @@ def _cnn_pool_impl(x: torch.Tensor, packed: torch.Tensor, n_conv: int) -> torch.
 
 
 def _lstm_fc_impl(pooled: torch.Tensor, packed: torch.Tensor, n_conv: int) -> torch.Tensor:
-    _require_cuda_f32(pooled, "pooled")
-    _check_packed(packed, n_conv, pooled)
-    if pooled.dim() != 2 or pooled.shape[1] != c_last(n_conv):
-        raise ValueError(f"pooled: expected [B, {c_last(n_conv)}], got {tuple(pooled.shape)}")
+    _require_pooled(pooled, packed, n_conv)
     pooled = pooled.contiguous()
     logits = torch.empty((pooled.shape[0], 2), device=pooled.device, dtype=torch.float32)
     with torch.cuda.device(pooled.device):
@@ -201,10 +232,8 @@ def _forward_pcm_impl(pcm: torch.Tensor, packed: torch.Tensor, n_conv: int, norm
 # functions above through torch.library; those stay as plain functions (`_logmel_impl` ...: tests and the raw launches of bench.py's legs).
 # The library does not link libwakeword_amd.so: it is handed the addresses of the fifteen C ABI functions it calls.
 # No fallback: without the compiled library the package does not import.
-import os as _os_ops
-
-TORCH_LIB_PATH = _os_ops.path.join(_os_ops.path.dirname(_os_ops.path.abspath(__file__)), "libwakeword_amd_torch.so")
-if not _os_ops.path.exists(TORCH_LIB_PATH):
+TORCH_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libwakeword_amd_torch.so")
+if not os.path.exists(TORCH_LIB_PATH):
     raise ImportError(f"{TORCH_LIB_PATH} is missing: build it with `make -C wakeword-jupyterlab_amd/csrc` "
                       "(or `python -c 'import __graft_entry__ as g; g.build()'`)")
 torch.ops.load_library(TORCH_LIB_PATH)
@@ -219,99 +248,55 @@ if _torch_lib.ww_torch_bind(_table, len(_TORCH_BIND_ORDER)) != 0:
     raise ImportError("libwakeword_amd_torch.so refused the C ABI table (rebuild: make -C wakeword-jupyterlab_amd/csrc)")
 
 
-# The public functions check argument types in Python first (TypeError / ValueError / NotImplementedError with the messages rounds 1-3
-# gave; the compiled kernels re-check with TORCH_CHECK -> RuntimeError), then dispatch: real tensors reach the HIP kernels, fake / meta
-# tensors the shape-only kernels.
-def _precheck_pcm(pcm) -> None:
-    _require_cuda_f32(pcm, "pcm")
-    if pcm.dim() != 2:
-        raise ValueError(f"pcm: expected [B, samples], got {tuple(pcm.shape)}")
-    if pcm.shape[1] == 0 or pcm.shape[1] > CLIP_SAMPLES:
-        raise ValueError(f"pcm: {pcm.shape[1]} samples per clip; the front-end takes 1..{CLIP_SAMPLES} "
-                         "(crop longer clips on the host, pad_or_truncate wakeword_training_script.py:78-83)")
-
-
-def _precheck_x(x) -> None:
-    _require_cuda_f32(x, "x")
-    if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != N_MELS:
-        raise ValueError(f"x: expected [B, 1, {N_MELS}, T], got {tuple(x.shape)}")
-    if not 1 <= x.shape[3] <= 32:
-        raise NotImplementedError(f"x: T = {x.shape[3]} frames; the conv kernels are built for 1..32 (1 s clips give 32)")
-
-
+# The public functions run the shared checks above first (the messages rounds 1-3 gave), then dispatch: real tensors reach the HIP kernels,
+# fake / meta tensors the shape-only kernels.
 def logmel(pcm: torch.Tensor, normalize: bool = True) -> torch.Tensor:
-    _precheck_pcm(pcm)
+    _require_pcm(pcm)
     return torch.ops.wakeword_amd.logmel(pcm, bool(normalize))
 
 
 def cnn_pool(x, packed, n_conv):
-    _precheck_x(x)
+    _require_x(x)
     _check_packed(packed, n_conv, x)
     return torch.ops.wakeword_amd.cnn_pool(x, packed, n_conv)
 
 
 def lstm_fc(pooled, packed, n_conv):
-    _require_cuda_f32(pooled, "pooled")
-    _check_packed(packed, n_conv, pooled)
-    if pooled.dim() != 2 or pooled.shape[1] != c_last(n_conv):
-        raise ValueError(f"pooled: expected [B, {c_last(n_conv)}], got {tuple(pooled.shape)}")
+    _require_pooled(pooled, packed, n_conv)
     return torch.ops.wakeword_amd.lstm_fc(pooled, packed, n_conv)
 
 
 def cnn_lstm_forward(x, packed, n_conv):
-    _precheck_x(x)
+    _require_x(x)
     _check_packed(packed, n_conv, x)
     return torch.ops.wakeword_amd.cnn_lstm_forward(x, packed, n_conv)
 
 
 def forward_pcm(pcm, packed, n_conv, normalize: bool = True):
-    _precheck_pcm(pcm)
+    _require_pcm(pcm)
     _check_packed(packed, n_conv, pcm)
     return torch.ops.wakeword_amd.forward_pcm(pcm, packed, n_conv, bool(normalize))
 
 
 # ---- clips of 0.25 s .. 2 s (inference): torch.ops.wakeword_amd.{logmel_frames,cnn_pool_wide,forward_pcm_frames} ----
-MAX_FRAMES = 63                         # 1 + 32000 // 512
-MIN_CLIP_SAMPLES, MAX_CLIP_SAMPLES = 4000, 32000
-
-
-def frames_of(n_samples: int) -> int:
-    if not MIN_CLIP_SAMPLES <= int(n_samples) <= MAX_CLIP_SAMPLES:
-        raise NotImplementedError(f"clips of {n_samples} samples: the front-end takes {MIN_CLIP_SAMPLES}..{MAX_CLIP_SAMPLES} (0.25 s .. 2 s)")
-    return 1 + int(n_samples) // 512
-
-
-def _precheck_pcm_frames(pcm, n_samples: int) -> None:
-    frames_of(n_samples)
-    _require_cuda_f32(pcm, "pcm")
-    if pcm.dim() != 2:
-        raise ValueError(f"pcm: expected [B, samples], got {tuple(pcm.shape)}")
-    if pcm.shape[1] == 0 or pcm.shape[1] > n_samples:
-        raise ValueError(f"pcm: {pcm.shape[1]} samples per clip; this clip length takes 1..{n_samples} (crop longer clips on the host)")
-
-
 def logmel_frames(pcm: torch.Tensor, n_samples: int, normalize: bool = True) -> torch.Tensor:
     """pcm [B, n <= n_samples] -> [B, 1, 80, T], T = 1 + n_samples // 512: the log-mel of clips zero-padded to n_samples.
     n_samples = 16000 gives exactly `logmel`'s result."""
-    _precheck_pcm_frames(pcm, n_samples)
+    _require_pcm(pcm, n_samples)
     return torch.ops.wakeword_amd.logmel_frames(pcm, int(n_samples), bool(normalize))
 
 
 def cnn_pool_wide(x, packed, n_conv):
     """x [B, 1, 80, T], 1 <= T <= 63 -> pooled features [B, C_last].  T <= 32 gives exactly `cnn_pool`'s result; wider images run the
     32-wide conv kernels over overlapping column tiles (csrc/ww_cnn.hip, ColTiling)."""
-    _require_cuda_f32(x, "x")
-    if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != N_MELS:
-        raise ValueError(f"x: expected [B, 1, {N_MELS}, T], got {tuple(x.shape)}")
-    if not 1 <= x.shape[3] <= MAX_FRAMES:
-        raise NotImplementedError(f"x: T = {x.shape[3]} frames; the conv kernels take 1..{MAX_FRAMES} (2 s clips give 63)")
+    _require_x(x, MAX_FRAMES)
     _check_packed(packed, n_conv, x)
     return torch.ops.wakeword_amd.cnn_pool_wide(x, packed, n_conv)
 
 
 def forward_pcm_frames(pcm, packed, n_conv, n_samples: int, normalize: bool = True):
     """pcm [B, n <= n_samples] -> logits [B, 2]: logmel_frames -> cnn_pool_wide -> lstm_fc in one native call."""
-    _precheck_pcm_frames(pcm, n_samples)
+    _require_pcm(pcm, n_samples)
     _check_packed(packed, n_conv, pcm)
     return torch.ops.wakeword_amd.forward_pcm_frames(pcm, packed, n_conv, int(n_samples), bool(normalize))
 
@@ -338,6 +323,39 @@ def _train_params_struct(params, n_conv):
     return tp
 
 
+def train_grads_struct(grads: dict, n_conv: int):
+    """nat.TrainGrads over gradient tensors keyed by parameter name.  The struct has one bias gradient per LSTM layer, filed under
+    bias_ih (d/d bias_hh is the same tensor), and none for weight_hh (h0 = 0 makes it exactly zero): those keys are not read."""
+    tg = nat.TrainGrads()
+    for i in range(n_conv):
+        tg.conv_weight[i], tg.conv_bias[i] = grads[f"conv{i + 1}.weight"].data_ptr(), grads[f"conv{i + 1}.bias"].data_ptr()
+    for layer in range(2):
+        tg.lstm_weight_ih[layer], tg.lstm_bias[layer] = grads[f"lstm.weight_ih_l{layer}"].data_ptr(), grads[f"lstm.bias_ih_l{layer}"].data_ptr()
+    tg.fc_weight, tg.fc_bias = grads["fc.weight"].data_ptr(), grads["fc.bias"].data_ptr()
+    return tg
+
+
+def train_workspace_bytes(B: int, n_conv: int, math: int) -> int:
+    """ww_train_workspace_bytes; `math` is a resolved WW_TRAIN_MATH_* value (ww_get_train_math(), read ONCE per step and handed to the
+    query, the forward and the backward alike)."""
+    return nat.check(nat.lib.ww_train_workspace_bytes(B, n_conv, math))
+
+
+def train_forward_into(x, tp, p_lstm, p_fc, seed, math, ws, logits) -> None:
+    """ww_train_forward_f32 on checked arguments: x as _check_x returns it, `tp` from _train_params_struct, `ws` uint8 of at least
+    train_workspace_bytes(B, n_conv, math), logits float32 [>= B, 2].  One native call on the current stream of the CURRENT device,
+    which the caller has made x's (a guard per launch showed in the trainer's step at B = 16); allocates nothing."""
+    nat.check(nat.lib.ww_train_forward_f32(_ptr(x), x.shape[0], x.shape[3], C.byref(tp), float(p_lstm), float(p_fc),
+                                           int(seed) & (2 ** 64 - 1), math, _ptr(ws), ws.numel(), _ptr(logits), _stream()))
+
+
+def train_backward_into(x, tp, dlogits, math, ws, tg) -> None:
+    """ww_train_backward_f32 on the x, `tp`, `math` and `ws` of the forward it follows, dlogits float32 [>= B, 2] contiguous and `tg` from
+    train_grads_struct.  One native call, x's device current as for train_forward_into; allocates nothing."""
+    nat.check(nat.lib.ww_train_backward_f32(_ptr(x), x.shape[0], x.shape[3], C.byref(tp), _ptr(dlogits), math, _ptr(ws), ws.numel(),
+                                            C.byref(tg), _stream()))
+
+
 class _TrainStep(torch.autograd.Function):
     """logits = model(x) in train mode, with d loss / d parameters from the HIP backward kernels.  `x` gets no gradient (the
     reference never asks for one)."""
@@ -356,20 +374,17 @@ class _TrainStep(torch.autograd.Function):
         params = tuple(p.detach().contiguous() for p in params)
         for p in params:
             _require_cuda_f32(p, "parameter")
-        B, T = x.shape[0], x.shape[3]
+        B = x.shape[0]
         if B == 0:
             raise ValueError("empty training batch")
         logits = torch.empty((B, 2), device=x.device, dtype=torch.float32)
         math = nat.lib.ww_get_train_math()                  # resolved ONCE: query, forward and backward of this step all get this value
+        ws = torch.empty(train_workspace_bytes(B, n_conv, math), device=x.device, dtype=torch.uint8)
         with torch.cuda.device(x.device):
-            ws = torch.empty(nat.check(nat.lib.ww_train_workspace_bytes(B, n_conv, math)), device=x.device, dtype=torch.uint8)
-            tp = _train_params_struct(params, n_conv)
-            nat.check(nat.lib.ww_train_forward_f32(_ptr(x), B, T, C.byref(tp), float(p_lstm), float(p_fc), int(seed) & (2 ** 64 - 1),
-                                                   math, _ptr(ws), ws.numel(), _ptr(logits), _stream()))
+            train_forward_into(x, _train_params_struct(params, n_conv), p_lstm, p_fc, seed, math, ws, logits)
         ctx.save_for_backward(x, ws, *params)
         ctx.n_conv = n_conv
         ctx.train_math = math
-        import weakref
         _TrainStep._last_ws_ref, _TrainStep.last_n_conv, _TrainStep.last_n = weakref.ref(ws), n_conv, B
         _TrainStep._last_ws_keep = ws if _TrainStep.keep else None
         return logits
@@ -378,25 +393,15 @@ class _TrainStep(torch.autograd.Function):
     def backward(ctx, dlogits):
         x, ws, *params = ctx.saved_tensors
         n_conv = ctx.n_conv
-        B, T = x.shape[0], x.shape[3]
         dlogits = dlogits.contiguous().float()
-        grads = [torch.empty_like(p) for p in params]
-        o = 2 * n_conv                      # index of lstm.weight_ih_l0
-        grads[o + 1].zero_()                # weight_hh: h0 = 0, the gradient is exactly zero
-        grads[o + 5].zero_()
-        tg = nat.TrainGrads()
-        for i in range(n_conv):
-            tg.conv_weight[i], tg.conv_bias[i] = grads[2 * i].data_ptr(), grads[2 * i + 1].data_ptr()
-        tg.lstm_weight_ih[0], tg.lstm_bias[0] = grads[o].data_ptr(), grads[o + 2].data_ptr()
-        tg.lstm_weight_ih[1], tg.lstm_bias[1] = grads[o + 4].data_ptr(), grads[o + 6].data_ptr()
-        tg.fc_weight, tg.fc_bias = grads[o + 8].data_ptr(), grads[o + 9].data_ptr()
+        grads = {k: torch.empty_like(p) for k, p in zip(_train_keys(n_conv), params)}
+        for layer in range(2):
+            grads[f"lstm.weight_hh_l{layer}"].zero_()       # h0 = 0: the gradient is exactly zero
         with torch.cuda.device(x.device):
-            tp = _train_params_struct(params, n_conv)
-            nat.check(nat.lib.ww_train_backward_f32(_ptr(x), B, T, C.byref(tp), _ptr(dlogits), ctx.train_math, _ptr(ws), ws.numel(),
-                                                    C.byref(tg), _stream()))
-        grads[o + 3].copy_(grads[o + 2])    # d/d bias_hh == d/d bias_ih
-        grads[o + 7].copy_(grads[o + 6])
-        return (None, None, None, None, None, *grads)
+            train_backward_into(x, _train_params_struct(params, n_conv), dlogits, ctx.train_math, ws, train_grads_struct(grads, n_conv))
+        for layer in range(2):
+            grads[f"lstm.bias_hh_l{layer}"].copy_(grads[f"lstm.bias_ih_l{layer}"])       # d/d bias_hh == d/d bias_ih
+        return (None, None, None, None, None, *grads.values())
 
 
 def train_forward(x, named_params: dict, n_conv: int, p_lstm: float, p_fc: float, seed: int):
@@ -484,65 +489,63 @@ def train_last_bit_images():
 
 
 CONV_MATH = {"f32": 0, "f16x3": 1, "f16x3d": 2}
+LOGMEL_MATH = {"f32": 0, "f64": 1, "auto": 2}
+TRAIN_MATH = {"f32": 0, "f16x3": 1}
+_MATH = {"conv": ("conv math", CONV_MATH), "logmel": ("log-mel math", LOGMEL_MATH), "train": ("train math", TRAIN_MATH)}   # ww_{set,get}_<kind>_math
+
+
+def _set_math(kind: str, mode, thread: bool = False) -> None:
+    what, table = _MATH[kind]
+    if mode not in table and not (thread and mode is None):
+        raise ValueError(f"{what} {mode!r}: expected one of {sorted(table)}" + (" or None" if thread else ""))
+    nat.check(getattr(nat.lib, f"ww_set_{kind}_math" + ("_thread" if thread else ""))(-1 if mode is None else table[mode]))
+
+
+def _get_math(kind: str) -> str:
+    return {v: k for k, v in _MATH[kind][1].items()}[getattr(nat.lib, f"ww_get_{kind}_math")()]
 
 
 def set_conv_math(mode: str) -> None:
     """Arithmetic of the conv / LSTM-gate GEMMs, process-wide: 'f32' (exact fp32 MFMA), 'f16x3' (each fp32 operand as two f16
     halves, three f16 MFMAs per product block, fp32 accumulate; ~2^-21 relative error, 3/16 the MFMA cycles; the 2-conv model's
     conv2 as a 1-D Winograd F(2,3)) or 'f16x3d' (f16x3 with every convolution in its direct form)."""
-    if mode not in CONV_MATH:
-        raise ValueError(f"conv math {mode!r}: expected one of {sorted(CONV_MATH)}")
-    nat.check(nat.lib.ww_set_conv_math(CONV_MATH[mode]))
+    _set_math("conv", mode)
 
 
 def set_conv_math_thread(mode) -> None:
     """Override the conv arithmetic for launches issued by the CALLING THREAD only (None clears it): a streamer thread and a batch
     job can then use different arithmetics safely."""
-    if mode is not None and mode not in CONV_MATH:
-        raise ValueError(f"conv math {mode!r}: expected one of {sorted(CONV_MATH)} or None")
-    nat.check(nat.lib.ww_set_conv_math_thread(-1 if mode is None else CONV_MATH[mode]))
+    _set_math("conv", mode, thread=True)
 
 
 def get_conv_math() -> str:
-    return {v: k for k, v in CONV_MATH.items()}[nat.lib.ww_get_conv_math()]
-
-
-LOGMEL_MATH = {"f32": 0, "f64": 1, "auto": 2}
+    return _get_math("conv")
 
 
 def set_logmel_math(mode: str) -> None:
     """Arithmetic of the log-mel front end, process-wide: 'f32' (float32 FFT), 'f64' (float64 window product / FFT / split, what
     the reference's numpy.fft.rfft computes) or 'auto' (default: float32, and the clips with a live mel band on the float32
     FFT's rounding floor are redone in float64)."""
-    if mode not in LOGMEL_MATH:
-        raise ValueError(f"log-mel math {mode!r}: expected one of {sorted(LOGMEL_MATH)}")
-    nat.check(nat.lib.ww_set_logmel_math(LOGMEL_MATH[mode]))
+    _set_math("logmel", mode)
 
 
 def set_logmel_math_thread(mode) -> None:
     """Per-thread override of the log-mel arithmetic (None clears it); see set_conv_math_thread."""
-    if mode is not None and mode not in LOGMEL_MATH:
-        raise ValueError(f"log-mel math {mode!r}: expected one of {sorted(LOGMEL_MATH)} or None")
-    nat.check(nat.lib.ww_set_logmel_math_thread(-1 if mode is None else LOGMEL_MATH[mode]))
+    _set_math("logmel", mode, thread=True)
 
 
 def get_logmel_math() -> str:
-    return {v: k for k, v in LOGMEL_MATH.items()}[nat.lib.ww_get_logmel_math()]
-
-
-TRAIN_MATH = {"f32": 0, "f16x3": 1}
+    return _get_math("logmel")
 
 
 def set_train_math(mode: str) -> None:
     """Arithmetic of the training step's conv kernels, process-wide: 'f16x3' (default: split precision on the f16 matrix
     instructions where a kernel exists -- SimpleWakewordModel's conv2 backward) or 'f32' (exact fp32 matrix instructions)."""
-    if mode not in TRAIN_MATH:
-        raise ValueError(f"train math {mode!r}: expected one of {sorted(TRAIN_MATH)}")
-    nat.check(nat.lib.ww_set_train_math(TRAIN_MATH[mode]))
+    _set_math("train", mode)
 
 
 def get_train_math() -> str:
-    return {v: k for k, v in TRAIN_MATH.items()}[nat.lib.ww_get_train_math()]
+    return _get_math("train")
 
 
 def init() -> None:
@@ -550,21 +553,27 @@ def init() -> None:
     nat.check(nat.lib.ww_init())
 
 
-import os as _os  # noqa: E402
-
-if _os.environ.get("WW_CONV_MATH"):
-    set_conv_math(_os.environ["WW_CONV_MATH"])
-if _os.environ.get("WW_LOGMEL_MATH"):
-    set_logmel_math(_os.environ["WW_LOGMEL_MATH"])
+if os.environ.get("WW_CONV_MATH"):
+    set_conv_math(os.environ["WW_CONV_MATH"])
+if os.environ.get("WW_LOGMEL_MATH"):
+    set_logmel_math(os.environ["WW_LOGMEL_MATH"])
 
 
 # ---- KA: augmentation ------------------------------------------------------------------
 AUG_MAX_SAMPLES = 16383                 # T = 1 + N // 512 <= 32 frames: the clip lengths training takes (4000 .. 16383 samples)
 
 
+def _require_clips(pcm, name: str, max_samples: int, min_rows: int = 0) -> None:
+    """pcm float32 [B >= min_rows, N] on the GPU, N in MIN_CLIP_SAMPLES..max_samples: what `name`, an augmentation function, takes."""
+    if pcm.device.type != "cuda":
+        raise RuntimeError(f"{name}: pcm must live on the MI355X (no CPU fallback)")
+    if pcm.dtype != torch.float32 or pcm.dim() != 2 or not MIN_CLIP_SAMPLES <= pcm.shape[1] <= max_samples or pcm.shape[0] < min_rows:
+        raise ValueError(f"{name}: expected float32 [{'B' if min_rows == 0 else f'B >= {min_rows}'}, N], N in {MIN_CLIP_SAMPLES}..{max_samples}, "
+                         f"got {pcm.dtype} {tuple(pcm.shape)}")
+
+
 def _plans_array(plans, B):
     """A ctypes array of _native.AugmentPlan as it is, a list of dict plans converted to one."""
-    import ctypes as C
     if isinstance(plans, C.Array):
         if len(plans) < B:
             raise ValueError(f"augment: {len(plans)} plans for {B} clips")
@@ -595,11 +604,7 @@ def augment(pcm: torch.Tensor, plans, bank=None, rirs=None) -> torch.Tensor:
     exactly what they give without a bank.
     With a reverb.ImpulseResponseBank (`rirs`), dict plans that carry `rir` get that room impulse response after the stretch and before
     the background; clips without the key, and a batch where no plan has it, give exactly what they give without."""
-    import ctypes as C
-    if pcm.device.type != "cuda":
-        raise RuntimeError("augment: pcm must live on the MI355X (no CPU fallback)")
-    if pcm.dtype != torch.float32 or pcm.dim() != 2 or not MIN_CLIP_SAMPLES <= pcm.shape[1] <= AUG_MAX_SAMPLES:
-        raise ValueError(f"augment: expected float32 [B, N], N in {MIN_CLIP_SAMPLES}..{AUG_MAX_SAMPLES}, got {pcm.dtype} {tuple(pcm.shape)}")
+    _require_clips(pcm, "augment", AUG_MAX_SAMPLES)
     N = int(pcm.shape[1])
     pcm = pcm.contiguous() if N == CLIP_SAMPLES else _aligned_rows(pcm)
     B = pcm.shape[0]
@@ -652,13 +657,7 @@ def augment_stages(pcm: torch.Tensor, plans, poison: bool = False) -> dict:
                    (stretch batch), the rolled input (neither)
         "out"      [B, N] the call's result (the stage plus the plans' Gaussian noise)
     `poison` fills the workspace with float32 NaN before the call: whatever a kernel reads without having written it shows in the output."""
-    import ctypes as C
-
-    import numpy as np
-    if pcm.device.type != "cuda":
-        raise RuntimeError("augment_stages: pcm must live on the MI355X (no CPU fallback)")
-    if pcm.dtype != torch.float32 or pcm.dim() != 2 or not MIN_CLIP_SAMPLES <= pcm.shape[1] <= AUG_MAX_SAMPLES or pcm.shape[0] < 1:
-        raise ValueError(f"augment_stages: expected float32 [B >= 1, N], N in {MIN_CLIP_SAMPLES}..{AUG_MAX_SAMPLES}, got {pcm.dtype} {tuple(pcm.shape)}")
+    _require_clips(pcm, "augment_stages", AUG_MAX_SAMPLES, min_rows=1)
     if not isinstance(plans, C.Array) and any(k in p for p in plans for k in ("bg_file", "rir")):
         raise ValueError("augment_stages: background and reverb are not staged")
     N = int(pcm.shape[1])
@@ -723,12 +722,7 @@ def mix_background(pcm: torch.Tensor, bank, files, starts, snr_db) -> torch.Tens
     """The background mix alone (ww_mix_background_f32): pcm [B, N] float32 on the GPU, N in 4000..32000 (every inference length) ->
     [B, N] with clip i + bank file `files[i]` from sample `starts[i]` (wrapping around the file) at `snr_db[i]` dB (a scalar applies to
     every clip).  A negative file index leaves that clip as it is.  For noisy evaluation sets at a fixed SNR."""
-    import ctypes as C
-    if pcm.device.type != "cuda":
-        raise RuntimeError("mix_background: pcm must live on the MI355X (no CPU fallback)")
-    if pcm.dtype != torch.float32 or pcm.dim() != 2 or not MIN_CLIP_SAMPLES <= pcm.shape[1] <= MAX_CLIP_SAMPLES:
-        raise ValueError(f"mix_background: expected float32 [B, N], N in {MIN_CLIP_SAMPLES}..{MAX_CLIP_SAMPLES}, got {pcm.dtype} "
-                         f"{tuple(pcm.shape)}")
+    _require_clips(pcm, "mix_background", MAX_CLIP_SAMPLES)
     _check_bank(bank, pcm.device)
     B, N = int(pcm.shape[0]), int(pcm.shape[1])
     if pcm.stride(1) != 1:
@@ -777,10 +771,7 @@ def reverb(pcm: torch.Tensor, rirs, index) -> torch.Tensor:
     """The reverb alone (ww_reverb_f32): pcm [B, N] float32 on the GPU, N in 4000..32000 (every inference length) -> [B, N] with clip i
     convolved with bank RIR `index[i]` (a scalar applies to every clip), advanced by its direct-path delay and rescaled to the clip's
     energy.  A negative index leaves that clip as it is.  For reverberant evaluation sets."""
-    if pcm.device.type != "cuda":
-        raise RuntimeError("reverb: pcm must live on the MI355X (no CPU fallback)")
-    if pcm.dtype != torch.float32 or pcm.dim() != 2 or not MIN_CLIP_SAMPLES <= pcm.shape[1] <= MAX_CLIP_SAMPLES:
-        raise ValueError(f"reverb: expected float32 [B, N], N in {MIN_CLIP_SAMPLES}..{MAX_CLIP_SAMPLES}, got {pcm.dtype} {tuple(pcm.shape)}")
+    _require_clips(pcm, "reverb", MAX_CLIP_SAMPLES)
     _check_rirs(rirs, pcm.device)
     B, N = int(pcm.shape[0]), int(pcm.shape[1])
     if pcm.stride(1) != 1:
@@ -1122,9 +1113,6 @@ def grad_norm(grads, max_norm: float):
 
 
 # ---- SpecAugment: time and frequency masks on log-mel batches (csrc/ww_specaug.hip) ----------------------
-from .config import SPEC_MAX_MASKS, SpecAugmentConfig, check_spec_augment_config  # noqa: E402
-
-
 def _spec_args(config, T: int):
     """(prob, n_freq, freq_max, n_time, time_max, fill_mode, fill_value) as ww_spec_augment_f32 takes them, for images of T frames."""
     check_spec_augment_config(config)

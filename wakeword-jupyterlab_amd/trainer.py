@@ -22,7 +22,6 @@ backward.
 """
 from __future__ import annotations
 
-import ctypes as C
 import warnings
 
 import torch
@@ -138,14 +137,7 @@ class WakewordTrainer:
         for k, p in zip(self._keys, self._params):
             if k.startswith("lstm.bias_hh"):
                 p.grad = self._grads[k.replace("bias_hh", "bias_ih")]
-        g = self._grads
-        tg = nat.TrainGrads()
-        for i in range(self._n_conv):
-            tg.conv_weight[i], tg.conv_bias[i] = g[f"conv{i + 1}.weight"].data_ptr(), g[f"conv{i + 1}.bias"].data_ptr()
-        for layer in range(2):
-            tg.lstm_weight_ih[layer], tg.lstm_bias[layer] = g[f"lstm.weight_ih_l{layer}"].data_ptr(), g[f"lstm.bias_ih_l{layer}"].data_ptr()
-        tg.fc_weight, tg.fc_bias = g["fc.weight"].data_ptr(), g["fc.bias"].data_ptr()
-        self._tg = tg
+        self._tg = ops.train_grads_struct(self._grads, self._n_conv)
         self._tp = ops._train_params_struct(self._params, self._n_conv)
         self._tp_key = tuple(p.data_ptr() for p in self._params)
 
@@ -201,7 +193,7 @@ class WakewordTrainer:
             raise NotImplementedError(f"training at T = {data.shape[3]} frames is not supported yet: the training kernels take 1..32 "
                                       "(clips of up to 1 s); clips of up to 2 s run in eval mode only")
         x = ops._check_x(data)
-        B, T = x.shape[0], x.shape[3]
+        B = x.shape[0]
         if B == 0:
             raise ValueError("empty training batch")
         y = self._target(target, B)
@@ -211,7 +203,7 @@ class WakewordTrainer:
         # the dropout seed exactly as _CnnLstm.forward draws it: one randint from torch's CPU generator
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         math = nat.lib.ww_get_train_math()                   # resolved once: query, forward and backward of this step get this value
-        need = nat.check(nat.lib.ww_train_workspace_bytes(B, self._n_conv, math))
+        need = ops.train_workspace_bytes(B, self._n_conv, math)
         with torch.cuda.device(self._dev):
             if self._ws is None or self._ws.numel() < need:
                 self._ws = None                              # release before growing
@@ -220,24 +212,15 @@ class WakewordTrainer:
                 self._logits = torch.empty((B, 2), device=self._dev, dtype=torch.float32)
                 self._dlogits = torch.empty((B, 2), device=self._dev, dtype=torch.float32)
                 self._cap = B
-            stream = ops._stream()
-            m = self.model
-            nat.check(nat.lib.ww_train_forward_f32(ops._ptr(x), B, T, C.byref(self._tp), float(m.lstm.dropout), float(m.dropout.p),
-                                                   seed & (2 ** 64 - 1), math, ops._ptr(self._ws), self._ws.numel(), ops._ptr(self._logits),
-                                                   stream))
-            if self._loss_opts is None:
-                nat.check(nat.lib.ww_ce_loss_f32(ops._ptr(self._logits), ops._ptr(y), B, ops._ptr(self._dlogits), ops._ptr(self.last_loss),
-                                                 ops._ptr(self.train_stats), stream))
-            else:
-                nat.check(nat.lib.ww_ce_loss_ex_f32(ops._ptr(self._logits), ops._ptr(y), B, C.byref(self._loss_opts), ops._ptr(self._dlogits),
-                                                    ops._ptr(self.last_loss), ops._ptr(self.train_stats), stream))
-            nat.check(nat.lib.ww_train_backward_f32(ops._ptr(x), B, T, C.byref(self._tp), ops._ptr(self._dlogits), math, ops._ptr(self._ws),
-                                                    self._ws.numel(), C.byref(self._tg), stream))
+            logits, m = self._logits if B == self._cap else self._logits[:B], self.model         # the buffers may hold more rows
+            ops.train_forward_into(x, self._tp, m.lstm.dropout, m.dropout.p, seed, math, self._ws, logits)
+            ops.ce_loss_into(logits, y, self._dlogits, self.last_loss, self.train_stats, opts=self._loss_opts)
+            ops.train_backward_into(x, self._tp, self._dlogits, math, self._ws, self._tg)
             if self.max_grad_norm is not None:
                 self._norm_step()
         self.optimizer.step(grad_scale=self._scale if self.max_grad_norm is not None else None)
         if entries is not None and self.ledger is not None:
-            self.ledger.update(entries, self._logits[:B], y)
+            self.ledger.update(entries, logits, y)
         return self.last_loss
 
     @property
