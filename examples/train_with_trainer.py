@@ -9,10 +9,11 @@ of the test set -- from counters kept on the device (section 3j) -- and, beyond 
     PYTHONPATH=. python examples/train_with_trainer.py [--epochs 10] [--data DIR] [--duration 1.0] [--background DIR] [--max-grad-norm 1.0]
                                                         [--spec-augment] [--monitor val_acc|val_f1|val_auc]
                                                         [--class-weights balanced|W0,W1] [--label-smoothing E] [--focal-gamma G]
-                                                        [--positive-fraction F]
+                                                        [--positive-fraction F] [--mixup]
 
 Imbalanced data (section 3k): `--class-weights balanced` weighs the classes by the training split's counts, `--label-smoothing` and
 `--focal-gamma` choose the loss of the fused step, `--positive-fraction 0.5` makes every training epoch half wake-word items.
+`--mixup` (section 3n) mixes rows of every training batch on the GPU and trains on the class probabilities that result.
 """
 import argparse
 import glob
@@ -23,8 +24,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from train_from_files import split  # noqa: E402
-from wakeword_jupyterlab_amd import (AudioConfig, AudioProcessor, DataLoader, FocalLoss, SpecAugmentConfig, TrainingConfig,  # noqa: E402
-                                     WakewordDataset, WakewordModel, WakewordTrainer, balanced_class_weights)
+from wakeword_jupyterlab_amd import (AudioConfig, AudioProcessor, DataLoader, FocalLoss, MixupConfig, SpecAugmentConfig,  # noqa: E402
+                                     TrainingConfig, WakewordDataset, WakewordModel, WakewordTrainer, balanced_class_weights)
 from wakeword_jupyterlab_amd.synth import create_sample_data  # noqa: E402
 
 
@@ -54,6 +55,8 @@ def main():
     ap.add_argument("--background", default=None, help="directory of background noise files (WAV / FLAC) mixed into the training clips")
     ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm after the backward (default: off)")
     ap.add_argument("--spec-augment", action="store_true", help="mask blocks of mel bins and frames of every training batch (SpecAugment)")
+    ap.add_argument("--mixup", action="store_true",
+                    help="mix rows of every training batch and train on class probabilities (mixup; excludes --focal-gamma)")
     ap.add_argument("--monitor", default="val_acc", choices=("val_acc", "val_f1", "val_auc"),
                     help="what the scheduler, the best checkpoint and early stopping follow (default: the reference's validation accuracy)")
     ap.add_argument("--class-weights", default=None, metavar="balanced|W0,W1",
@@ -80,6 +83,10 @@ def main():
         processor.set_background_noise(a.background)
     if a.spec_augment:
         processor.set_spec_augment(SpecAugmentConfig)                             # training loader only: the others run with augment=False
+    if a.mixup:
+        if a.focal_gamma is not None:
+            raise SystemExit("--mixup and --focal-gamma exclude one another: the focal loss takes integer labels")
+        processor.set_mixup(MixupConfig)                                          # training loader only, after SpecAugment
     model = WakewordModel(audio_config=audio_config).to(device)
     print(f"Parameters: {sum(p.numel() for p in model.parameters()):,}")
     bank = WakewordDataset(w_tr, n_tr, processor, augment=True).cache()           # every training file decoded once, onto the GPU

@@ -784,6 +784,40 @@ typedef struct ww_loss_opts {
 } ww_loss_opts;             /* 48 bytes, HOST memory */
 WW_API int ww_ce_loss_ex_f32(const float* logits_dev, const int64_t* labels_dev, int64_t n, const ww_loss_opts* opts_host, float* dlogits_dev,
                              float* loss_dev, ww_loss_stats* stats_dev, ww_stream_t stream);
+/* ww_ce_loss_soft_f32: cross-entropy on CLASS PROBABILITIES -- torch's F.cross_entropy(z, t, weight=w,
+ * label_smoothing=eps, reduction=) with a floating-point target t [n][2]: what mixup, distillation and soft relabelling need.
+ * ww_ce_loss_ex_f32's kernel shape: one launch, one workgroup, no atomics, every sum in one fixed order, the options by value in the
+ * kernel arguments (opts_host NULL: unit weights, eps = 0, the mean).  Per clip in float64, with p = softmax(z) and lse as above:
+ *   t'_c = (1 - eps) t_c + eps / 2;   l = w0 t'_0 (lse - z0) + w1 t'_1 (lse - z1);   dl/dz_k = p_k (w0 t'_0 + w1 t'_1) - w_k t'_k
+ *   a row counts iff both its targets are finite and >= 0 (they need not sum to 1); any other row adds nothing to the loss or the
+ *   denominator, its dlogits are exactly zero, and it is counted in bad_labels.
+ *   WW_REDUCE_MEAN divides the sum of l and every gradient by the NUMBER of counted rows, as torch divides by n -- deliberately NOT
+ *   the weighted denominator W of the integer-label form above: with class weights the two means differ, as they do in torch.
+ *   WW_REDUCE_SUM divides by 1.  A denominator of 0 under the mean: a NaN loss and an all-zero gradient, as in ww_ce_loss_ex_f32.
+ * Prediction, total, batches, nonfinite and loss_sum follow ww_ce_loss_f32; a counted clip is `correct` iff prediction == (t1 > t0):
+ * a tie in the target gives class 0, the prediction's rule.  With one-hot rows, unit weights and eps = 0 the loss, the gradient and the
+ * record have the bits of ww_ce_loss_f32 on the corresponding labels, under both reductions.
+ * logits_dev, targets_dev [n][2] float32; pointers and n as for ww_ce_loss_f32 (4-byte alignment, stats 8-byte; dlogits / loss / stats
+ * may be NULL).  Checked before any HIP call (WW_EINVAL naming the field): the range checks of ww_ce_loss_ex_f32, kind != WW_LOSS_CE,
+ * ignore_index != -100 (torch refuses one for floating-point targets). */
+WW_API int ww_ce_loss_soft_f32(const float* logits_dev, const float* targets_dev, int64_t n, const ww_loss_opts* opts_host, float* dlogits_dev,
+                               float* loss_dev, ww_loss_stats* stats_dev, ww_stream_t stream);
+/* ww_mixup_f32: mixup on a log-mel batch, with the class-probability targets ww_ce_loss_soft_f32 takes.
+ * Out of place (overlapping mel / out ranges: WW_EINVAL); one launch over B x chunks of a row; no atomics.  Per row i, with
+ * p = partner_dev[i], lam = lambda_dev[i] and oml = 1.0f - lam (ONE float32 subtraction):
+ *   lam == 1.0f, or p outside [0, B)   out[i] is a bit-exact copy of mel[i]; row p is not read
+ *   otherwise                          out[i] = fmaf(lam, mel[i], oml * mel[p]) element by element, the product rounded once
+ *   targets_dev[i]                     (NaN, NaN) when labels[i] lies outside {0, 1}, when p lies outside [0, B) (whatever lam is), or
+ *                                      when the row is mixed and labels[p] lies outside {0, 1}: the loss then counts a bad label;
+ *                                      else the exact one-hot of labels[i] when the row is not mixed or labels[p] == labels[i];
+ *                                      else t[labels[i]] = lam, t[labels[p]] = oml.
+ * The kernel clamps nothing and forms no address from an unchecked index: p is compared against the B ARGUMENT before mel[p] or
+ * labels[p] is touched.  mel_dev, out_dev [B][80][T] float32 (16-byte accesses when both are 16-byte aligned, else one float at a
+ * time: the same bits), labels_dev [B] int64, partner_dev [B] int32, lambda_dev [B] float32, targets_dev [B][2] float32.
+ * Checked before any HIP call (WW_EINVAL naming the field): B in 1..2^30, T in 1..WW_MAX_FRAMES, null pointers, 4-byte (labels:
+ * 8-byte) alignment, overlap. */
+WW_API int ww_mixup_f32(const float* mel_dev, float* out_dev, int64_t B, int32_t T, const int64_t* labels_dev, const int32_t* partner_dev,
+                        const float* lambda_dev, float* targets_dev, ww_stream_t stream);
 /* ww_adam_step_f32: one launch of torch's single-tensor Adam (no amsgrad, no maximize) over up to WW_ADAM_MAX_TENSORS tensors.  The table
  * is read on the HOST and travels in the kernel arguments: nothing is uploaded.
  *   g' = g * scale + weight_decay * p;  m += (g' - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g'^2;

@@ -279,6 +279,8 @@ PROTOTYPES = {
                                         C.POINTER(TrainGrads), C.c_void_p]),
     "ww_ce_loss_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_ce_loss_ex_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(LossOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_ce_loss_soft_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(LossOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_mixup_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_adam_step_f32": (C.c_int, [C.POINTER(AdamTensor), C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
                                    C.c_void_p, C.c_void_p]),
     "ww_grad_norm_workspace_bytes": (C.c_int64, [C.POINTER(AdamTensor), C.c_int64]),

@@ -17,6 +17,7 @@ T <= 32 (DURATION 0.25 .. 1.0, N = 4000 .. 16000 samples), and refuses longer cl
   set_background_noise(paths) -> background noise at a random SNR, mixed in after the stretch (background.py; not in the reference)
   set_room_impulse_responses(paths) -> reverberation with a random room impulse response, before the background (reverb.py; idem)
   set_spec_augment(config)    -> SpecAugment: blocks of mel bins and of frames masked on the log-mel batch, after K1 (idem)
+  set_mixup(config)           -> mixup: rows of the log-mel batch mixed with a partner row, the targets with them, last of all (idem)
 `load_audio` / `process_audio_file` read the file with the library's native reader (csrc/ww_files.cpp) and decode, mix down and
 resample it on the GPU (kernel K0: scipy.signal.resample_poly's Kaiser design -- NOT librosa's soxr resampler, an absent third-party
 library: parity unpinned) -- the same code path as the batched loaders, one file at a time.  PCM / float WAV and FLAC.
@@ -199,6 +200,60 @@ class AudioProcessor:
         if seed is None:
             seed = random.getrandbits(64)
         return ops.spec_augment(mel, seed=seed, config=config, out=out)
+
+    def set_mixup(self, config):
+        """Turn mixup on (a config.MixupConfig, or a class with its fields; validated here) or off (`None`, the default).  From then on
+        the batched loaders that augment -- dataset.loader() / batches() of a WakewordDataset(augment=True), ClipBank loaders with
+        augment=True -- finish every batch with mixup_batch: one more launch, after SpecAugment and after unreadable rows are zeroed, and
+        they yield `(data, target)` with target float32 [B, 2] class probabilities instead of int64 labels (WakewordTrainer.step takes
+        both).  Nothing that runs with augment=False, and nothing per item, draws or launches anything more.  Returns the config."""
+        if config is not None:
+            from .config import check_mixup_config
+            check_mixup_config(config)
+        self._mixup = config
+        return config
+
+    @property
+    def mixup(self):
+        """The mixup config in force, or None."""
+        return getattr(self, "_mixup", None)
+
+    def mixup_plan(self, B, bad=None):
+        """The draws of one batch of B rows, from python `random` in this order: one random.sample(range(B), B) for the partners; per
+        row, in batch order, random.random() < PROB; for a chosen row only, one random.betavariate(ALPHA, ALPHA), rounded to float32 and,
+        with DOMINANT and lam < 0.5, replaced by float32(1) - lam.  A row that is not chosen gets lam = 1 and itself as partner.  `bad`
+        (a boolean mask [B]: unreadable files, placeholders): those rows, and every row whose partner is one, are unmixed -- a fix-up
+        after the draws, which it does not change.  Returns (partner int32 [B], lam float32 [B]) on the host."""
+        from .config import MixupConfig
+        config = self.mixup or MixupConfig
+        B = int(B)
+        if B < 1:
+            raise ValueError(f"mixup_plan: B = {B}")
+        partner = np.asarray(random.sample(range(B), B), dtype=np.int32)
+        lam = np.ones(B, dtype=np.float32)
+        for i in range(B):
+            if random.random() < config.PROB:
+                v = np.float32(random.betavariate(config.ALPHA, config.ALPHA))
+                lam[i] = np.float32(1.0) - v if config.DOMINANT and v < np.float32(0.5) else v
+        if bad is not None:
+            bad = np.asarray(bad, dtype=bool)
+            if bad.shape != (B,):
+                raise ValueError(f"mixup_plan: bad must be a boolean mask [{B}], got {bad.shape}")
+            lam[bad | bad[partner]] = 1.0
+        mixed = lam != 1.0
+        partner = np.where(mixed, partner, np.arange(B, dtype=np.int32)).astype(np.int32)
+        return partner, lam
+
+    def mixup_batch(self, data, labels, plan=None):
+        """data [B, 1, 80, T] or [B, 80, T] and labels int64 [B] or [B, 1], both on the GPU -> (mixed data, targets float32 [B, 2]) by
+        `plan` = (partner, lam) as mixup_plan returns it (drawn here when None).  The plan goes up in ONE host-to-device copy."""
+        B = int(data.shape[0])
+        partner, lam = self.mixup_plan(B) if plan is None else plan
+        host = np.empty((2, B), dtype=np.int32)
+        host[0] = np.asarray(partner, dtype=np.int32)
+        host[1] = np.ascontiguousarray(lam, dtype=np.float32).view(np.int32)
+        dev = torch.from_numpy(host).to(data.device)
+        return ops.mixup(data, labels, dev[0], dev[1].view(torch.float32))
 
     def augment_batch(self, pcm, plans=None, config=AugmentationConfig) -> torch.Tensor:
         """pcm [B, N] (ndarray or tensor) -> augmented device tensor [B, N]; one plan per clip (drawn here if None).

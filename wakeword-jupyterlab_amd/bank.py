@@ -447,7 +447,10 @@ class BankLoader:
     `processor.set_spec_augment` on (which draws its seed), rows of placeholders set to 0.0 -- the draw order of the file loader, so a
     seeded epoch over the same files yields the same batches bit for bit.  `entries` (ClipBank.select_entries) keeps only the items of
     those entries.  `last_entries`: the bank entry of every row of the newest batch (host int64; -1 for a placeholder row, served as
-    zeros), set before the batch is yielded -- what a ledger.ClipLedger scatters by; nothing on the device is spent on it."""
+    zeros), set before the batch is yielded -- what a ledger.ClipLedger scatters by; nothing on the device is spent on it.
+    `last_labels`: the rows' own int64 labels [B] on the device.  When augmenting with `processor.set_mixup` on, `processor.mixup_plan`
+    (which draws) and `processor.mixup_batch` run last of all: `target` is then float32 [B, 2] class probabilities and `last_entries` is
+    -1 on every mixed row as well."""
 
     def __init__(self, bank, batch_size=16, shuffle=False, drop_last=False, augment=False, positive_fraction=None, crop=None, entries=None):
         if batch_size < 1:
@@ -459,6 +462,7 @@ class BankLoader:
         self.bank, self.batch_size, self.shuffle, self.drop_last, self.augment = bank, int(batch_size), bool(shuffle), bool(drop_last), bool(augment)
         self.entries = None if entries is None else bank.select_entries(entries)
         self.last_entries = None
+        self.last_labels = None           # the rows' own int64 labels [B] on the device (what `target` held before mixup)
 
     def item_entries(self) -> np.ndarray:
         """The entry of every item of this loader's epoch: the bank's, restricted to `entries`."""
@@ -498,4 +502,10 @@ class BankLoader:
                 data[torch.from_numpy(bad).to(data.device)] = 0.0
             target = torch.from_numpy(bank.labels[entries]).to(data.device).unsqueeze(1)
             self.last_entries = np.where(bad, -1, entries).astype(np.int64)
+            self.last_labels = target[:, 0]
+            if self.augment and getattr(proc, "mixup", None) is not None:
+                # mixup last of all: a mixed row is no longer one entry's clip, so the ledger skips it (-1)
+                partner, lam = proc.mixup_plan(len(entries), bad=bad)
+                data, target = proc.mixup_batch(data, self.last_labels, plan=(partner, lam))
+                self.last_entries = np.where(lam != 1.0, -1, self.last_entries).astype(np.int64)
             yield data, target

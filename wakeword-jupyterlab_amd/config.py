@@ -74,6 +74,28 @@ def check_spec_augment_config(cfg) -> None:
         raise ValueError(f"SpecAugment FILL {fill!r}: expected 'mean', 'min' or a float")
 
 
+class MixupConfig:
+    """Mixup on the log-mel batch (AudioProcessor.set_mixup; Zhang et al. 2018; not in the reference).  A row is mixed with PROB; its
+    weight lam is one Beta(ALPHA, ALPHA) draw, and with DOMINANT it is folded to lam >= 0.5 so that a row stays mostly itself.  PROB
+    and DOMINANT are this project's choices; ALPHA = 0.2 is the paper's value for speech commands."""
+    PROB = 0.5
+    ALPHA = 0.2
+    DOMINANT = True
+
+
+def check_mixup_config(cfg) -> None:
+    """ValueError for a PROB outside [0, 1] or an ALPHA that is not a positive finite number."""
+    import math
+    for name in ("PROB", "ALPHA"):
+        v = getattr(cfg, name)
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"Mixup {name} {v!r}: expected a number")
+    if not 0.0 <= float(cfg.PROB) <= 1.0:
+        raise ValueError(f"Mixup PROB {cfg.PROB}: expected a probability in [0, 1]")
+    if not (math.isfinite(float(cfg.ALPHA)) and float(cfg.ALPHA) > 0.0):
+        raise ValueError(f"Mixup ALPHA {cfg.ALPHA}: expected a positive finite number")
+
+
 class ModelConfig:            # WakewordModel (3 convs)
     HIDDEN_SIZE = 256
     NUM_LAYERS = 2

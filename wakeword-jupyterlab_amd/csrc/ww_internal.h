@@ -191,6 +191,9 @@ int launch_spec_draw(const SpecDraw& d, int64_t n, int T, int16_t* records, hipS
 // records NULL: drawn from `d` inside the kernel; in == out or disjoint (the entry point checks)
 int launch_spec_augment(const float* in, float* out, int64_t n, int T, const int16_t* records, const SpecDraw& d, int mode, float fill_value,
                         hipStream_t stream);
+// mixup on log-mel batches (ww_mixup.hip): out of place; 16-byte accesses when mel and out are both 16-byte aligned
+int launch_mixup(const float* mel, float* out, int64_t B, int T, const int64_t* labels, const int32_t* partner, const float* lambda,
+                 float* targets, hipStream_t stream);
 int sync_timeouts(unsigned int* count);   // bounded LDS-counter waits that expired (must be 0)
 int64_t cnn_scratch_bytes(int64_t n, int n_conv);
 int launch_cnn_pool(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch,

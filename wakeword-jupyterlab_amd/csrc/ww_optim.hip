@@ -4,6 +4,7 @@
 //                       one lane updates the ww_loss_stats record (stream order serialises the calls: no atomics)
 //   ce_loss_ex_kernel   the same shape with class weights, label smoothing, ignore_index, a sum reduction and the focal loss (section 3k):
 //                       under the mean a pass over the labels alone first gives the denominator
+//   ce_loss_soft_kernel the same shape on class probabilities [n][2] instead of labels (section 3n): weights, smoothing, mean or sum
 //   adam_kernel         one launch over up to 16 tensors, the table in the kernel arguments; torch's single-tensor Adam arithmetic
 //   grad_norm_kernel    float64 partial sums of g^2 per 4096 elements; grad_norm_finish_kernel adds them and writes norm and clip scale
 // All three are memory- and latency-bound.  No float atomics anywhere: every sum has one order, so results repeat bit for bit.
@@ -136,15 +137,26 @@ int launch_ce_loss(const float* logits, const int64_t* labels, int64_t n, float*
 // the loss and the gradient have the bits of ce_clip.
 struct ExClip { double loss, d0, d1; int correct, bad, nonfinite; };
 
+// The softmax and the log-sum-exp of one clip in float64: what ex_clip and soft_clip share, so that the two agree to the bit wherever
+// their formulas reduce to one another.
+struct Softmax2 { double z0, z1, lse, p0, p1; };
+
+__device__ __forceinline__ Softmax2 softmax2(float z0f, float z1f) {
+    Softmax2 r;
+    r.z0 = double(z0f); r.z1 = double(z1f);
+    const double m = r.z0 > r.z1 ? r.z0 : r.z1;
+    const double e0 = exp(r.z0 - m), e1 = exp(r.z1 - m), s = e0 + e1;
+    r.lse = m + log(s);
+    r.p0 = e0 / s; r.p1 = e1 / s;
+    return r;
+}
+
 __device__ __forceinline__ ExClip ex_clip(float z0f, float z1f, int64_t y, const ww_loss_opts& o) {
     ExClip r;
-    const double z0 = double(z0f), z1 = double(z1f);
-    const double m = z0 > z1 ? z0 : z1;
-    const double e0 = exp(z0 - m), e1 = exp(z1 - m), s = e0 + e1;
+    const Softmax2 sm = softmax2(z0f, z1f);
+    const double z0 = sm.z0, z1 = sm.z1, lse = sm.lse, p0 = sm.p0, p1 = sm.p1;
     const bool ignored = y == o.ignore_index;
     const bool valid = !ignored && (y == 0 || y == 1);
-    const double lse = m + log(s);
-    const double p0 = e0 / s, p1 = e1 / s;
     const double w0 = o.class_weight[0], w1 = o.class_weight[1];
     const double wy = y == 1 ? w1 : w0;
     const double nly = lse - (y == 1 ? z1 : z0);            // -log p_y
@@ -282,6 +294,141 @@ __global__ __launch_bounds__(kCeThreads) void ce_loss_ex_kernel(const float* __r
 int launch_ce_loss_ex(const float* logits, const int64_t* labels, int64_t n, const ww_loss_opts& opts, float* dlogits, float* loss,
                       ww_loss_stats* stats, hipStream_t stream) {
     hipLaunchKernelGGL(ce_loss_ex_kernel, dim3(1), dim3(kCeThreads), 0, stream, logits, labels, n, opts, dlogits, loss, stats);
+    WW_HIP(hipGetLastError());
+    return WW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// cross-entropy on class probabilities: mixup, distillation, soft relabelling
+// ---------------------------------------------------------------------------------------------
+// One clip in float64, NOT yet divided by the mean's denominator.  t' = (1 - eps) t + eps / 2; l = sum_c w_c t'_c (lse - z_c);
+// dl/dz_k = p_k (w0 t'_0 + w1 t'_1) - w_k t'_k.  A row counts (`valid`) iff both targets are finite and >= 0.  With a one-hot row, unit
+// weights and eps = 0 every product is by 1 or by 0, so loss and gradient have the bits of ce_clip / ex_clip on the label.
+__device__ __forceinline__ ExClip soft_clip(float z0f, float z1f, float t0f, float t1f, const ww_loss_opts& o) {
+    ExClip r;
+    const Softmax2 sm = softmax2(z0f, z1f);
+    const bool valid = isfinite(t0f) && isfinite(t1f) && t0f >= 0.f && t1f >= 0.f;
+    const double eps = o.label_smoothing, half = 0.5 * eps;
+    const double a0 = o.class_weight[0] * ((1.0 - eps) * double(t0f) + half);
+    const double a1 = o.class_weight[1] * ((1.0 - eps) * double(t1f) + half);
+    const double loss = a0 * (sm.lse - sm.z0) + a1 * (sm.lse - sm.z1);
+    const double wsum = a0 + a1;
+    const double d0 = sm.p0 * wsum - a0, d1 = sm.p1 * wsum - a1;
+    r.loss = valid ? loss : 0.0;
+    r.d0 = valid ? d0 : 0.0;
+    r.d1 = valid ? d1 : 0.0;
+    const int pred = z1f > z0f ? 1 : 0;
+    r.correct = valid && pred == (t1f > t0f ? 1 : 0);       // a tie in the target gives class 0: the prediction's rule
+    r.bad = !valid;
+    r.nonfinite = !(isfinite(z0f) && isfinite(z1f));
+    return r;
+}
+
+// ce_loss_ex_kernel's shape -- one workgroup, lane t owns the clip pairs t, t + 256, ..., the same fold -- on targets [n][2] float32: a
+// pair is 16 bytes of logits and 16 bytes of targets.  Under the mean a pass over the targets alone first counts the rows that count:
+// the denominator is their NUMBER (torch divides by n), not the weighted sum of the integer-label form.
+__global__ __launch_bounds__(kCeThreads) void ce_loss_soft_kernel(const float* __restrict__ logits, const float* __restrict__ targets, int64_t n,
+                                                                  const ww_loss_opts o, float* __restrict__ dlogits, float* __restrict__ loss_out,
+                                                                  ww_loss_stats* __restrict__ stats) {
+    __shared__ double red_loss[kCeThreads / 64];
+    __shared__ int red_cnt[3][kCeThreads / 64];
+    __shared__ int red_cls[kCeThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool z_wide = (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
+    const bool t_wide = (reinterpret_cast<uintptr_t>(targets) & 15) == 0;
+    const bool d_wide = (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;
+    const int64_t pairs = (n + 1) >> 1;
+    const bool mean = o.reduction == WW_REDUCE_MEAN;
+    double inv = 1.0;                                       // 1 / denominator; 0 when the denominator is 0: such a batch moves no weight
+    bool empty = false;
+    if (mean) {
+        int cnt = 0;
+        for (int64_t p = tid; p < pairs; p += kCeThreads) {
+            const int64_t i = 2 * p;
+            const bool two = i + 1 < n;
+            float t[4] = {0.f, 0.f, -1.f, -1.f};
+            if (two && t_wide) {
+                const float4 v = *reinterpret_cast<const float4*>(targets + 2 * i);
+                t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+            } else {
+                t[0] = targets[2 * i]; t[1] = targets[2 * i + 1];
+                if (two) { t[2] = targets[2 * i + 2]; t[3] = targets[2 * i + 3]; }
+            }
+            cnt += isfinite(t[0]) && isfinite(t[1]) && t[0] >= 0.f && t[1] >= 0.f;
+            cnt += isfinite(t[2]) && isfinite(t[3]) && t[2] >= 0.f && t[3] >= 0.f;
+        }
+        cnt = wave_sum(cnt);
+        if (lane == 0) red_cls[wave] = cnt;
+        __syncthreads();
+        int64_t counted = 0;
+#pragma unroll
+        for (int w = 0; w < kCeThreads / 64; ++w) counted += red_cls[w];
+        empty = counted == 0;
+        inv = empty ? 0.0 : 1.0 / double(counted);
+    }
+    double loss = 0.0;
+    int correct = 0, bad = 0, nonfinite = 0;
+    for (int64_t p = tid; p < pairs; p += kCeThreads) {
+        const int64_t i = 2 * p;
+        const bool two = i + 1 < n;
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        float t[4] = {0.f, 0.f, 0.f, 0.f};
+        if (two && z_wide) {
+            const float4 v = *reinterpret_cast<const float4*>(logits + 2 * i);
+            z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
+        } else {
+            z[0] = logits[2 * i]; z[1] = logits[2 * i + 1];
+            if (two) { z[2] = logits[2 * i + 2]; z[3] = logits[2 * i + 3]; }
+        }
+        if (two && t_wide) {
+            const float4 v = *reinterpret_cast<const float4*>(targets + 2 * i);
+            t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+        } else {
+            t[0] = targets[2 * i]; t[1] = targets[2 * i + 1];
+            if (two) { t[2] = targets[2 * i + 2]; t[3] = targets[2 * i + 3]; }
+        }
+        const ExClip a = soft_clip(z[0], z[1], t[0], t[1], o);
+        loss += a.loss; correct += a.correct; bad += a.bad; nonfinite += a.nonfinite;
+        float d[4] = {float(a.d0 * inv), float(a.d1 * inv), 0.f, 0.f};
+        if (two) {
+            const ExClip b = soft_clip(z[2], z[3], t[2], t[3], o);
+            loss += b.loss; correct += b.correct; bad += b.bad; nonfinite += b.nonfinite;
+            d[2] = float(b.d0 * inv); d[3] = float(b.d1 * inv);
+        }
+        if (empty) d[0] = d[1] = d[2] = d[3] = 0.f;         // not 0 x NaN
+        if (dlogits) {
+            if (two && d_wide) {
+                *reinterpret_cast<float4*>(dlogits + 2 * i) = make_float4(d[0], d[1], d[2], d[3]);
+            } else {
+                dlogits[2 * i] = d[0]; dlogits[2 * i + 1] = d[1];
+                if (two) { dlogits[2 * i + 2] = d[2]; dlogits[2 * i + 3] = d[3]; }
+            }
+        }
+    }
+    loss = wave_sum(loss); correct = wave_sum(correct); bad = wave_sum(bad); nonfinite = wave_sum(nonfinite);
+    if (lane == 0) { red_loss[wave] = loss; red_cnt[0][wave] = correct; red_cnt[1][wave] = bad; red_cnt[2][wave] = nonfinite; }
+    __syncthreads();
+    if (tid == 0) {
+        double total = red_loss[0];
+        int c = red_cnt[0][0], b = red_cnt[1][0], f = red_cnt[2][0];
+#pragma unroll
+        for (int w = 1; w < kCeThreads / 64; ++w) { total += red_loss[w]; c += red_cnt[0][w]; b += red_cnt[1][w]; f += red_cnt[2][w]; }
+        const float value = empty ? __builtin_nanf("") : float(total * inv);      // a mean over nothing is NaN; rounded once
+        if (loss_out) *loss_out = value;
+        if (stats) {
+            stats->loss_sum += double(value);
+            stats->correct += c;
+            stats->total += n;
+            stats->batches += 1;
+            stats->bad_labels += b;
+            stats->nonfinite += f;
+        }
+    }
+}
+
+int launch_ce_loss_soft(const float* logits, const float* targets, int64_t n, const ww_loss_opts& opts, float* dlogits, float* loss,
+                        ww_loss_stats* stats, hipStream_t stream) {
+    hipLaunchKernelGGL(ce_loss_soft_kernel, dim3(1), dim3(kCeThreads), 0, stream, logits, targets, n, opts, dlogits, loss, stats);
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
@@ -488,6 +635,21 @@ static int check_table(const ww_adam_tensor* tensors, int64_t n_tensors, bool st
     return WW_OK;
 }
 
+// Host checks of the loss options, before any HIP call: what ww_ce_loss_ex_f32 and ww_ce_loss_soft_f32 share.
+static int check_loss_opts(const ww_loss_opts& o) {
+    for (int c = 0; c < 2; ++c)
+        if (!(o.class_weight[c] >= 0.0) || std::isinf(o.class_weight[c]))
+            return fail(WW_EINVAL, "class_weight[%d] %g: expected a finite value >= 0", c, o.class_weight[c]);
+    if (!(o.label_smoothing >= 0.0 && o.label_smoothing <= 1.0)) return fail(WW_EINVAL, "label_smoothing %g: expected [0, 1]", o.label_smoothing);
+    if (!(o.focal_gamma >= 0.0) || std::isinf(o.focal_gamma)) return fail(WW_EINVAL, "focal_gamma %g: expected a finite value >= 0", o.focal_gamma);
+    if (o.kind != WW_LOSS_CE && o.kind != WW_LOSS_FOCAL) return fail(WW_EINVAL, "kind %d: expected WW_LOSS_CE or WW_LOSS_FOCAL", int(o.kind));
+    if (o.reduction != WW_REDUCE_MEAN && o.reduction != WW_REDUCE_SUM)
+        return fail(WW_EINVAL, "reduction %d: expected WW_REDUCE_MEAN or WW_REDUCE_SUM", int(o.reduction));
+    if (o.kind == WW_LOSS_FOCAL && o.label_smoothing != 0.0)
+        return fail(WW_EINVAL, "label_smoothing %g: the focal loss takes none", o.label_smoothing);
+    return WW_OK;
+}
+
 }  // namespace ww
 
 using namespace ww;
@@ -516,18 +678,27 @@ int ww_ce_loss_ex_f32(const float* logits_dev, const int64_t* labels_dev, int64_
     if ((reinterpret_cast<uintptr_t>(labels_dev) & 7) || (reinterpret_cast<uintptr_t>(stats_dev) & 7))
         return fail(WW_EINVAL, "labels_dev / stats_dev must be 8-byte aligned");
     const ww_loss_opts o = *opts_host;
-    for (int c = 0; c < 2; ++c)
-        if (!(o.class_weight[c] >= 0.0) || std::isinf(o.class_weight[c]))
-            return fail(WW_EINVAL, "class_weight[%d] %g: expected a finite value >= 0", c, o.class_weight[c]);
-    if (!(o.label_smoothing >= 0.0 && o.label_smoothing <= 1.0)) return fail(WW_EINVAL, "label_smoothing %g: expected [0, 1]", o.label_smoothing);
-    if (!(o.focal_gamma >= 0.0) || std::isinf(o.focal_gamma)) return fail(WW_EINVAL, "focal_gamma %g: expected a finite value >= 0", o.focal_gamma);
-    if (o.kind != WW_LOSS_CE && o.kind != WW_LOSS_FOCAL) return fail(WW_EINVAL, "kind %d: expected WW_LOSS_CE or WW_LOSS_FOCAL", int(o.kind));
-    if (o.reduction != WW_REDUCE_MEAN && o.reduction != WW_REDUCE_SUM)
-        return fail(WW_EINVAL, "reduction %d: expected WW_REDUCE_MEAN or WW_REDUCE_SUM", int(o.reduction));
-    if (o.kind == WW_LOSS_FOCAL && o.label_smoothing != 0.0)
-        return fail(WW_EINVAL, "label_smoothing %g: the focal loss takes none", o.label_smoothing);
+    if (int rc = check_loss_opts(o)) return rc;
     if (int rc = require_gfx950()) return rc;
     return launch_ce_loss_ex(logits_dev, labels_dev, n, o, dlogits_dev, loss_dev, stats_dev, static_cast<hipStream_t>(stream));
+}
+
+int ww_ce_loss_soft_f32(const float* logits_dev, const float* targets_dev, int64_t n, const ww_loss_opts* opts_host, float* dlogits_dev,
+                        float* loss_dev, ww_loss_stats* stats_dev, ww_stream_t stream) {
+    if (n <= 0 || n > (int64_t(1) << 30)) return fail(WW_EINVAL, "n %lld: expected 1..2^30", (long long)n);
+    ww_loss_opts o = {{1.0, 1.0}, 0.0, 0.0, -100, WW_LOSS_CE, WW_REDUCE_MEAN};             // NULL: nn.CrossEntropyLoss()'s defaults
+    if (opts_host) o = *opts_host;
+    if (int rc = check_loss_opts(o)) return rc;
+    if (o.kind != WW_LOSS_CE) return fail(WW_EINVAL, "kind %d: class-probability targets take WW_LOSS_CE only", int(o.kind));
+    if (o.ignore_index != -100)
+        return fail(WW_EINVAL, "ignore_index %lld: class-probability targets take none (leave it at -100)", (long long)o.ignore_index);
+    if (!logits_dev || !targets_dev) return fail(WW_EINVAL, "null logits / targets pointer");
+    if ((reinterpret_cast<uintptr_t>(logits_dev) & 3) || (reinterpret_cast<uintptr_t>(targets_dev) & 3) ||
+        (reinterpret_cast<uintptr_t>(dlogits_dev) & 3) || (reinterpret_cast<uintptr_t>(loss_dev) & 3))
+        return fail(WW_EINVAL, "logits_dev / targets_dev / dlogits_dev / loss_dev must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(stats_dev) & 7) return fail(WW_EINVAL, "stats_dev must be 8-byte aligned");
+    if (int rc = require_gfx950()) return rc;
+    return launch_ce_loss_soft(logits_dev, targets_dev, n, o, dlogits_dev, loss_dev, stats_dev, static_cast<hipStream_t>(stream));
 }
 
 int ww_adam_step_f32(const ww_adam_tensor* tensors_host, int64_t n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,

@@ -70,7 +70,9 @@ class WakewordDataset(Dataset):
         `positive_fraction=f` in (0, 1), with shuffle=True: every epoch keeps its length and holds that share of wake-word items
         (sampling.balanced_order); None, the default, leaves the order as it was.
         After every batch `loader.last_entries` holds each row's index into `files` (host int64, -1 for an unreadable file): what a
-        ledger.ClipLedger scatters by."""
+        ledger.ClipLedger scatters by; `loader.last_labels` holds the rows' own int64 labels on the device.
+        With augment=True and `processor.set_mixup` on, every batch ends with mixup: `target` is float32 [B, 2] class probabilities
+        and `last_entries` is -1 on mixed rows too."""
         return GpuBatchLoader(self, batch_size, shuffle=shuffle, drop_last=drop_last, positive_fraction=positive_fraction)
 
     def cache(self):
@@ -88,6 +90,7 @@ class GpuBatchLoader:
         self.positive_fraction = check_positive_fraction(positive_fraction, self.shuffle)
         self._encoded = None
         self.last_entries = None          # per row of the newest batch: its index into dataset.files (host int64; -1 where unreadable)
+        self.last_labels = None           # the rows' own int64 labels [B] on the device (what `target` held before mixup)
 
     def __len__(self):
         n = len(self.dataset)
@@ -153,6 +156,12 @@ class GpuBatchLoader:
                 data[torch.from_numpy(~ok).to(dev)] = 0.0
             target = torch.tensor(labels[s:e], dtype=torch.long, device=dev).unsqueeze(1)
             self.last_entries = np.where(np.asarray(ok, bool), np.asarray(idx[s:e], np.int64), -1).astype(np.int64)
+            self.last_labels = target[:, 0]
+            if ds.augment and getattr(ds.processor, "mixup", None) is not None:
+                # mixup last of all (set_mixup): float32 [B, 2] targets, and a mixed row is no longer one file's clip (-1)
+                partner, lam = ds.processor.mixup_plan(e - s, bad=~np.asarray(ok, bool))
+                data, target = ds.processor.mixup_batch(data, self.last_labels, plan=(partner, lam))
+                self.last_entries = np.where(lam != 1.0, -1, self.last_entries).astype(np.int64)
             yield data, target
 
 

@@ -890,6 +890,117 @@ def ce_loss(logits: torch.Tensor, labels: torch.Tensor, stats=None, grad: bool =
     return loss, dlogits
 
 
+# ---- class-probability targets: soft cross-entropy and mixup (csrc/ww_optim.hip, csrc/ww_mixup.hip) --------
+def _check_soft(logits, targets):
+    _require_cuda_f32(logits, "logits")
+    if logits.dim() != 2 or logits.shape[1] != 2 or logits.shape[0] == 0 or not logits.is_contiguous():
+        raise ValueError(f"logits: expected contiguous [n >= 1, 2], got {tuple(logits.shape)}")
+    if not isinstance(targets, torch.Tensor):
+        raise TypeError(f"targets: expected a torch.Tensor, got {type(targets).__name__}")
+    if targets.dtype != torch.float32:
+        raise TypeError(f"targets: expected float32 class probabilities, got {targets.dtype} (integer labels go to ops.ce_loss)")
+    if targets.device != logits.device:
+        raise RuntimeError(f"targets on {targets.device}, logits on {logits.device}")
+    if targets.shape != logits.shape or not targets.is_contiguous():
+        raise ValueError(f"targets: expected contiguous [{logits.shape[0]}, 2], got {tuple(targets.shape)}")
+
+
+def soft_loss_opts(weight=None, label_smoothing=0.0, reduction="mean", focal_gamma=None, ignore_index=-100):
+    """The options of ops.soft_ce_loss as the struct ww_ce_loss_soft_f32 takes, or None when every option is at its default.
+    NotImplementedError for a focal loss or reduction="none", ValueError for an ignore_index other than -100 (torch refuses one for
+    floating-point targets) and for every value ops.loss_opts refuses; nothing touches a device except a weight tensor's copy."""
+    if focal_gamma is not None:
+        raise NotImplementedError("soft_ce_loss: the focal loss takes integer labels (ops.ce_loss); class-probability targets take cross-entropy")
+    opts = loss_opts(weight, label_smoothing, ignore_index, reduction, None)
+    if int(ignore_index) != -100:
+        raise ValueError(f"ignore_index {ignore_index}: class-probability targets take none (torch refuses it too)")
+    return opts
+
+
+def soft_ce_loss_into(logits, targets, dlogits, loss, stats, *, weight=None, label_smoothing=0.0, reduction="mean", focal_gamma=None,
+                      opts=None) -> None:
+    """ww_ce_loss_soft_f32 on caller-owned outputs (each may be None); `opts` as in ce_loss_into (what soft_loss_opts made; it wins
+    over the keywords).  Allocates nothing on the device."""
+    if opts is None:
+        opts = soft_loss_opts(weight, label_smoothing, reduction, focal_gamma)
+    with torch.cuda.device(logits.device):
+        nat.check(nat.lib.ww_ce_loss_soft_f32(_ptr(logits), _ptr(targets), logits.shape[0], None if opts is None else C.byref(opts),
+                                              None if dlogits is None else _ptr(dlogits), None if loss is None else _ptr(loss),
+                                              None if stats is None else _ptr(stats), _stream()))
+
+
+def soft_ce_loss(logits: torch.Tensor, targets: torch.Tensor, stats=None, grad: bool = True, *, weight=None, label_smoothing=0.0,
+                 reduction="mean", focal_gamma=None):
+    """F.cross_entropy(logits, targets, weight=, label_smoothing=, reduction=) with class PROBABILITIES as targets: (loss [] float32,
+    dlogits [n, 2] or None with grad=False).  logits and targets float32 contiguous [n, 2] on the GPU; `stats` as in ce_loss.  A target
+    row counts iff both entries are finite and >= 0 (ops.mixup marks a row it could not label with NaN): any other row adds nothing, gets
+    a zero gradient and is counted in bad_labels.  "mean" divides by the NUMBER of counted rows, as torch divides by n -- not by the
+    weighted denominator of ce_loss.  With one-hot targets and default options the results have ce_loss's
+    bits.  `focal_gamma` and reduction="none" raise NotImplementedError."""
+    opts = soft_loss_opts(weight, label_smoothing, reduction, focal_gamma)
+    _check_soft(logits, targets)
+    if stats is not None:
+        _check_stats(stats, logits)
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    dlogits = torch.empty_like(logits) if grad else None
+    soft_ce_loss_into(logits, targets, dlogits, loss, stats, opts=opts)
+    return loss, dlogits
+
+
+def _check_mixup(mel, labels, partner, lam):
+    if not isinstance(mel, torch.Tensor):
+        raise TypeError(f"mel: expected a torch.Tensor, got {type(mel).__name__}")
+    if mel.device.type != "cuda":
+        raise RuntimeError(f"mel is on {mel.device}: this path has no CPU implementation; move it to the MI355X (`.cuda()`)")
+    if mel.dtype != torch.float32 or not ((mel.dim() == 4 and mel.shape[1] == 1 and mel.shape[2] == N_MELS) or
+                                          (mel.dim() == 3 and mel.shape[1] == N_MELS)) or not mel.is_contiguous() or mel.shape[0] == 0:
+        raise ValueError(f"mel: expected contiguous float32 [B >= 1, 1, {N_MELS}, T] or [B, {N_MELS}, T], got {mel.dtype} {tuple(mel.shape)}")
+    B = int(mel.shape[0])
+    _check_frames(int(mel.shape[-1]), "mel")
+    for name, t, dtype in (("labels", labels, torch.int64), ("partner", partner, torch.int32), ("lam", lam, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != mel.device:
+            raise TypeError(f"{name}: expected a {dtype} tensor on {mel.device}")
+    if labels.dim() == 2 and labels.shape[1] == 1:
+        labels = labels[:, 0]
+    for name, t in (("labels", labels), ("partner", partner), ("lam", lam)):
+        if t.dim() != 1 or t.shape[0] != B or (B > 1 and t.stride(0) != 1):
+            raise ValueError(f"{name}: expected [{B}] with unit stride, got {tuple(t.shape)}")
+    return labels
+
+
+def _check_mixup_out(mel, out, targets):
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != mel.shape or out.device != mel.device
+            or not out.is_contiguous()):
+        raise ValueError("out: expected a contiguous float32 tensor of mel's shape on mel's device")
+    if (not isinstance(targets, torch.Tensor) or targets.dtype != torch.float32 or tuple(targets.shape) != (mel.shape[0], 2)
+            or targets.device != mel.device or not targets.is_contiguous()):
+        raise ValueError(f"targets: expected a contiguous float32 [{mel.shape[0]}, 2] tensor on mel's device")
+
+
+def mixup_into(mel, labels, partner, lam, out, targets) -> None:
+    """ww_mixup_f32 on caller-owned `out` (like mel, not overlapping it) and `targets` [B, 2]; arguments as ops.mixup takes them.
+    Allocates nothing on the device."""
+    labels = _check_mixup(mel, labels, partner, lam)
+    _check_mixup_out(mel, out, targets)
+    with torch.cuda.device(mel.device):
+        nat.check(nat.lib.ww_mixup_f32(_ptr(mel), _ptr(out), mel.shape[0], int(mel.shape[-1]), _ptr(labels), _ptr(partner), _ptr(lam),
+                                       _ptr(targets), _stream()))
+
+
+def mixup(mel: torch.Tensor, labels: torch.Tensor, partner: torch.Tensor, lam: torch.Tensor, out=None):
+    """mel float32 [B, 1, 80, T] or [B, 80, T] on the GPU, contiguous, T <= 63; labels int64 [B] or [B, 1], partner int32 [B] and lam
+    float32 [B] on the same device -> (out like mel, targets float32 [B, 2]).  Row i with lam[i] == 1 is copied bit for bit; any other
+    row becomes fmaf(lam, mel[i], (1 - lam) * mel[partner[i]]) and its target the same mix of the two one-hot labels.  A label outside
+    {0, 1} on a row (or on the partner of a mixed row) and a partner outside [0, B) give a (NaN, NaN) target, which ops.soft_ce_loss counts
+    as a bad label.  Out of place: `out` must not overlap mel."""
+    labels = _check_mixup(mel, labels, partner, lam)
+    if out is None:
+        out = torch.empty_like(mel)
+    targets = torch.empty((mel.shape[0], 2), device=mel.device, dtype=torch.float32)
+    mixup_into(mel, labels, partner, lam, out, targets)
+    return out, targets
+
+
 # ---- clip evaluation as device counters (INTEGRATION.md section 3j; csrc/ww_metrics.hip) ---------------------------------------------
 class ClipMetricsState:
     """A ww_clip_metrics record in device memory (`buffer`, int64 words) with the probability thresholds it was made for and their float32

@@ -16,6 +16,10 @@ epoch and scatters every step's train-mode logits by the loader's `last_entries`
 eval-mode logits -- one more launch per batch, no wait.  With both None a step issues exactly the launches it
 always issued.
 
+A float32 target [B, 2] holds class probabilities (mixup through `processor.set_mixup`, distillation): `step` / `train_epoch` then run
+the soft cross-entropy (ww_ce_loss_soft_f32) in the loss's place, the launch count unchanged; `validate` keeps integer labels
+(INTEGRATION.md section 3n).
+
 One deliberate difference: the reference calls `clip_grad_norm_` BEFORE `backward()`, where it clips the previous batch's gradients or
 nothing, so the default here is no clipping; `max_grad_norm=1.0` gives the clip the call meant, after the
 backward.
@@ -155,14 +159,22 @@ class WakewordTrainer:
             self._norm_ws = ops.grad_norm_workspace(self._norm_tables, self._dev)
         ops.grad_norm_launch(self._norm_tables, self._dev, self.max_grad_norm, self._norm, self._scale, self._norm_ws)
 
-    def _target(self, target, B):
+    def _target(self, target, B, soft=False):
         if not isinstance(target, torch.Tensor):
             raise TypeError(f"target: expected a torch.Tensor, got {type(target).__name__}")
         if target.device != self._dev:
             target = target.to(self._dev)
+        if target.dtype == torch.float32 and soft:
+            # class probabilities [B, 2] (mixup, distillation): the soft cross-entropy of the fused step
+            if target.dim() != 2 or tuple(target.shape) != (B, 2):
+                raise ValueError(f"target: expected float32 class probabilities [{B}, 2], got {tuple(target.shape)}")
+            return target if target.is_contiguous() else target.contiguous()
         if target.dtype != torch.int64:
             if target.dtype.is_floating_point or target.dtype == torch.bool:
-                raise TypeError(f"target: expected integer class labels, got {target.dtype}")
+                if target.dtype.is_floating_point and not soft:
+                    raise TypeError(f"target: validate needs integer class labels (the clip metrics count hard labels), got {target.dtype}; "
+                                    "class-probability targets are for step / train_epoch")
+                raise TypeError(f"target: expected integer class labels or float32 class probabilities [B, 2], got {target.dtype}")
             target = target.to(torch.int64)
         if target.dim() == 2 and target.shape[1] == 1:
             target = target[:, 0]
@@ -179,9 +191,23 @@ class WakewordTrainer:
                             "(bank.loader() and dataset.loader() set it; a hand-written loop passes step(..., entries=))")
         return entries
 
-    def step(self, data, target, entries=None) -> torch.Tensor:
+    def _soft_opts(self):
+        """The criterion's options as ww_ce_loss_soft_f32 takes them (None: the defaults); refusals before any launch."""
+        from .loss import FocalLoss
+        if isinstance(self._criterion, FocalLoss):
+            raise NotImplementedError("WakewordTrainer.step: class-probability targets with a FocalLoss criterion are not supported "
+                                      "(the focal loss takes integer labels); use nn.CrossEntropyLoss")
+        if int(self._criterion.ignore_index) != -100:
+            raise ValueError(f"WakewordTrainer.step: ignore_index {self._criterion.ignore_index} with class-probability targets "
+                             "(torch refuses it too); leave it at -100")
+        return self._loss_opts
+
+    def step(self, data, target, entries=None, labels=None) -> torch.Tensor:
         """One training batch: data [B, 1, 80, T <= 32] float32 and target [B] or [B, 1] int64, both on the GPU (tensors elsewhere, or of
-        another integer type, are copied first).  Returns the batch's mean loss as a 0-d tensor ON THE DEVICE (self.last_loss, overwritten
+        another integer type, are copied first).  A float32 target [B, 2] holds class probabilities (mixup: what a loader yields under
+        `processor.set_mixup`; distillation): the step then launches ww_ce_loss_soft_f32 in place of the integer-label loss -- the same
+        number of launches, no wait, no allocation; `labels` [B] int64 on the device (train_epoch passes the loader's `last_labels`) are
+        then what the ledger records.  Returns the batch's mean loss as a 0-d tensor ON THE DEVICE (self.last_loss, overwritten
         by the next step); the running metrics are in self.train_stats.  The model must be in train mode.  `entries` [B] (a host integer
         array or an int64 device tensor; train_epoch passes the loader's `last_entries`): with `self.ledger` set, the step's train-mode
         logits and labels are added to it under these entries, one more launch after the optimiser's."""
@@ -196,7 +222,15 @@ class WakewordTrainer:
         B = x.shape[0]
         if B == 0:
             raise ValueError("empty training batch")
-        y = self._target(target, B)
+        y = self._target(target, B, soft=True)
+        soft = y.dtype == torch.float32
+        soft_opts = self._soft_opts() if soft else None
+        ledger_y = y
+        if soft and entries is not None and self.ledger is not None:
+            if labels is None:
+                raise TypeError("a ledger with class-probability targets needs the rows' integer labels: step(..., labels=) "
+                                "(bank.loader() and dataset.loader() set `last_labels`)")
+            ledger_y = self._target(labels, B)
         if not self._grads_bound():                          # optimizer.zero_grad() or a .to(): bind the buffers again
             self._bind_grads()
             self._norm_tables = None
@@ -214,13 +248,16 @@ class WakewordTrainer:
                 self._cap = B
             logits, m = self._logits if B == self._cap else self._logits[:B], self.model         # the buffers may hold more rows
             ops.train_forward_into(x, self._tp, m.lstm.dropout, m.dropout.p, seed, math, self._ws, logits)
-            ops.ce_loss_into(logits, y, self._dlogits, self.last_loss, self.train_stats, opts=self._loss_opts)
+            if soft:
+                ops.soft_ce_loss_into(logits, y, self._dlogits, self.last_loss, self.train_stats, opts=soft_opts)
+            else:
+                ops.ce_loss_into(logits, y, self._dlogits, self.last_loss, self.train_stats, opts=self._loss_opts)
             ops.train_backward_into(x, self._tp, self._dlogits, math, self._ws, self._tg)
             if self.max_grad_norm is not None:
                 self._norm_step()
         self.optimizer.step(grad_scale=self._scale if self.max_grad_norm is not None else None)
         if entries is not None and self.ledger is not None:
-            self.ledger.update(entries, logits, y)
+            self.ledger.update(entries, logits, ledger_y)
         return self.last_loss
 
     @property
@@ -244,7 +281,10 @@ class WakewordTrainer:
         if self.ledger is not None:
             self.ledger.begin_epoch()
         for data, target in train_loader:
-            self.step(data, target, None if self.ledger is None else self._entries_of(train_loader))
+            if self.ledger is None:
+                self.step(data, target)
+            else:
+                self.step(data, target, self._entries_of(train_loader), getattr(train_loader, "last_labels", None))
         return self._finish_epoch(self.train_stats, "train_epoch")
 
     def validate(self, val_loader):
