@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """The loss for imbalanced data: ww_ce_loss_ex_f32 against ww_ce_loss_f32 in one process, at the batch size of
-the training step (n = 16) and at n = 4096, for weighted + smoothed cross-entropy and for the focal loss.
+the training step (n = 16) and at n = 4096, for weighted + smoothed cross-entropy and for the focal loss, and ww_ce_loss_soft_f32 (section
+3n) with the weighted + smoothed options on [n, 2] class probabilities.
 
     PYTHONPATH=. python scripts/bench_loss.py [--launches 500] [--windows 9] [--out profiles/loss_bench.json]
 
 The C entry points themselves with their arguments prepared once; loss, gradient and the stats record all written, as in the step.  One
-device-event pair around `--launches` back-to-back calls per window; the three variants alternate window by window after a warm-up
+device-event pair around `--launches` back-to-back calls per window; the four variants alternate window by window after a warm-up
 window each; median and range of the windows, in microseconds per call.  Back-to-back calls on one stream serialise on the record, so
 this is the time from one call's start to the next one's, launch overhead included -- what a training step pays for its loss."""
 import argparse
@@ -22,6 +23,7 @@ from wakeword_jupyterlab_amd import _native as nat  # noqa: E402
 from wakeword_jupyterlab_amd import ops  # noqa: E402
 
 VARIANTS = {"plain": None, "weighted_smoothed": dict(weight=(0.25, 4.0), label_smoothing=0.125), "focal": dict(weight=(0.25, 4.0), focal_gamma=2.0)}
+SOFT = dict(weight=(0.25, 4.0), label_smoothing=0.125)
 
 
 def measure(n, launches, windows, dev):
@@ -37,6 +39,9 @@ def measure(n, launches, windows, dev):
         else:
             opts = ops.loss_opts(**kw)
             calls[name] = (nat.lib.ww_ce_loss_ex_f32, (ops._ptr(z), ops._ptr(y), n, C.byref(opts), ops._ptr(d), ops._ptr(loss), ops._ptr(stats), stream), opts)
+    t = torch.stack([1.0 - y.to(torch.float32), y.to(torch.float32)], dim=1).mul_(0.75).add_(0.125).contiguous()   # rows (0.875, 0.125) / (0.125, 0.875)
+    opts = ops.soft_loss_opts(**SOFT)
+    calls["soft"] = (nat.lib.ww_ce_loss_soft_f32, (ops._ptr(z), ops._ptr(t), n, C.byref(opts), ops._ptr(d), ops._ptr(loss), ops._ptr(stats), stream), opts)
     us = {name: [] for name in calls}
     for w in range(windows + 1):                                            # window 0 warms up
         for name, (fn, args, _) in calls.items():
@@ -53,7 +58,7 @@ def measure(n, launches, windows, dev):
     row = {"n": n, "launches_per_window": launches, "windows": windows}
     for name, v in us.items():
         row[name] = {"us_per_call_median": statistics.median(v), "us_per_call_min": min(v), "us_per_call_max": max(v)}
-    for name in ("weighted_smoothed", "focal"):
+    for name in ("weighted_smoothed", "focal", "soft"):
         row[f"{name}_over_plain"] = row[name]["us_per_call_median"] / row["plain"]["us_per_call_median"]
     return row
 

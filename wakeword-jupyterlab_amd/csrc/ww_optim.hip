@@ -1,10 +1,15 @@
 // What sits between the training forward and backward kernels and after them: cross-entropy with its
 // gradient and the epoch's running metrics, a multi-tensor Adam step, and the global gradient norm that clips it.
-//   ce_loss_kernel      one workgroup: per clip the loss and d loss / d logits in float64, the batch mean summed in a fixed order,
-//                       one lane updates the ww_loss_stats record (stream order serialises the calls: no atomics)
-//   ce_loss_ex_kernel   the same shape with class weights, label smoothing, ignore_index, a sum reduction and the focal loss (section 3k):
-//                       under the mean a pass over the labels alone first gives the denominator
-//   ce_loss_soft_kernel the same shape on class probabilities [n][2] instead of labels (section 3n): weights, smoothing, mean or sum
+//   loss_kernel<P>      one workgroup: per clip the loss and d loss / d logits in float64, the batch sum folded in a fixed order and
+//                       divided once, one lane updates the ww_loss_stats record (stream order serialises the calls: no atomics).  The
+//                       skeleton owns the walk over the clips, the loads and stores, the counting pass and every sum; a policy P
+//                       supplies the target type, the per-clip formula and the mean's denominator.  Three policies:
+//                         PlainLabels  int64 labels, the mean over n (section 3h)
+//                         OptLabels    labels with class weights, label smoothing, ignore_index, a sum reduction and the focal loss
+//                                      (section 3k): under the mean a pass over the labels alone first gives the denominator
+//                         Probs        class probabilities [n][2] with weights, smoothing, mean or sum (section 3n)
+//                       All three go through softmax2 and one order of summation, so where their formulas reduce to one another
+//                       (unit options, one-hot rows) so do their bits (tests/test_gpu_loss.py, tests/test_gpu_mixup.py).
 //   adam_kernel         one launch over up to 16 tensors, the table in the kernel arguments; torch's single-tensor Adam arithmetic
 //   grad_norm_kernel    float64 partial sums of g^2 per 4096 elements; grad_norm_finish_kernel adds them and writes norm and clip scale
 // All three are memory- and latency-bound.  No float atomics anywhere: every sum has one order, so results repeat bit for bit.
@@ -15,130 +20,14 @@
 namespace ww {
 
 // ---------------------------------------------------------------------------------------------
-// cross-entropy, two classes
+// cross-entropy, two classes: one workgroup skeleton, three per-clip rules
 // ---------------------------------------------------------------------------------------------
 constexpr int kCeThreads = 256;
 
-struct CeClip { double loss, d0, d1; int correct, bad, nonfinite; };
+// One clip in float64, NOT yet divided by the mean's denominator.
+struct LossClip { double loss, d0, d1; int correct, bad, nonfinite; };
 
-// One clip in float64: lse = max + log(exp(z0 - max) + exp(z1 - max)), loss = lse - z[y], d = softmax - onehot (the caller divides by n).
-__device__ __forceinline__ CeClip ce_clip(float z0f, float z1f, int64_t y) {
-    CeClip r;
-    const double z0 = double(z0f), z1 = double(z1f);
-    const double m = z0 > z1 ? z0 : z1;
-    const double e0 = exp(z0 - m), e1 = exp(z1 - m), s = e0 + e1;
-    const bool valid = y == 0 || y == 1;
-    const double lse = m + log(s);
-    r.loss = valid ? lse - (y == 1 ? z1 : z0) : 0.0;
-    r.d0 = valid ? e0 / s - (y == 0 ? 1.0 : 0.0) : 0.0;
-    r.d1 = valid ? e1 / s - (y == 1 ? 1.0 : 0.0) : 0.0;
-    const int pred = z1f > z0f ? 1 : 0;                     // a tie gives class 0, as torch.max(output, 1) does
-    r.correct = valid && int64_t(pred) == y;
-    r.bad = !valid;
-    r.nonfinite = !(isfinite(z0f) && isfinite(z1f));
-    return r;
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-__device__ __forceinline__ int wave_sum(int x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
-// Lane t owns the clip pairs t, t + 256, ...: a pair is 16 bytes of logits and 16 bytes of labels.  Its float64 sum runs over its clips
-// in rising order; the 256 lane sums are folded by the butterfly of wave_sum and the four wave sums are added in wave order -- an order
-// set by kCeThreads alone.  The pointers need 4-byte (labels: 8-byte) alignment only; the 16-byte accesses are taken where they are aligned.
-__global__ __launch_bounds__(kCeThreads) void ce_loss_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int64_t n,
-                                                             float* __restrict__ dlogits, float* __restrict__ loss_out,
-                                                             ww_loss_stats* __restrict__ stats) {
-    __shared__ double red_loss[kCeThreads / 64];
-    __shared__ int red_cnt[3][kCeThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool z_wide = (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
-    const bool y_wide = (reinterpret_cast<uintptr_t>(labels) & 15) == 0;
-    const bool d_wide = (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;
-    const double inv_n = 1.0 / double(n);
-    const int64_t pairs = (n + 1) >> 1;
-    double loss = 0.0;
-    int correct = 0, bad = 0, nonfinite = 0;
-    for (int64_t p = tid; p < pairs; p += kCeThreads) {
-        const int64_t i = 2 * p;
-        const bool two = i + 1 < n;
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        int64_t y[2] = {0, 0};
-        if (two && z_wide) {
-            const float4 v = *reinterpret_cast<const float4*>(logits + 2 * i);
-            z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
-        } else {
-            z[0] = logits[2 * i]; z[1] = logits[2 * i + 1];
-            if (two) { z[2] = logits[2 * i + 2]; z[3] = logits[2 * i + 3]; }
-        }
-        if (two && y_wide) {
-            const longlong2 v = *reinterpret_cast<const longlong2*>(labels + i);
-            y[0] = v.x; y[1] = v.y;
-        } else {
-            y[0] = labels[i];
-            if (two) y[1] = labels[i + 1];
-        }
-        const CeClip a = ce_clip(z[0], z[1], y[0]);
-        loss += a.loss; correct += a.correct; bad += a.bad; nonfinite += a.nonfinite;
-        float d[4] = {float(a.d0 * inv_n), float(a.d1 * inv_n), 0.f, 0.f};
-        if (two) {
-            const CeClip b = ce_clip(z[2], z[3], y[1]);
-            loss += b.loss; correct += b.correct; bad += b.bad; nonfinite += b.nonfinite;
-            d[2] = float(b.d0 * inv_n); d[3] = float(b.d1 * inv_n);
-        }
-        if (dlogits) {
-            if (two && d_wide) {
-                *reinterpret_cast<float4*>(dlogits + 2 * i) = make_float4(d[0], d[1], d[2], d[3]);
-            } else {
-                dlogits[2 * i] = d[0]; dlogits[2 * i + 1] = d[1];
-                if (two) { dlogits[2 * i + 2] = d[2]; dlogits[2 * i + 3] = d[3]; }
-            }
-        }
-    }
-    loss = wave_sum(loss); correct = wave_sum(correct); bad = wave_sum(bad); nonfinite = wave_sum(nonfinite);
-    if (lane == 0) { red_loss[wave] = loss; red_cnt[0][wave] = correct; red_cnt[1][wave] = bad; red_cnt[2][wave] = nonfinite; }
-    __syncthreads();
-    if (tid == 0) {
-        double total = red_loss[0];
-        int c = red_cnt[0][0], b = red_cnt[1][0], f = red_cnt[2][0];
-#pragma unroll
-        for (int w = 1; w < kCeThreads / 64; ++w) { total += red_loss[w]; c += red_cnt[0][w]; b += red_cnt[1][w]; f += red_cnt[2][w]; }
-        const float mean = float(total * inv_n);            // rounded once
-        if (loss_out) *loss_out = mean;
-        if (stats) {
-            stats->loss_sum += double(mean);                // what `running_loss += loss.item()` adds
-            stats->correct += c;
-            stats->total += n;
-            stats->batches += 1;
-            stats->bad_labels += b;
-            stats->nonfinite += f;
-        }
-    }
-}
-
-int launch_ce_loss(const float* logits, const int64_t* labels, int64_t n, float* dlogits, float* loss, ww_loss_stats* stats, hipStream_t stream) {
-    hipLaunchKernelGGL(ce_loss_kernel, dim3(1), dim3(kCeThreads), 0, stream, logits, labels, n, dlogits, loss, stats);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// cross-entropy with class weights, label smoothing and ignore_index, and focal loss
-// ---------------------------------------------------------------------------------------------
-// One clip in float64, NOT yet divided by the mean's denominator.  A clip counts (`valid`) with a label in {0, 1} that is not
-// ignore_index (the ignore test comes first, so ignore_index may be 0 or 1).  With unit weights, no smoothing and the cross-entropy kind
-// the loss and the gradient have the bits of ce_clip.
-struct ExClip { double loss, d0, d1; int correct, bad, nonfinite; };
-
-// The softmax and the log-sum-exp of one clip in float64: what ex_clip and soft_clip share, so that the two agree to the bit wherever
-// their formulas reduce to one another.
+// The softmax and the log-sum-exp of one clip in float64, lse = max + log(exp(z0 - max) + exp(z1 - max)): what the three rules share.
 struct Softmax2 { double z0, z1, lse, p0, p1; };
 
 __device__ __forceinline__ Softmax2 softmax2(float z0f, float z1f) {
@@ -151,83 +40,193 @@ __device__ __forceinline__ Softmax2 softmax2(float z0f, float z1f) {
     return r;
 }
 
-__device__ __forceinline__ ExClip ex_clip(float z0f, float z1f, int64_t y, const ww_loss_opts& o) {
-    ExClip r;
-    const Softmax2 sm = softmax2(z0f, z1f);
-    const double z0 = sm.z0, z1 = sm.z1, lse = sm.lse, p0 = sm.p0, p1 = sm.p1;
-    const bool ignored = y == o.ignore_index;
-    const bool valid = !ignored && (y == 0 || y == 1);
-    const double w0 = o.class_weight[0], w1 = o.class_weight[1];
-    const double wy = y == 1 ? w1 : w0;
-    const double nly = lse - (y == 1 ? z1 : z0);            // -log p_y
-    double loss, d0, d1;
-    if (o.kind == WW_LOSS_FOCAL) {
-        const double py = y == 1 ? p1 : p0, q = y == 1 ? p0 : p1;      // q = the OTHER class's softmax term, never 1 - p_y
-        const double qg = exp(-o.focal_gamma * (lse - (y == 1 ? z0 : z1)));    // q^gamma from log q = z_other - lse: one exp, and 1 at gamma = 0
-        loss = wy * qg * nly;
-        const double dy = wy * (-o.focal_gamma * py * qg * nly - qg * q);
-        d0 = y == 0 ? dy : -dy;
-        d1 = y == 1 ? dy : -dy;
-    } else {
-        const double eps = o.label_smoothing, keep = (1.0 - eps) * wy, half = 0.5 * eps;
-        loss = keep * nly + half * (w0 * (lse - z0) + w1 * (lse - z1));
-        d0 = keep * (p0 - (y == 0 ? 1.0 : 0.0)) + half * ((w0 + w1) * p0 - w0);
-        d1 = keep * (p1 - (y == 1 ? 1.0 : 0.0)) + half * ((w0 + w1) * p1 - w1);
-    }
-    r.loss = valid ? loss : 0.0;
-    r.d0 = valid ? d0 : 0.0;
-    r.d1 = valid ? d1 : 0.0;
-    const int pred = z1f > z0f ? 1 : 0;
-    r.correct = valid && int64_t(pred) == y;
+// What a clip adds to the stats record whatever the rule: a tie in the logits predicts class 0, as torch.max(output, 1) does.
+__device__ __forceinline__ void clip_counts(LossClip& r, float z0f, float z1f, bool valid, bool ignored, int target_class) {
+    r.correct = valid && (z1f > z0f ? 1 : 0) == target_class;
     r.bad = !ignored && !valid;
     r.nonfinite = !(isfinite(z0f) && isfinite(z1f));
-    return r;
 }
 
-// ce_loss_kernel's shape -- one workgroup, lane t owns the clip pairs t, t + 256, ..., the same fold -- with a pass over the labels alone
-// in front of it under the mean reduction: the weighted mean divides every gradient by W = n0 w0 + n1 w1, and two integer counts give W
-// exactly before the first gradient is written.  The options travel by value in the kernel arguments.
-__global__ __launch_bounds__(kCeThreads) void ce_loss_ex_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int64_t n,
-                                                                const ww_loss_opts o, float* __restrict__ dlogits, float* __restrict__ loss_out,
-                                                                ww_loss_stats* __restrict__ stats) {
-    __shared__ double red_loss[kCeThreads / 64];
-    __shared__ int red_cnt[3][kCeThreads / 64];
-    __shared__ int red_cls[2][kCeThreads / 64];
+// Integer labels, the mean over n: loss = lse - z[y], d = softmax - onehot.  A label outside {0, 1} is a bad label (-100 included).
+struct PlainLabels {
+    using Target = int64_t;
+    static constexpr int kPer = 1, kCounts = 0;             // no counting pass: the denominator is n, and a batch is never empty
+    __device__ __forceinline__ LossClip clip(float z0f, float z1f, const int64_t* t) const {
+        LossClip r;
+        const int64_t y = *t;
+        const Softmax2 sm = softmax2(z0f, z1f);
+        const bool valid = y == 0 || y == 1;
+        r.loss = valid ? sm.lse - (y == 1 ? sm.z1 : sm.z0) : 0.0;
+        r.d0 = valid ? sm.p0 - (y == 0 ? 1.0 : 0.0) : 0.0;
+        r.d1 = valid ? sm.p1 - (y == 1 ? 1.0 : 0.0) : 0.0;
+        clip_counts(r, z0f, z1f, valid, false, int(y));
+        return r;
+    }
+};
+
+// Integer labels with class weights, label smoothing and ignore_index, and the focal loss.  A clip counts
+// (`valid`) with a label in {0, 1} that is not ignore_index (the ignore test comes first, so ignore_index may be 0 or 1).  The weighted
+// mean divides every gradient by W = n0 w0 + n1 w1 (the focal mean by n0 + n1): two integer counts give it exactly before the first
+// gradient is written.  With unit weights, no smoothing and the cross-entropy kind loss and gradient have PlainLabels' bits.
+struct OptLabels {
+    using Target = int64_t;
+    static constexpr int kPer = 1, kCounts = 2;
+    ww_loss_opts o;
+    __device__ __forceinline__ bool counts_first() const { return o.reduction == WW_REDUCE_MEAN; }
+    __device__ __forceinline__ void tally(const int64_t* t, int* c) const {
+        const bool counted = *t != o.ignore_index;
+        c[0] += counted && *t == 0;
+        c[1] += counted && *t == 1;
+    }
+    __device__ __forceinline__ double denominator(const int64_t* totals) const {
+        return o.kind == WW_LOSS_FOCAL ? double(totals[0] + totals[1]) : double(totals[0]) * o.class_weight[0] + double(totals[1]) * o.class_weight[1];
+    }
+    __device__ __forceinline__ LossClip clip(float z0f, float z1f, const int64_t* t) const {
+        LossClip r;
+        const int64_t y = *t;
+        const Softmax2 sm = softmax2(z0f, z1f);
+        const double z0 = sm.z0, z1 = sm.z1, lse = sm.lse, p0 = sm.p0, p1 = sm.p1;
+        const bool ignored = y == o.ignore_index;
+        const bool valid = !ignored && (y == 0 || y == 1);
+        const double w0 = o.class_weight[0], w1 = o.class_weight[1];
+        const double wy = y == 1 ? w1 : w0;
+        const double nly = lse - (y == 1 ? z1 : z0);            // -log p_y
+        double loss, d0, d1;
+        if (o.kind == WW_LOSS_FOCAL) {
+            const double py = y == 1 ? p1 : p0, q = y == 1 ? p0 : p1;      // q = the OTHER class's softmax term, never 1 - p_y
+            const double qg = exp(-o.focal_gamma * (lse - (y == 1 ? z0 : z1)));    // q^gamma from log q = z_other - lse: one exp, and 1 at gamma = 0
+            loss = wy * qg * nly;
+            const double dy = wy * (-o.focal_gamma * py * qg * nly - qg * q);
+            d0 = y == 0 ? dy : -dy;
+            d1 = y == 1 ? dy : -dy;
+        } else {
+            const double eps = o.label_smoothing, keep = (1.0 - eps) * wy, half = 0.5 * eps;
+            loss = keep * nly + half * (w0 * (lse - z0) + w1 * (lse - z1));
+            d0 = keep * (p0 - (y == 0 ? 1.0 : 0.0)) + half * ((w0 + w1) * p0 - w0);
+            d1 = keep * (p1 - (y == 1 ? 1.0 : 0.0)) + half * ((w0 + w1) * p1 - w1);
+        }
+        r.loss = valid ? loss : 0.0;
+        r.d0 = valid ? d0 : 0.0;
+        r.d1 = valid ? d1 : 0.0;
+        clip_counts(r, z0f, z1f, valid, ignored, int(y));
+        return r;
+    }
+};
+
+// Class probabilities [n][2] float32: mixup, distillation, soft relabelling.  t' = (1 - eps) t + eps / 2;
+// l = sum_c w_c t'_c (lse - z_c); dl/dz_k = p_k (w0 t'_0 + w1 t'_1) - w_k t'_k.  A row counts iff both targets are finite and >= 0, and
+// the mean's denominator is the NUMBER of such rows (torch divides by n), not the weighted sum of the integer-label form.  With a
+// one-hot row, unit weights and eps = 0 every product is by 1 or by 0, so loss and gradient have the bits of the label rules.
+struct Probs {
+    using Target = float;
+    static constexpr int kPer = 2, kCounts = 1;
+    ww_loss_opts o;
+    static __device__ __forceinline__ bool counted(const float* t) { return isfinite(t[0]) && isfinite(t[1]) && t[0] >= 0.f && t[1] >= 0.f; }
+    __device__ __forceinline__ bool counts_first() const { return o.reduction == WW_REDUCE_MEAN; }
+    __device__ __forceinline__ void tally(const float* t, int* c) const { c[0] += counted(t); }
+    __device__ __forceinline__ double denominator(const int64_t* totals) const { return double(totals[0]); }
+    __device__ __forceinline__ LossClip clip(float z0f, float z1f, const float* t) const {
+        LossClip r;
+        const Softmax2 sm = softmax2(z0f, z1f);
+        const float t0f = t[0], t1f = t[1];
+        const bool valid = counted(t);
+        const double eps = o.label_smoothing, half = 0.5 * eps;
+        const double a0 = o.class_weight[0] * ((1.0 - eps) * double(t0f) + half);
+        const double a1 = o.class_weight[1] * ((1.0 - eps) * double(t1f) + half);
+        const double loss = a0 * (sm.lse - sm.z0) + a1 * (sm.lse - sm.z1);
+        const double wsum = a0 + a1;
+        const double d0 = sm.p0 * wsum - a0, d1 = sm.p1 * wsum - a1;
+        r.loss = valid ? loss : 0.0;
+        r.d0 = valid ? d0 : 0.0;
+        r.d1 = valid ? d1 : 0.0;
+        clip_counts(r, z0f, z1f, valid, false, t1f > t0f ? 1 : 0);      // a tie in the target gives class 0: the prediction's rule
+        return r;
+    }
+};
+
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+__device__ __forceinline__ int wave_sum(int x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+
+// The four wave sums of a 256-thread workgroup, added in wave order: the last step of every sum in this file.
+template <class T>
+__device__ __forceinline__ T fold_waves(const T* red) { return ((red[0] + red[1]) + red[2]) + red[3]; }
+
+// The 16 bytes of clip pair (i, i + 1), PER elements a clip: one 16-byte load where `wide` (src on the 16-byte grid) and the pair is
+// whole, single elements otherwise.  The second clip of an odd tail reads as zeros and is never used.  Zeros first, then every path
+// loads into v itself: filled any other way the paths end in register copies, and the compiler puts a wait for the logits in front of
+// the targets' load -- two memory latencies per pair instead of one (profiles/loss_refactor_bench.json, `first_attempt`).
+template <class T, int PER>
+__device__ __forceinline__ void load_pair(const T* __restrict__ src, int64_t i, bool two, bool wide, T (&v)[2 * PER]) {
+    static_assert(sizeof(T) * PER * 2 == 16, "a pair of clips is 16 bytes");
+    typedef T Pair __attribute__((ext_vector_type(2 * PER)));   // float4 / longlong2: 16 bytes, 16-byte aligned
+#pragma unroll
+    for (int j = 0; j < 2 * PER; ++j) v[j] = T(0);
+    if (two && wide) {
+        const Pair w = *reinterpret_cast<const Pair*>(src + PER * i);
+#pragma unroll
+        for (int j = 0; j < 2 * PER; ++j) v[j] = w[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < PER; ++j) v[j] = src[PER * i + j];
+        if (two) {
+#pragma unroll
+            for (int j = 0; j < PER; ++j) v[PER + j] = src[PER * (i + 1) + j];
+        }
+    }
+}
+
+// Lane t owns the clip pairs t, t + 256, ...: a pair is 16 bytes of logits and 16 bytes of targets.  Its float64 sum runs over its clips
+// in rising order; the 256 lane sums are folded by the butterfly of wave_sum and the four wave sums are added in wave order -- an order
+// set by kCeThreads alone.  The pointers need 4-byte (labels: 8-byte) alignment only; the 16-byte accesses are taken where they are
+// aligned.  A policy with kCounts > 0 gets, when its counts_first() says so, a pass over the targets alone in front: kCounts integer
+// tallies per clip, summed exactly, become the denominator every gradient is divided by; a denominator of 0 makes the batch `empty`:
+// a NaN loss, as in torch, and a gradient of zeros.  The policy (the options in it) travels by value in the kernel arguments.
+template <class P>
+__global__ __launch_bounds__(kCeThreads) void loss_kernel(const float* __restrict__ logits, const typename P::Target* __restrict__ targets, int64_t n,
+                                                          const P pol, float* __restrict__ dlogits, float* __restrict__ loss_out,
+                                                          ww_loss_stats* __restrict__ stats) {
+    using Target = typename P::Target;
+    constexpr int kPer = P::kPer, kCounts = P::kCounts, kWaves = kCeThreads / 64;
+    __shared__ double red_loss[kWaves];
+    __shared__ int red_cnt[3][kWaves];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool z_wide = (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
-    const bool y_wide = (reinterpret_cast<uintptr_t>(labels) & 15) == 0;
+    const bool t_wide = (reinterpret_cast<uintptr_t>(targets) & 15) == 0;
     const bool d_wide = (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;
     const int64_t pairs = (n + 1) >> 1;
-    const bool mean = o.reduction == WW_REDUCE_MEAN;
     double inv = 1.0;                                       // 1 / denominator; 0 when the denominator is 0: such a batch moves no weight
     bool empty = false;
-    if (mean) {
-        int c0 = 0, c1 = 0;
+    if constexpr (kCounts == 0) {
+        inv = 1.0 / double(n);
+    } else if (pol.counts_first()) {
+        __shared__ int red_tally[kCounts][kWaves];
+        int c[kCounts] = {};
         for (int64_t p = tid; p < pairs; p += kCeThreads) {
             const int64_t i = 2 * p;
             const bool two = i + 1 < n;
-            int64_t y[2] = {o.ignore_index, o.ignore_index};
-            if (two && y_wide) {
-                const longlong2 v = *reinterpret_cast<const longlong2*>(labels + i);
-                y[0] = v.x; y[1] = v.y;
-            } else {
-                y[0] = labels[i];
-                if (two) y[1] = labels[i + 1];
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const bool counted = y[j] != o.ignore_index;
-                c0 += counted && y[j] == 0;
-                c1 += counted && y[j] == 1;
-            }
+            Target t[2 * kPer];
+            load_pair<Target, kPer>(targets, i, two, t_wide, t);
+            pol.tally(t, c);
+            if (two) pol.tally(t + kPer, c);
         }
-        c0 = wave_sum(c0); c1 = wave_sum(c1);
-        if (lane == 0) { red_cls[0][wave] = c0; red_cls[1][wave] = c1; }
-        __syncthreads();
-        int64_t n0 = 0, n1 = 0;
+        int64_t totals[kCounts];
 #pragma unroll
-        for (int w = 0; w < kCeThreads / 64; ++w) { n0 += red_cls[0][w]; n1 += red_cls[1][w]; }
-        const double denom = o.kind == WW_LOSS_FOCAL ? double(n0 + n1) : double(n0) * o.class_weight[0] + double(n1) * o.class_weight[1];
+        for (int k = 0; k < kCounts; ++k) {
+            c[k] = wave_sum(c[k]);
+            if (lane == 0) red_tally[k][wave] = c[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kCounts; ++k) totals[k] = fold_waves(red_tally[k]);
+        const double denom = pol.denominator(totals);
         empty = !(denom > 0.0);
         inv = empty ? 0.0 : 1.0 / denom;
     }
@@ -236,27 +235,15 @@ __global__ __launch_bounds__(kCeThreads) void ce_loss_ex_kernel(const float* __r
     for (int64_t p = tid; p < pairs; p += kCeThreads) {
         const int64_t i = 2 * p;
         const bool two = i + 1 < n;
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        int64_t y[2] = {0, 0};
-        if (two && z_wide) {
-            const float4 v = *reinterpret_cast<const float4*>(logits + 2 * i);
-            z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
-        } else {
-            z[0] = logits[2 * i]; z[1] = logits[2 * i + 1];
-            if (two) { z[2] = logits[2 * i + 2]; z[3] = logits[2 * i + 3]; }
-        }
-        if (two && y_wide) {
-            const longlong2 v = *reinterpret_cast<const longlong2*>(labels + i);
-            y[0] = v.x; y[1] = v.y;
-        } else {
-            y[0] = labels[i];
-            if (two) y[1] = labels[i + 1];
-        }
-        const ExClip a = ex_clip(z[0], z[1], y[0], o);
+        float z[4];
+        Target t[2 * kPer];
+        load_pair<float, 2>(logits, i, two, z_wide, z);
+        load_pair<Target, kPer>(targets, i, two, t_wide, t);
+        const LossClip a = pol.clip(z[0], z[1], t);
         loss += a.loss; correct += a.correct; bad += a.bad; nonfinite += a.nonfinite;
         float d[4] = {float(a.d0 * inv), float(a.d1 * inv), 0.f, 0.f};
         if (two) {
-            const ExClip b = ex_clip(z[2], z[3], y[1], o);
+            const LossClip b = pol.clip(z[2], z[3], t + kPer);
             loss += b.loss; correct += b.correct; bad += b.bad; nonfinite += b.nonfinite;
             d[2] = float(b.d0 * inv); d[3] = float(b.d1 * inv);
         }
@@ -274,163 +261,37 @@ __global__ __launch_bounds__(kCeThreads) void ce_loss_ex_kernel(const float* __r
     if (lane == 0) { red_loss[wave] = loss; red_cnt[0][wave] = correct; red_cnt[1][wave] = bad; red_cnt[2][wave] = nonfinite; }
     __syncthreads();
     if (tid == 0) {
-        double total = red_loss[0];
-        int c = red_cnt[0][0], b = red_cnt[1][0], f = red_cnt[2][0];
-#pragma unroll
-        for (int w = 1; w < kCeThreads / 64; ++w) { total += red_loss[w]; c += red_cnt[0][w]; b += red_cnt[1][w]; f += red_cnt[2][w]; }
-        const float value = empty ? __builtin_nanf("") : float(total * inv);      // a mean over nothing is NaN, as in torch; rounded once
+        const float value = empty ? __builtin_nanf("") : float(fold_waves(red_loss) * inv);    // a mean over nothing is NaN, as in torch; rounded once
         if (loss_out) *loss_out = value;
         if (stats) {
-            stats->loss_sum += double(value);
-            stats->correct += c;
+            stats->loss_sum += double(value);               // what `running_loss += loss.item()` adds
+            stats->correct += fold_waves(red_cnt[0]);
             stats->total += n;
             stats->batches += 1;
-            stats->bad_labels += b;
-            stats->nonfinite += f;
+            stats->bad_labels += fold_waves(red_cnt[1]);
+            stats->nonfinite += fold_waves(red_cnt[2]);
         }
     }
 }
 
-int launch_ce_loss_ex(const float* logits, const int64_t* labels, int64_t n, const ww_loss_opts& opts, float* dlogits, float* loss,
-                      ww_loss_stats* stats, hipStream_t stream) {
-    hipLaunchKernelGGL(ce_loss_ex_kernel, dim3(1), dim3(kCeThreads), 0, stream, logits, labels, n, opts, dlogits, loss, stats);
+template <class P>
+static int launch_loss(const float* logits, const typename P::Target* targets, int64_t n, const P& pol, float* dlogits, float* loss,
+                       ww_loss_stats* stats, hipStream_t stream) {
+    hipLaunchKernelGGL(loss_kernel<P>, dim3(1), dim3(kCeThreads), 0, stream, logits, targets, n, pol, dlogits, loss, stats);
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// cross-entropy on class probabilities: mixup, distillation, soft relabelling
-// ---------------------------------------------------------------------------------------------
-// One clip in float64, NOT yet divided by the mean's denominator.  t' = (1 - eps) t + eps / 2; l = sum_c w_c t'_c (lse - z_c);
-// dl/dz_k = p_k (w0 t'_0 + w1 t'_1) - w_k t'_k.  A row counts (`valid`) iff both targets are finite and >= 0.  With a one-hot row, unit
-// weights and eps = 0 every product is by 1 or by 0, so loss and gradient have the bits of ce_clip / ex_clip on the label.
-__device__ __forceinline__ ExClip soft_clip(float z0f, float z1f, float t0f, float t1f, const ww_loss_opts& o) {
-    ExClip r;
-    const Softmax2 sm = softmax2(z0f, z1f);
-    const bool valid = isfinite(t0f) && isfinite(t1f) && t0f >= 0.f && t1f >= 0.f;
-    const double eps = o.label_smoothing, half = 0.5 * eps;
-    const double a0 = o.class_weight[0] * ((1.0 - eps) * double(t0f) + half);
-    const double a1 = o.class_weight[1] * ((1.0 - eps) * double(t1f) + half);
-    const double loss = a0 * (sm.lse - sm.z0) + a1 * (sm.lse - sm.z1);
-    const double wsum = a0 + a1;
-    const double d0 = sm.p0 * wsum - a0, d1 = sm.p1 * wsum - a1;
-    r.loss = valid ? loss : 0.0;
-    r.d0 = valid ? d0 : 0.0;
-    r.d1 = valid ? d1 : 0.0;
-    const int pred = z1f > z0f ? 1 : 0;
-    r.correct = valid && pred == (t1f > t0f ? 1 : 0);       // a tie in the target gives class 0: the prediction's rule
-    r.bad = !valid;
-    r.nonfinite = !(isfinite(z0f) && isfinite(z1f));
-    return r;
+static int launch_ce_loss(const float* logits, const int64_t* labels, int64_t n, float* dlogits, float* loss, ww_loss_stats* stats, hipStream_t stream) {
+    return launch_loss(logits, labels, n, PlainLabels{}, dlogits, loss, stats, stream);
 }
-
-// ce_loss_ex_kernel's shape -- one workgroup, lane t owns the clip pairs t, t + 256, ..., the same fold -- on targets [n][2] float32: a
-// pair is 16 bytes of logits and 16 bytes of targets.  Under the mean a pass over the targets alone first counts the rows that count:
-// the denominator is their NUMBER (torch divides by n), not the weighted sum of the integer-label form.
-__global__ __launch_bounds__(kCeThreads) void ce_loss_soft_kernel(const float* __restrict__ logits, const float* __restrict__ targets, int64_t n,
-                                                                  const ww_loss_opts o, float* __restrict__ dlogits, float* __restrict__ loss_out,
-                                                                  ww_loss_stats* __restrict__ stats) {
-    __shared__ double red_loss[kCeThreads / 64];
-    __shared__ int red_cnt[3][kCeThreads / 64];
-    __shared__ int red_cls[kCeThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool z_wide = (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
-    const bool t_wide = (reinterpret_cast<uintptr_t>(targets) & 15) == 0;
-    const bool d_wide = (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;
-    const int64_t pairs = (n + 1) >> 1;
-    const bool mean = o.reduction == WW_REDUCE_MEAN;
-    double inv = 1.0;                                       // 1 / denominator; 0 when the denominator is 0: such a batch moves no weight
-    bool empty = false;
-    if (mean) {
-        int cnt = 0;
-        for (int64_t p = tid; p < pairs; p += kCeThreads) {
-            const int64_t i = 2 * p;
-            const bool two = i + 1 < n;
-            float t[4] = {0.f, 0.f, -1.f, -1.f};
-            if (two && t_wide) {
-                const float4 v = *reinterpret_cast<const float4*>(targets + 2 * i);
-                t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
-            } else {
-                t[0] = targets[2 * i]; t[1] = targets[2 * i + 1];
-                if (two) { t[2] = targets[2 * i + 2]; t[3] = targets[2 * i + 3]; }
-            }
-            cnt += isfinite(t[0]) && isfinite(t[1]) && t[0] >= 0.f && t[1] >= 0.f;
-            cnt += isfinite(t[2]) && isfinite(t[3]) && t[2] >= 0.f && t[3] >= 0.f;
-        }
-        cnt = wave_sum(cnt);
-        if (lane == 0) red_cls[wave] = cnt;
-        __syncthreads();
-        int64_t counted = 0;
-#pragma unroll
-        for (int w = 0; w < kCeThreads / 64; ++w) counted += red_cls[w];
-        empty = counted == 0;
-        inv = empty ? 0.0 : 1.0 / double(counted);
-    }
-    double loss = 0.0;
-    int correct = 0, bad = 0, nonfinite = 0;
-    for (int64_t p = tid; p < pairs; p += kCeThreads) {
-        const int64_t i = 2 * p;
-        const bool two = i + 1 < n;
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        float t[4] = {0.f, 0.f, 0.f, 0.f};
-        if (two && z_wide) {
-            const float4 v = *reinterpret_cast<const float4*>(logits + 2 * i);
-            z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
-        } else {
-            z[0] = logits[2 * i]; z[1] = logits[2 * i + 1];
-            if (two) { z[2] = logits[2 * i + 2]; z[3] = logits[2 * i + 3]; }
-        }
-        if (two && t_wide) {
-            const float4 v = *reinterpret_cast<const float4*>(targets + 2 * i);
-            t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
-        } else {
-            t[0] = targets[2 * i]; t[1] = targets[2 * i + 1];
-            if (two) { t[2] = targets[2 * i + 2]; t[3] = targets[2 * i + 3]; }
-        }
-        const ExClip a = soft_clip(z[0], z[1], t[0], t[1], o);
-        loss += a.loss; correct += a.correct; bad += a.bad; nonfinite += a.nonfinite;
-        float d[4] = {float(a.d0 * inv), float(a.d1 * inv), 0.f, 0.f};
-        if (two) {
-            const ExClip b = soft_clip(z[2], z[3], t[2], t[3], o);
-            loss += b.loss; correct += b.correct; bad += b.bad; nonfinite += b.nonfinite;
-            d[2] = float(b.d0 * inv); d[3] = float(b.d1 * inv);
-        }
-        if (empty) d[0] = d[1] = d[2] = d[3] = 0.f;         // not 0 x NaN
-        if (dlogits) {
-            if (two && d_wide) {
-                *reinterpret_cast<float4*>(dlogits + 2 * i) = make_float4(d[0], d[1], d[2], d[3]);
-            } else {
-                dlogits[2 * i] = d[0]; dlogits[2 * i + 1] = d[1];
-                if (two) { dlogits[2 * i + 2] = d[2]; dlogits[2 * i + 3] = d[3]; }
-            }
-        }
-    }
-    loss = wave_sum(loss); correct = wave_sum(correct); bad = wave_sum(bad); nonfinite = wave_sum(nonfinite);
-    if (lane == 0) { red_loss[wave] = loss; red_cnt[0][wave] = correct; red_cnt[1][wave] = bad; red_cnt[2][wave] = nonfinite; }
-    __syncthreads();
-    if (tid == 0) {
-        double total = red_loss[0];
-        int c = red_cnt[0][0], b = red_cnt[1][0], f = red_cnt[2][0];
-#pragma unroll
-        for (int w = 1; w < kCeThreads / 64; ++w) { total += red_loss[w]; c += red_cnt[0][w]; b += red_cnt[1][w]; f += red_cnt[2][w]; }
-        const float value = empty ? __builtin_nanf("") : float(total * inv);      // a mean over nothing is NaN; rounded once
-        if (loss_out) *loss_out = value;
-        if (stats) {
-            stats->loss_sum += double(value);
-            stats->correct += c;
-            stats->total += n;
-            stats->batches += 1;
-            stats->bad_labels += b;
-            stats->nonfinite += f;
-        }
-    }
+static int launch_ce_loss_ex(const float* logits, const int64_t* labels, int64_t n, const ww_loss_opts& opts, float* dlogits, float* loss,
+                             ww_loss_stats* stats, hipStream_t stream) {
+    return launch_loss(logits, labels, n, OptLabels{opts}, dlogits, loss, stats, stream);
 }
-
-int launch_ce_loss_soft(const float* logits, const float* targets, int64_t n, const ww_loss_opts& opts, float* dlogits, float* loss,
-                        ww_loss_stats* stats, hipStream_t stream) {
-    hipLaunchKernelGGL(ce_loss_soft_kernel, dim3(1), dim3(kCeThreads), 0, stream, logits, targets, n, opts, dlogits, loss, stats);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+static int launch_ce_loss_soft(const float* logits, const float* targets, int64_t n, const ww_loss_opts& opts, float* dlogits, float* loss,
+                               ww_loss_stats* stats, hipStream_t stream) {
+    return launch_loss(logits, targets, n, Probs{opts}, dlogits, loss, stats, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -537,7 +398,7 @@ constexpr int kNormVecs = 4;
 constexpr int kNormChunk = kNormThreads * kNormVecs * 4;    // 4096 elements per partial sum
 
 // partial[block] = sum of g^2 over elements [4096 c, 4096 c + 4096) of the block's tensor, in float64: thread t adds its elements
-// 4 (t + 256 j) .. + 3, j = 0 .. 3, in rising order, then the butterfly and the wave order of ce_loss_kernel.  The order is in ELEMENT
+// 4 (t + 256 j) .. + 3, j = 0 .. 3, in rising order, then the butterfly and the wave order of loss_kernel.  The order is in ELEMENT
 // coordinates, so it does not move with the pointer's alignment (a g off the 16-byte grid is read one float at a time).
 __global__ __launch_bounds__(kNormThreads) void grad_norm_kernel(const TensorTable tab, double* __restrict__ partial) {
     __shared__ double red[kNormThreads / 64];
@@ -566,7 +427,7 @@ __global__ __launch_bounds__(kNormThreads) void grad_norm_kernel(const TensorTab
     acc = wave_sum(acc);
     if (lane == 0) red[wave] = acc;
     __syncthreads();
-    if (tid == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    if (tid == 0) partial[blockIdx.x] = fold_waves(red);
 }
 
 // One workgroup: thread t adds the partials t, t + 256, ... in rising order; same fold.  scale = min(1, max_norm / (norm + 1e-6)).
@@ -580,7 +441,7 @@ __global__ __launch_bounds__(kNormThreads) void grad_norm_finish_kernel(const do
     if (lane == 0) red[wave] = acc;
     __syncthreads();
     if (tid == 0) {
-        const double norm = sqrt(((red[0] + red[1]) + red[2]) + red[3]);
+        const double norm = sqrt(fold_waves(red));
         const double coef = max_norm / (norm + 1e-6);
         *norm_out = norm;
         *scale_out = float(coef < 1.0 ? coef : 1.0);        // a NaN norm leaves the gradients unscaled: they carry the NaN themselves
@@ -650,6 +511,32 @@ static int check_loss_opts(const ww_loss_opts& o) {
     return WW_OK;
 }
 
+// Host checks of a loss call, before any HIP call, in the one order the three entries keep: n; under `probs` (float32 targets [n][2],
+// a NULL opts_host leaves *o at the defaults it came with) the options; the NULL pointers -- with integer labels and options (`o`
+// given) opts_host among them; the 4-byte and 8-byte alignments; the options of integer labels; the device.  `o` receives the options.
+static int check_loss_call(const void* logits, const void* targets, bool probs, int64_t n, const ww_loss_opts* opts_host, ww_loss_opts* o,
+                           const void* dlogits, const void* loss, const void* stats) {
+    const auto off = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (n <= 0 || n > (int64_t(1) << 30)) return fail(WW_EINVAL, "n %lld: expected 1..2^30", (long long)n);
+    if (probs) {
+        if (opts_host) *o = *opts_host;
+        if (int rc = check_loss_opts(*o)) return rc;
+        if (o->kind != WW_LOSS_CE) return fail(WW_EINVAL, "kind %d: class-probability targets take WW_LOSS_CE only", int(o->kind));
+        if (o->ignore_index != -100)
+            return fail(WW_EINVAL, "ignore_index %lld: class-probability targets take none (leave it at -100)", (long long)o->ignore_index);
+    }
+    if (!logits || !targets) return fail(WW_EINVAL, "null logits / %s pointer", probs ? "targets" : "labels");
+    if (o && !probs && !opts_host) return fail(WW_EINVAL, "null opts_host pointer");
+    if (off(logits, 3) || (probs && off(targets, 3)) || off(dlogits, 3) || off(loss, 3))
+        return fail(WW_EINVAL, "logits_dev / %sdlogits_dev / loss_dev must be 4-byte aligned", probs ? "targets_dev / " : "");
+    if ((!probs && off(targets, 7)) || off(stats, 7)) return fail(WW_EINVAL, "%sstats_dev must be 8-byte aligned", probs ? "" : "labels_dev / ");
+    if (o && !probs) {
+        *o = *opts_host;
+        if (int rc = check_loss_opts(*o)) return rc;
+    }
+    return require_gfx950();
+}
+
 }  // namespace ww
 
 using namespace ww;
@@ -658,46 +545,21 @@ extern "C" {
 
 int ww_ce_loss_f32(const float* logits_dev, const int64_t* labels_dev, int64_t n, float* dlogits_dev, float* loss_dev, ww_loss_stats* stats_dev,
                    ww_stream_t stream) {
-    if (n <= 0 || n > (int64_t(1) << 30)) return fail(WW_EINVAL, "n %lld: expected 1..2^30", (long long)n);
-    if (!logits_dev || !labels_dev) return fail(WW_EINVAL, "null logits / labels pointer");
-    if ((reinterpret_cast<uintptr_t>(logits_dev) & 3) || (reinterpret_cast<uintptr_t>(dlogits_dev) & 3) || (reinterpret_cast<uintptr_t>(loss_dev) & 3))
-        return fail(WW_EINVAL, "logits_dev / dlogits_dev / loss_dev must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(labels_dev) & 7) || (reinterpret_cast<uintptr_t>(stats_dev) & 7))
-        return fail(WW_EINVAL, "labels_dev / stats_dev must be 8-byte aligned");
-    if (int rc = require_gfx950()) return rc;
+    if (int rc = check_loss_call(logits_dev, labels_dev, false, n, nullptr, nullptr, dlogits_dev, loss_dev, stats_dev)) return rc;
     return launch_ce_loss(logits_dev, labels_dev, n, dlogits_dev, loss_dev, stats_dev, static_cast<hipStream_t>(stream));
 }
 
 int ww_ce_loss_ex_f32(const float* logits_dev, const int64_t* labels_dev, int64_t n, const ww_loss_opts* opts_host, float* dlogits_dev,
                       float* loss_dev, ww_loss_stats* stats_dev, ww_stream_t stream) {
-    if (n <= 0 || n > (int64_t(1) << 30)) return fail(WW_EINVAL, "n %lld: expected 1..2^30", (long long)n);
-    if (!logits_dev || !labels_dev) return fail(WW_EINVAL, "null logits / labels pointer");
-    if (!opts_host) return fail(WW_EINVAL, "null opts_host pointer");
-    if ((reinterpret_cast<uintptr_t>(logits_dev) & 3) || (reinterpret_cast<uintptr_t>(dlogits_dev) & 3) || (reinterpret_cast<uintptr_t>(loss_dev) & 3))
-        return fail(WW_EINVAL, "logits_dev / dlogits_dev / loss_dev must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(labels_dev) & 7) || (reinterpret_cast<uintptr_t>(stats_dev) & 7))
-        return fail(WW_EINVAL, "labels_dev / stats_dev must be 8-byte aligned");
-    const ww_loss_opts o = *opts_host;
-    if (int rc = check_loss_opts(o)) return rc;
-    if (int rc = require_gfx950()) return rc;
+    ww_loss_opts o;
+    if (int rc = check_loss_call(logits_dev, labels_dev, false, n, opts_host, &o, dlogits_dev, loss_dev, stats_dev)) return rc;
     return launch_ce_loss_ex(logits_dev, labels_dev, n, o, dlogits_dev, loss_dev, stats_dev, static_cast<hipStream_t>(stream));
 }
 
 int ww_ce_loss_soft_f32(const float* logits_dev, const float* targets_dev, int64_t n, const ww_loss_opts* opts_host, float* dlogits_dev,
                         float* loss_dev, ww_loss_stats* stats_dev, ww_stream_t stream) {
-    if (n <= 0 || n > (int64_t(1) << 30)) return fail(WW_EINVAL, "n %lld: expected 1..2^30", (long long)n);
     ww_loss_opts o = {{1.0, 1.0}, 0.0, 0.0, -100, WW_LOSS_CE, WW_REDUCE_MEAN};             // NULL: nn.CrossEntropyLoss()'s defaults
-    if (opts_host) o = *opts_host;
-    if (int rc = check_loss_opts(o)) return rc;
-    if (o.kind != WW_LOSS_CE) return fail(WW_EINVAL, "kind %d: class-probability targets take WW_LOSS_CE only", int(o.kind));
-    if (o.ignore_index != -100)
-        return fail(WW_EINVAL, "ignore_index %lld: class-probability targets take none (leave it at -100)", (long long)o.ignore_index);
-    if (!logits_dev || !targets_dev) return fail(WW_EINVAL, "null logits / targets pointer");
-    if ((reinterpret_cast<uintptr_t>(logits_dev) & 3) || (reinterpret_cast<uintptr_t>(targets_dev) & 3) ||
-        (reinterpret_cast<uintptr_t>(dlogits_dev) & 3) || (reinterpret_cast<uintptr_t>(loss_dev) & 3))
-        return fail(WW_EINVAL, "logits_dev / targets_dev / dlogits_dev / loss_dev must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(stats_dev) & 7) return fail(WW_EINVAL, "stats_dev must be 8-byte aligned");
-    if (int rc = require_gfx950()) return rc;
+    if (int rc = check_loss_call(logits_dev, targets_dev, true, n, opts_host, &o, dlogits_dev, loss_dev, stats_dev)) return rc;
     return launch_ce_loss_soft(logits_dev, targets_dev, n, o, dlogits_dev, loss_dev, stats_dev, static_cast<hipStream_t>(stream));
 }
 

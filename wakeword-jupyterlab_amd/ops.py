@@ -819,10 +819,14 @@ def read_loss_stats(stats: torch.Tensor) -> dict:
     return out
 
 
-def _check_ce(logits, labels):
+def _check_logits(logits) -> None:
     _require_cuda_f32(logits, "logits")
     if logits.dim() != 2 or logits.shape[1] != 2 or logits.shape[0] == 0 or not logits.is_contiguous():
         raise ValueError(f"logits: expected contiguous [n >= 1, 2], got {tuple(logits.shape)}")
+
+
+def _check_ce(logits, labels):
+    _check_logits(logits)
     if not isinstance(labels, torch.Tensor):
         raise TypeError(f"labels: expected a torch.Tensor, got {type(labels).__name__}")
     if labels.dtype != torch.int64:
@@ -851,21 +855,31 @@ def loss_opts(weight=None, label_smoothing=0.0, ignore_index=-100, reduction="me
     return o
 
 
+def _loss_launch(logits, targets, soft: bool, opts, dlogits, loss, stats) -> None:
+    """ww_ce_loss_soft_f32 on class probabilities (`soft`), else ww_ce_loss_f32 without options and ww_ce_loss_ex_f32 with them."""
+    fn = nat.lib.ww_ce_loss_soft_f32 if soft else nat.lib.ww_ce_loss_f32 if opts is None else nat.lib.ww_ce_loss_ex_f32
+    byref = () if opts is None and not soft else (None if opts is None else C.byref(opts),)      # soft: NULL options are the defaults
+    with torch.cuda.device(logits.device):
+        nat.check(fn(_ptr(logits), _ptr(targets), logits.shape[0], *byref, None if dlogits is None else _ptr(dlogits),
+                     None if loss is None else _ptr(loss), None if stats is None else _ptr(stats), _stream()))
+
+
+def _loss_alloc_launch(logits, targets, soft: bool, opts, stats, grad: bool):
+    """The tail of ce_loss and soft_ce_loss on checked inputs: check the stats record, allocate loss and dlogits, launch."""
+    if stats is not None:
+        _check_stats(stats, logits)
+    loss, dlogits = torch.empty((), device=logits.device, dtype=torch.float32), torch.empty_like(logits) if grad else None
+    _loss_launch(logits, targets, soft, opts, dlogits, loss, stats)
+    return loss, dlogits
+
+
 def ce_loss_into(logits, labels, dlogits, loss, stats, *, weight=None, label_smoothing=0.0, ignore_index=-100, reduction="mean",
                  focal_gamma=None, opts=None) -> None:
     """ww_ce_loss_f32 -- or, with any loss option given, ww_ce_loss_ex_f32 -- on caller-owned outputs (each may be None); `labels` as
     _check_ce returns them.  `opts`: what ops.loss_opts() made of the options, built once by a caller that launches per batch (it wins
     over the keywords).  Allocates nothing on the device."""
-    if opts is None:
-        opts = loss_opts(weight, label_smoothing, ignore_index, reduction, focal_gamma)
-    with torch.cuda.device(logits.device):
-        if opts is None:
-            nat.check(nat.lib.ww_ce_loss_f32(_ptr(logits), _ptr(labels), logits.shape[0], None if dlogits is None else _ptr(dlogits),
-                                             None if loss is None else _ptr(loss), None if stats is None else _ptr(stats), _stream()))
-        else:
-            nat.check(nat.lib.ww_ce_loss_ex_f32(_ptr(logits), _ptr(labels), logits.shape[0], C.byref(opts),
-                                                None if dlogits is None else _ptr(dlogits), None if loss is None else _ptr(loss),
-                                                None if stats is None else _ptr(stats), _stream()))
+    opts = loss_opts(weight, label_smoothing, ignore_index, reduction, focal_gamma) if opts is None else opts
+    _loss_launch(logits, labels, False, opts, dlogits, loss, stats)
 
 
 def ce_loss(logits: torch.Tensor, labels: torch.Tensor, stats=None, grad: bool = True, *, weight=None, label_smoothing=0.0,
@@ -881,20 +895,12 @@ def ce_loss(logits: torch.Tensor, labels: torch.Tensor, stats=None, grad: bool =
     as one option differs from its default, labels equal to `ignore_index` (-100 unless said otherwise) are ignored as torch ignores
     them.  When the mean's denominator is 0 the loss is NaN, as in torch, and the gradient is all zeros, unlike torch's."""
     opts = loss_opts(weight, label_smoothing, ignore_index, reduction, focal_gamma)
-    labels = _check_ce(logits, labels)
-    if stats is not None:
-        _check_stats(stats, logits)
-    loss = torch.empty((), device=logits.device, dtype=torch.float32)
-    dlogits = torch.empty_like(logits) if grad else None
-    ce_loss_into(logits, labels, dlogits, loss, stats, opts=opts)
-    return loss, dlogits
+    return _loss_alloc_launch(logits, _check_ce(logits, labels), False, opts, stats, grad)
 
 
 # ---- class-probability targets: soft cross-entropy and mixup (INTEGRATION.md section 3n; csrc/ww_optim.hip, csrc/ww_mixup.hip) --------
 def _check_soft(logits, targets):
-    _require_cuda_f32(logits, "logits")
-    if logits.dim() != 2 or logits.shape[1] != 2 or logits.shape[0] == 0 or not logits.is_contiguous():
-        raise ValueError(f"logits: expected contiguous [n >= 1, 2], got {tuple(logits.shape)}")
+    _check_logits(logits)
     if not isinstance(targets, torch.Tensor):
         raise TypeError(f"targets: expected a torch.Tensor, got {type(targets).__name__}")
     if targets.dtype != torch.float32:
@@ -921,12 +927,8 @@ def soft_ce_loss_into(logits, targets, dlogits, loss, stats, *, weight=None, lab
                       opts=None) -> None:
     """ww_ce_loss_soft_f32 on caller-owned outputs (each may be None); `opts` as in ce_loss_into (what soft_loss_opts made; it wins
     over the keywords).  Allocates nothing on the device."""
-    if opts is None:
-        opts = soft_loss_opts(weight, label_smoothing, reduction, focal_gamma)
-    with torch.cuda.device(logits.device):
-        nat.check(nat.lib.ww_ce_loss_soft_f32(_ptr(logits), _ptr(targets), logits.shape[0], None if opts is None else C.byref(opts),
-                                              None if dlogits is None else _ptr(dlogits), None if loss is None else _ptr(loss),
-                                              None if stats is None else _ptr(stats), _stream()))
+    opts = soft_loss_opts(weight, label_smoothing, reduction, focal_gamma) if opts is None else opts
+    _loss_launch(logits, targets, True, opts, dlogits, loss, stats)
 
 
 def soft_ce_loss(logits: torch.Tensor, targets: torch.Tensor, stats=None, grad: bool = True, *, weight=None, label_smoothing=0.0,
@@ -939,12 +941,7 @@ def soft_ce_loss(logits: torch.Tensor, targets: torch.Tensor, stats=None, grad: 
     bits.  `focal_gamma` and reduction="none" raise NotImplementedError."""
     opts = soft_loss_opts(weight, label_smoothing, reduction, focal_gamma)
     _check_soft(logits, targets)
-    if stats is not None:
-        _check_stats(stats, logits)
-    loss = torch.empty((), device=logits.device, dtype=torch.float32)
-    dlogits = torch.empty_like(logits) if grad else None
-    soft_ce_loss_into(logits, targets, dlogits, loss, stats, opts=opts)
-    return loss, dlogits
+    return _loss_alloc_launch(logits, targets, True, opts, stats, grad)
 
 
 def _check_mixup(mel, labels, partner, lam):
