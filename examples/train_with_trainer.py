@@ -9,11 +9,13 @@ of the test set -- from counters kept on the device (section 3j) -- and, beyond 
     PYTHONPATH=. python examples/train_with_trainer.py [--epochs 10] [--data DIR] [--duration 1.0] [--background DIR] [--max-grad-norm 1.0]
                                                         [--spec-augment] [--monitor val_acc|val_f1|val_auc]
                                                         [--class-weights balanced|W0,W1] [--label-smoothing E] [--focal-gamma G]
-                                                        [--positive-fraction F] [--mixup]
+                                                        [--positive-fraction F] [--mixup] [--ema DECAY]
 
 Imbalanced data (section 3k): `--class-weights balanced` weighs the classes by the training split's counts, `--label-smoothing` and
 `--focal-gamma` choose the loss of the fused step, `--positive-fraction 0.5` makes every training epoch half wake-word items.
 `--mixup` (section 3n) mixes rows of every training batch on the GPU and trains on the class probabilities that result.
+`--ema 0.999` (section 3o) keeps an exponential moving average of the weights inside the Adam launch; validation, the scheduler, the best
+checkpoint, early stopping and the final test then follow the averaged model, which is also what `ema_wakeword_model.pth` holds.
 """
 import argparse
 import glob
@@ -25,7 +27,7 @@ import torch  # noqa: E402
 
 from train_from_files import split  # noqa: E402
 from wakeword_jupyterlab_amd import (AudioConfig, AudioProcessor, DataLoader, FocalLoss, MixupConfig, SpecAugmentConfig,  # noqa: E402
-                                     TrainingConfig, WakewordDataset, WakewordModel, WakewordTrainer, balanced_class_weights)
+                                     TrainingConfig, WakewordDataset, WakewordModel, WakewordTrainer, WeightAverage, balanced_class_weights)
 from wakeword_jupyterlab_amd.synth import create_sample_data  # noqa: E402
 
 
@@ -65,6 +67,8 @@ def main():
     ap.add_argument("--focal-gamma", type=float, default=None, help="train with the focal loss of this gamma instead of cross-entropy")
     ap.add_argument("--positive-fraction", type=float, default=None,
                     help="share of wake-word items in every training epoch, in (0, 1) (default: the files as they are)")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                    help="keep an exponential moving average of the weights with this decay (with warmup) and evaluate it (default: off)")
     a = ap.parse_args()
     device = torch.device("cuda")
     print(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
@@ -95,8 +99,10 @@ def main():
     val_loader = DataLoader(WakewordDataset(w_va, n_va, processor, augment=False).cache(), batch_size=config.BATCH_SIZE, shuffle=False)
     test_loader = DataLoader(WakewordDataset(w_te, n_te, processor, augment=False).cache(), batch_size=config.BATCH_SIZE, shuffle=False)
     crit = criterion(a, len(n_tr), len(w_tr))
+    ema = WeightAverage(model, mode="ema", decay=a.ema, warmup=True) if a.ema is not None else None
     trainer = WakewordTrainer(model, device, config, checkpoint_path=os.path.join(a.data, "best_wakeword_model.pth"),
-                              max_grad_norm=a.max_grad_norm, monitor=a.monitor, thresholds=(0.8,), criterion=crit.to(device) if crit is not None else None)
+                              max_grad_norm=a.max_grad_norm, monitor=a.monitor, thresholds=(0.8,), criterion=crit.to(device) if crit is not None else None,
+                              average=ema, evaluate="average" if ema is not None else "model")
     print(f"Criterion: {trainer.criterion}")
     best = trainer.train(train_loader, val_loader, config.EPOCHS)
     _, test_acc = trainer.validate(test_loader)
@@ -116,6 +122,9 @@ def main():
               f"threshold for FPR <= 1 %: {report.threshold_for(0.01):.4f}")
     torch.save({"model_state_dict": model.state_dict(), "best_val_acc": best, "device": str(device)},
                os.path.join(a.data, "final_wakeword_model.pth"))
+    if ema is not None:
+        torch.save({"model_state_dict": ema.model.state_dict(), "best_val_acc": best, "n_averaged": ema.n_averaged, "device": str(device)},
+                   os.path.join(a.data, "ema_wakeword_model.pth"))
 
 
 if __name__ == "__main__":

@@ -837,6 +837,30 @@ typedef struct ww_adam_tensor {
 } ww_adam_tensor;   /* 40 bytes */
 WW_API int ww_adam_step_f32(const ww_adam_tensor* tensors_host, int64_t n_tensors, double lr, double beta1, double beta2, double eps,
                             double weight_decay, int64_t step, const float* grad_scale_dev, ww_stream_t stream);
+/* Averaged weights: an exponential moving average (EMA) or an equal-weight average (SWA) of the parameters, kept as one more float32
+ * tensor per parameter.  One rule, used by both entries: a = the averaged value, p = the parameter as stored
+ * (after this step's Adam update), w = avg_weight, rounded ONCE on the host to w32 = (float)w and omw32 = (float)(1 - w):
+ *   w == 1      a = p            a copy: a is NOT read, so a NaN or uninitialised average is simply overwritten
+ *   w == 0      a keeps its bits: nothing is read or written for it (ww_adam_avg_step_f32 then is ww_adam_step_f32)
+ *   w32 < 0.5   a = fmaf(w32, p - a, a)
+ *   otherwise   a = fmaf(-omw32, p - a, p)
+ * which is torch.lerp(a, p, w) with its threshold, each branch an explicit fma, so the bits do not depend on what a compiler contracts
+ * and are the same on the 16-byte and on the one-float path.  The schedule -- which w an update gets -- is the caller's
+ * (average.update_weight: 1 on the first update, then 1 - decay for an EMA or 1 / (n + 1) for SWA).
+ * ww_adam_avg_step_f32: ww_adam_step_f32 with the rule applied to the register value of every p it stores, in the same launch:
+ * avg_host[k] (HOST array of n_tensors DEVICE pointers, read on the host like the table) is the average of tensors_host[k].  36 bytes per
+ * element against Adam's 28.  p, m and v get ww_adam_step_f32's bits; the average is accessed 16 bytes at a time where it shares the phase
+ * of p, g, m and v on the 16-byte grid, one float at a time otherwise, with the same bits.
+ * ww_weight_average_f32: the rule alone, one launch over up to 16 tensors; only p and n of an entry are read (g, m, v may be anything).
+ * For per-epoch SWA, for parameters that got no gradient in a step, and for optimisers other than Adam.
+ * Checked before any HIP call (WW_EINVAL naming the field): everything ww_adam_step_f32 checks (the second entry: n_tensors, n, p);
+ * avg_weight finite and in [0, 1]; avg_host not NULL, every average pointer not NULL and 4-byte aligned; no average's range [a, a + n)
+ * overlapping another average or any p, m, v or g range of the table (the second entry: any p range). */
+WW_API int ww_adam_avg_step_f32(const ww_adam_tensor* tensors_host, float* const* avg_host, int64_t n_tensors, double lr, double beta1,
+                                double beta2, double eps, double weight_decay, int64_t step, const float* grad_scale_dev, double avg_weight,
+                                ww_stream_t stream);
+WW_API int ww_weight_average_f32(const ww_adam_tensor* tensors_host, float* const* avg_host, int64_t n_tensors, double avg_weight,
+                                 ww_stream_t stream);
 /* ww_grad_norm_f32: *norm_dev = the L2 norm over every g of the table (an entry counts once per entry, as clip_grad_norm_ counts a
  * gradient once per parameter), float64 partial sums over 4096 elements each in a fixed order in element coordinates, added by a second
  * kernel; *scale_dev = min(1, max_norm / (norm + 1e-6)), clip_grad_norm_'s coefficient.  Only g and n of the entries are read.

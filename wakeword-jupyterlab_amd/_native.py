@@ -283,6 +283,9 @@ PROTOTYPES = {
     "ww_mixup_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_adam_step_f32": (C.c_int, [C.POINTER(AdamTensor), C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
                                    C.c_void_p, C.c_void_p]),
+    "ww_adam_avg_step_f32": (C.c_int, [C.POINTER(AdamTensor), C.POINTER(C.c_void_p), C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                       C.c_double, C.c_int64, C.c_void_p, C.c_double, C.c_void_p]),
+    "ww_weight_average_f32": (C.c_int, [C.POINTER(AdamTensor), C.POINTER(C.c_void_p), C.c_int64, C.c_double, C.c_void_p]),
     "ww_grad_norm_workspace_bytes": (C.c_int64, [C.POINTER(AdamTensor), C.c_int64]),
     "ww_grad_norm_f32": (C.c_int, [C.POINTER(AdamTensor), C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_clip_metrics_bytes": (C.c_int64, []),

@@ -11,9 +11,16 @@
 //                       All three go through softmax2 and one order of summation, so where their formulas reduce to one another
 //                       (unit options, one-hot rows) so do their bits (tests/test_gpu_loss.py, tests/test_gpu_mixup.py).
 //   adam_kernel         one launch over up to 16 tensors, the table in the kernel arguments; torch's single-tensor Adam arithmetic
+//   adam_avg_kernel     the same launch with an averaged copy of the weights (EMA / SWA): after adam_one the
+//                       register value of p goes through avg_one into a second tensor -- one more read and one more write per
+//                       element, 36 bytes against Adam's 28 (32 when the weight is 1: the average is then written, never read);
+//                       p, m and v take the path and get the bits of adam_kernel
+//   weight_average_kernel  the averaging alone over the same table layout: reads p, writes the average, 12 bytes per element (8 when the
+//                       weight is 1).  Both are memory-bound, 256 threads with one 16-byte vector per lane, no atomics and no LDS.
 //   grad_norm_kernel    float64 partial sums of g^2 per 4096 elements; grad_norm_finish_kernel adds them and writes norm and clip scale
-// All three are memory- and latency-bound.  No float atomics anywhere: every sum has one order, so results repeat bit for bit.
+// All of them are memory- and latency-bound.  No float atomics anywhere: every sum has one order, so results repeat bit for bit.
 #include <cmath>
+#include <type_traits>
 
 #include "ww_internal.h"
 
@@ -329,14 +336,50 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
     p = p - s.lr_c1 * (m / denom);
 }
 
+// The averaged weights: one average pointer per entry of the tensor table, and the weight w of this update
+// as the host rounded it from double -- w32 = float(w), omw32 = float(1 - w).  A weight of 0 never reaches a kernel (the average
+// keeps its bits: nothing is launched for it), so three rules remain.
+constexpr int kAvgCopy = 0, kAvgLow = 1, kAvgHigh = 2;     // w == 1;  w32 < 0.5 (torch.lerp's threshold);  the rest
+struct AvgArgs {
+    float* a[kMaxTensors];
+    float w32, omw32;
+    int32_t rule;
+};
+struct NoAvg {};                                            // the plain Adam launch: no average in the kernel arguments
+
+// torch.lerp(a, p, w) with each branch one explicit fma of the one difference p - a: nothing is left for the compiler to contract.
+__device__ __forceinline__ float avg_one(float a, float p, float w32, float omw32, bool low) {
+    const float d = p - a;
+    return low ? fmaf(w32, d, a) : fmaf(-omw32, d, p);
+}
+
+__device__ __forceinline__ int phase_of(const void* ptr) { return int((reinterpret_cast<uintptr_t>(ptr) >> 2) & 3); }
+
 // A block owns 256 vectors of one tensor.  Vectors are laid on the 16-byte grid of the ADDRESSES: with a = the phase of p in floats,
 // vector q holds the elements 4 q - a .. 4 q - a + 3, so a tensor that starts between grid lines gets a scalar head and tail and 16-byte
 // accesses between them -- when p, g, m and v share the phase (views cut the same way do); otherwise every element goes alone.
-__global__ __launch_bounds__(kAdamThreads) void adam_kernel(const TensorTable tab, const AdamScalars s, const float* __restrict__ grad_scale) {
+// With an average (A = AvgArgs) the value of p that is stored also goes through avg_one; under kAvgCopy the average is written and
+// never loaded, so whatever it held (NaN, uninitialised memory) is gone.  The average never decides which path Adam takes: the compiler
+// contracts adam_one's sums of two products differently on the two paths (v differs in its last bit), and p, m and v must be
+// ww_adam_step_f32's bit for bit.  So on the 16-byte path an average of another phase is read and written one float at a time; its own
+// bits do not depend on that (avg_one is explicit fmas).
+template <class A>
+__device__ __forceinline__ void adam_block(const TensorTable& tab, const AdamScalars& s, const float* __restrict__ grad_scale, const A& avg) {
+    constexpr bool kAvg = !std::is_same<A, NoAvg>::value;
     const int k = tensor_of(tab, int(blockIdx.x));
     const ww_adam_tensor t = tab.t[k];
     const float scale = grad_scale ? *grad_scale : 1.0f;
     const int a = int((reinterpret_cast<uintptr_t>(t.p) >> 2) & 3);
+    float* av = nullptr;
+    bool read_avg = false, low = false, avg_wide = false;
+    float w32 = 0.f, omw32 = 0.f;
+    if constexpr (kAvg) {
+        av = avg.a[k];
+        avg_wide = a == phase_of(av);
+        read_avg = avg.rule != kAvgCopy;
+        low = avg.rule == kAvgLow;
+        w32 = avg.w32; omw32 = avg.omw32;
+    }
     const bool same = a == int((reinterpret_cast<uintptr_t>(t.g) >> 2) & 3) && a == int((reinterpret_cast<uintptr_t>(t.m) >> 2) & 3) &&
                       a == int((reinterpret_cast<uintptr_t>(t.v) >> 2) & 3);
     const int shift = same ? a : 0;
@@ -348,6 +391,13 @@ __global__ __launch_bounds__(kAdamThreads) void adam_kernel(const TensorTable ta
         const float4 g = *reinterpret_cast<const float4*>(t.g + e0);
         float4 m = *reinterpret_cast<const float4*>(t.m + e0);
         float4 v = *reinterpret_cast<const float4*>(t.v + e0);
+        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (kAvg) {
+            if (read_avg) {
+                if (avg_wide) x = *reinterpret_cast<const float4*>(av + e0);
+                else x = make_float4(av[e0], av[e0 + 1], av[e0 + 2], av[e0 + 3]);
+            }
+        }
         adam_one(p.x, g.x, m.x, v.x, scale, s);
         adam_one(p.y, g.y, m.y, v.y, scale, s);
         adam_one(p.z, g.z, m.z, v.z, scale, s);
@@ -355,6 +405,21 @@ __global__ __launch_bounds__(kAdamThreads) void adam_kernel(const TensorTable ta
         *reinterpret_cast<float4*>(t.p + e0) = p;
         *reinterpret_cast<float4*>(t.m + e0) = m;
         *reinterpret_cast<float4*>(t.v + e0) = v;
+        if constexpr (kAvg) {
+            if (read_avg) {
+                x.x = avg_one(x.x, p.x, w32, omw32, low);
+                x.y = avg_one(x.y, p.y, w32, omw32, low);
+                x.z = avg_one(x.z, p.z, w32, omw32, low);
+                x.w = avg_one(x.w, p.w, w32, omw32, low);
+            } else {
+                x = p;
+            }
+            if (avg_wide) {
+                *reinterpret_cast<float4*>(av + e0) = x;
+            } else {
+                av[e0] = x.x; av[e0 + 1] = x.y; av[e0 + 2] = x.z; av[e0 + 3] = x.w;
+            }
+        }
         return;
     }
 #pragma unroll
@@ -364,6 +429,53 @@ __global__ __launch_bounds__(kAdamThreads) void adam_kernel(const TensorTable ta
         float p = t.p[e], m = t.m[e], v = t.v[e];
         adam_one(p, t.g[e], m, v, scale, s);
         t.p[e] = p; t.m[e] = m; t.v[e] = v;
+        if constexpr (kAvg) av[e] = read_avg ? avg_one(av[e], p, w32, omw32, low) : p;
+    }
+}
+
+__global__ __launch_bounds__(kAdamThreads) void adam_kernel(const TensorTable tab, const AdamScalars s, const float* __restrict__ grad_scale) {
+    adam_block(tab, s, grad_scale, NoAvg{});
+}
+
+__global__ __launch_bounds__(kAdamThreads) void adam_avg_kernel(const TensorTable tab, const AdamScalars s, const float* __restrict__ grad_scale,
+                                                                const AvgArgs avg) {
+    adam_block(tab, s, grad_scale, avg);
+}
+
+// The averaging alone: avg_one over the p of every entry (g, m and v of the table are not read), the block decomposition of adam_kernel
+// with the phases of p and the average deciding between the 16-byte and the one-float path.  The bits are those of adam_avg_kernel.
+__global__ __launch_bounds__(kAdamThreads) void weight_average_kernel(const TensorTable tab, const AvgArgs avg) {
+    const int k = tensor_of(tab, int(blockIdx.x));
+    const float* __restrict__ src = tab.t[k].p;
+    float* __restrict__ av = avg.a[k];
+    const int64_t n = tab.t[k].n;
+    const int a = phase_of(src);
+    const bool same = a == phase_of(av);
+    const bool read_avg = avg.rule != kAvgCopy, low = avg.rule == kAvgLow;
+    const float w32 = avg.w32, omw32 = avg.omw32;
+    const int shift = same ? a : 0;
+    const int64_t q = int64_t(int(blockIdx.x) - tab.first_block[k]) * kAdamThreads + threadIdx.x;
+    const int64_t e0 = 4 * q - shift;
+    if (e0 >= n) return;
+    if (same && e0 >= 0 && e0 + 4 <= n) {
+        const float4 p = *reinterpret_cast<const float4*>(src + e0);
+        float4 x = p;
+        if (read_avg) {
+            x = *reinterpret_cast<const float4*>(av + e0);
+            x.x = avg_one(x.x, p.x, w32, omw32, low);
+            x.y = avg_one(x.y, p.y, w32, omw32, low);
+            x.z = avg_one(x.z, p.z, w32, omw32, low);
+            x.w = avg_one(x.w, p.w, w32, omw32, low);
+        }
+        *reinterpret_cast<float4*>(av + e0) = x;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t e = e0 + j;
+        if (e < 0 || e >= n) continue;
+        const float p = src[e];
+        av[e] = read_avg ? avg_one(av[e], p, w32, omw32, low) : p;
     }
 }
 
@@ -386,6 +498,40 @@ int launch_adam(const ww_adam_tensor* tensors, int n_tensors, const AdamScalars&
     TensorTable tab;
     if (int rc = fill_table(tensors, n_tensors, kAdamChunk, &tab)) return rc;
     hipLaunchKernelGGL(adam_kernel, dim3(unsigned(tab.first_block[kMaxTensors])), dim3(kAdamThreads), 0, stream, tab, s, grad_scale);
+    WW_HIP(hipGetLastError());
+    return WW_OK;
+}
+
+// The kernel arguments of an averaging launch from the weight in double: the two float32 roundings and the rule.  The comparison with
+// 0.5 is made on w32, the value torch.lerp compares.  Callers send a weight of 0 nowhere near a kernel.
+static AvgArgs avg_args(float* const* avg, int n_tensors, double weight) {
+    AvgArgs a;
+    for (int k = 0; k < kMaxTensors; ++k) a.a[k] = k < n_tensors ? avg[k] : nullptr;
+    a.w32 = float(weight);
+    a.omw32 = float(1.0 - weight);
+    a.rule = weight == 1.0 ? kAvgCopy : a.w32 < 0.5f ? kAvgLow : kAvgHigh;
+    return a;
+}
+
+int launch_adam_avg(const ww_adam_tensor* tensors, float* const* avg, int n_tensors, const AdamScalars& s, const float* grad_scale, double weight,
+                    hipStream_t stream) {
+    if (weight == 0.0) return launch_adam(tensors, n_tensors, s, grad_scale, stream);      // the average keeps its bits: the plain kernel
+    TensorTable tab;
+    if (int rc = fill_table(tensors, n_tensors, kAdamChunk, &tab)) return rc;
+    hipLaunchKernelGGL(adam_avg_kernel, dim3(unsigned(tab.first_block[kMaxTensors])), dim3(kAdamThreads), 0, stream, tab, s, grad_scale,
+                       avg_args(avg, n_tensors, weight));
+    WW_HIP(hipGetLastError());
+    return WW_OK;
+}
+
+int launch_weight_average(const ww_adam_tensor* tensors, float* const* avg, int n_tensors, double weight, hipStream_t stream) {
+    if (weight == 0.0) return WW_OK;                        // nothing moves: nothing is launched
+    TensorTable tab;
+    ww_adam_tensor only_p[kMaxTensors];                     // g, m and v of the caller's table are not read: they do not travel either
+    for (int k = 0; k < n_tensors; ++k) only_p[k] = ww_adam_tensor{tensors[k].p, nullptr, nullptr, nullptr, tensors[k].n};
+    if (int rc = fill_table(only_p, n_tensors, kAdamChunk, &tab)) return rc;
+    hipLaunchKernelGGL(weight_average_kernel, dim3(unsigned(tab.first_block[kMaxTensors])), dim3(kAdamThreads), 0, stream, tab,
+                       avg_args(avg, n_tensors, weight));
     WW_HIP(hipGetLastError());
     return WW_OK;
 }
@@ -496,6 +642,65 @@ static int check_table(const ww_adam_tensor* tensors, int64_t n_tensors, bool st
     return WW_OK;
 }
 
+// Host checks of an averaging call, before any HIP call.  `adam`: the table went through check_table(..., true) and its g, m and v are
+// live as well as p; otherwise only p and n of an entry are read, and they are checked here.  An average is written, so its range may
+// meet no other average and nothing of the table that the launch reads or writes -- the gradients included.
+static int check_average(const ww_adam_tensor* tensors, float* const* avg, int64_t n_tensors, double weight, bool adam) {
+    if (!adam) {
+        if (n_tensors < 1 || n_tensors > kMaxTensors) return fail(WW_EINVAL, "n_tensors %lld: expected 1..%d", (long long)n_tensors, kMaxTensors);
+        if (!tensors) return fail(WW_EINVAL, "null tensors pointer");
+        for (int k = 0; k < int(n_tensors); ++k) {
+            if (tensors[k].n <= 0 || tensors[k].n > (int64_t(1) << 40))
+                return fail(WW_EINVAL, "tensors[%d].n %lld: expected 1..2^40", k, (long long)tensors[k].n);
+            if (!tensors[k].p) return fail(WW_EINVAL, "tensors[%d]: null p pointer", k);
+            if (reinterpret_cast<uintptr_t>(tensors[k].p) & 3) return fail(WW_EINVAL, "tensors[%d]: p must be 4-byte aligned", k);
+        }
+    }
+    if (!(weight >= 0.0 && weight <= 1.0)) return fail(WW_EINVAL, "avg_weight %g: expected [0, 1]", weight);
+    if (!avg) return fail(WW_EINVAL, "null avg_host pointer");
+    for (int k = 0; k < int(n_tensors); ++k) {
+        if (!avg[k]) return fail(WW_EINVAL, "avg_host[%d]: null pointer", k);
+        if (reinterpret_cast<uintptr_t>(avg[k]) & 3) return fail(WW_EINVAL, "avg_host[%d] must be 4-byte aligned", k);
+    }
+    const auto meets = [](const void* x, const void* y, int64_t nx, int64_t ny) {
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(x), a1 = a0 + uintptr_t(nx) * 4;
+        const uintptr_t b0 = reinterpret_cast<uintptr_t>(y), b1 = b0 + uintptr_t(ny) * 4;
+        return a0 < b1 && b0 < a1;
+    };
+    for (int i = 0; i < int(n_tensors); ++i)
+        for (int j = 0; j < int(n_tensors); ++j) {
+            const ww_adam_tensor& t = tensors[j];
+            if (j > i && meets(avg[i], avg[j], tensors[i].n, t.n)) return fail(WW_EINVAL, "avg_host[%d] and avg_host[%d]: ranges overlap", i, j);
+            if (meets(avg[i], t.p, tensors[i].n, t.n) ||
+                (adam && (meets(avg[i], t.g, tensors[i].n, t.n) || meets(avg[i], t.m, tensors[i].n, t.n) || meets(avg[i], t.v, tensors[i].n, t.n))))
+                return fail(WW_EINVAL, "avg_host[%d] and tensors[%d]: the average's range overlaps %s", i, j, adam ? "p / g / m / v" : "p");
+        }
+    return WW_OK;
+}
+
+// Host checks of an Adam call's scalars and table, before any HIP call, and the kernel's float32 scalars: the bias corrections in
+// double, as torch computes them, then one rounding.
+static int adam_prepare(const ww_adam_tensor* tensors_host, int64_t n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
+                        int64_t step, const float* grad_scale_dev, AdamScalars* s) {
+    if (!(lr >= 0.0) || std::isinf(lr)) return fail(WW_EINVAL, "lr %g: expected a finite value >= 0", lr);
+    if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail(WW_EINVAL, "beta1 %g: expected [0, 1)", beta1);
+    if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail(WW_EINVAL, "beta2 %g: expected [0, 1)", beta2);
+    if (!(eps > 0.0) || std::isinf(eps)) return fail(WW_EINVAL, "eps %g: expected a finite value > 0", eps);
+    if (!(weight_decay >= 0.0) || std::isinf(weight_decay)) return fail(WW_EINVAL, "weight_decay %g: expected a finite value >= 0", weight_decay);
+    if (step < 1) return fail(WW_EINVAL, "step %lld: expected >= 1", (long long)step);
+    if (int rc = check_table(tensors_host, n_tensors, true)) return rc;
+    if (reinterpret_cast<uintptr_t>(grad_scale_dev) & 3) return fail(WW_EINVAL, "grad_scale_dev must be 4-byte aligned");
+    const double c1 = 1.0 - std::pow(beta1, double(step)), c2 = 1.0 - std::pow(beta2, double(step));
+    s->lr_c1 = float(lr / c1);
+    s->inv_c2_sqrt = float(1.0 / std::sqrt(c2));
+    s->eps = float(eps);
+    s->omb1 = float(1.0 - beta1);
+    s->beta2 = float(beta2);
+    s->omb2 = float(1.0 - beta2);
+    s->weight_decay = float(weight_decay);
+    return WW_OK;
+}
+
 // Host checks of the loss options, before any HIP call: what ww_ce_loss_ex_f32 and ww_ce_loss_soft_f32 share.
 static int check_loss_opts(const ww_loss_opts& o) {
     for (int c = 0; c < 2; ++c)
@@ -565,26 +770,25 @@ int ww_ce_loss_soft_f32(const float* logits_dev, const float* targets_dev, int64
 
 int ww_adam_step_f32(const ww_adam_tensor* tensors_host, int64_t n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
                      int64_t step, const float* grad_scale_dev, ww_stream_t stream) {
-    if (!(lr >= 0.0) || std::isinf(lr)) return fail(WW_EINVAL, "lr %g: expected a finite value >= 0", lr);
-    if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail(WW_EINVAL, "beta1 %g: expected [0, 1)", beta1);
-    if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail(WW_EINVAL, "beta2 %g: expected [0, 1)", beta2);
-    if (!(eps > 0.0) || std::isinf(eps)) return fail(WW_EINVAL, "eps %g: expected a finite value > 0", eps);
-    if (!(weight_decay >= 0.0) || std::isinf(weight_decay)) return fail(WW_EINVAL, "weight_decay %g: expected a finite value >= 0", weight_decay);
-    if (step < 1) return fail(WW_EINVAL, "step %lld: expected >= 1", (long long)step);
-    if (int rc = check_table(tensors_host, n_tensors, true)) return rc;
-    if (reinterpret_cast<uintptr_t>(grad_scale_dev) & 3) return fail(WW_EINVAL, "grad_scale_dev must be 4-byte aligned");
-    // the bias corrections in double, as torch computes them, then one rounding to the kernel's float32
-    const double c1 = 1.0 - std::pow(beta1, double(step)), c2 = 1.0 - std::pow(beta2, double(step));
     AdamScalars s;
-    s.lr_c1 = float(lr / c1);
-    s.inv_c2_sqrt = float(1.0 / std::sqrt(c2));
-    s.eps = float(eps);
-    s.omb1 = float(1.0 - beta1);
-    s.beta2 = float(beta2);
-    s.omb2 = float(1.0 - beta2);
-    s.weight_decay = float(weight_decay);
+    if (int rc = adam_prepare(tensors_host, n_tensors, lr, beta1, beta2, eps, weight_decay, step, grad_scale_dev, &s)) return rc;
     if (int rc = require_gfx950()) return rc;
     return launch_adam(tensors_host, int(n_tensors), s, grad_scale_dev, static_cast<hipStream_t>(stream));
+}
+
+int ww_adam_avg_step_f32(const ww_adam_tensor* tensors_host, float* const* avg_host, int64_t n_tensors, double lr, double beta1, double beta2,
+                         double eps, double weight_decay, int64_t step, const float* grad_scale_dev, double avg_weight, ww_stream_t stream) {
+    AdamScalars s;
+    if (int rc = adam_prepare(tensors_host, n_tensors, lr, beta1, beta2, eps, weight_decay, step, grad_scale_dev, &s)) return rc;
+    if (int rc = check_average(tensors_host, avg_host, n_tensors, avg_weight, true)) return rc;
+    if (int rc = require_gfx950()) return rc;
+    return launch_adam_avg(tensors_host, avg_host, int(n_tensors), s, grad_scale_dev, avg_weight, static_cast<hipStream_t>(stream));
+}
+
+int ww_weight_average_f32(const ww_adam_tensor* tensors_host, float* const* avg_host, int64_t n_tensors, double avg_weight, ww_stream_t stream) {
+    if (int rc = check_average(tensors_host, avg_host, n_tensors, avg_weight, false)) return rc;
+    if (int rc = require_gfx950()) return rc;
+    return launch_weight_average(tensors_host, avg_host, int(n_tensors), avg_weight, static_cast<hipStream_t>(stream));
 }
 
 int64_t ww_grad_norm_workspace_bytes(const ww_adam_tensor* tensors_host, int64_t n_tensors) {

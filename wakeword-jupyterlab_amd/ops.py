@@ -1199,6 +1199,68 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, *, lr, betas, eps, weight_de
     adam_launch(tab, grads[0].device, lr, betas, eps, weight_decay, step, grad_scale)
 
 
+def average_pointers(avgs, params=None):
+    """A list of float32 GPU tensors (the averaged copies of up to 16 parameters) -> the ctypes pointer array ww_adam_avg_step_f32 and
+    ww_weight_average_f32 take beside an adam_table.  With `params`, every average must have its parameter's size and device."""
+    n = len(avgs)
+    if not 1 <= n <= nat.ADAM_MAX_TENSORS:
+        raise ValueError(f"{n} tensors: one launch takes 1..{nat.ADAM_MAX_TENSORS}")
+    if params is not None and len(params) != n:
+        raise ValueError("params and avgs differ in length")
+    ptrs = (C.c_void_p * n)()
+    for k, a in enumerate(avgs):
+        _require_cuda_f32(a, f"average {k}")
+        if not a.is_contiguous():
+            raise RuntimeError(f"average {k} is not contiguous")
+        if params is not None and (a.numel() != params[k].numel() or a.device != params[k].device):
+            raise ValueError(f"average {k}: {a.numel()} elements on {a.device}, its parameter has {params[k].numel()} on {params[k].device}")
+        ptrs[k] = a.data_ptr()
+    return ptrs
+
+
+def adam_average_launch(table, avg_ptrs, device, lr, betas, eps, weight_decay, step, avg_weight, grad_scale=None) -> None:
+    """ww_adam_avg_step_f32 on a prepared adam_table and its average_pointers: the Adam step and the averaging of its result in one
+    launch.  `avg_weight` comes from average.update_weight.  Allocates nothing."""
+    if len(avg_ptrs) != len(table):
+        raise ValueError(f"{len(avg_ptrs)} averages for a table of {len(table)}")
+    with torch.cuda.device(device):
+        nat.check(nat.lib.ww_adam_avg_step_f32(table, avg_ptrs, len(table), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                               float(weight_decay), int(step), None if grad_scale is None else _ptr(grad_scale),
+                                               float(avg_weight), _stream()))
+
+
+def adam_average_step(params, grads, exp_avgs, exp_avg_sqs, avgs, *, lr, betas, eps, weight_decay, step, avg_weight, grad_scale=None) -> None:
+    """adam_step with the averaging of its result in the same launch (ww_adam_avg_step_f32): avgs[k] <- lerp(avgs[k], params[k], avg_weight)
+    with the parameter as this step leaves it.  Version counters do not move (optim.FusedAdam bumps them)."""
+    tab = adam_table(params, grads, exp_avgs, exp_avg_sqs)
+    ptrs = average_pointers(avgs, params)
+    if grad_scale is not None:
+        _require_cuda_f32(grad_scale, "grad_scale")
+        if grad_scale.numel() != 1 or grad_scale.device != grads[0].device:
+            raise ValueError("grad_scale: expected one float32 on the gradients' device")
+    adam_average_launch(tab, ptrs, grads[0].device, lr, betas, eps, weight_decay, step, avg_weight, grad_scale)
+
+
+def weight_average_launch(table, avg_ptrs, device, avg_weight) -> None:
+    """ww_weight_average_f32 on a prepared table (only its p and n are read) and its average_pointers.  Allocates nothing."""
+    if len(avg_ptrs) != len(table):
+        raise ValueError(f"{len(avg_ptrs)} averages for a table of {len(table)}")
+    with torch.cuda.device(device):
+        nat.check(nat.lib.ww_weight_average_f32(table, avg_ptrs, len(table), float(avg_weight), _stream()))
+
+
+def weight_average(params, avgs, weight: float) -> None:
+    """avgs[k] <- lerp(avgs[k], params[k], weight) in place, one launch per 16 tensors (ww_weight_average_f32): weight 1 copies without
+    reading the average, weight 0 leaves it alone.  The averages are written behind autograd's back: their version counters do not
+    move (average.WeightAverage bumps them)."""
+    params, avgs = list(params), list(avgs)
+    if len(params) != len(avgs):
+        raise ValueError("params and avgs differ in length")
+    for i in range(0, len(params), nat.ADAM_MAX_TENSORS):
+        ps = params[i:i + nat.ADAM_MAX_TENSORS]
+        weight_average_launch(adam_table(ps, ps, ps, ps), average_pointers(avgs[i:i + nat.ADAM_MAX_TENSORS], ps), ps[0].device, weight)
+
+
 def grad_norm_workspace(table, device) -> torch.Tensor:
     return torch.empty(max(256, nat.check(nat.lib.ww_grad_norm_workspace_bytes(table, len(table)))), device=device, dtype=torch.uint8)
 

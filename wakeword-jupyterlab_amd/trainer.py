@@ -20,6 +20,11 @@ A float32 target [B, 2] holds class probabilities (mixup through `processor.set_
 the soft cross-entropy (ww_ce_loss_soft_f32) in the loss's place, the launch count unchanged; `validate` keeps integer labels
 (INTEGRATION.md section 3n).
 
+`average=` (average.WeightAverage around the same model) keeps an EMA or SWA of the weights: an every="step"
+average is written by the Adam launch itself (ww_adam_avg_step_f32 in ww_adam_step_f32's place -- `step` issues the same number of native
+calls), an every="epoch" one is updated once after `train_epoch`.  `evaluate="average"` makes `validate`, `val_report`, the monitor, the
+scheduler, early stopping and the best checkpoint follow `average.model`; the checkpoint gains "average_state_dict" when an average is set.
+
 One deliberate difference: the reference calls `clip_grad_norm_` BEFORE `backward()`, where it clips the previous batch's gradients or
 nothing, so the default here is no clipping; `max_grad_norm=1.0` gives the clip the call meant, after the
 backward.
@@ -40,11 +45,12 @@ from .optim import FusedAdam
 
 MONITORS = ("val_acc", "val_f1", "val_auc")
 MONITOR_NAMES = {"val_acc": "Acc", "val_f1": "F1", "val_auc": "AUC"}
+EVALUATE = ("model", "average")
 
 
 class WakewordTrainer:
     def __init__(self, model, device, config=TrainingConfig, *, checkpoint_path="best_wakeword_model.pth", max_grad_norm=None,
-                 monitor="val_acc", thresholds=(0.8,), criterion=None, ledger=None, val_ledger=None):
+                 monitor="val_acc", thresholds=(0.8,), criterion=None, ledger=None, val_ledger=None, average=None, evaluate="model"):
         if not isinstance(model, (SimpleWakewordModel, WakewordModel)):
             raise TypeError(f"WakewordTrainer drives the HIP training kernels of SimpleWakewordModel and WakewordModel; got {type(model).__name__}")
         if any(p.device.type != "cuda" for p in model.parameters()):
@@ -53,7 +59,15 @@ class WakewordTrainer:
             raise ValueError(f"max_grad_norm {max_grad_norm}: expected a positive number or None")
         if monitor not in MONITORS:
             raise ValueError(f"monitor {monitor!r}: expected one of {MONITORS}")
+        if evaluate not in EVALUATE:
+            raise ValueError(f"evaluate {evaluate!r}: expected one of {EVALUATE}")
+        if evaluate == "average" and average is None:
+            raise ValueError("evaluate='average' needs an average: WakewordTrainer(..., average=WeightAverage(model))")
+        if average is not None and any(average.average_of(p) is None for p in model.parameters()):
+            raise ValueError("average: it was built around another model (WeightAverage(model) takes the model that is trained)")
         self.monitor = monitor
+        self.evaluate = evaluate
+        self.average = average                                         # average.WeightAverage or None
         self.model = model
         self.device = device
         self.config = config
@@ -65,6 +79,7 @@ class WakewordTrainer:
         # the reference's attribute; `step` and `validate` compute the same loss in ww_ce_loss_f32 / ww_ce_loss_ex_f32 (the property below)
         self.criterion = nn.CrossEntropyLoss().to(device) if criterion is None else criterion
         self.optimizer = FusedAdam(model.parameters(), lr=config.LEARNING_RATE, weight_decay=1e-5)
+        self.optimizer.average = average                               # an every="step" average rides in the Adam launch
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="max", factor=0.5, patience=5)
 
         self.train_losses = []
@@ -285,10 +300,14 @@ class WakewordTrainer:
                 self.step(data, target)
             else:
                 self.step(data, target, self._entries_of(train_loader), getattr(train_loader, "last_labels", None))
-        return self._finish_epoch(self.train_stats, "train_epoch")
+        result = self._finish_epoch(self.train_stats, "train_epoch")
+        if self.average is not None and self.average.every == "epoch":
+            self.average.update()
+        return result
 
     def validate(self, val_loader):
         self.model.eval()
+        model = self.average.model.eval() if self.evaluate == "average" else self.model
         self.val_stats.zero_()
         ops.reset_clip_metrics(self.val_metrics)
         self._val_report = None
@@ -299,7 +318,7 @@ class WakewordTrainer:
             for data, target in val_loader:
                 if data.device != self._dev:
                     data = data.to(self._dev)
-                output = self.model(data)
+                output = model(data)
                 y = self._target(target, output.shape[0])
                 ops.ce_loss_into(output, y, None, None, self.val_stats, opts=self._loss_opts)
                 ops.clip_metrics_update_into(output, y, self.val_metrics)
@@ -360,8 +379,11 @@ class WakewordTrainer:
                 self.best_monitor = monitored
                 self.best_val_acc = val_acc                  # the accuracy of the best epoch by the monitor
                 self.epochs_no_improve = 0
-                torch.save({"epoch": epoch, "model_state_dict": self.model.state_dict(), "optimizer_state_dict": self.optimizer.state_dict(),
-                            "val_acc": val_acc, "train_acc": train_acc, "train_loss": train_loss, "val_loss": val_loss}, self.checkpoint_path)
+                ckpt = {"epoch": epoch, "model_state_dict": self.model.state_dict(), "optimizer_state_dict": self.optimizer.state_dict(),
+                        "val_acc": val_acc, "train_acc": train_acc, "train_loss": train_loss, "val_loss": val_loss}
+                if self.average is not None:
+                    ckpt["average_state_dict"] = self.average.state_dict()
+                torch.save(ckpt, self.checkpoint_path)
                 print(f"New best model saved! Validation accuracy: {val_acc:.2f}%")
             else:
                 self.epochs_no_improve += 1
