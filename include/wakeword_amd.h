@@ -387,7 +387,16 @@ WW_API int ww_kaiser_best_host(float* out_host);
  *   normalize    != 0: divide the clip by max|x| first (process_audio_file order, :131-133);
  *                a silent clip then yields NaN, as the reference does
  *   logmel_dev   [n_clips][80][32]  (== the [B,1,80,32] tensor WakewordDataset.__getitem__ :204-216
- *                returns, batched), dB in [-80, 0] with per-clip max exactly 0 */
+ *                returns, batched), dB in [-80, 0] with per-clip max exactly 0
+ * Non-finite samples: a clip with a NaN or an Inf among its clip_len samples gives NaN in EVERY output of its row, in all three
+ * arithmetics and with either `normalize` -- what x / np.max(np.abs(x)) and power_to_db(ref=np.max) make of it (the per-clip maximum
+ * is NaN once any mel power is NaN or Inf).  The other rows of the batch keep their bits; samples past clip_len are never read.
+ * Signal level (normalize != 0): a gain of 2^k changes no output bit for |k| <= 31 in any arithmetic (int16 or int32 PCM may be passed
+ * unscaled), in float64 mode for |k| <= 60 (tests/test_gpu_logmel_nonfinite.py).  Measured on MI355X (profiles/logmel_levels.json,
+ * clips of peak 0.01 .. 1 times 2^k): float64 mode stays within 1e-4 dB of the reference for 2^-100 .. 2^100.  The float32 kernel
+ * (float32 and auto mode) squares the raw samples and applies 1 / peak^2 to the mel powers: within 1e-4 dB for 2^-50 .. 2^50; at
+ * 2^60 and beyond (powers or peak^2 overflow) and at 2^-70 and below (1 / peak^2 overflows) the row is all NaN; around 2^-60 the
+ * powers go subnormal and auto mode gave a finite but wrong image for a noise-free clip.  Scale such material first, or use float64. */
 WW_API int ww_logmel_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len,
                   int normalize, float* logmel_dev, ww_stream_t stream);
 
@@ -395,7 +404,8 @@ WW_API int ww_logmel_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_str
  *   pcm_dev      rows of clip_len valid samples as above, 0 < clip_len <= n_samples; rows are right-zero-padded to n_samples
  *   n_samples    N in [WW_MIN_CLIP_SAMPLES, WW_MAX_CLIP_SAMPLES]; T = 1 + N / 512 frames
  *   logmel_dev   [n_clips][80][T], dB in [-80, 0], per-clip max (over all T frames) exactly 0
- * Same arithmetic modes (ww_set_logmel_math); N with T = 32 (16,000 samples among them) runs the 1 s kernel, bit for bit. */
+ * Same arithmetic modes (ww_set_logmel_math); N with T = 32 (16,000 samples among them) runs the 1 s kernel, bit for bit.
+ * Non-finite samples and signal level: ww_logmel_f32's rules (a NaN or Inf among a row's clip_len samples: the whole row is NaN). */
 WW_API int ww_logmel_frames_f32(const float* pcm_dev, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples,
                                 int normalize, float* logmel_dev, ww_stream_t stream);
 

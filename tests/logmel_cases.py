@@ -1,0 +1,140 @@
+"""Shared cases for the log-mel tests on non-finite samples and extreme levels (plain numpy, seeded): the host tests pin what the
+oracle makes of them, the GPU tests hold the three arithmetics of K1 to it.
+
+The reference turns a clip with one NaN or Inf sample into an all-NaN image: `audio / np.max(np.abs(audio))` makes every sample NaN
+when the maximum is NaN (np.max keeps it) and leaves Inf / Inf = NaN when it is Inf; power_to_db(ref=np.max) then subtracts 10 log10
+of a maximum that is NaN -- or Inf -- from every value, so without the normalisation the result is the same."""
+import numpy as np
+
+from oracle import mel_oracle
+from wakeword_jupyterlab_amd import synth
+
+QNAN_NEG = 0xFFC00000          # quiet NaN with the sign bit set
+SNAN = 0x7F800001              # a signalling pattern
+# x * 2^k for these k must not change one output bit with normalize=True (tests: *_power_of_two_gain_*); see level_gains
+POW2_GAINS = (-31, -20, -8, 8, 15, 31)
+POW2_GAINS_F64 = (-60, 60)
+
+
+def f32_from_bits(bits):
+    return np.array([bits], dtype=np.uint32).view(np.float32)[0]
+
+
+def tones(n):
+    """Noise-free signals (tests/test_gpu_duration._tones): bands 60-80 dB under the peak sit on a float32 FFT's rounding floor, so
+    auto mode marks them for the float64 pass."""
+    t = np.arange(n) / 16000.0
+    sig = [np.sin(2 * np.pi * 440 * t), np.sin(2 * np.pi * 3000 * t) + 1e-3 * np.sin(2 * np.pi * 700 * t),
+           np.sign(np.sin(2 * np.pi * 150 * t)), np.where((t > 0.1) & (t < 0.2), np.sin(2 * np.pi * 1000 * t), 0.0)]
+    imp = np.zeros(n)
+    imp[n // 3] = 1.0
+    sig.append(imp)
+    return np.stack(sig).astype(np.float32)
+
+
+def noisy(seed, n):
+    return synth.make_clip(seed, n)
+
+
+def nonfinite_cases(n, valid=None):
+    """{name: clip of `valid` (default n) samples}: a noisy clip with one planted value each, and the variants of the issue."""
+    valid = n if valid is None else valid
+    nan, inf = np.float32(np.nan), np.float32(np.inf)
+    cases = {}
+
+    def plant(name, seed, at_values, base=None):
+        x = (noisy(seed, valid) if base is None else base[:valid]).copy()
+        for at, v in at_values:
+            assert 0 <= at < valid
+            x[at] = v
+        cases[name] = x
+
+    for j, at in enumerate((0, 1, 511, 512, 1023, 1024, n // 2, valid - 1)):
+        at = min(at, valid - 1)
+        plant(f"nan@{at}" if at != valid - 1 else "nan@last", 700 + j, [(at, nan)])
+    plant("nan_negative", 710, [(n // 3, f32_from_bits(QNAN_NEG))])
+    plant("nan_signalling", 711, [(n // 3 + 1, f32_from_bits(SNAN))])
+    plant("two_nans_apart", 712, [(300, nan), (valid - 300, nan)])      # more than 2048 apart: no frame holds both
+    plant("+inf", 713, [(min(n // 2, valid - 1), inf)])
+    plant("-inf", 714, [(min(n // 2, valid - 1), -inf)])
+    plant("+inf_and_nan", 715, [(valid // 4, inf), (3 * valid // 4, nan)])
+    cases["all_nan"] = np.full(valid, nan, np.float32)
+    plant("nan_in_tone", 0, [(valid // 2 + 7, nan)], base=tones(n)[0])
+    plant("+inf_in_tone", 0, [(valid // 2 + 7, inf)], base=tones(n)[1])
+    assert len(cases) == 17
+    for name, x in cases.items():
+        assert x.dtype == np.float32 and x.shape == (valid,) and not np.isfinite(x).all(), name
+    return cases
+
+
+def oracle_mel(x, n, normalize):
+    """process_audio_file's numeric part at clip length n: normalise -> right zero-pad to n -> log-mel; [len(x), 1, 80, 1 + n // 512]."""
+    basis = mel_oracle.mel_filterbank()
+    out = []
+    with np.errstate(all="ignore"):
+        for clip in x:
+            a = np.asarray(clip, dtype=np.float32)
+            if normalize:
+                a = mel_oracle.normalize_audio(a).astype(np.float32)
+            a = np.pad(a, (0, n - len(a)))
+            out.append(mel_oracle.power_to_db_librosa32(mel_oracle.melspectrogram_librosa32(a, basis))[None])
+    return np.stack(out).astype(np.float32)
+
+
+def check_rows(out, special_rows, control_out):
+    """Every special row is NaN in EVERY element; every other row equals, bit for bit, the same row of `control_out` (the same launch
+    shape with each special row replaced by a finite noisy clip): a leak between the clips of a persistent workgroup shows there."""
+    out, control_out = np.asarray(out), np.asarray(control_out)
+    assert out.shape == control_out.shape, (out.shape, control_out.shape)
+    special = np.zeros(len(out), bool)
+    special[list(special_rows)] = True
+    for i in np.flatnonzero(special):
+        row = out[i]
+        assert np.isnan(row).all(), (f"row {i}: {int((~np.isnan(row)).sum())} of {row.size} values are not NaN; "
+                                     f"finite values span [{np.nanmin(row)}, {np.nanmax(row)}]")
+    for i in np.flatnonzero(~special):
+        assert np.array_equal(out[i], control_out[i]), f"ordinary row {i} differs from the control batch"
+        assert np.isfinite(out[i]).all(), f"ordinary row {i} is not finite"
+
+
+# ------------------------------------------------------------------------------------------------ a stand-in of the float epilogue
+def standin_logmel(x, n, normalize, sticky):
+    """numpy stand-in of logmel_kernel's epilogue on the oracle's mel powers of the RAW samples (the kernel defers the peak gain to the
+    powers).  sticky=False is the epilogue before the fix: fmax folds that drop a NaN for the peak and the mel maximum, g2 = 1 / peak^2,
+    the amin and -80 clamps written with `<` (false for a NaN).  sticky=True: the maximum is NaN once any power is NaN or Inf."""
+    f = np.float32
+    out = []
+    with np.errstate(all="ignore"):
+        for clip in x:
+            a = np.pad(np.asarray(clip, f), (0, n - len(clip)))
+            mel = mel_oracle.melspectrogram_librosa32(a)                           # [80, T] float32 powers
+            peak = np.fmax.reduce(np.abs(a), initial=f(0))                          # fmaxf fold from 0: a NaN operand is ignored
+            mmax = np.fmax.reduce(mel.ravel(), initial=f(0))
+            if sticky and not np.isfinite(mel).all():
+                mmax = f(np.nan)
+            g2 = f(1)
+            if normalize:
+                g = f(1) / peak
+                g2 = g * g
+            amin = f(1e-10)
+            ref = mmax * g2
+            ref = amin if ref < amin else ref
+            ref_db = f(10) * np.log10(ref)
+            v = mel * g2
+            v = np.where(v < amin, amin, v)
+            db = f(10) * np.log10(v) - ref_db
+            db = np.where(db < f(-80), f(-80), db)
+            out.append(db.astype(f)[None])
+    return np.stack(out)
+
+
+# ------------------------------------------------------------------------------------------------ levels
+def level_gains():
+    """k of test_level_range_is_recorded: steps of 10 from -100 to +100."""
+    return list(range(-100, 101, 10))
+
+
+def scaled(x, k):
+    """x * 2^k in float32 (exact while nothing overflows or goes subnormal; overflow gives Inf, underflow a subnormal or 0)."""
+    with np.errstate(all="ignore"):
+        return (np.asarray(x, np.float64) * 2.0 ** k).astype(np.float32)

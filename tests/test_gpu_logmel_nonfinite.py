@@ -1,0 +1,273 @@
+"""K1 on the inputs no other test feeds it: clips that hold a NaN or an Inf sample, and signal levels far from 1.
+
+Non-finite samples.  The reference makes an all-NaN image of such a clip (tests/test_host_logmel_nonfinite.py pins that on the oracle):
+`audio / np.max(np.abs(audio))` and `power_to_db(ref=np.max)` both spread the value over the whole clip.  Every instantiated log-mel
+kernel (4 and 8 waves, the 32- and the 64-frame tile, float32 / float64 / auto) must do the same, with or without the normalisation,
+and must leave every other clip of the batch exactly as it is in a batch without the value (logmel_cases.check_rows): the workgroups
+are persistent over clips, so the mel tile, the frame-mask words and red[] of one clip are the next clip's.
+
+Level.  The float kernel squares raw samples and applies 1 / peak^2 to the mel powers.  Every operation of both kernels commutes with
+a gain of 2^k while nothing overflows or goes subnormal, so for |k| <= 31 -- the largest power is at most (2^31 * 1024)^2 = 2^82, and a
+power 80 dB under the maximum stays far above 2^-126 -- the output must not change in one bit (k = 15 and 31: int16 and int32 PCM
+passed unscaled).  The float64 kernel divides by the peak before anything is squared: +-60 hold there too.
+test_level_range_is_recorded sweeps k = -100 .. 100 and writes what each arithmetic does (WW_LOGMEL_LEVEL_JSON=path ->
+profiles/logmel_levels.json)."""
+import functools
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import logmel_cases as lc
+import wakeword_jupyterlab_amd as pkg
+from wakeword_jupyterlab_amd import ops
+from wakeword_jupyterlab_amd.config import AudioConfig, n_samples
+
+pytestmark = pytest.mark.gpu
+
+MEL_TOL = 1e-4
+MATHS = ["f32", "f64", "auto"]
+# (n_samples, batch): 16000 is the 32-frame tile, everything else the 64-frame tile (T = 8, 47, 63); 24 clips run the 8-wave form
+# (at most one clip per CU), 300 the persistent 4-wave form
+FORMS = [(16000, 24), (16000, 300), (4000, 24), (24000, 24), (32000, 300)]
+LEVELS = {}
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "gpu-marked tests need the MI355X"
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _levels_file():
+    yield
+    path = os.environ.get("WW_LOGMEL_LEVEL_JSON")
+    if path and LEVELS:
+        with open(path, "w") as f:
+            json.dump(LEVELS, f, indent=1)
+
+
+@functools.lru_cache(maxsize=None)
+def _form(n, B):
+    """(batch, control, special rows, noisy rows to check, tone rows to check).  The 17 cases of logmel_cases.nonfinite_cases sit at
+    evenly spread rows, the first and the last included; the ordinary rows are noisy clips (16 distinct ones under per-row gains) with
+    a noise-free tone in every third place, so that auto mode marks neighbours of the special rows."""
+    cases = lc.nonfinite_cases(n)
+    special = [int(r) for r in np.round(np.linspace(0, B - 1, len(cases)))]
+    assert len(set(special)) == len(cases) and special[0] == 0 and special[-1] == B - 1
+    base, tones = pkg.synth.make_clips(0, 16, n=n), lc.tones(n)
+    x = np.empty((B, n), np.float32)
+    kinds = []
+    j = 0
+    for i in range(B):
+        if i in special:
+            kinds.append("special")
+            continue
+        if j % 3 == 1:
+            x[i] = tones[(j // 3) % len(tones)]
+            kinds.append("tone")
+        else:
+            x[i] = base[j % 16] * np.float32(1.0 - 0.37 * (j // 16) / max(1, B // 16))
+            kinds.append("noisy")
+        j += 1
+    control = x.copy()
+    for r, clip in zip(special, cases.values()):
+        x[r] = clip
+        control[r] = lc.noisy(900 + r, n)
+    assert np.isfinite(control).all()
+    noisy = [i for i, k in enumerate(kinds) if k == "noisy"]
+    tone = [i for i, k in enumerate(kinds) if k == "tone"]
+    x.setflags(write=False)
+    control.setflags(write=False)
+    return x, control, special, [noisy[0], noisy[-1]], [tone[len(tone) // 2]]
+
+
+@functools.lru_cache(maxsize=None)
+def _form_oracle(n, B, normalize):
+    """The oracle on the checked ordinary rows of a form: 15 rows over all forms, computed once."""
+    x, _, _, noisy, tone = _form(n, B)
+    return lc.oracle_mel(x[noisy + tone], n, normalize)
+
+
+def _logmel(x, n, normalize, dev):
+    t = x if isinstance(x, torch.Tensor) else torch.tensor(x, device=dev)
+    return (ops.logmel(t, normalize) if n == 16000 else ops.logmel_frames(t, n, normalize)).cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------ non-finite samples
+@pytest.mark.parametrize("form", FORMS, ids=lambda f: f"n{f[0]}-B{f[1]}")
+@pytest.mark.parametrize("normalize", [True, False])
+@pytest.mark.parametrize("math", MATHS)
+def test_nonfinite_clip_is_all_nan(dev, math, normalize, form):
+    n, B = form
+    x, control, special, noisy, tone = _form(n, B)
+    ops.set_logmel_math(math)
+    try:
+        out = _logmel(x, n, normalize, dev)
+        ctl = _logmel(control, n, normalize, dev)
+    finally:
+        ops.set_logmel_math("auto")
+    assert out.shape == (B, 1, 80, 1 + n // 512)
+    lc.check_rows(out, special, ctl)
+    ref = _form_oracle(n, B, normalize)
+    err = np.abs(out[noisy + tone] - ref).max(axis=(1, 2, 3))
+    print(f"{math} normalize={normalize} n={n} B={B}: max|err| noisy {err[:len(noisy)].max():.3e}, tone {err[len(noisy):].max():.3e}")
+    assert err[:len(noisy)].max() <= MEL_TOL, err
+    if math != "f32":                     # noise-free rows: the auto and f64 modes only, as everywhere else
+        assert err[len(noisy):].max() <= MEL_TOL, err
+
+
+@pytest.mark.parametrize("B", [24, 300])
+@pytest.mark.parametrize("math", MATHS)
+def test_short_rows_do_not_read_their_padding(dev, math, B):
+    """Rows of 9000 valid samples as views into a wider buffer full of NaN: behind every row's end lies NaN, not the zeros the kernel
+    pads with.  Row stride 16000 (taken as it is), then 16001 from an odd offset (the wrapper copies the rows)."""
+    valid = 9000
+    rows = np.stack([lc.noisy(50 + i % 16, valid) * np.float32(1.0 - 0.01 * (i // 16)) for i in range(B)])
+    rows[1::3] = lc.tones(16000)[np.arange(len(rows[1::3])) % 5, :valid]
+    packed = torch.from_numpy(rows).to(dev)
+    wide = torch.full((B, 16000), float("nan"), device=dev)
+    wide[:, :valid] = packed
+    odd = torch.full((B * 16001 + 1,), float("nan"), device=dev)[1:].view(B, 16001)
+    odd[:, :valid] = packed
+    ops.set_logmel_math(math)
+    try:
+        for n in (16000, 24000):
+            want = _logmel(packed, n, True, dev)
+            assert np.isfinite(want).all()
+            assert np.array_equal(_logmel(wide[:, :valid], n, True, dev), want), n
+            assert np.array_equal(_logmel(odd[:, :valid], n, True, dev), want), n
+    finally:
+        ops.set_logmel_math("auto")
+    assert torch.isnan(wide[:, valid:]).all() and torch.isnan(odd[:, valid:]).all()
+
+
+def _cfg(n):
+    return type(f"AudioConfig{n}", (AudioConfig,), {"DURATION": n / 16000.0})
+
+
+@pytest.mark.parametrize("arch", ["simple", "full"])
+@pytest.mark.parametrize("n", [4000, 16000])
+@pytest.mark.parametrize("math", MATHS)
+def test_forward_pcm_rows(dev, math, n, arch):
+    """The composed PCM -> logits calls: a special row gives NaN logits, every other row the control batch's bits."""
+    assert n_samples(_cfg(n)) == n
+    x, control, special, _, _ = _form(n, 24)
+    packed = torch.from_numpy(ops.pack_state_dict(pkg.synth.make_state_dict(arch, seed=1234))).to(dev)
+    n_conv = 2 if arch == "simple" else 3
+    calls = {"forward_pcm_frames": lambda t: ops.forward_pcm_frames(t, packed, n_conv, n)}
+    if n == 16000:
+        calls["forward_pcm"] = lambda t: ops.forward_pcm(t, packed, n_conv)
+    ordinary = np.setdiff1d(np.arange(len(x)), special)
+    ops.set_logmel_math(math)
+    try:
+        for name, call in calls.items():
+            got = call(torch.tensor(x, device=dev)).cpu().numpy()
+            ctl = call(torch.tensor(control, device=dev)).cpu().numpy()
+            assert np.isfinite(ctl).all(), name
+            assert np.isnan(got[special]).all(), (name, got[special])
+            assert np.array_equal(got[ordinary], ctl[ordinary]), name
+    finally:
+        ops.set_logmel_math("auto")
+
+
+@pytest.mark.parametrize("math", MATHS)
+def test_streaming_recovers_after_a_nan_leaves_the_ring(dev, math):
+    """0.25 s windows (10 hops of 400), 3 microphones; microphone 1 gets one NaN sample in hop 3, a control detector a finite value
+    there.  While the sample is in the window (hops 3 .. 12) microphone 1 reads NaN and detects nothing; from hop 13 on it is, bit
+    for bit, the control.  Microphones 0 and 2 never notice."""
+    n, hop, n_mics, n_hops, bad_hop = 4000, 400, 3, 25, 3
+    m = pkg.SimpleWakewordModel(audio_config=_cfg(n))
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in pkg.synth.make_state_dict("simple", seed=1234).items()})
+    m = m.to(dev).eval()
+    clean = np.stack([lc.noisy(600 + i, n_hops * hop) for i in range(n_mics)])
+    bad = clean.copy()
+    bad[1, bad_hop * hop + 123] = np.nan
+    clean[1, bad_hop * hop + 123] = 0.25
+    last_inside = bad_hop + n // hop - 1
+    ops.set_logmel_math(math)
+    try:
+        det = pkg.StreamingDetector(m, n_mics=n_mics, hop_samples=hop, threshold=0.0)
+        ctl = pkg.StreamingDetector(m, n_mics=n_mics, hop_samples=hop, threshold=0.0)
+        for k in range(n_hops):
+            det.step(torch.from_numpy(bad[:, k * hop:(k + 1) * hop]).to(dev))
+            ctl.step(torch.from_numpy(clean[:, k * hop:(k + 1) * hop]).to(dev))
+            fired, fired_ctl = det.detections().cpu().numpy(), ctl.detections().cpu().numpy()      # waits for the detector's stream
+            ctl.stream.synchronize()
+            logits, prob = det.logits.cpu().numpy(), det.prob.cpu().numpy()
+            logits_c, prob_c = ctl.logits.cpu().numpy(), ctl.prob.cpu().numpy()
+            assert np.isfinite(logits_c).all() and np.isfinite(prob_c).all() and fired_ctl.all(), k
+            others = [0, 2]
+            assert np.array_equal(logits[others], logits_c[others]) and np.array_equal(prob[others], prob_c[others]), k
+            assert fired[others].all(), k
+            if bad_hop <= k <= last_inside:
+                assert np.isnan(prob[1]) and np.isnan(logits[1]).all() and not fired[1], (k, prob, logits)
+            else:
+                assert np.array_equal(logits, logits_c) and np.array_equal(prob, prob_c) and fired[1], (k, logits, logits_c)
+        det.close()
+        ctl.close()
+    finally:
+        ops.set_logmel_math("auto")
+
+
+# ------------------------------------------------------------------------------------------------ level
+def _level_rows(n):
+    return np.concatenate([np.stack([lc.noisy(3, n), lc.noisy(4, n), lc.noisy(5, n) * np.float32(0.01)]), lc.tones(n)])
+
+
+@pytest.mark.parametrize("n", [16000, 4000, 32000])
+@pytest.mark.parametrize("math", MATHS)
+def test_power_of_two_gain_changes_no_bit(dev, math, n):
+    x = _level_rows(n)
+    gains = lc.POW2_GAINS + (lc.POW2_GAINS_F64 if math == "f64" else ())
+    ops.set_logmel_math(math)
+    try:
+        base = _logmel(x, n, True, dev)
+        got = {k: _logmel(lc.scaled(x, k), n, True, dev) for k in gains}
+    finally:
+        ops.set_logmel_math("auto")
+    assert np.isfinite(base).all() and np.all(base.max(axis=(1, 2, 3)) == 0.0)
+    bad = {k: [int(i) for i in np.flatnonzero((v != base).any(axis=(1, 2, 3)) | np.isnan(v).any(axis=(1, 2, 3)))] for k, v in got.items()}
+    print(f"{math} n={n}: rows that changed under 2^k: { {k: r for k, r in bad.items() if r} }")
+    assert not any(bad.values()), bad
+
+
+def _status(out, ref, tol):
+    if np.isnan(out).all():
+        return "all-NaN"
+    if np.isfinite(out).all() and np.abs(out - ref).max() <= tol:
+        return "within 1e-4 dB of the oracle"
+    return "finite but wrong" if np.isfinite(out).all() else "partly NaN"
+
+
+def test_level_range_is_recorded(dev):
+    """x * 2^k for k = -100 .. 100 in steps of 10, normalize=True, per arithmetic and per kind of clip (noisy / noise-free): within
+    MEL_TOL of the oracle (which normalises first and therefore sees the same clip at every k while the float32 samples stay normal),
+    all-NaN, or finite but wrong.  Asserted is only what the module docstring derives: |k| <= 30 is `within` in every arithmetic
+    (noise-free clips: auto and f64, as everywhere), and +-60 in f64.  The rest is recorded."""
+    n = 16000
+    x = _level_rows(n)
+    kinds = {"noisy": [0, 1, 2], "noise-free": list(range(3, len(x)))}
+    refs = {k: lc.oracle_mel(lc.scaled(x, k), n, True) for k in lc.level_gains()}
+    for math in MATHS:
+        ops.set_logmel_math(math)
+        try:
+            outs = {k: _logmel(lc.scaled(x, k), n, True, dev) for k in lc.level_gains()}
+        finally:
+            ops.set_logmel_math("auto")
+        for kind, rows in kinds.items():
+            rec = LEVELS.setdefault(math, {}).setdefault(kind, {})
+            for k in lc.level_gains():
+                per_row = sorted({_status(outs[k][r], refs[k][r], MEL_TOL) for r in rows})
+                rec[f"2^{k}"] = per_row[0] if len(per_row) == 1 else " / ".join(per_row)
+            print(math, kind, rec)
+    for math in MATHS:
+        for kind in kinds:
+            if kind == "noise-free" and math == "f32":
+                continue
+            for k in lc.level_gains():
+                if abs(k) <= 30 or (math == "f64" and abs(k) <= 60):
+                    assert LEVELS[math][kind][f"2^{k}"] == "within 1e-4 dB of the oracle", (math, kind, k, LEVELS[math][kind])

@@ -131,6 +131,14 @@ __device__ __forceinline__ float absmax3(float a, float b, float m) {
     return r;
 }
 
+// The per-clip mel maximum follows np.max: one non-finite mel power (a NaN or Inf sample reaches every band of the two to four frames
+// that cover it; an overflowed power) makes the maximum NaN, and through ref_db every output of the clip, as power_to_db(ref=np.max) does.
+// nan_max is IEEE 754-2019 `maximum`, one v_maximum3_f32: a NaN operand gives NaN where fmaxf drops it (and needs no canonicalising
+// v_max of its operands); every fold of the mel maximum -- per thread, across the lanes, across the waves -- uses it.
+// finite_or_nan, once on the folded maximum: x for a finite x >= 0, NaN for Inf (Inf * 0) and NaN.
+__device__ __forceinline__ float nan_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float finite_or_nan(float x) { return fmaf(x, 0.f, x); }
+
 // Eight 16-byte loads of one frame (samples base + 256*n1 .. +3) through a buffer descriptor whose range is exactly the
 // clip: the hardware returns 0 for every dword outside [0, clip_len) -- the STFT's centre padding, the right zero-pad
 // of short clips and "no next clip" (a zero-record descriptor) cost no compare, select or branch, and the eight loads
@@ -474,13 +482,13 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
             if (fr_live)
                 for (int b = wave; b < kMels; b += kWavesPerBlock) {
                     const float p = mel[b * kMelStride + lane];
-                    mmax = fmaxf(mmax, p);
+                    mmax = nan_max(mmax, p);
                     if (mark) e_part = fmaf(p, invw[b], e_part);
                 }
             if (mark) frm[wave * FR + lane] = e_part;
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) {
-                mmax = fmaxf(mmax, __shfl_xor(mmax, off));
+                mmax = nan_max(mmax, __shfl_xor(mmax, off));
                 peak = fmaxf(peak, __shfl_xor(peak, off));
             }
             if (lane == 0) { red[wave] = mmax; red[kWavesPerBlock + wave] = peak; }
@@ -488,7 +496,8 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
             mmax = red[0];
             peak = red[kWavesPerBlock];
 #pragma unroll
-            for (int w = 1; w < kWavesPerBlock; ++w) { mmax = fmaxf(mmax, red[w]); peak = fmaxf(peak, red[kWavesPerBlock + w]); }
+            for (int w = 1; w < kWavesPerBlock; ++w) { mmax = nan_max(mmax, red[w]); peak = fmaxf(peak, red[kWavesPerBlock + w]); }
+            mmax = finite_or_nan(mmax);     // a NaN or Inf power anywhere in the clip: every output is NaN, as with ref=np.max
             const float amin = 1e-10f;
             float g2 = 1.f;
             if (normalize) { const float g = 1.0f / peak; g2 = g * g; }
@@ -554,7 +563,7 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
         float* frm = lds + kOffFrm;
         for (int idx = tid; idx < kMels * kFrames; idx += kThreads) {
             const float p = mel[(idx >> 5) * kMelStride + (idx & 31)];
-            mmax = fmaxf(mmax, p);
+            mmax = nan_max(mmax, p);
             if (mark) e_part = fmaf(p, invw[idx >> 5], e_part);
         }
         if (mark) {
@@ -563,7 +572,7 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
-            mmax = fmaxf(mmax, __shfl_xor(mmax, off));
+            mmax = nan_max(mmax, __shfl_xor(mmax, off));
             peak = fmaxf(peak, __shfl_xor(peak, off));
         }
         if (lane == 0) { red[wave] = mmax; red[kWavesPerBlock + wave] = peak; }
@@ -571,9 +580,10 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
         mmax = red[0];
         peak = red[kWavesPerBlock];
 #pragma unroll
-        for (int w = 1; w < kWavesPerBlock; ++w) { mmax = fmaxf(mmax, red[w]); peak = fmaxf(peak, red[kWavesPerBlock + w]); }
+        for (int w = 1; w < kWavesPerBlock; ++w) { mmax = nan_max(mmax, red[w]); peak = fmaxf(peak, red[kWavesPerBlock + w]); }
+        mmax = finite_or_nan(mmax);     // a NaN or Inf power anywhere in the clip: every output is NaN, as with ref=np.max
 
-        // power_to_db(S, ref=np.max, amin=1e-10, top_db=80): NaN must propagate (silent clip, 0/0)
+        // power_to_db(S, ref=np.max, amin=1e-10, top_db=80): NaN must propagate (silent clip, 0/0; a non-finite sample through mmax)
         const float amin = 1e-10f;
         float g2 = 1.f;
         if (normalize) { const float g = 1.0f / peak; g2 = g * g; }
@@ -964,23 +974,20 @@ __global__ __launch_bounds__(256, 2) void logmel64_kernel(const float* __restric
             frame = frame_next;
         }
         __syncthreads();
-        // a NaN anywhere (silent clip, 0/0) must reach every output like in the reference: fmaxf would drop it
+        // a NaN or Inf anywhere (silent clip, 0/0; a non-finite sample) must reach every output like in the reference: fmaxf would drop it
         float mmax = 0.f;
-        bool any_nan = false;
         for (int idx = tid; idx < kMels * nfr; idx += kThreads) {
             const int b = FR == kFrames ? idx >> 5 : idx / nfr, t = FR == kFrames ? idx & 31 : idx - b * nfr;
-            const float p = mel[b * kMelStride + t];
-            any_nan |= p != p;
-            mmax = fmaxf(mmax, p);
+            mmax = nan_max(mmax, mel[b * kMelStride + t]);
         }
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mmax = fmaxf(mmax, __shfl_xor(mmax, off));
-        any_nan = __builtin_amdgcn_ballot_w64(any_nan) != 0ull;
-        if (lane == 0) red[wave] = any_nan ? __uint_as_float(0x7fc00000u) : mmax;
+        for (int off = 32; off > 0; off >>= 1) mmax = nan_max(mmax, __shfl_xor(mmax, off));
+        if (lane == 0) red[wave] = mmax;
         __syncthreads();
         mmax = red[0];
 #pragma unroll
-        for (int w = 1; w < kWavesPerBlock; ++w) mmax = (red[w] != red[w] || mmax != mmax) ? __uint_as_float(0x7fc00000u) : fmaxf(mmax, red[w]);
+        for (int w = 1; w < kWavesPerBlock; ++w) mmax = nan_max(mmax, red[w]);
+        mmax = finite_or_nan(mmax);
         const float amin = 1e-10f;
         float ref = mmax;
         ref = ref < amin ? amin : ref;
