@@ -795,7 +795,8 @@ typedef struct ww_loss_opts {
 WW_API int ww_ce_loss_ex_f32(const float* logits_dev, const int64_t* labels_dev, int64_t n, const ww_loss_opts* opts_host, float* dlogits_dev,
                              float* loss_dev, ww_loss_stats* stats_dev, ww_stream_t stream);
 /* ww_ce_loss_soft_f32: cross-entropy on CLASS PROBABILITIES -- torch's F.cross_entropy(z, t, weight=w,
- * label_smoothing=eps, reduction=) with a floating-point target t [n][2]: what mixup, distillation and soft relabelling need.
+ * label_smoothing=eps, reduction=) with a floating-point target t [n][2]: what mixup and soft relabelling need (distillation from a
+ * teacher's LOGITS, with a temperature and a hard term in the same loss, is ww_distill_loss_f32 below).
  * ww_ce_loss_ex_f32's kernel shape: one launch, one workgroup, no atomics, every sum in one fixed order, the options by value in the
  * kernel arguments (opts_host NULL: unit weights, eps = 0, the mean).  Per clip in float64, with p = softmax(z) and lse as above:
  *   t'_c = (1 - eps) t_c + eps / 2;   l = w0 t'_0 (lse - z0) + w1 t'_1 (lse - z1);   dl/dz_k = p_k (w0 t'_0 + w1 t'_1) - w_k t'_k
@@ -812,6 +813,48 @@ WW_API int ww_ce_loss_ex_f32(const float* logits_dev, const int64_t* labels_dev,
  * ignore_index != -100 (torch refuses one for floating-point targets). */
 WW_API int ww_ce_loss_soft_f32(const float* logits_dev, const float* targets_dev, int64_t n, const ww_loss_opts* opts_host, float* dlogits_dev,
                                float* loss_dev, ww_loss_stats* stats_dev, ww_stream_t stream);
+/* ww_distill_loss_f32: knowledge distillation -- a hard term on the batch's own targets and Hinton's
+ * teacher term in ONE loss, one launch in the place of ww_ce_loss_ex_f32 / ww_ce_loss_soft_f32 and in their kernel shape: one workgroup,
+ * no atomics, every sum in one fixed order, the options, alpha and the temperature by value in the kernel arguments.  With z the student
+ * logits, zt the teacher logits, T = temperature and alpha the mixing weight:
+ *   L = (1 - alpha) H(z, y) + alpha T^2 KD(z, zt)
+ *   KD_i = sum_c q_c (log q_c - log p_c),  q = softmax(zt_i / T),  p = softmax(z_i / T);   dKD_i / dz_k = (p_k - q_k) / T
+ * which is F.kl_div(log_softmax(z / T), softmax(zt / T), reduction="batchmean") * T^2.  zt / T and z / T are formed in float64 and go
+ * through the max-subtracted log-sum-exp of the other losses; log q_c = zt_c / T - lse, never log(q_c).
+ *   H          target_kind WW_TARGET_LABELS: targets_dev is int64 [n] and H is ww_ce_loss_ex_f32's loss under *opts_host, per clip and
+ *              in its denominator (class weights, smoothing, ignore_index, focal, mean or sum); opts_host NULL: unit weights, eps = 0,
+ *              ignore_index -100, cross-entropy, the mean.  WW_TARGET_PROBS: targets_dev is float32 [n][2] and H is ww_ce_loss_soft_f32's.
+ *              targets_dev NULL: no target at all (unlabelled audio) -- L = T^2 KD, alpha and target_kind are not read, and of the
+ *              options only `reduction` is.
+ *   KD rows    a row counts for KD iff both its teacher logits are finite; any other row adds nothing to KD or its gradient and is
+ *              counted in teacher_nonfinite.
+ *   mean       H is divided by its rule's own denominator and KD by the NUMBER of KD rows; WW_REDUCE_SUM divides both by 1.
+ *   dlogits    (1 - alpha) dH/dz / (H's denominator) + alpha T (p - q) / (KD's denominator), in float64, rounded to float32 once.
+ *   a term without a counted row (a denominator of 0 under the mean), or with coefficient 0, contributes exactly 0 to loss and gradient
+ *   -- selected, never multiplied: 0 x NaN is not formed.  When NEITHER term has a counted row under the mean the loss is NaN and every
+ *   dlogits entry exactly 0, the rule of ww_ce_loss_ex_f32; under WW_REDUCE_SUM such a batch sums to 0, as there.
+ *   alpha = 0  loss, gradient and *stats_dev have the bits of ww_ce_loss_ex_f32 / ww_ce_loss_soft_f32 on the same inputs.
+ * stats_dev is updated as the hard rule's own entry point updates it (loss_sum adds the float32 L); without a target only total,
+ * batches, nonfinite and loss_sum move.  distill_stats_dev (NULL allowed) accumulates what tells the two terms apart.
+ * logits_dev, teacher_logits_dev [n][2] float32, 4-byte aligned (16-byte loads where a pointer allows them); labels and both records
+ * 8-byte aligned; dlogits_dev, loss_dev, stats_dev and distill_stats_dev may be NULL.  Checked before any HIP call (WW_EINVAL naming the
+ * field): what ww_ce_loss_ex_f32 (labels) or ww_ce_loss_soft_f32 (probabilities) checks, target_kind, alpha in [0, 1], a finite
+ * temperature > 0, a NULL teacher_logits_dev. */
+#define WW_TARGET_LABELS 0
+#define WW_TARGET_PROBS 1
+typedef struct ww_distill_stats {
+    double hard_sum;           /* sum over the batches of H as a float32 value, NOT weighted by 1 - alpha (0 for a batch without hard rows) */
+    double kd_sum;             /* the same of T^2 KD, NOT weighted by alpha */
+    int64_t kd_rows;           /* rows with two finite teacher logits */
+    int64_t hard_rows;         /* rows the hard rule counts (a valid label that is not ignored; a valid probability row) */
+    int64_t agree;             /* KD rows where the student's prediction equals the teacher's (a tie gives class 0, as everywhere) */
+    int64_t teacher_correct;   /* hard rows where the TEACHER's prediction equals the label (the argmax of a probability row) */
+    int64_t teacher_nonfinite; /* rows with an Inf or NaN teacher logit */
+    int64_t batches;           /* calls */
+} ww_distill_stats;            /* 64 bytes, DEVICE memory; zero it before an epoch */
+WW_API int ww_distill_loss_f32(const float* logits_dev, const float* teacher_logits_dev, const void* targets_dev, int target_kind, int64_t n,
+                               const ww_loss_opts* opts_host, double alpha, double temperature, float* dlogits_dev, float* loss_dev,
+                               ww_loss_stats* stats_dev, ww_distill_stats* distill_stats_dev, ww_stream_t stream);
 /* ww_mixup_f32: mixup on a log-mel batch, with the class-probability targets ww_ce_loss_soft_f32 takes.
  * Out of place (overlapping mel / out ranges: WW_EINVAL); one launch over B x chunks of a row; no atomics.  Per row i, with
  * p = partner_dev[i], lam = lambda_dev[i] and oml = 1.0f - lam (ONE float32 subtraction):

@@ -24,7 +24,7 @@ def __getattr__(name):
             "AugmentationConfig": "config", "SpecAugmentConfig": "config", "MixupConfig": "config", "BackgroundNoiseBank": "background", "ClipBank": "bank",
             "ImpulseResponseBank": "reverb", "scan_files": "scan", "det_curve": "scan", "Scan": "scan", "TrainingConfig": "config", "FusedAdam": "optim",
             "WakewordTrainer": "trainer", "ClipReport": "metrics", "evaluate_report": "inference", "evaluate_report_pcm": "inference",
-            "FocalLoss": "loss", "balanced_class_weights": "loss", "balanced_order": "sampling", "BankAudit": "audit", "ClipLedger": "ledger", "LedgerReport": "ledger", "WeightAverage": "average"}
+            "FocalLoss": "loss", "DistillationLoss": "loss", "balanced_class_weights": "loss", "balanced_order": "sampling", "BankAudit": "audit", "ClipLedger": "ledger", "LedgerReport": "ledger", "WeightAverage": "average"}
     if name in lazy:
         return getattr(importlib.import_module(f"{__name__}.{lazy[name]}"), name)
     raise AttributeError(name)

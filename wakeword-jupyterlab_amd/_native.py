@@ -131,6 +131,13 @@ class LossOpts(C.Structure):
 
 LOSS_CE, LOSS_FOCAL = 0, 1
 REDUCE_MEAN, REDUCE_SUM = 0, 1
+TARGET_LABELS, TARGET_PROBS = 0, 1
+
+
+class DistillStats(C.Structure):
+    """struct ww_distill_stats (include/wakeword_amd.h): what tells the two terms of a distillation epoch apart, device memory."""
+    _fields_ = [("hard_sum", C.c_double), ("kd_sum", C.c_double), ("kd_rows", C.c_int64), ("hard_rows", C.c_int64), ("agree", C.c_int64),
+                ("teacher_correct", C.c_int64), ("teacher_nonfinite", C.c_int64), ("batches", C.c_int64)]
 
 
 class AdamTensor(C.Structure):
@@ -280,6 +287,8 @@ PROTOTYPES = {
     "ww_ce_loss_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_ce_loss_ex_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(LossOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_ce_loss_soft_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(LossOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_distill_loss_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(LossOpts), C.c_double, C.c_double,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_mixup_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_adam_step_f32": (C.c_int, [C.POINTER(AdamTensor), C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
                                    C.c_void_p, C.c_void_p]),

@@ -10,6 +10,9 @@
 //                         Probs        class probabilities [n][2] with weights, smoothing, mean or sum (section 3n)
 //                       All three go through softmax2 and one order of summation, so where their formulas reduce to one another
 //                       (unit options, one-hot rows) so do their bits (tests/test_gpu_loss.py, tests/test_gpu_mixup.py).
+//   distill_loss_kernel<P>  loss_kernel's shape with the teacher's logits as a second stream (section 3p): the hard term of OptLabels, Probs
+//                       or of no target at all (NoTarget) and Hinton's teacher term, each over its own denominator, in one loss and
+//                       one gradient; updates ww_loss_stats as the policy's own kernel does, and ww_distill_stats
 //   adam_kernel         one launch over up to 16 tensors, the table in the kernel arguments; torch's single-tensor Adam arithmetic
 //   adam_avg_kernel     the same launch with an averaged copy of the weights (EMA / SWA): after adam_one the
 //                       register value of p goes through avg_one into a second tensor -- one more read and one more write per
@@ -37,9 +40,9 @@ struct LossClip { double loss, d0, d1; int correct, bad, nonfinite; };
 // The softmax and the log-sum-exp of one clip in float64, lse = max + log(exp(z0 - max) + exp(z1 - max)): what the three rules share.
 struct Softmax2 { double z0, z1, lse, p0, p1; };
 
-__device__ __forceinline__ Softmax2 softmax2(float z0f, float z1f) {
+__device__ __forceinline__ Softmax2 softmax2(double z0, double z1) {
     Softmax2 r;
-    r.z0 = double(z0f); r.z1 = double(z1f);
+    r.z0 = z0; r.z1 = z1;
     const double m = r.z0 > r.z1 ? r.z0 : r.z1;
     const double e0 = exp(r.z0 - m), e1 = exp(r.z1 - m), s = e0 + e1;
     r.lse = m + log(s);
@@ -120,7 +123,8 @@ struct OptLabels {
     }
 };
 
-// Class probabilities [n][2] float32: mixup, distillation, soft relabelling.  t' = (1 - eps) t + eps / 2;
+// Class probabilities [n][2] float32: mixup, soft relabelling, a teacher's softmax (distillation proper, with
+// a temperature and a hard term beside the teacher's, is distill_loss_kernel below).  t' = (1 - eps) t + eps / 2;
 // l = sum_c w_c t'_c (lse - z_c); dl/dz_k = p_k (w0 t'_0 + w1 t'_1) - w_k t'_k.  A row counts iff both targets are finite and >= 0, and
 // the mean's denominator is the NUMBER of such rows (torch divides by n), not the weighted sum of the integer-label form.  With a
 // one-hot row, unit weights and eps = 0 every product is by 1 or by 0, so loss and gradient have the bits of the label rules.
@@ -299,6 +303,187 @@ static int launch_ce_loss_ex(const float* logits, const int64_t* labels, int64_t
 static int launch_ce_loss_soft(const float* logits, const float* targets, int64_t n, const ww_loss_opts& opts, float* dlogits, float* loss,
                                ww_loss_stats* stats, hipStream_t stream) {
     return launch_loss(logits, targets, n, Probs{opts}, dlogits, loss, stats, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// knowledge distillation: the hard term of a policy above and the teacher term in one loss
+// ---------------------------------------------------------------------------------------------
+// No target at all (unlabelled audio): the hard term is absent and L = T^2 KD.
+struct NoTarget {};
+
+struct DistillArgs { double alpha, temperature; int32_t reduction; };      // reduction: the policy's own, repeated where NoTarget has none
+
+// One clip's teacher term in float64, NOT yet times T^2 or divided: kd = sum_c q_c (log q_c - log p_c) with q = softmax(zt / T) and
+// p = softmax(z / T), log q_c = zt_c / T - lse (a q_c that underflows to 0 multiplies a finite difference); d_k = p_k - q_k, the
+// gradient but for its factor 1 / T.  A row counts iff both teacher logits are finite.
+struct KdClip { double kd, d0, d1; int counted, agree; };
+
+__device__ __forceinline__ KdClip kd_clip(float z0f, float z1f, float t0f, float t1f, double T) {
+    KdClip r;
+    const bool counted = isfinite(t0f) && isfinite(t1f);
+    const Softmax2 s = softmax2(double(z0f) / T, double(z1f) / T), t = softmax2(double(t0f) / T, double(t1f) / T);
+    const double kd = t.p0 * ((t.z0 - t.lse) - (s.z0 - s.lse)) + t.p1 * ((t.z1 - t.lse) - (s.z1 - s.lse));
+    r.kd = counted ? kd : 0.0;
+    r.d0 = counted ? s.p0 - t.p0 : 0.0;
+    r.d1 = counted ? s.p1 - t.p1 : 0.0;
+    r.counted = counted;
+    r.agree = counted && (z1f > z0f) == (t1f > t0f);         // a tie predicts class 0 on either side
+    return r;
+}
+
+// loss_kernel's shape with a second 16-byte stream, the teacher's logits, beside the student's.  The pass in front always runs: it
+// gives the policy's tallies (its denominator under the mean, hard_rows always) and the number of KD rows before the first gradient
+// is written.  The hard term is P::clip, P::tally and P::denominator as loss_kernel uses them; the teacher's accuracy is the `correct`
+// of P::clip on the TEACHER's logits (the rest of that clip is dead code).  Each term has its own denominator and its own float64 sum
+// in loss_kernel's order; a term is selected into loss and gradient, never multiplied in, so one that is absent, empty or weighted 0
+// contributes exactly 0 and no 0 x NaN is formed.  With alpha = 0 the selects leave (1.0 * x) + 0.0: loss_kernel<P>'s bits.
+template <class P>
+__global__ __launch_bounds__(kCeThreads) void distill_loss_kernel(const float* __restrict__ logits, const float* __restrict__ teacher,
+                                                                  const void* __restrict__ targets_raw, int64_t n, const P pol, const DistillArgs da,
+                                                                  float* __restrict__ dlogits, float* __restrict__ loss_out,
+                                                                  ww_loss_stats* __restrict__ stats, ww_distill_stats* __restrict__ dstats) {
+    constexpr bool kHard = !std::is_same<P, NoTarget>::value;
+    using Hard = std::conditional_t<kHard, P, PlainLabels>;  // NoTarget: a target type that is never loaded, and no tallies
+    using Target = typename Hard::Target;
+    constexpr int kPer = Hard::kPer, kCounts = Hard::kCounts, kWaves = kCeThreads / 64;
+    constexpr int kTally = kCounts + 2;                      // the policy's tallies, then KD rows and non-finite teacher rows
+    const Target* __restrict__ targets = static_cast<const Target*>(targets_raw);
+    __shared__ int red_tally[kTally][kWaves];
+    __shared__ double red_loss[2][kWaves];
+    __shared__ int red_cnt[5][kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool z_wide = (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
+    const bool q_wide = (reinterpret_cast<uintptr_t>(teacher) & 15) == 0;
+    const bool t_wide = (reinterpret_cast<uintptr_t>(targets) & 15) == 0;
+    const bool d_wide = (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;
+    const int64_t pairs = (n + 1) >> 1;
+    const bool mean = da.reduction == WW_REDUCE_MEAN;
+    const double T = da.temperature;
+
+    int c[kTally] = {};
+    for (int64_t p = tid; p < pairs; p += kCeThreads) {
+        const int64_t i = 2 * p;
+        const bool two = i + 1 < n;
+        float q[4];
+        load_pair<float, 2>(teacher, i, two, q_wide, q);
+        if constexpr (kHard) {
+            Target t[2 * kPer];
+            load_pair<Target, kPer>(targets, i, two, t_wide, t);
+            pol.tally(t, c);
+            if (two) pol.tally(t + kPer, c);
+        }
+        const bool f0 = isfinite(q[0]) && isfinite(q[1]), f1 = two && isfinite(q[2]) && isfinite(q[3]);
+        c[kCounts] += int(f0) + int(f1);
+        c[kCounts + 1] += int(!f0) + int(two && !f1);
+    }
+    int64_t totals[kTally];
+#pragma unroll
+    for (int k = 0; k < kTally; ++k) {
+        c[k] = wave_sum(c[k]);
+        if (lane == 0) red_tally[k][wave] = c[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kTally; ++k) totals[k] = fold_waves(red_tally[k]);
+    const int64_t kd_rows = totals[kCounts], teacher_nonfinite = totals[kCounts + 1];
+    int64_t hard_rows = 0;
+    double hard_denom = 0.0;
+    if constexpr (kHard) {
+#pragma unroll
+        for (int k = 0; k < kCounts; ++k) hard_rows += totals[k];
+        hard_denom = mean ? pol.denominator(totals) : 1.0;
+    }
+    const double kd_denom = mean ? double(kd_rows) : 1.0;
+    const bool hard_has = kHard && hard_denom > 0.0, kd_has = kd_denom > 0.0;
+    const bool empty = !hard_has && !kd_has;                // under the mean only: a sum divides by 1
+    const double inv_h = hard_has ? 1.0 / hard_denom : 0.0, inv_k = kd_has ? 1.0 / kd_denom : 0.0;
+    const double ch = kHard ? 1.0 - da.alpha : 0.0, ck = kHard ? da.alpha : 1.0;       // the coefficients of H and of T^2 KD
+    const bool hard_on = hard_has && ch > 0.0, kd_on = kd_has && ck > 0.0;
+    const double gk = ck * T;                               // alpha T^2 / T: the gradient's factor on p - q
+
+    double loss_h = 0.0, loss_k = 0.0;
+    int correct = 0, bad = 0, nonfinite = 0, agree = 0, teacher_correct = 0;
+    for (int64_t p = tid; p < pairs; p += kCeThreads) {
+        const int64_t i = 2 * p;
+        const bool two = i + 1 < n;
+        float z[4], q[4];
+        Target t[2 * kPer] = {};
+        load_pair<float, 2>(logits, i, two, z_wide, z);
+        load_pair<float, 2>(teacher, i, two, q_wide, q);
+        if constexpr (kHard) load_pair<Target, kPer>(targets, i, two, t_wide, t);
+        (void)t;
+        float d[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (j == 1 && !two) break;
+            const float z0 = z[2 * j], z1 = z[2 * j + 1], q0 = q[2 * j], q1 = q[2 * j + 1];
+            LossClip a;
+            if constexpr (kHard) {
+                a = pol.clip(z0, z1, t + kPer * j);
+                teacher_correct += pol.clip(q0, q1, t + kPer * j).correct;
+            } else {
+                a.loss = a.d0 = a.d1 = 0.0;
+                clip_counts(a, z0, z1, false, true, 0);     // nothing is valid and nothing is bad: `nonfinite` alone
+            }
+            const KdClip k = kd_clip(z0, z1, q0, q1, T);
+            loss_h += a.loss; loss_k += k.kd;
+            correct += a.correct; bad += a.bad; nonfinite += a.nonfinite; agree += k.agree;
+            const double dh0 = hard_on ? ch * (a.d0 * inv_h) : 0.0, dh1 = hard_on ? ch * (a.d1 * inv_h) : 0.0;
+            const double dk0 = kd_on ? gk * k.d0 * inv_k : 0.0, dk1 = kd_on ? gk * k.d1 * inv_k : 0.0;
+            d[2 * j] = float(dh0 + dk0); d[2 * j + 1] = float(dh1 + dk1);
+        }
+        if (dlogits) {
+            if (two && d_wide) {
+                *reinterpret_cast<float4*>(dlogits + 2 * i) = make_float4(d[0], d[1], d[2], d[3]);
+            } else {
+                dlogits[2 * i] = d[0]; dlogits[2 * i + 1] = d[1];
+                if (two) { dlogits[2 * i + 2] = d[2]; dlogits[2 * i + 3] = d[3]; }
+            }
+        }
+    }
+    loss_h = wave_sum(loss_h); loss_k = wave_sum(loss_k);
+    correct = wave_sum(correct); bad = wave_sum(bad); nonfinite = wave_sum(nonfinite); agree = wave_sum(agree);
+    teacher_correct = wave_sum(teacher_correct);
+    if (lane == 0) {
+        red_loss[0][wave] = loss_h; red_loss[1][wave] = loss_k;
+        red_cnt[0][wave] = correct; red_cnt[1][wave] = bad; red_cnt[2][wave] = nonfinite; red_cnt[3][wave] = agree;
+        red_cnt[4][wave] = teacher_correct;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double hard = hard_has ? fold_waves(red_loss[0]) * inv_h : 0.0;           // H and T^2 KD, each over its own denominator
+        const double kd = kd_has ? T * T * (fold_waves(red_loss[1]) * inv_k) : 0.0;
+        const double total = (hard_on ? ch * hard : 0.0) + (kd_on ? ck * kd : 0.0);
+        const float value = empty ? __builtin_nanf("") : float(total);                  // rounded once
+        if (loss_out) *loss_out = value;
+        if (stats) {
+            stats->loss_sum += double(value);
+            stats->correct += fold_waves(red_cnt[0]);
+            stats->total += n;
+            stats->batches += 1;
+            stats->bad_labels += fold_waves(red_cnt[1]);
+            stats->nonfinite += fold_waves(red_cnt[2]);
+        }
+        if (dstats) {
+            dstats->hard_sum += double(float(hard));
+            dstats->kd_sum += double(float(kd));
+            dstats->kd_rows += kd_rows;
+            dstats->hard_rows += hard_rows;
+            dstats->agree += fold_waves(red_cnt[3]);
+            dstats->teacher_correct += fold_waves(red_cnt[4]);
+            dstats->teacher_nonfinite += teacher_nonfinite;
+            dstats->batches += 1;
+        }
+    }
+}
+
+template <class P>
+static int launch_distill(const float* logits, const float* teacher, const void* targets, int64_t n, const P& pol, const DistillArgs& da,
+                          float* dlogits, float* loss, ww_loss_stats* stats, ww_distill_stats* dstats, hipStream_t stream) {
+    hipLaunchKernelGGL(distill_loss_kernel<P>, dim3(1), dim3(kCeThreads), 0, stream, logits, teacher, targets, n, pol, da, dlogits, loss, stats,
+                       dstats);
+    WW_HIP(hipGetLastError());
+    return WW_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -766,6 +951,39 @@ int ww_ce_loss_soft_f32(const float* logits_dev, const float* targets_dev, int64
     ww_loss_opts o = {{1.0, 1.0}, 0.0, 0.0, -100, WW_LOSS_CE, WW_REDUCE_MEAN};             // NULL: nn.CrossEntropyLoss()'s defaults
     if (int rc = check_loss_call(logits_dev, targets_dev, true, n, opts_host, &o, dlogits_dev, loss_dev, stats_dev)) return rc;
     return launch_ce_loss_soft(logits_dev, targets_dev, n, o, dlogits_dev, loss_dev, stats_dev, static_cast<hipStream_t>(stream));
+}
+
+int ww_distill_loss_f32(const float* logits_dev, const float* teacher_logits_dev, const void* targets_dev, int target_kind, int64_t n,
+                        const ww_loss_opts* opts_host, double alpha, double temperature, float* dlogits_dev, float* loss_dev,
+                        ww_loss_stats* stats_dev, ww_distill_stats* distill_stats_dev, ww_stream_t stream) {
+    const auto off = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    ww_loss_opts o = {{1.0, 1.0}, 0.0, 0.0, -100, WW_LOSS_CE, WW_REDUCE_MEAN};             // NULL: nn.CrossEntropyLoss()'s defaults
+    const ww_loss_opts defaults = o;
+    const bool probs = target_kind == WW_TARGET_PROBS;
+    // the distillation's own arguments first: check_loss_call ends with the device query
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(WW_EINVAL, "alpha %g: expected [0, 1]", alpha);
+    if (!(temperature > 0.0) || std::isinf(temperature)) return fail(WW_EINVAL, "temperature %g: expected a finite value > 0", temperature);
+    if (!teacher_logits_dev) return fail(WW_EINVAL, "null teacher_logits pointer");
+    if (off(teacher_logits_dev, 3)) return fail(WW_EINVAL, "teacher_logits_dev must be 4-byte aligned");
+    if (off(distill_stats_dev, 7)) return fail(WW_EINVAL, "distill_stats_dev must be 8-byte aligned");
+    if (targets_dev) {
+        if (target_kind != WW_TARGET_LABELS && !probs) return fail(WW_EINVAL, "target_kind %d: expected WW_TARGET_LABELS or WW_TARGET_PROBS", target_kind);
+        if (int rc = check_loss_call(logits_dev, targets_dev, probs, n, probs || opts_host ? opts_host : &defaults, &o, dlogits_dev, loss_dev, stats_dev))
+            return rc;
+    } else {                                                // no target: of the options only the reduction is read
+        if (n <= 0 || n > (int64_t(1) << 30)) return fail(WW_EINVAL, "n %lld: expected 1..2^30", (long long)n);
+        if (opts_host) o = *opts_host;
+        if (int rc = check_loss_opts(o)) return rc;
+        if (!logits_dev) return fail(WW_EINVAL, "null logits pointer");
+        if (off(logits_dev, 3) || off(dlogits_dev, 3) || off(loss_dev, 3)) return fail(WW_EINVAL, "logits_dev / dlogits_dev / loss_dev must be 4-byte aligned");
+        if (off(stats_dev, 7)) return fail(WW_EINVAL, "stats_dev must be 8-byte aligned");
+        if (int rc = require_gfx950()) return rc;
+    }
+    const DistillArgs da = {alpha, temperature, o.reduction};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!targets_dev) return launch_distill(logits_dev, teacher_logits_dev, nullptr, n, NoTarget{}, da, dlogits_dev, loss_dev, stats_dev, distill_stats_dev, s);
+    if (probs) return launch_distill(logits_dev, teacher_logits_dev, targets_dev, n, Probs{o}, da, dlogits_dev, loss_dev, stats_dev, distill_stats_dev, s);
+    return launch_distill(logits_dev, teacher_logits_dev, targets_dev, n, OptLabels{o}, da, dlogits_dev, loss_dev, stats_dev, distill_stats_dev, s);
 }
 
 int ww_adam_step_f32(const ww_adam_tensor* tensors_host, int64_t n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,

@@ -211,6 +211,18 @@ def _cnn_lstm_forward_impl(x: torch.Tensor, packed: torch.Tensor, n_conv: int) -
     return logits
 
 
+def forward_workspace_bytes(B: int, n_conv: int) -> int:
+    """ww_workspace_bytes: what ww_model_forward_f32 needs for B clips (at least 1, so that a buffer of this size has a pointer)."""
+    return max(1, nat.check(nat.lib.ww_workspace_bytes(B, n_conv)))
+
+
+def model_forward_into(x, packed, n_conv: int, ws, logits) -> None:
+    """ww_model_forward_f32, the eval-mode chain of cnn_lstm_forward, on caller-owned buffers: x as _check_x returns it (T <= 32), `packed`
+    as model.packed_weights() gives it, `ws` uint8 of at least forward_workspace_bytes(B, n_conv), logits float32 [>= B, 2] contiguous.
+    One native call on the current stream of the CURRENT device, which the caller has made x's; allocates nothing."""
+    nat.check(nat.lib.ww_model_forward_f32(_ptr(x), x.shape[0], x.shape[3], _ptr(packed), n_conv, _ptr(ws), _ptr(logits), _stream()))
+
+
 def _forward_pcm_impl(pcm: torch.Tensor, packed: torch.Tensor, n_conv: int, normalize: bool = True) -> torch.Tensor:
     pcm = _check_pcm(pcm)
     _check_packed(packed, n_conv, pcm)
@@ -942,6 +954,106 @@ def soft_ce_loss(logits: torch.Tensor, targets: torch.Tensor, stats=None, grad: 
     opts = soft_loss_opts(weight, label_smoothing, reduction, focal_gamma)
     _check_soft(logits, targets)
     return _loss_alloc_launch(logits, targets, True, opts, stats, grad)
+
+
+# ---- knowledge distillation: hard term + teacher term in one launch (csrc/ww_optim.hip) --------------------
+DISTILL_STATS_FIELDS = ("hard_sum", "kd_sum", "kd_rows", "hard_rows", "agree", "teacher_correct", "teacher_nonfinite", "batches")
+
+
+def new_distill_stats(device) -> torch.Tensor:
+    """A zeroed ww_distill_stats record in device memory: eight 8-byte words (the first two float64); `.zero_()` starts a new epoch."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"distillation stats on {device}: this path has no CPU implementation")
+    return torch.zeros(len(DISTILL_STATS_FIELDS), device=device, dtype=torch.int64)
+
+
+def _check_distill_stats(stats, like: torch.Tensor) -> None:
+    if (not isinstance(stats, torch.Tensor) or stats.dtype != torch.int64 or stats.shape != (len(DISTILL_STATS_FIELDS),)
+            or not stats.is_contiguous()):
+        raise TypeError("distill_stats: expected the record ops.new_distill_stats() makes (int64 [8], contiguous)")
+    if stats.device != like.device:
+        raise RuntimeError(f"distill_stats on {stats.device}, logits on {like.device}")
+
+
+def read_distill_stats(stats: torch.Tensor) -> dict:
+    """The record on the host: {hard_sum, kd_sum: float, kd_rows, hard_rows, agree, teacher_correct, teacher_nonfinite, batches: int}.
+    One device-to-host copy (none for a record that already is on the host)."""
+    host = stats.cpu()
+    out = {k: int(v) for k, v in zip(DISTILL_STATS_FIELDS[2:], host[2:].tolist())}
+    out["hard_sum"], out["kd_sum"] = (float(v) for v in host[:2].view(torch.float64).tolist())
+    return out
+
+
+def _check_teacher_logits(logits, teacher_logits) -> None:
+    if not isinstance(teacher_logits, torch.Tensor):
+        raise TypeError(f"teacher_logits: expected a torch.Tensor, got {type(teacher_logits).__name__}")
+    if teacher_logits.dtype != torch.float32:
+        raise TypeError(f"teacher_logits: expected float32, got {teacher_logits.dtype}")
+    if teacher_logits.device != logits.device:
+        raise RuntimeError(f"teacher_logits on {teacher_logits.device}, logits on {logits.device}")
+    if teacher_logits.shape != logits.shape or not teacher_logits.is_contiguous():
+        raise ValueError(f"teacher_logits: expected contiguous [{logits.shape[0]}, 2], got {tuple(teacher_logits.shape)}")
+
+
+def distill_opts(targets, weight=None, label_smoothing=0.0, ignore_index=-100, reduction="mean", focal_gamma=None):
+    """The hard term's options for the kind of `targets` (None, int64 labels, float32 probabilities), as ww_distill_loss_f32 takes them,
+    or None when every option is at its default.  Without a target only `reduction` is kept; refusals as loss_opts / soft_loss_opts."""
+    if targets is None:
+        loss_opts(weight, label_smoothing, ignore_index, reduction, focal_gamma)           # checked, then all but the reduction dropped
+        return loss_opts(reduction=reduction)
+    if targets.dtype == torch.float32:
+        return soft_loss_opts(weight, label_smoothing, reduction, focal_gamma, ignore_index)
+    return loss_opts(weight, label_smoothing, ignore_index, reduction, focal_gamma)
+
+
+def distill_loss_into(logits, teacher_logits, targets, dlogits, loss, stats, distill_stats, *, alpha=0.5, temperature=2.0, weight=None,
+                      label_smoothing=0.0, ignore_index=-100, reduction="mean", focal_gamma=None, opts=None) -> None:
+    """ww_distill_loss_f32 on caller-owned outputs (each may be None) and checked inputs: `targets` None (no target), int64 labels as
+    _check_ce returns them, or float32 probabilities [n, 2].  `opts`: what distill_opts made of the options, built once by a caller that
+    launches per batch (it wins over the keywords).  alpha and temperature are checked on the host (loss.check_distillation) before
+    anything is launched.  Allocates nothing on the device."""
+    from .loss import check_distillation
+    alpha, temperature = check_distillation(alpha, temperature)
+    opts = distill_opts(targets, weight, label_smoothing, ignore_index, reduction, focal_gamma) if opts is None else opts
+    kind = nat.TARGET_PROBS if targets is not None and targets.dtype == torch.float32 else nat.TARGET_LABELS
+    with torch.cuda.device(logits.device):
+        nat.check(nat.lib.ww_distill_loss_f32(_ptr(logits), _ptr(teacher_logits), None if targets is None else _ptr(targets), kind,
+                                              logits.shape[0], None if opts is None else C.byref(opts), alpha, temperature,
+                                              None if dlogits is None else _ptr(dlogits), None if loss is None else _ptr(loss),
+                                              None if stats is None else _ptr(stats),
+                                              None if distill_stats is None else _ptr(distill_stats), _stream()))
+
+
+def distill_loss(logits: torch.Tensor, teacher_logits: torch.Tensor, targets=None, stats=None, distill_stats=None, grad: bool = True, *,
+                 alpha=0.5, temperature=2.0, weight=None, label_smoothing=0.0, ignore_index=-100, reduction="mean", focal_gamma=None):
+    """L = (1 - alpha) H(logits, targets) + alpha T^2 KD(logits, teacher_logits), Hinton's distillation loss, in one launch:
+    (loss [] float32, dlogits [n, 2] or None with grad=False).  KD is F.kl_div(log_softmax(z / T), softmax(zt / T), "batchmean") over
+    the rows whose teacher logits are both finite.  `targets`: int64 labels [n] or [n, 1] (H as in ce_loss with the keyword options,
+    labels equal to ignore_index ignored), float32 class probabilities [n, 2] (H as in soft_ce_loss), or None -- unlabelled audio,
+    L = T^2 KD and alpha is not read.  Under "mean" each term is divided by its own denominator; a term without a counted row adds
+    exactly 0, and when neither has one the loss is NaN and the gradient all zeros.  `stats` as in ce_loss; `distill_stats`
+    (ops.new_distill_stats) accumulates the two terms, the student-teacher agreement and the teacher's accuracy.  A bad option, alpha
+    outside [0, 1] or a temperature that is not finite and > 0 raises ValueError before any device call."""
+    from .loss import check_distillation
+    check_distillation(alpha, temperature)
+    if targets is not None and not isinstance(targets, torch.Tensor):
+        raise TypeError(f"targets: expected a torch.Tensor or None, got {type(targets).__name__}")
+    opts = distill_opts(targets, weight, label_smoothing, ignore_index, reduction, focal_gamma)
+    _check_logits(logits)
+    _check_teacher_logits(logits, teacher_logits)
+    if targets is not None and targets.dtype == torch.float32:
+        _check_soft(logits, targets)
+    elif targets is not None:
+        targets = _check_ce(logits, targets)
+    if stats is not None:
+        _check_stats(stats, logits)
+    if distill_stats is not None:
+        _check_distill_stats(distill_stats, logits)
+    loss, dlogits = torch.empty((), device=logits.device, dtype=torch.float32), torch.empty_like(logits) if grad else None
+    distill_loss_into(logits, teacher_logits, targets, dlogits, loss, stats, distill_stats, alpha=alpha, temperature=temperature,
+                      opts=opts)                             # None: every option at its default, which the keywords' defaults repeat
+    return loss, dlogits
 
 
 def _check_mixup(mel, labels, partner, lam):

@@ -16,7 +16,7 @@ epoch and scatters every step's train-mode logits by the loader's `last_entries`
 eval-mode logits -- one more launch per batch, no wait.  With both None a step issues exactly the launches it
 always issued.
 
-A float32 target [B, 2] holds class probabilities (mixup through `processor.set_mixup`, distillation): `step` / `train_epoch` then run
+A float32 target [B, 2] holds class probabilities (mixup through `processor.set_mixup`, soft relabelling): `step` / `train_epoch` then run
 the soft cross-entropy (ww_ce_loss_soft_f32) in the loss's place, the launch count unchanged; `validate` keeps integer labels
 (INTEGRATION.md section 3n).
 
@@ -24,6 +24,13 @@ the soft cross-entropy (ww_ce_loss_soft_f32) in the loss's place, the launch cou
 average is written by the Adam launch itself (ww_adam_avg_step_f32 in ww_adam_step_f32's place -- `step` issues the same number of native
 calls), an every="epoch" one is updated once after `train_epoch`.  `evaluate="average"` makes `validate`, `val_report`, the monitor, the
 scheduler, early stopping and the best checkpoint follow `average.model`; the checkpoint gains "average_state_dict" when an average is set.
+
+`teacher=` (an eval-mode SimpleWakewordModel or WakewordModel on the same device, of either class; `average.model` gives the mean
+teacher) turns the step into knowledge distillation: the teacher's eval forward on the same batch into a
+persistent buffer, then ONE ww_distill_loss_f32 launch in the loss's place -- (1 - distill_alpha) * criterion + distill_alpha * T^2 * KD
+at T = distill_temperature -- with integer labels, class probabilities or no target at all (`step(data, None)`: unlabelled audio).
+`trainer.distill_stats` keeps the two terms apart on the device and `train_epoch` publishes them as `trainer.distill_report`.
+`validate` and the checkpoint do not change.  Without a teacher nothing here is reached.
 
 One deliberate difference: the reference calls `clip_grad_norm_` BEFORE `backward()`, where it clips the previous batch's gradients or
 nothing, so the default here is no clipping; `max_grad_norm=1.0` gives the clip the call meant, after the
@@ -50,9 +57,13 @@ EVALUATE = ("model", "average")
 
 class WakewordTrainer:
     def __init__(self, model, device, config=TrainingConfig, *, checkpoint_path="best_wakeword_model.pth", max_grad_norm=None,
-                 monitor="val_acc", thresholds=(0.8,), criterion=None, ledger=None, val_ledger=None, average=None, evaluate="model"):
+                 monitor="val_acc", thresholds=(0.8,), criterion=None, ledger=None, val_ledger=None, average=None, evaluate="model",
+                 teacher=None, distill_alpha=0.5, distill_temperature=2.0):
         if not isinstance(model, (SimpleWakewordModel, WakewordModel)):
             raise TypeError(f"WakewordTrainer drives the HIP training kernels of SimpleWakewordModel and WakewordModel; got {type(model).__name__}")
+        from .loss import check_distillation
+        self.distill_alpha, self.distill_temperature = check_distillation(distill_alpha, distill_temperature)
+        self._check_teacher(teacher, model)
         if any(p.device.type != "cuda" for p in model.parameters()):
             raise TypeError("WakewordTrainer: the model's parameters are on the CPU; this path has no CPU implementation (model.to('cuda'))")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
@@ -111,6 +122,18 @@ class WakewordTrainer:
         self._val_report = None
         self._validated = False
         self.last_loss = torch.zeros((), device=self._dev, dtype=torch.float32)       # the newest batch's mean loss, on the device
+        # ---- distillation: the teacher, its persistent forward buffers and the record of the two terms ----
+        self.teacher = teacher
+        self.distill_stats = self.distill_report = None
+        self._tlogits = self._tws = None
+        self._last_teacher_logits = None
+        if teacher is not None:
+            if any(p.device != self._dev for p in teacher.parameters()):
+                raise RuntimeError(f"WakewordTrainer: the teacher must be on the student's device ({self._dev})")
+            # one buffer behind both epoch records: train_epoch reads them in ONE device-to-host copy
+            self._epoch_stats = torch.zeros(len(ops.LOSS_STATS_FIELDS) + len(ops.DISTILL_STATS_FIELDS), device=self._dev, dtype=torch.int64)
+            self.train_stats = self._epoch_stats[:len(ops.LOSS_STATS_FIELDS)]
+            self.distill_stats = self._epoch_stats[len(ops.LOSS_STATS_FIELDS):]
         self._cap = 0                                                                  # clips the batch buffers hold
         self._logits = self._dlogits = None
         self._ws = None
@@ -141,6 +164,47 @@ class WakewordTrainer:
             raise TypeError(f"WakewordTrainer.criterion: the fused step computes nn.CrossEntropyLoss or FocalLoss, not {type(module).__name__} "
                             "(a hand-written loop over ops.train_forward can use any loss)")
         self._criterion, self._loss_opts = module, opts
+        self._no_target_opts = ops.loss_opts(reduction=module.reduction)      # an unlabelled distillation batch reads the reduction alone
+
+    # ---- distillation ----
+    @staticmethod
+    def _check_teacher(teacher, model) -> None:
+        """Refusals of a teacher that need no device: its class, the student itself, train mode, trainable parameters that are the
+        student's (the optimiser would move the teacher with every step)."""
+        if teacher is None:
+            return
+        if teacher is model:
+            raise ValueError("WakewordTrainer: the teacher is the model that is trained (for a mean teacher pass WeightAverage(model).model)")
+        if not isinstance(teacher, (SimpleWakewordModel, WakewordModel)):
+            raise TypeError(f"WakewordTrainer: the teacher runs on the HIP inference kernels of SimpleWakewordModel and WakewordModel; "
+                            f"got {type(teacher).__name__}")
+        if teacher.training:
+            raise RuntimeError("WakewordTrainer: the teacher is in train mode; call teacher.eval()")
+        own = {p.untyped_storage().data_ptr() for p in model.parameters()}
+        if any(p.requires_grad and p.untyped_storage().data_ptr() in own for p in teacher.parameters()):
+            raise ValueError("WakewordTrainer: a trainable parameter of the teacher shares its storage with the student's")
+
+    def _teacher_forward(self, x, B):
+        """The teacher's eval-mode logits of `x` in the persistent buffer: ww_model_forward_f32 on a persistent workspace, on the current
+        stream; the caller has made x's device current.  The packed weights are the teacher's own cache (model.packed_weights): built
+        once for a fixed teacher, rebuilt after every update of a mean teacher."""
+        t = self.teacher
+        if t.training:
+            raise RuntimeError("WakewordTrainer.step: the teacher is in train mode; call teacher.eval()")
+        need = ops.forward_workspace_bytes(B, t._n_conv)
+        if self._tws is None or self._tws.numel() < need:
+            self._tws = None
+            self._tws = torch.empty(need, device=self._dev, dtype=torch.uint8)
+        if self._tlogits is None or self._tlogits.shape[0] < self._cap:
+            self._tlogits = torch.empty((self._cap, 2), device=self._dev, dtype=torch.float32)
+        out = self._tlogits if B == self._tlogits.shape[0] else self._tlogits[:B]
+        ops.model_forward_into(x, t.packed_weights(), t._n_conv, self._tws, out)
+        return out
+
+    @property
+    def last_teacher_logits(self):
+        """The newest step's teacher logits [B, 2]: a view of the persistent buffer, or the `teacher_logits=` the step was given."""
+        return self._last_teacher_logits
 
     # ---- gradients: one persistent buffer per parameter, bound once ----
     def _bind_grads(self) -> None:
@@ -180,7 +244,7 @@ class WakewordTrainer:
         if target.device != self._dev:
             target = target.to(self._dev)
         if target.dtype == torch.float32 and soft:
-            # class probabilities [B, 2] (mixup, distillation): the soft cross-entropy of the fused step
+            # class probabilities [B, 2] (mixup, soft relabelling): the soft cross-entropy of the fused step, or the hard term beside a teacher
             if target.dim() != 2 or tuple(target.shape) != (B, 2):
                 raise ValueError(f"target: expected float32 class probabilities [{B}, 2], got {tuple(target.shape)}")
             return target if target.is_contiguous() else target.contiguous()
@@ -217,15 +281,20 @@ class WakewordTrainer:
                              "(torch refuses it too); leave it at -100")
         return self._loss_opts
 
-    def step(self, data, target, entries=None, labels=None) -> torch.Tensor:
+    def step(self, data, target, entries=None, labels=None, teacher_logits=None) -> torch.Tensor:
         """One training batch: data [B, 1, 80, T <= 32] float32 and target [B] or [B, 1] int64, both on the GPU (tensors elsewhere, or of
         another integer type, are copied first).  A float32 target [B, 2] holds class probabilities (mixup: what a loader yields under
-        `processor.set_mixup`; distillation): the step then launches ww_ce_loss_soft_f32 in place of the integer-label loss -- the same
+        `processor.set_mixup`; soft relabelling): the step then launches ww_ce_loss_soft_f32 in place of the integer-label loss -- the same
         number of launches, no wait, no allocation; `labels` [B] int64 on the device (train_epoch passes the loader's `last_labels`) are
         then what the ledger records.  Returns the batch's mean loss as a 0-d tensor ON THE DEVICE (self.last_loss, overwritten
         by the next step); the running metrics are in self.train_stats.  The model must be in train mode.  `entries` [B] (a host integer
         array or an int64 device tensor; train_epoch passes the loader's `last_entries`): with `self.ledger` set, the step's train-mode
-        logits and labels are added to it under these entries, one more launch after the optimiser's."""
+        logits and labels are added to it under these entries, one more launch after the optimiser's.
+
+        With a teacher (`teacher_logits`: float32 [B, 2] on the device, precomputed -- an ensemble, a teacher at another precision --
+        then take the teacher forward's place) the loss launch is ww_distill_loss_f32: (1 - distill_alpha) * criterion +
+        distill_alpha * T^2 * KD on integer labels or class probabilities, and on `target=None` (unlabelled audio) T^2 * KD alone.
+        Integer labels then follow the rule of a criterion WITH options even under the default one: a label of -100 is ignored."""
         if not self.model.training:
             raise RuntimeError("WakewordTrainer.step: the model is in eval mode (train_epoch calls model.train())")
         if isinstance(data, torch.Tensor) and data.device != self._dev:
@@ -237,10 +306,22 @@ class WakewordTrainer:
         B = x.shape[0]
         if B == 0:
             raise ValueError("empty training batch")
-        y = self._target(target, B, soft=True)
-        soft = y.dtype == torch.float32
+        distill = self.teacher is not None
+        if not distill and (target is None or teacher_logits is not None):
+            raise TypeError("WakewordTrainer.step: target=None (an unlabelled batch) and teacher_logits= need a teacher: "
+                            "WakewordTrainer(..., teacher=)")
+        y = None if target is None else self._target(target, B, soft=True)
+        soft = y is not None and y.dtype == torch.float32
         soft_opts = self._soft_opts() if soft else None
+        if teacher_logits is not None:
+            if (not isinstance(teacher_logits, torch.Tensor) or teacher_logits.dtype != torch.float32 or teacher_logits.device != self._dev
+                    or tuple(teacher_logits.shape) != (B, 2) or not teacher_logits.is_contiguous()):
+                raise ValueError(f"teacher_logits: expected a contiguous float32 [{B}, 2] tensor on {self._dev}")
         ledger_y = y
+        if y is None and entries is not None and self.ledger is not None:
+            if labels is None:
+                raise TypeError("a ledger on an unlabelled batch needs the rows' integer labels: step(..., labels=)")
+            ledger_y = self._target(labels, B)
         if soft and entries is not None and self.ledger is not None:
             if labels is None:
                 raise TypeError("a ledger with class-probability targets needs the rows' integer labels: step(..., labels=) "
@@ -263,7 +344,13 @@ class WakewordTrainer:
                 self._cap = B
             logits, m = self._logits if B == self._cap else self._logits[:B], self.model         # the buffers may hold more rows
             ops.train_forward_into(x, self._tp, m.lstm.dropout, m.dropout.p, seed, math, self._ws, logits)
-            if soft:
+            if distill:
+                zt = self._teacher_forward(x, B) if teacher_logits is None else teacher_logits
+                self._last_teacher_logits = zt
+                ops.distill_loss_into(logits, zt, y, self._dlogits, self.last_loss, self.train_stats, self.distill_stats,
+                                      alpha=self.distill_alpha, temperature=self.distill_temperature,
+                                      opts=self._no_target_opts if y is None else soft_opts if soft else self._loss_opts)
+            elif soft:
                 ops.soft_ce_loss_into(logits, y, self._dlogits, self.last_loss, self.train_stats, opts=soft_opts)
             else:
                 ops.ce_loss_into(logits, y, self._dlogits, self.last_loss, self.train_stats, opts=self._loss_opts)
@@ -290,9 +377,23 @@ class WakewordTrainer:
             raise ValueError(f"{what}: the loader gave no batch")
         return s["loss_sum"] / s["batches"], 100.0 * s["correct"] / s["total"]
 
+    @staticmethod
+    def _distill_report(d) -> dict:
+        """An epoch's ww_distill_stats as what one reads off it: the mean of the batches' hard and KD terms (neither weighted by
+        alpha; T^2 inside the KD term), the student-teacher agreement over the KD rows and the teacher's accuracy over the labelled
+        rows in percent (NaN without such rows), the rows with a non-finite teacher logit, and the counts behind them."""
+        nan = float("nan")
+        return {"hard_loss": d["hard_sum"] / d["batches"] if d["batches"] else nan,
+                "kd_loss": d["kd_sum"] / d["batches"] if d["batches"] else nan,
+                "agreement": 100.0 * d["agree"] / d["kd_rows"] if d["kd_rows"] else nan,
+                "teacher_accuracy": 100.0 * d["teacher_correct"] / d["hard_rows"] if d["hard_rows"] else nan,
+                "teacher_nonfinite": d["teacher_nonfinite"], "kd_rows": d["kd_rows"], "hard_rows": d["hard_rows"], "batches": d["batches"]}
+
     def train_epoch(self, train_loader):
         self.model.train()
         self.train_stats.zero_()
+        if self.teacher is not None:
+            self.distill_stats.zero_()
         if self.ledger is not None:
             self.ledger.begin_epoch()
         for data, target in train_loader:
@@ -300,7 +401,12 @@ class WakewordTrainer:
                 self.step(data, target)
             else:
                 self.step(data, target, self._entries_of(train_loader), getattr(train_loader, "last_labels", None))
-        result = self._finish_epoch(self.train_stats, "train_epoch")
+        if self.teacher is None:
+            result = self._finish_epoch(self.train_stats, "train_epoch")
+        else:
+            host = self._epoch_stats.cpu()                   # both records in the epoch's one device-to-host copy
+            result = self._finish_epoch(host[:len(ops.LOSS_STATS_FIELDS)], "train_epoch")
+            self.distill_report = self._distill_report(ops.read_distill_stats(host[len(ops.LOSS_STATS_FIELDS):]))
         if self.average is not None and self.average.every == "epoch":
             self.average.update()
         return result
