@@ -449,6 +449,51 @@ WW_API int ww_spec_augment_f32(const float* mel_in, float* mel_out, int64_t n, i
                                float prob, int32_t n_freq, int32_t freq_max, int32_t n_time, int32_t time_max, int32_t fill_mode,
                                float fill_value, ww_stream_t stream);
 
+/* ---- Microphone-channel augmentation: random EQ, band limit, clipping ---- */
+/* The waveform stage between the augmentation chain and K1 (the reference has none): a clip of N float32 samples goes through
+ * WW_CHANNEL_SECTIONS second-order sections in a fixed order, then an optional saturator.  Section s is
+ *   y[i] = b0 x[i] + b1 x[i-1] + b2 x[i-2] - a1 y[i-1] - a2 y[i-2]      (zero state before sample 0)
+ * and [1, 0, 0, 0, 0] is the identity; slot 0 is a high-pass, 1 a low shelf, 2..5 peaks, 6 a high shelf, 7 a low-pass (RBJ "Audio EQ
+ * Cookbook" forms at 16 kHz, normalised by a0; passes and shelves at Q = 1/sqrt(2)).  The saturator with drive d > 0:
+ *   p = max |y| over the clip after the cascade (a NaN is passed over); out = p tanh(d y / p) / tanh(d); p == 0: out = y
+ * Each clip has one record of WW_CHANNEL_RECORD_F32 float32 (ww_channel_record_bytes() = 192 bytes, 16-byte aligned):
+ *   8 x [b0, b1, b2, a1, a2], then d, then 7 zeros.  Eight identity sections and d == 0 mean "off": with pcm_out == pcm_in such a clip
+ *   is neither read nor written, otherwise it is copied bit for bit.
+ * Records: records_dev [n][48] filled by the caller (cfg may then be NULL), or NULL = drawn inside the kernel from cfg and SpecAugment's
+ * generator r(c, j) (above; c the clip's index in the batch, so clip c's record does not depend on n):
+ *   on(j, P)  = float(r >> 40) * 2^-24 < P            u(j) = double(r >> 11) * 2^-53
+ *   uniform   lo + u (hi - lo)                        log-uniform   lo * pow(hi / lo, u)            (float64; lo, hi the float32 fields)
+ *   j = 0  the clip is touched at all (prob)          1, 2  high-pass on, f          3, 4, 5  low shelf on, f, gain dB
+ *   6 + 4 i .. 9 + 4 i  peak i < peaks: on, f, gain dB, Q       22, 23, 24  high shelf on, f, gain dB
+ *   25, 26  low-pass on, f                            27, 28  saturator on, d
+ * Frequencies and Q are log-uniform, gains (within +-shelf_db, +-peak_db) and the drive uniform.  Coefficients are computed in float64 and
+ * rounded once to float32.  ww_channel_draw writes exactly the records ww_channel_f32 draws with records_dev NULL.
+ * Records the caller fills are trusted, not checked: poles outside the unit circle, NaN coefficients or a negative d give what the
+ * recurrence and the saturator give for them (the launch stays in bounds and ends whatever they hold).
+ * pcm rows: n rows of n_samples floats, row_stride floats apart (>= n_samples), the same for pcm_in and pcm_out; 4-byte aligned.
+ * Both launches are asynchronous, allocate and copy nothing and are capturable; n == 0 is WW_OK without a launch.  Checked before any HIP
+ * call: n_samples other than 16000 or 4000 .. 16383 (WW_EUNSUPPORTED); n outside 0 .. 2^30, a null or misaligned pointer, row_stride <
+ * n_samples, buffers that overlap without being the same, a probability outside [0, 1], a frequency outside (0, 7600], a Q <= 0 or > 1e6,
+ * peaks outside 0 .. 4, a drive outside [0, 8], a negative dB span, a reversed range or a non-finite field (WW_EINVAL). */
+#define WW_CHANNEL_SECTIONS 8
+#define WW_CHANNEL_MAX_PEAKS 4
+#define WW_CHANNEL_RECORD_F32 48
+typedef struct ww_channel_config {
+    float prob;
+    float highpass_prob, highpass_lo, highpass_hi;
+    float low_shelf_prob, low_shelf_lo, low_shelf_hi;
+    float high_shelf_prob, high_shelf_lo, high_shelf_hi;
+    float shelf_db;
+    float peak_prob, peak_lo, peak_hi, peak_db, peak_q_lo, peak_q_hi;
+    float lowpass_prob, lowpass_lo, lowpass_hi;
+    float drive_prob, drive_lo, drive_hi;
+    int32_t peaks;
+} ww_channel_config;
+WW_API int64_t ww_channel_record_bytes(void);
+WW_API int ww_channel_draw(uint64_t seed, int64_t n, const ww_channel_config* cfg, float* records_dev, ww_stream_t stream);
+WW_API int ww_channel_f32(const float* pcm_in, float* pcm_out, int64_t n, int64_t n_samples, int64_t row_stride, const float* records_dev,
+                          uint64_t seed, const ww_channel_config* cfg, ww_stream_t stream);
+
 /* ---- weights ------------------------------------------------------------------------------ */
 /* The reference state_dict (train_wakeword.py:28-36 / wakeword_training_script.py:141-165) as
  * host pointers in torch layout.  conv3_* are NULL for SimpleWakewordModel.  weight_hh_l* are not

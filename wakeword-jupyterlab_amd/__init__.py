@@ -21,7 +21,7 @@ def __getattr__(name):
     lazy = {"AudioProcessor": "audio", "WakewordDataset": "dataset", "DataLoader": "dataset", "SimpleWakewordModel": "model",
             "WakewordModel": "model", "StreamingDetector": "streaming", "predict_wakeword": "inference",
             "evaluate": "inference", "AudioConfig": "config", "ModelConfig": "config", "Config": "config",
-            "AugmentationConfig": "config", "SpecAugmentConfig": "config", "MixupConfig": "config", "BackgroundNoiseBank": "background", "ClipBank": "bank",
+            "AugmentationConfig": "config", "SpecAugmentConfig": "config", "ChannelConfig": "config", "MixupConfig": "config", "BackgroundNoiseBank": "background", "ClipBank": "bank",
             "ImpulseResponseBank": "reverb", "scan_files": "scan", "det_curve": "scan", "Scan": "scan", "TrainingConfig": "config", "FusedAdam": "optim",
             "WakewordTrainer": "trainer", "ClipReport": "metrics", "evaluate_report": "inference", "evaluate_report_pcm": "inference",
             "FocalLoss": "loss", "DistillationLoss": "loss", "balanced_class_weights": "loss", "balanced_order": "sampling", "BankAudit": "audit", "ClipLedger": "ledger", "LedgerReport": "ledger", "WeightAverage": "average"}

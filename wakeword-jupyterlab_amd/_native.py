@@ -115,6 +115,15 @@ class BankEntryStats(C.Structure):
 AUDIT_HOP, AUDIT_FRAME = 512, 2048
 SPEC_RECORD_INT16 = 16
 SPEC_FILL_MEAN, SPEC_FILL_MIN, SPEC_FILL_VALUE = 0, 1, 2
+CHANNEL_SECTIONS, CHANNEL_MAX_PEAKS, CHANNEL_RECORD_F32 = 8, 4, 48
+
+
+class ChannelConfig(C.Structure):
+    """struct ww_channel_config (include/wakeword_amd.h): what the channel stage's generator draws a record from."""
+    _fields_ = [(k, C.c_float) for k in (
+        "prob", "highpass_prob", "highpass_lo", "highpass_hi", "low_shelf_prob", "low_shelf_lo", "low_shelf_hi", "high_shelf_prob",
+        "high_shelf_lo", "high_shelf_hi", "shelf_db", "peak_prob", "peak_lo", "peak_hi", "peak_db", "peak_q_lo", "peak_q_hi", "lowpass_prob",
+        "lowpass_lo", "lowpass_hi", "drive_prob", "drive_lo", "drive_hi")] + [("peaks", C.c_int32)]
 
 
 class LossStats(C.Structure):
@@ -279,6 +288,10 @@ PROTOTYPES = {
                                        C.c_void_p]),
     "ww_spec_augment_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_uint64, C.c_float, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    "ww_channel_record_bytes": (C.c_int64, []),
+    "ww_channel_draw": (C.c_int, [C.c_uint64, C.c_int64, C.POINTER(ChannelConfig), C.c_void_p, C.c_void_p]),
+    "ww_channel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_uint64, C.POINTER(ChannelConfig),
+                                 C.c_void_p]),
     "ww_train_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "ww_train_forward_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(TrainParams), C.c_float, C.c_float, C.c_uint64, C.c_int32,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -17,6 +17,7 @@ T <= 32 (DURATION 0.25 .. 1.0, N = 4000 .. 16000 samples), and refuses longer cl
   set_background_noise(paths) -> background noise at a random SNR, mixed in after the stretch (background.py; not in the reference)
   set_room_impulse_responses(paths) -> reverberation with a random room impulse response, before the background (reverb.py; idem)
   set_spec_augment(config)    -> SpecAugment: blocks of mel bins and of frames masked on the log-mel batch, after K1 (idem)
+  set_channel_effects(config) -> microphone-channel augmentation: random EQ, band limit and clipping on the waveform, before K1 (idem)
   set_mixup(config)           -> mixup: rows of the log-mel batch mixed with a partner row, the targets with them, last of all (idem)
 `load_audio` / `process_audio_file` read the file with the library's native reader (csrc/ww_files.cpp) and decode, mix down and
 resample it on the GPU (kernel K0: scipy.signal.resample_poly's Kaiser design -- NOT librosa's soxr resampler, an absent third-party
@@ -201,6 +202,40 @@ class AudioProcessor:
             seed = random.getrandbits(64)
         return ops.spec_augment(mel, seed=seed, config=config, out=out)
 
+    def set_channel_effects(self, config):
+        """Turn the microphone-channel stage on (a config.ChannelConfig, or a class with its fields; validated here) or off (`None`, the
+        default).  From then on everything of this processor that augments -- process_audio_file(augment=True), WakewordDataset(augment=True)
+        per item and through loader() / batches(), ClipBank loaders with augment=True -- follows augment_batch with one in-place launch
+        on the waveform (a random equaliser and saturator per clip: the microphone hears speech, room, background and noise alike)
+        whose seed is one `random.getrandbits(64)` per batch, drawn after augment_batch's draws and before SpecAugment's seed.  Nothing
+        that runs with augment=False draws or launches anything more.  Returns the config (or None)."""
+        if config is not None:
+            from .config import check_channel_config
+            check_channel_config(config)
+        self._channel_effects = config
+        return config
+
+    @property
+    def channel_effects(self):
+        """The channel-effects config in force, or None."""
+        return getattr(self, "_channel_effects", None)
+
+    def channel_effects_batch(self, pcm, plans=None, seed=None, inplace=False) -> torch.Tensor:
+        """pcm [B, N] float32 on the GPU -> the batch through the channel stage, with the config in force (config.ChannelConfig when none
+        is set).  `plans`: a list of dicts per clip (ops.pack_channel_plans); else the records are drawn on the device from `seed`,
+        which is `random.getrandbits(64)` when not given."""
+        from .config import ChannelConfig
+        config = self.channel_effects or ChannelConfig
+        out = pcm if inplace else None
+        if plans is not None:
+            if seed is not None:
+                raise ValueError("channel_effects_batch: give `plans` or `seed`, not both")
+            records = torch.from_numpy(ops.pack_channel_plans(plans)).to(pcm.device)
+            return ops.channel_effects(pcm, records=records, config=config, out=out)
+        if seed is None:
+            seed = random.getrandbits(64)
+        return ops.channel_effects(pcm, seed=seed, config=config, out=out)
+
     def set_mixup(self, config):
         """Turn mixup on (a config.MixupConfig, or a class with its fields; validated here) or off (`None`, the default).  From then on
         the batched loaders that augment -- dataset.loader() / batches() of a WakewordDataset(augment=True), ClipBank loaders with
@@ -279,8 +314,9 @@ class AudioProcessor:
 
     def process_audio_file(self, file_path, augment=False):
         """load -> normalise over the whole file -> random crop / zero pad -> (augment) -> log-mel (:125-138), all on the GPU:
-        native reader -> K0 -> (KA) -> K1 -> (SpecAugment, when set_spec_augment is on).  The random draws are python `random`'s in
-        the reference's order (crop, then augmentation, then the masking seed)."""
+        native reader -> K0 -> (KA) -> (channel effects, when set_channel_effects is on) -> K1 -> (SpecAugment, when set_spec_augment is
+        on).  The random draws are python `random`'s in the reference's order (crop, then augmentation, then the channel seed, then the
+        masking seed)."""
         if augment:
             self._check_augment()
         pcm, ok = self.load_clips_gpu([file_path])
@@ -288,6 +324,8 @@ class AudioProcessor:
             return None
         if augment:
             pcm = self.augment_batch(pcm)
+            if self.channel_effects is not None:
+                self.channel_effects_batch(pcm, inplace=True)
         mel = self.mel_batch(pcm, normalize=False)
         if augment and self.spec_augment is not None:
             self.spec_augment_batch(mel, inplace=True)

@@ -443,7 +443,8 @@ class ClipBank:
 class BankLoader:
     """One epoch = the bank's items (ClipBank.item_entries), in order or in a fresh `torch.randperm` per epoch.  Per batch, in this order:
     the starts of its items in batch order (python `random`; `crop="active"` changes their range, not their number), the gather, `processor.augment_batch` when augmenting (which draws its
-    plans), `processor.mel_batch(pcm, normalize=False)`, `processor.spec_augment_batch(data, inplace=True)` when augmenting with
+    plans), `processor.channel_effects_batch(pcm, inplace=True)` when augmenting with `processor.set_channel_effects` on (which draws its
+    seed), `processor.mel_batch(pcm, normalize=False)`, `processor.spec_augment_batch(data, inplace=True)` when augmenting with
     `processor.set_spec_augment` on (which draws its seed), rows of placeholders set to 0.0 -- the draw order of the file loader, so a
     seeded epoch over the same files yields the same batches bit for bit.  `entries` (ClipBank.select_entries) keeps only the items of
     those entries.  `last_entries`: the bank entry of every row of the newest batch (host int64; -1 for a placeholder row, served as
@@ -494,6 +495,8 @@ class BankLoader:
             pcm = bank._gather(entries, starts, window[entries])
             if self.augment:
                 pcm = proc.augment_batch(pcm)
+                if getattr(proc, "channel_effects", None) is not None:
+                    proc.channel_effects_batch(pcm, inplace=True)
             data = proc.mel_batch(pcm, normalize=False)
             if self.augment and getattr(proc, "spec_augment", None) is not None:
                 proc.spec_augment_batch(data, inplace=True)

@@ -74,6 +74,83 @@ def check_spec_augment_config(cfg) -> None:
         raise ValueError(f"SpecAugment FILL {fill!r}: expected 'mean', 'min' or a float")
 
 
+class ChannelConfig:
+    """Microphone-channel augmentation on the waveform (AudioProcessor.set_channel_effects; not in the reference): a random equaliser
+    -- high-pass, low shelf, up to PEAKS peaks, high shelf, low-pass, each second-order and each on with its own probability -- and a
+    peak-preserving tanh saturator.  These values are this project's choices, not a published recipe's.  A clip is touched at all with
+    PROB.  Frequencies (Hz) and Q are drawn log-uniformly in their (lo, hi) range, gains uniformly in +-DB and the drive uniformly;
+    passes and shelves have Q = 1/sqrt(2)."""
+    PROB = 0.5
+    HIGHPASS_PROB = 0.5
+    HIGHPASS_HZ = (20.0, 400.0)
+    LOW_SHELF_PROB = 0.5
+    LOW_SHELF_HZ = (100.0, 400.0)
+    HIGH_SHELF_PROB = 0.5
+    HIGH_SHELF_HZ = (2000.0, 5000.0)
+    SHELF_DB = 6.0
+    PEAKS = 3
+    PEAK_PROB = 0.5
+    PEAK_HZ = (100.0, 6000.0)
+    PEAK_DB = 6.0
+    PEAK_Q = (0.5, 2.0)
+    LOWPASS_PROB = 0.3
+    LOWPASS_HZ = (3000.0, 7500.0)
+    DRIVE_PROB = 0.2
+    DRIVE = (0.5, 3.0)
+
+
+CHANNEL_SECTIONS = 8          # second-order sections one record holds (csrc/ww_channel.hip)
+CHANNEL_MAX_PEAKS = 4
+CHANNEL_MAX_HZ = 7600.0       # below Nyquist, where the cookbook forms stay well conditioned
+CHANNEL_MAX_DRIVE = 8.0
+CHANNEL_MAX_DB = 40.0
+CHANNEL_MAX_Q = 1e6
+
+
+def check_channel_config(cfg) -> None:
+    """ValueError for what the channel stage refuses: a probability outside [0, 1], a frequency outside (0, 7600], a Q <= 0, more than
+    4 peaks, a drive < 0 or > 8, a dB span outside [0, 40], a reversed range, a value that is not a finite number.  Every value is
+    judged as the float32 the kernel receives (a frequency of 1e-50 is 0 there), so what passes here passes the library's own check."""
+    import ctypes
+    import math
+
+    def num(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(float(v)):
+            raise ValueError(f"Channel {name} {v!r}: expected a finite number")
+        v = ctypes.c_float(float(v)).value
+        if not math.isfinite(v):
+            raise ValueError(f"Channel {name}: the value does not fit a float32")
+        return v
+
+    def rng(name):
+        v = getattr(cfg, name)
+        if not isinstance(v, (tuple, list)) or len(v) != 2:
+            raise ValueError(f"Channel {name} {v!r}: expected a (lo, hi) pair")
+        lo, hi = num(name, v[0]), num(name, v[1])
+        if lo > hi:
+            raise ValueError(f"Channel {name} {v!r}: the range is reversed")
+        return lo, hi
+
+    for name in ("PROB", "HIGHPASS_PROB", "LOW_SHELF_PROB", "HIGH_SHELF_PROB", "PEAK_PROB", "LOWPASS_PROB", "DRIVE_PROB"):
+        if not 0.0 <= num(name, getattr(cfg, name)) <= 1.0:
+            raise ValueError(f"Channel {name} {getattr(cfg, name)}: expected a probability in [0, 1]")
+    for name in ("HIGHPASS_HZ", "LOW_SHELF_HZ", "HIGH_SHELF_HZ", "PEAK_HZ", "LOWPASS_HZ"):
+        lo, hi = rng(name)
+        if not (0.0 < lo and hi <= CHANNEL_MAX_HZ):
+            raise ValueError(f"Channel {name} {getattr(cfg, name)}: expected frequencies in (0, {CHANNEL_MAX_HZ:g}] Hz")
+    q_lo, q_hi = rng("PEAK_Q")
+    if not (q_lo > 0.0 and q_hi <= CHANNEL_MAX_Q):
+        raise ValueError(f"Channel PEAK_Q {cfg.PEAK_Q}: expected 0 < Q <= {CHANNEL_MAX_Q:g}")
+    for name in ("SHELF_DB", "PEAK_DB"):
+        if not 0.0 <= num(name, getattr(cfg, name)) <= CHANNEL_MAX_DB:
+            raise ValueError(f"Channel {name} {getattr(cfg, name)}: expected a span in [0, {CHANNEL_MAX_DB:g}] dB")
+    if isinstance(cfg.PEAKS, bool) or int(cfg.PEAKS) != cfg.PEAKS or not 0 <= cfg.PEAKS <= CHANNEL_MAX_PEAKS:
+        raise ValueError(f"Channel PEAKS {cfg.PEAKS}: expected an integer in 0..{CHANNEL_MAX_PEAKS}")
+    lo, hi = rng("DRIVE")
+    if lo < 0.0 or hi > CHANNEL_MAX_DRIVE:
+        raise ValueError(f"Channel DRIVE {cfg.DRIVE}: expected drives in [0, {CHANNEL_MAX_DRIVE:g}]")
+
+
 class MixupConfig:
     """Mixup on the log-mel batch (AudioProcessor.set_mixup; Zhang et al. 2018; not in the reference).  A row is mixed with PROB; its
     weight lam is one Beta(ALPHA, ALPHA) draw, and with DOMINANT it is folded to lam >= 0.5 so that a row stays mostly itself.  PROB

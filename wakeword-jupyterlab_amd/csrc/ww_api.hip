@@ -656,6 +656,60 @@ int ww_spec_augment_f32(const float* mel_in, float* mel_out, int64_t n, int32_t 
     return launch_spec_augment(mel_in, mel_out, n, width, records_dev, d, fill_mode, fill_value, static_cast<hipStream_t>(stream));
 }
 
+// Microphone-channel augmentation: what the draw and the filter call share, all of it before any HIP call
+static int check_channel_config(const ww_channel_config* g) {
+    if (!g) return fail(WW_EINVAL, "null config pointer");
+    const float probs[] = {g->prob, g->highpass_prob, g->low_shelf_prob, g->high_shelf_prob, g->peak_prob, g->lowpass_prob, g->drive_prob};
+    for (float p : probs)
+        if (!(p >= 0.f && p <= 1.f)) return fail(WW_EINVAL, "probability %g outside [0, 1]", double(p));
+    const float hz[][2] = {{g->highpass_lo, g->highpass_hi}, {g->low_shelf_lo, g->low_shelf_hi}, {g->high_shelf_lo, g->high_shelf_hi},
+                           {g->peak_lo, g->peak_hi}, {g->lowpass_lo, g->lowpass_hi}};
+    for (const auto& r : hz)
+        if (!(r[0] > 0.f && r[0] <= r[1] && r[1] <= 7600.f))
+            return fail(WW_EINVAL, "frequency range (%g, %g): expected 0 < lo <= hi <= 7600 Hz", double(r[0]), double(r[1]));
+    if (!(g->peak_q_lo > 0.f && g->peak_q_lo <= g->peak_q_hi && g->peak_q_hi <= 1e6f))
+        return fail(WW_EINVAL, "Q range (%g, %g): expected 0 < lo <= hi", double(g->peak_q_lo), double(g->peak_q_hi));
+    if (!(g->shelf_db >= 0.f && g->shelf_db <= 40.f && g->peak_db >= 0.f && g->peak_db <= 40.f))
+        return fail(WW_EINVAL, "shelf_db %g / peak_db %g outside [0, 40]", double(g->shelf_db), double(g->peak_db));
+    if (g->peaks < 0 || g->peaks > WW_CHANNEL_MAX_PEAKS) return fail(WW_EINVAL, "peaks %d outside 0..%d", g->peaks, WW_CHANNEL_MAX_PEAKS);
+    if (!(g->drive_lo >= 0.f && g->drive_lo <= g->drive_hi && g->drive_hi <= 8.f))
+        return fail(WW_EINVAL, "drive range (%g, %g): expected 0 <= lo <= hi <= 8", double(g->drive_lo), double(g->drive_hi));
+    return WW_OK;
+}
+
+int64_t ww_channel_record_bytes(void) { return WW_CHANNEL_RECORD_F32 * int64_t(sizeof(float)); }
+
+int ww_channel_draw(uint64_t seed, int64_t n, const ww_channel_config* cfg, float* records_dev, ww_stream_t stream) {
+    if (n < 0 || n > (int64_t(1) << 30)) return fail(WW_EINVAL, "n %lld out of range", (long long)n);
+    if (int rc = check_channel_config(cfg)) return rc;
+    if (n == 0) return WW_OK;
+    if (!records_dev) return fail(WW_EINVAL, "null records pointer");
+    if (reinterpret_cast<uintptr_t>(records_dev) & 15) return fail(WW_EINVAL, "records_dev must be 16-byte aligned");
+    if (int rc = require_gfx950()) return rc;
+    return launch_channel_draw(*cfg, seed, n, records_dev, static_cast<hipStream_t>(stream));
+}
+
+int ww_channel_f32(const float* pcm_in, float* pcm_out, int64_t n, int64_t n_samples, int64_t row_stride, const float* records_dev,
+                   uint64_t seed, const ww_channel_config* cfg, ww_stream_t stream) {
+    if (n_samples < WW_MIN_CLIP_SAMPLES || n_samples > WW_AUG_MAX_SAMPLES)
+        return fail(WW_EUNSUPPORTED, "n_samples %lld: the channel stage takes clips of %d..%d samples", (long long)n_samples, WW_MIN_CLIP_SAMPLES,
+                    WW_AUG_MAX_SAMPLES);
+    if (n < 0 || n > (int64_t(1) << 30)) return fail(WW_EINVAL, "n %lld out of range", (long long)n);
+    if (!records_dev || cfg)
+        if (int rc = check_channel_config(cfg)) return rc;
+    if (n == 0) return WW_OK;
+    if (!pcm_in || !pcm_out) return fail(WW_EINVAL, "null pcm pointer");
+    if (row_stride < n_samples || row_stride > (int64_t(1) << 31)) return fail(WW_EINVAL, "row_stride %lld < n_samples %lld", (long long)row_stride, (long long)n_samples);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(pcm_in), b = reinterpret_cast<uintptr_t>(pcm_out);
+    if ((a & 3) || (b & 3) || (reinterpret_cast<uintptr_t>(records_dev) & 15))
+        return fail(WW_EINVAL, "pcm_in and pcm_out must be 4-byte and records_dev 16-byte aligned");
+    const uintptr_t bytes = (uintptr_t(n - 1) * uintptr_t(row_stride) + uintptr_t(n_samples)) * sizeof(float);
+    if (a != b && a < b + bytes && b < a + bytes) return fail(WW_EINVAL, "pcm_in and pcm_out overlap partially: pass the same buffer or disjoint ones");
+    if (int rc = require_gfx950()) return rc;
+    static const ww_channel_config none = {};
+    return launch_channel(pcm_in, pcm_out, n, int(n_samples), row_stride, records_dev, seed, cfg ? *cfg : none, static_cast<hipStream_t>(stream));
+}
+
 int64_t ww_cnn_scratch_bytes(int64_t n, int32_t n_conv) { return cnn_scratch_bytes(n, n_conv); }
 
 int ww_cnn_pool_f32(const float* mel_dev, int64_t n, int32_t width, const float* packed_dev, int32_t n_conv,

@@ -191,6 +191,11 @@ int launch_spec_draw(const SpecDraw& d, int64_t n, int T, int16_t* records, hipS
 // records NULL: drawn from `d` inside the kernel; in == out or disjoint (the entry point checks)
 int launch_spec_augment(const float* in, float* out, int64_t n, int T, const int16_t* records, const SpecDraw& d, int mode, float fill_value,
                         hipStream_t stream);
+// microphone-channel augmentation (ww_channel.hip): records [n][48] float32 or NULL = drawn from (seed, g) inside the kernel; in == out or
+// disjoint, n_samples 4000 .. 16383 (the entry point checks)
+int launch_channel_draw(const ww_channel_config& g, uint64_t seed, int64_t n, float* records, hipStream_t stream);
+int launch_channel(const float* in, float* out, int64_t n, int n_samples, int64_t row_stride, const float* records, uint64_t seed,
+                   const ww_channel_config& g, hipStream_t stream);
 // mixup on log-mel batches (ww_mixup.hip): out of place; 16-byte accesses when mel and out are both 16-byte aligned
 int launch_mixup(const float* mel, float* out, int64_t B, int T, const int64_t* labels, const int32_t* partner, const float* lambda,
                  float* targets, hipStream_t stream);

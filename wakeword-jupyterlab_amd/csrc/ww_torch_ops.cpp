@@ -3,7 +3,8 @@
 // torch.library (no Meta kernel: FakeTensor tracing / torch.compile of the drop-in modules could not work, and every call paid Python
 // dispatch); this translation unit replaces them.  It is host code only: it validates tensors, allocates outputs with ATen and calls
 //   ww_logmel_f32 / ww_cnn_pool_f32 / ww_lstm_fc_f32 / ww_model_forward_f32 / ww_forward_pcm_f32      (include/wakeword_amd.h)
-// and, for clips of 0.25 s to 2 s, ww_logmel_frames_f32 / ww_cnn_pool_wide_f32 / ww_forward_pcm_frames_f32, and ww_spec_augment_f32
+// and, for clips of 0.25 s to 2 s, ww_logmel_frames_f32 / ww_cnn_pool_wide_f32 / ww_forward_pcm_frames_f32, and ww_spec_augment_f32 and
+// ww_channel_f32
 // on torch's current HIP stream.  The ww_* functions are neither linked nor looked up by name: the Python package hands their ADDRESSES in
 // (ww_torch_bind, from the ctypes handle of libwakeword_amd.so or of the build named by WW_LIB_OVERRIDE), so nothing enters the global
 // symbol scope -- several builds of the library can live in one process (scripts/ab_kernels.py) without interposing each other's kernels.
@@ -40,8 +41,9 @@ struct Abi {
     decltype(&::ww_workspace_frames_bytes) workspace_frames_bytes = nullptr;
     decltype(&::ww_forward_pcm_frames_f32) forward_pcm_frames_f32 = nullptr;
     decltype(&::ww_spec_augment_f32) spec_augment_f32 = nullptr;
+    decltype(&::ww_channel_f32) channel_f32 = nullptr;
 } abi;
-constexpr int kAbiEntries = 15;
+constexpr int kAbiEntries = 16;
 const Abi& bound() {
     TORCH_CHECK(abi.forward_pcm_f32 != nullptr, "wakeword_amd: the operators are not bound to libwakeword_amd.so (import wakeword_jupyterlab_amd does it)");
     return abi;
@@ -61,6 +63,7 @@ const Abi& bound() {
 #define ww_workspace_frames_bytes bound().workspace_frames_bytes
 #define ww_forward_pcm_frames_f32 bound().forward_pcm_frames_f32
 #define ww_spec_augment_f32 bound().spec_augment_f32
+#define ww_channel_f32 bound().channel_f32
 
 void* stream_of(const at::Tensor& t) { return static_cast<void*>(c10::hip::getCurrentHIPStream(t.device().index()).stream()); }
 
@@ -256,6 +259,31 @@ at::Tensor spec_augment_cuda(const at::Tensor& mel_in, const at::Tensor& records
     return out;
 }
 
+// Microphone-channel augmentation, out of place: pcm [B, N] float32, records float32 [B, 48] on the same device
+void check_channel_shapes(const at::Tensor& pcm, const at::Tensor& records) {
+    TORCH_CHECK(pcm.scalar_type() == at::kFloat, "pcm: expected float32, got ", pcm.scalar_type());
+    TORCH_CHECK(pcm.dim() == 2, "pcm: expected [B, samples], got ", pcm.sizes());
+    const int64_t n = pcm.size(1);
+    TORCH_CHECK_NOT_IMPLEMENTED(n >= kMinSamples && n <= WW_AUG_MAX_SAMPLES, "pcm: ", n, " samples per clip; the channel stage takes ", kMinSamples,
+                                "..", WW_AUG_MAX_SAMPLES);
+    TORCH_CHECK(records.scalar_type() == at::kFloat && records.dim() == 2 && records.size(0) == pcm.size(0) && records.size(1) == WW_CHANNEL_RECORD_F32,
+                "records: expected float32 [", pcm.size(0), ", ", WW_CHANNEL_RECORD_F32, "], got ", records.scalar_type(), " ", records.sizes());
+    TORCH_CHECK(records.device() == pcm.device(), "records on ", records.device(), ", pcm on ", pcm.device());
+}
+
+at::Tensor channel_effects_cuda(const at::Tensor& pcm_in, const at::Tensor& records_in) {
+    require_cuda_f32(pcm_in, "pcm");
+    check_channel_shapes(pcm_in, records_in);
+    const at::Tensor pcm = pcm_in.contiguous();
+    at::Tensor records = records_in.contiguous();
+    if (reinterpret_cast<uintptr_t>(records.data_ptr()) % 16) records = records.clone();
+    at::Tensor out = at::empty_like(pcm);
+    c10::DeviceGuard guard(pcm.device());
+    check_rc(ww_channel_f32(pcm.data_ptr<float>(), out.data_ptr<float>(), pcm.size(0), pcm.size(1), pcm.size(1), records.data_ptr<float>(), 0, nullptr,
+                            stream_of(pcm)), "channel_effects");
+    return out;
+}
+
 // ---------------------------------------------------------------- Meta kernels: shapes only (FakeTensor / torch.compile tracing)
 at::Tensor logmel_meta(const at::Tensor& pcm, bool) {
     TORCH_CHECK(pcm.dim() == 2 && pcm.size(1) >= 1 && pcm.size(1) <= kClip, "pcm: expected [B, 1..", kClip, "], got ", pcm.sizes());
@@ -303,6 +331,11 @@ at::Tensor spec_augment_meta(const at::Tensor& mel, const at::Tensor& records, i
     return at::empty(mel.sizes(), mel.options());
 }
 
+at::Tensor channel_effects_meta(const at::Tensor& pcm, const at::Tensor& records) {
+    check_channel_shapes(pcm, records);
+    return at::empty(pcm.sizes(), pcm.options());
+}
+
 // ---------------------------------------------------------------- CPU: there is none
 [[noreturn]] void no_cpu(const char* name) {
     TORCH_CHECK(false, "wakeword_amd::", name, ": no CPU implementation exists (HIP/gfx950 only); move the tensors to the GPU");
@@ -316,6 +349,7 @@ at::Tensor logmel_frames_cpu(const at::Tensor&, int64_t, bool) { no_cpu("logmel_
 at::Tensor cnn_pool_wide_cpu(const at::Tensor&, const at::Tensor&, int64_t) { no_cpu("cnn_pool_wide"); }
 at::Tensor forward_pcm_frames_cpu(const at::Tensor&, const at::Tensor&, int64_t, int64_t, bool) { no_cpu("forward_pcm_frames"); }
 at::Tensor spec_augment_cpu(const at::Tensor&, const at::Tensor&, int64_t, double) { no_cpu("spec_augment"); }
+at::Tensor channel_effects_cpu(const at::Tensor&, const at::Tensor&) { no_cpu("channel_effects"); }
 
 }  // namespace
 
@@ -334,10 +368,11 @@ at::Tensor spec_augment_cpu(const at::Tensor&, const at::Tensor&, int64_t, doubl
 #undef ww_workspace_frames_bytes
 #undef ww_forward_pcm_frames_f32
 #undef ww_spec_augment_f32
+#undef ww_channel_f32
 
 // fns[kAbiEntries]: addresses of ww_last_error, ww_packed_weights_floats, ww_cnn_scratch_bytes, ww_workspace_bytes, ww_logmel_f32,
 // ww_cnn_pool_f32, ww_lstm_fc_f32, ww_model_forward_f32, ww_forward_pcm_f32, ww_logmel_frames_f32, ww_cnn_wide_scratch_bytes, ww_cnn_pool_wide_f32,
-// ww_workspace_frames_bytes, ww_forward_pcm_frames_f32, ww_spec_augment_f32 of ONE build of libwakeword_amd.so.  Returns 0, or -1 on a bad table.
+// ww_workspace_frames_bytes, ww_forward_pcm_frames_f32, ww_spec_augment_f32, ww_channel_f32 of ONE build of libwakeword_amd.so.  Returns 0, or -1 on a bad table.
 extern "C" __attribute__((visibility("default"))) int ww_torch_bind(const void* const* fns, int n) {
     if (!fns || n != kAbiEntries) return -1;
     for (int i = 0; i < n; ++i)
@@ -357,6 +392,7 @@ extern "C" __attribute__((visibility("default"))) int ww_torch_bind(const void* 
     abi.workspace_frames_bytes = reinterpret_cast<decltype(abi.workspace_frames_bytes)>(const_cast<void*>(fns[12]));
     abi.forward_pcm_frames_f32 = reinterpret_cast<decltype(abi.forward_pcm_frames_f32)>(const_cast<void*>(fns[13]));
     abi.spec_augment_f32 = reinterpret_cast<decltype(abi.spec_augment_f32)>(const_cast<void*>(fns[14]));
+    abi.channel_f32 = reinterpret_cast<decltype(abi.channel_f32)>(const_cast<void*>(fns[15]));
     return 0;
 }
 
@@ -370,6 +406,7 @@ TORCH_LIBRARY(wakeword_amd, m) {
     m.def("cnn_pool_wide(Tensor x, Tensor packed, int n_conv) -> Tensor");
     m.def("forward_pcm_frames(Tensor pcm, Tensor packed, int n_conv, int n_samples, bool normalize=True) -> Tensor");
     m.def("spec_augment(Tensor mel, Tensor records, int fill_mode, float fill_value) -> Tensor");
+    m.def("channel_effects(Tensor pcm, Tensor records) -> Tensor");
 }
 TORCH_LIBRARY_IMPL(wakeword_amd, CUDA, m) {
     m.impl("logmel", &logmel_cuda);
@@ -381,6 +418,7 @@ TORCH_LIBRARY_IMPL(wakeword_amd, CUDA, m) {
     m.impl("cnn_pool_wide", &cnn_pool_wide_cuda);
     m.impl("forward_pcm_frames", &forward_pcm_frames_cuda);
     m.impl("spec_augment", &spec_augment_cuda);
+    m.impl("channel_effects", &channel_effects_cuda);
 }
 TORCH_LIBRARY_IMPL(wakeword_amd, Meta, m) {
     m.impl("logmel", &logmel_meta);
@@ -392,6 +430,7 @@ TORCH_LIBRARY_IMPL(wakeword_amd, Meta, m) {
     m.impl("cnn_pool_wide", &cnn_pool_wide_meta);
     m.impl("forward_pcm_frames", &forward_pcm_frames_meta);
     m.impl("spec_augment", &spec_augment_meta);
+    m.impl("channel_effects", &channel_effects_meta);
 }
 TORCH_LIBRARY_IMPL(wakeword_amd, CPU, m) {
     m.impl("logmel", &logmel_cpu);
@@ -403,4 +442,5 @@ TORCH_LIBRARY_IMPL(wakeword_amd, CPU, m) {
     m.impl("cnn_pool_wide", &cnn_pool_wide_cpu);
     m.impl("forward_pcm_frames", &forward_pcm_frames_cpu);
     m.impl("spec_augment", &spec_augment_cpu);
+    m.impl("channel_effects", &channel_effects_cpu);
 }

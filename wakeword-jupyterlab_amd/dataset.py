@@ -13,7 +13,8 @@ substitute is zeros of the real width, [80, 32] -- or [80, T] for a processor co
 (0.25 .. 2 s: items and batches are [1, 80, T] / [B, 1, 80, T], T = 1 + int(16000 * DURATION) // 512).
 
 `augment=True` (the training split, :456) runs AudioProcessor.augment_audio's transforms on the GPU (kernels KA)
-between decode and log-mel: per item in `__getitem__`, per batch in `batches()`; with `processor.set_spec_augment(config)` it also masks
+between decode and log-mel: per item in `__getitem__`, per batch in `batches()`; with `processor.set_channel_effects(config)` it also
+runs a random equaliser and saturator on the augmented waveform, in place, before K1; with `processor.set_spec_augment(config)` it also masks
 blocks of mel bins and frames of the log-mel batch, in place, after K1.  Augmentation, and so the training split, takes
 DURATION 0.25 .. 1.0 (T = 8 .. 32); longer clips serve inference only (augment=False).
 """
@@ -146,6 +147,8 @@ class GpuBatchLoader:
             # both loaders already peak-normalised each file before the crop/pad, as the reference does (:131-133)
             if ds.augment:
                 pcm_dev = ds.processor.augment_batch(pcm_dev)          # process_audio_file :134-135
+                if getattr(ds.processor, "channel_effects", None) is not None:
+                    ds.processor.channel_effects_batch(pcm_dev, inplace=True)    # one seed per batch, drawn after augment_batch's plans
             data = ds.processor.mel_batch(pcm_dev, normalize=False)
             if ds.augment and getattr(ds.processor, "spec_augment", None) is not None:
                 ds.processor.spec_augment_batch(data, inplace=True)    # one seed per batch, drawn after augment_batch's plans

@@ -19,7 +19,8 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .config import CLIP_SAMPLES, N_FRAMES, SPEC_MAX_MASKS, AudioConfig, SpecAugmentConfig, check_spec_augment_config
+from .config import (CHANNEL_MAX_DRIVE, CHANNEL_MAX_HZ, CHANNEL_MAX_PEAKS, CHANNEL_SECTIONS, CLIP_SAMPLES, N_FRAMES, SPEC_MAX_MASKS, AudioConfig,
+                     ChannelConfig, SpecAugmentConfig, check_channel_config, check_spec_augment_config)
 
 N_MELS = AudioConfig.N_MELS
 MAX_FRAMES = 63                         # 1 + 32000 // 512
@@ -242,7 +243,7 @@ def _forward_pcm_impl(pcm: torch.Tensor, packed: torch.Tensor, n_conv: int, norm
 # section 7 step 2).  The CUDA kernels validate, allocate with ATen and call the C ABI on torch's current stream; the Meta kernels give
 # shapes only (FakeTensor / torch.compile tracing of the drop-in modules); the CPU kernels refuse.  Rounds 1-3 registered the Python
 # functions above through torch.library; those stay as plain functions (`_logmel_impl` ...: tests and the raw launches of bench.py's legs).
-# The library does not link libwakeword_amd.so: it is handed the addresses of the fifteen C ABI functions it calls.
+# The library does not link libwakeword_amd.so: it is handed the addresses of the sixteen C ABI functions it calls.
 # No fallback: without the compiled library the package does not import.
 TORCH_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libwakeword_amd_torch.so")
 if not os.path.exists(TORCH_LIB_PATH):
@@ -253,7 +254,7 @@ torch.ops.load_library(TORCH_LIB_PATH)
 _TORCH_BIND_ORDER = ("ww_last_error", "ww_packed_weights_floats", "ww_cnn_scratch_bytes", "ww_workspace_bytes", "ww_logmel_f32",
                      "ww_cnn_pool_f32", "ww_lstm_fc_f32", "ww_model_forward_f32", "ww_forward_pcm_f32",
                      "ww_logmel_frames_f32", "ww_cnn_wide_scratch_bytes", "ww_cnn_pool_wide_f32", "ww_workspace_frames_bytes",
-                     "ww_forward_pcm_frames_f32", "ww_spec_augment_f32")
+                     "ww_forward_pcm_frames_f32", "ww_spec_augment_f32", "ww_channel_f32")
 _torch_lib = C.CDLL(TORCH_LIB_PATH)
 _table = (C.c_void_p * len(_TORCH_BIND_ORDER))(*[C.cast(getattr(nat.lib, _n), C.c_void_p).value for _n in _TORCH_BIND_ORDER])
 if _torch_lib.ww_torch_bind(_table, len(_TORCH_BIND_ORDER)) != 0:
@@ -1479,4 +1480,150 @@ def spec_augment(mel: torch.Tensor, records=None, *, seed=None, config=SpecAugme
     with torch.cuda.device(mel.device):
         nat.check(nat.lib.ww_spec_augment_f32(_ptr(mel), _ptr(out), B, T, None if records is None else _ptr(records), int(seed) & (2 ** 64 - 1),
                                               prob, n_freq, freq_max, n_time, time_max, mode, value, _stream()))
+    return out
+
+
+# ---- microphone-channel augmentation: random EQ, band limit, clipping (csrc/ww_channel.hip) -------------
+CHANNEL_MIN_SAMPLES, CHANNEL_MAX_SAMPLES = 4000, 16383
+
+
+def _channel_struct(config) -> "nat.ChannelConfig":
+    """config.ChannelConfig (or a class with its fields; validated) as the struct ww_channel_draw / ww_channel_f32 take."""
+    check_channel_config(config)
+    g = nat.ChannelConfig()
+    g.prob = config.PROB
+    g.highpass_prob, (g.highpass_lo, g.highpass_hi) = config.HIGHPASS_PROB, config.HIGHPASS_HZ
+    g.low_shelf_prob, (g.low_shelf_lo, g.low_shelf_hi) = config.LOW_SHELF_PROB, config.LOW_SHELF_HZ
+    g.high_shelf_prob, (g.high_shelf_lo, g.high_shelf_hi) = config.HIGH_SHELF_PROB, config.HIGH_SHELF_HZ
+    g.shelf_db = config.SHELF_DB
+    g.peak_prob, (g.peak_lo, g.peak_hi), g.peak_db, (g.peak_q_lo, g.peak_q_hi) = config.PEAK_PROB, config.PEAK_HZ, config.PEAK_DB, config.PEAK_Q
+    g.lowpass_prob, (g.lowpass_lo, g.lowpass_hi) = config.LOWPASS_PROB, config.LOWPASS_HZ
+    g.drive_prob, (g.drive_lo, g.drive_hi) = config.DRIVE_PROB, config.DRIVE
+    g.peaks = int(config.PEAKS)
+    return g
+
+
+def channel_records(seed: int, B: int, config=ChannelConfig, device=None) -> torch.Tensor:
+    """The records `channel_effects(pcm, seed=seed, config=config)` applies to a batch of B clips: float32 [B, 48] on the device,
+    8 x [b0, b1, b2, a1, a2], the drive d, 7 zeros per clip (ww_channel_draw).  Clip c's record does not depend on B."""
+    if B < 0:
+        raise ValueError(f"channel_records: B = {B}")
+    g = _channel_struct(config)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"channel_records on {device}: this path has no CPU implementation")
+    records = torch.empty((B, nat.CHANNEL_RECORD_F32), device=device, dtype=torch.float32)
+    with torch.cuda.device(device):
+        nat.check(nat.lib.ww_channel_draw(int(seed) & (2 ** 64 - 1), B, C.byref(g), _ptr(records), _stream()))
+    return records
+
+
+def channel_coefficients(kind: str, hz: float, db: float = 0.0, q: float = 2.0 ** -0.5):
+    """One second-order section of the RBJ "Audio EQ Cookbook" at 16 kHz in numpy float64: (b0, b1, b2, a1, a2), divided by a0.
+    kind: "highpass", "lowpass", "peak", "low_shelf", "high_shelf"; the shelves take q as their slope's Q."""
+    w0 = 2.0 * np.pi * np.float64(hz) / 16000.0
+    cs, alpha = np.cos(w0), np.sin(w0) / (2.0 * np.float64(q))
+    A = np.power(np.float64(10.0), np.float64(db) / 40.0)
+    if kind == "highpass":
+        b, a = ((1.0 + cs) / 2.0, -(1.0 + cs), (1.0 + cs) / 2.0), (1.0 + alpha, -2.0 * cs, 1.0 - alpha)
+    elif kind == "lowpass":
+        b, a = ((1.0 - cs) / 2.0, 1.0 - cs, (1.0 - cs) / 2.0), (1.0 + alpha, -2.0 * cs, 1.0 - alpha)
+    elif kind == "peak":
+        b, a = (1.0 + alpha * A, -2.0 * cs, 1.0 - alpha * A), (1.0 + alpha / A, -2.0 * cs, 1.0 - alpha / A)
+    elif kind in ("low_shelf", "high_shelf"):
+        t, ap, am = 2.0 * np.sqrt(A) * alpha, A + 1.0, A - 1.0
+        if kind == "low_shelf":
+            b = (A * (ap - am * cs + t), 2.0 * A * (am - ap * cs), A * (ap - am * cs - t))
+            a = (ap + am * cs + t, -2.0 * (am + ap * cs), ap + am * cs - t)
+        else:
+            b = (A * (ap + am * cs + t), -2.0 * A * (am + ap * cs), A * (ap + am * cs - t))
+            a = (ap - am * cs + t, 2.0 * (am - ap * cs), ap - am * cs - t)
+    else:
+        raise ValueError(f"channel_coefficients: unknown section kind {kind!r}")
+    return np.array([b[0] / a[0], b[1] / a[0], b[2] / a[0], a[1] / a[0], a[2] / a[0]], dtype=np.float64)
+
+
+def pack_channel_plans(plans) -> np.ndarray:
+    """A list of dicts, one per clip -> numpy float32 [B, 48] in the kernel's record layout.  Keys, all optional: "highpass": hz,
+    "low_shelf": (hz, db), "peaks": [(hz, db, q), ...] (at most 4), "high_shelf": (hz, db), "lowpass": hz, "drive": d.  A missing key is
+    an identity section (no saturator).  The coefficients are computed in numpy float64 (channel_coefficients) and rounded once.
+    ValueError for a frequency outside (0, 7600], a Q <= 0, more than 4 peaks or a drive outside [0, 8]."""
+    out = np.zeros((len(plans), nat.CHANNEL_RECORD_F32), dtype=np.float32)
+    out[:, 0:5 * CHANNEL_SECTIONS:5] = 1.0
+
+    def hz_of(i, v):
+        v = float(v)
+        if not 0.0 < v <= CHANNEL_MAX_HZ:
+            raise ValueError(f"plan {i}: frequency {v} outside (0, {CHANNEL_MAX_HZ:g}] Hz")
+        return v
+
+    for i, plan in enumerate(plans):
+        unknown = set(plan) - {"highpass", "low_shelf", "peaks", "high_shelf", "lowpass", "drive"}
+        if unknown:
+            raise ValueError(f"plan {i}: unknown keys {sorted(unknown)}")
+        sections = {}
+        if plan.get("highpass") is not None:
+            sections[0] = channel_coefficients("highpass", hz_of(i, plan["highpass"]))
+        if plan.get("low_shelf") is not None:
+            sections[1] = channel_coefficients("low_shelf", hz_of(i, plan["low_shelf"][0]), float(plan["low_shelf"][1]))
+        peaks = list(plan.get("peaks") or ())
+        if len(peaks) > CHANNEL_MAX_PEAKS:
+            raise ValueError(f"plan {i}: {len(peaks)} peaks; a record holds {CHANNEL_MAX_PEAKS}")
+        for k, (hz, db, q) in enumerate(peaks):
+            if not float(q) > 0.0:
+                raise ValueError(f"plan {i}: peak Q {q} <= 0")
+            sections[2 + k] = channel_coefficients("peak", hz_of(i, hz), float(db), float(q))
+        if plan.get("high_shelf") is not None:
+            sections[6] = channel_coefficients("high_shelf", hz_of(i, plan["high_shelf"][0]), float(plan["high_shelf"][1]))
+        if plan.get("lowpass") is not None:
+            sections[7] = channel_coefficients("lowpass", hz_of(i, plan["lowpass"]))
+        for slot, co in sections.items():
+            out[i, 5 * slot:5 * slot + 5] = co.astype(np.float32)
+        d = float(plan.get("drive") or 0.0)
+        if not 0.0 <= d <= CHANNEL_MAX_DRIVE:
+            raise ValueError(f"plan {i}: drive {d} outside [0, {CHANNEL_MAX_DRIVE:g}]")
+        out[i, 5 * CHANNEL_SECTIONS] = d
+    return out
+
+
+def _require_channel_pcm(pcm) -> None:
+    if not isinstance(pcm, torch.Tensor):
+        raise TypeError(f"pcm: expected a torch.Tensor, got {type(pcm).__name__}")
+    if pcm.device.type != "cuda":
+        raise RuntimeError(f"pcm is on {pcm.device}: this path has no CPU implementation; move it to the MI355X (`.cuda()`)")
+    if pcm.dtype != torch.float32 or pcm.dim() != 2 or not pcm.is_contiguous():
+        raise ValueError(f"pcm: expected contiguous float32 [B, N], got {pcm.dtype} {tuple(pcm.shape)}")
+    if not CHANNEL_MIN_SAMPLES <= pcm.shape[1] <= CHANNEL_MAX_SAMPLES:
+        raise NotImplementedError(f"pcm: {pcm.shape[1]} samples per clip; the channel stage takes {CHANNEL_MIN_SAMPLES}..{CHANNEL_MAX_SAMPLES} "
+                                  "(the lengths augmentation runs at)")
+
+
+def channel_effects(pcm: torch.Tensor, records=None, *, seed=None, config=ChannelConfig, out=None) -> torch.Tensor:
+    """pcm float32 [B, N] on the GPU, contiguous, N = 4000 .. 16383 -> the same shape, every clip through its record's second-order
+    sections and saturator.  Exactly one of `records` (float32 [B, 48] on the device: channel_records, or pack_channel_plans uploaded)
+    and `seed` (the records are drawn inside the kernel from `config`) is given.  `out=pcm` filters in place (a clip whose record is
+    "off" is then neither read nor written); any other `out` is a contiguous tensor like pcm that does not overlap it."""
+    _require_channel_pcm(pcm)
+    B, N = int(pcm.shape[0]), int(pcm.shape[1])
+    if (records is None) == (seed is None):
+        raise ValueError("channel_effects: give exactly one of `records` and `seed`")
+    g = None
+    if records is not None:
+        if (not isinstance(records, torch.Tensor) or records.dtype != torch.float32 or tuple(records.shape) != (B, nat.CHANNEL_RECORD_F32)
+                or records.device != pcm.device):
+            raise ValueError(f"records: expected float32 [{B}, {nat.CHANNEL_RECORD_F32}] on {pcm.device}")
+        records = records.contiguous()
+        if records.data_ptr() % 16:
+            records = records.clone()
+        seed = 0
+    else:
+        g = _channel_struct(config)
+    if out is None:
+        out = torch.empty_like(pcm)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != pcm.shape or out.device != pcm.device
+          or not out.is_contiguous()):
+        raise ValueError("out: expected a contiguous float32 tensor of pcm's shape on pcm's device")
+    with torch.cuda.device(pcm.device):
+        nat.check(nat.lib.ww_channel_f32(_ptr(pcm), _ptr(out), B, N, N, None if records is None else _ptr(records), int(seed) & (2 ** 64 - 1),
+                                         None if g is None else C.byref(g), _stream()))
     return out
