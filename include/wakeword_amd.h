@@ -900,6 +900,46 @@ typedef struct ww_distill_stats {
 WW_API int ww_distill_loss_f32(const float* logits_dev, const float* teacher_logits_dev, const void* targets_dev, int target_kind, int64_t n,
                                const ww_loss_opts* opts_host, double alpha, double temperature, float* dlogits_dev, float* loss_dev,
                                ww_loss_stats* stats_dev, ww_distill_stats* distill_stats_dev, ww_stream_t stream);
+/* ww_hard_select_f32: online hard example mining -- rank the n rows of a candidate batch by the per-clip loss
+ * the step's criterion would compute and name the `keep` hardest.  One launch of one workgroup, no wait, no float atomics (integer LDS
+ * atomics fill histograms, whose result does not depend on order): the same bytes from run to run.
+ *   score    the row's loss in float64 BEFORE the mean's division: ww_ce_loss_f32's rule with integer labels and opts_host NULL,
+ *            ww_ce_loss_ex_f32's with integer labels and options (class weights, smoothing, ignore_index, focal; the reduction is not
+ *            read), ww_ce_loss_soft_f32's with WW_TARGET_PROBS (opts_host NULL: its defaults) -- the same device functions.
+ *   order    1. rank class, descending: 2 for a counting row of class keep_class (for probabilities the class is t1 > t0) with finite
+ *               logits and a finite score; 1 for any other counting row with finite logits and a finite score; 0 for the rest -- an
+ *               ignored or bad label, an invalid probability row, a non-finite logit or score
+ *            2. score, descending        3. row index, ascending
+ *   sel_dev [keep] int64: the first `keep` rows of that order, listed in RISING ROW INDEX (keep == n: 0 .. n - 1).
+ *   scores_dev [n] float64 (NULL allowed): the scores; -inf for a rank-0 row.
+ *   stats_dev (NULL allowed): one lane adds this call to the record, in stream order, as for ww_loss_stats.
+ *   workspace_dev: ww_hard_select_workspace_bytes(n) bytes, 256-byte aligned; nothing outside the n rows, the keep outputs and it is touched.
+ * logits_dev [n][2] float32 and probabilities [n][2] float32 need 4-byte alignment, labels [n] int64, sel, scores and stats 8-byte.
+ * Checked before any HIP call (WW_EINVAL naming the field): 1 <= keep <= n <= 65536, keep_class in {-1, 0, 1}, target_kind, the options as
+ * the loss entry points check them, null or misaligned pointers.
+ *
+ * ww_select_rows_f32: row sel_dev[j] -> row j, j < keep, of each tensor whose source and output are both given (a pair may be NULL, not
+ * all four): mel [n][80][width] float32, the targets of either kind, entries [n] and labels [n] int64.  One launch; 16-byte accesses where
+ * the row size and both mel pointers allow them, single floats otherwise -- the same bits.  An index outside [0, n) writes a row of zeros
+ * and reads nothing.  Out of place: an output that overlaps its source is WW_EINVAL, as are n outside 1..2^30, keep outside 1..n and
+ * null or misaligned pointers; width outside 1..32 is WW_EUNSUPPORTED. */
+typedef struct ww_select_stats {
+    int64_t batches;            /* calls */
+    int64_t candidates;         /* rows scored (sum of n) */
+    int64_t kept;               /* rows selected (sum of keep) */
+    int64_t candidate_positive; /* counting rows of class 1 among the candidates (whatever their rank) */
+    int64_t kept_positive;      /* ... among the selected */
+    int64_t unranked;           /* rank-0 rows among the candidates */
+    int64_t kept_unranked;      /* rank-0 rows that were selected: nothing else was left */
+    int64_t threshold_bits;     /* NOT a sum: the float64 bits of the smallest selected score of the newest call (-inf: a rank-0 row) */
+} ww_select_stats;              /* 64 bytes, DEVICE memory; zero it before an epoch */
+WW_API int64_t ww_hard_select_workspace_bytes(int64_t n);
+WW_API int ww_hard_select_f32(const float* logits_dev, const void* targets_dev, int target_kind, int64_t n, int64_t keep,
+                              const ww_loss_opts* opts_host, int32_t keep_class, int64_t* sel_dev, double* scores_dev,
+                              ww_select_stats* stats_dev, void* workspace_dev, ww_stream_t stream);
+WW_API int ww_select_rows_f32(const float* mel_dev, int64_t n, int32_t width, const int64_t* sel_dev, int64_t keep, float* mel_out,
+                              const void* targets_dev, int target_kind, void* targets_out, const int64_t* entries_dev, int64_t* entries_out,
+                              const int64_t* labels_dev, int64_t* labels_out, ww_stream_t stream);
 /* ww_mixup_f32: mixup on a log-mel batch, with the class-probability targets ww_ce_loss_soft_f32 takes.
  * Out of place (overlapping mel / out ranges: WW_EINVAL); one launch over B x chunks of a row; no atomics.  Per row i, with
  * p = partner_dev[i], lam = lambda_dev[i] and oml = 1.0f - lam (ONE float32 subtraction):

@@ -149,6 +149,15 @@ class DistillStats(C.Structure):
                 ("teacher_correct", C.c_int64), ("teacher_nonfinite", C.c_int64), ("batches", C.c_int64)]
 
 
+class SelectStats(C.Structure):
+    """struct ww_select_stats (include/wakeword_amd.h): what loss-ranked selection did over an epoch, device memory."""
+    _fields_ = [(k, C.c_int64) for k in ("batches", "candidates", "kept", "candidate_positive", "kept_positive", "unranked", "kept_unranked",
+                                         "threshold_bits")]
+
+
+SELECT_MAX_ROWS = 65536
+
+
 class AdamTensor(C.Structure):
     """struct ww_adam_tensor (include/wakeword_amd.h): one entry of the Adam / gradient-norm table, DEVICE pointers."""
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
@@ -302,6 +311,11 @@ PROTOTYPES = {
     "ww_ce_loss_soft_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(LossOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_distill_loss_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(LossOpts), C.c_double, C.c_double,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_hard_select_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "ww_hard_select_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.POINTER(LossOpts), C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_select_rows_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_mixup_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_adam_step_f32": (C.c_int, [C.POINTER(AdamTensor), C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
                                    C.c_void_p, C.c_void_p]),

@@ -1111,6 +1111,93 @@ def mixup(mel: torch.Tensor, labels: torch.Tensor, partner: torch.Tensor, lam: t
     return out, targets
 
 
+# ---- loss-ranked selection: train on the hardest k of a batch (csrc/ww_select.hip) -------------------------
+SELECT_STATS_FIELDS = ("batches", "candidates", "kept", "candidate_positive", "kept_positive", "unranked", "kept_unranked", "threshold_bits")
+SELECT_MAX_ROWS = nat.SELECT_MAX_ROWS
+
+
+def new_select_stats(device) -> torch.Tensor:
+    """A zeroed ww_select_stats record in device memory: eight int64 words; `.zero_()` starts a new epoch."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"selection stats on {device}: this path has no CPU implementation")
+    return torch.zeros(len(SELECT_STATS_FIELDS), device=device, dtype=torch.int64)
+
+
+def read_select_stats(stats: torch.Tensor) -> dict:
+    """The record on the host: the seven counters as int and `threshold`, the float64 the record's last word holds (the smallest
+    selected score of the newest call; -inf when a rank-0 row was selected; NaN before the first call).  One device-to-host copy (none
+    for a record that already is on the host)."""
+    host = stats.cpu()
+    out = {k: int(v) for k, v in zip(SELECT_STATS_FIELDS[:-1], host[:-1].tolist())}
+    out["threshold"] = float(host[-1:].view(torch.float64).item()) if out["batches"] else float("nan")
+    return out
+
+
+def hard_select_workspace_bytes(n: int) -> int:
+    return nat.check(nat.lib.ww_hard_select_workspace_bytes(int(n)))
+
+
+def _keep_class(keep_class) -> int:
+    if keep_class is None:
+        return -1
+    if isinstance(keep_class, bool) or not isinstance(keep_class, int) or keep_class not in (0, 1):
+        raise ValueError(f"keep_class {keep_class!r}: expected None, 0 or 1")
+    return keep_class
+
+
+def hard_select_into(logits, targets, keep, sel, scores, stats, workspace, *, opts=None, keep_class=None) -> None:
+    """ww_hard_select_f32 on caller-owned buffers: logits float32 [n, 2] contiguous, `targets` int64 labels [n] (unit stride) or float32
+    probabilities [n, 2]; `sel` int64 [>= keep] receives the kept rows in rising index, `scores` float64 [>= n] (or None) every row's
+    score, `stats` the record of ops.new_select_stats (or None); `workspace` uint8 of hard_select_workspace_bytes(n).  `opts`: the
+    criterion's options as ops.loss_opts / ops.soft_loss_opts made them (None: the plain rule).  One launch, no wait, no allocation."""
+    kind = nat.TARGET_PROBS if targets.dtype == torch.float32 else nat.TARGET_LABELS
+    with torch.cuda.device(logits.device):
+        nat.check(nat.lib.ww_hard_select_f32(_ptr(logits), _ptr(targets), kind, logits.shape[0], int(keep), None if opts is None else C.byref(opts),
+                                             _keep_class(keep_class), _ptr(sel), None if scores is None else _ptr(scores),
+                                             None if stats is None else _ptr(stats), _ptr(workspace), _stream()))
+
+
+def select_rows_into(x, sel, x_out, targets=None, targets_out=None, entries=None, entries_out=None, labels=None, labels_out=None) -> None:
+    """ww_select_rows_f32 on caller-owned buffers: row sel[j] of `x` (float32 [n, 1, 80, T] or [n, 80, T], T <= 32, contiguous), of
+    `targets` (int64 [n] or float32 [n, 2]), of `entries` and of `labels` (int64 [n]) -> row j of the matching output, j < len(sel).
+    Every pair but x's may be None.  One launch, no wait, no allocation; out of place."""
+    if not (x.is_contiguous() and x_out.is_contiguous() and sel.is_contiguous()) or tuple(x_out.shape) != (sel.shape[0],) + tuple(x.shape[1:]):
+        raise ValueError(f"select_rows_into: x, x_out and sel must be contiguous and x_out {(sel.shape[0],) + tuple(x.shape[1:])}, "
+                         f"got {tuple(x_out.shape)}")
+    kind = nat.TARGET_PROBS if targets is not None and targets.dtype == torch.float32 else nat.TARGET_LABELS
+    opt = lambda t: None if t is None else _ptr(t)           # noqa: E731
+    with torch.cuda.device(x.device):
+        nat.check(nat.lib.ww_select_rows_f32(_ptr(x), x.shape[0], int(x.shape[-1]), _ptr(sel), sel.shape[0], _ptr(x_out), opt(targets), kind,
+                                             opt(targets_out), opt(entries), opt(entries_out), opt(labels), opt(labels_out), _stream()))
+
+
+def hard_select(logits: torch.Tensor, targets: torch.Tensor, keep: int, *, opts=None, keep_class=None):
+    """The `keep` hardest rows of a batch: (sel int64 [keep] in rising row index, scores float64 [n]).  logits float32 [n, 2] and
+    `targets` -- int64 labels [n] or [n, 1], or float32 class probabilities [n, 2] -- on the GPU, n <= 65536.  A row's score is the
+    per-clip loss of the criterion `opts` describes (ops.loss_opts(...) for labels, ops.soft_loss_opts(...) for probabilities; None:
+    plain cross-entropy), before the mean's division; rows are ranked by (rank class desc, score desc, index asc) with rank class 2 for
+    counting rows of class `keep_class`, 1 for other counting rows with finite logits and score, 0 for the rest (score -inf).
+    Allocates its outputs and a workspace; ops.hard_select_into is the form that allocates nothing."""
+    _check_logits(logits)
+    if isinstance(targets, torch.Tensor) and targets.dtype == torch.float32:
+        _check_soft(logits, targets)
+    else:
+        targets = _check_ce(logits, targets)
+    n = logits.shape[0]
+    if isinstance(keep, bool) or not isinstance(keep, int) or not 1 <= keep <= n:
+        raise ValueError(f"keep {keep!r}: expected an integer in 1..{n}")
+    _keep_class(keep_class)
+    if n > SELECT_MAX_ROWS:
+        raise ValueError(f"hard_select: {n} rows; the selection kernel takes up to {SELECT_MAX_ROWS}")
+    sel = torch.empty(keep, device=logits.device, dtype=torch.int64)
+    scores = torch.empty(n, device=logits.device, dtype=torch.float64)
+    ws = torch.empty(hard_select_workspace_bytes(n), device=logits.device, dtype=torch.uint8)
+    hard_select_into(logits, targets, keep, sel, scores, None, ws, opts=opts, keep_class=keep_class)
+    ws.record_stream(torch.cuda.current_stream())
+    return sel, scores
+
+
 # ---- clip evaluation as device counters (INTEGRATION.md section 3j; csrc/ww_metrics.hip) ---------------------------------------------
 class ClipMetricsState:
     """A ww_clip_metrics record in device memory (`buffer`, int64 words) with the probability thresholds it was made for and their float32

@@ -32,6 +32,15 @@ at T = distill_temperature -- with integer labels, class probabilities or no tar
 `trainer.distill_stats` keeps the two terms apart on the device and `train_epoch` publishes them as `trainer.distill_report`.
 `validate` and the checkpoint do not change.  Without a teacher nothing here is reached.
 
+`select=` (mining.HardSelect, also assignable as an attribute) turns the step into online hard example mining:
+with k = select.rows(B) < B the step first scores all B rows -- the train kernels' forward with both dropout probabilities 0, on the raw
+parameters, so nothing is packed and nothing waits -- then ONE ww_hard_select_f32 launch ranks the rows by the criterion's own per-clip
+loss, ONE ww_select_rows_f32 launch gathers the k hardest (data, target, entries, labels) into persistent buffers, and the step as it
+always was runs on those k rows.  `train_stats`, the epoch's loss and accuracy and the ledger then speak of the KEPT rows only;
+`trainer.select_stats` is the device record of what was kept, `train_epoch` publishes it as `trainer.select_report`, and
+`trainer.last_selected` / `trainer.last_scores` are views of the newest step's choice.  Without `select`, or with k >= B, nothing here is
+reached.  `select` together with a teacher raises NotImplementedError.
+
 One deliberate difference: the reference calls `clip_grad_norm_` BEFORE `backward()`, where it clips the previous batch's gradients or
 nothing, so the default here is no clipping; `max_grad_norm=1.0` gives the clip the call meant, after the
 backward.
@@ -58,12 +67,13 @@ EVALUATE = ("model", "average")
 class WakewordTrainer:
     def __init__(self, model, device, config=TrainingConfig, *, checkpoint_path="best_wakeword_model.pth", max_grad_norm=None,
                  monitor="val_acc", thresholds=(0.8,), criterion=None, ledger=None, val_ledger=None, average=None, evaluate="model",
-                 teacher=None, distill_alpha=0.5, distill_temperature=2.0):
+                 teacher=None, distill_alpha=0.5, distill_temperature=2.0, select=None):
         if not isinstance(model, (SimpleWakewordModel, WakewordModel)):
             raise TypeError(f"WakewordTrainer drives the HIP training kernels of SimpleWakewordModel and WakewordModel; got {type(model).__name__}")
         from .loss import check_distillation
         self.distill_alpha, self.distill_temperature = check_distillation(distill_alpha, distill_temperature)
         self._check_teacher(teacher, model)
+        self._check_select(select, teacher)
         if any(p.device.type != "cuda" for p in model.parameters()):
             raise TypeError("WakewordTrainer: the model's parameters are on the CPU; this path has no CPU implementation (model.to('cuda'))")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
@@ -127,6 +137,12 @@ class WakewordTrainer:
         self.distill_stats = self.distill_report = None
         self._tlogits = self._tws = None
         self._last_teacher_logits = None
+        # ---- loss-ranked selection: the rule, the record of what it kept and the persistent buffers of the scoring pass and the gather ----
+        self._select = select
+        self.select_stats = self.select_report = None
+        self._slogits = self._sel = self._scores = self._sel_ws = None
+        self._gathered = {}
+        self._last_selected = self._last_scores = None
         if teacher is not None:
             if any(p.device != self._dev for p in teacher.parameters()):
                 raise RuntimeError(f"WakewordTrainer: the teacher must be on the student's device ({self._dev})")
@@ -134,6 +150,11 @@ class WakewordTrainer:
             self._epoch_stats = torch.zeros(len(ops.LOSS_STATS_FIELDS) + len(ops.DISTILL_STATS_FIELDS), device=self._dev, dtype=torch.int64)
             self.train_stats = self._epoch_stats[:len(ops.LOSS_STATS_FIELDS)]
             self.distill_stats = self._epoch_stats[len(ops.LOSS_STATS_FIELDS):]
+        else:
+            # the same arrangement for the selection's record (a rule may be assigned later; without one the second half stays zero)
+            self._epoch_stats = torch.zeros(len(ops.LOSS_STATS_FIELDS) + len(ops.SELECT_STATS_FIELDS), device=self._dev, dtype=torch.int64)
+            self.train_stats = self._epoch_stats[:len(ops.LOSS_STATS_FIELDS)]
+            self.select_stats = self._epoch_stats[len(ops.LOSS_STATS_FIELDS):]
         self._cap = 0                                                                  # clips the batch buffers hold
         self._logits = self._dlogits = None
         self._ws = None
@@ -183,6 +204,87 @@ class WakewordTrainer:
         own = {p.untyped_storage().data_ptr() for p in model.parameters()}
         if any(p.requires_grad and p.untyped_storage().data_ptr() in own for p in teacher.parameters()):
             raise ValueError("WakewordTrainer: a trainable parameter of the teacher shares its storage with the student's")
+
+    # ---- loss-ranked selection ----
+    @staticmethod
+    def _check_select(select, teacher) -> None:
+        """Refusals of a selection rule that need no device: its class, and a teacher beside it."""
+        if select is None:
+            return
+        from .mining import HardSelect
+        if not isinstance(select, HardSelect):
+            raise TypeError(f"WakewordTrainer: select must be a mining.HardSelect or None, got {type(select).__name__}")
+        if teacher is not None:
+            raise NotImplementedError("WakewordTrainer: select= together with teacher= is not supported (ranking rows by the distillation "
+                                      "loss is not implemented); drop one of the two")
+
+    @property
+    def select(self):
+        """The selection rule of `step` (mining.HardSelect) or None.  Assignable; a rule beside a teacher raises NotImplementedError."""
+        return self._select
+
+    @select.setter
+    def select(self, rule):
+        self._check_select(rule, self.teacher)
+        self._select = rule
+
+    @property
+    def last_selected(self):
+        """The rows the newest mined step kept: int64 [k] in rising row index, a view of the persistent buffer (None before one)."""
+        return self._last_selected
+
+    @property
+    def last_scores(self):
+        """The newest mined step's scores, float64 [B]: the per-clip loss of every candidate row at dropout 0, -inf for a rank-0 row."""
+        return self._last_scores
+
+    def _gather_buffer(self, name, shape, dtype):
+        buf = self._gathered.get(name)
+        if buf is None or tuple(buf.shape) != tuple(shape):
+            self._gathered[name] = None                      # release before replacing
+            buf = self._gathered[name] = torch.empty(shape, device=self._dev, dtype=dtype)
+        return buf
+
+    def _mine(self, x, y, soft, soft_opts, entries, ledger_y, B, k, math):
+        """The scoring forward on all B rows (dropout 0: no seed is drawn, the raw parameters are read), the selection and the gather:
+        returns the k kept rows of (x, y, entries, ledger_y) in persistent buffers.  Three native calls, no wait; no allocation after
+        the first batch of a size.  The caller has made x's device current and sized self._ws for B rows."""
+        if B > ops.SELECT_MAX_ROWS:
+            raise ValueError(f"WakewordTrainer.step: select= takes batches of up to {ops.SELECT_MAX_ROWS} rows, got {B}")
+        if self._slogits is None or self._slogits.shape[0] < B:
+            self._slogits = self._sel = self._scores = self._sel_ws = None
+            self._slogits = torch.empty((B, 2), device=self._dev, dtype=torch.float32)
+            self._sel = torch.empty(B, device=self._dev, dtype=torch.int64)
+            self._scores = torch.empty(B, device=self._dev, dtype=torch.float64)
+            self._sel_ws = torch.empty(ops.hard_select_workspace_bytes(B), device=self._dev, dtype=torch.uint8)
+        slogits = self._slogits if B == self._slogits.shape[0] else self._slogits[:B]
+        ops.train_forward_into(x, self._tp, 0.0, 0.0, 0, math, self._ws, slogits)
+        sel = self._sel[:k]
+        ops.hard_select_into(slogits, y, k, sel, self._scores, self.select_stats, self._sel_ws,
+                             opts=soft_opts if soft else self._loss_opts, keep_class=self._select.keep_class)
+        self._last_selected, self._last_scores = sel, self._scores[:B]
+        want_ledger = entries is not None and self.ledger is not None
+        if want_ledger and not isinstance(entries, torch.Tensor):
+            entries = self.ledger._upload(entries, B)        # host integers: the ledger's own pinned staging, no wait
+        gx = self._gather_buffer("x", (k,) + tuple(x.shape[1:]), torch.float32)
+        gy = self._gather_buffer("soft" if soft else "y", (k, 2) if soft else (k,), y.dtype)
+        ge = self._gather_buffer("entries", (k,), torch.int64) if want_ledger else None
+        gl = self._gather_buffer("labels", (k,), torch.int64) if want_ledger and soft else None
+        ops.select_rows_into(x, sel, gx, y, gy, entries if want_ledger else None, ge, ledger_y if gl is not None else None, gl)
+        return gx, gy, ge if want_ledger else entries, gl if gl is not None else gy
+
+    @staticmethod
+    def _select_report(s) -> dict:
+        """An epoch's ww_select_stats as what one reads off it: the fraction of the candidate rows that were trained on, the share of
+        positives (counting rows of class 1) among the candidates and among the kept, the rank-0 rows (ignored or bad targets, non-finite
+        logits) seen and kept, the smallest kept score of the newest mined step, and the counts behind them."""
+        nan = float("nan")
+        return {"kept_fraction": s["kept"] / s["candidates"] if s["candidates"] else nan,
+                "candidate_positive_fraction": s["candidate_positive"] / s["candidates"] if s["candidates"] else nan,
+                "kept_positive_fraction": s["kept_positive"] / s["kept"] if s["kept"] else nan,
+                "unranked": s["unranked"], "kept_unranked": s["kept_unranked"], "threshold": s["threshold"],
+                "candidates": s["candidates"], "kept": s["kept"], "candidate_positive": s["candidate_positive"],
+                "kept_positive": s["kept_positive"], "batches": s["batches"]}
 
     def _teacher_forward(self, x, B):
         """The teacher's eval-mode logits of `x` in the persistent buffer: ww_model_forward_f32 on a persistent workspace, on the current
@@ -294,7 +396,10 @@ class WakewordTrainer:
         With a teacher (`teacher_logits`: float32 [B, 2] on the device, precomputed -- an ensemble, a teacher at another precision --
         then take the teacher forward's place) the loss launch is ww_distill_loss_f32: (1 - distill_alpha) * criterion +
         distill_alpha * T^2 * KD on integer labels or class probabilities, and on `target=None` (unlabelled audio) T^2 * KD alone.
-        Integer labels then follow the rule of a criterion WITH options even under the default one: a label of -100 is ignored."""
+        Integer labels then follow the rule of a criterion WITH options even under the default one: a label of -100 is ignored.
+
+        With `self.select` set and k = select.rows(B) < B the batch is first scored without dropout, and everything above -- loss,
+        gradient, train_stats, last_logits, the ledger's rows -- is about the k rows `self.last_selected` names (section 3r)."""
         if not self.model.training:
             raise RuntimeError("WakewordTrainer.step: the model is in eval mode (train_epoch calls model.train())")
         if isinstance(data, torch.Tensor) and data.device != self._dev:
@@ -307,6 +412,9 @@ class WakewordTrainer:
         if B == 0:
             raise ValueError("empty training batch")
         distill = self.teacher is not None
+        k = B if self._select is None else self._select.rows(B)
+        if k < B and distill:
+            raise NotImplementedError("WakewordTrainer.step: select= together with a teacher is not supported")
         if not distill and (target is None or teacher_logits is not None):
             raise TypeError("WakewordTrainer.step: target=None (an unlabelled batch) and teacher_logits= need a teacher: "
                             "WakewordTrainer(..., teacher=)")
@@ -342,6 +450,9 @@ class WakewordTrainer:
                 self._logits = torch.empty((B, 2), device=self._dev, dtype=torch.float32)
                 self._dlogits = torch.empty((B, 2), device=self._dev, dtype=torch.float32)
                 self._cap = B
+            if k < B:
+                x, y, entries, ledger_y = self._mine(x, y, soft, soft_opts, entries, ledger_y, B, k, math)
+                B = k
             logits, m = self._logits if B == self._cap else self._logits[:B], self.model         # the buffers may hold more rows
             ops.train_forward_into(x, self._tp, m.lstm.dropout, m.dropout.p, seed, math, self._ws, logits)
             if distill:
@@ -394,6 +505,9 @@ class WakewordTrainer:
         self.train_stats.zero_()
         if self.teacher is not None:
             self.distill_stats.zero_()
+        mined = self._select is not None and self.select_stats is not None
+        if mined:
+            self.select_stats.zero_()
         if self.ledger is not None:
             self.ledger.begin_epoch()
         for data, target in train_loader:
@@ -401,7 +515,11 @@ class WakewordTrainer:
                 self.step(data, target)
             else:
                 self.step(data, target, self._entries_of(train_loader), getattr(train_loader, "last_labels", None))
-        if self.teacher is None:
+        if mined:
+            host = self._epoch_stats.cpu()                   # both records in the epoch's one device-to-host copy
+            result = self._finish_epoch(host[:len(ops.LOSS_STATS_FIELDS)], "train_epoch")
+            self.select_report = self._select_report(ops.read_select_stats(host[len(ops.LOSS_STATS_FIELDS):]))
+        elif self.teacher is None:
             result = self._finish_epoch(self.train_stats, "train_epoch")
         else:
             host = self._epoch_stats.cpu()                   # both records in the epoch's one device-to-host copy
