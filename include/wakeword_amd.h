@@ -1007,6 +1007,34 @@ WW_API int64_t ww_grad_norm_workspace_bytes(const ww_adam_tensor* tensors_host, 
 WW_API int ww_grad_norm_f32(const ww_adam_tensor* tensors_host, int64_t n_tensors, double max_norm, double* norm_dev, float* scale_dev,
                             void* workspace_dev, ww_stream_t stream);
 
+/* ---- post-training weight quantisation: symmetric int8 per group ------------------------------------------ */
+/* ww_quant_weights_f32: one launch over up to WW_QUANT_MAX_TENSORS tensors; the table is read on the HOST and travels in the kernel
+ * arguments.  Nothing waits, nothing is allocated, there are no atomics.  A tensor is rows x cols float32, contiguous, and a row is one
+ * quantisation group with one scale: an output channel of a conv weight (cols = Cin * 9), a gate row of an LSTM matrix, a row of
+ * fc.weight, or the whole tensor (rows = 1).  With qmax = 2^(bits - 1) - 1, every operation in float32 and rounded to nearest once:
+ *   amax  = max |w| over the row's finite elements (0 when it has none)
+ *   scale = max(amax / qmax, 2^-126)                   one division; the floor keeps the next one finite
+ *   q     = clamp(rint(w / scale), -qmax, qmax)        one division, ties to even; a non-finite w gives q = 0 and is counted in bad
+ *   deq   = (float)q * scale                           one multiplication; -0.0 and every non-finite w give +0.0
+ * err[row] = { sum of w^2, sum of (w - deq)^2, max |w - deq| } in float64 over the row's finite elements, in a fixed order: the same
+ * call writes the same bytes every time.  Rows of up to 1024 elements take a wave each, longer rows a workgroup each; no row is split
+ * across workgroups.  q, deq, err and bad may each be NULL.  w, scale, deq, bad: 4-byte aligned (longer rows use 16-byte accesses where
+ * a row starts on the 16-byte grid, with the same bits); err: 8-byte aligned.
+ * Checked before any HIP call (WW_EINVAL naming the field): n_tensors in 1..16, bits in 2..8, tensors_host, w and scale not NULL, rows
+ * and cols in 1..2^30 with rows x cols <= 2^40, the alignments, deq not overlapping w. */
+#define WW_QUANT_MAX_TENSORS 16
+typedef struct ww_quant_tensor {
+    const float* w;  /* [rows][cols], read only */
+    float* scale;    /* [rows] */
+    int8_t* q;       /* [rows][cols] or NULL */
+    float* deq;      /* [rows][cols] or NULL: the fake-quant weights */
+    double* err;     /* [rows][3] or NULL */
+    int32_t* bad;    /* [rows] or NULL: non-finite elements of the row */
+    int64_t rows;
+    int64_t cols;
+} ww_quant_tensor;   /* 64 bytes, DEVICE pointers */
+WW_API int ww_quant_weights_f32(const ww_quant_tensor* tensors_host, int64_t n_tensors, int bits, ww_stream_t stream);
+
 /* ---- clip evaluation: confusion, operating points and a margin histogram as device counters ---------- */
 /* What notebook cell 17 collects clip by clip on the host (`all_preds.extend(predicted.cpu().numpy())`) kept as integer counters in
  * device memory: one launch per batch adds the batch to the record in stream order, nothing waits for the device, and the record is read

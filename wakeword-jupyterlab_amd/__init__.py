@@ -16,7 +16,7 @@ def __getattr__(name):
     # lazy: `import wakeword_jupyterlab_amd` must work on a box where only host utilities are needed
     import importlib
     if name in ("ops", "model", "audio", "dataset", "streaming", "inference", "distributed", "_native", "background", "reverb",
-                "scan", "bank", "audit", "optim", "trainer", "metrics", "loss", "sampling", "ledger", "average", "mining"):
+                "scan", "bank", "audit", "optim", "trainer", "metrics", "loss", "sampling", "ledger", "average", "mining", "quant"):
         return importlib.import_module(f"{__name__}.{name}")
     lazy = {"AudioProcessor": "audio", "WakewordDataset": "dataset", "DataLoader": "dataset", "SimpleWakewordModel": "model",
             "WakewordModel": "model", "StreamingDetector": "streaming", "predict_wakeword": "inference",
@@ -25,7 +25,8 @@ def __getattr__(name):
             "ImpulseResponseBank": "reverb", "scan_files": "scan", "det_curve": "scan", "Scan": "scan", "TrainingConfig": "config", "FusedAdam": "optim",
             "WakewordTrainer": "trainer", "ClipReport": "metrics", "evaluate_report": "inference", "evaluate_report_pcm": "inference",
             "FocalLoss": "loss", "DistillationLoss": "loss", "balanced_class_weights": "loss", "balanced_order": "sampling", "BankAudit": "audit", "ClipLedger": "ledger", "LedgerReport": "ledger", "WeightAverage": "average",
-            "HardSelect": "mining"}
+            "HardSelect": "mining", "WeightQuant": "quant", "QuantReport": "quant", "save_quantized_package": "quant",
+            "load_quantized_package": "quant"}
     if name in lazy:
         return getattr(importlib.import_module(f"{__name__}.{lazy[name]}"), name)
     raise AttributeError(name)

@@ -164,6 +164,15 @@ class AdamTensor(C.Structure):
 
 
 ADAM_MAX_TENSORS = 16
+
+
+class QuantTensor(C.Structure):
+    """struct ww_quant_tensor (include/wakeword_amd.h): one entry of the weight-quantisation table, DEVICE pointers."""
+    _fields_ = [("w", C.c_void_p), ("scale", C.c_void_p), ("q", C.c_void_p), ("deq", C.c_void_p), ("err", C.c_void_p), ("bad", C.c_void_p),
+                ("rows", C.c_int64), ("cols", C.c_int64)]
+
+
+QUANT_MAX_TENSORS = 16
 METRICS_MAX_THRESHOLDS, METRICS_BINS = 8, 4096
 
 
@@ -324,6 +333,7 @@ PROTOTYPES = {
     "ww_weight_average_f32": (C.c_int, [C.POINTER(AdamTensor), C.POINTER(C.c_void_p), C.c_int64, C.c_double, C.c_void_p]),
     "ww_grad_norm_workspace_bytes": (C.c_int64, [C.POINTER(AdamTensor), C.c_int64]),
     "ww_grad_norm_f32": (C.c_int, [C.POINTER(AdamTensor), C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ww_quant_weights_f32": (C.c_int, [C.POINTER(QuantTensor), C.c_int64, C.c_int, C.c_void_p]),
     "ww_clip_metrics_bytes": (C.c_int64, []),
     "ww_clip_metrics_margin_host": (C.c_float, [C.c_float]),
     "ww_clip_metrics_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -1482,6 +1482,108 @@ def grad_norm(grads, max_norm: float):
     return norm, scale
 
 
+# ---- post-training weight quantisation (csrc/ww_quant.hip) -------------------------------------------------
+def check_quant_bits(bits) -> int:
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 2 <= bits <= 8:
+        raise ValueError(f"bits {bits!r}: expected an integer in 2..8")
+    return bits
+
+
+def quant_groups(t: torch.Tensor, per_channel: bool = True):
+    """(rows, cols) of a weight tensor as ww_quant_weights_f32 groups it: one group per slice of the first dimension (an output channel, a
+    gate row, a row of fc.weight), or the whole tensor as one group in per-tensor mode and for anything with fewer than two dimensions."""
+    if per_channel and t.dim() >= 2:
+        return int(t.shape[0]), t.numel() // max(1, int(t.shape[0]))
+    return 1, t.numel()
+
+
+def _quant_mode_list(per_channel, n):
+    modes = [bool(per_channel)] * n if isinstance(per_channel, (bool, int)) else [bool(m) for m in per_channel]
+    if len(modes) != n:
+        raise ValueError(f"per_channel: {len(modes)} entries for {n} tensors")
+    return modes
+
+
+def quant_table(weights, scales, qs=None, deqs=None, errs=None, bads=None, per_channel=True):
+    """Up to 16 float32 GPU weight tensors and their outputs -> a ctypes array of _native.QuantTensor.  Per tensor of rows x cols
+    (quant_groups; `per_channel` a bool or one per tensor): scale float32 [rows]; q int8, deq float32 of the weight's size; err float64
+    [rows, 3]; bad int32 [rows].  Each of qs, deqs, errs, bads may be None, and so may single entries of them."""
+    weights = list(weights)
+    n = len(weights)
+    if not 1 <= n <= nat.QUANT_MAX_TENSORS:
+        raise ValueError(f"{n} tensors: one launch takes 1..{nat.QUANT_MAX_TENSORS}")
+    modes = _quant_mode_list(per_channel, n)
+    cols_of = [[None] * n if c is None else list(c) for c in (scales, qs, deqs, errs, bads)]
+    if any(len(c) != n for c in cols_of):
+        raise ValueError("weights, scales, qs, deqs, errs and bads differ in length")
+    tab = (nat.QuantTensor * n)()
+    for k, w in enumerate(weights):
+        _require_cuda_f32(w, f"weight {k}")
+        if not w.is_contiguous():
+            raise RuntimeError(f"weight {k} is not contiguous")
+        if w.numel() == 0:
+            raise ValueError(f"weight {k} is empty")
+        rows, cols = quant_groups(w, modes[k])
+        scale, q, deq, err, bad = (c[k] for c in cols_of)
+        if scale is None:
+            raise TypeError(f"scale {k}: expected a float32 tensor [{rows}]")
+        for name, t, dtype, numel in (("scale", scale, torch.float32, rows), ("q", q, torch.int8, w.numel()), ("deq", deq, torch.float32, w.numel()),
+                                      ("err", err, torch.float64, 3 * rows), ("bad", bad, torch.int32, rows)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+                raise TypeError(f"{name} {k}: expected a {dtype} torch.Tensor")
+            if t.device != w.device:
+                raise RuntimeError(f"{name} {k} on {t.device}, its weight on {w.device}")
+            if t.numel() != numel or not t.is_contiguous():
+                raise ValueError(f"{name} {k}: expected {numel} contiguous elements, got {tuple(t.shape)}")
+        e = tab[k]
+        e.w, e.scale, e.rows, e.cols = w.data_ptr(), scale.data_ptr(), rows, cols
+        e.q, e.deq, e.err, e.bad = (None if t is None else t.data_ptr() for t in (q, deq, err, bad))
+    return tab
+
+
+def quantize_weights_launch(table, device, bits) -> None:
+    """ww_quant_weights_f32 on a prepared quant_table (quant.WeightQuant keeps its tables between updates).  Allocates nothing."""
+    with torch.cuda.device(device):
+        nat.check(nat.lib.ww_quant_weights_f32(table, len(table), int(bits), _stream()))
+
+
+def quantize_weights_into(weights, scales, qs=None, deqs=None, errs=None, bads=None, *, bits=8, per_channel=True) -> None:
+    """Quantise `weights` into caller-owned outputs (quant_table has the shapes), one launch per 16 tensors, in stream order; nothing
+    waits for the device.  The outputs are written behind autograd's back: version counters do not move (quant.WeightQuant bumps them)."""
+    bits = check_quant_bits(bits)
+    weights = list(weights)
+    modes = _quant_mode_list(per_channel, len(weights))
+    outs = [[None] * len(weights) if c is None else list(c) for c in (scales, qs, deqs, errs, bads)]
+    if any(len(c) != len(weights) for c in outs):
+        raise ValueError("weights, scales, qs, deqs, errs and bads differ in length")
+    step = nat.QUANT_MAX_TENSORS
+    tables = [quant_table(weights[i:i + step], *(c[i:i + step] for c in outs), per_channel=modes[i:i + step]) for i in range(0, len(weights), step)]
+    for i, tab in enumerate(tables):                         # every table was checked before the first launch
+        quantize_weights_launch(tab, weights[i * step].device, bits)
+
+
+def quantize_weights(tensors, bits=8, per_channel=True):
+    """[(q int8, scale float32 [rows], deq float32, err float64 [rows, 3], bad int32 [rows])] for a list of float32 GPU weight tensors:
+    symmetric `bits`-bit quantisation per output channel / row (per_channel=True) or per tensor, by the rule of include/wakeword_amd.h
+    (ww_quant_weights_f32).  q and deq have the weight's shape; err rows are (sum w^2, sum (w - deq)^2, max |w - deq|)."""
+    bits = check_quant_bits(bits)
+    tensors = list(tensors)
+    modes = _quant_mode_list(per_channel, len(tensors))
+    for k, w in enumerate(tensors):
+        _require_cuda_f32(w, f"weight {k}")
+    out = []
+    for w, m in zip(tensors, modes):
+        rows, _ = quant_groups(w, m)
+        out.append((torch.empty(w.shape, device=w.device, dtype=torch.int8), torch.empty(rows, device=w.device, dtype=torch.float32),
+                    torch.empty(w.shape, device=w.device, dtype=torch.float32), torch.empty((rows, 3), device=w.device, dtype=torch.float64),
+                    torch.empty(rows, device=w.device, dtype=torch.int32)))
+    if tensors:
+        quantize_weights_into(tensors, *([o[j] for o in out] for j in (1, 0, 2, 3, 4)), bits=bits, per_channel=modes)
+    return out
+
+
 # ---- SpecAugment: time and frequency masks on log-mel batches (INTEGRATION.md section 3i; csrc/ww_specaug.hip) ----------------------
 def _spec_args(config, T: int):
     """(prob, n_freq, freq_max, n_time, time_max, fill_mode, fill_value) as ww_spec_augment_f32 takes them, for images of T frames."""

@@ -25,6 +25,11 @@ average is written by the Adam launch itself (ww_adam_avg_step_f32 in ww_adam_st
 calls), an every="epoch" one is updated once after `train_epoch`.  `evaluate="average"` makes `validate`, `val_report`, the monitor, the
 scheduler, early stopping and the best checkpoint follow `average.model`; the checkpoint gains "average_state_dict" when an average is set.
 
+`quant=` (quant.WeightQuant around the model or around `average.model`) with `evaluate="quant"`: `validate`
+re-quantises (one launch, no wait) and then it, `val_report`, the monitor, the scheduler, early stopping and the best checkpoint follow
+`quant.model`, the fake-quant model -- the kept checkpoint is the one that survives quantisation.  The checkpoint gains "quant_state_dict"
+when a quantiser is set.  Without one nothing here is reached.
+
 `teacher=` (an eval-mode SimpleWakewordModel or WakewordModel on the same device, of either class; `average.model` gives the mean
 teacher) turns the step into knowledge distillation: the teacher's eval forward on the same batch into a
 persistent buffer, then ONE ww_distill_loss_f32 launch in the loss's place -- (1 - distill_alpha) * criterion + distill_alpha * T^2 * KD
@@ -61,19 +66,25 @@ from .optim import FusedAdam
 
 MONITORS = ("val_acc", "val_f1", "val_auc")
 MONITOR_NAMES = {"val_acc": "Acc", "val_f1": "F1", "val_auc": "AUC"}
-EVALUATE = ("model", "average")
+EVALUATE = ("model", "average", "quant")
 
 
 class WakewordTrainer:
     def __init__(self, model, device, config=TrainingConfig, *, checkpoint_path="best_wakeword_model.pth", max_grad_norm=None,
                  monitor="val_acc", thresholds=(0.8,), criterion=None, ledger=None, val_ledger=None, average=None, evaluate="model",
-                 teacher=None, distill_alpha=0.5, distill_temperature=2.0, select=None):
+                 teacher=None, distill_alpha=0.5, distill_temperature=2.0, select=None, quant=None):
         if not isinstance(model, (SimpleWakewordModel, WakewordModel)):
             raise TypeError(f"WakewordTrainer drives the HIP training kernels of SimpleWakewordModel and WakewordModel; got {type(model).__name__}")
         from .loss import check_distillation
         self.distill_alpha, self.distill_temperature = check_distillation(distill_alpha, distill_temperature)
         self._check_teacher(teacher, model)
         self._check_select(select, teacher)
+        if evaluate == "quant" and quant is None:
+            raise ValueError("evaluate='quant' needs a quantiser: WakewordTrainer(..., quant=WeightQuant(model))")
+        if quant is not None:
+            from .quant import WeightQuant
+            if not isinstance(quant, WeightQuant):
+                raise TypeError(f"WakewordTrainer: quant must be a quant.WeightQuant or None, got {type(quant).__name__}")
         if any(p.device.type != "cuda" for p in model.parameters()):
             raise TypeError("WakewordTrainer: the model's parameters are on the CPU; this path has no CPU implementation (model.to('cuda'))")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
@@ -89,6 +100,7 @@ class WakewordTrainer:
         self.monitor = monitor
         self.evaluate = evaluate
         self.average = average                                         # average.WeightAverage or None
+        self.quant = quant                                             # quant.WeightQuant or None
         self.model = model
         self.device = device
         self.config = config
@@ -531,7 +543,11 @@ class WakewordTrainer:
 
     def validate(self, val_loader):
         self.model.eval()
-        model = self.average.model.eval() if self.evaluate == "average" else self.model
+        if self.evaluate == "quant":
+            self.quant.update()                              # from its source's current weights: one launch, no wait
+            model = self.quant.model.eval()
+        else:
+            model = self.average.model.eval() if self.evaluate == "average" else self.model
         self.val_stats.zero_()
         ops.reset_clip_metrics(self.val_metrics)
         self._val_report = None
@@ -607,6 +623,10 @@ class WakewordTrainer:
                         "val_acc": val_acc, "train_acc": train_acc, "train_loss": train_loss, "val_loss": val_loss}
                 if self.average is not None:
                     ckpt["average_state_dict"] = self.average.state_dict()
+                if self.quant is not None:
+                    if self.evaluate != "quant":
+                        self.quant.update()                  # validate did not: the saved integers belong to the saved weights
+                    ckpt["quant_state_dict"] = self.quant.state_dict()
                 torch.save(ckpt, self.checkpoint_path)
                 print(f"New best model saved! Validation accuracy: {val_acc:.2f}%")
             else:
