@@ -255,9 +255,8 @@ static int streamer_enqueue(ww_streamer* s, const void* hop_dev, float* prob_dev
     } else {
         const int threads = 256;
         const int blocks = (s->n_mics * s->hop + threads - 1) / threads;
-        hipLaunchKernelGGL(ring_append_kernel, dim3(blocks), dim3(threads), 0, s->stream, s->ring, s->pos,
-                           reinterpret_cast<uint32_t*>(s->pos + 1), static_cast<const float*>(hop_dev), s->n_mics, s->hop, s->n_samples);
-        WW_HIP(hipGetLastError());
+        if (int rc = launch<ring_append_kernel>(dim3(blocks), dim3(threads), 0, s->stream, s->ring, s->pos, reinterpret_cast<uint32_t*>(s->pos + 1),
+                                                static_cast<const float*>(hop_dev), s->n_mics, s->hop, s->n_samples)) return rc;
     }
     // N = 16000 (T = 32) is launch_logmel's 1 s ring kernel with the same arguments as ever; other N the 64-frame tile in ring form
     const int N = s->n_samples;
@@ -1100,9 +1099,7 @@ int ww_streamer_latency(const ww_streamer* s) {
 
 int ww_streamer_window(ww_streamer* s, float* window_dev) {
     if (!s || !window_dev) return fail(WW_EINVAL, "null argument");
-    hipLaunchKernelGGL(ring_unroll_kernel, dim3(1024), dim3(256), 0, s->stream, s->ring, s->pos, window_dev, s->n_mics, s->n_samples);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<ring_unroll_kernel>(dim3(1024), dim3(256), 0, s->stream, s->ring, s->pos, window_dev, s->n_mics, s->n_samples);
 }
 
 int ww_streamer_destroy(ww_streamer* s) {

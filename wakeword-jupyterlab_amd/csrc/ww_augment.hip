@@ -752,34 +752,21 @@ static int launch_records(const AugCall& c, const AugDev* plan, const BgDev* bg,
     float* bufB = reinterpret_cast<float*>(w + lay.buf_b);
     float2* S = reinterpret_cast<float2*>(w + lay.spec);
     float* Y = reinterpret_cast<float*>(w + lay.y);
-    {
-        static std::mutex mu;
-        static bool attr[64] = {};
-        std::lock_guard<std::mutex> lock(mu);
-        int dev = 0;
-        WW_HIP(hipGetDevice(&dev));
-        if (dev >= 0 && dev < 64 && !attr[dev]) {
-            WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(istft_kernel<kN>), hipFuncAttributeMaxDynamicSharedMemorySize, kIstftLds));
-            WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stft_pv_kernel<kN>), hipFuncAttributeMaxDynamicSharedMemorySize, kStftPvLds));
-            WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(resample_kernel<kN>), hipFuncAttributeMaxDynamicSharedMemorySize, kResampleLds));
-            attr[dev] = true;
-        }
-    }
     const int nn = int(c.n_samples);
     const dim3 egrid(unsigned((row / 4 + 255) / 256), unsigned(n));
-    hipLaunchKernelGGL(roll_kernel<kN>, egrid, dim3(256), 0, stream, c.pcm, c.stride, plan, bufA, nn);
+    if (int rc = launch<roll_kernel<kN>>(egrid, dim3(256), 0, stream, c.pcm, c.stride, plan, bufA, nn)) return rc;
     float* cur = bufA;
     float* other = bufB;
     if (any_pitch) {
-        hipLaunchKernelGGL(stft_pv_kernel<kN>, dim3(unsigned(n)), dim3(256), kStftPvLds, stream, cur, plan, 0, tb, S, nn);
-        hipLaunchKernelGGL(istft_kernel<kN>, dim3(unsigned(n)), dim3(256), kIstftLds, stream, S, plan, 0, tb,
-                           static_cast<const float*>(nullptr), Y, int64_t(kAugYStride), nn);
-        hipLaunchKernelGGL(resample_kernel<kN>, dim3(unsigned(n)), dim3(1024), kResampleLds, stream, Y, plan, tb, cur, other, nn);
+        if (int rc = launch<stft_pv_kernel<kN>>(dim3(unsigned(n)), dim3(256), kStftPvLds, stream, cur, plan, 0, tb, S, nn)) return rc;
+        if (int rc = launch<istft_kernel<kN>>(dim3(unsigned(n)), dim3(256), kIstftLds, stream, S, plan, 0, tb, nullptr, Y, int64_t(kAugYStride), nn))
+            return rc;
+        if (int rc = launch<resample_kernel<kN>>(dim3(unsigned(n)), dim3(1024), kResampleLds, stream, Y, plan, tb, cur, other, nn)) return rc;
         float* t = cur; cur = other; other = t;
     }
     if (any_stretch) {
-        hipLaunchKernelGGL(stft_pv_kernel<kN>, dim3(unsigned(n)), dim3(256), kStftPvLds, stream, cur, plan, 1, tb, S, nn);
-        hipLaunchKernelGGL(istft_kernel<kN>, dim3(unsigned(n)), dim3(256), kIstftLds, stream, S, plan, 1, tb, cur, other, row, nn);
+        if (int rc = launch<stft_pv_kernel<kN>>(dim3(unsigned(n)), dim3(256), kStftPvLds, stream, cur, plan, 1, tb, S, nn)) return rc;
+        if (int rc = launch<istft_kernel<kN>>(dim3(unsigned(n)), dim3(256), kIstftLds, stream, S, plan, 1, tb, cur, other, row, nn)) return rc;
         float* t = cur; cur = other; other = t;
     }
     if (rir) {
@@ -788,12 +775,9 @@ static int launch_records(const AugCall& c, const AugDev* plan, const BgDev* bg,
         float* t = cur; cur = other; other = t;
     }
     if (bg)
-        hipLaunchKernelGGL((mix_kernel<kN, 16, true>), dim3(unsigned(n)), dim3(kMixThreads), 0, stream, cur, row, plan, bg, c.bank, c.bank_len,
-                           c.out, c.out_stride, nn);
-    else
-        hipLaunchKernelGGL(noise_kernel<kN>, egrid, dim3(256), 0, stream, cur, plan, c.out, c.out_stride, nn);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+        return launch<mix_kernel<kN, 16, true>>(dim3(unsigned(n)), dim3(kMixThreads), 0, stream, cur, row, plan, bg, c.bank, c.bank_len, c.out,
+                                                c.out_stride, nn);
+    return launch<noise_kernel<kN>>(egrid, dim3(256), 0, stream, cur, plan, c.out, c.out_stride, nn);
 }
 
 // 16000 samples run the compile-time 1 s instance (the kernels the 1 s entry points always ran), every other length the run-time one.
@@ -885,16 +869,11 @@ int launch_mix_background(const AugCall& c, const void* records_host) {
     const AugDev* no_plan = nullptr;
     const dim3 grid = dim3(unsigned(c.n)), block = dim3(kMixThreads);
     if (c.n_samples == kClip)
-        hipLaunchKernelGGL((mix_kernel<kClip, 16, false>), grid, block, 0, c.stream, c.pcm, c.stride, no_plan, bg, c.bank, c.bank_len, c.out,
-                           c.out_stride, nn);
-    else if (c.n_samples <= 16 * kMixThreads)
-        hipLaunchKernelGGL((mix_kernel<0, 16, false>), grid, block, 0, c.stream, c.pcm, c.stride, no_plan, bg, c.bank, c.bank_len, c.out,
-                           c.out_stride, nn);
-    else
-        hipLaunchKernelGGL((mix_kernel<0, 32, false>), grid, block, 0, c.stream, c.pcm, c.stride, no_plan, bg, c.bank, c.bank_len, c.out,
-                           c.out_stride, nn);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+        return launch<mix_kernel<kClip, 16, false>>(grid, block, 0, c.stream, c.pcm, c.stride, no_plan, bg, c.bank, c.bank_len, c.out, c.out_stride,
+                                                    nn);
+    if (c.n_samples <= 16 * kMixThreads)
+        return launch<mix_kernel<0, 16, false>>(grid, block, 0, c.stream, c.pcm, c.stride, no_plan, bg, c.bank, c.bank_len, c.out, c.out_stride, nn);
+    return launch<mix_kernel<0, 32, false>>(grid, block, 0, c.stream, c.pcm, c.stride, no_plan, bg, c.bank, c.bank_len, c.out, c.out_stride, nn);
 }
 
 }  // namespace ww

@@ -152,10 +152,8 @@ int launch_bank_peaks(const float* audio, int64_t total, const int64_t* offsets,
     const int64_t cap = int64_t(device_cu_count()) * 8;                       // memory-bound: a capped grid, contiguous chunks per workgroup
     const int64_t per = (n_chunks + cap - 1) / cap;
     const int64_t grid = (n_chunks + per - 1) / per;
-    hipLaunchKernelGGL(bank_peaks_kernel, dim3(unsigned(grid)), dim3(kPeakThreads), 0, stream, audio, total, offsets, n,
-                       reinterpret_cast<uint32_t*>(peaks), per);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<bank_peaks_kernel>(dim3(unsigned(grid)), dim3(kPeakThreads), 0, stream, audio, total, offsets, n,
+                                     reinterpret_cast<uint32_t*>(peaks), per);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -263,11 +261,8 @@ int launch_bank_gather(const float* audio, const ww_bank_item* items_host, int64
     const int64_t cap = int64_t(device_cu_count()) * 8;
     const dim3 grid(unsigned(n < cap ? n : cap)), block(kGatherThreads);
     if (N <= 4 * kGatherThreads * 16)
-        hipLaunchKernelGGL(bank_gather_kernel<16>, grid, block, 0, stream, audio, items, int(n), N, out, out_stride);
-    else
-        hipLaunchKernelGGL(bank_gather_kernel<32>, grid, block, 0, stream, audio, items, int(n), N, out, out_stride);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+        return launch<bank_gather_kernel<16>>(grid, block, 0, stream, audio, items, int(n), N, out, out_stride);
+    return launch<bank_gather_kernel<32>>(grid, block, 0, stream, audio, items, int(n), N, out, out_stride);
 }
 
 }  // namespace ww

@@ -294,15 +294,12 @@ int launch_bank_audit(const float* audio, int64_t total, const int64_t* offsets,
         int64_t per = (n_hops + cap - 1) / cap;
         per = (per + kAuditWaves - 1) / kAuditWaves * kAuditWaves;
         const int64_t grid = (n_hops + per - 1) / per;
-        hipLaunchKernelGGL(bank_hops_kernel, dim3(unsigned(grid)), dim3(kAuditThreads), 0, stream, audio, total, offsets, hop_prefix, n, clip_level,
-                           recs, per);
-        WW_HIP(hipGetLastError());
+        if (int rc = launch<bank_hops_kernel>(dim3(unsigned(grid)), dim3(kAuditThreads), 0, stream, audio, total, offsets, hop_prefix, n, clip_level,
+                                              recs, per)) return rc;
     }
     const int64_t groups = (int64_t(n) + kAuditWaves - 1) / kAuditWaves, ecap = cap / 2;     // the fold is light: waves stride over the entries
-    hipLaunchKernelGGL(bank_entry_kernel, dim3(unsigned(groups < ecap ? groups : ecap)), dim3(kAuditThreads), 0, stream, offsets, total, hop_prefix,
-                       n, recs, ratio, stats);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<bank_entry_kernel>(dim3(unsigned(groups < ecap ? groups : ecap)), dim3(kAuditThreads), 0, stream, offsets, total, hop_prefix, n,
+                                     recs, ratio, stats);
 }
 
 }  // namespace ww

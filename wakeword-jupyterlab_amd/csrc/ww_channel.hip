@@ -253,9 +253,7 @@ __global__ __launch_bounds__(kChanThreads) void channel_kernel(const float* in, 
 
 int launch_channel_draw(const ww_channel_config& g, uint64_t seed, int64_t n, float* records, hipStream_t stream) {
     const int64_t grid = (n * 16 + kChanThreads - 1) / kChanThreads;
-    hipLaunchKernelGGL(channel_draw_kernel, dim3(unsigned(grid)), dim3(kChanThreads), 0, stream, records, n, seed, g);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<channel_draw_kernel>(dim3(unsigned(grid)), dim3(kChanThreads), 0, stream, records, n, seed, g);
 }
 
 int launch_channel(const float* in, float* out, int64_t n, int n_samples, int64_t row_stride, const float* records, uint64_t seed,
@@ -263,10 +261,7 @@ int launch_channel(const float* in, float* out, int64_t n, int n_samples, int64_
     const int L = (n_samples + kChanThreads - 1) / kChanThreads;
     if (L < 2 || L > kChanMaxChunk) return fail(WW_EUNSUPPORTED, "n_samples %d: chunks of 2..%d samples", n_samples, kChanMaxChunk);
     const uint32_t l_recip = uint32_t((uint64_t(1) << 32) / uint64_t(L)) + 1u;
-    hipLaunchKernelGGL(channel_kernel, dim3(unsigned(n)), dim3(kChanThreads), 0, stream, in, out, n_samples, L, l_recip, row_stride, records, seed,
-                       g);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<channel_kernel>(dim3(unsigned(n)), dim3(kChanThreads), 0, stream, in, out, n_samples, L, l_recip, row_stride, records, seed, g);
 }
 
 }  // namespace ww

@@ -24,7 +24,6 @@
 // Diagnostic build: -DWW_STAMPS adds s_memtime phase stamps (never in the shipped library).
 #include <cstdlib>
 #include <type_traits>
-#include <mutex>
 
 #include "ww_conv1.h"
 #include "ww_internal.h"
@@ -787,6 +786,7 @@ static_assert(kWTileRows % 4 == 0, "four producers with equal shares");
 // bits[n][40 tile rows][4 N-tiles][2 column halves][2 rows][4 j] x 64 bits (ww_train_h.hip: mask2_byte), and bits1[n][80][32] = 32 bits per position, bit c = [relu(conv1)[c] > 0]
 // (2 x uint16, one per producer half-wave): all the backward pass needs of the activations (ww_train_h.hip).
 // OUT 3 (training forward of the 3-conv model): relu(conv2) and apow2 as under OUT 0, plus bits1.
+constexpr int kOutMid = 0, kOutPool = 1, kOutPoolBits = 2, kOutMidBits1 = 3;      // the values of OUT, by name
 template <int OUT, bool TILED = false>
 __global__ __launch_bounds__(768, 3) void cnn2w_kernel(const float* __restrict__ mel, int n, int width,
                                                        const u32x4* __restrict__ w1H, const float* __restrict__ hs1,
@@ -796,7 +796,7 @@ __global__ __launch_bounds__(768, 3) void cnn2w_kernel(const float* __restrict__
                                                        float* __restrict__ out, float* __restrict__ apow2, uint16_t* __restrict__ bits,
                                                        uint16_t* __restrict__ bits1, ColTiling tl) {
     static_assert(!TILED || OUT <= 1, "column tiling is an inference form");
-    constexpr bool POOL = OUT == 1 || OUT == 2, BITS = OUT == 2, BITS1 = OUT == 2 || OUT == 3;
+    constexpr bool POOL = OUT == kOutPool || OUT == kOutPoolBits, BITS = OUT == kOutPoolBits, BITS1 = OUT == kOutPoolBits || OUT == kOutMidBits1;
     extern __shared__ __attribute__((aligned(16))) char ldsb[];
     char* act0 = ldsb;
     _Float16* melh0 = reinterpret_cast<_Float16*>(ldsb + kWNB * kWBuf);      // 2 clips x (hi plane, lo plane) of [82][36] f16
@@ -1504,95 +1504,60 @@ int64_t cnn_scratch_bytes(int64_t n, int n_conv) {
     return n_conv == 3 ? mid_bytes(n) + ((n * int64_t(sizeof(float)) + 255) & ~int64_t(255)) : 0;
 }
 
-// > 64 KiB of dynamic LDS needs an opt-in per kernel, once per device
-static int opt_in_lds() {
-    static std::mutex mu;
-    static bool done[64] = {};
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    WW_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(WW_EINVAL, "device ordinal out of range");
-    if (done[dev]) return WW_OK;
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn2h16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kC2h16Lds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn2h16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kC2h16Lds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn2w_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kCWLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn2w_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kCWLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn2w_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, kCWLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn3w_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kC3wLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn3w_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kC3wLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn2w_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, kCWLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn3h_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kC3hLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               int(sizeof(float) * kC3LdsFloats)));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               int(sizeof(float) * kC3LdsFloats)));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn2w_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kCWLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn2w_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kCWLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn3w_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kC3wLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cnn3_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               int(sizeof(float) * kC3LdsFloats)));
-    done[dev] = true;
-    return WW_OK;
+// ------------------------------------------------------------------------------------------------
+// Host path.  Each conv kernel is launched from exactly one function, templated like the kernel: it takes what varies between its callers
+// (the clips, the outputs, the column tiling) and builds the rest of the argument list from the packed image; the two exact-f32 kernels
+// take their weights as pointers, because the training forward runs them on the live parameters.  Every grid is persistent.
+// ------------------------------------------------------------------------------------------------
+static dim3 persistent_grid(int64_t n, int per_cu) {
+    const int64_t resident = int64_t(device_cu_count()) * per_cu;
+    return dim3(unsigned(n < resident ? n : resident));
 }
 
-// training forward of the 2-conv model in split precision (ww_train.hip): the inference kernel with the ReLU mask as a second output.
-// `packed`: a packed image whose conv1 / conv2-Winograd / range entries were written on the device from the live parameters.
-int launch_cnn2w_pool_bits(const float* mel, int64_t n, int width, const float* packed, float* pooled, uint32_t* bits, uint32_t* bits1,
-                           hipStream_t stream) {
-    if (n == 0) return WW_OK;
-    const PackedLayout L = packed_layout(2);
-    if (int rc = opt_in_lds()) return rc;
-    const int cus = device_cu_count();
-    hipLaunchKernelGGL(cnn2w_kernel<2>, dim3(int(n < cus ? n : cus)), dim3(768), kCWLds, stream, mel, int(n), width,
-                       reinterpret_cast<const u32x4*>(packed + L.conv1_h), packed + L.conv1_hs, packed + L.conv1_b,
-                       reinterpret_cast<const u32x4*>(packed + L.conv2_hw), packed + L.conv2_hws, packed + L.conv2_b, packed + L.range, pooled,
-                       static_cast<float*>(nullptr), reinterpret_cast<uint16_t*>(bits), reinterpret_cast<uint16_t*>(bits1), ColTiling{});
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+template <bool POOL, bool TILED = false>
+static int run_cnn2(const float* mel, int64_t n, int width, const float* w1, const float* b1, const float* wB, const float* b2, float* out,
+                    ColTiling tl, hipStream_t stream) {
+    return launch<cnn2_kernel<POOL, TILED>>(persistent_grid(n, 2), dim3(256), sizeof(float) * kC2LdsFloats, stream, mel, int(n), width, w1, b1, wB,
+                                            b2, out, tl);                      // two 4-wave workgroups per CU
 }
 
-// training forward of the 3-conv model in split precision: the inference kernels; relu(conv2) stays in `mid2` as float32
-// [n][80 rows][32 columns][64 channels], the ReLU mask of conv3 and the sign bits of conv1 as bit images.
-int launch_cnn3w_pool_bits(const float* mel, int64_t n, int width, const float* packed, float* mid2, float* apow2, float* pooled,
-                           uint32_t* bits3, uint32_t* bits1, hipStream_t stream) {
-    if (n == 0) return WW_OK;
-    const PackedLayout L = packed_layout(3);
-    if (int rc = opt_in_lds()) return rc;
-    const int cus = device_cu_count();
-    const int grid1 = int(n < cus ? n : cus);
-    hipLaunchKernelGGL(cnn2w_kernel<3>, dim3(grid1), dim3(768), kCWLds, stream, mel, int(n), width,
-                       reinterpret_cast<const u32x4*>(packed + L.conv1_h), packed + L.conv1_hs, packed + L.conv1_b,
-                       reinterpret_cast<const u32x4*>(packed + L.conv2_hw), packed + L.conv2_hws, packed + L.conv2_b, packed + L.range, mid2,
-                       apow2, static_cast<uint16_t*>(nullptr), reinterpret_cast<uint16_t*>(bits1), ColTiling{});
-    WW_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cnn3w_kernel<true>, dim3(grid1), dim3(512), kC3wLds, stream, static_cast<const float*>(mid2),
-                       static_cast<const float*>(apow2), int(n), width, reinterpret_cast<const u32x4*>(packed + L.conv3_hw),
-                       packed + L.conv3_hws, packed + L.conv3_b, pooled, reinterpret_cast<uint16_t*>(bits3), ColTiling{});
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+template <bool STORE, bool TILED = false>
+static int run_cnn3(const float* mid2, int64_t n, int width, const float* wB, const float* b3, float* out, float* mid3, ColTiling tl,
+                    hipStream_t stream) {
+    return launch<cnn3_kernel<STORE, TILED>>(persistent_grid(n, 1), dim3(512), sizeof(float) * kC3LdsFloats, stream, mid2, int(n), width, wB, b3,
+                                             out, mid3, tl);
 }
 
-// training forward (ww_train.hip): conv1 + conv2 + ReLU in exact fp32, relu(conv2) kept as [n][80][64][32]
-int launch_cnn2_f32_mid(const float* mel, int64_t n, int width, const float* w1, const float* b1, const float* wB, const float* b2, float* mid,
-                        hipStream_t stream) {
-    if (n == 0) return WW_OK;
-    const int64_t cus = device_cu_count();
-    const int grid2 = int(n < 2 * cus ? n : 2 * cus);
-    hipLaunchKernelGGL(cnn2_kernel<false>, dim3(grid2), dim3(256), sizeof(float) * kC2LdsFloats, stream, mel, int(n), width, w1, b1, wB, b2, mid, ColTiling{});
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+template <bool POOL>
+static int run_cnn2h16(const float* mel, int64_t n, int width, const float* packed, const PackedLayout& L, float* out, float* apow2,
+                       hipStream_t stream) {
+    return launch<cnn2h16_kernel<POOL>>(persistent_grid(n, 1), dim3(768), kC2h16Lds, stream, mel, int(n), width,
+                                        reinterpret_cast<const u32x4*>(packed + L.conv1_h), packed + L.conv1_hs, packed + L.conv1_b,
+                                        reinterpret_cast<const u32x4*>(packed + L.conv2_h16), packed + L.conv2_hs, packed + L.conv2_b,
+                                        packed + L.range, out, apow2);
 }
 
-// training forward of the 3-conv model: conv3 + ReLU + pool in exact fp32 from relu(conv2) [n][80][64][32], keeping relu(conv3)
-int launch_cnn3_f32_store(const float* mid2, int64_t n, int width, const float* wB, const float* b3, float* pooled, float* mid3,
-                          hipStream_t stream) {
-    if (n == 0) return WW_OK;
-    if (int rc = opt_in_lds()) return rc;
-    const int64_t cus = device_cu_count();
-    hipLaunchKernelGGL(cnn3_kernel<true>, dim3(int(n < cus ? n : cus)), dim3(512), sizeof(float) * kC3LdsFloats, stream, mid2, int(n), width, wB, b3,
-                       pooled, mid3, ColTiling{});
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+static int run_cnn3h(const float* mid2, const float* apow2, int64_t n, int width, const float* packed, const PackedLayout& L, float* out,
+                     hipStream_t stream) {
+    return launch<cnn3h_kernel>(persistent_grid(n, 1), dim3(512), kC3hLds, stream, reinterpret_cast<const _Float16*>(mid2), apow2, int(n), width,
+                                reinterpret_cast<const u32x4*>(packed + L.conv3_h), packed + L.conv3_hs, packed + L.conv3_b, out);
+}
+
+template <int OUT, bool TILED = false>
+static int run_cnn2w(const float* mel, int64_t n, int width, const float* packed, const PackedLayout& L, float* out, float* apow2,
+                     uint32_t* bits, uint32_t* bits1, ColTiling tl, hipStream_t stream) {
+    return launch<cnn2w_kernel<OUT, TILED>>(persistent_grid(n, 1), dim3(768), kCWLds, stream, mel, int(n), width,
+                                            reinterpret_cast<const u32x4*>(packed + L.conv1_h), packed + L.conv1_hs, packed + L.conv1_b,
+                                            reinterpret_cast<const u32x4*>(packed + L.conv2_hw), packed + L.conv2_hws, packed + L.conv2_b,
+                                            packed + L.range, out, apow2, reinterpret_cast<uint16_t*>(bits), reinterpret_cast<uint16_t*>(bits1), tl);
+}
+
+template <bool BITS, bool TILED = false>
+static int run_cnn3w(const float* mid2, const float* apow2, int64_t n, int width, const float* packed, const PackedLayout& L, float* out,
+                     uint32_t* bits3, ColTiling tl, hipStream_t stream) {
+    return launch<cnn3w_kernel<BITS, TILED>>(persistent_grid(n, 1), dim3(512), kC3wLds, stream, mid2, apow2, int(n), width,
+                                             reinterpret_cast<const u32x4*>(packed + L.conv3_hw), packed + L.conv3_hws, packed + L.conv3_b, out,
+                                             reinterpret_cast<uint16_t*>(bits3), tl);
 }
 
 // Experiment knob (WW_CNN3_SUBBATCH, read once): clips per conv2 -> conv3 sub-batch of the 3-conv model's Winograd path.
@@ -1605,81 +1570,78 @@ static int64_t cnn3_subbatch() {
     return v;
 }
 
+// The inference conv stack under the current conv math: n clips of `width` columns -> out [n][64 | 128].  TILED: the clips are the column
+// tiles `tl` of wider ones (below).  scratch (n_conv 3): cnn_scratch_bytes(n, 3) = relu(conv2), then one float per clip (f16x3: 2^a2).
+template <bool TILED>
+static int conv_stack(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch, float* out, ColTiling tl,
+                      hipStream_t stream) {
+    const PackedLayout L = packed_layout(n_conv);
+    float* mid = static_cast<float*>(scratch);
+    float* apow2 = n_conv == 3 ? reinterpret_cast<float*>(static_cast<char*>(scratch) + mid_bytes(n)) : nullptr;
+    const int cmath = conv_math_mode();                        // read once per launch (thread override, else the process default)
+    if constexpr (!TILED) {
+        if (cmath == WW_CONV_MATH_F16X3_DIRECT) {              // f16x3, every conv in its direct form
+            if (n_conv == 2) return run_cnn2h16<true>(mel, n, width, packed, L, out, nullptr, stream);
+            if (int rc = run_cnn2h16<false>(mel, n, width, packed, L, mid, apow2, stream)) return rc;
+            return run_cnn3h(mid, apow2, n, width, packed, L, out, stream);
+        }
+    }
+    if (cmath == WW_CONV_MATH_F16X3) {                         // f16x3, conv2 (and conv3) as 1-D Winograd
+        if (n_conv == 2) return run_cnn2w<kOutPool, TILED>(mel, n, width, packed, L, out, nullptr, nullptr, nullptr, tl, stream);
+        // conv2 -> conv3 over sub-batches that reuse the FRONT of the scratch buffer: the 655 KB per clip of relu(conv2) are then
+        // written and read back inside the 256 MB Infinity Cache instead of going through HBM (cnn3_subbatch() clips; 0 = one pass)
+        const int64_t sub = !TILED && cnn3_subbatch() > 0 ? cnn3_subbatch() : n;
+        for (int64_t s0 = 0; s0 < n; s0 += sub) {
+            const int64_t cnt = n - s0 < sub ? n - s0 : sub;
+            if (int rc = run_cnn2w<kOutMid, TILED>(mel + s0 * 80 * width, cnt, width, packed, L, mid, apow2, nullptr, nullptr, tl, stream)) return rc;
+            if (int rc = run_cnn3w<false, TILED>(mid, apow2, cnt, width, packed, L, out + s0 * 128, nullptr, tl, stream)) return rc;
+        }
+        return WW_OK;
+    }
+    // exact f32
+    const float *w1 = packed + L.conv1_w, *b1 = packed + L.conv1_b, *w2 = packed + L.conv2_w, *b2 = packed + L.conv2_b;
+    if (n_conv == 2) return run_cnn2<true, TILED>(mel, n, width, w1, b1, w2, b2, out, tl, stream);
+    if (int rc = run_cnn2<false, TILED>(mel, n, width, w1, b1, w2, b2, mid, tl, stream)) return rc;
+    return run_cnn3<false, TILED>(mid, n, width, packed + L.conv3_w, packed + L.conv3_b, out, nullptr, tl, stream);
+}
+
 int launch_cnn_pool(const float* mel, int64_t n, int width, const float* packed, int n_conv, void* scratch,
                     float* pooled, hipStream_t stream) {
     if (n == 0) return WW_OK;
     if (n_conv == 3 && !scratch) return fail(WW_EINVAL, "n_conv == 3 needs ww_cnn_scratch_bytes() of scratch");
-    const PackedLayout L = packed_layout(n_conv);
-    if (int rc = opt_in_lds()) return rc;
-    const int cus = device_cu_count();
-    const int grid1 = int(n < cus ? n : cus);                  // persistent: one workgroup per CU
-    const int cmath = conv_math_mode();                        // read once per launch (thread override, else the process default)
-    if (cmath != 0) {                                          // f16x3
-        const u32x4* w1h = reinterpret_cast<const u32x4*>(packed + L.conv1_h);
-        const u32x4* w2h = reinterpret_cast<const u32x4*>(packed + L.conv2_h16);
-        if (cmath == 1) {                                      // conv2 (and conv3) as 1-D Winograd
-            const u32x4* w2w = reinterpret_cast<const u32x4*>(packed + L.conv2_hw);
-            if (n_conv == 2) {
-                hipLaunchKernelGGL(cnn2w_kernel<true>, dim3(grid1), dim3(768), kCWLds, stream, mel, int(n), width, w1h,
-                                   packed + L.conv1_hs, packed + L.conv1_b, w2w, packed + L.conv2_hws, packed + L.conv2_b,
-                                   packed + L.range, pooled, static_cast<float*>(nullptr), static_cast<uint16_t*>(nullptr),
-                                   static_cast<uint16_t*>(nullptr), ColTiling{});
-                WW_HIP(hipGetLastError());
-                return WW_OK;
-            }
-            float* apw = reinterpret_cast<float*>(static_cast<char*>(scratch) + mid_bytes(n));
-            // conv2 -> conv3 over sub-batches that reuse the FRONT of the scratch buffer: the 655 KB per clip of relu(conv2) are then
-            // written and read back inside the 256 MB Infinity Cache instead of going through HBM (cnn3_subbatch() clips; 0 = one pass)
-            const int64_t sub = cnn3_subbatch() > 0 ? cnn3_subbatch() : n;
-            for (int64_t s0 = 0; s0 < n; s0 += sub) {
-                const int64_t cnt = n - s0 < sub ? n - s0 : sub;
-                const int g = int(cnt < cus ? cnt : cus);
-                hipLaunchKernelGGL(cnn2w_kernel<false>, dim3(g), dim3(768), kCWLds, stream, mel + s0 * 80 * width, int(cnt), width, w1h,
-                                   packed + L.conv1_hs, packed + L.conv1_b, w2w, packed + L.conv2_hws, packed + L.conv2_b,
-                                   packed + L.range, static_cast<float*>(scratch), apw, static_cast<uint16_t*>(nullptr), static_cast<uint16_t*>(nullptr), ColTiling{});
-                WW_HIP(hipGetLastError());
-                hipLaunchKernelGGL(cnn3w_kernel<false>, dim3(g), dim3(512), kC3wLds, stream, static_cast<const float*>(scratch),
-                                   static_cast<const float*>(apw), int(cnt), width, reinterpret_cast<const u32x4*>(packed + L.conv3_hw),
-                                   packed + L.conv3_hws, packed + L.conv3_b, pooled + s0 * 128, static_cast<uint16_t*>(nullptr), ColTiling{});
-                WW_HIP(hipGetLastError());
-            }
-            return WW_OK;
-        }
-        if (n_conv == 2) {
-            hipLaunchKernelGGL(cnn2h16_kernel<true>, dim3(grid1), dim3(768), kC2h16Lds, stream, mel, int(n), width, w1h,
-                               packed + L.conv1_hs, packed + L.conv1_b, w2h, packed + L.conv2_hs, packed + L.conv2_b,
-                               packed + L.range, pooled, static_cast<float*>(nullptr));
-            WW_HIP(hipGetLastError());
-            return WW_OK;
-        }
-        float* apow2 = reinterpret_cast<float*>(static_cast<char*>(scratch) + mid_bytes(n));
-        hipLaunchKernelGGL(cnn2h16_kernel<false>, dim3(grid1), dim3(768), kC2h16Lds, stream, mel, int(n), width, w1h,
-                           packed + L.conv1_hs, packed + L.conv1_b, w2h, packed + L.conv2_hs, packed + L.conv2_b,
-                           packed + L.range, static_cast<float*>(scratch), apow2);
-        WW_HIP(hipGetLastError());
-        hipLaunchKernelGGL(cnn3h_kernel, dim3(grid1), dim3(512), kC3hLds, stream, static_cast<const _Float16*>(scratch),
-                           static_cast<const float*>(apow2), int(n), width, reinterpret_cast<const u32x4*>(packed + L.conv3_h),
-                           packed + L.conv3_hs, packed + L.conv3_b, pooled);
-        WW_HIP(hipGetLastError());
-        return WW_OK;
-    }
-    // exact f32
-    const int grid2 = int(n < 2 * int64_t(cus) ? n : 2 * int64_t(cus));   // two 4-wave workgroups per CU
-    const size_t lds2 = sizeof(float) * kC2LdsFloats;
-    if (n_conv == 2) {
-        hipLaunchKernelGGL(cnn2_kernel<true>, dim3(grid2), dim3(256), lds2, stream, mel, int(n), width,
-                           packed + L.conv1_w, packed + L.conv1_b, packed + L.conv2_w, packed + L.conv2_b, pooled, ColTiling{});
-        WW_HIP(hipGetLastError());
-        return WW_OK;
-    }
-    float* mid = static_cast<float*>(scratch);
-    hipLaunchKernelGGL(cnn2_kernel<false>, dim3(grid2), dim3(256), lds2, stream, mel, int(n), width,
-                       packed + L.conv1_w, packed + L.conv1_b, packed + L.conv2_w, packed + L.conv2_b, mid, ColTiling{});
-    WW_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cnn3_kernel<false>, dim3(grid1), dim3(512), sizeof(float) * kC3LdsFloats, stream, mid, int(n), width,
-                       packed + L.conv3_w, packed + L.conv3_b, pooled, static_cast<float*>(nullptr), ColTiling{});
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return conv_stack<false>(mel, n, width, packed, n_conv, scratch, pooled, ColTiling{}, stream);
+}
+
+// training forward of the 2-conv model in split precision (ww_train.hip): the inference kernel with the ReLU mask as a second output.
+// `packed`: a packed image whose conv1 / conv2-Winograd / range entries were written on the device from the live parameters.
+int launch_cnn2w_pool_bits(const float* mel, int64_t n, int width, const float* packed, float* pooled, uint32_t* bits, uint32_t* bits1,
+                           hipStream_t stream) {
+    if (n == 0) return WW_OK;
+    return run_cnn2w<kOutPoolBits>(mel, n, width, packed, packed_layout(2), pooled, nullptr, bits, bits1, ColTiling{}, stream);
+}
+
+// training forward of the 3-conv model in split precision: the inference kernels; relu(conv2) stays in `mid2` as float32
+// [n][80 rows][32 columns][64 channels], the ReLU mask of conv3 and the sign bits of conv1 as bit images.
+int launch_cnn3w_pool_bits(const float* mel, int64_t n, int width, const float* packed, float* mid2, float* apow2, float* pooled,
+                           uint32_t* bits3, uint32_t* bits1, hipStream_t stream) {
+    if (n == 0) return WW_OK;
+    const PackedLayout L = packed_layout(3);
+    if (int rc = run_cnn2w<kOutMidBits1>(mel, n, width, packed, L, mid2, apow2, nullptr, bits1, ColTiling{}, stream)) return rc;
+    return run_cnn3w<true>(mid2, apow2, n, width, packed, L, pooled, bits3, ColTiling{}, stream);
+}
+
+// training forward (ww_train.hip): conv1 + conv2 + ReLU in exact fp32, relu(conv2) kept as [n][80][64][32]
+int launch_cnn2_f32_mid(const float* mel, int64_t n, int width, const float* w1, const float* b1, const float* wB, const float* b2, float* mid,
+                        hipStream_t stream) {
+    if (n == 0) return WW_OK;
+    return run_cnn2<false>(mel, n, width, w1, b1, wB, b2, mid, ColTiling{}, stream);
+}
+
+// training forward of the 3-conv model: conv3 + ReLU + pool in exact fp32 from relu(conv2) [n][80][64][32], keeping relu(conv3)
+int launch_cnn3_f32_store(const float* mid2, int64_t n, int width, const float* wB, const float* b3, float* pooled, float* mid3,
+                          hipStream_t stream) {
+    if (n == 0) return WW_OK;
+    return run_cnn3<true>(mid2, n, width, wB, b3, pooled, mid3, ColTiling{}, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1714,62 +1676,16 @@ int launch_cnn_pool_wide(const float* mel, int64_t n, int width, const float* pa
     if (n == 0) return WW_OK;
     if (!scratch) return fail(WW_EINVAL, "the wide conv stack needs ww_cnn_wide_scratch_bytes() of scratch");
     const ColTiling tl = col_tiling(width, n_conv);
-    const int64_t nv64 = n * tl.K;
-    if (nv64 > (int64_t(1) << 30)) return fail(WW_EINVAL, "batch too large for the column-tiled conv stack: %lld tiles", (long long)nv64);
-    const int nv = int(nv64);
+    const int64_t nv = n * tl.K;
+    if (nv > (int64_t(1) << 30)) return fail(WW_EINVAL, "batch too large for the column-tiled conv stack: %lld tiles", (long long)nv);
     const int C = n_conv == 3 ? 128 : 64;
-    const PackedLayout L = packed_layout(n_conv);
-    if (int rc = opt_in_lds()) return rc;
-    float* partial = static_cast<float*>(scratch);
-    char* rest = static_cast<char*>(scratch) + up256(nv64 * C * int64_t(sizeof(float)));
-    const int cus = device_cu_count();
-    const int grid1 = nv < cus ? nv : cus;
-    const int cmath = conv_math_mode();
-    if (cmath == WW_CONV_MATH_F16X3_DIRECT)   // one model, one arithmetic: no silent switch to the Winograd form for wide images
+    if (conv_math_mode() == WW_CONV_MATH_F16X3_DIRECT)   // one model, one arithmetic: no silent switch to the Winograd form for wide images
         return fail(WW_EUNSUPPORTED, "WW_CONV_MATH_F16X3_DIRECT has no column-tiled form (widths > 32): use WW_CONV_MATH_F16X3 or WW_CONV_MATH_F32");
-    if (cmath != 0) {        // f16x3: the Winograd kernels
-        const u32x4* w1h = reinterpret_cast<const u32x4*>(packed + L.conv1_h);
-        const u32x4* w2w = reinterpret_cast<const u32x4*>(packed + L.conv2_hw);
-        if (n_conv == 2) {
-            hipLaunchKernelGGL((cnn2w_kernel<1, true>), dim3(grid1), dim3(768), kCWLds, stream, mel, nv, kW, w1h, packed + L.conv1_hs,
-                               packed + L.conv1_b, w2w, packed + L.conv2_hws, packed + L.conv2_b, packed + L.range, partial,
-                               static_cast<float*>(nullptr), static_cast<uint16_t*>(nullptr), static_cast<uint16_t*>(nullptr), tl);
-            WW_HIP(hipGetLastError());
-        } else {
-            float* mid = reinterpret_cast<float*>(rest);
-            float* apw = reinterpret_cast<float*>(rest + mid_bytes(nv64));
-            hipLaunchKernelGGL((cnn2w_kernel<0, true>), dim3(grid1), dim3(768), kCWLds, stream, mel, nv, kW, w1h, packed + L.conv1_hs,
-                               packed + L.conv1_b, w2w, packed + L.conv2_hws, packed + L.conv2_b, packed + L.range, mid, apw,
-                               static_cast<uint16_t*>(nullptr), static_cast<uint16_t*>(nullptr), tl);
-            WW_HIP(hipGetLastError());
-            hipLaunchKernelGGL((cnn3w_kernel<false, true>), dim3(grid1), dim3(512), kC3wLds, stream, static_cast<const float*>(mid),
-                               static_cast<const float*>(apw), nv, kW, reinterpret_cast<const u32x4*>(packed + L.conv3_hw),
-                               packed + L.conv3_hws, packed + L.conv3_b, partial, static_cast<uint16_t*>(nullptr), tl);
-            WW_HIP(hipGetLastError());
-        }
-    } else {                 // exact f32
-        const int grid2 = int(nv64 < 2 * int64_t(cus) ? nv64 : 2 * int64_t(cus));
-        const size_t lds2 = sizeof(float) * kC2LdsFloats;
-        if (n_conv == 2) {
-            hipLaunchKernelGGL((cnn2_kernel<true, true>), dim3(grid2), dim3(256), lds2, stream, mel, nv, kW, packed + L.conv1_w,
-                               packed + L.conv1_b, packed + L.conv2_w, packed + L.conv2_b, partial, tl);
-            WW_HIP(hipGetLastError());
-        } else {
-            float* mid = reinterpret_cast<float*>(rest);
-            hipLaunchKernelGGL((cnn2_kernel<false, true>), dim3(grid2), dim3(256), lds2, stream, mel, nv, kW, packed + L.conv1_w,
-                               packed + L.conv1_b, packed + L.conv2_w, packed + L.conv2_b, mid, tl);
-            WW_HIP(hipGetLastError());
-            hipLaunchKernelGGL((cnn3_kernel<false, true>), dim3(grid1), dim3(512), sizeof(float) * kC3LdsFloats, stream,
-                               static_cast<const float*>(mid), nv, kW, packed + L.conv3_w, packed + L.conv3_b, partial,
-                               static_cast<float*>(nullptr), tl);
-            WW_HIP(hipGetLastError());
-        }
-    }
+    float* partial = static_cast<float*>(scratch);
+    char* rest = static_cast<char*>(scratch) + up256(nv * C * int64_t(sizeof(float)));
+    if (int rc = conv_stack<true>(mel, nv, kW, packed, n_conv, rest, partial, tl, stream)) return rc;
     const int64_t n_out = n * C;
-    hipLaunchKernelGGL(pool_tiles_kernel, dim3(unsigned((n_out + 255) / 256)), dim3(256), 0, stream, static_cast<const float*>(partial),
-                       n_out, tl.K, C, pooled);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<pool_tiles_kernel>(dim3(unsigned((n_out + 255) / 256)), dim3(256), 0, stream, partial, n_out, tl.K, C, pooled);
 }
 
 }  // namespace ww

@@ -506,13 +506,9 @@ int launch_stream_input(const StreamInput& si, const void* hop, int n_mics, floa
     // every microphone reads every tap once or more per hop: in LDS whenever they fit beside the hop's frames (a hop's span is far
     // shorter than K0's 7,168-frame blocks, so the 11.025 kHz filter's 12,801 taps fit here; K0 reads them from global memory)
     const int grid = n_mics;
-    if (si.lh > 0 && si.lh + si.span <= kStreamLds) {
-        hipLaunchKernelGGL(stream_input_kernel<true>, dim3(grid), dim3(kStreamThreads), (si.lh + si.span) * sizeof(float), stream, a);
-    } else {
-        hipLaunchKernelGGL(stream_input_kernel<false>, dim3(grid), dim3(kStreamThreads), si.span * sizeof(float), stream, a);
-    }
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    if (si.lh > 0 && si.lh + si.span <= kStreamLds)
+        return launch<stream_input_kernel<true>>(dim3(grid), dim3(kStreamThreads), (si.lh + si.span) * sizeof(float), stream, a);
+    return launch<stream_input_kernel<false>>(dim3(grid), dim3(kStreamThreads), si.span * sizeof(float), stream, a);
 }
 
 }  // namespace ww
@@ -558,13 +554,11 @@ int ww_decode_resample_n(const uint8_t* raw_dev, const ww_clip_desc* descs_dev, 
     if (int rc = require_gfx950()) return rc;
     const int64_t resident = int64_t(device_cu_count()) * 8;
     const int grid = int(n_clips < resident ? n_clips : resident);
-    hipLaunchKernelGGL(decode_resample_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), raw_dev,
-                       descs_dev, int(n_clips), normalize, pcm_out_dev, int(n_samples));
+    if (int rc = launch<decode_resample_kernel>(dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), raw_dev, descs_dev, int(n_clips),
+                                                normalize, pcm_out_dev, int(n_samples))) return rc;
     const int64_t resident2 = int64_t(device_cu_count()) * 2;
-    hipLaunchKernelGGL(resample_lds_kernel, dim3(int(n_clips < resident2 ? n_clips : resident2)), dim3(kRsThreads), kRsLds,
-                       static_cast<hipStream_t>(stream), raw_dev, descs_dev, int(n_clips), normalize, pcm_out_dev, int(n_samples));
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<resample_lds_kernel>(dim3(int(n_clips < resident2 ? n_clips : resident2)), dim3(kRsThreads), kRsLds,
+                                       static_cast<hipStream_t>(stream), raw_dev, descs_dev, int(n_clips), normalize, pcm_out_dev, int(n_samples));
 }
 
 }  // extern "C"

@@ -109,26 +109,21 @@ int launch_events_sweep(const float* prob, const int64_t* offsets, int n_segs, i
     if (n_segs == 0) return WW_OK;
     if (n_windows > 0) {
         const int64_t blocks = (n_windows + 255) / 256;
-        hipLaunchKernelGGL(smooth_kernel, dim3(unsigned(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, prob, offsets, n_segs,
-                           n_windows, smooth, s_work);
-        WW_HIP(hipGetLastError());
+        if (int rc = launch<smooth_kernel>(dim3(unsigned(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, prob, offsets, n_segs, n_windows,
+                                           smooth, s_work)) return rc;
     }
     if (n_thr == 0) return WW_OK;
     const dim3 grid(unsigned((n_thr + kSweepThreads - 1) / kSweepThreads), unsigned(n_segs < 65535 ? n_segs : 65535));
-    hipLaunchKernelGGL(event_sweep_kernel, grid, dim3(kSweepThreads), 0, stream, s_work, offsets, n_segs, n_windows, thresholds, n_thr, refractory,
-                       counts, fired);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<event_sweep_kernel>(grid, dim3(kSweepThreads), 0, stream, s_work, offsets, n_segs, n_windows, thresholds, n_thr, refractory, counts,
+                                      fired);
 }
 
 int launch_events_step(const float* prob, int n_mics, int smooth, float threshold, int64_t refractory, void* state, uint8_t* fired,
                        hipStream_t stream) {
     int64_t* head = static_cast<int64_t*>(state);
     float* ring = reinterpret_cast<float*>(static_cast<char*>(state) + 16 * int64_t(n_mics));
-    hipLaunchKernelGGL(event_step_kernel, dim3(unsigned((n_mics + 255) / 256)), dim3(256), 0, stream, prob, n_mics, smooth, threshold,
-                       refractory, head, ring, fired);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<event_step_kernel>(dim3(unsigned((n_mics + 255) / 256)), dim3(256), 0, stream, prob, n_mics, smooth, threshold, refractory, head,
+                                     ring, fired);
 }
 
 }  // namespace ww

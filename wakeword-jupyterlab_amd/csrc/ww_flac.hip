@@ -225,10 +225,7 @@ __attribute__((visibility("default"))) int launch_flac_decode(uint8_t* raw_dev, 
                                                                 ww_clip_desc* descs_dev, hipStream_t stream) {
     if (n_flac <= 0 || n_frames_total <= 0) return WW_OK;
     const int64_t blocks = (n_frames_total + kFlacThreads - 1) / kFlacThreads;
-    hipLaunchKernelGGL(flac_decode_kernel, dim3(unsigned(blocks)), dim3(kFlacThreads), 0, stream, raw_dev, clips_dev, n_flac, n_frames_total,
-                       descs_dev);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<flac_decode_kernel>(dim3(unsigned(blocks)), dim3(kFlacThreads), 0, stream, raw_dev, clips_dev, n_flac, n_frames_total, descs_dev);
 }
 
 int flac_errors(unsigned int* count) {

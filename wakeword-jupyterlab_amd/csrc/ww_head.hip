@@ -258,14 +258,11 @@ int launch_lstm_fc_train(const float* pooled, int64_t n, int C, const float* w_i
     float* b0 = w0 + int64_t(C) * kGateCols;
     float* w1 = b0 + kGateCols;
     float* b1 = w1 + int64_t(kHidden) * kGateCols;
-    hipLaunchKernelGGL(pack_lstm_dev_kernel, dim3(192), dim3(256), 0, stream, w_ih0, b_ih0, b_hh0, C, w0, b0);
-    hipLaunchKernelGGL(pack_lstm_dev_kernel, dim3(768), dim3(256), 0, stream, w_ih1, b_ih1, b_hh1, kHidden, w1, b1);
-    WW_HIP(hipGetLastError());
+    if (int rc = launch<pack_lstm_dev_kernel>(dim3(192), dim3(256), 0, stream, w_ih0, b_ih0, b_hh0, C, w0, b0)) return rc;
+    if (int rc = launch<pack_lstm_dev_kernel>(dim3(768), dim3(256), 0, stream, w_ih1, b_ih1, b_hh1, kHidden, w1, b1)) return rc;
     const int grid = int((n + kClipsPerBlock - 1) / kClipsPerBlock);
-    hipLaunchKernelGGL(lstm_fc_train_kernel, dim3(grid), dim3(512), 0, stream, pooled, int(n), C, w0, b0, w1, b1, fcw, fcb, gates0, mask0, hd0,
-                       gates1, mask1, hd1, p_lstm, p_fc, uint32_t(seed), uint32_t(seed >> 32), logits);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<lstm_fc_train_kernel>(dim3(grid), dim3(512), 0, stream, pooled, int(n), C, w0, b0, w1, b1, fcw, fcb, gates0, mask0, hd0, gates1,
+                                        mask1, hd1, p_lstm, p_fc, uint32_t(seed), uint32_t(seed >> 32), logits);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -434,18 +431,12 @@ int launch_lstm_fc(const float* pooled, int64_t n, const float* packed, int n_co
     const PackedLayout L = packed_layout(n_conv);
     const int grid = int((n + kClipsPerBlock - 1) / kClipsPerBlock);
     if (conv_math_mode() != 0) {
-        hipLaunchKernelGGL(lstm_fc_h_kernel, dim3(grid), dim3(512), 0, stream, pooled, int(n), L.c_last,
-                           reinterpret_cast<const u32x4_t*>(packed + L.l0_h), packed + L.l0_b,
-                           reinterpret_cast<const u32x4_t*>(packed + L.l1_h), packed + L.l1_b, packed + L.lstm_hs,
-                           packed + L.fc_w, packed + L.fc_b, logits, prob);
-        WW_HIP(hipGetLastError());
-        return WW_OK;
+        return launch<lstm_fc_h_kernel>(dim3(grid), dim3(512), 0, stream, pooled, int(n), L.c_last, reinterpret_cast<const u32x4_t*>(packed + L.l0_h),
+                                        packed + L.l0_b, reinterpret_cast<const u32x4_t*>(packed + L.l1_h), packed + L.l1_b, packed + L.lstm_hs,
+                                        packed + L.fc_w, packed + L.fc_b, logits, prob);
     }
-    hipLaunchKernelGGL(lstm_fc_kernel, dim3(grid), dim3(512), 0, stream, pooled, int(n), L.c_last, packed + L.l0_w,
-                       packed + L.l0_b, packed + L.l1_w, packed + L.l1_b, packed + L.fc_w, packed + L.fc_b, logits,
-                       prob);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<lstm_fc_kernel>(dim3(grid), dim3(512), 0, stream, pooled, int(n), L.c_last, packed + L.l0_w, packed + L.l0_b, packed + L.l1_w,
+                                  packed + L.l1_b, packed + L.fc_w, packed + L.fc_b, logits, prob);
 }
 
 }  // namespace ww

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <mutex>
+#include <utility>
 #include <vector>
 
 #include "wakeword_amd.h"
@@ -23,6 +26,53 @@ int fail(int code, const char* fmt, ...);
 
 // THE rounding of every workspace region: sizes and offsets are multiples of 256 bytes
 inline int64_t up256(int64_t b) { return (b + 255) & ~int64_t(255); }
+
+// ---------------------------------------------------------------------------------------------
+// THE kernel launch: LDS opt-in, launch and error check.  Every launch in the library is
+//     return launch<kernel<...>>(grid, block, lds_bytes, stream, args...);
+// (or `if (int rc = launch<...>(...)) return rc;` where more follows).  The arguments convert to the kernel's parameter types as in a
+// plain call, so a null pointer is `nullptr`.  An error carries the call site's file and line, in WW_HIP's form.
+// ---------------------------------------------------------------------------------------------
+constexpr size_t kLdsNoOptIn = 64 * 1024;   // dynamic LDS a kernel gets without asking; up to 160 KiB per workgroup with an opt-in
+constexpr int kLdsOptInDevices = 64;
+
+struct LaunchGrid {        // the grid, with the place it was written at
+    dim3 dim;
+    const char* file;
+    int line;
+    LaunchGrid(dim3 d, const char* f = __builtin_FILE(), int l = __builtin_LINE()) : dim(d), file(f), line(l) {}
+};
+
+inline int launch_fail(const char* what, hipError_t e, const LaunchGrid& at) {
+    return fail(WW_EHIP, "%s failed: %s (%s:%d)", what, hipGetErrorString(e), at.file, at.line);
+}
+
+// The slow path of launch(): `granted` is the byte count this kernel instantiation was last opted in to on the current device.
+inline int lds_opt_in(const void* kernel, size_t lds_bytes, std::atomic<size_t>& granted, const LaunchGrid& at) {
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    if (lds_bytes <= granted.load(std::memory_order_relaxed)) return WW_OK;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes));
+    if (e != hipSuccess) return launch_fail("the opt-in to hipFuncAttributeMaxDynamicSharedMemorySize", e, at);
+    granted.store(lds_bytes, std::memory_order_release);
+    return WW_OK;
+}
+
+template <auto Kernel, class... A>
+int launch(LaunchGrid grid, dim3 block, size_t lds_bytes, hipStream_t stream, A&&... args) {
+    if (lds_bytes > kLdsNoOptIn) {       // once per (kernel instantiation, device), before its first launch there
+        static std::atomic<size_t> granted[kLdsOptInDevices] = {};
+        int dev = 0;
+        const hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return launch_fail("hipGetDevice(&dev)", e, grid);
+        if (dev < 0 || dev >= kLdsOptInDevices) return fail(WW_EINVAL, "device ordinal out of range");
+        if (lds_bytes > granted[dev].load(std::memory_order_acquire))
+            if (int rc = lds_opt_in(reinterpret_cast<const void*>(Kernel), lds_bytes, granted[dev], grid)) return rc;
+    }
+    hipLaunchKernelGGL(Kernel, grid.dim, block, lds_bytes, stream, std::forward<A>(args)...);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? WW_OK : launch_fail("hipGetLastError()", e, grid);
+}
 
 // ---------------------------------------------------------------------------------------------
 // K1 tables (one image per device, built on the host in double precision)
@@ -236,6 +286,11 @@ int launch_cnn3w_pool_bits(const float* mel, int64_t n, int width, const float* 
                            uint32_t* bits3, uint32_t* bits1, hipStream_t stream);
 int launch_cnn2w_pool_bits(const float* mel, int64_t n, int width, const float* packed, float* pooled, uint32_t* bits, uint32_t* bits1,
                            hipStream_t stream);
+// the exact-fp32 training forward of the conv stack, on the live parameters (wB: conv2 / conv3 weights in B-operand order)
+int launch_cnn2_f32_mid(const float* mel, int64_t n, int width, const float* w1, const float* b1, const float* wB, const float* b2, float* mid,
+                        hipStream_t stream);
+int launch_cnn3_f32_store(const float* mid2, int64_t n, int width, const float* wB, const float* b3, float* pooled, float* mid3,
+                          hipStream_t stream);
 int launch_conv2_wgrad_h(const float* mel, const uint32_t* maskbits, const float* gp, int64_t n, int width, const float* packed,
                          float* partial, int grid, hipStream_t st);
 

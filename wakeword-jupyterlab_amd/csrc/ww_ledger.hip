@@ -124,10 +124,8 @@ int ww_clip_ledger_init(void* ledger_dev, int64_t n_entries, ww_stream_t stream)
     if (int rc = require_gfx950()) return rc;
     const int64_t total = kLedHeaderWords + int64_t(kLedEntryWords) * n_entries;
     const int64_t blocks = (total + kLedThreads - 1) / kLedThreads;
-    hipLaunchKernelGGL(clip_ledger_init_kernel, dim3(unsigned(blocks < 4096 ? blocks : 4096)), dim3(kLedThreads), 0, static_cast<hipStream_t>(stream),
-                       static_cast<u64*>(ledger_dev), n_entries);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<clip_ledger_init_kernel>(dim3(unsigned(blocks < 4096 ? blocks : 4096)), dim3(kLedThreads), 0, static_cast<hipStream_t>(stream),
+                                           static_cast<u64*>(ledger_dev), n_entries);
 }
 
 int ww_clip_ledger_update_f32(const float* logits_dev, const int64_t* labels_dev, const int64_t* entries_dev, int64_t n, int32_t epoch,
@@ -141,11 +139,9 @@ int ww_clip_ledger_update_f32(const float* logits_dev, const int64_t* labels_dev
     if (int rc = check_ledger(ledger_dev, n_entries)) return rc;
     if (n == 0) return WW_OK;
     if (int rc = require_gfx950()) return rc;
-    hipLaunchKernelGGL(clip_ledger_kernel, dim3(unsigned((n + kLedThreads - 1) / kLedThreads)), dim3(kLedThreads), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const float2*>(logits_dev), labels_dev, entries_dev, n, int(epoch),
-                       static_cast<ww_ledger_header*>(ledger_dev), n_entries);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<clip_ledger_kernel>(dim3(unsigned((n + kLedThreads - 1) / kLedThreads)), dim3(kLedThreads), 0, static_cast<hipStream_t>(stream),
+                                      reinterpret_cast<const float2*>(logits_dev), labels_dev, entries_dev, n, int(epoch),
+                                      static_cast<ww_ledger_header*>(ledger_dev), n_entries);
 }
 
 }  // extern "C"

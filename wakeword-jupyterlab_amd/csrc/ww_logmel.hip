@@ -18,7 +18,6 @@
 //
 // Other clip lengths (ww_logmel_frames_f32, 0.25 .. 2 s): the same kernels with a 64-frame mel tile (template parameter FR = 64), computing
 // ceil(T / waves) rounds of frames and keeping the first T; the epilogue maps lane = frame, and auto mode's frame mask is 64 bits wide.
-#include <mutex>
 #include <type_traits>
 
 #include "ww_internal.h"
@@ -1013,13 +1012,10 @@ static int launch_logmel_w(const float* pcm, int64_t n_clips, int64_t clip_strid
     const int grid = int(n_clips < resident ? n_clips : resident);
     const size_t lds_bytes = sizeof(float) * L::kLdsFloats;
     if (ring_pos)
-        hipLaunchKernelGGL((logmel_kernel<true, WAVES, FR>), dim3(grid), dim3(L::kThreads), lds_bytes, stream, pcm, clip_stride, int(clip_len),
-                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark, n_frames);
-    else
-        hipLaunchKernelGGL((logmel_kernel<false, WAVES, FR>), dim3(grid), dim3(L::kThreads), lds_bytes, stream, pcm, clip_stride, int(clip_len),
-                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark, n_frames);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+        return launch<logmel_kernel<true, WAVES, FR>>(dim3(grid), dim3(L::kThreads), lds_bytes, stream, pcm, clip_stride, int(clip_len),
+                                                      int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark, n_frames);
+    return launch<logmel_kernel<false, WAVES, FR>>(dim3(grid), dim3(L::kThreads), lds_bytes, stream, pcm, clip_stride, int(clip_len),
+                                                   int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, mark, n_frames);
 }
 
 template <bool ONLY_FLAGGED, int FR = kFrames>
@@ -1030,46 +1026,10 @@ static int launch_logmel64(const float* pcm, int64_t n_clips, int64_t clip_strid
     const int grid = int(n_clips < resident ? n_clips : resident);
     const size_t lds_bytes = sizeof(float) * K64Layout<FR>::kLdsFloats;
     if (ring_pos)
-        hipLaunchKernelGGL((logmel64_kernel<true, ONLY_FLAGGED, FR>), dim3(grid), dim3(256), lds_bytes, stream, pcm, clip_stride, int(clip_len),
-                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, n_frames);
-    else
-        hipLaunchKernelGGL((logmel64_kernel<false, ONLY_FLAGGED, FR>), dim3(grid), dim3(256), lds_bytes, stream, pcm, clip_stride, int(clip_len),
-                           int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, n_frames);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
-}
-
-// > 64 KiB of dynamic LDS needs an opt-in per kernel, once per device
-static int logmel_opt_in_lds() {
-    static std::mutex mu;
-    static bool done[64] = {};
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    WW_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(WW_EINVAL, "device ordinal out of range");
-    if (done[dev]) return WW_OK;
-    const int b4 = int(sizeof(float) * K1Layout<4>::kLdsFloats), b8 = int(sizeof(float) * K1Layout<8>::kLdsFloats);
-    const int b64 = int(sizeof(float) * k64LdsFloats);
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, b4));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, b4));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, b8));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, b8));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, b64));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, b64));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, b64));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, b64));
-    const int c4 = int(sizeof(float) * K1Layout<4, 64>::kLdsFloats), c8 = int(sizeof(float) * K1Layout<8, 64>::kLdsFloats);
-    const int c64 = int(sizeof(float) * K64Layout<64>::kLdsFloats);
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<true, 4, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c4));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<false, 4, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c4));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<true, 8, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c8));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<false, 8, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c8));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<true, true, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c64));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<true, false, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c64));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<false, true, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c64));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel64_kernel<false, false, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, c64));
-    done[dev] = true;
-    return WW_OK;
+        return launch<logmel64_kernel<true, ONLY_FLAGGED, FR>>(dim3(grid), dim3(256), lds_bytes, stream, pcm, clip_stride, int(clip_len),
+                                                               int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, n_frames);
+    return launch<logmel64_kernel<false, ONLY_FLAGGED, FR>>(dim3(grid), dim3(256), lds_bytes, stream, pcm, clip_stride, int(clip_len),
+                                                            int(n_clips), normalize, ring_pos, int(ring_len), tb, logmel, n_frames);
 }
 
 int launch_logmel(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int normalize,
@@ -1077,19 +1037,19 @@ int launch_logmel(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_
     if (n_clips == 0) return WW_OK;
     const LogmelTables* tb = device_tables();
     if (!tb) return WW_EHIP;
-    if (int rc = logmel_opt_in_lds()) return rc;
     const int mode = logmel_math_mode();
-    if (mode == WW_LOGMEL_MATH_F64)
-        return launch_logmel64<false>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, stream);
-    const int mark = mode == WW_LOGMEL_MATH_AUTO;
-    // at most one clip per CU (streaming, small batches): the 8-wave latency form; otherwise the 4-wave throughput form
-    int rc;
-    if (n_clips <= device_cu_count())
-        rc = launch_logmel_w<8>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, mark, stream);
-    else
-        rc = launch_logmel_w<4>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, mark, stream);
-    if (rc != WW_OK || !mark) return rc;
-    return launch_logmel64<true>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, stream);
+    if (mode != WW_LOGMEL_MATH_F64) {
+        const int mark = mode == WW_LOGMEL_MATH_AUTO;
+        // more clips than CUs: the 4-wave throughput form; otherwise (streaming, small batches) the 8-wave latency form
+        int rc;
+        if (n_clips > device_cu_count())
+            rc = launch_logmel_w<4>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, mark, stream);
+        else
+            rc = launch_logmel_w<8>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, mark, stream);
+        if (rc != WW_OK || !mark) return rc;
+        return launch_logmel64<true>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, stream);
+    }
+    return launch_logmel64<false>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, stream);
 }
 
 // Any clip length (ww_logmel_frames_f32): rows of n_samples (clip_len valid, the rest zero), T = 1 + n_samples / 512 frames, [n][80][T].
@@ -1103,18 +1063,18 @@ int launch_logmel_frames(const float* pcm, int64_t n_clips, int64_t clip_stride,
     if (n_clips == 0) return WW_OK;
     const LogmelTables* tb = device_tables();
     if (!tb) return WW_EHIP;
-    if (int rc = logmel_opt_in_lds()) return rc;
     const int mode = logmel_math_mode();
-    if (mode == WW_LOGMEL_MATH_F64)
-        return launch_logmel64<false, 64>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, stream, T);
-    const int mark = mode == WW_LOGMEL_MATH_AUTO;
-    int rc;
-    if (n_clips <= device_cu_count())
-        rc = launch_logmel_w<8, 64>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, mark, stream, T);
-    else
-        rc = launch_logmel_w<4, 64>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, mark, stream, T);
-    if (rc != WW_OK || !mark) return rc;
-    return launch_logmel64<true, 64>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, stream, T);
+    if (mode != WW_LOGMEL_MATH_F64) {
+        const int mark = mode == WW_LOGMEL_MATH_AUTO;
+        int rc;
+        if (n_clips > device_cu_count())
+            rc = launch_logmel_w<4, 64>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, mark, stream, T);
+        else
+            rc = launch_logmel_w<8, 64>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, mark, stream, T);
+        if (rc != WW_OK || !mark) return rc;
+        return launch_logmel64<true, 64>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, stream, T);
+    }
+    return launch_logmel64<false, 64>(pcm, n_clips, clip_stride, clip_len, normalize, ring_pos, ring_len, logmel, tb, stream, T);
 }
 int launch_logmel_frames(const float* pcm, int64_t n_clips, int64_t clip_stride, int64_t clip_len, int64_t n_samples, int normalize,
                          float* logmel, hipStream_t stream) {

@@ -106,9 +106,7 @@ __global__ __launch_bounds__(256) void clip_metrics_clear_kernel(ww_clip_metrics
 }
 
 static int launch_clear(ww_clip_metrics* st, const MetMargins& margins, int n_thr, int write_margins, hipStream_t stream) {
-    hipLaunchKernelGGL(clip_metrics_clear_kernel, dim3((kMetCounterWords + 255) / 256), dim3(256), 0, stream, st, margins, n_thr, write_margins);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<clip_metrics_clear_kernel>(dim3((kMetCounterWords + 255) / 256), dim3(256), 0, stream, st, margins, n_thr, write_margins);
 }
 
 static bool threshold_ok(float p) { return p > 0.0f && p < 1.0f; }             // false for a NaN
@@ -168,10 +166,8 @@ int ww_clip_metrics_update_f32(const float* logits_dev, const int64_t* labels_de
     if (int rc = check_state(state_dev)) return rc;
     if (n == 0) return WW_OK;
     if (int rc = require_gfx950()) return rc;
-    hipLaunchKernelGGL(clip_metrics_kernel, dim3(1), dim3(kMetThreads), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const float2*>(logits_dev), labels_dev, n, state_dev);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<clip_metrics_kernel>(dim3(1), dim3(kMetThreads), 0, static_cast<hipStream_t>(stream), reinterpret_cast<const float2*>(logits_dev),
+                                       labels_dev, n, state_dev);
 }
 
 }  // extern "C"

@@ -78,11 +78,8 @@ int launch_mixup(const float* mel, float* out, int64_t B, int T, const int64_t* 
     const dim3 grid(unsigned((row_floats + kMixChunk - 1) / kMixChunk), unsigned(B < kMixMaxGridRows ? B : kMixMaxGridRows)), block(kMixThreads);
     const bool wide = ((reinterpret_cast<uintptr_t>(mel) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
     if (wide)
-        hipLaunchKernelGGL(mixup_kernel<true>, grid, block, 0, stream, mel, out, B, row_floats, labels, partner, lambda, targets);
-    else
-        hipLaunchKernelGGL(mixup_kernel<false>, grid, block, 0, stream, mel, out, B, row_floats, labels, partner, lambda, targets);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+        return launch<mixup_kernel<true>>(grid, block, 0, stream, mel, out, B, row_floats, labels, partner, lambda, targets);
+    return launch<mixup_kernel<false>>(grid, block, 0, stream, mel, out, B, row_floats, labels, partner, lambda, targets);
 }
 
 }  // namespace ww

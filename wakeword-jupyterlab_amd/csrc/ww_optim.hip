@@ -168,9 +168,7 @@ __global__ __launch_bounds__(kCeThreads) void loss_kernel(const float* __restric
 template <class P>
 static int launch_loss(const float* logits, const typename P::Target* targets, int64_t n, const P& pol, float* dlogits, float* loss,
                        ww_loss_stats* stats, hipStream_t stream) {
-    hipLaunchKernelGGL(loss_kernel<P>, dim3(1), dim3(kCeThreads), 0, stream, logits, targets, n, pol, dlogits, loss, stats);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<loss_kernel<P>>(dim3(1), dim3(kCeThreads), 0, stream, logits, targets, n, pol, dlogits, loss, stats);
 }
 
 static int launch_ce_loss(const float* logits, const int64_t* labels, int64_t n, float* dlogits, float* loss, ww_loss_stats* stats, hipStream_t stream) {
@@ -360,10 +358,7 @@ __global__ __launch_bounds__(kCeThreads) void distill_loss_kernel(const float* _
 template <class P>
 static int launch_distill(const float* logits, const float* teacher, const void* targets, int64_t n, const P& pol, const DistillArgs& da,
                           float* dlogits, float* loss, ww_loss_stats* stats, ww_distill_stats* dstats, hipStream_t stream) {
-    hipLaunchKernelGGL(distill_loss_kernel<P>, dim3(1), dim3(kCeThreads), 0, stream, logits, teacher, targets, n, pol, da, dlogits, loss, stats,
-                       dstats);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<distill_loss_kernel<P>>(dim3(1), dim3(kCeThreads), 0, stream, logits, teacher, targets, n, pol, da, dlogits, loss, stats, dstats);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -562,9 +557,7 @@ static int fill_table(const ww_adam_tensor* tensors, int n_tensors, int chunk, T
 int launch_adam(const ww_adam_tensor* tensors, int n_tensors, const AdamScalars& s, const float* grad_scale, hipStream_t stream) {
     TensorTable tab;
     if (int rc = fill_table(tensors, n_tensors, kAdamChunk, &tab)) return rc;
-    hipLaunchKernelGGL(adam_kernel, dim3(unsigned(tab.first_block[kMaxTensors])), dim3(kAdamThreads), 0, stream, tab, s, grad_scale);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<adam_kernel>(dim3(unsigned(tab.first_block[kMaxTensors])), dim3(kAdamThreads), 0, stream, tab, s, grad_scale);
 }
 
 // The kernel arguments of an averaging launch from the weight in double: the two float32 roundings and the rule.  The comparison with
@@ -583,10 +576,8 @@ int launch_adam_avg(const ww_adam_tensor* tensors, float* const* avg, int n_tens
     if (weight == 0.0) return launch_adam(tensors, n_tensors, s, grad_scale, stream);      // the average keeps its bits: the plain kernel
     TensorTable tab;
     if (int rc = fill_table(tensors, n_tensors, kAdamChunk, &tab)) return rc;
-    hipLaunchKernelGGL(adam_avg_kernel, dim3(unsigned(tab.first_block[kMaxTensors])), dim3(kAdamThreads), 0, stream, tab, s, grad_scale,
-                       avg_args(avg, n_tensors, weight));
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<adam_avg_kernel>(dim3(unsigned(tab.first_block[kMaxTensors])), dim3(kAdamThreads), 0, stream, tab, s, grad_scale,
+                                   avg_args(avg, n_tensors, weight));
 }
 
 int launch_weight_average(const ww_adam_tensor* tensors, float* const* avg, int n_tensors, double weight, hipStream_t stream) {
@@ -595,10 +586,8 @@ int launch_weight_average(const ww_adam_tensor* tensors, float* const* avg, int 
     ww_adam_tensor only_p[kMaxTensors];                     // g, m and v of the caller's table are not read: they do not travel either
     for (int k = 0; k < n_tensors; ++k) only_p[k] = ww_adam_tensor{tensors[k].p, nullptr, nullptr, nullptr, tensors[k].n};
     if (int rc = fill_table(only_p, n_tensors, kAdamChunk, &tab)) return rc;
-    hipLaunchKernelGGL(weight_average_kernel, dim3(unsigned(tab.first_block[kMaxTensors])), dim3(kAdamThreads), 0, stream, tab,
-                       avg_args(avg, n_tensors, weight));
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<weight_average_kernel>(dim3(unsigned(tab.first_block[kMaxTensors])), dim3(kAdamThreads), 0, stream, tab,
+                                         avg_args(avg, n_tensors, weight));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -670,11 +659,8 @@ int launch_grad_norm(const ww_adam_tensor* tensors, int n_tensors, double max_no
     if (int rc = fill_table(tensors, n_tensors, kNormChunk, &tab)) return rc;
     const int blocks = tab.first_block[kMaxTensors];
     double* partial = static_cast<double*>(workspace);
-    hipLaunchKernelGGL(grad_norm_kernel, dim3(unsigned(blocks)), dim3(kNormThreads), 0, stream, tab, partial);
-    WW_HIP(hipGetLastError());
-    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(kNormThreads), 0, stream, partial, blocks, max_norm, norm, scale);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    if (int rc = launch<grad_norm_kernel>(dim3(unsigned(blocks)), dim3(kNormThreads), 0, stream, tab, partial)) return rc;
+    return launch<grad_norm_finish_kernel>(dim3(1), dim3(kNormThreads), 0, stream, partial, blocks, max_norm, norm, scale);
 }
 
 // Host checks of a table, before any HIP call.  `state`: p, m and v are read and written (Adam); the norm reads g alone.

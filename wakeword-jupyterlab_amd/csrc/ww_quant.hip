@@ -245,9 +245,7 @@ int launch_quant(const ww_quant_tensor* tensors, int n_tensors, int bits, hipStr
     for (int k = n_tensors; k < kQuantMax; ++k) tab.t[k] = ww_quant_tensor{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
     tab.n_tensors = n_tensors;
     tab.qmax = float((1 << (bits - 1)) - 1);
-    hipLaunchKernelGGL(quant_kernel, dim3(unsigned(blocks)), dim3(kQuantThreads), 0, stream, tab);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<quant_kernel>(dim3(unsigned(blocks)), dim3(kQuantThreads), 0, stream, tab);
 }
 
 }  // namespace

@@ -261,13 +261,10 @@ int launch_reverb_records(const float* in, int64_t in_stride, int64_t n, int n_s
     const LogmelTables* tb = device_tables();
     if (!tb) return WW_EHIP;
     if (n_samples <= kRvN)
-        hipLaunchKernelGGL(reverb_kernel<1>, dim3(unsigned(n)), dim3(kRvThreads), 0, stream, in, in_stride, rir, spectra, n_rirs, tb, out,
-                           out_stride, n_samples);
-    else
-        hipLaunchKernelGGL(reverb_kernel<2>, dim3(unsigned(n)), dim3(kRvThreads), 0, stream, in, in_stride, rir, spectra, n_rirs, tb, out,
-                           out_stride, n_samples);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+        return launch<reverb_kernel<1>>(dim3(unsigned(n)), dim3(kRvThreads), 0, stream, in, in_stride, rir, spectra, n_rirs, tb, out, out_stride,
+                                        n_samples);
+    return launch<reverb_kernel<2>>(dim3(unsigned(n)), dim3(kRvThreads), 0, stream, in, in_stride, rir, spectra, n_rirs, tb, out, out_stride,
+                                    n_samples);
 }
 
 int64_t reverb_workspace_bytes(int64_t n) { return up256(n * int64_t(sizeof(RirDev))); }
@@ -304,10 +301,7 @@ int launch_rir_spectra(const float* taps, int64_t taps_len, const int64_t* offse
     const size_t bytes = size_t(n_rirs) * sizeof(RirSrc);
     void* const dst = src;
     if (int rc = stage_to_device(&from, &bytes, &dst, 1, stream)) return rc;
-    hipLaunchKernelGGL(rir_spectrum_kernel, dim3(unsigned(n_rirs)), dim3(kRvThreads), 0, stream, taps, src, tb,
-                       reinterpret_cast<float2*>(spectra));
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<rir_spectrum_kernel>(dim3(unsigned(n_rirs)), dim3(kRvThreads), 0, stream, taps, src, tb, reinterpret_cast<float2*>(spectra));
 }
 
 }  // namespace ww

@@ -201,10 +201,8 @@ static int launch_select(const float* logits, const void* targets, int64_t n, in
                          double* scores, ww_select_stats* stats, void* workspace, hipStream_t stream) {
     uint64_t* keys = static_cast<uint64_t*>(workspace);
     uint8_t* cls = static_cast<uint8_t*>(workspace) + up256(n * int64_t(sizeof(uint64_t)));
-    hipLaunchKernelGGL(hard_select_kernel<P>, dim3(1), dim3(kSelThreads), 0, stream, logits, static_cast<const typename P::Target*>(targets),
-                       int(n), int(keep), pol, keep_class, sel, scores, stats, keys, cls);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<hard_select_kernel<P>>(dim3(1), dim3(kSelThreads), 0, stream, logits, static_cast<const typename P::Target*>(targets), int(n),
+                                         int(keep), pol, keep_class, sel, scores, stats, keys, cls);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -321,9 +319,7 @@ int ww_select_rows_f32(const float* mel_dev, int64_t n, int32_t width, const int
     if (int rc = require_gfx950()) return rc;
     RowGather g = {mel_dev, mel_out, targets_dev, targets_out, entries_dev, entries_out, labels_dev, labels_out, n, int32_t(row_floats), probs ? 1 : 0,
                    (row_floats % 4 == 0 && !misaligned(mel_dev, 15) && !misaligned(mel_out, 15)) ? 1 : 0};
-    hipLaunchKernelGGL(select_rows_kernel, dim3(unsigned(keep)), dim3(kRowThreads), 0, static_cast<hipStream_t>(stream), sel_dev, g);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<select_rows_kernel>(dim3(unsigned(keep)), dim3(kRowThreads), 0, static_cast<hipStream_t>(stream), sel_dev, g);
 }
 
 }  // extern "C"

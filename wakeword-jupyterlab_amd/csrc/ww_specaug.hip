@@ -164,9 +164,7 @@ __global__ __launch_bounds__(kSpecThreads) void spec_augment_kernel(const float*
 
 int launch_spec_draw(const SpecDraw& d, int64_t n, int T, int16_t* records, hipStream_t stream) {
     const int64_t grid = (n + kSpecThreads - 1) / kSpecThreads;
-    hipLaunchKernelGGL(spec_draw_kernel, dim3(unsigned(grid)), dim3(kSpecThreads), 0, stream, records, n, T, d);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<spec_draw_kernel>(dim3(unsigned(grid)), dim3(kSpecThreads), 0, stream, records, n, T, d);
 }
 
 int launch_spec_augment(const float* in, float* out, int64_t n, int T, const int16_t* records, const SpecDraw& d, int mode, float fill_value,
@@ -174,13 +172,10 @@ int launch_spec_augment(const float* in, float* out, int64_t n, int T, const int
     const dim3 grid(unsigned((n + kSpecWaves - 1) / kSpecWaves)), block(kSpecThreads);
     const uint32_t t_recip = T == 1 ? 0u : uint32_t((uint64_t(1) << 32) / uint64_t(T)) + 1u;
     if (T <= 16)
-        hipLaunchKernelGGL(spec_augment_kernel<5>, grid, block, 0, stream, in, out, n, T, t_recip, records, d, mode, fill_value);
-    else if (T <= 32)
-        hipLaunchKernelGGL(spec_augment_kernel<10>, grid, block, 0, stream, in, out, n, T, t_recip, records, d, mode, fill_value);
-    else
-        hipLaunchKernelGGL(spec_augment_kernel<20>, grid, block, 0, stream, in, out, n, T, t_recip, records, d, mode, fill_value);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+        return launch<spec_augment_kernel<5>>(grid, block, 0, stream, in, out, n, T, t_recip, records, d, mode, fill_value);
+    if (T <= 32)
+        return launch<spec_augment_kernel<10>>(grid, block, 0, stream, in, out, n, T, t_recip, records, d, mode, fill_value);
+    return launch<spec_augment_kernel<20>>(grid, block, 0, stream, in, out, n, T, t_recip, records, d, mode, fill_value);
 }
 
 }  // namespace ww

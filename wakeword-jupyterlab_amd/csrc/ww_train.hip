@@ -572,20 +572,19 @@ __global__ void combine_splitk_kernel(const float* __restrict__ part, int splits
 }
 
 // `part`: scratch of at least 8 * (M * N + M) floats for the GEMMs that are split (the reused gradient-partial block of the workspace)
-static void sgemm(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, float* C, int64_t ldc, int M, int N, int K,
-                  hipStream_t st, float* rowsum = nullptr, float* part = nullptr) {
+static int sgemm(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, float* C, int64_t ldc, int M, int N, int K,
+                 hipStream_t st, float* rowsum = nullptr, float* part = nullptr) {
     const int tiles = ((N + 31) / 32) * ((M + 31) / 32);
     int splits = 1;
     if (part != nullptr && K >= 512) {
         while (splits < 8 && tiles * splits < 1024 && K / (2 * splits) >= 128) splits *= 2;     // ~4 workgroups per CU, >= 64 k pairs per slice
     }
-    hipLaunchKernelGGL(mfma_gemm_kernel, dim3((N + 31) / 32, (M + 31) / 32, splits), dim3(256), 0, st, A, sam, sak, B, sbk, sbn, C, ldc, M, N, K, rowsum,
-                       part);
-    if (splits > 1) {
-        const int64_t work = int64_t(M) * N + (rowsum ? M : 0);
-        hipLaunchKernelGGL(combine_splitk_kernel, dim3(unsigned((work + 255) / 256 < 1024 ? (work + 255) / 256 : 1024)), dim3(256), 0, st, part, splits, M,
-                           N, C, ldc, rowsum);
-    }
+    if (int rc = launch<mfma_gemm_kernel>(dim3((N + 31) / 32, (M + 31) / 32, splits), dim3(256), 0, st, A, sam, sak, B, sbk, sbn, C, ldc, M, N, K, rowsum,
+                                          part)) return rc;
+    if (splits == 1) return WW_OK;
+    const int64_t work = int64_t(M) * N + (rowsum ? M : 0);
+    return launch<combine_splitk_kernel>(dim3(unsigned((work + 255) / 256 < 1024 ? (work + 255) / 256 : 1024)), dim3(256), 0, st, part, splits, M, N, C,
+                                         ldc, rowsum);
 }
 
 // gp[b][co] = dpooled[b][co] / (80 * width)
@@ -596,10 +595,6 @@ __global__ void scale_kernel(const float* __restrict__ x, float s, int64_t len, 
 // ------------------------------------------------------------------------------------------------
 // workspace and orchestration
 // ------------------------------------------------------------------------------------------------
-int launch_cnn2_f32_mid(const float* mel, int64_t n, int width, const float* w1, const float* b1, const float* wB, const float* b2, float* mid,
-                        hipStream_t stream);   // ww_cnn.hip
-int launch_cnn3_f32_store(const float* mid2, int64_t n, int width, const float* wB, const float* b3, float* pooled, float* mid3,
-                          hipStream_t stream);   // ww_cnn.hip
 int launch_lstm_fc_train(const float* pooled, int64_t n, int C, const float* w_ih0, const float* b_ih0, const float* b_hh0,
                          const float* w_ih1, const float* b_ih1, const float* b_hh1, const float* fcw, const float* fcb, float* packed_ws,
                          float* gates0, float* mask0, float* hd0, float* gates1, float* mask1, float* hd1, float p_lstm, float p_fc,
@@ -686,25 +681,6 @@ static TrainWs carve_train(void* base, int64_t n, int n_conv, int mode) {
 }
 
 int64_t train_workspace_bytes(int64_t n, int n_conv, int mode) { return carve_train(nullptr, n, n_conv, mode).total; }
-
-static int train_opt_in() {
-    static std::mutex mu;
-    static bool done[64] = {};
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    WW_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(WW_EINVAL, "device ordinal out of range");
-    if (done[dev]) return WW_OK;
-    auto opt = [](const void* f, int floats) { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, floats * 4); };
-    WW_HIP(opt(reinterpret_cast<const void*>(conv_wgrad_kernel<32, 64, 8, false, true>), WgradCfg<32, 64, 8>::kLdsFloats));
-    WW_HIP(opt(reinterpret_cast<const void*>(conv_wgrad_kernel<32, 64, 8, true, true>), WgradCfg<32, 64, 8>::kLdsFloats));
-    WW_HIP(opt(reinterpret_cast<const void*>(conv_wgrad_kernel<64, 128, 4, false, false>), WgradCfg<64, 128, 4>::kLdsFloats));
-    WW_HIP(opt(reinterpret_cast<const void*>(conv_dgrad_kernel<32, 64, false, true>), DgradCfg<32, 64>::kLdsFloats));
-    WW_HIP(opt(reinterpret_cast<const void*>(conv_dgrad_kernel<32, 64, true, true>), DgradCfg<32, 64>::kLdsFloats));
-    WW_HIP(opt(reinterpret_cast<const void*>(conv_dgrad_kernel<64, 128, false, false>), DgradCfg<64, 128>::kLdsFloats));
-    done[dev] = true;
-    return WW_OK;
-}
 
 // test / diagnostic: copies of the dropout factors the last forward on this workspace drew ([n][256] each)
 int train_masks(const void* workspace, int64_t n, int n_conv, float* mask0, float* mask1, hipStream_t st) {
@@ -813,16 +789,13 @@ int train_forward(const float* mel, int64_t n, int width, const ww_train_params*
                                     p->lstm_bias_ih[1], p->lstm_bias_hh[1], p->fc_weight, p->fc_bias, w.lstm_packed, w.gates0, w.mask0, w.hd0,
                                     w.gates1, w.mask1, w.hd1, p_lstm, p_fc, seed, logits, st);
     }
-    hipLaunchKernelGGL(pack_conv_b_dev_kernel, dim3(72), dim3(256), 0, st, p->conv_weight[1], 64, 32, w.conv2_b_op);
-    WW_HIP(hipGetLastError());
+    if (int rc = launch<pack_conv_b_dev_kernel>(dim3(72), dim3(256), 0, st, p->conv_weight[1], 64, 32, w.conv2_b_op)) return rc;
     if (int rc = launch_cnn2_f32_mid(mel, n, width, p->conv_weight[0], p->conv_bias[0], w.conv2_b_op, p->conv_bias[1], w.mid2, st)) return rc;
     if (nc == 3) {
-        hipLaunchKernelGGL(pack_conv_b_dev_kernel, dim3(288), dim3(256), 0, st, p->conv_weight[2], 128, 64, w.conv3_b_op);
-        WW_HIP(hipGetLastError());
+        if (int rc = launch<pack_conv_b_dev_kernel>(dim3(288), dim3(256), 0, st, p->conv_weight[2], 128, 64, w.conv3_b_op)) return rc;
         if (int rc = launch_cnn3_f32_store(w.mid2, n, width, w.conv3_b_op, p->conv_bias[2], w.pooled, w.mid3, st)) return rc;
     } else {
-        hipLaunchKernelGGL(pool_mid_kernel, dim3(int(n)), dim3(256), 0, st, w.mid2, int(n), width, w.pooled);
-        WW_HIP(hipGetLastError());
+        if (int rc = launch<pool_mid_kernel>(dim3(int(n)), dim3(256), 0, st, w.mid2, int(n), width, w.pooled)) return rc;
     }
     return launch_lstm_fc_train(w.pooled, n, c_last, p->lstm_weight_ih[0], p->lstm_bias_ih[0], p->lstm_bias_hh[0], p->lstm_weight_ih[1],
                                 p->lstm_bias_ih[1], p->lstm_bias_hh[1], p->fc_weight, p->fc_bias, w.lstm_packed, w.gates0, w.mask0, w.hd0,
@@ -832,14 +805,12 @@ int train_forward(const float* mel, int64_t n, int width, const ww_train_params*
 // partial[groups][len] -> the weight part and the bias part of the gradient
 static int reduce_to(const TrainWs& w, int groups, int len, int w_len, float* dw, float* db, int b_len, hipStream_t st) {
     (void)b_len;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3((len + 63) / 64 < 1024 ? (len + 63) / 64 : 1024), dim3(256), 0, st, w.partial, groups, len, w_len, dw, db);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<reduce_partials_kernel>(dim3((len + 63) / 64 < 1024 ? (len + 63) / 64 : 1024), dim3(256), 0, st, w.partial, groups, len, w_len, dw,
+                                          db);
 }
 
 int train_backward(const float* mel, int64_t n, int width, const ww_train_params* p, const float* dlogits, int mode, void* workspace,
                    int64_t workspace_bytes, const ww_train_grads* g, hipStream_t st) {
-    if (int rc = train_opt_in()) return rc;
     const int nc = p->n_conv, c_last = nc == 3 ? 128 : 64;
     const int cus = device_cu_count();
     const int grid = int(n < cus ? n : cus);         // one persistent workgroup per CU (117-149 KB of LDS each)
@@ -857,67 +828,61 @@ int train_backward(const float* mel, int64_t n, int width, const ww_train_params
     // the split-K scratch: the gradient-partial block, not yet in use at this point of the backward (largest need: 8 x (1024 x 256 + 1024) floats)
     float* gpart = w.partial;
     static_assert(int64_t(kMaxGroups) * kWg2Partial >= 8 * (1024 * 256 + 1024), "split-K scratch fits the partial block");
-    sgemm(dlogits, 1, 2, w.hd1, H, 1, g->fc_weight, H, 2, H, N, st, g->fc_bias, gpart);
-    sgemm(dlogits, 2, 1, p->fc_weight, H, 1, w.dhd1, H, N, H, 2, st);
-    // layer 1
-    hipLaunchKernelGGL(lstm_gates_bwd_kernel, dim3(1024), dim3(256), 0, st, w.dhd1, w.gates1, w.mask1, N, w.dg1);
-    sgemm(w.dg1, 1, 4 * H, w.hd0, H, 1, g->lstm_weight_ih[1], H, 4 * H, H, N, st, g->lstm_bias[1], gpart);   // [1024][256] = dg1^T hd0; bias = its A's row sums
-    sgemm(w.dg1, 4 * H, 1, p->lstm_weight_ih[1], H, 1, w.dhd0, H, N, H, 4 * H, st, nullptr, gpart);            // [n][256] = dg1 W_ih_l1
-    // layer 0
-    hipLaunchKernelGGL(lstm_gates_bwd_kernel, dim3(1024), dim3(256), 0, st, w.dhd0, w.gates0, w.mask0, N, w.dg0);
-    sgemm(w.dg0, 1, 4 * H, w.pooled, c_last, 1, g->lstm_weight_ih[0], c_last, 4 * H, c_last, N, st, g->lstm_bias[0], gpart);   // [1024][C] = dg0^T pooled
-    sgemm(w.dg0, 4 * H, 1, p->lstm_weight_ih[0], c_last, 1, w.dpooled, c_last, N, c_last, 4 * H, st, nullptr, gpart);      // [n][C] = dg0 W_ih_l0
+    if (int rc = sgemm(dlogits, 1, 2, w.hd1, H, 1, g->fc_weight, H, 2, H, N, st, g->fc_bias, gpart)) return rc;
+    if (int rc = sgemm(dlogits, 2, 1, p->fc_weight, H, 1, w.dhd1, H, N, H, 2, st)) return rc;
+    // layer 1: [1024][256] = dg1^T hd0 (bias = its A's row sums), then [n][256] = dg1 W_ih_l1
+    if (int rc = launch<lstm_gates_bwd_kernel>(dim3(1024), dim3(256), 0, st, w.dhd1, w.gates1, w.mask1, N, w.dg1)) return rc;
+    if (int rc = sgemm(w.dg1, 1, 4 * H, w.hd0, H, 1, g->lstm_weight_ih[1], H, 4 * H, H, N, st, g->lstm_bias[1], gpart)) return rc;
+    if (int rc = sgemm(w.dg1, 4 * H, 1, p->lstm_weight_ih[1], H, 1, w.dhd0, H, N, H, 4 * H, st, nullptr, gpart)) return rc;
+    // layer 0: [1024][C] = dg0^T pooled, then [n][C] = dg0 W_ih_l0
+    if (int rc = launch<lstm_gates_bwd_kernel>(dim3(1024), dim3(256), 0, st, w.dhd0, w.gates0, w.mask0, N, w.dg0)) return rc;
+    if (int rc = sgemm(w.dg0, 1, 4 * H, w.pooled, c_last, 1, g->lstm_weight_ih[0], c_last, 4 * H, c_last, N, st, g->lstm_bias[0], gpart)) return rc;
+    if (int rc = sgemm(w.dg0, 4 * H, 1, p->lstm_weight_ih[0], c_last, 1, w.dpooled, c_last, N, c_last, 4 * H, st, nullptr, gpart)) return rc;
     if (bits) {
         if (int rc = launch_gp_max(w.dpooled, 1.0f / float(kTH * width), n, nc, w.gp, w.dgh, st)) return rc;
     } else {
-        hipLaunchKernelGGL(scale_kernel, dim3(256), dim3(256), 0, st, w.dpooled, 1.0f / float(kTH * width), n * c_last, w.gp);
-        WW_HIP(hipGetLastError());
+        if (int rc = launch<scale_kernel>(dim3(256), dim3(256), 0, st, w.dpooled, 1.0f / float(kTH * width), n * c_last, w.gp)) return rc;
     }
     // conv stack, top down.  The last conv feeds the pool (rank-one gradient gp * [act > 0]); below it the gradient is dense.
     const float* w1 = p->conv_weight[0];
     const float* b1 = p->conv_bias[0];
-    if (nc == 3) {
-        if (!bits) hipLaunchKernelGGL(pack_dgrad_b_dev_kernel, dim3(288), dim3(256), 0, st, p->conv_weight[2], 128, 64, w.dgrad3_b_op);
-        if (bits) {
-            if (int rc = launch_conv3_wgrad_h(w.mid2, w.apow2, w.maskbits, w.gp, n, w.partial, g->conv_weight[2], g->conv_bias[2], grid, st)) return rc;
-        } else {
-            hipLaunchKernelGGL((conv_wgrad_kernel<64, 128, 4, false, false>), dim3(grid), dim3(512), kWg3Lds, st,
-                               mel, w.mid2, w.mid3, w.gp, N, width, w1, b1, w.partial);
-            WW_HIP(hipGetLastError());
-            if (int rc = reduce_to(w, grid, kWg3Partial, 128 * 64 * 9, g->conv_weight[2], g->conv_bias[2], 128, st)) return rc;
-        }
-        if (bits) {
-            if (int rc = launch_conv3_dgrad_h(w.mid2, w.maskbits, w.gp, p->conv_weight[2], w.dgh, n, w.dz2, dgrad_h_dzs(w.dgh, n), grid, st)) return rc;
-        } else
-            hipLaunchKernelGGL((conv_dgrad_kernel<64, 128, false, false>), dim3(grid), dim3(512), kDg3Lds, st,
-                               mel, w.mid2, w.mid3, w.gp, N, width, w1, b1, w.dgrad3_b_op, w.dz2);
-        WW_HIP(hipGetLastError());
+    if (nc == 3 && bits) {
+        if (int rc = launch_conv3_wgrad_h(w.mid2, w.apow2, w.maskbits, w.gp, n, w.partial, g->conv_weight[2], g->conv_bias[2], grid, st)) return rc;
+        if (int rc = launch_conv3_dgrad_h(w.mid2, w.maskbits, w.gp, p->conv_weight[2], w.dgh, n, w.dz2, dgrad_h_dzs(w.dgh, n), grid, st)) return rc;
+    } else if (nc == 3) {
+        if (int rc = launch<pack_dgrad_b_dev_kernel>(dim3(288), dim3(256), 0, st, p->conv_weight[2], 128, 64, w.dgrad3_b_op)) return rc;
+        if (int rc = launch<conv_wgrad_kernel<64, 128, 4, false, false>>(dim3(grid), dim3(512), kWg3Lds, st, mel, w.mid2, w.mid3, w.gp, N, width, w1,
+                                                                         b1, w.partial)) return rc;
+        if (int rc = reduce_to(w, grid, kWg3Partial, 128 * 64 * 9, g->conv_weight[2], g->conv_bias[2], 128, st)) return rc;
+        if (int rc = launch<conv_dgrad_kernel<64, 128, false, false>>(dim3(grid), dim3(512), kDg3Lds, st, mel, w.mid2, w.mid3, w.gp, N, width, w1, b1,
+                                                                      w.dgrad3_b_op, w.dz2)) return rc;
     }
-    if (!bits) hipLaunchKernelGGL(pack_dgrad_b_dev_kernel, dim3(72), dim3(256), 0, st, p->conv_weight[1], 64, 32, w.dgrad2_b_op);
+    if (!bits)
+        if (int rc = launch<pack_dgrad_b_dev_kernel>(dim3(72), dim3(256), 0, st, p->conv_weight[1], 64, 32, w.dgrad2_b_op)) return rc;
     if (nc == 3 && bits) {
         if (int rc = launch_conv2_wgrad_h_dense(mel, w.dz2, dgrad_h_dzs(w.dgh, n), n, width, w.wpk, w.partial, grid, st)) return rc;
-    } else if (nc == 3)
-        hipLaunchKernelGGL((conv_wgrad_kernel<32, 64, 8, true, true>), dim3(grid), dim3(512), kWg2Lds, st,
-                           mel, static_cast<const float*>(nullptr), w.dz2, w.gp, N, width, w1, b1, w.partial);
-    else if (split) {
+    } else if (nc == 3) {
+        if (int rc = launch<conv_wgrad_kernel<32, 64, 8, true, true>>(dim3(grid), dim3(512), kWg2Lds, st, mel, nullptr, w.dz2, w.gp, N, width, w1, b1,
+                                                                      w.partial)) return rc;
+    } else if (split) {
         if (int rc = launch_conv2_wgrad_h(mel, w.maskbits, w.gp, n, width, w.wpk, w.partial, grid, st)) return rc;
-    } else
-        hipLaunchKernelGGL((conv_wgrad_kernel<32, 64, 8, false, true>), dim3(grid), dim3(512), kWg2Lds, st,
-                           mel, static_cast<const float*>(nullptr), w.mid2, w.gp, N, width, w1, b1, w.partial);
-    WW_HIP(hipGetLastError());
+    } else {
+        if (int rc = launch<conv_wgrad_kernel<32, 64, 8, false, true>>(dim3(grid), dim3(512), kWg2Lds, st, mel, nullptr, w.mid2, w.gp, N, width, w1, b1,
+                                                                       w.partial)) return rc;
+    }
     if (int rc = reduce_to(w, grid, kWg2Partial, 64 * 32 * 9, g->conv_weight[1], g->conv_bias[1], 64, st)) return rc;
     if (nc == 3 && bits) {
         if (int rc = launch_conv2_dgrad_h_dense(mel, w.dz2, dgrad_h_dzs(w.dgh, n), w.bits1, p->conv_weight[1], dgrad_h_scratch2(w.dgh, n), n, width,
                                                 w.partial, grid, st)) return rc;
-    } else if (nc == 3)
-        hipLaunchKernelGGL((conv_dgrad_kernel<32, 64, true, true>), dim3(grid), dim3(256), kDg2Lds, st,
-                           mel, static_cast<const float*>(nullptr), w.dz2, w.gp, N, width, w1, b1, w.dgrad2_b_op, w.partial);
-    else if (split) {
+    } else if (nc == 3) {
+        if (int rc = launch<conv_dgrad_kernel<32, 64, true, true>>(dim3(grid), dim3(256), kDg2Lds, st, mel, nullptr, w.dz2, w.gp, N, width, w1, b1,
+                                                                   w.dgrad2_b_op, w.partial)) return rc;
+    } else if (split) {
         if (int rc = launch_conv2_dgrad_h(mel, w.maskbits, w.bits1, w.gp, p->conv_weight[1], w.dgh, n, width, w.partial, grid, st)) return rc;
-    } else
-        hipLaunchKernelGGL((conv_dgrad_kernel<32, 64, false, true>), dim3(grid), dim3(256), kDg2Lds, st,
-                           mel, static_cast<const float*>(nullptr), w.mid2, w.gp, N, width, w1, b1, w.dgrad2_b_op, w.partial);
-    WW_HIP(hipGetLastError());
+    } else {
+        if (int rc = launch<conv_dgrad_kernel<32, 64, false, true>>(dim3(grid), dim3(256), kDg2Lds, st, mel, nullptr, w.mid2, w.gp, N, width, w1, b1,
+                                                                    w.dgrad2_b_op, w.partial)) return rc;
+    }
     if (int rc = reduce_to(w, grid, kDgPartial, 32 * 9, g->conv_weight[0], g->conv_bias[0], 32, st)) return rc;
     note_workspace_backward(workspace);
     return WW_OK;

@@ -14,7 +14,6 @@
 // 32-term sum once: scripts/ubench/mfma_round.hip).  16x the matrix rate of v_mfma_f32_32x32x2_f32 at 2-3 instructions per product.
 //
 // The masks travel as BITS written by the forward kernels: maskbits[b][row][col] = COUT bits, bits1[b][row][col] = conv1's 32 sign bits.
-#include <mutex>
 
 #include "ww_conv1.h"
 #include "ww_internal.h"
@@ -175,14 +174,13 @@ __global__ void copy_floats_kernel(const float* __restrict__ src, float* __restr
 int launch_pack_conv_h_dev(const ww_train_params* p, float* img, hipStream_t st) {
     const PackedLayout L = packed_layout(p->n_conv);
     const PackOffsets o{L.conv1_h, L.conv1_hs, L.conv1_b, L.conv2_hw, L.conv2_hws, L.conv2_b, L.range};
-    hipLaunchKernelGGL(pack_conv1_h_dev_kernel, dim3(1), dim3(256), 0, st, p->conv_weight[0], p->conv_bias[0], p->conv_bias[1], img, o);
-    hipLaunchKernelGGL(pack_conv_wino_dev_kernel<32>, dim3(64), dim3(128), 0, st, p->conv_weight[1], img, L.conv2_hw, L.conv2_hws, L.range + 2);
-    if (p->n_conv == 3) {
-        hipLaunchKernelGGL(pack_conv_wino_dev_kernel<64>, dim3(128), dim3(256), 0, st, p->conv_weight[2], img, L.conv3_hw, L.conv3_hws, int64_t(-1));
-        hipLaunchKernelGGL(copy_floats_kernel, dim3(1), dim3(128), 0, st, p->conv_bias[2], img + L.conv3_b, 128);
-    }
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    if (int rc = launch<pack_conv1_h_dev_kernel>(dim3(1), dim3(256), 0, st, p->conv_weight[0], p->conv_bias[0], p->conv_bias[1], img, o)) return rc;
+    if (int rc = launch<pack_conv_wino_dev_kernel<32>>(dim3(64), dim3(128), 0, st, p->conv_weight[1], img, L.conv2_hw, L.conv2_hws, L.range + 2))
+        return rc;
+    if (p->n_conv != 3) return WW_OK;
+    if (int rc = launch<pack_conv_wino_dev_kernel<64>>(dim3(128), dim3(256), 0, st, p->conv_weight[2], img, L.conv3_hw, L.conv3_hws, int64_t(-1)))
+        return rc;
+    return launch<copy_floats_kernel>(dim3(1), dim3(128), 0, st, p->conv_bias[2], img + L.conv3_b, 128);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1296,9 +1294,7 @@ __global__ void decode_mask_image_kernel(const uint8_t* __restrict__ img, int64_
     }
 }
 int launch_decode_mask_image(const uint32_t* img, int64_t n, int C, uint8_t* out, hipStream_t st) {
-    hipLaunchKernelGGL(decode_mask_image_kernel, dim3(1024), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(img), n, C, out);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<decode_mask_image_kernel>(dim3(1024), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(img), n, C, out);
 }
 
 // test / diagnostic: a 64-channel channels-last image as plain float32 out[b][row][c][col].  scale == nullptr: src is float32
@@ -1319,64 +1315,35 @@ __global__ void decode_channels_last_kernel(const void* __restrict__ src, const 
     }
 }
 int launch_decode_channels_last(const float* src, const float* scale, int64_t n, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(decode_channels_last_kernel, dim3(1024), dim3(256), 0, st, static_cast<const void*>(src), scale, n, out);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<decode_channels_last_kernel>(dim3(1024), dim3(256), 0, st, static_cast<const void*>(src), scale, n, out);
 }
 
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-static int train_h_opt_in() {
-    static std::mutex mu;
-    static bool done[64] = {};
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    WW_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(WW_EINVAL, "device ordinal out of range");
-    if (done[dev]) return WW_OK;
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_wgrad_h_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, WgH::kLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_wgrad_h_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, WgHT<true>::kLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_dgrad_h_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, DgH::kLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_dgrad_h_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, DgHT<true>::kLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_wgrad_h_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, Wg3H::kLds));
-    WW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_dgrad_h_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, Dg3H::kLds));
-    done[dev] = true;
-    return WW_OK;
-}
-
 int launch_conv2_wgrad_h(const float* mel, const uint32_t* maskbits, const float* gp, int64_t n, int width, const float* packed,
                          float* partial, int grid, hipStream_t st) {
-    if (int rc = train_h_opt_in()) return rc;
     const PackedLayout P = packed_layout(2);
-    hipLaunchKernelGGL(conv2_wgrad_h_kernel<false>, dim3(grid), dim3(768), WgH::kLds, st, mel, reinterpret_cast<const uint8_t*>(maskbits), gp, int(n),
-                       width, reinterpret_cast<const u32x4*>(packed + P.conv1_h), packed + P.conv1_hs, packed + P.conv1_b, packed + P.range,
-                       partial);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<conv2_wgrad_h_kernel<false>>(dim3(grid), dim3(768), WgH::kLds, st, mel, reinterpret_cast<const uint8_t*>(maskbits), gp, int(n),
+                                               width, reinterpret_cast<const u32x4*>(packed + P.conv1_h), packed + P.conv1_hs, packed + P.conv1_b,
+                                               packed + P.range, partial);
 }
 
 // conv2 weight gradient of the 3-conv model from the pre-split dense gradient dz2h (conv3_dgrad_h_kernel)
 int launch_conv2_wgrad_h_dense(const float* mel, const float* dz2h, const float* dzs, int64_t n, int width, const float* packed, float* partial,
                                int grid, hipStream_t st) {
-    if (int rc = train_h_opt_in()) return rc;
     const PackedLayout P = packed_layout(3);
-    hipLaunchKernelGGL(conv2_wgrad_h_kernel<true>, dim3(grid), dim3(768), WgHT<true>::kLds, st, mel, reinterpret_cast<const uint8_t*>(dz2h), dzs,
-                       int(n), width, reinterpret_cast<const u32x4*>(packed + P.conv1_h), packed + P.conv1_hs, packed + P.conv1_b,
-                       packed + P.range, partial);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    return launch<conv2_wgrad_h_kernel<true>>(dim3(grid), dim3(768), WgHT<true>::kLds, st, mel, reinterpret_cast<const uint8_t*>(dz2h), dzs, int(n),
+                                              width, reinterpret_cast<const u32x4*>(packed + P.conv1_h), packed + P.conv1_hs, packed + P.conv1_b,
+                                              packed + P.range, partial);
 }
 
 // conv3 weight gradient of the 3-conv model: partial [grid][128*64*9 + 128] (lane order) -> dw [128][64][3][3], db [128]
 int launch_conv3_wgrad_h(const float* act2, const float* apow2, const uint32_t* maskbits, const float* gp, int64_t n, float* partial,
                          float* dw, float* db, int grid, hipStream_t st) {
-    if (int rc = train_h_opt_in()) return rc;
-    hipLaunchKernelGGL(conv3_wgrad_h_kernel, dim3(grid), dim3(768), Wg3H::kLds, st, act2, apow2, reinterpret_cast<const uint8_t*>(maskbits), gp,
-                       int(n), partial);
-    hipLaunchKernelGGL(reduce_wgrad3_h_kernel, dim3(1024), dim3(256), 0, st, partial, grid, dw, db);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    if (int rc = launch<conv3_wgrad_h_kernel>(dim3(grid), dim3(768), Wg3H::kLds, st, act2, apow2, reinterpret_cast<const uint8_t*>(maskbits), gp,
+                                              int(n), partial)) return rc;
+    return launch<reduce_wgrad3_h_kernel>(dim3(1024), dim3(256), 0, st, partial, grid, dw, db);
 }
 
 // dgrad scratch (floats): wp [2*18*64*8 | 4*2*18*64*8], wmax [4], gpmax [n]
@@ -1388,52 +1355,41 @@ float* dgrad_h_dzs(float* scratch, int64_t n) { return dgrad_h_scratch2(scratch,
 
 int launch_gp_max(const float* dpooled, float s, int64_t n, int n_conv, float* gp, float* scratch, hipStream_t st) {
     float* gpmax = scratch + wp_floats(n_conv) + 4;
-    if (n_conv == 3) hipLaunchKernelGGL(gp_max128_kernel, dim3(unsigned((n + 3) / 4)), dim3(256), 0, st, dpooled, s, int(n), gp, gpmax);
-    else hipLaunchKernelGGL(gp_max_kernel, dim3(unsigned((n + 3) / 4)), dim3(256), 0, st, dpooled, s, int(n), gp, gpmax);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    if (n_conv == 3) return launch<gp_max128_kernel>(dim3(unsigned((n + 3) / 4)), dim3(256), 0, st, dpooled, s, int(n), gp, gpmax);
+    return launch<gp_max_kernel>(dim3(unsigned((n + 3) / 4)), dim3(256), 0, st, dpooled, s, int(n), gp, gpmax);
 }
 
 int launch_conv3_dgrad_h(const float* act2, const uint32_t* maskbits, const float* gp, const float* w3, float* scratch, int64_t n, float* dz2h,
                          float* dzs, int grid, hipStream_t st) {
-    if (int rc = train_h_opt_in()) return rc;
     float* wp = scratch;
     float* wmax = scratch + wp_floats(3);
     float* gpmax = wmax + 4;
     WW_HIP(hipMemsetAsync(wmax, 0, 16, st));
-    hipLaunchKernelGGL(pack_dgrad3_h_dev_kernel, dim3(144), dim3(256), 0, st, w3, wp, reinterpret_cast<unsigned int*>(wmax));
-    hipLaunchKernelGGL(conv3_dgrad_h_kernel, dim3(grid), dim3(512), Dg3H::kLds, st, act2, reinterpret_cast<const uint8_t*>(maskbits), gp, gpmax,
-                       wp, wmax, int(n), reinterpret_cast<_Float16*>(dz2h), dzs);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    if (int rc = launch<pack_dgrad3_h_dev_kernel>(dim3(144), dim3(256), 0, st, w3, wp, reinterpret_cast<unsigned int*>(wmax))) return rc;
+    return launch<conv3_dgrad_h_kernel>(dim3(grid), dim3(512), Dg3H::kLds, st, act2, reinterpret_cast<const uint8_t*>(maskbits), gp, gpmax, wp, wmax,
+                                        int(n), reinterpret_cast<_Float16*>(dz2h), dzs);
 }
 
 int launch_conv2_dgrad_h(const float* mel, const uint32_t* maskbits, const uint32_t* bits1, const float* gp, const float* w2, float* scratch,
                          int64_t n, int width, float* partial, int grid, hipStream_t st) {
-    if (int rc = train_h_opt_in()) return rc;
     float* wp = scratch;
     float* wmax = scratch + wp_floats(2);
     float* gpmax = wmax + 4;
     WW_HIP(hipMemsetAsync(wmax, 0, 16, st));
-    hipLaunchKernelGGL(pack_dgrad_h_dev_kernel, dim3(36), dim3(256), 0, st, w2, wp, reinterpret_cast<unsigned int*>(wmax));
-    hipLaunchKernelGGL(conv2_dgrad_h_kernel<false>, dim3(grid), dim3(512), DgH::kLds, st, mel, reinterpret_cast<const uint8_t*>(maskbits), bits1, gp,
-                       gpmax, wp, wmax, int(n), width, partial);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    if (int rc = launch<pack_dgrad_h_dev_kernel>(dim3(36), dim3(256), 0, st, w2, wp, reinterpret_cast<unsigned int*>(wmax))) return rc;
+    return launch<conv2_dgrad_h_kernel<false>>(dim3(grid), dim3(512), DgH::kLds, st, mel, reinterpret_cast<const uint8_t*>(maskbits), bits1, gp,
+                                               gpmax, wp, wmax, int(n), width, partial);
 }
 
 // conv2 data gradient + conv1 weight gradient of the 3-conv model from the pre-split dense gradient dz2h; scratch2: wp [2*18*64*8] + wmax [4]
 int launch_conv2_dgrad_h_dense(const float* mel, const float* dz2h, const float* dzs, const uint32_t* bits1, const float* w2, float* scratch2,
                                int64_t n, int width, float* partial, int grid, hipStream_t st) {
-    if (int rc = train_h_opt_in()) return rc;
     float* wp = scratch2;
     float* wmax = scratch2 + wp_floats(2);
     WW_HIP(hipMemsetAsync(wmax, 0, 16, st));
-    hipLaunchKernelGGL(pack_dgrad_h_dev_kernel, dim3(36), dim3(256), 0, st, w2, wp, reinterpret_cast<unsigned int*>(wmax));
-    hipLaunchKernelGGL(conv2_dgrad_h_kernel<true>, dim3(grid), dim3(512), DgHT<true>::kLds, st, mel, reinterpret_cast<const uint8_t*>(dz2h), bits1,
-                       static_cast<const float*>(nullptr), dzs, wp, wmax, int(n), width, partial);
-    WW_HIP(hipGetLastError());
-    return WW_OK;
+    if (int rc = launch<pack_dgrad_h_dev_kernel>(dim3(36), dim3(256), 0, st, w2, wp, reinterpret_cast<unsigned int*>(wmax))) return rc;
+    return launch<conv2_dgrad_h_kernel<true>>(dim3(grid), dim3(512), DgHT<true>::kLds, st, mel, reinterpret_cast<const uint8_t*>(dz2h), bits1,
+                                              nullptr, dzs, wp, wmax, int(n), width, partial);
 }
 
 }  // namespace ww
