@@ -1035,6 +1035,56 @@ typedef struct ww_quant_tensor {
 } ww_quant_tensor;   /* 64 bytes, DEVICE pointers */
 WW_API int ww_quant_weights_f32(const ww_quant_tensor* tensors_host, int64_t n_tensors, int bits, ww_stream_t stream);
 
+/* ---- clipped scales and the straight-through estimator: quantisation-aware training ---------------------- */
+/* A clipped scale gives up a row's outliers for a finer step.  Candidate j in 0 .. WW_QUANT_CLIP_STEPS - 1 has the fraction
+ * f_j = (64 - j) / 64, exact in float32: 1.0 down to 17/64.  With amax and qmax as above, every operation float32 and rounded once:
+ *   scale_j = max((amax * f_j) / qmax, 2^-126)         one multiplication, one division
+ *   r       = rint(w / scale_j)                        ties to even; a non-finite w counts as 0 and goes to bad
+ *   sat     = |r| > qmax                               the clamp moved this element
+ *   q       = clamp(r, -qmax, qmax);  deq = (float)q * scale_j
+ * j = 0 multiplies amax by 1.0f: it is ww_quant_weights_f32 bit for bit.
+ * All three entry points below are one launch over up to WW_QUANT_MAX_TENSORS tensors with the table in the kernel arguments: no
+ * atomics, no wait, no allocation, no row split across workgroups (rows of up to 1024 elements take a wave, longer rows a workgroup),
+ * the same bytes for the same call.  Arguments are checked before any HIP call (WW_EINVAL naming the field): what
+ * ww_quant_weights_f32 checks for the fields the two structs share, and the new fields as said below.
+ *
+ * ww_quant_weights_clip_f32: ww_quant_weights_f32 with one clip index per row, uint8 in DEVICE memory (an index above 47 counts as 47;
+ * it is not read on the host), and one more optional output: sat [rows], the row's saturated elements.  clip not NULL; sat 4-byte aligned.
+ *
+ * ww_quant_clip_search_f32: per row, cand_err[row][j] = the float64 sum of (w - deq_j)^2 over the row's finite elements for all 48
+ * candidates, in ww_quant_weights_f32's order of summation (so cand_err[row][0] is its err[row][1] bit for bit); clip[row] = the smallest j
+ * whose cand_err is the minimum of the written values; scale[row] = that candidate's scale.  cand_err may be NULL; q, deq, err, bad and
+ * sat are not read or written.  clip (written here) and scale not NULL; cand_err 8-byte aligned.  A workgroup per long row carries 48
+ * float64 sums per thread: per-tensor mode is slow (scripts/bench_qat.py measures it) and is not on a per-step path.
+ *
+ * ww_quant_ste_f32: the straight-through estimator with clipping.  tensors[k] = { w, scale (read), g (modified in place), rows, cols }:
+ * where w is finite and |rint(w / scale[row])| > qmax, g becomes +0.0 (a select: a NaN gradient there becomes 0 too); everywhere else,
+ * every non-finite w included, g keeps its bits.  w, scale, g not NULL and 4-byte aligned; g must not overlap w. */
+#define WW_QUANT_CLIP_STEPS 48
+typedef struct ww_quant_clip_tensor {
+    const float* w;   /* [rows][cols], read only */
+    float* scale;     /* [rows] */
+    int8_t* q;        /* [rows][cols] or NULL */
+    float* deq;       /* [rows][cols] or NULL */
+    double* err;      /* [rows][3] or NULL */
+    int32_t* bad;     /* [rows] or NULL */
+    uint8_t* clip;    /* [rows]: read by ww_quant_weights_clip_f32, written by ww_quant_clip_search_f32 */
+    int32_t* sat;     /* [rows] or NULL: saturated elements of the row (ww_quant_weights_clip_f32) */
+    double* cand_err; /* [rows][WW_QUANT_CLIP_STEPS] or NULL (ww_quant_clip_search_f32) */
+    int64_t rows;
+    int64_t cols;
+} ww_quant_clip_tensor;   /* 88 bytes, DEVICE pointers */
+typedef struct ww_quant_ste_tensor {
+    const float* w;     /* [rows][cols], read only */
+    const float* scale; /* [rows], read only: what the clipped launch stored */
+    float* g;           /* [rows][cols], modified in place */
+    int64_t rows;
+    int64_t cols;
+} ww_quant_ste_tensor;    /* 40 bytes, DEVICE pointers */
+WW_API int ww_quant_weights_clip_f32(const ww_quant_clip_tensor* tensors_host, int64_t n_tensors, int bits, ww_stream_t stream);
+WW_API int ww_quant_clip_search_f32(const ww_quant_clip_tensor* tensors_host, int64_t n_tensors, int bits, ww_stream_t stream);
+WW_API int ww_quant_ste_f32(const ww_quant_ste_tensor* tensors_host, int64_t n_tensors, int bits, ww_stream_t stream);
+
 /* ---- clip evaluation: confusion, operating points and a margin histogram as device counters ---------- */
 /* What notebook cell 17 collects clip by clip on the host (`all_preds.extend(predicted.cpu().numpy())`) kept as integer counters in
  * device memory: one launch per batch adds the batch to the record in stream order, nothing waits for the device, and the record is read

@@ -172,7 +172,19 @@ class QuantTensor(C.Structure):
                 ("rows", C.c_int64), ("cols", C.c_int64)]
 
 
+class QuantClipTensor(C.Structure):
+    """struct ww_quant_clip_tensor (include/wakeword_amd.h): ww_quant_tensor's fields, then clip, sat and cand_err, DEVICE pointers."""
+    _fields_ = [("w", C.c_void_p), ("scale", C.c_void_p), ("q", C.c_void_p), ("deq", C.c_void_p), ("err", C.c_void_p), ("bad", C.c_void_p),
+                ("clip", C.c_void_p), ("sat", C.c_void_p), ("cand_err", C.c_void_p), ("rows", C.c_int64), ("cols", C.c_int64)]
+
+
+class QuantSteTensor(C.Structure):
+    """struct ww_quant_ste_tensor (include/wakeword_amd.h): one entry of the straight-through estimator's table, DEVICE pointers."""
+    _fields_ = [("w", C.c_void_p), ("scale", C.c_void_p), ("g", C.c_void_p), ("rows", C.c_int64), ("cols", C.c_int64)]
+
+
 QUANT_MAX_TENSORS = 16
+QUANT_CLIP_STEPS = 48
 METRICS_MAX_THRESHOLDS, METRICS_BINS = 8, 4096
 
 
@@ -334,6 +346,9 @@ PROTOTYPES = {
     "ww_grad_norm_workspace_bytes": (C.c_int64, [C.POINTER(AdamTensor), C.c_int64]),
     "ww_grad_norm_f32": (C.c_int, [C.POINTER(AdamTensor), C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ww_quant_weights_f32": (C.c_int, [C.POINTER(QuantTensor), C.c_int64, C.c_int, C.c_void_p]),
+    "ww_quant_weights_clip_f32": (C.c_int, [C.POINTER(QuantClipTensor), C.c_int64, C.c_int, C.c_void_p]),
+    "ww_quant_clip_search_f32": (C.c_int, [C.POINTER(QuantClipTensor), C.c_int64, C.c_int, C.c_void_p]),
+    "ww_quant_ste_f32": (C.c_int, [C.POINTER(QuantSteTensor), C.c_int64, C.c_int, C.c_void_p]),
     "ww_clip_metrics_bytes": (C.c_int64, []),
     "ww_clip_metrics_margin_host": (C.c_float, [C.c_float]),
     "ww_clip_metrics_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -11,7 +11,16 @@
 //                  Per element (include/wakeword_amd.h has the rule): two correctly rounded float32 operations, written with the explicit
 //                  round-to-nearest intrinsics so no reciprocal and no contraction can take their place.  The error sums are float64 fmas in
 //                  an order set by the mapping alone: the same input gives the same bytes.
-// Memory- and latency-bound; the models' weights are 0.6 M and 1.0 M floats.  Not on a per-step path.
+//   quant_kernel<true>   the same kernel with one clip index per row (uint8, device memory) and a per-row count of the elements the clamp
+//                  moved (ww_quant_weights_clip_f32): scale_j = max((amax * f_j) / qmax, 2^-126), f_j = (64 - j) / 64.
+//                  j = 0 multiplies by 1.0f: the bits of quant_kernel<false>.  This is the launch in front of a QAT step's forward.
+//   search_kernel  all WW_QUANT_CLIP_STEPS candidates of a row: the float64 sum of (w - deq_j)^2 per candidate in quant_kernel's own
+//                  lane mapping and order of summation (candidate 0 IS its err[row][1]), the first argmin and its scale.  A wave keeps its
+//                  row in registers and loops over the candidates; a workgroup per long row makes one pass for amax and one that carries 48
+//                  float64 sums per thread (the 48 scales sit in LDS), folded through LDS in wave order.  Calibration, not a per-step path.
+//   ste_kernel     the straight-through estimator with clipping: g = +0.0 where a finite w lies outside the clipped range (a store, so a
+//                  NaN gradient there goes too); every other g is neither read nor written.
+// Memory- and latency-bound; the models' weights are 0.6 M and 1.0 M floats.
 #include "ww_internal.h"
 
 namespace ww {
@@ -23,12 +32,18 @@ constexpr int kQuantWaveCols = 1024;                         // the longest row 
 constexpr int kQuantPerLane = kQuantWaveCols / 64;
 constexpr int kQuantMax = WW_QUANT_MAX_TENSORS;
 
-struct QuantTable {
-    ww_quant_tensor t[kQuantMax];
+constexpr int kClipSteps = WW_QUANT_CLIP_STEPS;
+
+template <class Tensor>
+struct QuantTableOf {
+    Tensor t[kQuantMax];
     int32_t first_block[kQuantMax + 1];                     // prefix sums of the tensors' block counts
     int32_t n_tensors;
     float qmax;                                             // 2^(bits - 1) - 1
 };
+using QuantTable = QuantTableOf<ww_quant_tensor>;
+using ClipTable = QuantTableOf<ww_quant_clip_tensor>;
+using SteTable = QuantTableOf<ww_quant_ste_tensor>;
 
 __device__ __forceinline__ float qwave_max(float x) {
 #pragma unroll
@@ -54,17 +69,21 @@ __device__ __forceinline__ int qwave_sum(int x) {
 __device__ __forceinline__ float finite_abs(float w) { return isfinite(w) ? fabsf(w) : 0.0f; }
 
 __device__ __forceinline__ float scale_of(float amax, float qmax) { return fmaxf(__fdiv_rn(amax, qmax), 0x1p-126f); }
+// Candidate j of the clipped rule: the fraction (64 - j) / 64 is exact, an index past the last candidate counts as the last.
+__device__ __forceinline__ float clip_fraction(int j) { return __fmul_rn(float(64 - min(j, kClipSteps - 1)), 0x1p-6f); }
+__device__ __forceinline__ float scale_of(float amax, float fraction, float qmax) { return scale_of(__fmul_rn(amax, fraction), qmax); }
 
 // What one lane gathers over its elements: the float64 sums of w^2 and (w - deq)^2, the largest |w - deq|, the non-finite count.
 struct QuantAcc {
     double sw = 0.0, se = 0.0, emax = 0.0;
-    int bad = 0;
+    int bad = 0, sat = 0;                                   // sat: elements the clamp moved (always 0 under the unclipped scale)
 };
 
 // One element.  A non-finite w quantises to 0, is counted, and enters no sum.
 __device__ __forceinline__ void quant_one(float w, float scale, float qmax, int& q, float& deq, QuantAcc& acc) {
     const bool fin = isfinite(w);
     float r = rintf(__fdiv_rn(fin ? w : 0.0f, scale));     // ties to even
+    acc.sat += fabsf(r) > qmax ? 1 : 0;
     r = fminf(fmaxf(r, -qmax), qmax);
     q = int(r);
     deq = __fmul_rn(float(q), scale);
@@ -78,18 +97,22 @@ __device__ __forceinline__ void quant_one(float w, float scale, float qmax, int&
     }
 }
 
-__device__ __forceinline__ int tensor_of(const QuantTable& tab, int block) {
+template <class Table>
+__device__ __forceinline__ int tensor_of(const Table& tab, int block) {
     int k = 0;
     for (int j = 1; j < tab.n_tensors; ++j) k = tab.first_block[j] <= block ? j : k;
     return k;
 }
 
-__global__ __launch_bounds__(kQuantThreads) void quant_kernel(const QuantTable tab) {
+// kClip: the table's tensors carry a clip index per row (read) and a saturation count per row (written, optional)
+template <bool kClip>
+__global__ __launch_bounds__(kQuantThreads) void quant_kernel(const std::conditional_t<kClip, ClipTable, QuantTable> tab) {
     __shared__ float red_amax[kQuantWaves];
     __shared__ double red_d[3][kQuantWaves];
     __shared__ int red_bad[kQuantWaves];
+    __shared__ int red_sat[kQuantWaves];
     const int k = tensor_of(tab, int(blockIdx.x));
-    const ww_quant_tensor t = tab.t[k];
+    const auto t = tab.t[k];
     const float qmax = tab.qmax;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t blk = int64_t(int(blockIdx.x) - tab.first_block[k]);
@@ -110,7 +133,9 @@ __global__ __launch_bounds__(kQuantThreads) void quant_kernel(const QuantTable t
             amax = fmaxf(amax, finite_abs(v[j]));
         }
         amax = qwave_max(amax);
-        const float scale = scale_of(amax, qmax);
+        float scale;
+        if constexpr (kClip) scale = scale_of(amax, clip_fraction(t.clip[row]), qmax);
+        else scale = scale_of(amax, qmax);
         QuantAcc acc;
 #pragma unroll
         for (int j = 0; j < kQuantPerLane; ++j) {
@@ -129,6 +154,10 @@ __global__ __launch_bounds__(kQuantThreads) void quant_kernel(const QuantTable t
             t.scale[row] = scale;
             if (t.err) { t.err[3 * row] = sw; t.err[3 * row + 1] = se; t.err[3 * row + 2] = emax; }
             if (t.bad) t.bad[row] = bad;
+        }
+        if constexpr (kClip) {
+            const int sat = qwave_sum(acc.sat);
+            if (lane == 0 && t.sat) t.sat[row] = sat;
         }
         return;
     }
@@ -158,7 +187,9 @@ __global__ __launch_bounds__(kQuantThreads) void quant_kernel(const QuantTable t
     amax = red_amax[0];
 #pragma unroll
     for (int j = 1; j < kQuantWaves; ++j) amax = fmaxf(amax, red_amax[j]);
-    const float scale = scale_of(amax, qmax);
+    float scale;
+    if constexpr (kClip) scale = scale_of(amax, clip_fraction(t.clip[row]), qmax);
+    else scale = scale_of(amax, qmax);
     QuantAcc acc;
     for (int64_t e0 = 4 * int64_t(tid); e0 < cols; e0 += 4 * kQuantThreads) {
         const bool whole = e0 + 4 <= cols;
@@ -199,6 +230,10 @@ __global__ __launch_bounds__(kQuantThreads) void quant_kernel(const QuantTable t
     const double sw = qwave_sum(acc.sw), se = qwave_sum(acc.se), emax = qwave_max(acc.emax);
     const int bad = qwave_sum(acc.bad);
     if (lane == 0) { red_d[0][wave] = sw; red_d[1][wave] = se; red_d[2][wave] = emax; red_bad[wave] = bad; }
+    if constexpr (kClip) {
+        const int sat = qwave_sum(acc.sat);
+        if (lane == 0) red_sat[wave] = sat;
+    }
     __syncthreads();
     if (tid == 0) {
         double a = red_d[0][0], b = red_d[1][0], c = red_d[2][0];
@@ -207,33 +242,239 @@ __global__ __launch_bounds__(kQuantThreads) void quant_kernel(const QuantTable t
         t.scale[row] = scale;
         if (t.err) { t.err[3 * row] = a; t.err[3 * row + 1] = b; t.err[3 * row + 2] = c; }
         if (t.bad) t.bad[row] = nb;
+        if constexpr (kClip) {
+            int ns = red_sat[0];
+            for (int j = 1; j < kQuantWaves; ++j) ns += red_sat[j];
+            if (t.sat) t.sat[row] = ns;
+        }
+    }
+}
+
+// (w - deq)^2 of one element under `scale`, added to `se` as quant_one adds it to its sum: the one definition, the other sums unused.
+__device__ __forceinline__ double add_sq_err(float w, float scale, float qmax, double se) {
+    QuantAcc acc;
+    acc.se = se;
+    int q;
+    float deq;
+    quant_one(w, scale, qmax, q, deq, acc);
+    return acc.se;
+}
+
+// The clip search: quant_kernel's two mappings, element for element and sum for sum, over all kClipSteps candidates of a row.
+__global__ __launch_bounds__(kQuantThreads) void search_kernel(const ClipTable tab) {
+    __shared__ float red_amax[kQuantWaves];
+    __shared__ float cand_scale[kClipSteps];
+    __shared__ double red_c[kClipSteps][kQuantWaves];
+    const int k = tensor_of(tab, int(blockIdx.x));
+    const ww_quant_clip_tensor t = tab.t[k];
+    const float qmax = tab.qmax;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t blk = int64_t(int(blockIdx.x) - tab.first_block[k]);
+    const int64_t cols = t.cols;
+
+    if (cols <= kQuantWaveCols) {
+        // ---- a wave per row: the row stays in registers, the candidates are a loop ----
+        const int64_t row = blk * kQuantWaves + wave;
+        if (row >= t.rows) return;
+        const int64_t base = row * cols;
+        const int n = int(cols);
+        float v[kQuantPerLane];
+        float amax = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kQuantPerLane; ++j) {
+            const int c = lane + 64 * j;
+            v[j] = c < n ? t.w[base + c] : 0.0f;
+            amax = fmaxf(amax, finite_abs(v[j]));
+        }
+        amax = qwave_max(amax);
+        double best = 0.0;
+        float best_scale = 0.0f;
+        int best_c = 0;
+#pragma unroll 1
+        for (int c = 0; c < kClipSteps; ++c) {
+            const float scale = scale_of(amax, clip_fraction(c), qmax);
+            double se = 0.0;
+#pragma unroll
+            for (int j = 0; j < kQuantPerLane; ++j)
+                if (lane + 64 * j < n) se = add_sq_err(v[j], scale, qmax, se);
+            se = qwave_sum(se);                             // the same value in every lane
+            if (lane == 0 && t.cand_err) t.cand_err[row * kClipSteps + c] = se;
+            if (c == 0 || se < best) { best = se; best_scale = scale; best_c = c; }     // strictly smaller: the first minimum stays
+        }
+        if (lane == 0) { t.clip[row] = uint8_t(best_c); t.scale[row] = best_scale; }
+        return;
+    }
+
+    // ---- a workgroup per row: amax, then ONE pass with a float64 sum per candidate and thread ----
+    const int64_t row = blk;
+    const float* __restrict__ w = t.w + row * cols;
+    const bool w_wide = (reinterpret_cast<uintptr_t>(w) & 15) == 0;
+    float amax = 0.0f;
+#pragma unroll 4
+    for (int64_t e0 = 4 * int64_t(tid); e0 < cols; e0 += 4 * kQuantThreads) {
+        if (w_wide && e0 + 4 <= cols) {
+            const float4 x = *reinterpret_cast<const float4*>(w + e0);
+            amax = fmaxf(fmaxf(amax, finite_abs(x.x)), fmaxf(finite_abs(x.y), fmaxf(finite_abs(x.z), finite_abs(x.w))));
+        } else {
+            for (int i = 0; i < 4; ++i)
+                if (e0 + i < cols) amax = fmaxf(amax, finite_abs(w[e0 + i]));
+        }
+    }
+    amax = qwave_max(amax);
+    if (lane == 0) red_amax[wave] = amax;
+    __syncthreads();
+    amax = red_amax[0];
+#pragma unroll
+    for (int j = 1; j < kQuantWaves; ++j) amax = fmaxf(amax, red_amax[j]);
+    if (tid < kClipSteps) cand_scale[tid] = scale_of(amax, clip_fraction(tid), qmax);
+    __syncthreads();
+    double se[kClipSteps];
+#pragma unroll
+    for (int c = 0; c < kClipSteps; ++c) se[c] = 0.0;
+    for (int64_t e0 = 4 * int64_t(tid); e0 < cols; e0 += 4 * kQuantThreads) {
+        float x[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (w_wide && e0 + 4 <= cols) {
+            const float4 f = *reinterpret_cast<const float4*>(w + e0);
+            x[0] = f.x; x[1] = f.y; x[2] = f.z; x[3] = f.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (e0 + i < cols) x[i] = w[e0 + i];
+        }
+#pragma unroll
+        for (int c = 0; c < kClipSteps; ++c) {              // unrolled: se[] stays in registers
+            const float scale = cand_scale[c];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (e0 + i < cols) se[c] = add_sq_err(x[i], scale, qmax, se[c]);         // rising element order within the thread
+            __builtin_amdgcn_sched_barrier(0);              // one candidate at a time: 48 interleaved division chains would spill
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < kClipSteps; ++c) {
+        const double s = qwave_sum(se[c]);
+        if (lane == 0) red_c[c][wave] = s;
+    }
+    __syncthreads();
+    if (wave == 0) {                                        // lane c folds candidate c in wave order; lanes past the last hold +inf
+        double a = HUGE_VAL;
+        if (lane < kClipSteps) {
+            a = red_c[lane][0];
+            for (int j = 1; j < kQuantWaves; ++j) a += red_c[lane][j];
+            if (t.cand_err) t.cand_err[row * kClipSteps + lane] = a;
+        }
+        int c = lane;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {            // the smallest error; among equal ones the smallest index
+            const double oa = __shfl_xor(a, off);
+            const int oc = __shfl_xor(c, off);
+            if (oa < a || (oa == a && oc < c)) { a = oa; c = oc; }
+        }
+        c = min(c, kClipSteps - 1);                         // lanes past the last candidate never win: finite sums are below +inf
+        if (lane == 0) { t.clip[row] = uint8_t(c); t.scale[row] = cand_scale[c]; }
+    }
+}
+
+// The clamp of the stored scale moved this element: its gradient is cut.  A non-finite w quantises to 0 and is never moved.
+__device__ __forceinline__ bool clamp_moved(float w, float scale, float qmax) { return isfinite(w) && fabsf(rintf(__fdiv_rn(w, scale))) > qmax; }
+
+__global__ __launch_bounds__(kQuantThreads) void ste_kernel(const SteTable tab) {
+    const int k = tensor_of(tab, int(blockIdx.x));
+    const ww_quant_ste_tensor t = tab.t[k];
+    const float qmax = tab.qmax;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t blk = int64_t(int(blockIdx.x) - tab.first_block[k]);
+    const int64_t cols = t.cols;
+    if (cols <= kQuantWaveCols) {
+        const int64_t row = blk * kQuantWaves + wave;
+        if (row >= t.rows) return;
+        const int64_t base = row * cols;
+        const float scale = t.scale[row];
+        for (int c = lane; c < int(cols); c += 64)
+            if (clamp_moved(t.w[base + c], scale, qmax)) t.g[base + c] = 0.0f;
+        return;
+    }
+    const int64_t row = blk;
+    const float* __restrict__ w = t.w + row * cols;
+    float* __restrict__ g = t.g + row * cols;
+    const bool w_wide = (reinterpret_cast<uintptr_t>(w) & 15) == 0;
+    const float scale = t.scale[row];
+    for (int64_t e0 = 4 * int64_t(tid); e0 < cols; e0 += 4 * kQuantThreads) {
+        float x[4] = {0.0f, 0.0f, 0.0f, 0.0f};            // a zero is never moved
+        if (w_wide && e0 + 4 <= cols) {
+            const float4 f = *reinterpret_cast<const float4*>(w + e0);
+            x[0] = f.x; x[1] = f.y; x[2] = f.z; x[3] = f.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (e0 + i < cols) x[i] = w[e0 + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (e0 + i < cols && clamp_moved(x[i], scale, qmax)) g[e0 + i] = 0.0f;
     }
 }
 
 // Host checks, before any HIP call.
-int check_quant(const ww_quant_tensor* tensors, int64_t n_tensors, int bits) {
-    const auto off = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+int check_call(const void* tensors, int64_t n_tensors, int bits) {
     if (n_tensors < 1 || n_tensors > kQuantMax) return fail(WW_EINVAL, "n_tensors %lld: expected 1..%d", (long long)n_tensors, kQuantMax);
     if (bits < 2 || bits > 8) return fail(WW_EINVAL, "bits %d: expected 2..8", bits);
     if (!tensors) return fail(WW_EINVAL, "null tensors pointer");
+    return WW_OK;
+}
+
+int check_shape(int k, int64_t rows, int64_t cols) {
+    if (rows < 1 || rows > (int64_t(1) << 30)) return fail(WW_EINVAL, "tensors[%d].rows %lld: expected 1..2^30", k, (long long)rows);
+    if (cols < 1 || cols > (int64_t(1) << 30)) return fail(WW_EINVAL, "tensors[%d].cols %lld: expected 1..2^30", k, (long long)cols);
+    if (rows * cols > (int64_t(1) << 40)) return fail(WW_EINVAL, "tensors[%d]: rows x cols %lld: expected at most 2^40", k, (long long)(rows * cols));
+    return WW_OK;
+}
+
+int check_disjoint(int k, const float* w, const float* other, int64_t n, const char* name) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(w), b0 = reinterpret_cast<uintptr_t>(other), len = uintptr_t(n) * 4;
+    if (a0 < b0 + len && b0 < a0 + len) return fail(WW_EINVAL, "tensors[%d]: the w and %s ranges overlap", k, name);
+    return WW_OK;
+}
+
+// The fields ww_quant_tensor and ww_quant_clip_tensor share; with kClip the clip tensor's own fields after them.
+template <class Tensor>
+int check_quant(const Tensor* tensors, int64_t n_tensors, int bits) {
+    if (int rc = check_call(tensors, n_tensors, bits)) return rc;
     for (int k = 0; k < int(n_tensors); ++k) {
-        const ww_quant_tensor& t = tensors[k];
-        if (t.rows < 1 || t.rows > (int64_t(1) << 30)) return fail(WW_EINVAL, "tensors[%d].rows %lld: expected 1..2^30", k, (long long)t.rows);
-        if (t.cols < 1 || t.cols > (int64_t(1) << 30)) return fail(WW_EINVAL, "tensors[%d].cols %lld: expected 1..2^30", k, (long long)t.cols);
-        if (t.rows * t.cols > (int64_t(1) << 40)) return fail(WW_EINVAL, "tensors[%d]: rows x cols %lld: expected at most 2^40", k, (long long)(t.rows * t.cols));
+        const Tensor& t = tensors[k];
+        if (int rc = check_shape(k, t.rows, t.cols)) return rc;
         if (!t.w || !t.scale) return fail(WW_EINVAL, "tensors[%d]: null w / scale pointer", k);
-        if (off(t.w, 3) || off(t.scale, 3) || off(t.deq, 3) || off(t.bad, 3)) return fail(WW_EINVAL, "tensors[%d]: w / scale / deq / bad must be 4-byte aligned", k);
-        if (off(t.err, 7)) return fail(WW_EINVAL, "tensors[%d]: err must be 8-byte aligned", k);
-        if (t.deq) {                                        // out of place: a row is read twice
-            const uintptr_t a0 = reinterpret_cast<uintptr_t>(t.w), b0 = reinterpret_cast<uintptr_t>(t.deq), len = uintptr_t(t.rows * t.cols) * 4;
-            if (a0 < b0 + len && b0 < a0 + len) return fail(WW_EINVAL, "tensors[%d]: the w and deq ranges overlap", k);
+        if (misaligned(t.w, 3) || misaligned(t.scale, 3) || misaligned(t.deq, 3) || misaligned(t.bad, 3))
+            return fail(WW_EINVAL, "tensors[%d]: w / scale / deq / bad must be 4-byte aligned", k);
+        if (misaligned(t.err, 7)) return fail(WW_EINVAL, "tensors[%d]: err must be 8-byte aligned", k);
+        if (t.deq)                                          // out of place: a row is read twice
+            if (int rc = check_disjoint(k, t.w, t.deq, t.rows * t.cols, "deq")) return rc;
+        if constexpr (std::is_same_v<Tensor, ww_quant_clip_tensor>) {
+            if (!t.clip) return fail(WW_EINVAL, "tensors[%d]: null clip pointer", k);
+            if (misaligned(t.sat, 3)) return fail(WW_EINVAL, "tensors[%d]: sat must be 4-byte aligned", k);
+            if (misaligned(t.cand_err, 7)) return fail(WW_EINVAL, "tensors[%d]: cand_err must be 8-byte aligned", k);
         }
     }
     return WW_OK;
 }
 
-int launch_quant(const ww_quant_tensor* tensors, int n_tensors, int bits, hipStream_t stream) {
-    QuantTable tab;
+int check_ste(const ww_quant_ste_tensor* tensors, int64_t n_tensors, int bits) {
+    if (int rc = check_call(tensors, n_tensors, bits)) return rc;
+    for (int k = 0; k < int(n_tensors); ++k) {
+        const ww_quant_ste_tensor& t = tensors[k];
+        if (int rc = check_shape(k, t.rows, t.cols)) return rc;
+        if (!t.w || !t.scale || !t.g) return fail(WW_EINVAL, "tensors[%d]: null w / scale / g pointer", k);
+        if (misaligned(t.w, 3) || misaligned(t.scale, 3) || misaligned(t.g, 3)) return fail(WW_EINVAL, "tensors[%d]: w / scale / g must be 4-byte aligned", k);
+        if (int rc = check_disjoint(k, t.w, t.g, t.rows * t.cols, "g")) return rc;
+    }
+    return WW_OK;
+}
+
+// The table of one launch: the tensors, the prefix sums of their block counts (a block is 16 short rows or one long row) and qmax.
+template <class Table, class Tensor>
+int fill_table(Table& tab, const Tensor* tensors, int n_tensors, int bits, unsigned* grid) {
     int64_t blocks = 0;
     for (int k = 0; k < n_tensors; ++k) {
         tab.t[k] = tensors[k];
@@ -242,10 +483,19 @@ int launch_quant(const ww_quant_tensor* tensors, int n_tensors, int bits, hipStr
         if (blocks > (int64_t(1) << 30)) return fail(WW_EUNSUPPORTED, "tensors[%d]: the table needs more than 2^30 blocks", k);
     }
     for (int k = n_tensors; k <= kQuantMax; ++k) tab.first_block[k] = int32_t(blocks);
-    for (int k = n_tensors; k < kQuantMax; ++k) tab.t[k] = ww_quant_tensor{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    for (int k = n_tensors; k < kQuantMax; ++k) tab.t[k] = Tensor{};
     tab.n_tensors = n_tensors;
     tab.qmax = float((1 << (bits - 1)) - 1);
-    return launch<quant_kernel>(dim3(unsigned(blocks)), dim3(kQuantThreads), 0, stream, tab);
+    *grid = unsigned(blocks);
+    return WW_OK;
+}
+
+template <auto Kernel, class Table, class Tensor>
+int launch_table(const Tensor* tensors, int64_t n_tensors, int bits, ww_stream_t stream) {
+    Table tab;
+    unsigned grid = 0;
+    if (int rc = fill_table(tab, tensors, int(n_tensors), bits, &grid)) return rc;
+    return launch<Kernel>(dim3(grid), dim3(kQuantThreads), 0, static_cast<hipStream_t>(stream), tab);
 }
 
 }  // namespace
@@ -258,7 +508,25 @@ extern "C" {
 int ww_quant_weights_f32(const ww_quant_tensor* tensors_host, int64_t n_tensors, int bits, ww_stream_t stream) {
     if (int rc = check_quant(tensors_host, n_tensors, bits)) return rc;
     if (int rc = require_gfx950()) return rc;
-    return launch_quant(tensors_host, int(n_tensors), bits, static_cast<hipStream_t>(stream));
+    return launch_table<quant_kernel<false>, QuantTable>(tensors_host, n_tensors, bits, stream);
+}
+
+int ww_quant_weights_clip_f32(const ww_quant_clip_tensor* tensors_host, int64_t n_tensors, int bits, ww_stream_t stream) {
+    if (int rc = check_quant(tensors_host, n_tensors, bits)) return rc;
+    if (int rc = require_gfx950()) return rc;
+    return launch_table<quant_kernel<true>, ClipTable>(tensors_host, n_tensors, bits, stream);
+}
+
+int ww_quant_clip_search_f32(const ww_quant_clip_tensor* tensors_host, int64_t n_tensors, int bits, ww_stream_t stream) {
+    if (int rc = check_quant(tensors_host, n_tensors, bits)) return rc;
+    if (int rc = require_gfx950()) return rc;
+    return launch_table<search_kernel, ClipTable>(tensors_host, n_tensors, bits, stream);
+}
+
+int ww_quant_ste_f32(const ww_quant_ste_tensor* tensors_host, int64_t n_tensors, int bits, ww_stream_t stream) {
+    if (int rc = check_ste(tensors_host, n_tensors, bits)) return rc;
+    if (int rc = require_gfx950()) return rc;
+    return launch_table<ste_kernel, SteTable>(tensors_host, n_tensors, bits, stream);
 }
 
 }  // extern "C"

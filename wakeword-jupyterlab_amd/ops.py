@@ -1504,39 +1504,51 @@ def _quant_mode_list(per_channel, n):
     return modes
 
 
-def quant_table(weights, scales, qs=None, deqs=None, errs=None, bads=None, per_channel=True):
-    """Up to 16 float32 GPU weight tensors and their outputs -> a ctypes array of _native.QuantTensor.  Per tensor of rows x cols
-    (quant_groups; `per_channel` a bool or one per tensor): scale float32 [rows]; q int8, deq float32 of the weight's size; err float64
-    [rows, 3]; bad int32 [rows].  Each of qs, deqs, errs, bads may be None, and so may single entries of them."""
+def _quant_entry(k, w, per_channel, outputs):
+    """Check weight `k` and its outputs [(name, tensor or None, dtype, elements per row or None for the weight's size)] -> (rows, cols)."""
+    _require_cuda_f32(w, f"weight {k}")
+    if not w.is_contiguous():
+        raise RuntimeError(f"weight {k} is not contiguous")
+    if w.numel() == 0:
+        raise ValueError(f"weight {k} is empty")
+    rows, cols = quant_groups(w, per_channel)
+    for name, t, dtype, per_row in outputs:
+        if t is None:
+            continue
+        numel = w.numel() if per_row is None else per_row * rows
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise TypeError(f"{name} {k}: expected a {dtype} torch.Tensor")
+        if t.device != w.device:
+            raise RuntimeError(f"{name} {k} on {t.device}, its weight on {w.device}")
+        if t.numel() != numel or not t.is_contiguous():
+            raise ValueError(f"{name} {k}: expected {numel} contiguous elements, got {tuple(t.shape)}")
+    return rows, cols
+
+
+def _quant_columns(weights, columns, what):
     weights = list(weights)
     n = len(weights)
     if not 1 <= n <= nat.QUANT_MAX_TENSORS:
         raise ValueError(f"{n} tensors: one launch takes 1..{nat.QUANT_MAX_TENSORS}")
-    modes = _quant_mode_list(per_channel, n)
-    cols_of = [[None] * n if c is None else list(c) for c in (scales, qs, deqs, errs, bads)]
+    cols_of = [[None] * n if c is None else list(c) for c in columns]
     if any(len(c) != n for c in cols_of):
-        raise ValueError("weights, scales, qs, deqs, errs and bads differ in length")
+        raise ValueError(f"{what} differ in length")
+    return weights, n, cols_of
+
+
+def quant_table(weights, scales, qs=None, deqs=None, errs=None, bads=None, per_channel=True):
+    """Up to 16 float32 GPU weight tensors and their outputs -> a ctypes array of _native.QuantTensor.  Per tensor of rows x cols
+    (quant_groups; `per_channel` a bool or one per tensor): scale float32 [rows]; q int8, deq float32 of the weight's size; err float64
+    [rows, 3]; bad int32 [rows].  Each of qs, deqs, errs, bads may be None, and so may single entries of them."""
+    weights, n, cols_of = _quant_columns(weights, (scales, qs, deqs, errs, bads), "weights, scales, qs, deqs, errs and bads")
+    modes = _quant_mode_list(per_channel, n)
     tab = (nat.QuantTensor * n)()
     for k, w in enumerate(weights):
-        _require_cuda_f32(w, f"weight {k}")
-        if not w.is_contiguous():
-            raise RuntimeError(f"weight {k} is not contiguous")
-        if w.numel() == 0:
-            raise ValueError(f"weight {k} is empty")
-        rows, cols = quant_groups(w, modes[k])
         scale, q, deq, err, bad = (c[k] for c in cols_of)
+        rows, cols = _quant_entry(k, w, modes[k], (("scale", scale, torch.float32, 1), ("q", q, torch.int8, None), ("deq", deq, torch.float32, None),
+                                                   ("err", err, torch.float64, 3), ("bad", bad, torch.int32, 1)))
         if scale is None:
             raise TypeError(f"scale {k}: expected a float32 tensor [{rows}]")
-        for name, t, dtype, numel in (("scale", scale, torch.float32, rows), ("q", q, torch.int8, w.numel()), ("deq", deq, torch.float32, w.numel()),
-                                      ("err", err, torch.float64, 3 * rows), ("bad", bad, torch.int32, rows)):
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor) or t.dtype != dtype:
-                raise TypeError(f"{name} {k}: expected a {dtype} torch.Tensor")
-            if t.device != w.device:
-                raise RuntimeError(f"{name} {k} on {t.device}, its weight on {w.device}")
-            if t.numel() != numel or not t.is_contiguous():
-                raise ValueError(f"{name} {k}: expected {numel} contiguous elements, got {tuple(t.shape)}")
         e = tab[k]
         e.w, e.scale, e.rows, e.cols = w.data_ptr(), scale.data_ptr(), rows, cols
         e.q, e.deq, e.err, e.bad = (None if t is None else t.data_ptr() for t in (q, deq, err, bad))
@@ -1582,6 +1594,131 @@ def quantize_weights(tensors, bits=8, per_channel=True):
     if tensors:
         quantize_weights_into(tensors, *([o[j] for o in out] for j in (1, 0, 2, 3, 4)), bits=bits, per_channel=modes)
     return out
+
+
+# ---- clipped scales and the straight-through estimator (csrc/ww_quant.hip) ---------------------------------
+QUANT_CLIPS = ("max", "mse")
+
+
+def check_quant_clip(clip) -> str:
+    if clip not in QUANT_CLIPS:
+        raise ValueError(f"clip {clip!r}: expected one of {QUANT_CLIPS}")
+    return clip
+
+
+def quant_clip_table(weights, scales, clips, qs=None, deqs=None, errs=None, bads=None, sats=None, cand_errs=None, per_channel=True):
+    """quant_table for ww_quant_weights_clip_f32 and ww_quant_clip_search_f32 -> a ctypes array of _native.QuantClipTensor: per tensor
+    also clip uint8 [rows] (read by the first, written by the second), sat int32 [rows] and cand_err float64 [rows, 48], both optional."""
+    columns = (scales, clips, qs, deqs, errs, bads, sats, cand_errs)
+    weights, n, cols_of = _quant_columns(weights, columns, "weights, scales, clips, qs, deqs, errs, bads, sats and cand_errs")
+    modes = _quant_mode_list(per_channel, n)
+    tab = (nat.QuantClipTensor * n)()
+    for k, w in enumerate(weights):
+        scale, clip, q, deq, err, bad, sat, cand = (c[k] for c in cols_of)
+        rows, cols = _quant_entry(k, w, modes[k], (("scale", scale, torch.float32, 1), ("clip", clip, torch.uint8, 1), ("q", q, torch.int8, None),
+                                                   ("deq", deq, torch.float32, None), ("err", err, torch.float64, 3), ("bad", bad, torch.int32, 1),
+                                                   ("sat", sat, torch.int32, 1), ("cand_err", cand, torch.float64, nat.QUANT_CLIP_STEPS)))
+        if scale is None or clip is None:
+            raise TypeError(f"scale / clip {k}: expected a float32 and a uint8 tensor [{rows}]")
+        e = tab[k]
+        e.w, e.scale, e.clip, e.rows, e.cols = w.data_ptr(), scale.data_ptr(), clip.data_ptr(), rows, cols
+        e.q, e.deq, e.err, e.bad, e.sat, e.cand_err = (None if t is None else t.data_ptr() for t in (q, deq, err, bad, sat, cand))
+    return tab
+
+
+def quantize_weights_clip_launch(table, device, bits) -> None:
+    """ww_quant_weights_clip_f32 on a prepared quant_clip_table.  Allocates nothing."""
+    with torch.cuda.device(device):
+        nat.check(nat.lib.ww_quant_weights_clip_f32(table, len(table), int(bits), _stream()))
+
+
+def quant_clip_search_launch(table, device, bits) -> None:
+    """ww_quant_clip_search_f32 on a prepared quant_clip_table: writes clip, scale and, where given, cand_err.  Allocates nothing."""
+    with torch.cuda.device(device):
+        nat.check(nat.lib.ww_quant_clip_search_f32(table, len(table), int(bits), _stream()))
+
+
+def quant_ste_table(weights, scales, grads, per_channel=True):
+    """Up to 16 float32 GPU weight tensors, their stored scales float32 [rows] and their gradients (float32, the weight's size, modified in
+    place) -> a ctypes array of _native.QuantSteTensor."""
+    weights, n, (scales, grads) = _quant_columns(weights, (scales, grads), "weights, scales and grads")
+    modes = _quant_mode_list(per_channel, n)
+    tab = (nat.QuantSteTensor * n)()
+    for k, w in enumerate(weights):
+        rows, cols = _quant_entry(k, w, modes[k], (("scale", scales[k], torch.float32, 1), ("grad", grads[k], torch.float32, None)))
+        if scales[k] is None or grads[k] is None:
+            raise TypeError(f"scale / grad {k}: expected float32 tensors")
+        e = tab[k]
+        e.w, e.scale, e.g, e.rows, e.cols = w.data_ptr(), scales[k].data_ptr(), grads[k].data_ptr(), rows, cols
+    return tab
+
+
+def quant_ste_launch(table, device, bits) -> None:
+    """ww_quant_ste_f32 on a prepared quant_ste_table.  Allocates nothing."""
+    with torch.cuda.device(device):
+        nat.check(nat.lib.ww_quant_ste_f32(table, len(table), int(bits), _stream()))
+
+
+def _quant_chunks(n):
+    return [slice(i, i + nat.QUANT_MAX_TENSORS) for i in range(0, n, nat.QUANT_MAX_TENSORS)]
+
+
+def _quant_inputs(tensors, bits, per_channel):
+    bits = check_quant_bits(bits)
+    tensors = list(tensors)
+    modes = _quant_mode_list(per_channel, len(tensors))
+    for k, w in enumerate(tensors):
+        _require_cuda_f32(w, f"weight {k}")
+    return tensors, bits, modes
+
+
+def quantize_weights_clip(tensors, clips, bits=8, per_channel=True):
+    """[(q, scale, deq, err, bad, sat)] for float32 GPU weight tensors under the clipped rule of include/wakeword_amd.h
+    (ww_quant_weights_clip_f32): `clips` holds one uint8 [rows] GPU tensor of candidate indices per weight; sat int32 [rows] counts the
+    elements the clamp moved.  All-zero indices give quantize_weights' bits."""
+    tensors, bits, modes = _quant_inputs(tensors, bits, per_channel)
+    clips = list(clips)
+    if len(clips) != len(tensors):
+        raise ValueError("tensors and clips differ in length")
+    out = []
+    for w, m in zip(tensors, modes):
+        rows, _ = quant_groups(w, m)
+        new = lambda shape, dtype: torch.empty(shape, device=w.device, dtype=dtype)     # noqa: E731
+        out.append((new(w.shape, torch.int8), new(rows, torch.float32), new(w.shape, torch.float32), new((rows, 3), torch.float64),
+                    new(rows, torch.int32), new(rows, torch.int32)))
+    tables = [quant_clip_table(tensors[c], [o[1] for o in out[c]], clips[c], [o[0] for o in out[c]], [o[2] for o in out[c]], [o[3] for o in out[c]],
+                               [o[4] for o in out[c]], [o[5] for o in out[c]], per_channel=modes[c]) for c in _quant_chunks(len(tensors))]
+    for c, tab in zip(_quant_chunks(len(tensors)), tables):      # every table was checked before the first launch
+        quantize_weights_clip_launch(tab, tensors[c.start].device, bits)
+    return out
+
+
+def quant_clip_search(tensors, bits=8, per_channel=True, cand_err=True):
+    """[(clip uint8 [rows], scale float32 [rows], cand_err float64 [rows, 48] or None)] for float32 GPU weight tensors
+    (ww_quant_clip_search_f32): per row the squared error of every clip candidate, the first candidate with the smallest one and its scale."""
+    tensors, bits, modes = _quant_inputs(tensors, bits, per_channel)
+    out = []
+    for w, m in zip(tensors, modes):
+        rows, _ = quant_groups(w, m)
+        out.append((torch.empty(rows, device=w.device, dtype=torch.uint8), torch.empty(rows, device=w.device, dtype=torch.float32),
+                    torch.empty((rows, nat.QUANT_CLIP_STEPS), device=w.device, dtype=torch.float64) if cand_err else None))
+    tables = [quant_clip_table(tensors[c], [o[1] for o in out[c]], [o[0] for o in out[c]], cand_errs=[o[2] for o in out[c]], per_channel=modes[c])
+              for c in _quant_chunks(len(tensors))]
+    for c, tab in zip(_quant_chunks(len(tensors)), tables):
+        quant_clip_search_launch(tab, tensors[c.start].device, bits)
+    return out
+
+
+def quant_ste_(weights, scales, grads, bits=8, per_channel=True) -> None:
+    """The straight-through estimator with clipping, in place on `grads` (ww_quant_ste_f32): where a finite weight lies outside its row's
+    clipped range, |rint(w / scale)| > qmax, the gradient becomes +0.0; every other gradient keeps its bits.  Nothing waits."""
+    weights, bits, modes = _quant_inputs(weights, bits, per_channel)
+    scales, grads = list(scales), list(grads)
+    if len(scales) != len(weights) or len(grads) != len(weights):
+        raise ValueError("weights, scales and grads differ in length")
+    tables = [quant_ste_table(weights[c], scales[c], grads[c], per_channel=modes[c]) for c in _quant_chunks(len(weights))]
+    for c, tab in zip(_quant_chunks(len(weights)), tables):
+        quant_ste_launch(tab, weights[c.start].device, bits)
 
 
 # ---- SpecAugment: time and frequency masks on log-mel batches (INTEGRATION.md section 3i; csrc/ww_specaug.hip) ----------------------

@@ -12,8 +12,14 @@ into them without leaving the GPU, says what that costs, and writes a file both 
   load_quantized_package      rebuilds the weights from q * scale alone, on the CPU or the GPU: the bits of WeightQuant.model
   WakewordTrainer(quant=, evaluate="quant")   validation, the monitor and the best checkpoint follow the quantised model
 
-The arithmetic has one definition (include/wakeword_amd.h); tests/quant_ref.py restates it in numpy.  Out of scope: quantisation-aware
-training, activation quantisation, int8 forward kernels -- the fake-quant model runs the float32 kernels on int8-representable weights.
+  WeightQuant(clip="mse")     a clipped scale per row: of 48 candidates amax * (64 - j) / 64 the one with the smallest squared error
+                              (ww_quant_clip_search_f32 at .calibrate(), ww_quant_weights_clip_f32 at every .update()); section 3t
+  WakewordTrainer(quant=, qat=True)           quantisation-aware training: the step's forward and backward read the fake-quant weights,
+                              the gradients of clipped weights are cut (ww_quant_ste_f32), Adam moves the float32 master weights
+
+The arithmetic has one definition (include/wakeword_amd.h); tests/quant_ref.py and tests/qat_ref.py restate it in numpy.  Out of scope:
+activation quantisation, int8 forward kernels, learned step sizes -- the fake-quant model runs the float32 kernels on int8-representable
+weights.
 """
 from __future__ import annotations
 
@@ -31,23 +37,34 @@ class QuantReport:
                sqnr_db (10 log10 of sum w^2 / sum (w - deq)^2 from the kernel's float64 sums: inf when nothing was lost, nan for an
                all-zero tensor), max_error (the largest |w - deq|), nonfinite (elements that were NaN or +-Inf: they quantise to 0)
     .totals    the same over all quantised tensors, plus float_bytes: what stayed float32 (the biases, by default)
+    .clip      "max" or "mse"; under "mse" every tensor also has saturated (elements the clamp moved) and clip_min / clip_mean (the
+               smallest and the mean clip fraction of its rows; 1.0 is the unclipped scale), and the totals the same
     str()      a table"""
 
-    def __init__(self, bits, per_channel, tensors, float_bytes):
-        self.bits, self.per_channel, self.tensors = bits, per_channel, tensors
+    def __init__(self, bits, per_channel, tensors, float_bytes, clip="max"):
+        self.bits, self.per_channel, self.tensors, self.clip = bits, per_channel, tensors, clip
         sw, se = sum(t["sum_w2"] for t in tensors), sum(t["sum_err2"] for t in tensors)
         self.totals = {"tensors": len(tensors), "rows": sum(t["rows"] for t in tensors),
                        "fp32_bytes": sum(t["fp32_bytes"] for t in tensors), "int8_bytes": sum(t["int8_bytes"] for t in tensors),
                        "float_bytes": float_bytes, "sum_w2": sw, "sum_err2": se, "sqnr_db": sqnr_db(sw, se),
                        "max_error": max([t["max_error"] for t in tensors], default=0.0), "nonfinite": sum(t["nonfinite"] for t in tensors)}
+        if clip == "mse":
+            rows = max(1, self.totals["rows"])
+            self.totals.update(saturated=sum(t["saturated"] for t in tensors), clip_min=min([t["clip_min"] for t in tensors], default=1.0),
+                               clip_mean=sum(t["clip_mean"] * t["rows"] for t in tensors) / rows)
 
     def __str__(self):
+        mse = self.clip == "mse"
         head = f"{'tensor':<22}{'shape':<20}{'rows':>6}{'fp32 B':>10}{'int8 B':>10}{'SQNR dB':>10}{'max err':>12}{'non-finite':>12}"
-        lines = [f"int{self.bits} weights, {'one scale per row' if self.per_channel else 'one scale per tensor'}", head, "-" * len(head)]
+        if mse:
+            head += f"{'saturated':>11}{'clip min':>10}{'clip mean':>11}"
+        title = f"int{self.bits} weights, {'one scale per row' if self.per_channel else 'one scale per tensor'}"
+        lines = [title + (", clipped to the smallest squared error" if mse else ""), head, "-" * len(head)]
         for t in self.tensors + [dict(self.totals, name="total", shape="")]:
             shape = "x".join(str(s) for s in t["shape"]) if t["shape"] != "" else ""
             lines.append(f"{t['name']:<22}{shape:<20}{t['rows']:>6}{t['fp32_bytes']:>10}{t['int8_bytes']:>10}{t['sqnr_db']:>10.2f}"
-                         f"{t['max_error']:>12.3e}{t['nonfinite']:>12}")
+                         f"{t['max_error']:>12.3e}{t['nonfinite']:>12}"
+                         + (f"{t['saturated']:>11}{t['clip_min']:>10.4f}{t['clip_mean']:>11.4f}" if mse else ""))
         lines.append(f"kept in float32: {self.totals['float_bytes']} bytes")
         return "\n".join(lines)
 
@@ -72,13 +89,20 @@ def dequantize(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return q.to(torch.float32) * scale.reshape((rows,) + (1,) * (q.dim() - 1) if rows != 1 else (1,) * q.dim())
 
 
-def _check_options(bits, per_channel, quantize_bias):
-    from .ops import check_quant_bits
+def _check_options(bits, per_channel, quantize_bias, clip="max"):
+    from .ops import check_quant_bits, check_quant_clip
     bits = check_quant_bits(bits)
     for name, v in (("per_channel", per_channel), ("quantize_bias", quantize_bias)):
         if not isinstance(v, bool):
             raise TypeError(f"{name} {v!r}: expected a bool")
+    check_quant_clip(clip)
     return bits, per_channel, quantize_bias
+
+
+def clip_fractions(clip: torch.Tensor) -> torch.Tensor:
+    """The fractions (64 - j) / 64 of clip indices j (an index past the last candidate counts as the last), float32, exact."""
+    from ._native import QUANT_CLIP_STEPS
+    return (64.0 - clip.to(torch.float32).clamp(max=QUANT_CLIP_STEPS - 1)) / 64.0
 
 
 class WeightQuant:
@@ -92,14 +116,20 @@ class WeightQuant:
     .report()     a QuantReport, from ONE device-to-host copy
     .q, .scale    {parameter name: int8 tensor of the weight's shape} and {name: float32 [rows]}
 
+    clip="max" (the default) takes every row's scale from its largest element.  clip="mse" gives up a row's outliers for a finer step:
+    .clip         {name: uint8 [rows]} the row's candidate index j; its scale is max(amax * ((64 - j) / 64) / qmax, 2^-126).  Empty under "max".
+    .calibrate()  searches every row's 48 candidates for the smallest squared error (one launch per 16 tensors, no wait), then update().
+                  Construction on the GPU calibrates once; update() keeps the stored indices and runs no search.
+
     A model on the GPU is quantised at construction.  Around a model on the CPU the object can be built, load a state dict and write a
     package; update() needs the GPU (there is no CPU implementation of the kernel)."""
 
-    def __init__(self, model, bits=8, per_channel=True, quantize_bias=False):
+    def __init__(self, model, bits=8, per_channel=True, quantize_bias=False, clip="max"):
         from .model import SimpleWakewordModel, WakewordModel
         if not isinstance(model, (SimpleWakewordModel, WakewordModel)):
             raise TypeError(f"WeightQuant: expected a SimpleWakewordModel or a WakewordModel, got {type(model).__name__}")
-        self.bits, self.per_channel, self.quantize_bias = _check_options(bits, per_channel, quantize_bias)
+        self.bits, self.per_channel, self.quantize_bias = _check_options(bits, per_channel, quantize_bias, clip)
+        self.clip_mode = clip
         self.source = model
         self.model = copy.deepcopy(model)
         self.model.eval()
@@ -111,9 +141,12 @@ class WeightQuant:
         self._names = list(self._own)
         self._allocate()
         self._tables = {}                                    # (pointers of the source's tensors) -> the ctypes tables of an update
-        self.n_updates = 0
+        self.n_updates = self.n_calibrations = 0
         if self._device.type == "cuda":
-            self.update()
+            if self.clip_mode == "mse":
+                self.calibrate()
+            else:
+                self.update()
 
     # ---- buffers: allocated once ----
     def _groups(self, name):
@@ -124,21 +157,28 @@ class WeightQuant:
         return quant_groups(p, mode) + (mode,)
 
     def _allocate(self):
-        """q per tensor, and ONE buffer behind every err, scale and bad so that report() reads them in one copy."""
+        """q per tensor, and ONE buffer behind every err, scale and bad -- under clip="mse" also behind every sat and clip, after them
+        -- so that report() reads them in one copy."""
         self._device = next(iter(self._own.values())).device
         self.quantized = [k for k in self._names if self._own[k].dim() >= 2 or self.quantize_bias]
         self.kept = [k for k in self._names if k not in self.quantized]
         rows = [self._groups(k)[0] for k in self.quantized]
         total = sum(rows)
-        self._stats = torch.zeros(total * (24 + 4 + 4), device=self._device, dtype=torch.uint8)
+        mse = self.clip_mode == "mse"
+        self._stats = torch.zeros(total * (24 + 4 + 4 + (4 + 1 if mse else 0)), device=self._device, dtype=torch.uint8)
         err = self._stats[:24 * total].view(torch.float64).view(total, 3)
         scale = self._stats[24 * total:28 * total].view(torch.float32)
-        bad = self._stats[28 * total:].view(torch.int32)
+        bad = self._stats[28 * total:32 * total].view(torch.int32)
+        sat = self._stats[32 * total:36 * total].view(torch.int32) if mse else None
+        clip = self._stats[36 * total:] if mse else None
         self.q, self.scale, self._err, self._bad = OrderedDict(), OrderedDict(), OrderedDict(), OrderedDict()
+        self.clip, self._sat = OrderedDict(), OrderedDict()
         at = 0
         for k, r in zip(self.quantized, rows):
             self.q[k] = torch.zeros(self._own[k].shape, device=self._device, dtype=torch.int8)
             self.scale[k], self._err[k], self._bad[k] = scale[at:at + r], err[at:at + r], bad[at:at + r]
+            if mse:
+                self.clip[k], self._sat[k] = clip[at:at + r], sat[at:at + r]
             at += r
 
     # ---- the update ----
@@ -154,18 +194,12 @@ class WeightQuant:
                 raise ValueError(f"WeightQuant.update: {k} has shape {tuple(named[k].shape)}, expected {tuple(self._own[k].shape)}")
         return named
 
-    @torch.no_grad()
-    def update(self, model=None) -> None:
-        """Quantise the current weights of `model` (default: the model given at construction; another instance of the same class is
-        paired by parameter name) into .q, .scale and the parameters of .model."""
+    def _tables_of(self, named, search=False):
+        """The ctypes tables of an update (or of a search) from these source tensors: built once per set of pointers."""
         from . import _native as nat
         from . import ops
-        from .average import WeightAverage
-        named = self._pair(model)
-        if self._device.type != "cuda":
-            raise RuntimeError("WeightQuant.update: the model is on the CPU; this path has no CPU implementation (model.to('cuda'))")
         srcs = [named[k] for k in self.quantized]
-        key = tuple(s.data_ptr() for s in srcs)
+        key = (search,) + tuple(s.data_ptr() for s in srcs)
         tables = self._tables.get(key)
         if tables is None:
             if len(self._tables) > 64:
@@ -173,52 +207,120 @@ class WeightQuant:
             tables, step = [], nat.QUANT_MAX_TENSORS
             for i in range(0, len(srcs), step):
                 ks = self.quantized[i:i + step]
-                tables.append(ops.quant_table(srcs[i:i + step], [self.scale[k] for k in ks], [self.q[k] for k in ks], [self._own[k] for k in ks],
-                                              [self._err[k] for k in ks], [self._bad[k] for k in ks], per_channel=[self._groups(k)[2] for k in ks]))
+                col = lambda d: [d[k] for k in ks]                                      # noqa: E731
+                modes = [self._groups(k)[2] for k in ks]
+                if search:
+                    tables.append(ops.quant_clip_table(srcs[i:i + step], col(self.scale), col(self.clip), per_channel=modes))
+                elif self.clip_mode == "mse":
+                    tables.append(ops.quant_clip_table(srcs[i:i + step], col(self.scale), col(self.clip), col(self.q), col(self._own), col(self._err),
+                                                       col(self._bad), col(self._sat), per_channel=modes))
+                else:
+                    tables.append(ops.quant_table(srcs[i:i + step], col(self.scale), col(self.q), col(self._own), col(self._err), col(self._bad),
+                                                  per_channel=modes))
             self._tables[key] = tables
-        for tab in tables:
-            ops.quantize_weights_launch(tab, self._device, self.bits)
+        return tables
+
+    @torch.no_grad()
+    def update(self, model=None, weights_only=False) -> None:
+        """Quantise the current weights of `model` (default: the model given at construction; another instance of the same class is
+        paired by parameter name) into .q, .scale and the parameters of .model.  `weights_only` leaves the kept float32 parameters (the
+        biases) of .model as they are: the launch and the version counters alone -- what a QAT step runs, which reads the biases elsewhere."""
+        from . import ops
+        from .average import WeightAverage
+        named = self._pair(model)
+        if self._device.type != "cuda":
+            raise RuntimeError("WeightQuant.update: the model is on the CPU; this path has no CPU implementation (model.to('cuda'))")
+        launch = ops.quantize_weights_clip_launch if self.clip_mode == "mse" else ops.quantize_weights_launch
+        for tab in self._tables_of(named):
+            launch(tab, self._device, self.bits)
         WeightAverage.touched(self._own[k] for k in self.quantized)     # written behind autograd's back: move the version counters
-        for k in self.kept:
-            self._own[k].copy_(named[k])                     # float32 as they are; copy_ moves the version counter itself
+        if not weights_only:
+            for k in self.kept:
+                self._own[k].copy_(named[k])                 # float32 as they are; copy_ moves the version counter itself
         self.n_updates += 1
+
+    @torch.no_grad()
+    def calibrate(self, model=None) -> None:
+        """clip="mse": choose every row's clip index anew from the current weights of `model` -- the candidate with the smallest squared
+        error, ww_quant_clip_search_f32, one launch per 16 tensors and no wait -- then update(model).  Under clip="max" it is update(model)."""
+        from . import ops
+        if self.clip_mode == "mse":
+            named = self._pair(model)
+            if self._device.type != "cuda":
+                raise RuntimeError("WeightQuant.calibrate: the model is on the CPU; this path has no CPU implementation (model.to('cuda'))")
+            for tab in self._tables_of(named, search=True):
+                ops.quant_clip_search_launch(tab, self._device, self.bits)
+            self.n_calibrations += 1
+        self.update(model)
+
+    def ste_tables(self, grads: dict, model=None):
+        """The ctypes tables of ww_quant_ste_f32 over the quantised tensors: the source's weights, the stored scales and `grads`
+        {parameter name: gradient tensor}.  WakewordTrainer(qat=True) launches them after its backward."""
+        from . import _native as nat
+        from . import ops
+        named = self._pair(model)
+        step = nat.QUANT_MAX_TENSORS
+        return [ops.quant_ste_table([named[k] for k in ks], [self.scale[k] for k in ks], [grads[k] for k in ks],
+                                    per_channel=[self._groups(k)[2] for k in ks])
+                for ks in (self.quantized[i:i + step] for i in range(0, len(self.quantized), step))]
 
     # ---- what it cost ----
     def report(self) -> QuantReport:
         host = self._stats.cpu()                             # the one copy
         total = sum(self._groups(k)[0] for k in self.quantized)
         err = host[:24 * total].view(torch.float64).view(total, 3).numpy()
-        bad = host[28 * total:].view(torch.int32).numpy()
+        bad = host[28 * total:32 * total].view(torch.int32).numpy()
+        mse = self.clip_mode == "mse"
+        if mse:
+            sat = host[32 * total:36 * total].view(torch.int32).numpy()
+            fraction = clip_fractions(host[36 * total:]).numpy()
         tensors, at = [], 0
         for k in self.quantized:
             rows, cols, _ = self._groups(k)
             e, b = err[at:at + rows], bad[at:at + rows]
-            at += rows
             sw, se = float(e[:, 0].sum()), float(e[:, 1].sum())
             tensors.append({"name": k, "shape": tuple(self._own[k].shape), "rows": rows, "cols": cols, "fp32_bytes": 4 * rows * cols,
                             "int8_bytes": rows * cols + 4 * rows, "sum_w2": sw, "sum_err2": se, "sqnr_db": sqnr_db(sw, se),
                             "max_error": float(e[:, 2].max()), "nonfinite": int(b.sum())})
-        return QuantReport(self.bits, self.per_channel, tensors, sum(4 * self._own[k].numel() for k in self.kept))
+            if mse:
+                f = fraction[at:at + rows]
+                tensors[-1].update(saturated=int(sat[at:at + rows].sum()), clip_min=float(f.min()), clip_mean=float(f.mean()))
+            at += rows
+        return QuantReport(self.bits, self.per_channel, tensors, sum(4 * self._own[k].numel() for k in self.kept), self.clip_mode)
 
     # ---- state ----
     def state_dict(self):
         """bits, per_channel, quantize_bias, q {name: int8}, scale {name: float32 [rows]} and float {name: float32}: the parameters that
-        were not quantised.  q * scale and `float` together are .model's weights."""
-        return {"bits": self.bits, "per_channel": self.per_channel, "quantize_bias": self.quantize_bias,
-                "q": OrderedDict((k, v.detach().clone()) for k, v in self.q.items()),
-                "scale": OrderedDict((k, v.detach().clone()) for k, v in self.scale.items()),
-                "float": OrderedDict((k, self._own[k].detach().clone()) for k in self.kept)}
+        were not quantised.  q * scale and `float` together are .model's weights.  Under clip="mse" also clip {name: uint8 [rows]}: the
+        indices the scales were taken at (the scales already hold them; a loader needs q and scale alone)."""
+        state = {"bits": self.bits, "per_channel": self.per_channel, "quantize_bias": self.quantize_bias,
+                 "q": OrderedDict((k, v.detach().clone()) for k, v in self.q.items()),
+                 "scale": OrderedDict((k, v.detach().clone()) for k, v in self.scale.items()),
+                 "float": OrderedDict((k, self._own[k].detach().clone()) for k in self.kept)}
+        if self.clip_mode == "mse":
+            state["clip"] = OrderedDict((k, v.detach().clone()) for k, v in self.clip.items())
+        return state
 
     @torch.no_grad()
     def load_state_dict(self, state) -> None:
-        bits, per_channel, quantize_bias = _check_options(int(state["bits"]), bool(state["per_channel"]), bool(state.get("quantize_bias", False)))
-        if (per_channel, quantize_bias) != (self.per_channel, self.quantize_bias):
-            self.per_channel, self.quantize_bias = per_channel, quantize_bias
+        clip_mode = "mse" if "clip" in state else "max"
+        bits, per_channel, quantize_bias = _check_options(int(state["bits"]), bool(state["per_channel"]), bool(state.get("quantize_bias", False)),
+                                                          clip_mode)
+        if (per_channel, quantize_bias, clip_mode) != (self.per_channel, self.quantize_bias, self.clip_mode):
+            self.per_channel, self.quantize_bias, self.clip_mode = per_channel, quantize_bias, clip_mode
             self._allocate()
             self._tables = {}
         self.bits = bits
         if list(state["q"]) != self.quantized or list(state["scale"]) != self.quantized or list(state["float"]) != self.kept:
             raise ValueError("WeightQuant.load_state_dict: the state's tensor names differ from the quantised model's")
+        if clip_mode == "mse":
+            if list(state["clip"]) != self.quantized:
+                raise ValueError("WeightQuant.load_state_dict: the state's clip names differ from the quantised model's")
+            for k in self.quantized:
+                c = state["clip"][k]
+                if c.dtype != torch.uint8 or c.numel() != self.clip[k].numel():
+                    raise ValueError(f"WeightQuant.load_state_dict: {k}: clip {c.dtype} with {c.numel()} rows, expected uint8 with {self.clip[k].numel()}")
+                self.clip[k].copy_(c.reshape(-1))
         for k in self.quantized:
             q, s = state["q"][k], state["scale"][k]
             if q.shape != self.q[k].shape or s.numel() != self.scale[k].numel():

@@ -30,6 +30,16 @@ re-quantises (one launch, no wait) and then it, `val_report`, the monitor, the s
 `quant.model`, the fake-quant model -- the kept checkpoint is the one that survives quantisation.  The checkpoint gains "quant_state_dict"
 when a quantiser is set.  Without one nothing here is reached.
 
+`qat=True` (with `quant=WeightQuant(model, ...)` around the model that is trained) turns the step into
+quantisation-aware training: ONE quantiser launch in front of the forward (`quant.update(weights_only=True)`), the train forward and
+backward read a second parameter table -- `quant.model`'s fake-quant weights, and the master's own float32 biases unless the quantiser
+quantises them too --, the gradients land in the master's `.grad` buffers as always, under clip="mse" ONE ww_quant_ste_f32 launch zeroes
+the gradients of the weights the clipped scale saturates (under "max" nothing saturates and nothing is launched), and the gradient
+norm and Adam move the float32 master weights.  `qat_calibrate` says when a clip="mse" quantiser searches its clip indices anew: "epoch"
+(train_epoch, before its first batch), an integer n (every n steps) or None (never after construction).  Losses, a teacher, the average
+(of the master weights), the ledgers and evaluate="quant" compose unchanged; `select=` raises NotImplementedError.  With qat=False a
+step is launch for launch what it was.
+
 `teacher=` (an eval-mode SimpleWakewordModel or WakewordModel on the same device, of either class; `average.model` gives the mean
 teacher) turns the step into knowledge distillation: the teacher's eval forward on the same batch into a
 persistent buffer, then ONE ww_distill_loss_f32 launch in the loss's place -- (1 - distill_alpha) * criterion + distill_alpha * T^2 * KD
@@ -72,7 +82,7 @@ EVALUATE = ("model", "average", "quant")
 class WakewordTrainer:
     def __init__(self, model, device, config=TrainingConfig, *, checkpoint_path="best_wakeword_model.pth", max_grad_norm=None,
                  monitor="val_acc", thresholds=(0.8,), criterion=None, ledger=None, val_ledger=None, average=None, evaluate="model",
-                 teacher=None, distill_alpha=0.5, distill_temperature=2.0, select=None, quant=None):
+                 teacher=None, distill_alpha=0.5, distill_temperature=2.0, select=None, quant=None, qat=False, qat_calibrate="epoch"):
         if not isinstance(model, (SimpleWakewordModel, WakewordModel)):
             raise TypeError(f"WakewordTrainer drives the HIP training kernels of SimpleWakewordModel and WakewordModel; got {type(model).__name__}")
         from .loss import check_distillation
@@ -85,6 +95,8 @@ class WakewordTrainer:
             from .quant import WeightQuant
             if not isinstance(quant, WeightQuant):
                 raise TypeError(f"WakewordTrainer: quant must be a quant.WeightQuant or None, got {type(quant).__name__}")
+        self._qat, self.qat_calibrate = self._check_qat(qat, qat_calibrate, quant, model, select)
+        self._qat_steps = 0
         if any(p.device.type != "cuda" for p in model.parameters()):
             raise TypeError("WakewordTrainer: the model's parameters are on the CPU; this path has no CPU implementation (model.to('cuda'))")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
@@ -217,6 +229,33 @@ class WakewordTrainer:
         if any(p.requires_grad and p.untyped_storage().data_ptr() in own for p in teacher.parameters()):
             raise ValueError("WakewordTrainer: a trainable parameter of the teacher shares its storage with the student's")
 
+    # ---- quantisation-aware training ----
+    @staticmethod
+    def _check_qat(qat, qat_calibrate, quant, model, select):
+        """Refusals of the QAT options that need no device; returns (qat, qat_calibrate)."""
+        if not isinstance(qat, bool):
+            raise TypeError(f"qat {qat!r}: expected a bool")
+        if not (qat_calibrate is None or qat_calibrate == "epoch"
+                or (isinstance(qat_calibrate, int) and not isinstance(qat_calibrate, bool) and qat_calibrate >= 1)):
+            raise ValueError(f"qat_calibrate {qat_calibrate!r}: expected 'epoch', a positive integer (steps) or None")
+        if not qat:
+            return False, qat_calibrate
+        if quant is None:
+            raise ValueError("qat=True needs a quantiser: WakewordTrainer(..., quant=WeightQuant(model), qat=True)")
+        if quant.source is not model:
+            raise ValueError("qat: the quantiser was built around another model (WeightQuant(model) takes the model that is trained)")
+        if select is not None:
+            raise NotImplementedError("WakewordTrainer: select= together with qat=True is not supported (mining under QAT is out of scope)")
+        if quant.clip_mode == "mse" and quant.quantize_bias:
+            raise NotImplementedError("WakewordTrainer: qat=True with clip='mse' and quantize_bias=True is not supported (the two biases of an "
+                                      "LSTM layer share one gradient buffer, which cannot carry two masks)")
+        return True, qat_calibrate
+
+    @property
+    def qat(self) -> bool:
+        """Whether `step` trains through the quantiser (set at construction)."""
+        return self._qat
+
     # ---- loss-ranked selection ----
     @staticmethod
     def _check_select(select, teacher) -> None:
@@ -238,6 +277,8 @@ class WakewordTrainer:
     @select.setter
     def select(self, rule):
         self._check_select(rule, self.teacher)
+        if rule is not None and self._qat:
+            raise NotImplementedError("WakewordTrainer: select= together with qat=True is not supported (mining under QAT is out of scope)")
         self._select = rule
 
     @property
@@ -337,6 +378,17 @@ class WakewordTrainer:
         self._tg = ops.train_grads_struct(self._grads, self._n_conv)
         self._tp = ops._train_params_struct(self._params, self._n_conv)
         self._tp_key = tuple(p.data_ptr() for p in self._params)
+        if self._qat:
+            self._bind_qat()
+
+    def _bind_qat(self) -> None:
+        """The second parameter table of a QAT step -- the fake-quant model's tensors where the quantiser writes them, the master's own
+        elsewhere (the float32 biases) -- and, under clip="mse", the table of the straight-through launch over the master's gradients."""
+        wq = self.quant
+        self._tp_q = ops._train_params_struct([wq._own[k] if k in wq.q else p for k, p in zip(self._keys, self._params)], self._n_conv)
+        grads = {k: p.grad for k, p in zip(self._keys, self._params)}
+        self._ste_tables = wq.ste_tables(grads) if wq.clip_mode == "mse" else []
+        self._qat_stats = wq._stats                          # the buffer behind the scales the tables point at: held, and watched by `step`
 
     def _grads_bound(self) -> bool:
         for k, p in zip(self._keys, self._params):
@@ -411,7 +463,10 @@ class WakewordTrainer:
         Integer labels then follow the rule of a criterion WITH options even under the default one: a label of -100 is ignored.
 
         With `self.select` set and k = select.rows(B) < B the batch is first scored without dropout, and everything above -- loss,
-        gradient, train_stats, last_logits, the ledger's rows -- is about the k rows `self.last_selected` names (section 3r)."""
+        gradient, train_stats, last_logits, the ledger's rows -- is about the k rows `self.last_selected` names (section 3r).
+
+        With qat=True the quantiser runs first (one launch), forward and backward read the fake-quant weights, and under clip="mse" one
+        more launch after the backward cuts the gradients of saturated weights (section 3t); the seed is drawn as always."""
         if not self.model.training:
             raise RuntimeError("WakewordTrainer.step: the model is in eval mode (train_epoch calls model.train())")
         if isinstance(data, torch.Tensor) and data.device != self._dev:
@@ -450,6 +505,17 @@ class WakewordTrainer:
         if not self._grads_bound():                          # optimizer.zero_grad() or a .to(): bind the buffers again
             self._bind_grads()
             self._norm_tables = None
+        tp = self._tp
+        if self._qat:
+            wq = self.quant
+            if wq._stats is not self._qat_stats:             # load_state_dict changed the quantiser's grouping or clip mode: new buffers
+                self._bind_qat()
+            if wq.clip_mode == "mse" and isinstance(self.qat_calibrate, int) and self._qat_steps > 0 and self._qat_steps % self.qat_calibrate == 0:
+                wq.calibrate()                               # the search, then the full update
+            else:
+                wq.update(weights_only=True)                 # one launch, no wait: the forward below reads the master's own biases
+            self._qat_steps += 1
+            tp = self._tp_q
         # the dropout seed exactly as _CnnLstm.forward draws it: one randint from torch's CPU generator
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         math = nat.lib.ww_get_train_math()                   # resolved once: query, forward and backward of this step get this value
@@ -466,7 +532,7 @@ class WakewordTrainer:
                 x, y, entries, ledger_y = self._mine(x, y, soft, soft_opts, entries, ledger_y, B, k, math)
                 B = k
             logits, m = self._logits if B == self._cap else self._logits[:B], self.model         # the buffers may hold more rows
-            ops.train_forward_into(x, self._tp, m.lstm.dropout, m.dropout.p, seed, math, self._ws, logits)
+            ops.train_forward_into(x, tp, m.lstm.dropout, m.dropout.p, seed, math, self._ws, logits)
             if distill:
                 zt = self._teacher_forward(x, B) if teacher_logits is None else teacher_logits
                 self._last_teacher_logits = zt
@@ -477,7 +543,10 @@ class WakewordTrainer:
                 ops.soft_ce_loss_into(logits, y, self._dlogits, self.last_loss, self.train_stats, opts=soft_opts)
             else:
                 ops.ce_loss_into(logits, y, self._dlogits, self.last_loss, self.train_stats, opts=self._loss_opts)
-            ops.train_backward_into(x, self._tp, self._dlogits, math, self._ws, self._tg)
+            ops.train_backward_into(x, tp, self._dlogits, math, self._ws, self._tg)
+            if self._qat:
+                for tab in self._ste_tables:                 # clip="mse" alone: under "max" nothing saturates
+                    ops.quant_ste_launch(tab, self._dev, self.quant.bits)
             if self.max_grad_norm is not None:
                 self._norm_step()
         self.optimizer.step(grad_scale=self._scale if self.max_grad_norm is not None else None)
@@ -522,6 +591,8 @@ class WakewordTrainer:
             self.select_stats.zero_()
         if self.ledger is not None:
             self.ledger.begin_epoch()
+        if self._qat and self.qat_calibrate == "epoch" and self.quant.clip_mode == "mse":
+            self.quant.calibrate()
         for data, target in train_loader:
             if self.ledger is None:
                 self.step(data, target)
