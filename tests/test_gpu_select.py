@@ -413,3 +413,29 @@ def test_mined_step_has_no_hidden_waits_and_allocates_nothing():
     assert before == after
     torch.cuda.synchronize()
     assert ops.read_loss_stats(trainer.train_stats)["batches"] == 5 and ops.read_select_stats(trainer.select_stats)["batches"] == 5
+
+
+def test_mined_steps_of_changing_batch_size_allocate_nothing():
+    """An epoch's ragged last batch and the full batch after it: the gather buffers only grow, like the logits' -- a step at a batch
+    size that has been seen allocates nothing, whatever size came between."""
+    trainer = _trainer("simple", select=pkg.HardSelect(0.5), ledger=pkg.ClipLedger(40, DEV))
+    batches = {B: _batch(B, 8, seed=B) + (torch.arange(B, device=DEV),) for B in (16, 5)}
+    for B in (16, 5):
+        trainer.step(*batches[B][:2], entries=batches[B][2])
+    torch.cuda.synchronize()
+    import gc
+    gc.collect()                                                     # earlier tests' trainers are not freed inside the window
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        for B in (16, 5, 16):
+            x, y, entries = batches[B]
+            before = torch.cuda.memory_allocated()
+            trainer.step(x, y, entries=entries)
+            assert torch.cuda.memory_allocated() == before, B
+            k = trainer.select.rows(B)
+            assert trainer.last_selected.shape == (k,) and trainer.last_logits[:k].shape == (k, 2)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    sel = trainer.last_selected
+    assert torch.equal(trainer._gathered["x"][:8], batches[16][0][sel]) and torch.equal(trainer._gathered["entries"][:8], sel)
+    assert ops.read_select_stats(trainer.select_stats)["batches"] == 5

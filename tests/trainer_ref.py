@@ -93,3 +93,17 @@ def clip(grads, max_norm):
     """(global L2 norm, min(1, max_norm / (norm + 1e-6))) over a list of arrays, in float64."""
     norm = float(np.sqrt(sum(float(np.sum(np.asarray(g, np.float64) ** 2)) for g in grads)))
     return norm, min(1.0, max_norm / (norm + 1e-6))
+
+
+# The bounds tests/test_gpu_trainer.py (test_grad_norm_and_clip_scale, test_max_grad_norm_clips_after_the_backward) holds ww_grad_norm_f32
+# to, by name for the tests that check the norm of a composed step: the norm within 2^-22 of the float64 value, relative; an active
+# scale within that plus one float32 rounding; an inactive one is exactly 1.
+NORM_REL = 2.0 ** -22
+
+
+def norm_bound(norm64: float) -> float:
+    return NORM_REL * norm64
+
+
+def scale_bound(scale64: float) -> float:
+    return (NORM_REL + U) * scale64

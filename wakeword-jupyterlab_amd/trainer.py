@@ -292,11 +292,13 @@ class WakewordTrainer:
         return self._last_scores
 
     def _gather_buffer(self, name, shape, dtype):
+        """The first shape[0] rows of the persistent buffer `name`.  Like the logits' buffers it only grows: a smaller batch (an
+        epoch's ragged last one) takes a view, and the batch after it finds the rows it had."""
         buf = self._gathered.get(name)
-        if buf is None or tuple(buf.shape) != tuple(shape):
+        if buf is None or tuple(buf.shape[1:]) != tuple(shape[1:]) or buf.shape[0] < shape[0]:
             self._gathered[name] = None                      # release before replacing
             buf = self._gathered[name] = torch.empty(shape, device=self._dev, dtype=dtype)
-        return buf
+        return buf if buf.shape[0] == shape[0] else buf[:shape[0]]
 
     def _mine(self, x, y, soft, soft_opts, entries, ledger_y, B, k, math):
         """The scoring forward on all B rows (dropout 0: no seed is drawn, the raw parameters are read), the selection and the gather:
