@@ -97,6 +97,79 @@ def check_rows(out, special_rows, control_out):
         assert np.isfinite(out[i]).all(), f"ordinary row {i} is not finite"
 
 
+# ------------------------------------------------------------------------------------------------ clip-to-clip hand-over
+# A persistent log-mel workgroup walks clip, clip + grid, ...; its LDS (mel tile, red[], the auto-mode flag words, the sample prefetch)
+# is what one clip hands to the next.  carry_batch orders five kinds of rows so that every kind follows every kind inside a workgroup.
+CARRY_KINDS = ("noisy", "tone", "special", "silent", "loud")
+ORDINARY_KINDS = ("noisy", "tone", "loud")
+# the grids of csrc/ww_logmel.hip in units of the CU count: K1Layout::kBlocksPerCu (3: 4 waves, 32 frames; 2: 4 waves, 64 frames) and
+# K64Layout::kBlocksPerCu (2: 32 frames; 1: 64 frames)
+CARRY_GRIDS_PER_CU = (1, 2, 3)
+
+
+def carry_rows(n_cu):
+    """Rows of carry_batch: two full rounds of the widest grid (3 per CU) and an odd tail, so that every grid iterates at least twice."""
+    return 2 * max(CARRY_GRIDS_PER_CU) * n_cu + 41
+
+
+def carry_kinds(n_rows, n_cu, grids_per_cu=CARRY_GRIDS_PER_CU):
+    """Kind of every row.  Row i = q n_cu + r gets CARRY_KINDS[(r + q (r // 5)) % 5]: the row g = m n_cu further on has the index
+    m (r // 5) higher, and over r every start kind meets every difference.  (A fixed period cannot do this: 3 n_cu is a multiple of 3,
+    and a period of 3 pairs every row with its own kind.)  The condition itself is asserted, not the formula."""
+    kinds = [CARRY_KINDS[(i % n_cu + (i // n_cu) * ((i % n_cu) // 5)) % 5] for i in range(n_rows)]
+    for m in grids_per_cu:
+        g = m * n_cu
+        assert n_rows > 2 * g, (n_rows, g)
+        pairs = {(kinds[c], kinds[c + g]) for c in range(n_rows - g)}
+        missing = {(a, b) for a in CARRY_KINDS for b in CARRY_KINDS} - pairs
+        assert not missing, f"grid {g}: no row of the second kind follows one of the first in a workgroup: {sorted(missing)}"
+    return kinds
+
+
+def carry_batch(n, n_cu):
+    """(x, control, kinds) for carry_rows(n_cu) rows of n samples (seeded, repeatable).
+    noisy: 16 base clips under per-row gains (as the non-finite tests' batches); tone: tones(n), which auto mode marks; special: the 17
+    nonfinite_cases, cycled; silent: zeros; loud: a noisy clip * 2^15.  `control` holds finite noisy clips in the special and silent rows."""
+    B = carry_rows(n_cu)
+    kinds = carry_kinds(B, n_cu)
+    base, tone, cases = synth.make_clips(0, 16, n=n), tones(n), list(nonfinite_cases(n).values())
+    fill = np.stack([noisy(900 + k, n) for k in range(8)])
+    x = np.zeros((B, n), np.float32)
+    control = np.empty((B, n), np.float32)
+    count = dict.fromkeys(CARRY_KINDS, 0)
+    for i, kind in enumerate(kinds):
+        j = count[kind]
+        count[kind] += 1
+        gain = np.float32(1.0 - 0.37 * (j // 16) / max(1, B // 16))
+        if kind == "noisy":
+            x[i] = base[j % 16] * gain
+        elif kind == "tone":
+            x[i] = tone[j % len(tone)]
+        elif kind == "special":
+            x[i] = cases[j % len(cases)]
+        elif kind == "loud":
+            x[i] = scaled(base[(j + 5) % 16] * gain, 15)
+        control[i] = fill[j % len(fill)] * gain if kind in ("special", "silent") else x[i]
+    assert np.isfinite(control).all() and min(count.values()) >= len(cases)
+    for i, kind in enumerate(kinds):
+        assert np.isfinite(x[i]).all() == (kind != "special") and (x[i] != 0).any() == (kind != "silent"), (i, kind)
+    return x, control, kinds
+
+
+def carry_sample_rows(kinds, n_cu):
+    """The ordinary rows held to the oracle: for each grid g and each of special / silent / tone, a row that directly follows a row of
+    that kind in its workgroup (row c + g after row c) -- one noisy or loud and one tone, 18 rows.  -> (noisy-or-loud rows, tone rows)"""
+    plain, tone = [], []
+    for m in CARRY_GRIDS_PER_CU:
+        g = m * n_cu
+        for before in ("special", "silent", "tone"):
+            for want, rows in ((("noisy", "loud")[(m + len(plain)) % 2], plain), ("tone", tone)):
+                rows.append(next(c + g for c in range(len(kinds) - g)
+                                 if kinds[c] == before and kinds[c + g] == want and c + g not in rows))
+    assert len(set(plain)) == 9 and len(set(tone)) == 9
+    return plain, tone
+
+
 # ------------------------------------------------------------------------------------------------ a stand-in of the float epilogue
 def standin_logmel(x, n, normalize, sticky):
     """numpy stand-in of logmel_kernel's epilogue on the oracle's mel powers of the RAW samples (the kernel defers the peak gain to the

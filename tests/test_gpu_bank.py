@@ -162,6 +162,59 @@ def test_gather_special_values():
     assert _same_bits(got[0], _ref_row(x, 8000, n, "window", 0)) and np.isnan(got[0, 1000])
 
 
+def _grid_items(n_items, g, pairs, silent):
+    """(entry, start, norm) of item i = q g + r: pair i % len(pairs) and norm (r + q ((r // 3) % 3)) % 3 of (None, entry, window), so that
+    over r the norms of item c and item c + g -- consecutive rows of one workgroup of a grid of g -- run through all nine ordered pairs.
+    Asserted here: that, and that a silent window normalised by its own peak (the zero row) and an ordinary such window follow each
+    other in a workgroup in both orders (red[] holds the peak of the window before)."""
+    kinds = [None, "entry", "window"]
+    items = [pairs[i % len(pairs)] + (kinds[(i % g + (i // g) * ((i % g // 3) % 3)) % 3],) for i in range(n_items)]
+    assert n_items > 2 * g
+    seen = {(items[c][2], items[c + g][2]) for c in range(n_items - g)}
+    assert len(seen) == 9, seen
+    quiet = [k == "window" and (e, s) in silent for e, s, k in items]
+    loud = [k == "window" and (e, s) not in silent for e, s, k in items]
+    assert any(quiet[c] and loud[c + g] for c in range(n_items - g)) and any(loud[c] and quiet[c + g] for c in range(n_items - g))
+    return items
+
+
+def test_gather_beyond_the_resident_grid():
+    """bank_gather_kernel's grid is capped at 8 workgroups per CU and the other gather tests pass at most 37 items, so its loop over
+    the items is never entered a second time.  Here 2 x 8 x CUs + 77 items at N = 4000 in ONE launch: every workgroup takes two rows
+    and 77 take three.  WINDOW rows reduce their peak through red[] behind two barriers, the other norms meet no barrier, and
+    _grid_items mixes the three norms between consecutive rows of a workgroup; among the windows are silent ones (the zero row), windows
+    hanging over the front and over the end of their entry, entries shorter than a window and the empty entry.  Against the numpy
+    definition of test_gather_equals_the_definition, bit for bit."""
+    n = 4000
+    g = 8 * torch.cuda.get_device_properties(DEV).multi_processor_count      # launch_bank_gather's cap
+    n_items = 2 * g + 77
+    rng = np.random.default_rng(77)
+    L = [3 * n + 7, n - 1, 0, n + 1, 5, 2 * n]
+    x = (rng.standard_normal(sum(L)) * 0.3).astype(np.float32)
+    x[100:100 + n + 50] = 0.0                                            # a silent stretch in entry 0
+    at = np.concatenate([[0], np.cumsum(L)])
+    x[at[1]:at[2]] = 0.0                                                 # entry 1 is all zero: peak 0
+    b = pkg.ClipBank(_proc(n))
+    b.add_buffer(torch.from_numpy(x).to(DEV), L)
+    xs = [x[at[i]:at[i + 1]] for i in range(len(L))]
+    silent = {(0, 120), (0, 100), (1, 0), (1, -7), (2, 0)}
+    pairs = sorted(silent) + [(0, 0), (0, -5), (0, -n), (0, L[0] - n), (0, L[0] - 3), (0, L[0]), (0, 2 * n + 1), (3, 1), (3, -n + 1), (3, 2),
+                              (4, -17), (4, 5), (4, 0), (5, n), (5, n + 3), (5, -1), (5, n - 2), (0, 4101)]
+    assert len(pairs) == 23 and all(-n <= s <= xs[e].size for e, s in pairs)          # a prime: no period shared with the norms or the grid
+    items = _grid_items(n_items, g, pairs, silent)                                   # asserted before the launch
+    got = b.gather([e for e, _, _ in items], [s for _, s, _ in items], normalize=[k for _, _, k in items])
+    assert got.shape == (n_items, n) and got.dtype == torch.float32
+    got = got.cpu().numpy()
+    want = {}
+    for r, (e, s, k) in enumerate(items):
+        if (e, s, k) not in want:
+            want[e, s, k] = _ref_row(xs[e], s, n, k, b.peaks[e])
+        assert _same_bits(got[r], want[e, s, k]), (r, e, s, k)
+    assert len(want) == 3 * len(pairs)
+    zero_rows = [r for r, (e, s, k) in enumerate(items) if k == "window" and (e, s) in silent]
+    assert len(zero_rows) > 100 and (got[zero_rows].view(np.uint32) == 0).all()
+
+
 # ---- peaks ----------------------------------------------------------------------------------------------------------------------
 def _np_peaks(x, lengths):
     at = np.concatenate([[0], np.cumsum(lengths)])

@@ -307,6 +307,114 @@ def test_1100_interleaved_descriptors_in_one_launch_equal_each_alone(dev):
     assert (np.abs(batch[1][:len(y) - crop] - y[crop:]) <= do.stage_bound(A, nn)[crop:]).all() and not batch[1][len(y) - crop:].any()
 
 
+def _k0_path(desc, row_len):
+    """The branch of decode_resample_kernel a descriptor takes (csrc/ww_decode.hip), from the descriptor alone."""
+    off, n, ch, sr, fmt, crop = desc
+    if sr != 16000 and k0.in_lds(sr):
+        return f"resample_lds_kernel's ({sr})"
+    if fmt == nat.FMT_FLAC:
+        return "skipped FLAC"
+    if n == 0:
+        return "zero frames"
+    if sr != 16000:
+        return f"direct taps ({sr})"
+    if row_len == 16000 and ch == 1 and fmt == do.FMT_S16 and n <= 16000 and crop == 0 and off % 16 == 0:
+        return "16 k vector path"
+    return "16 k general loop"
+
+
+_GRID_KINDS = (48000, 44100, "16 k aligned", 11025, 8000, "flac", "16 k general", "empty")
+
+
+def _grid_pack(n_cu):
+    """2 x 8 x CUs + 77 tiny files in one pack: the rates, the undecoded FLAC descriptor and the empty files of the 1100-descriptor test,
+    keyed so that the interleave cannot alias decode_resample_kernel's grid g = 8 x CUs: descriptor i = q g + r is of kind
+    (r + q d) % 8 with d = 1 + (r // 8) % 7, so the next clip of a workgroup (i + g) is d kinds on -- never the same kind, and over r
+    every kind precedes every other.  16 kHz files come in two kinds: 16-byte aligned with crop 0 (the vector path at rows of 16000) and
+    at an odd sample with a crop (the general loop); "empty" is a 16 kHz file of no frames (and a few of resample_lds_kernel's files are empty)."""
+    g = 8 * n_cu
+    noise = np.random.default_rng(8).integers(-32768, 32768, size=40000, dtype=np.int64)
+    pack = k0.Pack()
+    off = pack.add_bytes(k0.to_bytes(noise, do.FMT_S16))
+    assert off % 16 == 0
+    for i in range(2 * g + 77):
+        q, r = divmod(i, g)
+        kind = _GRID_KINDS[(r + q * (1 + (r // 8) % 7)) % 8]
+        lds_empty = kind in (48000, 44100, 8000) and (r + 3 * q) % 50 == 7       # resample_lds_kernel's own empty files
+        n = 0 if kind == "empty" or lds_empty else 150 + (i * 37) % 500
+        start = (i * 64) % 30000                                  # a multiple of 8 samples: 16-byte aligned
+        if kind == "16 k aligned":
+            pack.desc(off + 2 * start, n, 1, 16000, do.FMT_S16, crop_start=0)
+        elif kind == "16 k general":
+            pack.desc(off + 2 * (start + 1), n, 1, 16000, do.FMT_S16, crop_start=(i % 3) * 5)
+        elif kind in ("flac", "empty"):
+            pack.desc(off + 2 * start, n, 1, 16000, nat.FMT_FLAC if kind == "flac" else do.FMT_S16, crop_start=0)
+        else:
+            pack.desc(off + 2 * (start + i % 2), n, 1, kind, do.FMT_S16, crop_start=(i % 3) * 5)
+    return pack, noise, off
+
+
+def _check_grid_paths(pack, n_cu, row_len):
+    """Consecutive clips of a decode_resample_kernel workgroup (c, then c + g) never take the same branch, and each of the kernel's own
+    branches is entered right after, and right before, each other one.  (Rows of 4000 have no vector path: there the two 16 kHz kinds
+    share the general loop.)  -> the path of every descriptor"""
+    g = 8 * n_cu
+    n_desc = len(pack.descs)
+    assert n_desc > 2 * g
+    paths = [_k0_path(d, row_len) for d in pack.descs]
+    pairs = {(paths[c], paths[c + g]) for c in range(n_desc - g)}
+    same = {a for a, b in pairs if a == b}
+    assert same <= (set() if row_len == 16000 else {"16 k general loop"}), same
+    own = ["16 k general loop", "skipped FLAC", "zero frames", "direct taps (11025)"] + (["16 k vector path"] if row_len == 16000 else [])
+    missing = [(a, b) for a in own for b in own if a != b and (a, b) not in pairs]
+    assert not missing, missing
+    lds = sorted({p for p in paths if p.startswith("resample_lds")})
+    assert len(lds) == 3 and all((a, b) in pairs and (b, a) in pairs for a in lds for b in own), "a skipped descriptor before and after each branch"
+    return paths
+
+
+@pytest.mark.parametrize("row_len", [4000, 16000])
+def test_descriptors_beyond_the_resident_grid_of_both_kernels(dev, row_len):
+    """test_1100_interleaved_descriptors...'s sibling for decode_resample_kernel, whose grid is 8 per CU: at 1100 descriptors its
+    workgroups take one clip each, and its red[], its early `continue`s and the vector path's own barriers are never handed from clip
+    to clip.  Here 2 x 8 x CUs + 77 descriptors (_grid_pack): every workgroup of decode_resample_kernel enters its second iteration and
+    77 their third (resample_lds_kernel, 2 per CU, takes eight or nine; its order is not controlled here).  Rows of 4000 as in the
+    sibling, and rows of 16000, without which the vector path of 16 kHz files cannot be taken.  Batch == launches of at most one clip
+    per CU (grid = n: no second iteration), bit for bit, for both `normalize` values; one row per path against the oracle."""
+    n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+    g = 8 * n_cu
+    pack, noise, off = _grid_pack(n_cu)
+    n_desc = len(pack.descs)
+    assert n_desc == 2 * g + 77
+    paths = _check_grid_paths(pack, n_cu, row_len)               # before any launch
+
+    def chunked(normalize):
+        parts = []
+        for c in range(0, n_desc, n_cu):
+            sub = k0.Pack()
+            sub.chunks, sub.size, sub.descs = pack.chunks, pack.size, pack.descs[c:c + n_cu]
+            parts.append(run_k0(dev, sub, normalize, row_len))
+        return np.concatenate(parts)
+
+    for normalize in (1, 0):
+        batch = run_k0(dev, pack, normalize, row_len)
+        assert _same(batch, chunked(normalize))
+        empty = np.array([d[4] == nat.FMT_FLAC or d[1] == 0 for d in pack.descs])
+        assert np.array_equal(empty, ~batch.any(axis=1))          # zero rows for skipped and zero-length files, over the 7.0 pre-fill
+        assert np.isfinite(batch).all() and np.count_nonzero(batch) > 100000
+    # one unnormalised row per path against the oracle, so that "equal" is not "equally wrong": each a second or third clip of its workgroup
+    for want in sorted(set(paths) - {"skipped FLAC", "zero frames"}):
+        i = next(i for i in range(g, n_desc) if paths[i] == want and pack.descs[i][1] > 0)
+        o, n, ch, sr, fmt, crop = pack.descs[i]
+        _, x32 = do.mono_f64(noise[(o - off) // 2:(o - off) // 2 + n], do.FMT_S16, 1)
+        if sr == 16000:                                          # no filter: the converted samples themselves
+            assert np.array_equal(batch[i][:n - crop], x32[crop:]) and not batch[i][n - crop:].any(), (want, i)
+            continue
+        t, up, down, hl = k0.taps(sr)
+        y, A, nn = do.resample_own_input(x32, t, up, down, hl)
+        assert (np.abs(batch[i][:len(y) - crop] - y[crop:]) <= do.stage_bound(A, nn)[crop:]).all() and not batch[i][len(y) - crop:].any(), (want, i)
+
+
 def test_normalise_takes_the_peak_of_the_whole_file(dev):
     """The peak outside the crop window; a crop whose valid part is shorter than the row; silent files on all three code paths (LDS form,
     general loop, vector path): NaN in the valid part -- the reference divides by max|x| = 0 -- and 0.0 in the padding."""

@@ -110,7 +110,9 @@ def test_logmel_frames_matches_oracle(dev, duration, mode):
 
 @pytest.mark.parametrize("mode", ["auto", "f32"])
 def test_logmel_frames_large_batch_matches_single_clips(dev, mode):
-    """More clips than CUs: the 4-wave form, workgroups looping over clips; every clip equals its batch-of-1 result bit for bit."""
+    """More clips than CUs: the 4-wave form; every clip equals its batch-of-1 result (the 8-wave form) bit for bit.  300 clips are fewer
+    than the float kernel's grid of 2 per CU on a 256-CU part, so no float workgroup takes a second clip here (only auto's
+    logmel64_kernel<., 64>, 1 per CU, may); the clip loop itself is entered in tests/test_gpu_logmel_carry.py."""
     n = 24000
     x = pkg.synth.make_clips(0, 300, n=n)
     x[::7] = _tones(n)[np.arange(len(x[::7])) % 5]                       # noise-free clips among them: auto mode redoes those

@@ -3,8 +3,11 @@
 Non-finite samples.  The reference makes an all-NaN image of such a clip (tests/test_host_logmel_nonfinite.py pins that on the oracle):
 `audio / np.max(np.abs(audio))` and `power_to_db(ref=np.max)` both spread the value over the whole clip.  Every instantiated log-mel
 kernel (4 and 8 waves, the 32- and the 64-frame tile, float32 / float64 / auto) must do the same, with or without the normalisation,
-and must leave every other clip of the batch exactly as it is in a batch without the value (logmel_cases.check_rows): the workgroups
-are persistent over clips, so the mel tile, the frame-mask words and red[] of one clip are the next clip's.
+and must leave every other clip of the batch exactly as it is in a batch without the value (logmel_cases.check_rows).  The workgroups
+are persistent over clips, so the mel tile, the frame-mask words and red[] of one clip are the next clip's -- but NOT at these batch
+sizes: with 300 clips on a 256-CU part every float workgroup (grids of 2 and 3 per CU) and logmel64_kernel<., 32> (2 per CU) take one
+clip each, and only logmel64_kernel<., 64> (1 per CU) sees a second clip, in 44 workgroups.  What these tests show is that a launch's
+rows do not disturb each other; the hand-over from clip to clip inside a workgroup is tests/test_gpu_logmel_carry.py's.
 
 Level.  The float kernel squares raw samples and applies 1 / peak^2 to the mel powers.  Every operation of both kernels commutes with
 a gain of 2^k while nothing overflows or goes subnormal, so for |k| <= 31 -- the largest power is at most (2^31 * 1024)^2 = 2^82, and a
@@ -30,7 +33,7 @@ pytestmark = pytest.mark.gpu
 MEL_TOL = 1e-4
 MATHS = ["f32", "f64", "auto"]
 # (n_samples, batch): 16000 is the 32-frame tile, everything else the 64-frame tile (T = 8, 47, 63); 24 clips run the 8-wave form
-# (at most one clip per CU), 300 the persistent 4-wave form
+# (at most one clip per CU), 300 the 4-wave form -- on a 256-CU part still one clip per workgroup (its grid is 2 or 3 per CU)
 FORMS = [(16000, 24), (16000, 300), (4000, 24), (24000, 24), (32000, 300)]
 LEVELS = {}
 
@@ -124,7 +127,8 @@ def test_nonfinite_clip_is_all_nan(dev, math, normalize, form):
 @pytest.mark.parametrize("math", MATHS)
 def test_short_rows_do_not_read_their_padding(dev, math, B):
     """Rows of 9000 valid samples as views into a wider buffer full of NaN: behind every row's end lies NaN, not the zeros the kernel
-    pads with.  Row stride 16000 (taken as it is), then 16001 from an odd offset (the wrapper copies the rows)."""
+    pads with.  Row stride 16000 (taken as it is), then 16001 from an odd offset (the wrapper copies the rows).  (One clip per float
+    workgroup at both batch sizes; test_gpu_logmel_carry.test_short_rows_in_a_looping_batch is this layout with a looping grid.)"""
     valid = 9000
     rows = np.stack([lc.noisy(50 + i % 16, valid) * np.float32(1.0 - 0.01 * (i // 16)) for i in range(B)])
     rows[1::3] = lc.tones(16000)[np.arange(len(rows[1::3])) % 5, :valid]

@@ -616,7 +616,9 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
             const uint32_t fm = uint32_t(bal) | uint32_t(bal >> 32);
             if (fm != 0u && lane == 0) __hip_atomic_fetch_or(flag + (clip_it & 1), fm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-        __syncthreads();   // the frame mask is complete (mel / red / frm are rewritten only behind the next clip's barriers)
+        // the frame mask is complete; every read of mel / red / frm for the dB pass is done.  red and frm are rewritten only behind the
+        // next clip's barriers; mel is NOT: the next clip's first round of frames writes it with no barrier in between
+        __syncthreads();
         if (mark) {
             const uint32_t fm = flag[clip_it & 1];                           // uniform
             if (fm != 0u) {
@@ -627,6 +629,7 @@ __global__ __launch_bounds__(WAVES * 64, (K1Layout<WAVES, FR>::kWavesPerSimd)) v
                     reinterpret_cast<uint32_t*>(o)[0] = kRedoMark;
                     reinterpret_cast<uint32_t*>(o)[1] = fm | 3u;
                 }
+                __syncthreads();   // mel is read above: no wave may start the next clip's frames (which rewrite it) before all are done
             }
         }
         }
